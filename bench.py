@@ -2,6 +2,7 @@
 """bench.py -- the contract benchmark: spin-updates/s of the checkerboard Gibbs sweep on an L x L Ising lattice.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--L 4096] [--sweeps-per-step 256] [--sweeps-per-launch 8]
+                    [--dump-outputs DIR]
 
 N = 1: BASELINE.json configs[1] (IsingModel2D 4096 x 4096 at T_c, periodic, physical bias mode) on one MI355X.
 N > 1 (one rank per GPU, started by torch.distributed.run -- by the caller, or by bench.py itself as a child process
@@ -11,6 +12,8 @@ configs[3] (ONE lattice cut into N slabs).  The run refuses to report a world di
 
 A step = `sweeps-per-step` full lattice sweeps (each sweep updates every spin once: colour 0, then colour 1).
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.
+`--dump-outputs DIR` writes the lattice the last timed step left behind to DIR/*.npy (see dump_outputs): the start state,
+seeds and sweep counters depend on the arguments alone, so two builds run with the same arguments can be compared file by file.
 """
 import argparse
 import json
@@ -127,6 +130,25 @@ def issue_roofline(entry, updates_per_launch, launch_seconds, what="spin update"
             "valu_wave_instructions_per_launch": insts, "clock_ghz_in_pmc_pass": entry["clock_ghz"],
             "cycles_per_wave_instruction_assumed": VALU_CYCLES_PER_WAVE_INSTRUCTION,
             "note": "SQ_INSTS_VALU and GRBM_GUI_ACTIVE from profiles/counters.json (rocprofv3 --pmc passes), launch time from this run"}
+
+
+DUMP_SPIN_BYTES = 32 << 20  # float32 spins written by --dump-outputs: every row up to 2896^2 sites, a row sample above
+
+
+def dump_outputs(out_dir, spins, sums=None, name="spins", budget=DUMP_SPIN_BYTES):
+    """--dump-outputs: what a caller of the timed path holds after its last step.
+      <name>.npy       float32 (k, cols): the +-1 spins of every row when they fit in `budget` bytes, else of k rows drawn
+                       once with seed 0 (the same rows for the same lattice shape, in ascending order)
+      <name>_rows.npy  float64 (k,): the indices of those rows
+      observables.npy  float64 [sum of spins, sum over bonds] as Lattice.observables() returns them (exact integers; only
+                       when `sums` is given)"""
+    rows, cols = spins.shape
+    k = max(1, min(rows, budget // (4 * cols)))
+    idx = np.arange(rows) if k == rows else np.sort(np.random.default_rng(0).choice(rows, k, replace=False))
+    np.save(os.path.join(out_dir, name + ".npy"), spins[idx].astype(np.float32))
+    np.save(os.path.join(out_dir, name + "_rows.npy"), idx.astype(np.float64))
+    if sums is not None:
+        np.save(os.path.join(out_dir, "observables.npy"), np.asarray(sums, dtype=np.float64))
 
 
 def time_lattice(hip, ctx, L, k, sweeps, reps=3, cols=None, counters=None, ckey=None, sweeps_per_launch=None):
@@ -443,6 +465,8 @@ def build_parser():
                          "instead of the default weak scaling (L x L per GPU)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the lattice after the last timed step to DIR/*.npy (float32 spins, float64 observables; <= 32 MiB)")
     return ap
 
 
@@ -480,6 +504,8 @@ def _free_port():
 
 def main():
     args = build_parser().parse_args()
+    if args.steps < 1:
+        raise SystemExit(f"bench.py: --steps must be >= 1, got {args.steps}")
     mode, what = launch_plan(args.gpus, os.environ, sys.argv[1:], _free_port)
     if mode == "error":
         raise SystemExit("bench.py: " + what)
@@ -489,6 +515,8 @@ def main():
         env = dict(os.environ, MASTER_ADDR="127.0.0.1")
         proc = subprocess.run(what, env=env)
         raise SystemExit(proc.returncode)
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)  # before the GPU is touched: a path that cannot be written ends the run here
 
     import torch
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -619,6 +647,10 @@ def main():
         s, b = lat.observables()
     else:
         s, b = slab.observables()
+    if args.dump_outputs:
+        # every rank its own slab (a share of the byte budget each); the observables are the whole lattice's, written once
+        dump_outputs(args.dump_outputs, lat.get_spins() if world == 1 else slab.local_spins(), (s, b) if rank == 0 else None,
+                     name="spins" if world == 1 else f"spins_rank{rank}", budget=DUMP_SPIN_BYTES // world)
 
     multi_extra = None
     if world > 1 and not args.no_extra and not args.strong:
