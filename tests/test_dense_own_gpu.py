@@ -304,3 +304,26 @@ def test_a_run_that_gives_up_half_way_is_redone_on_the_other_paths():
         for r in range(3):
             np.testing.assert_array_equal(out[r], ora.dense_sweep_philox(sts[r], J64, b, [1.0, 0.7, 1.4][r], 2, 1 + r, sweep0=0, replica=r))
         d.close()
+
+
+def test_a_replica_call_keeps_k2_own_off_after_a_single_chain_gave_up():
+    """A single chain's give-up is sticky: later calls skip k2_own.  A replica call in between (which k2_own then declines, the
+    replicas going one after the other through the other paths) must not switch it back on for the single chain."""
+    n = 2304
+    J, b, s0 = _system(n, 29, False)
+    J64 = J.astype(np.float64)
+    d = _dense(J, b, False)
+    d.set_state(s0)
+    with _env(TSU_K2_OWN_TEST_FAIL=0):
+        d.sweep(1.0, 1, seed=4, sweep0=0)  # k2_own gives up at its first superblock, k2_pipe redoes the call
+    want = ora.dense_sweep_philox(s0, J64, b, 1.0, 1, 4, sweep0=0)
+    np.testing.assert_array_equal(d.get_state(), want)
+    sts = np.array([np.random.default_rng(50 + r).integers(0, 2, size=n) for r in range(2)], dtype=np.int8)
+    out = d.sweep_replicas(sts, [1.0, 0.8], 2, [5, 6], [0, 3], replicas=[0, 1])
+    for r in range(2):
+        np.testing.assert_array_equal(out[r], ora.dense_sweep_philox(sts[r], J64, b, [1.0, 0.8][r], 2, 5 + r, sweep0=[0, 3][r], replica=r))
+    d.set_state(want)
+    d.sweep(0.9, 1, seed=4, sweep0=1)
+    np.testing.assert_array_equal(d.get_state(), ora.dense_sweep_philox(want, J64, b, 0.9, 1, 4, sweep0=1))
+    assert d.launch_counts()[0] == 0
+    d.close()

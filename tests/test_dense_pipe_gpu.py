@@ -1,13 +1,34 @@
 """K2 pipeline kernel (k2_pipe: streamers + solver teams, csrc/dense_coop.hip) against the oracle, bit for bit, at sizes
-around its superblock sizes (4096 / 8192): one and several superblocks, partial last superblock, width not a multiple of the
+around its superblock sizes (2048 / 4096): one and several superblocks, partial last superblock, width not a multiple of the
 vector width's strip, f32 / f64 couplings, a bias, and long calls in which the fields are handed from sweep to sweep (a
-single-superblock system once raced here: its rows are committed by all solver workgroups just before the next solve)."""
+single-superblock system once raced here: its rows are committed by all solver workgroups just before the next solve).
+k2_pipe serves 452 ... 2047 sites and is k2_own's fallback above: from 2048 sites the sweeps run with k2_own giving up at its
+first superblock (TSU_K2_OWN_TEST_FAIL=0), the route a call takes when k2_own's bounded waits expire."""
+import os
+
 import numpy as np
 import pytest
 
 from oracle import oracle as ora
 
 pytestmark = pytest.mark.gpu
+
+
+class _env:
+    def __init__(self, **kw):
+        self.kw = kw
+
+    def __enter__(self):
+        self.old = {k: os.environ.get(k) for k in self.kw}
+        for k, v in self.kw.items():
+            os.environ[k] = str(v)
+
+    def __exit__(self, *a):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
 
 
 def _system(n, seed, f64=False, bias=True):
@@ -27,7 +48,14 @@ def test_pipeline_sweeps_match_oracle(n, T, f64):
     J, b, s0 = _system(n, n, f64)
     d = _hip.DenseSystem(J, b, _hip.DTYPE_F64 if f64 else _hip.DTYPE_F32)
     d.set_state(s0)
-    d.sweep(T, 3, seed=7, sweep0=2)
+    if n < 2048:
+        d.sweep(T, 3, seed=7, sweep0=2)
+        assert d.launch_counts()[1] >= 1
+    else:
+        with _env(TSU_K2_OWN_TEST_FAIL=0):
+            d.sweep(T, 3, seed=7, sweep0=2)
+        own, pipe = d.launch_counts()
+        assert own == 0 and pipe >= 1
     want = ora.dense_sweep_philox(s0, np.asarray(J, dtype=np.float64), b, T, 3, 7, sweep0=2)
     np.testing.assert_array_equal(d.get_state(), want)
     d.close()
@@ -41,10 +69,13 @@ def test_pipeline_long_call_hands_fields_from_sweep_to_sweep(n):
     d.set_state(s0)
     want, done = s0, 0
     for k in (4, 20):
-        d.sweep(1.0, k, seed=1, sweep0=done)
+        with _env(TSU_K2_OWN_TEST_FAIL=0):
+            d.sweep(1.0, k, seed=1, sweep0=done)
         want = ora.dense_sweep_philox(want, J.astype(np.float64), None, 1.0, k, 1, sweep0=done)
         done += k
         np.testing.assert_array_equal(d.get_state(), want)
+    own, pipe = d.launch_counts()
+    assert own == 0 and pipe >= 1
     assert abs(d.energy() - ora.c_dense_energy(want.astype(np.int64), J.astype(np.float64))) < 1e-6 * n
     d.close()
 

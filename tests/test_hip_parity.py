@@ -391,8 +391,9 @@ def test_dense_sweep_matches_oracle(hip, n, dtype):
 
 @pytest.mark.parametrize("n,dtype,T,sym", [(4500, "f32", 1.0, True), (2051, "f64", 0.3, False), (6144, "f32", 0.2, True)])
 def test_dense_superblocks_match_oracle(hip, n, dtype, T, sym):
-    """Several superblocks of 2048 positions (fixed-point iteration, change lists, strip updates, grid barriers across
-    the XCDs): bit-exact against the oracle's sequential sweep; vector and scalar load paths, symmetric and not."""
+    """Several superblocks: bit-exact against the oracle's sequential sweep; vector and scalar load paths, symmetric and not.
+    4500 / 6144 sites run on k2_own (owner-computes, value-mask hand-offs between workgroups); 2051 (not a multiple of 4, which
+    k2_own and k2_pipe decline) on k2_coop (fixed-point iteration, change lists, strip updates, grid barriers across the XCDs)."""
     rng = np.random.default_rng(n)
     J = rng.standard_normal((n, n)) / np.sqrt(n)
     if sym:
@@ -410,6 +411,10 @@ def test_dense_superblocks_match_oracle(hip, n, dtype, T, sym):
     d.sweep(T, 2, seed=77, sweep0=8)
     want = ora.dense_sweep_philox(want, J, b, T, 2, 77, sweep0=8)
     np.testing.assert_array_equal(d.get_state(), want)
+    if n == 2051:
+        assert d.launch_counts() == (0, 0)
+    else:
+        assert d.launch_counts()[0] >= 1
     if n == 2051:  # many sweeps in one call: fields handed from sweep to sweep, recomputed every 64th
         d.set_state(st)
         d.sweep(T, 70, seed=78, sweep0=0)
@@ -502,8 +507,8 @@ def test_dense_sweep_replicas_match_oracle(hip, n):
 
 
 def test_dense_long_run_stays_on_the_oracle_chain(hip):
-    """Soak for the cooperative kernel's barrier / agent-scope data path: 200 sweeps of a 5000-site glass (two
-    superblocks, ~4000 grid barriers, fields handed on between sweeps) in ONE call stay bit-identical to the oracle."""
+    """Soak for k2_own's hand-offs between workgroups: 200 sweeps of a 5000-site glass (two superblocks, value masks published
+    and polled generation after generation, fields handed on between sweeps) in ONE call stay bit-identical to the oracle."""
     n, T = 5000, 0.7
     rng = np.random.default_rng(5)
     J = rng.standard_normal((n, n)).astype(np.float32).astype(np.float64) / np.sqrt(n)
@@ -512,6 +517,7 @@ def test_dense_long_run_stays_on_the_oracle_chain(hip):
     d = hip.DenseSystem(J, None, hip.DTYPE_F64)
     d.set_state(st)
     d.sweep(T, 200, seed=3, sweep0=0)
+    assert d.launch_counts()[0] >= 1
     np.testing.assert_array_equal(d.get_state(), ora.dense_sweep_philox(st, J, None, T, 200, 3, sweep0=0))
     d.close()
 

@@ -15,15 +15,9 @@ struct tsu_dense {
     double* field;
     int64_t* order;  // device copy of the visiting order (n_sweeps * n) or NULL
     double* uniforms;
-    size_t order_cap, uni_cap;
+    size_t order_cap, uni_cap;  // bytes allocated (so are all *_cap below: dense_grow)
     double* d_energy;
-    // superblock fixed-point path
-    int8_t* delta[2];   // ping-pong flip vectors of the current superblock
-    double* logit;      // T * logit(u) per site of the current superblock... stored as logit(u)
-    int* sb_sync;       // [0 .. SB_MAX_IT): changes per iteration, [SB_MAX_IT]: converged flag, per superblock
-    int8_t* backup;     // state at the start of the call (re-run on the exact path if a superblock did not converge)
-    int sb_cap;         // superblocks allocated in sb_sync
-    int sb_budget;      // iteration launches per superblock: slowest fixed point of the last call + 8 (16 .. SB_MAX_IT)
+    int8_t* backup;     // state at the start of a one-launch call (restored when a kernel gives up half way)
     // cooperative single-launch path (dense_coop.hip)
     double* co_logit;   // logit(u) per site for the current sweep
     double* co_corr;    // intra-superblock correction per site
@@ -51,7 +45,7 @@ struct tsu_dense {
     int8_t* h_stage;        // pinned host buffer (n bytes + 8): get_state / energy come back through it (a copy into the caller's
                             // pageable memory is staged by the runtime and costs ~10 us more)
     int rep_match;          // the resident state (tsu_dense_set_state) IS row rep_match - 1 of rep_prev: tsu_dense_energy takes its kept fields (0: no)
-    int co_disabled;    // cooperative launch unavailable or failed once: use the multi-launch path
+    int co_disabled;    // cooperative launch unavailable or failed once: natural-order calls skip the one-launch kernels
     unsigned long long* pp_masks;  // k2_pipe: flip-mask granules of the solver teams
     int pp_failed;      // k2_pipe ran and left the state half updated: the caller restores it, later calls skip the pipeline
     // k2_pipe hands the fields f = J s + b from call to call (a loop of one-sweep calls -- annealing, tempering -- would otherwise
@@ -62,7 +56,7 @@ struct tsu_dense {
     int pipe_streak;    // consecutive pipeline calls on this state: the second one starts to keep the fields
     // owner-computes kernel (dense_own.hip): value-mask granules of the running generation and of the superblocks' final values
     unsigned long long* own_gran;
-    size_t own_cap;     // 8-byte words allocated in own_gran
+    size_t own_cap;
     int own_failed;     // k2_own ran and gave up half way: the caller restores the state, later calls skip it
     uint64_t n_own, n_pipe;  // successful launches of k2_own / k2_pipe (tsu_dense_launch_counts)
 };
@@ -108,14 +102,43 @@ static __device__ __forceinline__ int dense_decide(double F, double lg, double T
     return xa > lg ? 1 : 0;
 }
 
-// cooperative single-launch sweep (dense_coop.hip): TSU_OK with *done = 1 when the call was carried out, *done = 0
-// when the path is unavailable or a superblock did not converge (state untouched or restored by the caller)
-int tsu_dense_pipe_run(tsu_dense* d, double T, const double* temps_dev, int n_total, int rec_from, int rec_every, int8_t* samples_dev,
-                       uint64_t seed, uint32_t sweep0, uint32_t replica, bool have_uni, int* done, const int64_t* order_dev = nullptr);
+// grow-only device buffer: reallocated (contents dropped) only when it holds fewer than `bytes`; no memset, no synchronisation
+template <typename T>
+static inline hipError_t dense_grow(T*& p, size_t& cap, size_t bytes) {
+    if (cap >= bytes) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+}
+
+// an integer switch from the environment (unset: dflt)
+static inline int dense_env(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// something other than a one-launch kernel's successful call writes (or is about to write) d->state: the fields kept from call to call
+// are no longer its fields, and the run of consecutive one-launch calls on it ends
+static inline void dense_forget_fields(tsu_dense* d) {
+    d->fields_valid = 0;
+    d->rep_match = 0;
+    d->pipe_streak = 0;
+}
+
+// The one-launch kernels for d->state (dense_coop.hip), in this order: k2_own; then, natural order only, k2_pipe; then, for a plain
+// sweep (plain: no recorded states, no schedule), k2_coop.  n_sweeps sweeps with the state recorded into samples_dev after rec_from,
+// rec_from + rec_every, ... of them; temps_dev: one temperature per sweep or nullptr; uniforms_dev: [n_sweeps][n] replayed uniforms or
+// nullptr; order_dev: [n_sweeps][n] visiting orders or nullptr.  TSU_OK with *done = 1 when one of them carried out the call,
+// *done = 0 when none did: the state is then the one at the start of the call.
+int tsu_dense_one_launch(tsu_dense* d, double T, const double* temps_dev, int n_sweeps, int rec_from, int rec_every, int8_t* samples_dev,
+                         uint64_t seed, uint32_t sweep0, uint32_t replica, const double* uniforms_dev, const int64_t* order_dev, bool plain,
+                         int* done);
 // owner-computes kernel (dense_own.hip): n_sweeps sweeps of R states ([R][n] at states_dev; R == 1: d->state) in one launch, natural
-// order or the caller's (order_dev: [n_sweeps][n]); *done as above
+// order or the caller's (order_dev: [n_sweeps][n]).  *done = 0: the kernel does not take this call (nothing was written) or it gave
+// up half way (d->own_failed set: the state must be restored)
 int tsu_dense_own_run(tsu_dense* d, int R, const OwnRep* reps, int8_t* states_dev, int n_sweeps, const double* uniforms_dev,
                       const int64_t* order_dev, const double* temps_dev, int8_t* samples_dev, int rec_from, int rec_every, bool fields_were_valid,
                       bool allow_persist, int* done);
-int tsu_dense_coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica,
-                         bool have_uni, int* done, const int64_t* order_dev = nullptr);

@@ -9,20 +9,17 @@
 //   * k2_small (n <= 192 fp32 J / 128 fp64 J): a whole call (or sample_boltzmann run, annealing schedule, tempering
 //     ladder) in one launch of a single wave, J in LDS;
 //   * k2_wg (n <= 528 / 448): one workgroup, a thread per site, J^T columns from L2;
-//   * larger: dense_coop.hip -- the whole call in one cooperative launch (superblock fixed point);
-//   * the same fixed point with one launch per iteration (k2_sb_iter / k2_sb_finish) when a cooperative launch is
-//     not available;
+//   * larger: the whole call in one launch of a co-resident grid (tsu_dense_one_launch: k2_own, k2_pipe, k2_coop);
 //   * k2_block: per sweep the field f = J s + b (k2_matvec), then the visiting order in blocks of 64 positions, one
 //     launch per block in which every workgroup gathers the 64 x 64 sub-block into LDS, a wave resolves the 64
 //     sites in order by jumping from flip to flip (ballot + ffs: a lane's pending decision only changes when an
 //     earlier site of the block actually flips), and the block's flips are added to the other fields through rows
-//     of J^T.  Serves custom visiting orders (np.random.permutation), tiny systems and the never-seen case of a
-//     superblock that did not converge.
+//     of J^T.  Serves what no one-launch kernel takes: small systems in a caller's order, systems above 65536 sites,
+//     and calls the one-launch kernels gave up on.
 //
 // Uniforms: replayed doubles from the host (bit-exact replay of np.random.rand) or Philox doubles keyed by
 // (site, sweep): a = W[2(i&1)] >> 5, b = W[2(i&1)+1] >> 6, u = (a 2^26 + b) / 2^53 with
 // W = Philox4x32-10(ctr = (i >> 1, 0, sweep, TAG_DENSE | replica << 8), key = seed).
-#include <algorithm>
 #include <vector>
 
 #include "dense.h"
@@ -320,27 +317,15 @@ __global__ __launch_bounds__(64) void k2_small_replicas(const TJ* __restrict__ J
 
 // largest n on the one-workgroup kernel: the measured crossover against the cooperative kernel
 // (tools/dense_mid_times.py): fp32 J ~600 sites, fp64 J ~470 against the barrier kernel; against the pipeline (which now starts
-// at n = 452 with a streamer grid sized to the system) fp32 ~530: n = 500 30 us here / 34 there, n = 576 41 / 36; TSU_K2_WG=n overrides (0: never)
+// at n = 452 with a streamer grid sized to the system) fp32 ~530: n = 500 30 us here / 34 there, n = 576 41 / 36
 static bool k2wg_takes(const tsu_dense* d) {
-    static int use_wg = -2;
-    if (use_wg == -2) {
-        const char* e = getenv("TSU_K2_WG");
-        use_wg = e ? atoi(e) : -1;
-        if (use_wg > 1024) use_wg = 1024;
-    }
-    return d->n <= (use_wg >= 0 ? use_wg : (d->dtype == TSU_DTYPE_F64 ? 448 : 528));
+    return d->n <= (d->dtype == TSU_DTYPE_F64 ? 448 : 528);
 }
 
-// slots per lane the one-wave kernels need for this system, 0 if it does not fit one CU's LDS (TSU_K2_WAVE=0: at most 1)
+// slots per lane the one-wave kernels need for this system, 0 if it does not fit one CU's LDS
 static int k2w_slots(const tsu_dense* d) {
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("TSU_K2_WAVE");
-        enabled = e ? atoi(e) : 1;
-    }
     const int m = (d->n + 63) / 64;
-    const int cap = !enabled ? 1 : (d->dtype == TSU_DTYPE_F64 ? 2 : K2W_MAX_SLOTS);
-    return m <= cap ? m : 0;
+    return m <= (d->dtype == TSU_DTYPE_F64 ? 2 : K2W_MAX_SLOTS) ? m : 0;
 }
 
 static size_t k2w_lds_bytes(const tsu_dense* d, int m) {
@@ -595,166 +580,6 @@ __global__ __launch_bounds__(1024) void k2_energy(const double* __restrict__ f, 
     }
 }
 
-// ================================================================== superblock fixed-point resolve
-// The sequential sweep is the unique solution of a triangular system: delta_i = dec_i(f_i + sum_{j<i} J_ij delta_j).
-// For a superblock of S consecutive positions that system is solved by fixed-point iteration with ALL sites of the
-// block updated in parallel: iteration m is one row-parallel triangular matvec over the S x S sub-block (which
-// stays in L2) plus one decision per site.  Site i is exact from iteration i on, so the iteration reaches the
-// sequential result; in practice the intra-block corrections are small against the decision gaps and it converges
-// in about ten iterations.  A launch finds "no site changed in the previous iteration" and returns at once, so a
-// fixed launch budget costs little; if the budget is exhausted without convergence the whole call is re-run on the
-// block-by-block path (k2_block) from a backup of the state.  Natural visiting order only.
-#define SB_MAX_IT 32  // slots per superblock; the launch budget adapts below this
-
-template <typename TJ>
-__global__ __launch_bounds__(256) void k2_sb_iter(const TJ* __restrict__ J, const int8_t* __restrict__ s,
-                                                 const double* __restrict__ f, const double* __restrict__ uniforms,
-                                                 const int8_t* __restrict__ din, int8_t* __restrict__ dout,
-                                                 double* __restrict__ logit, int* __restrict__ sync, int m, int n, int p0,
-                                                 int cnt, double T, uint32_t sweep, uint32_t tag, uint32_t k0, uint32_t k1) {
-    if (m > 0 && sync[m - 1] == 0) return;  // the previous iteration changed nothing: delta is the fixed point
-    const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    if (wave >= cnt) return;
-    const int site = p0 + wave;
-    double c = 0.0;
-    if (m > 0) {  // iteration 0 starts from delta = 0
-        const TJ* row = J + (size_t)site * n + p0;
-        for (int j = lane; j < wave; j += 64) {
-            const int dj = din[j];
-            if (dj) c += (double)dj * (double)row[j];
-        }
-        for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    }
-    if (lane == 0) {
-        double lg;
-        double u = 0.0;
-        if (m == 0) {
-            u = uniforms ? uniforms[site] : dense_uniform((uint32_t)site, sweep, tag, k0, k1);
-            lg = log(u) - log1p(-u);
-            logit[wave] = lg;
-        } else {
-            lg = logit[wave];
-        }
-        const double F = f[site] + c;
-        const double xa = F * (1.0 / T);
-        int cand;
-        if (fabs(fabs(xa) - 20.0) < 1e-9 || fabs(xa - lg) <= 1e-9 * (1.0 + fabs(lg))) {
-            if (m > 0) u = uniforms ? uniforms[site] : dense_uniform((uint32_t)site, sweep, tag, k0, k1);
-            cand = (u < sigmoid_clamped(F / T)) ? 1 : 0;  // the reference's own expression decides close calls
-        } else if (xa > 20.0) cand = 1;
-        else if (xa < -20.0) cand = 0;
-        else cand = xa > lg ? 1 : 0;
-        const int8_t dn = (int8_t)(cand - (int)s[site]);
-        const int8_t dp = m > 0 ? din[wave] : (int8_t)0;
-        dout[wave] = dn;
-        if (dn != dp) atomicAdd(&sync[m], 1);
-    }
-}
-
-// commit the superblock (new bits into the next-state array, convergence flag) and add its flips to the fields of
-// every later site: one wave per later row, reading the S contiguous entries J[row][p0 .. p0+cnt)
-template <typename TJ>
-__global__ __launch_bounds__(256) void k2_sb_finish(const TJ* __restrict__ J, const int8_t* __restrict__ s,
-                                                   int8_t* __restrict__ s_new, double* __restrict__ f,
-                                                   const int8_t* __restrict__ d0, const int8_t* __restrict__ d1,
-                                                   int* __restrict__ sync, int n, int p0, int cnt, int budget) {
-    const int gw = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
-    // the fixed point sits in the buffer iteration mc wrote, mc = first iteration that changed nothing (later launches
-    // returned without writing); without convergence take the last buffer written (the host re-runs the call anyway)
-    int mc = budget - 1;
-    for (int m = budget - 1; m >= 0; --m)
-        if (sync[m] == 0) mc = m;
-    const int8_t* __restrict__ dfinal = (mc & 1) ? d1 : d0;
-    if (blockIdx.x == 0) {
-        for (int i = threadIdx.x; i < cnt; i += blockDim.x) s_new[p0 + i] = (int8_t)(s[p0 + i] + dfinal[i]);
-        if (threadIdx.x == 0) {
-            int ok = 0;
-            for (int m = 0; m < budget; ++m) ok |= (sync[m] == 0);
-            sync[SB_MAX_IT] = ok;
-        }
-    }
-    const int row = p0 + cnt + gw;
-    if (row >= n) return;
-    const TJ* jr = J + (size_t)row * n + p0;
-    double c = 0.0;
-    for (int j = lane; j < cnt; j += 64) {
-        const int dj = dfinal[j];
-        if (dj) c += (double)dj * (double)jr[j];
-    }
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
-    if (lane == 0) f[row] += c;
-}
-
-template <typename TJ>
-static int dense_sweep_superblocks(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica,
-                                   bool have_uni, int* converged) {
-    if (d->sb_budget < 16) d->sb_budget = 20;
-    const int budget = d->sb_budget;
-    tsu_ctx* ctx = d->ctx;
-    const TJ* J = (const TJ*)d->J;
-    const int n = d->n;
-    const uint32_t tag = TSU_TAG_DENSE | (replica << 8);
-    const int nsb = (n + SB_SIZE - 1) / SB_SIZE;
-    const size_t sync_ints = (size_t)nsb * n_sweeps * (SB_MAX_IT + 1);
-    if (!d->delta[0]) {
-        TSU_HIP_TRY(ctx, hipMalloc(&d->delta[0], SB_SIZE));
-        TSU_HIP_TRY(ctx, hipMalloc(&d->delta[1], SB_SIZE));
-        TSU_HIP_TRY(ctx, hipMalloc(&d->logit, SB_SIZE * sizeof(double)));
-    }
-    if ((size_t)d->sb_cap < sync_ints) {
-        if (d->sb_sync) (void)hipFree(d->sb_sync);
-        d->sb_sync = nullptr;
-        d->sb_cap = 0;
-        TSU_HIP_TRY(ctx, hipMalloc(&d->sb_sync, sync_ints * sizeof(int)));
-        d->sb_cap = (int)sync_ints;
-    }
-    TSU_HIP_TRY(ctx, hipMemsetAsync(d->sb_sync, 0, sync_ints * sizeof(int), ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(d->backup, d->state, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
-    const unsigned mv_grid = (unsigned)(((size_t)n * 64 + 255) / 256);
-    int* sync = d->sb_sync;
-    for (int s = 0; s < n_sweeps; ++s) {
-        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state2, d->state, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
-        k2_matvec<TJ><<<mv_grid, 256, 0, ctx->stream>>>(J, d->state, d->bias, d->field, n);
-        const double* uni = have_uni ? d->uniforms + (size_t)s * n : nullptr;
-        for (int p0 = 0; p0 < n; p0 += SB_SIZE, sync += SB_MAX_IT + 1) {
-            const int cnt = n - p0 < SB_SIZE ? n - p0 : SB_SIZE;
-            const unsigned it_grid = (unsigned)((cnt * 64 + 255) / 256);
-            for (int m = 0; m < budget; ++m)
-                k2_sb_iter<TJ><<<it_grid, 256, 0, ctx->stream>>>(J, d->state, d->field, uni, d->delta[(m + 1) & 1], d->delta[m & 1],
-                                                                 d->logit, sync, m, n, p0, cnt, T, sweep0 + (uint32_t)s, tag,
-                                                                 (uint32_t)seed, (uint32_t)(seed >> 32));
-            const int later = n - (p0 + cnt);
-            const unsigned fin_grid = (unsigned)(((size_t)(later > 0 ? later : 1) * 64 + 255) / 256);
-            k2_sb_finish<TJ><<<fin_grid, 256, 0, ctx->stream>>>(J, d->state, d->state2, d->field, d->delta[0], d->delta[1], sync, n, p0,
-                                                               cnt, budget);
-        }
-        int8_t* t = d->state;
-        d->state = d->state2;
-        d->state2 = t;
-    }
-    TSU_HIP_TRY(ctx, hipGetLastError());
-    // one synchronisation per call: did every superblock reach its fixed point within the launch budget?
-    std::vector<int> h(sync_ints);
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(h.data(), d->sb_sync, sync_ints * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *converged = 1;
-    int worst = 0;
-    for (size_t b = 0; b < (size_t)nsb * n_sweeps; ++b) {
-        if (!h[b * (SB_MAX_IT + 1) + SB_MAX_IT]) *converged = 0;
-        int mc = budget;
-        for (int m = budget - 1; m >= 0; --m)
-            if (h[b * (SB_MAX_IT + 1) + m] == 0) mc = m;
-        if (mc > worst) worst = mc;
-    }
-    // adapt the launch budget to this system (temperature, coupling strength): slowest fixed point + margin
-    // (an unused launch exits at once and costs ~3 us; a failed attempt costs the whole call again)
-    d->sb_budget = *converged ? (worst + 8 < 16 ? 16 : (worst + 8 > SB_MAX_IT ? SB_MAX_IT : worst + 8)) : SB_MAX_IT;
-    if (getenv("TSU_K2_VERBOSE"))
-        fprintf(stderr, "[tsu] dense superblocks: n=%d, %d superblocks x %d sweeps, slowest fixed point after %d iterations (budget %d, next %d)\n",
-                n, nsb, n_sweeps, worst, budget, d->sb_budget);
-    return TSU_OK;
-}
-
 template <typename TJ>
 static int dense_sweep_impl(tsu_dense* d, double T, int n_sweeps, bool have_order, uint64_t seed, uint32_t sweep0,
                             uint32_t replica, bool have_uni) {
@@ -867,10 +692,6 @@ int tsu_dense_destroy(tsu_dense* d) {
     if (d->order) (void)hipFree(d->order);
     if (d->uniforms) (void)hipFree(d->uniforms);
     if (d->d_energy) (void)hipFree(d->d_energy);
-    if (d->delta[0]) (void)hipFree(d->delta[0]);
-    if (d->delta[1]) (void)hipFree(d->delta[1]);
-    if (d->logit) (void)hipFree(d->logit);
-    if (d->sb_sync) (void)hipFree(d->sb_sync);
     if (d->backup) (void)hipFree(d->backup);
     if (d->samples) (void)hipFree(d->samples);
     if (d->temps) (void)hipFree(d->temps);
@@ -924,11 +745,9 @@ int tsu_dense_set_state(tsu_dense* d, const int8_t* bits_host) {
     TSU_REQUIRE(d->ctx, dense_bits01(bits_host, (size_t)d->n), "dense_set_state: state must be 0/1");
     TSU_HIP_TRY(d->ctx, hipMemcpyAsync(d->state, bits_host, (size_t)d->n, hipMemcpyHostToDevice, d->ctx->stream));
     TSU_HIP_TRY(d->ctx, hipStreamSynchronize(d->ctx->stream));
-    d->fields_valid = 0;  // the pipeline's kept fields belong to the old state
-    d->pipe_streak = 0;
+    dense_forget_fields(d);  // the kept fields belong to the old state ...
     // ... but the state may be one the last replica call returned (a tempering loop asks for every replica's energy between its
     // sweeps, gibbs.py:303-323): its fields are still there
-    d->rep_match = 0;
     for (int p = 0; p < d->rep_prev_n && !d->rep_match; ++p)
         if (memcmp(bits_host, d->rep_prev + (size_t)p * d->n, (size_t)d->n) == 0) d->rep_match = p + 1;
     return TSU_OK;
@@ -945,134 +764,100 @@ int tsu_dense_get_state(tsu_dense* d, int8_t* bits_host) {
     return TSU_OK;
 }
 
-int tsu_dense_sweep(tsu_dense* d, double T, int n_sweeps, const int64_t* order, uint64_t seed, uint32_t sweep0,
-                    uint32_t replica, const double* replay_uniforms) {
-    TSU_ENTER(d ? d->ctx : nullptr);
-    if (!d) return TSU_E_INVALID;
+// -1, or the first of `rows` visiting orders that is not a permutation of 0..n-1.  Every sweep must visit every site exactly once
+// (np.random.permutation, gibbs.py:157): the sweep reads the frozen current state for "old" bits, which is only right for a site's
+// first visit
+static int dense_bad_order_row(const int64_t* order, int rows, int n) {
+    std::vector<int> seen((size_t)n, -1);  // the row that saw the site last: one pass, no clearing per row
+    for (int sw = 0; sw < rows; ++sw) {
+        const int64_t* row = order + (size_t)sw * n;
+        for (int i = 0; i < n; ++i) {
+            const long long v = row[i];
+            if (v < 0 || v >= n || seen[(size_t)v] == sw) return sw;
+            seen[(size_t)v] = sw;
+        }
+    }
+    return -1;
+}
+
+// the inputs of `rows` sweeps into the handle's buffers, asynchronously (the caller's host arrays must outlive the copies): its visiting
+// orders (checked to be permutations unless `checked`), replayed uniforms and an annealing schedule, each where given
+static int dense_upload_inputs(tsu_dense* d, int rows, const int64_t* order, bool checked, const double* uniforms, const double* temps) {
+    tsu_ctx* ctx = d->ctx;
+    const size_t cnt = (size_t)rows * d->n;
+    if (order) {
+        TSU_HIP_TRY(ctx, dense_grow(d->order, d->order_cap, cnt * 8));
+        // (the upload runs while the host checks the rows)
+        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->order, order, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+        const int bad = checked ? -1 : dense_bad_order_row(order, rows, d->n);
+        if (bad >= 0) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return tsu_fail(ctx, TSU_E_INVALID, "dense_sweep: order row %d is not a permutation of 0..%d", bad, d->n - 1);
+        }
+    }
+    if (uniforms) {
+        TSU_HIP_TRY(ctx, dense_grow(d->uniforms, d->uni_cap, cnt * 8));
+        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->uniforms, uniforms, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (temps) {
+        TSU_HIP_TRY(ctx, dense_grow(d->temps, d->temps_cap, (size_t)rows * 8));
+        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->temps, temps, (size_t)rows * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    return TSU_OK;
+}
+
+// tsu_dense_sweep; checked: the caller has checked the visiting orders already
+static int dense_sweep(tsu_dense* d, double T, int n_sweeps, const int64_t* order, uint64_t seed, uint32_t sweep0, uint32_t replica,
+                       const double* replay_uniforms, bool checked) {
     tsu_ctx* ctx = d->ctx;
     TSU_REQUIRE(ctx, T > 0.0, "Temperature must be positive");
     TSU_REQUIRE(ctx, n_sweeps >= 0, "dense_sweep: n_sweeps must be >= 0");
     if (n_sweeps == 0) return TSU_OK;
-    size_t cnt = (size_t)n_sweeps * d->n;
-    if (order) {
-        if (d->order_cap < cnt) {
-            if (d->order) (void)hipFree(d->order);
-            d->order = nullptr;
-            d->order_cap = 0;
-            TSU_HIP_TRY(ctx, hipMalloc(&d->order, cnt * 8));
-            d->order_cap = cnt;
-        }
-        // (the upload runs while the host checks the rows; nothing reads the device copy before the synchronisation below)
-        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->order, order, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-        // every sweep must visit every site exactly once (np.random.permutation, gibbs.py:157): the sweep reads the
-        // frozen current state for "old" bits, which is only right for a site's first visit
-        std::vector<int> seen((size_t)d->n, -1);  // the row that saw the site last: one pass, no clearing per row
-        bool ok = true;
-        int bad_row = -1;
-        for (int sw = 0; sw < n_sweeps && ok; ++sw) {
-            const int64_t* row = order + (size_t)sw * d->n;
-            for (int i = 0; i < d->n; ++i) {
-                const long long v = row[i];
-                if (v < 0 || v >= d->n || seen[(size_t)v] == sw) {
-                    ok = false;
-                    bad_row = sw;
-                    break;
-                }
-                seen[(size_t)v] = sw;
-            }
-        }
-        if (!ok) {
-            (void)hipStreamSynchronize(ctx->stream);
-            return tsu_fail(ctx, TSU_E_INVALID, "dense_sweep: order row %d is not a permutation of 0..%d", bad_row, d->n - 1);
-        }
-    }
-    if (replay_uniforms) {
-        if (d->uni_cap < cnt) {
-            if (d->uniforms) (void)hipFree(d->uniforms);
-            d->uniforms = nullptr;
-            d->uni_cap = 0;
-            TSU_HIP_TRY(ctx, hipMalloc(&d->uniforms, cnt * 8));
-            d->uni_cap = cnt;
-        }
-        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->uniforms, replay_uniforms, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-    }
+    const int rc = dense_upload_inputs(d, n_sweeps, order, checked, replay_uniforms, nullptr);
+    if (rc != TSU_OK) return rc;
     if (order || replay_uniforms) TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // host buffers are the caller's
+    const double* uni = replay_uniforms ? d->uniforms : nullptr;
+    const uint32_t tag = TSU_TAG_DENSE | (replica << 8);
     if (!order) {
         // systems of at most 192 (fp32) / 128 (fp64) sites: all sweeps of the call in one launch of a single wave
         const int wave_m = k2w_slots(d);
         if (wave_m) {
-            TSU_HIP_TRY(ctx, k2w_launch(d, wave_m, ctx->stream, replay_uniforms ? d->uniforms : nullptr, nullptr, T, nullptr, n_sweeps, 1, 0, sweep0,
-                                        TSU_TAG_DENSE | (replica << 8), (uint32_t)seed, (uint32_t)(seed >> 32)));
+            TSU_HIP_TRY(ctx, k2w_launch(d, wave_m, ctx->stream, uni, nullptr, T, nullptr, n_sweeps, 1, 0, sweep0, tag, (uint32_t)seed,
+                                        (uint32_t)(seed >> 32)));
+            return TSU_OK;
+        }
+        if (k2wg_takes(d)) {
+            // mid-size systems: one workgroup, thread per site, all sweeps of the call in one launch
+            static const bool verbose_wg = dense_env("TSU_K2_VERBOSE", 0) != 0;
+            TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, uni, nullptr, T, nullptr, n_sweeps, 1, 0, sweep0, tag, (uint32_t)seed, (uint32_t)(seed >> 32),
+                                         verbose_wg ? (unsigned*)d->d_energy : nullptr));
+            if (verbose_wg) {
+                unsigned w = 0;
+                TSU_HIP_TRY(ctx, hipMemcpyAsync(&w, d->d_energy, 4, hipMemcpyDeviceToHost, ctx->stream));
+                TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                fprintf(stderr, "[tsu] k2_wg n=%d: %d sweeps, slowest fixed point %u iterations\n", d->n, n_sweeps, w);
+            }
             return TSU_OK;
         }
     }
-    if (!order && k2wg_takes(d)) {
-        // mid-size systems: one workgroup, thread per site, all sweeps of the call in one launch
-        static const bool verbose_wg = getenv("TSU_K2_VERBOSE") != nullptr;
-        TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, replay_uniforms ? d->uniforms : nullptr, nullptr, T, nullptr, n_sweeps, 1, 0, sweep0,
-                                     TSU_TAG_DENSE | (replica << 8), (uint32_t)seed, (uint32_t)(seed >> 32),
-                                     verbose_wg ? (unsigned*)d->d_energy : nullptr));
-        if (verbose_wg) {
-            unsigned w = 0;
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(&w, d->d_energy, 4, hipMemcpyDeviceToHost, ctx->stream));
-            TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            fprintf(stderr, "[tsu] k2_wg n=%d: %d sweeps, slowest fixed point %u iterations\n", d->n, n_sweeps, w);
-        }
-        return TSU_OK;
-    }
-    if (order && d->n >= 2 * DB) {
-        // a caller's visiting order (update_order="random"): the owner-computes kernel follows it in one launch (dense_own.hip);
-        // it declines small systems and reports a failed run with done = 0 -- then the block-by-block path below takes the call
-        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->backup, d->state, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
+    // larger systems, and a caller's order from 128 sites: the whole call in one launch (tsu_dense_one_launch); the block-by-block
+    // path takes what none of those kernels does
+    if (d->n >= 2 * DB) {
         int done = 0;
-        const int rc = tsu_dense_coop_sweep(d, T, n_sweeps, seed, sweep0, replica, replay_uniforms != nullptr, &done, d->order);
-        if (rc != TSU_OK) return rc;
-        if (done) return TSU_OK;
+        const int rc1 = tsu_dense_one_launch(d, T, nullptr, n_sweeps, 0, 1, nullptr, seed, sweep0, replica, uni, order ? d->order : nullptr, true, &done);
+        if (rc1 != TSU_OK || done) return rc1;
+    } else {
+        dense_forget_fields(d);
     }
-    static int use_sb = -1, use_coop = -1;
-    if (use_sb < 0) {
-        const char* e = getenv("TSU_K2_SUPERBLOCK");
-        use_sb = e ? atoi(e) : 1;
-        e = getenv("TSU_K2_COOP");
-        use_coop = e ? atoi(e) : 1;
-    }
-    // natural order: the whole call in one cooperative launch; if that is unavailable, the same fixed point with one
-    // launch per iteration; the block-by-block path serves custom orders, tiny systems and a superblock that did not
-    // converge within its iteration slots
-    if (!(use_coop && !d->co_disabled && !order && d->n >= 2 * DB)) {  // another path writes the state: the pipeline's kept fields go stale
-        d->fields_valid = 0;
-        d->rep_match = 0;
-        d->pipe_streak = 0;
-    }
-    if (use_coop && !d->co_disabled && !order && d->n >= 2 * DB) {
-        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->backup, d->state, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
-        int done = 0;
-        int rc = tsu_dense_coop_sweep(d, T, n_sweeps, seed, sweep0, replica, replay_uniforms != nullptr, &done);
-        if (rc != TSU_OK) return rc;
-        if (done) return TSU_OK;
-        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (use_sb && !order && d->n >= 2 * DB) {
-        int ok = 0;
-        int rc = d->dtype == TSU_DTYPE_F64
-                     ? dense_sweep_superblocks<double>(d, T, n_sweeps, seed, sweep0, replica, replay_uniforms != nullptr, &ok)
-                     : dense_sweep_superblocks<float>(d, T, n_sweeps, seed, sweep0, replica, replay_uniforms != nullptr, &ok);
-        if (rc != TSU_OK) return rc;
-        if (!ok) {
-            // a superblock ran out of iteration launches: restore the state and retry once with the full budget
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
-            rc = d->dtype == TSU_DTYPE_F64
-                     ? dense_sweep_superblocks<double>(d, T, n_sweeps, seed, sweep0, replica, replay_uniforms != nullptr, &ok)
-                     : dense_sweep_superblocks<float>(d, T, n_sweeps, seed, sweep0, replica, replay_uniforms != nullptr, &ok);
-            if (rc != TSU_OK) return rc;
-        }
-        if (ok) return TSU_OK;
-        // still not converged within SB_MAX_IT iterations: redo the call on the exact block-by-block path
-        TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (d->dtype == TSU_DTYPE_F64)
-        return dense_sweep_impl<double>(d, T, n_sweeps, order != nullptr, seed, sweep0, replica, replay_uniforms != nullptr);
-    return dense_sweep_impl<float>(d, T, n_sweeps, order != nullptr, seed, sweep0, replica, replay_uniforms != nullptr);
+    if (d->dtype == TSU_DTYPE_F64) return dense_sweep_impl<double>(d, T, n_sweeps, order != nullptr, seed, sweep0, replica, uni != nullptr);
+    return dense_sweep_impl<float>(d, T, n_sweeps, order != nullptr, seed, sweep0, replica, uni != nullptr);
+}
+
+int tsu_dense_sweep(tsu_dense* d, double T, int n_sweeps, const int64_t* order, uint64_t seed, uint32_t sweep0,
+                    uint32_t replica, const double* replay_uniforms) {
+    TSU_ENTER(d ? d->ctx : nullptr);
+    if (!d) return TSU_E_INVALID;
+    return dense_sweep(d, T, n_sweeps, order, seed, sweep0, replica, replay_uniforms, false);
 }
 
 // shared by tsu_dense_sample (one temperature) and tsu_dense_anneal (temps: one temperature per sweep, host array)
@@ -1086,119 +871,43 @@ static int dense_run(tsu_dense* d, double T, const double* temps, int n_burnin, 
     TSU_REQUIRE(ctx, total <= (1ll << 30) && (uint64_t)sweep0 + (uint64_t)total <= (1ull << 32), "dense_sample: sweep counter overflow");
     const int n = d->n;
     const size_t out_bytes = (size_t)n_samples * n;
-    if (d->samples_cap < out_bytes) {
-        if (d->samples) (void)hipFree(d->samples);
-        d->samples = nullptr;
-        d->samples_cap = 0;
-        TSU_HIP_TRY(ctx, hipMalloc(&d->samples, out_bytes));
-        d->samples_cap = out_bytes;
-    }
+    TSU_HIP_TRY(ctx, dense_grow(d->samples, d->samples_cap, out_bytes));
+    const uint32_t tag = TSU_TAG_DENSE | (replica << 8);
     const int wave_m = order ? 0 : k2w_slots(d);
-    const bool wg = !order && !wave_m && k2wg_takes(d);
-    if (wave_m || wg) {
-        const double* temps_dev = nullptr;
-        if (temps && total > 0) {
-            if (d->temps_cap < (size_t)total) {
-                if (d->temps) (void)hipFree(d->temps);
-                d->temps = nullptr;
-                d->temps_cap = 0;
-                TSU_HIP_TRY(ctx, hipMalloc(&d->temps, (size_t)total * 8));
-                d->temps_cap = (size_t)total;
-            }
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(d->temps, temps, (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
-            temps_dev = d->temps;
-        }
-        const size_t cnt = (size_t)total * n;
-        if (replay_uniforms && cnt) {
-            if (d->uni_cap < cnt) {
-                if (d->uniforms) (void)hipFree(d->uniforms);
-                d->uniforms = nullptr;
-                d->uni_cap = 0;
-                TSU_HIP_TRY(ctx, hipMalloc(&d->uniforms, cnt * 8));
-                d->uni_cap = cnt;
-            }
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(d->uniforms, replay_uniforms, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
-        }
-        const uint32_t tag = TSU_TAG_DENSE | (replica << 8);
-        if (total > 0 && wave_m)
-            TSU_HIP_TRY(ctx, k2w_launch(d, wave_m, ctx->stream, replay_uniforms ? d->uniforms : nullptr, d->samples, T, temps_dev, n_burnin, n_sweeps,
-                                        n_samples, sweep0, tag, (uint32_t)seed, (uint32_t)(seed >> 32)));
-        else if (total > 0)
-            TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, replay_uniforms ? d->uniforms : nullptr, d->samples, T, temps_dev, n_burnin, n_sweeps,
-                                         n_samples, sweep0, tag, (uint32_t)seed, (uint32_t)(seed >> 32), nullptr));
-    } else {
-        // larger systems in natural order: the whole run in ONE launch of the pipeline kernel (it records the states itself and takes
-        // a temperature per sweep) -- a loop of calls costs ~60 us per call beside sweeps of 40-100 us at n = 1000-4000
-        static int one_launch = -1;
-        if (one_launch < 0) {
-            const char* e = getenv("TSU_K2_RUN_ONE_LAUNCH");
-            one_launch = e ? atoi(e) : 1;
-        }
-        const size_t ucnt = (size_t)total * n;
-        if (one_launch && total > 0 && (order || !d->co_disabled) && n >= 2 * DB && (!replay_uniforms || ucnt * 8 <= ((size_t)1 << 29)) &&
-            (!order || ucnt * 8 <= ((size_t)1 << 29))) {
-            const double* temps_dev = nullptr;
-            if (temps) {  // (a schedule: n_burnin == 0, n_sweeps == 1, one temperature per recorded state)
-                if (d->temps_cap < (size_t)total) {
-                    if (d->temps) (void)hipFree(d->temps);
-                    d->temps = nullptr;
-                    d->temps_cap = 0;
-                    TSU_HIP_TRY(ctx, hipMalloc(&d->temps, (size_t)total * 8));
-                    d->temps_cap = (size_t)total;
-                }
-                TSU_HIP_TRY(ctx, hipMemcpyAsync(d->temps, temps, (size_t)total * 8, hipMemcpyHostToDevice, ctx->stream));
-                temps_dev = d->temps;
-            }
-            if (replay_uniforms) {
-                if (d->uni_cap < ucnt) {
-                    if (d->uniforms) (void)hipFree(d->uniforms);
-                    d->uniforms = nullptr;
-                    d->uni_cap = 0;
-                    TSU_HIP_TRY(ctx, hipMalloc(&d->uniforms, ucnt * 8));
-                    d->uni_cap = ucnt;
-                }
-                TSU_HIP_TRY(ctx, hipMemcpyAsync(d->uniforms, replay_uniforms, ucnt * 8, hipMemcpyHostToDevice, ctx->stream));
-            }
-            if (order) {  // (validated as permutations by tsu_dense_sweep's check, repeated here for the one-launch path)
-                std::vector<char> seen((size_t)n);
-                for (long long sw = 0; sw < total; ++sw) {
-                    std::fill(seen.begin(), seen.end(), 0);
-                    for (int i = 0; i < n; ++i) {
-                        const long long v = order[(size_t)sw * n + i];
-                        TSU_REQUIRE(ctx, v >= 0 && v < n && !seen[(size_t)v], "dense_sweep: order row %d is not a permutation of 0..%d", (int)sw, n - 1);
-                        seen[(size_t)v] = 1;
-                    }
-                }
-                if (d->order_cap < ucnt) {
-                    if (d->order) (void)hipFree(d->order);
-                    d->order = nullptr;
-                    d->order_cap = 0;
-                    TSU_HIP_TRY(ctx, hipMalloc(&d->order, ucnt * 8));
-                    d->order_cap = ucnt;
-                }
-                TSU_HIP_TRY(ctx, hipMemcpyAsync(d->order, order, ucnt * 8, hipMemcpyHostToDevice, ctx->stream));
-            }
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(d->backup, d->state, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
-            int done = 0;
-            const int rc1 = tsu_dense_pipe_run(d, T, temps_dev, (int)total, n_burnin, n_sweeps, d->samples, seed, sweep0, replica, replay_uniforms != nullptr,
-                                               &done, order ? d->order : nullptr);
+    const bool small = wave_m || (!order && k2wg_takes(d));
+    // The whole run in ONE launch: on the small kernels, or above them on a one-launch kernel, which records the states itself and takes
+    // a temperature per sweep (a loop of calls costs ~60 us per call beside sweeps of 40-100 us at n = 1000-4000) -- where one may
+    // take it (natural order: not after a failed cooperative launch) and the staged orders / uniforms stay within 512 MB
+    const bool one = total > 0 && (small || (n >= 2 * DB && (order || !d->co_disabled) &&
+                                             ((!replay_uniforms && !order) || (size_t)total * n * 8 <= ((size_t)1 << 29))));
+    int done = 0;
+    if (one) {
+        const int rc = dense_upload_inputs(d, (int)total, order, false, replay_uniforms, temps);
+        if (rc != TSU_OK) return rc;
+        const double* uni = replay_uniforms ? d->uniforms : nullptr;
+        const double* temps_dev = temps ? d->temps : nullptr;
+        if (wave_m)
+            TSU_HIP_TRY(ctx, k2w_launch(d, wave_m, ctx->stream, uni, d->samples, T, temps_dev, n_burnin, n_sweeps, n_samples, sweep0, tag,
+                                        (uint32_t)seed, (uint32_t)(seed >> 32)));
+        else if (small)
+            TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, uni, d->samples, T, temps_dev, n_burnin, n_sweeps, n_samples, sweep0, tag, (uint32_t)seed,
+                                         (uint32_t)(seed >> 32), nullptr));
+        else {
+            const int rc1 = tsu_dense_one_launch(d, T, temps_dev, (int)total, n_burnin, n_sweeps, d->samples, seed, sweep0, replica, uni,
+                                                 order ? d->order : nullptr, false, &done);
             if (rc1 != TSU_OK) return rc1;
-            if (done) {
-                if (out_bytes) TSU_HIP_TRY(ctx, hipMemcpyAsync(samples_host, d->samples, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-                TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                return TSU_OK;
-            }
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));  // declined or gave up: the loop below
         }
-        // otherwise the sweep paths above, one call per recorded state; samples gathered on the device
-        // (with a schedule every recorded state is one sweep: n_burnin == 0 and n_sweeps == 1)
-        int rc = tsu_dense_sweep(d, T, n_burnin, order, seed, sweep0, replica, replay_uniforms);
+    }
+    if (!small && !done) {
+        // otherwise the sweep paths, one call per recorded state; samples gathered on the device (with a schedule every recorded state
+        // is one sweep: n_burnin == 0 and n_sweeps == 1).  Orders staged above were checked there.
+        int rc = dense_sweep(d, T, n_burnin, order, seed, sweep0, replica, replay_uniforms, one);
         if (rc != TSU_OK) return rc;
         size_t off = (size_t)n_burnin * n;
         uint32_t sw = sweep0 + (uint32_t)n_burnin;
         for (int k = 0; k < n_samples; ++k) {
-            rc = tsu_dense_sweep(d, temps ? temps[k] : T, n_sweeps, order ? order + off : nullptr, seed, sw, replica,
-                                 replay_uniforms ? replay_uniforms + off : nullptr);
+            rc = dense_sweep(d, temps ? temps[k] : T, n_sweeps, order ? order + off : nullptr, seed, sw, replica,
+                             replay_uniforms ? replay_uniforms + off : nullptr, one);
             if (rc != TSU_OK) return rc;
             TSU_HIP_TRY(ctx, hipMemcpyAsync(d->samples + (size_t)k * n, d->state, (size_t)n, hipMemcpyDeviceToDevice, ctx->stream));
             off += (size_t)n_sweeps * n;
@@ -1258,13 +967,7 @@ int tsu_dense_sweep_replicas(tsu_dense* d, int n_replicas, const double* tempera
             const int mp = m <= 2 ? 2 : m <= 4 ? 4 : 8;  // (padding replicas repeat the group's first one; their results are dropped)
             const size_t sb_ = (size_t)mp * n, ub_ = replay_uniforms ? (size_t)mp * n_sweeps * n * 8 : 0;
             const size_t need_ = ((sb_ + 7) / 8) * 8 + ub_;
-            if (d->rep_cap < need_) {
-                if (d->rep_buf) (void)hipFree(d->rep_buf);
-                d->rep_buf = nullptr;
-                d->rep_cap = 0;
-                TSU_HIP_TRY(ctx, hipMalloc(&d->rep_buf, need_));
-                d->rep_cap = need_;
-            }
+            TSU_HIP_TRY(ctx, dense_grow(d->rep_buf, d->rep_cap, need_));
             int8_t* ds = (int8_t*)d->rep_buf;
             double* du = ub_ ? (double*)((char*)d->rep_buf + ((sb_ + 7) / 8) * 8) : nullptr;
             if (!d->h_rep && hipHostMalloc((void**)&d->h_rep, (size_t)8 * n, hipHostMallocDefault) != hipSuccess) {
@@ -1313,13 +1016,16 @@ int tsu_dense_sweep_replicas(tsu_dense* d, int n_replicas, const double* tempera
             }
             if (d->h_rep) TSU_HIP_TRY(ctx, hipMemcpyAsync(ds, d->h_rep, (size_t)mp * n, hipMemcpyHostToDevice, ctx->stream));
             int done = 0;
+            const int own_failed = d->own_failed;
             const int rc = tsu_dense_own_run(d, mp, reps, ds, n_sweeps, du, nullptr, nullptr, nullptr, 0, 1, all_known, can_keep, &done);
             if (rc != TSU_OK) {
                 d->rep_prev_n = 0;
                 return rc;
             }
             if (!done) {
-                d->own_failed = 0;  // (the replicas' states live in a scratch buffer: nothing of the system was touched)
+                // the replicas' states live in a scratch buffer: nothing of the system was touched, and a give-up here does not take
+                // k2_own away from the single chain (nor does it clear a single-chain give-up: that one stays sticky)
+                d->own_failed = own_failed;
                 d->rep_prev_n = 0;
                 all_done = false;
                 break;
@@ -1347,13 +1053,7 @@ int tsu_dense_sweep_replicas(tsu_dense* d, int n_replicas, const double* tempera
     const size_t sbytes = (size_t)n_replicas * n, ubytes = replay_uniforms ? (size_t)n_replicas * n_sweeps * n * 8 : 0;
     const size_t rbytes = (size_t)n_replicas * sizeof(K2Replica);
     const size_t need = ((sbytes + 7) / 8) * 8 + ubytes + rbytes;
-    if (d->rep_cap < need) {
-        if (d->rep_buf) (void)hipFree(d->rep_buf);
-        d->rep_buf = nullptr;
-        d->rep_cap = 0;
-        TSU_HIP_TRY(ctx, hipMalloc(&d->rep_buf, need));
-        d->rep_cap = need;
-    }
+    TSU_HIP_TRY(ctx, dense_grow(d->rep_buf, d->rep_cap, need));
     int8_t* d_states = (int8_t*)d->rep_buf;
     double* d_uni = ubytes ? (double*)((char*)d->rep_buf + ((sbytes + 7) / 8) * 8) : nullptr;
     K2Replica* d_reps = (K2Replica*)((char*)d->rep_buf + ((sbytes + 7) / 8) * 8 + ubytes);
@@ -1422,13 +1122,7 @@ int tsu_dense_energies(tsu_dense* d, const int8_t* states_host, int n_states, do
     const size_t n = (size_t)d->n;
     TSU_REQUIRE(ctx, dense_bits01(states_host, n * (size_t)n_states), "dense_energies: states must be 0/1");
     // the states share the sample buffer (it is only ever a staging area of one call), the energies get a scratch array
-    if (d->samples_cap < n * (size_t)n_states) {
-        if (d->samples) (void)hipFree(d->samples);
-        d->samples = nullptr;
-        d->samples_cap = 0;
-        TSU_HIP_TRY(ctx, hipMalloc(&d->samples, n * (size_t)n_states));
-        d->samples_cap = n * (size_t)n_states;
-    }
+    TSU_HIP_TRY(ctx, dense_grow(d->samples, d->samples_cap, n * (size_t)n_states));
     double* d_e = nullptr;
     TSU_HIP_TRY(ctx, hipMalloc(&d_e, (size_t)n_states * 8));
     hipError_t e = hipMemcpyAsync(d->samples, states_host, n * (size_t)n_states, hipMemcpyHostToDevice, ctx->stream);

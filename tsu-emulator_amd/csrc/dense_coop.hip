@@ -1,10 +1,9 @@
 // dense_coop.hip -- K2 in ONE launch of a co-resident grid per call: natural-order sequential Gibbs sweeps on a dense J.
 //
-// Same mathematics as the superblock path in dense.hip (the sequential pass over a superblock of SB_SIZE positions is
-// the unique fixed point of delta = decide(f + L delta), reached exactly by Jacobi iteration from delta = 0), but
+// The sequential pass over a superblock of SB_SIZE positions is the unique fixed point of delta = decide(f + L delta),
+// reached exactly by Jacobi iteration from delta = 0 (site i is exact from iteration i on); here
 //   * all phases of all sweeps run inside one grid of co-resident workgroups separated by grid barriers (release /
-//     acquire at agent scope on one counter), so an iteration costs a barrier (~2 us) instead of a launch, and a
-//     converged superblock costs nothing more (no budget of early-exit launches);
+//     acquire at agent scope on one counter), so an iteration costs a barrier (~2 us) instead of a launch;
 //   * after the first full triangular pass an iteration is INCREMENTAL: only the sites whose decision changed in the
 //     previous iteration (a list of tens) are applied to the rows below them;
 //   * the streaming passes (field, triangular pass, strip update of the later rows) read J with 16-byte loads,
@@ -803,45 +802,24 @@ __global__ __launch_bounds__(CO_THREADS) void k2_pipe(PipeParams P) {
 }
 
 template <typename TJ>
-static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, bool have_uni,
-                      int* done, bool fields_were_valid, const double* temps_dev = nullptr, int8_t* samples_dev = nullptr, int rec_from = 0,
-                      int rec_every = 1) {
+static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, const double* uniforms,
+                      int* done, bool fields_were_valid, const double* temps_dev, int8_t* samples_dev, int rec_from, int rec_every) {
     tsu_ctx* ctx = d->ctx;
     const int n = d->n;
     *done = 0;
-    static int use_pipe = -1;
-    if (use_pipe < 0) {
-        const char* e = getenv("TSU_K2_PIPE");
-        use_pipe = e ? atoi(e) : 1;
-    }
-    int grid = ctx->cus;
-    // small systems: fewer streamer workgroups (every workgroup takes part in the hand-off counters, and a system of a few hundred
-    // rows has no work for 4000 waves); from 2048 rows up every CU streams.  TSU_K2_PIPE_WG_PER_1024 = workgroups per 1024 rows (0: every CU)
-    static int grid_env = -1;
-    if (grid_env < 0) {
-        const char* e = getenv("TSU_K2_PIPE_WG_PER_1024");
-        grid_env = e ? atoi(e) : 128;  // measured (n = 580 / 1024: 36 / 42 us per sweep; with every CU 46 / 49, with 64 per 1024 rows 40 / 44)
-    }
-    static int sb_env = -1;
-    if (sb_env < 0) {
-        const char* e = getenv("TSU_K2_PIPE_SB");
-        sb_env = e ? atoi(e) : 0;
-    }
     // superblock: 4096 (2048 for systems that fit one): re-measured on the finished pipeline (profiles/r02_k2_notes.txt) -- 8192,
     // which had won up to n = 12288 half-way through its development, loses everywhere now
-    const int sb = (sb_env == 2048 || sb_env == 4096 || sb_env == 8192) ? sb_env : (n <= 2048 ? 2048 : 4096);
+    const int sb = n <= 2048 ? 2048 : 4096;
     const int ns = sb / 256;
-    if (grid_env > 0) {
-        const int want = ns + (int)(((long long)n * grid_env + 1023) / 1024);
-        if (want < grid) grid = want;
-    }
-    static int pipe_min = -1;
-    if (pipe_min < 0) {
-        const char* e = getenv("TSU_K2_PIPE_MIN");
-        pipe_min = e ? atoi(e) : 452;  // just above the one-workgroup kernel (k2_wg: 576 fp32 / 448 fp64 sites): 45-50 us per sweep at
-                                       // n = 580 .. 1020 against 50-62 us on the barrier kernel
-    }
-    if (!use_pipe || n > CO_MAX_N || n < pipe_min || grid < 2 * ns) return TSU_OK;
+    // small systems: fewer streamer workgroups (every workgroup takes part in the hand-off counters, and a system of a few hundred
+    // rows has no work for 4000 waves); from 2048 rows up every CU streams.  128 workgroups per 1024 rows: measured (n = 580 / 1024:
+    // 36 / 42 us per sweep; with every CU 46 / 49, with 64 per 1024 rows 40 / 44)
+    int grid = ctx->cus;
+    const int want = ns + (int)(((long long)n * 128 + 1023) / 1024);
+    if (want < grid) grid = want;
+    // smallest system: 452, just above the one-workgroup kernel (k2_wg: 528 fp32 / 448 fp64 sites): 45-50 us per sweep at
+    // n = 580 .. 1020 against 50-62 us on the barrier kernel
+    if (n > CO_MAX_N || n < 452 || grid < 2 * ns) return TSU_OK;
     if ((long long)(grid - ns) * (CO_THREADS / 64) * PP_MAXR < n) return TSU_OK;
     if (n % 4) return TSU_OK;  // state / flips travel as dwords
     const bool vec = (n % JVec<TJ>::W) == 0;
@@ -849,8 +827,7 @@ static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     // hand-offs and gathers queue behind them): ONE while those rows take less time than the iterations anyway (N = 16384:
     // 0.386 -> 0.353 ms per sweep; profiles/r02_k2_notes.txt), eight once the strips dominate
     const bool gentle = n <= 20480;
-    void (*kern)(PipeParams) = sb == 8192 ? (vec ? k2_pipe<TJ, true, 8192, 1> : k2_pipe<TJ, false, 8192, 1>)
-                               : sb == 2048 ? (vec ? k2_pipe<TJ, true, 2048, 1> : k2_pipe<TJ, false, 2048, 1>)
+    void (*kern)(PipeParams) = sb == 2048 ? (vec ? k2_pipe<TJ, true, 2048, 1> : k2_pipe<TJ, false, 2048, 1>)
                                : gentle   ? (vec ? k2_pipe<TJ, true, 4096, 1> : k2_pipe<TJ, false, 4096, 1>)
                                           : (vec ? k2_pipe<TJ, true, 4096, 8> : k2_pipe<TJ, false, 4096, 8>);
     const size_t lds_bytes = (size_t)((n > sb ? n : sb) + 15) / 16 * 16;
@@ -878,7 +855,7 @@ static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     P.state = d->state;
     P.f = d->field;
     P.d1 = d->co_d1;
-    P.uniforms = have_uni ? d->uniforms : nullptr;
+    P.uniforms = uniforms;
     P.masks = d->pp_masks;
     P.corr = d->co_corr;
     P.d0 = d->co_d0;
@@ -892,22 +869,16 @@ static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     P.k1 = (uint32_t)(seed >> 32);
     // fields from call to call: resume when the previous pipeline call left them for exactly this state and no refresh is due;
     // keep them from the second consecutive call on (a lone call does not pay for rows it would not need again)
-    static int keep_fields = -1;
-    if (keep_fields < 0) {
-        const char* e = getenv("TSU_K2_KEEP_FIELDS");
-        keep_fields = e ? atoi(e) : 1;
-    }
     P.fields_all = d->co_fields;
     P.temps = temps_dev;
     P.samples = samples_dev;
     P.rec_from = rec_from;
     P.rec_every = rec_every > 0 ? rec_every : 1;
-    P.resume = keep_fields && fields_were_valid && (d->since_refresh % CO_REFRESH) != 0 ? 1 : 0;
+    P.resume = fields_were_valid && (d->since_refresh % CO_REFRESH) != 0 ? 1 : 0;
     P.refresh_off = P.resume ? d->since_refresh : 0;
-    P.persist = keep_fields && d->pipe_streak >= 1 ? 1 : 0;
-    const char* verbose = getenv("TSU_K2_VERBOSE");
+    P.persist = d->pipe_streak >= 1 ? 1 : 0;
     unsigned long long* d_tl = nullptr;
-    if (verbose && atoi(verbose) >= 2) {
+    if (dense_env("TSU_K2_VERBOSE", 0) >= 2) {
         TSU_HIP_TRY(ctx, hipMalloc(&d_tl, 10 * sizeof(unsigned long long)));
         TSU_HIP_TRY(ctx, hipMemsetAsync(d_tl, 0, 10 * sizeof(unsigned long long), ctx->stream));
     }
@@ -941,8 +912,8 @@ static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
                 tl[6] / 100.0 / nsb_tot, tl[7] / 100.0 / nsb_tot, tl[8] / 100.0 / nsb_tot, tl[9] / 100.0 / nsb_tot);
     }
     if (h[1] || h[3]) {
-        // a wait expired (GPU shared with another long-running kernel) or -- never seen -- no fixed point: the caller
-        // restores the state from its backup and the other paths take the call
+        // a wait expired (GPU shared with another long-running kernel) or -- never seen -- no fixed point: the state is restored
+        // from the backup and the other paths take the call
         fprintf(stderr, "[tsu] dense sweep (pipeline): %s; continuing on the barrier path\n", h[1] ? "a wait timed out (GPU shared?)" : "no fixed point");
         d->pp_failed = 1;
         return TSU_OK;
@@ -956,12 +927,12 @@ static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
 }
 
 template <typename TJ>
-static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, bool have_uni,
+static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, const double* uniforms,
                       int* done) {
     tsu_ctx* ctx = d->ctx;
     const int n = d->n;
     *done = 0;
-    if (n > CO_MAX_N) return TSU_OK;  // the staged state vector must fit in LDS: larger systems take the multi-launch path
+    if (n > CO_MAX_N) return TSU_OK;  // the staged state vector must fit in LDS: larger systems take the block-by-block path
     const bool vec = (n % JVec<TJ>::W) == 0;
     void (*kern)(CoopParams) = vec ? k2_coop<TJ, true> : k2_coop<TJ, false>;
     const size_t lds_bytes = (size_t)((n > SB_SIZE ? n : SB_SIZE) + 15) / 16 * 16;
@@ -984,13 +955,7 @@ static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     if (!d->co_d1) TSU_HIP_TRY(ctx, hipMalloc(&d->co_d1, (size_t)n));
     if (!d->co_lists) TSU_HIP_TRY(ctx, hipMalloc(&d->co_lists, 2 * SB_SIZE * sizeof(int)));
     if (!d->co_bar) TSU_HIP_TRY(ctx, hipMalloc(&d->co_bar, BAR_WORDS * sizeof(unsigned)));
-    if (d->co_counts_cap < count_ints) {
-        if (d->co_counts) (void)hipFree(d->co_counts);
-        d->co_counts = nullptr;
-        d->co_counts_cap = 0;
-        TSU_HIP_TRY(ctx, hipMalloc(&d->co_counts, count_ints * sizeof(int)));
-        d->co_counts_cap = count_ints;
-    }
+    TSU_HIP_TRY(ctx, dense_grow(d->co_counts, d->co_counts_cap, count_ints * sizeof(int)));
     TSU_HIP_TRY(ctx, hipMemsetAsync(d->co_counts, 0, count_ints * sizeof(int), ctx->stream));
     TSU_HIP_TRY(ctx, hipMemsetAsync(d->co_bar, 0, BAR_WORDS * sizeof(unsigned), ctx->stream));
     CoopParams P;
@@ -1003,7 +968,7 @@ static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     P.corr = d->co_corr;
     P.d0 = d->co_d0;
     P.d1 = d->co_d1;
-    P.uniforms = have_uni ? d->uniforms : nullptr;
+    P.uniforms = uniforms;
     P.lists = d->co_lists;
     P.counts = d->co_counts;
     P.bar = d->co_bar;
@@ -1014,9 +979,9 @@ static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     P.tag = TSU_TAG_DENSE | (replica << 8);
     P.k0 = (uint32_t)seed;
     P.k1 = (uint32_t)(seed >> 32);
-    const char* verbose = getenv("TSU_K2_VERBOSE");
+    const int verbose = dense_env("TSU_K2_VERBOSE", 0);
     unsigned long long* d_tl = nullptr;
-    if (verbose && atoi(verbose) >= 2) TSU_HIP_TRY(ctx, hipMalloc(&d_tl, 8 * sizeof(unsigned long long)));
+    if (verbose >= 2) TSU_HIP_TRY(ctx, hipMalloc(&d_tl, 8 * sizeof(unsigned long long)));
     P.timeline = d_tl;
     // one workgroup per CU: every phase is either a stream (16 waves x 8 loads in flight per CU) or tiny, and fewer
     // arrivals make a cheaper barrier; small systems use fewer workgroups still
@@ -1045,8 +1010,8 @@ static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (h[1]) {
         // a workgroup waited 4 s at a barrier: the grid was not co-resident (GPU shared with another long-running
-        // kernel).  The caller restores the state from its backup and continues on the one-launch-per-iteration path.
-        fprintf(stderr, "[tsu] dense sweep: grid barrier timed out (GPU shared?); continuing with one launch per iteration\n");
+        // kernel).  The state is restored from the backup and the block-by-block path takes the call.
+        fprintf(stderr, "[tsu] dense sweep: grid barrier timed out (GPU shared?); continuing on the block-by-block path\n");
         d->co_disabled = 1;
         if (d_tl) (void)hipFree(d_tl);
         return TSU_OK;
@@ -1062,7 +1027,7 @@ static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     if (verbose)
         fprintf(stderr, "[tsu] dense cooperative: n=%d, %d workgroups, %d sweeps, slowest fixed point after %u iterations%s\n", n, grid,
                 n_sweeps, h[2], h[3] ? " (NOT converged)" : "");
-    if (h[3]) return TSU_OK;  // *done stays 0: the caller restores the state and takes the other path
+    if (h[3]) return TSU_OK;  // *done stays 0: the state is restored and the block-by-block path takes the call
     if (n_sweeps & 1) {
         int8_t* tmp = d->state;
         d->state = d->state2;
@@ -1072,81 +1037,54 @@ static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
     return TSU_OK;
 }
 
-// the owner-computes kernel (dense_own.hip) for one state: same contract as pipe_sweep
-static int own_try(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, bool have_uni, const int64_t* order_dev,
-                   const double* temps_dev, int8_t* samples_dev, int rec_from, int rec_every, bool fields_were_valid, int* done) {
-    OwnRep rep;
-    rep.T = T;
-    rep.sweep0 = sweep0;
-    rep.tag = TSU_TAG_DENSE | (replica << 8);
-    rep.k0 = (uint32_t)seed;
-    rep.k1 = (uint32_t)(seed >> 32);
-    return tsu_dense_own_run(d, 1, &rep, d->state, n_sweeps, have_uni ? d->uniforms : nullptr, order_dev, temps_dev, samples_dev, rec_from, rec_every,
-                             fields_were_valid, true, done);
-}
-
-// a whole run (burn-in, then n_samples x n_sweeps sweeps with the state recorded after each group; or an annealing schedule: one
-// temperature per sweep) in ONE launch -- the owner-computes kernel first, then the pipeline; *done = 0: neither takes it (the
-// caller's loop of calls does).  order_dev: the caller's visiting orders ([n_total][n], owner-computes kernel only) or nullptr.
-int tsu_dense_pipe_run(tsu_dense* d, double T, const double* temps_dev, int n_total, int rec_from, int rec_every, int8_t* samples_dev,
-                       uint64_t seed, uint32_t sweep0, uint32_t replica, bool have_uni, int* done, const int64_t* order_dev) {
+int tsu_dense_one_launch(tsu_dense* d, double T, const double* temps_dev, int n_sweeps, int rec_from, int rec_every, int8_t* samples_dev,
+                         uint64_t seed, uint32_t sweep0, uint32_t replica, const double* uniforms_dev, const int64_t* order_dev, bool plain,
+                         int* done) {
+    tsu_ctx* ctx = d->ctx;
+    const bool f64 = d->dtype == TSU_DTYPE_F64;
     *done = 0;
+    // whatever runs below, the fields kept from the last call stop being those of d->state: the kernel that takes the call sets them
+    // again, and it is handed the streak of consecutive one-launch calls (the second one starts to keep the fields)
     bool fields_were_valid = d->fields_valid != 0;
     const int streak = d->pipe_streak;
-    d->fields_valid = 0;
-    d->rep_match = 0;
-    d->pipe_streak = 0;
-    if (n_total <= 0) return TSU_OK;
+    dense_forget_fields(d);
+    // (natural order: a cooperative launch that could not run or timed out once takes all three kernels out for this handle)
+    if (n_sweeps <= 0 || (!order_dev && d->co_disabled)) return TSU_OK;
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(d->backup, d->state, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
     if (!d->own_failed) {
+        OwnRep rep;
+        rep.T = T;
+        rep.sweep0 = sweep0;
+        rep.tag = TSU_TAG_DENSE | (replica << 8);
+        rep.k0 = (uint32_t)seed;
+        rep.k1 = (uint32_t)(seed >> 32);
         d->pipe_streak = streak;
-        const int rc = own_try(d, T, n_total, seed, sweep0, replica, have_uni, order_dev, temps_dev, samples_dev, rec_from, rec_every, fields_were_valid, done);
+        const int rc = tsu_dense_own_run(d, 1, &rep, d->state, n_sweeps, uniforms_dev, order_dev, temps_dev, samples_dev, rec_from, rec_every,
+                                         fields_were_valid, true, done);
         if (!*done) d->pipe_streak = 0;
         if (rc != TSU_OK || *done) return rc;
-        if (d->own_failed) {  // it ran and gave up half way: back to the state at the start of the call (the caller's backup)
-            TSU_HIP_TRY(d->ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, d->ctx->stream));
+        if (d->own_failed) {  // it ran and gave up half way (later calls skip it): back to the state at the start of the call
+            TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
             fields_were_valid = false;
         }
     }
-    if (d->pp_failed || order_dev) return TSU_OK;
-    d->pipe_streak = streak;
-    const int rc = d->dtype == TSU_DTYPE_F64
-                       ? pipe_sweep<double>(d, T, n_total, seed, sweep0, replica, have_uni, done, fields_were_valid, temps_dev, samples_dev, rec_from, rec_every)
-                       : pipe_sweep<float>(d, T, n_total, seed, sweep0, replica, have_uni, done, fields_were_valid, temps_dev, samples_dev, rec_from, rec_every);
-    if (!*done) d->pipe_streak = 0;
-    return rc;
-}
-
-int tsu_dense_coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, bool have_uni,
-                         int* done, const int64_t* order_dev) {
-    // first choice: the owner-computes kernel, then the two-role pipeline (both in place on d->state); they decline small / odd systems
-    // and report a failed run with *done = 0, in which case the state is restored here and the barrier kernel below takes the call
-    // (whatever happens below, the fields kept from the last call stop being those of d->state; a successful call sets the flag again)
-    bool fields_were_valid = d->fields_valid != 0;
-    const int streak = d->pipe_streak;
-    d->fields_valid = 0;
-    d->rep_match = 0;
-    d->pipe_streak = 0;
-    *done = 0;
-    if (!d->own_failed) {
-        d->pipe_streak = streak;
-        const int rc = own_try(d, T, n_sweeps, seed, sweep0, replica, have_uni, order_dev, nullptr, nullptr, 0, 1, fields_were_valid, done);
-        if (!*done) d->pipe_streak = 0;
-        if (rc != TSU_OK || *done) return rc;
-        if (d->own_failed) {
-            TSU_HIP_TRY(d->ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, d->ctx->stream));
-            fields_were_valid = false;
-        }
-    }
-    if (order_dev) return TSU_OK;  // the other one-launch kernels run in natural order only
+    if (order_dev) return TSU_OK;  // the other two run in natural order only
     if (!d->pp_failed) {
         d->pipe_streak = streak;
-        const int rc = d->dtype == TSU_DTYPE_F64 ? pipe_sweep<double>(d, T, n_sweeps, seed, sweep0, replica, have_uni, done, fields_were_valid)
-                                                 : pipe_sweep<float>(d, T, n_sweeps, seed, sweep0, replica, have_uni, done, fields_were_valid);
+        const int rc = f64 ? pipe_sweep<double>(d, T, n_sweeps, seed, sweep0, replica, uniforms_dev, done, fields_were_valid, temps_dev, samples_dev,
+                                                rec_from, rec_every)
+                           : pipe_sweep<float>(d, T, n_sweeps, seed, sweep0, replica, uniforms_dev, done, fields_were_valid, temps_dev, samples_dev,
+                                               rec_from, rec_every);
         if (!*done) d->pipe_streak = 0;
         if (rc != TSU_OK || *done) return rc;
-        if (d->pp_failed)  // it ran and gave up half way: back to the state at the start of the call (the caller's backup)
-            TSU_HIP_TRY(d->ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, d->ctx->stream));
+        if (d->pp_failed)  // as above
+            TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    if (d->dtype == TSU_DTYPE_F64) return coop_sweep<double>(d, T, n_sweeps, seed, sweep0, replica, have_uni, done);
-    return coop_sweep<float>(d, T, n_sweeps, seed, sweep0, replica, have_uni, done);
+    if (!plain) return TSU_OK;  // (k2_coop neither records states nor follows a schedule)
+    const int rc = f64 ? coop_sweep<double>(d, T, n_sweeps, seed, sweep0, replica, uniforms_dev, done)
+                       : coop_sweep<float>(d, T, n_sweeps, seed, sweep0, replica, uniforms_dev, done);
+    if (rc != TSU_OK || *done) return rc;
+    // declined, could not launch, timed out or found no fixed point
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
+    return TSU_OK;
 }

@@ -1354,11 +1354,6 @@ static own_kern own_pick(int M, int R, bool ord) {
     return R == 2 ? k2_own<TJ, 1, 2, false> : R == 4 ? k2_own<TJ, 1, 4, false> : R == 8 ? k2_own<TJ, 1, 8, false> : nullptr;
 }
 
-static int own_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-
 // One launch of k2_own: n_sweeps sweeps of R states.  *done = 0: the kernel does not take this call (the caller's other paths do;
 // nothing was written) or it gave up half way (d->own_failed set: the caller restores the state from its backup).
 //   states_dev: [R][n] device states (R == 1: d->state), uniforms_dev: [R][n_sweeps][n] or nullptr, order_dev: [n_sweeps][n] or nullptr
@@ -1368,9 +1363,9 @@ int tsu_dense_own_run(tsu_dense* d, int R_real, const OwnRep* reps, int8_t* stat
     tsu_ctx* ctx = d->ctx;
     const int n = d->n;
     *done = 0;
-    static const int use_own = own_env("TSU_K2_OWN", 1);
-    static const int own_min = own_env("TSU_K2_OWN_MIN", 2048);
-    const int sb_env = own_env("TSU_K2_OWN_SB", 0), m_env = own_env("TSU_K2_OWN_M", 0);  // (read per call: tests vary them)
+    static const int use_own = dense_env("TSU_K2_OWN", 1);
+    static const int own_min = dense_env("TSU_K2_OWN_MIN", 2048);
+    const int sb_env = dense_env("TSU_K2_OWN_SB", 0), m_env = dense_env("TSU_K2_OWN_M", 0);  // (read per call: tests vary them)
     if (!use_own || d->own_failed || n < own_min || n > 65536 || n_sweeps <= 0) return TSU_OK;
     const bool ord = order_dev != nullptr;
     if (R_real < 1 || R_real > OWN_MAX_R || (ord && R_real != 1)) return TSU_OK;
@@ -1420,13 +1415,7 @@ int tsu_dense_own_run(tsu_dense* d, int R_real, const OwnRep* reps, int8_t* stat
         return TSU_OK;
     }
     const size_t gen_words = (size_t)OWN_NGEN * R * G * 2, fin_words = (size_t)OWN_RING * R * G * 2;
-    if (d->own_cap < gen_words + fin_words) {
-        if (d->own_gran) (void)hipFree(d->own_gran);
-        d->own_gran = nullptr;
-        d->own_cap = 0;
-        TSU_HIP_TRY(ctx, hipMalloc(&d->own_gran, (gen_words + fin_words) * 8));
-        d->own_cap = gen_words + fin_words;
-    }
+    TSU_HIP_TRY(ctx, dense_grow(d->own_gran, d->own_cap, (gen_words + fin_words) * 8));
     if (!d->co_bar) TSU_HIP_TRY(ctx, hipMalloc(&d->co_bar, BAR_WORDS * sizeof(unsigned)));
     if (!d->co_fields) TSU_HIP_TRY(ctx, hipMalloc(&d->co_fields, (size_t)n * 8));
     TSU_HIP_TRY(ctx, hipMemsetAsync(d->own_gran, 0, (gen_words + fin_words) * 8, ctx->stream));
@@ -1451,28 +1440,27 @@ int tsu_dense_own_run(tsu_dense* d, int R_real, const OwnRep* reps, int8_t* stat
     P.lmax = lmax;
     P.rec_from = rec_from;
     P.rec_every = rec_every > 0 ? rec_every : 1;
-    P.fail_at = own_env("TSU_K2_OWN_TEST_FAIL", -1);
+    P.fail_at = dense_env("TSU_K2_OWN_TEST_FAIL", -1);
     // lists a deciding wave gathers by itself: up to 32 entries in natural order, 48 in a caller's order and for replicas (n = 16384:
     // natural order is flat from 16 to 32, the other two from 48 to 64); a replica's own short list has 64 slots
-    P.solo_max = own_env("TSU_K2_OWN_SOLO_MAX", (ord || R > 1) ? 48 : OWN_SOLO_MAX);
+    P.solo_max = dense_env("TSU_K2_OWN_SOLO_MAX", (ord || R > 1) ? 48 : OWN_SOLO_MAX);
     if (P.solo_max > 64) P.solo_max = 64;
     if (P.solo_max < 0) P.solo_max = 0;
     // solo generations (one chain): the deciding wave polls one group per lane in natural order, four in a caller's order.  (Replicas
     // always run their generations wave by wave: rep_step.)  Both switches are read per call: A/B measurements.
-    P.solo = own_env("TSU_K2_OWN_SOLO", 1) && (ord ? NP <= 256 : NP <= 64) && (R == 1 || M == 1);
+    P.solo = dense_env("TSU_K2_OWN_SOLO", 1) && (ord ? NP <= 256 : NP <= 64) && (R == 1 || M == 1);
     for (int r = 0; r < R; ++r) P.rep[r] = reps[r < R_real ? r : 0];  // (padding replicas repeat replica 0 on its own state copy: see the caller)
-    static const int keep_fields = own_env("TSU_K2_KEEP_FIELDS", 1);
     const bool single = R_real == 1 && allow_persist;
-    P.resume = single && keep_fields && fields_were_valid && (d->since_refresh % CO_REFRESH) != 0 ? 1 : 0;
+    P.resume = single && fields_were_valid && (d->since_refresh % CO_REFRESH) != 0 ? 1 : 0;
     P.refresh_off = P.resume ? d->since_refresh : 0;
-    P.persist = single && keep_fields && d->pipe_streak >= 1 ? 1 : 0;
+    P.persist = single && d->pipe_streak >= 1 ? 1 : 0;
     if (R_real > 1) {  // (replicas: the caller matched the incoming states with the ones whose fields are kept: rep[].src)
-        const bool rk = allow_persist && keep_fields && d->rep_fields[0] && d->rep_fields[1];
+        const bool rk = allow_persist && d->rep_fields[0] && d->rep_fields[1];
         P.resume = rk && fields_were_valid && (d->rep_since % CO_REFRESH) != 0 ? 1 : 0;
         P.refresh_off = P.resume ? d->rep_since : 0;
         P.persist = rk ? 1 : 0;
     }
-    static const int verbose = own_env("TSU_K2_VERBOSE", 0);
+    static const int verbose = dense_env("TSU_K2_VERBOSE", 0);
     unsigned long long* d_tl = nullptr;
     if (verbose >= 2) {
         TSU_HIP_TRY(ctx, hipMalloc(&d_tl, 12 * sizeof(unsigned long long)));
