@@ -45,7 +45,8 @@ extern "C" {
 #define TSU_KERNEL_AUTO 0    /* pick the fastest kernel that supports the lattice */
 #define TSU_KERNEL_GENERIC 1 /* one colour per launch, global memory, any shape / boundary */
 #define TSU_KERNEL_TILED 2   /* LDS-staged halo tiles, several sweeps per launch */
-#define TSU_KERNEL_SMALL 3   /* whole (small) lattice resident in one workgroup's LDS, all sweeps in one launch */
+#define TSU_KERNEL_SMALL 3   /* whole lattice of <= 1024 octets: resident in one workgroup's LDS, all sweeps in one launch
+                                (one-row and one-column lattices: the generic kernel) */
 
 typedef struct tsu_ctx tsu_ctx;
 typedef struct tsu_ising2d tsu_ising2d;
@@ -135,9 +136,9 @@ int tsu_ising2d_sample(tsu_ising2d* lat, int n_burnin, int n_sweeps, int n_sampl
 
 /* Many independent lattices at once (one per temperature of a scan, ising.py:424-476; replicas of a tempering
  * ladder): lattice i does n_sweeps sweeps with its own thresholds, seeds[i], sweep0s[i], replicas[i] -- the same
- * results as n calls of tsu_ising2d_sweep.  Lattices that fit the one-workgroup kernel (TSU_KERNEL_SMALL) run as ONE
- * launch, one workgroup each; larger ones go to a few side streams and run side by side as far as they fit the chip
- * together.  observables_batch: one synchronisation for all. */
+ * results as n calls of tsu_ising2d_sweep.  Lattices of one shape and boundary that all run on the one-workgroup kernel
+ * (TSU_KERNEL_SMALL) run as ONE launch, one workgroup each; any other batch goes to a few side streams and runs side by
+ * side as far as it fits the chip together.  observables_batch: one synchronisation for all. */
 int tsu_ising2d_sweep_batch(tsu_ising2d* const* lats, int n_lats, int n_sweeps, const uint64_t* seeds,
                             const uint32_t* sweep0s, const uint32_t* replicas);
 int tsu_ising2d_observables_batch(tsu_ising2d* const* lats, int n_lats, int64_t* sum_s, int64_t* sum_bonds);

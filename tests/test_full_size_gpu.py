@@ -87,7 +87,7 @@ def test_config2_lattice_8192_kernels_agree(hip):
                                               (5888, 6144, (9, 3)),      # ragged tile rows: 256 x 512 nibble tiles, one launch per 8 sweeps
                                               (8192, 16384, (11,))])     # 2^27 sites, whole tiles
 def test_nibble_plane_lattices_chosen_automatically_equal_the_generic_kernel(hip, rows, cols, sweeps):
-    """Lattices above 2^25 sites take the nibble colour planes (csrc/ising2d_tiled.hip: pick_variant): the automatic choice
+    """Lattices above 2^25 sites take the nibble colour planes (csrc/ising2d_tiled.hip: plan_call): the automatic choice
     must give the generic kernel's lattice, by checksum and observables, over several calls (sweep counters run on)."""
     lats = []
     for kern in (hip.KERNEL_AUTO, hip.KERNEL_GENERIC):

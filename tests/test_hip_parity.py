@@ -183,6 +183,36 @@ def test_ising2d_colour_plane_kernel_bit_exact(hip, rows, cols, periodic):
         lat.close()
 
 
+ROUTE_CALLS = (1, 3, 8, 9, 20)
+PLANES = [1] * 5                          # k1_planes: one launch per call
+GENERIC = [2 * n for n in ROUTE_CALLS]    # k1_generic: one launch per colour
+TILED = [-(-n // 8) for n in ROUTE_CALLS]  # the tiled kernel: one launch per 8 sweeps
+RESIDENT = [1] * 5                        # ... and one per call when the tiles stay resident (calls above 8 sweeps)
+
+
+@pytest.mark.parametrize("rows,cols,periodic,kernel,want", [
+    (32, 32, True, "auto", PLANES), (32, 32, True, "small", PLANES), (130, 36, True, "auto", PLANES), (130, 36, True, "small", PLANES),
+    (33, 47, False, "auto", PLANES), (33, 47, False, "small", PLANES), (6, 20, True, "auto", PLANES), (6, 20, True, "small", PLANES),
+    (1, 9, False, "auto", GENERIC), (1, 9, False, "small", GENERIC), (9, 1, False, "auto", GENERIC), (9, 1, False, "small", GENERIC),
+    (1, 1, False, "auto", GENERIC), (1, 1, False, "small", GENERIC),
+    (4096, 4096, True, "auto", RESIDENT), (1000, 1000, True, "auto", RESIDENT), (1000, 1000, False, "tiled", RESIDENT),
+    (96, 4096, True, "auto", TILED), (96, 4096, True, "tiled", TILED)])
+def test_ising2d_route_launch_counts(hip, rows, cols, periodic, kernel, want):
+    """Which kernel a call runs on, pinned by its launches for calls of 1, 3, 8, 9 and 20 sweeps.  1000^2 stays resident
+    through the flexible cut, 96 x 4096 (one tile row) launches once per 8 sweeps."""
+    lat = hip.Lattice(rows, cols, periodic)
+    lat.set_kernel({"auto": hip.KERNEL_AUTO, "small": hip.KERNEL_SMALL, "tiled": hip.KERNEL_TILED}[kernel])
+    lat.randomize(3)
+    lat.set_model(1.0, 0.0, 2.269185)
+    got = []
+    for n in ROUTE_CALLS:
+        n0 = lat.launch_count()
+        lat.sweep(n, 3, 0)
+        got.append(lat.launch_count() - n0)
+    assert got == want
+    lat.close()
+
+
 def test_ising2d_tiled_ties_and_clamps(hip):
     """Coarse / extreme threshold tables drive the tiled kernel's tie path (low 16 bits) and the 0 / 2^32 clamps."""
     rows, cols = 128, 1040
@@ -267,25 +297,29 @@ def test_ising2d_replica_and_fill(hip):
     np.testing.assert_array_equal(lat.get_spins(), want)
 
 
-@pytest.mark.parametrize("rows,cols,periodic", [(32, 32, True), (20, 20, False), (64, 256, True), (128, 1024, True)])
+@pytest.mark.parametrize("rows,cols,periodic", [(32, 32, True), (20, 20, False), (64, 256, True), (128, 1024, True), (1, 40, False),
+                                               (20, 20, "mixed")])
 def test_ising2d_sweep_batch_equals_one_by_one(hip, rows, cols, periodic):
     """tsu_ising2d_sweep_batch / observables_batch: lattices at different temperatures, seeds, counters and replica
-    ids advance together (one launch when they fit the one-workgroup kernel) == each swept alone == the oracle."""
+    ids advance together (one launch when they fit the one-workgroup kernel) == each swept alone == the oracle.
+    "mixed": periodic and open lattices of one shape in one batch."""
     Ts = [1.5, 2.0, 2.269185, 3.0, 4.5]
-    lats, want = [], []
+    lats, want, pers = [], [], []
     for i, T in enumerate(Ts):
-        lat = hip.Lattice(rows, cols, periodic)
+        per = (i % 2 == 0) if periodic == "mixed" else periodic
+        pers.append(per)
+        lat = hip.Lattice(rows, cols, per)
         lat.randomize(100 + i, replica=i)
         lat.set_model(1.0, 0.05 * i, T)
         lats.append(lat)
         table = ora.ising2d_thresholds(1.0, 0.05 * i, T, 0)
         s0 = ora.ising2d_randomize(rows, cols, 100 + i, replica=i)
-        want.append(ora.ising2d_sweep(s0, periodic, table, 9, 100 + i, sweep0=3 * i, replica=i))
+        want.append(ora.ising2d_sweep(s0, per, table, 9, 100 + i, sweep0=3 * i, replica=i))
     hip.sweep_batch(lats, 9, [100 + i for i in range(len(Ts))], [3 * i for i in range(len(Ts))], list(range(len(Ts))))
     obs = hip.observables_batch(lats)
     for i, lat in enumerate(lats):
         np.testing.assert_array_equal(lat.get_spins(), want[i])
-        assert obs[i] == ora.ising2d_observables(want[i], periodic) == lat.observables()
+        assert obs[i] == ora.ising2d_observables(want[i], pers[i]) == lat.observables()
         lat.close()
 
 

@@ -20,19 +20,37 @@ struct tsu_ising2d {
     hipEvent_t ev0, ev1;
     int timed, timing;
     unsigned long long launches;  // sweep-kernel launches so far
-    int* d_sync;         // tile-resident kernel: per-tile generation counters
     uint64_t* d_xbuf;    // tile-resident kernel: exchange strips
-    size_t xbuf_cap;
+    size_t xbuf_cap;     // bytes allocated (so are batch_cap and obs_batch_cap: ising2d_grow)
     uint32_t xgen;       // generations numbered so far in d_xbuf (every strip element carries its generation number)
     uint64_t xsig;       // strip layout the numbering belongs to (0: buffer not cleared yet)
     void* d_batch;       // tsu_ising2d_sweep_batch: device copy of the per-lattice launch items
     size_t batch_cap;
     void* d_obs_batch;   // tsu_ising2d_observables_batch: [n][2] sums of the batch (lives with its first lattice)
     size_t obs_batch_cap;
-    size_t sync_cap;     // ints allocated in d_sync
     int* h_err;          // host-mapped flag the tile-resident kernel sets if a bounded wait expires
 };
 
+// grow-only device buffer: reallocated (contents dropped) only when it holds fewer than `bytes`; no memset, no synchronisation
+template <typename T>
+static inline hipError_t ising2d_grow(T*& p, size_t& cap, size_t bytes) {
+    if (cap >= bytes) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    const hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+}
+
+// Philox key and stream tags of a sweep (K1Params, TiledParams, PlanesItem)
+template <typename P>
+static inline void ising2d_set_keys(P& p, uint64_t seed, uint32_t replica) {
+    p.k0 = (uint32_t)seed;
+    p.k1 = (uint32_t)(seed >> 32);
+    p.tag_hi = TSU_TAG_ISING_HI | (replica << 8);
+    p.tag_lo = TSU_TAG_ISING_LO | (replica << 8);
+}
 
 // ising2d_tiled.hip
 int tsu_ising2d_tiled_supported(const tsu_ising2d* L);

@@ -51,7 +51,7 @@ static __device__ __forceinline__ bool row_exists(const K1Params& p, int r) {
 // ------------------------------------------------------------------ one octet of one colour
 // 16 consecutive columns of one row (8 sites of the half-sweep's colour): neighbour bytes, degree and up-count per
 // site, one Philox block, thresholds from s_tbl, masked 16-byte store.  `row`, `up_row`, `dn_row` (NULL = absent) and
-// `out_chunk` may point into global memory (k1_generic) or LDS (k1_small): the row layout is the same.
+// `out_chunk` point into the lattice buffer (k1_generic).
 static __device__ __forceinline__ void k1_update_octet(const K1Params& p, const uint64_t* s_tbl, const int8_t* row,
                                                        const int8_t* up_row, const int8_t* dn_row, int8_t* out_chunk, int q,
                                                        long long gr, int par, int nchunks, uint32_t hs) {
@@ -167,86 +167,6 @@ __global__ __launch_bounds__(256) void k1_generic(K1Params p, K1Table tbl, int c
         if (row_exists(p, r + 1)) dn_row = row + p.pitch;
     }
     k1_update_octet(p, s_tbl, row, up_row, dn_row, p.out + (long long)r * p.pitch + 16 * q, q, gr, par, nchunks, p.hs);
-}
-
-// ------------------------------------------------------------------ small lattices: one workgroup, one launch
-// The whole lattice (not a slab) lives in LDS with the HBM row layout; all n_sweeps run inside one launch with one
-// workgroup barrier per half-sweep (in place: a half-sweep only writes its own colour, which no site of that colour
-// reads).  Same octet update, same Philox counters, hence the same results as k1_generic -- without two launches per
-// sweep, which is all a 32 x 32 lattice (BASELINE configs[0]) costs there.
-__global__ __launch_bounds__(1024) void k1_small(K1Params p, K1Table tbl, uint32_t sweep0, int n_sweeps) {
-    extern __shared__ int8_t s_lat[];
-    __shared__ uint64_t s_tbl[25];
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const int nchunks = (p.cols + 15) >> 4;
-    const int lp = 16 * nchunks;  // LDS row pitch: whole chunks, pad bytes 0 like the HBM rows
-    if (tid < 25) s_tbl[tid] = tbl.t[tid];
-    for (int t = tid; t < p.rows * nchunks; t += nt) {
-        const int r = t / nchunks, q = t - r * nchunks;
-        *reinterpret_cast<uint4*>(s_lat + r * lp + 16 * q) = *reinterpret_cast<const uint4*>(p.base + (long long)r * p.pitch + 16 * q);
-    }
-    __syncthreads();
-    for (int hsi = 0; hsi < 2 * n_sweeps; ++hsi) {
-        const int colour = hsi & 1;
-        const uint32_t hs = 2u * (sweep0 + (uint32_t)(hsi >> 1)) + (uint32_t)colour;
-        for (int t = tid; t < p.rows * nchunks; t += nt) {
-            const int r = t / nchunks, q = t - r * nchunks;
-            const int par = (r + colour) & 1;
-            int8_t* row = s_lat + r * lp;
-            const int8_t* up_row = r > 0 ? row - lp : (p.periodic ? s_lat + (p.rows - 1) * lp : nullptr);
-            const int8_t* dn_row = r < p.rows - 1 ? row + lp : (p.periodic ? s_lat : nullptr);
-            k1_update_octet(p, s_tbl, row, up_row, dn_row, row + 16 * q, q, (long long)r, par, nchunks, hs);
-        }
-        __syncthreads();
-    }
-    for (int t = tid; t < p.rows * nchunks; t += nt) {
-        const int r = t / nchunks, q = t - r * nchunks;
-        *reinterpret_cast<uint4*>(p.out + (long long)r * p.pitch + 16 * q) = *reinterpret_cast<const uint4*>(s_lat + r * lp + 16 * q);
-    }
-}
-
-// k1_small for many lattices of one shape: workgroup b sweeps lattice b (own buffer, thresholds, seed, counters)
-struct K1BatchItem {
-    K1Params p;
-    K1Table tbl;
-    uint32_t sweep0;
-};
-
-__global__ __launch_bounds__(1024) void k1_small_batch(const K1BatchItem* __restrict__ items, int n_sweeps) {
-    extern __shared__ int8_t s_lat[];
-    __shared__ uint64_t s_tbl[25];
-    __shared__ K1Params sp;
-    const K1BatchItem& it = items[blockIdx.x];
-    const int tid = threadIdx.x, nt = blockDim.x;
-    if (tid == 0) sp = it.p;
-    if (tid < 25) s_tbl[tid] = it.tbl.t[tid];
-    __syncthreads();
-    const K1Params& p = sp;
-    const uint32_t sweep0 = it.sweep0;
-    const int nchunks = (p.cols + 15) >> 4;
-    const int lp = 16 * nchunks;
-    for (int t = tid; t < p.rows * nchunks; t += nt) {
-        const int r = t / nchunks, q = t - r * nchunks;
-        *reinterpret_cast<uint4*>(s_lat + r * lp + 16 * q) = *reinterpret_cast<const uint4*>(p.base + (long long)r * p.pitch + 16 * q);
-    }
-    __syncthreads();
-    for (int hsi = 0; hsi < 2 * n_sweeps; ++hsi) {
-        const int colour = hsi & 1;
-        const uint32_t hs = 2u * (sweep0 + (uint32_t)(hsi >> 1)) + (uint32_t)colour;
-        for (int t = tid; t < p.rows * nchunks; t += nt) {
-            const int r = t / nchunks, q = t - r * nchunks;
-            const int par = (r + colour) & 1;
-            int8_t* row = s_lat + r * lp;
-            const int8_t* up_row = r > 0 ? row - lp : (p.periodic ? s_lat + (p.rows - 1) * lp : nullptr);
-            const int8_t* dn_row = r < p.rows - 1 ? row + lp : (p.periodic ? s_lat : nullptr);
-            k1_update_octet(p, s_tbl, row, up_row, dn_row, row + 16 * q, q, (long long)r, par, nchunks, hs);
-        }
-        __syncthreads();
-    }
-    for (int t = tid; t < p.rows * nchunks; t += nt) {
-        const int r = t / nchunks, q = t - r * nchunks;
-        *reinterpret_cast<uint4*>(p.out + (long long)r * p.pitch + 16 * q) = *reinterpret_cast<const uint4*>(s_lat + r * lp + 16 * q);
-    }
 }
 
 // ------------------------------------------------------------------ K4: sum of spins, sum over bonds
@@ -374,12 +294,26 @@ static K1Params make_params(const tsu_ising2d* L, int8_t* buf) {
     return p;
 }
 
-// k1_small: a whole lattice (not a slab) with at most one octet per thread of one workgroup (measured: 32 x 32 3.2 us
-// per sweep against 11 us for two generic launches; at 256 x 256 the whole chip wins: 8 us against 30 us)
+// a whole lattice (not a slab) of at most 1024 octets (rows x ceil(cols/16)): TSU_KERNEL_SMALL takes it
 static bool small_supported(const tsu_ising2d* L) {
     if (L->ghost != 0 || L->total_rows != L->rows || L->row0 != 0) return false;
     const long long nchunks = (L->cols + 15) >> 4, tasks = (long long)L->rows * nchunks;
     return tasks <= 1024;
+}
+
+// The kernel a sweep of L over `part` runs on.  AUTO: a lattice that fits one workgroup's LDS runs all its sweeps in one
+// k1_planes launch (measured: 32 x 32 3.2 us per sweep against 11 us for two generic launches; at 256 x 256 the whole chip
+// wins: 8 us against 30 us); larger ones take the tiled kernel where it applies, the generic one otherwise.  SMALL: k1_planes,
+// or k1_generic for the one-row and one-column lattices k1_planes does not take (same octet update, same counters).
+// K1_NONE: the lattice's kernel setting does not take it.
+enum { K1_NONE = -1, K1_GENERIC, K1_TILED, K1_PLANES };
+static int k1_path(const tsu_ising2d* L, int part) {
+    if (L->kernel == TSU_KERNEL_SMALL && !small_supported(L)) return K1_NONE;
+    if (L->kernel == TSU_KERNEL_TILED && !tsu_ising2d_tiled_supported(L)) return K1_NONE;
+    if (part == TSU_PART_ALL && (L->kernel == TSU_KERNEL_SMALL || (L->kernel == TSU_KERNEL_AUTO && small_supported(L))))
+        return tsu_ising2d_planes_supported(L) ? K1_PLANES : K1_GENERIC;
+    if (L->kernel == TSU_KERNEL_TILED || (L->kernel == TSU_KERNEL_AUTO && tsu_ising2d_tiled_supported(L))) return K1_TILED;
+    return K1_GENERIC;
 }
 
 static dim3 grid_for(const tsu_ising2d* L, int nrows) {
@@ -444,7 +378,6 @@ int tsu_ising2d_create_slab(tsu_ctx* ctx, int64_t total_rows, int cols, int peri
     L->timed = 0;
     L->timing = 0;
     L->launches = 0;
-    L->d_sync = nullptr;
     L->d_xbuf = nullptr;
     L->xbuf_cap = 0;
     L->xgen = 0;
@@ -453,7 +386,6 @@ int tsu_ising2d_create_slab(tsu_ctx* ctx, int64_t total_rows, int cols, int peri
     L->batch_cap = 0;
     L->d_obs_batch = nullptr;
     L->obs_batch_cap = 0;
-    L->sync_cap = 0;
     L->h_err = nullptr;
     size_t bytes = (size_t)(rows + 2 * ghost) * L->pitch;
     hipError_t e = hipMalloc(&L->alloc[0], bytes);
@@ -485,7 +417,6 @@ int tsu_ising2d_destroy(tsu_ising2d* L) {
     for (int i = 0; i < 2; ++i)
         if (L->alloc[i]) (void)hipFree(L->alloc[i]);
     if (L->d_obs) (void)hipFree(L->d_obs);
-    if (L->d_sync) (void)hipFree(L->d_sync);
     if (L->d_xbuf) (void)hipFree(L->d_xbuf);
     if (L->d_batch) (void)hipFree(L->d_batch);
     if (L->d_obs_batch) (void)hipFree(L->d_obs_batch);
@@ -588,11 +519,13 @@ int tsu_ising2d_set_kernel(tsu_ising2d* L, int kernel, int sweeps_per_launch) {
     if (!L) return TSU_E_INVALID;
     TSU_REQUIRE(L->ctx, kernel >= TSU_KERNEL_AUTO && kernel <= TSU_KERNEL_SMALL, "ising2d_set_kernel: bad kernel %d", kernel);
     TSU_REQUIRE(L->ctx, sweeps_per_launch >= 0 && sweeps_per_launch <= 16, "ising2d_set_kernel: sweeps_per_launch in [0,16]");
-    if (kernel == TSU_KERNEL_TILED && !tsu_ising2d_tiled_supported(L))
-        return tsu_fail(L->ctx, TSU_E_UNSUPPORTED, "ising2d_set_kernel: tiled kernel does not support this lattice");
-    if (kernel == TSU_KERNEL_SMALL && !small_supported(L))
-        return tsu_fail(L->ctx, TSU_E_UNSUPPORTED, "ising2d_set_kernel: the one-workgroup kernel takes whole lattices of at most 1024 octets (rows x ceil(cols/16))");
+    const int prev = L->kernel;
     L->kernel = kernel;
+    if (k1_path(L, TSU_PART_ALL) == K1_NONE) {
+        L->kernel = prev;
+        return tsu_fail(L->ctx, TSU_E_UNSUPPORTED, kernel == TSU_KERNEL_TILED ? "ising2d_set_kernel: tiled kernel does not support this lattice"
+                                                                               : "ising2d_set_kernel: the one-workgroup kernel takes whole lattices of at most 1024 octets (rows x ceil(cols/16))");
+    }
     L->sweeps_per_launch = sweeps_per_launch;
     return TSU_OK;
 }
@@ -614,42 +547,20 @@ int tsu_ising2d_sweep_part(tsu_ising2d* L, int n_sweeps, uint64_t seed, uint32_t
                 "ising2d_sweep: %d sweeps need %d ghost rows, slab has %d", n_sweeps, 2 * n_sweeps, L->ghost);
     if (n_sweeps == 0) return TSU_OK;
     if (L->timing) TSU_HIP_TRY(ctx, hipEventRecord(L->ev0, ctx->stream));
-    // AUTO: a lattice that fits one workgroup's LDS runs all its sweeps in one launch; larger ones take the tiled
-    // kernel where it applies, the generic one otherwise
-    const int use_small = part == TSU_PART_ALL && ((L->kernel == TSU_KERNEL_SMALL) || (L->kernel == TSU_KERNEL_AUTO && small_supported(L)));
-    int use_tiled = !use_small && ((L->kernel == TSU_KERNEL_TILED) || (L->kernel == TSU_KERNEL_AUTO && tsu_ising2d_tiled_supported(L)));
-    if (part != TSU_PART_ALL && !(use_tiled && tsu_ising2d_tiled_part_supported(L)))
+    const int path = k1_path(L, part);
+    if (part != TSU_PART_ALL && !(path == K1_TILED && tsu_ising2d_tiled_part_supported(L)))
         return tsu_fail(ctx, TSU_E_UNSUPPORTED, "ising2d_sweep_part: split sweeps need a slab on the tiled kernel with rows %% 64 == 0");
-    if (use_small && tsu_ising2d_planes_supported(L)) {
-        // colour planes in LDS, packed-byte update (ising2d_tiled.hip); k1_small below keeps the shapes it does not take
+    if (path == K1_PLANES) {
         int rc = tsu_ising2d_planes_sweep(&L, 1, n_sweeps, &seed, &sweep0, &replica);
         if (rc != TSU_OK) return rc;
-    } else if (use_small) {
-        K1Params p = make_params(L, L->alloc[L->cur]);
-        K1Table tbl;
-        memcpy(tbl.t, L->table, sizeof(tbl.t));
-        p.k0 = (uint32_t)seed;
-        p.k1 = (uint32_t)(seed >> 32);
-        p.tag_hi = TSU_TAG_ISING_HI | (replica << 8);
-        p.tag_lo = TSU_TAG_ISING_LO | (replica << 8);
-        const int nchunks = (L->cols + 15) >> 4, tasks = L->rows * nchunks;
-        const unsigned threads = tasks >= 1024 ? 1024u : (unsigned)((tasks + 63) / 64 * 64);
-        const size_t lds_bytes = (size_t)tasks * 16;
-        TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)k1_small, 128 * 1024));
-        k1_small<<<1, threads, lds_bytes, ctx->stream>>>(p, tbl, sweep0, n_sweeps);
-        L->launches += 1;
-        TSU_HIP_TRY(ctx, hipGetLastError());
-    } else if (use_tiled) {
+    } else if (path == K1_TILED) {
         int rc = tsu_ising2d_tiled_sweep(L, n_sweeps, seed, sweep0, replica, part);
         if (rc != TSU_OK) return rc;
     } else {
         K1Params p = make_params(L, L->alloc[L->cur]);
         K1Table tbl;
         memcpy(tbl.t, L->table, sizeof(tbl.t));
-        p.k0 = (uint32_t)seed;
-        p.k1 = (uint32_t)(seed >> 32);
-        p.tag_hi = TSU_TAG_ISING_HI | (replica << 8);
-        p.tag_lo = TSU_TAG_ISING_LO | (replica << 8);
+        ising2d_set_keys(p, seed, replica);
         int half = 0;  // half-sweeps since the ghost rows were fresh
         const bool top_edge = !L->periodic && L->row0 <= L->ghost;
         const bool bot_edge = !L->periodic && L->total_rows - (L->row0 + L->rows) <= L->ghost;
@@ -753,94 +664,59 @@ int tsu_ising2d_sweep_batch(tsu_ising2d* const* lats, int n_lats, int n_sweeps, 
     tsu_ctx* ctx = lats[0]->ctx;
     TSU_REQUIRE(ctx, seeds && sweep0s && replicas, "ising2d_sweep_batch: seeds, sweep0s and replicas are per-lattice arrays");
     TSU_REQUIRE(ctx, n_sweeps >= 0, "ising2d_sweep: n_sweeps must be >= 0");
-    bool one_launch = true;
+    bool one_launch = true;  // every lattice on k1_planes, all of one shape and boundary: one launch, one workgroup each
     for (int i = 0; i < n_lats; ++i) {
         tsu_ising2d* L = lats[i];
         TSU_REQUIRE(ctx, L && L->ctx == ctx, "ising2d_sweep_batch: lattice %d is NULL or belongs to another context", i);
         TSU_REQUIRE(ctx, L->have_table, "ising2d_sweep: call tsu_ising2d_set_model / set_thresholds first");
         TSU_REQUIRE(ctx, (uint64_t)sweep0s[i] + (uint64_t)n_sweeps <= (1ull << 31), "ising2d_sweep: sweep counter overflow");
-        one_launch = one_launch && small_supported(L) && L->rows == lats[0]->rows && L->cols == lats[0]->cols &&
-                     (L->kernel == TSU_KERNEL_AUTO || L->kernel == TSU_KERNEL_SMALL);
+        one_launch = one_launch && k1_path(L, TSU_PART_ALL) == K1_PLANES && L->rows == lats[0]->rows && L->cols == lats[0]->cols &&
+                     L->periodic == lats[0]->periodic;
     }
     if (n_sweeps == 0) return TSU_OK;
-    if (!one_launch) {
-        // larger lattices: each lattice's launches go to one of a few side streams, so that lattices which do not fill
-        // the chip on their own (a 1024^2 lattice keeps 128 CUs busy) run side by side.  Fork / join with events
-        // on the context's stream, which therefore sees the batch as one ordered operation.
-        if (ctx->pool_n == 0) {
-            TSU_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
-            for (int i = 0; i < 8; ++i) {
-                TSU_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->pool[i], hipStreamNonBlocking));
-                TSU_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pool_ev[i], hipEventDisableTiming));
-                ctx->pool_n = i + 1;
-            }
+    if (one_launch) return tsu_ising2d_planes_sweep(lats, n_lats, n_sweeps, seeds, sweep0s, replicas);
+    // everything else: each lattice's launches go to one of a few side streams, so that lattices which do not fill
+    // the chip on their own (a 1024^2 lattice keeps 128 CUs busy) run side by side.  Fork / join with events
+    // on the context's stream, which therefore sees the batch as one ordered operation.
+    if (ctx->pool_n == 0) {
+        TSU_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
+        for (int i = 0; i < 8; ++i) {
+            TSU_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->pool[i], hipStreamNonBlocking));
+            TSU_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->pool_ev[i], hipEventDisableTiming));
+            ctx->pool_n = i + 1;
         }
-        hipStream_t main_stream = ctx->stream;
-        TSU_HIP_TRY(ctx, hipEventRecord(ctx->fork_ev, main_stream));
-        // Tile-resident launches wait inside the kernel for all of their workgroups: never have more of them in flight
-        // than fit the chip together (one workgroup per CU counted), or two half-placed grids could wait for each other.
-        int max_tiles = 0;
-        ctx->in_batch = 1;  // (the tile plan of a lattice in a batch differs from that of a lattice on its own: see tile_plan)
-        for (int i = 0; i < n_lats; ++i) {
-            const int t = tsu_ising2d_tiled_tiles(lats[i]);
-            if (t > max_tiles) max_tiles = t;
-        }
-        ctx->in_batch = 0;
-        int used = n_lats < ctx->pool_n ? n_lats : ctx->pool_n;
-        if (max_tiles > 0) {
-            const int fit = ctx->cus / max_tiles;
-            if (used > fit) used = fit < 1 ? 1 : fit;
-        }
-        for (int i = 0; i < used; ++i) TSU_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pool[i], ctx->fork_ev, 0));
-        int rc = TSU_OK;
-        ctx->in_batch = 1;
-        for (int i = 0; i < n_lats && rc == TSU_OK; ++i) {
-            ctx->stream = ctx->pool[i % used];
-            rc = tsu_ising2d_sweep(lats[i], n_sweeps, seeds[i], sweep0s[i], replicas[i]);
-        }
-        ctx->in_batch = 0;
-        ctx->stream = main_stream;
-        for (int i = 0; i < used; ++i) {
-            hipError_t e = hipEventRecord(ctx->pool_ev[i], ctx->pool[i]);
-            if (e == hipSuccess) e = hipStreamWaitEvent(main_stream, ctx->pool_ev[i], 0);
-            if (e != hipSuccess && rc == TSU_OK) rc = tsu_fail(ctx, TSU_E_HIP, "ising2d_sweep_batch: %s", hipGetErrorString(e));
-        }
-        return rc;
     }
-    bool planes = true;
-    for (int i = 0; i < n_lats; ++i) planes = planes && tsu_ising2d_planes_supported(lats[i]) && lats[i]->periodic == lats[0]->periodic;
-    if (planes) return tsu_ising2d_planes_sweep(lats, n_lats, n_sweeps, seeds, sweep0s, replicas);
-    std::vector<K1BatchItem> items((size_t)n_lats);
+    hipStream_t main_stream = ctx->stream;
+    TSU_HIP_TRY(ctx, hipEventRecord(ctx->fork_ev, main_stream));
+    // Tile-resident launches wait inside the kernel for all of their workgroups: never have more of them in flight
+    // than fit the chip together (one workgroup per CU counted), or two half-placed grids could wait for each other.
+    int max_tiles = 0;
+    ctx->in_batch = 1;  // (the tile plan of a lattice in a batch differs from that of a lattice on its own: see plan_call)
     for (int i = 0; i < n_lats; ++i) {
-        tsu_ising2d* L = lats[i];
-        K1BatchItem& it = items[(size_t)i];
-        it.p = make_params(L, L->alloc[L->cur]);
-        memcpy(it.tbl.t, L->table, sizeof(it.tbl.t));
-        it.p.k0 = (uint32_t)seeds[i];
-        it.p.k1 = (uint32_t)(seeds[i] >> 32);
-        it.p.tag_hi = TSU_TAG_ISING_HI | (replicas[i] << 8);
-        it.p.tag_lo = TSU_TAG_ISING_LO | (replicas[i] << 8);
-        it.sweep0 = sweep0s[i];
+        const int t = tsu_ising2d_tiled_tiles(lats[i]);
+        if (t > max_tiles) max_tiles = t;
     }
-    const size_t bytes = items.size() * sizeof(K1BatchItem);
-    tsu_ising2d* L0 = lats[0];  // the staging buffer for the items lives with the first lattice of the batch
-    if (L0->batch_cap < bytes) {
-        if (L0->d_batch) (void)hipFree(L0->d_batch);
-        L0->d_batch = nullptr;
-        L0->batch_cap = 0;
-        TSU_HIP_TRY(ctx, hipMalloc(&L0->d_batch, bytes));
-        L0->batch_cap = bytes;
+    ctx->in_batch = 0;
+    int used = n_lats < ctx->pool_n ? n_lats : ctx->pool_n;
+    if (max_tiles > 0) {
+        const int fit = ctx->cus / max_tiles;
+        if (used > fit) used = fit < 1 ? 1 : fit;
     }
-    // stream order keeps a previous batch launch from still reading the buffer; the host array dies with this call, so
-    // the copy is waited for (a few KB); the launch itself stays asynchronous
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(L0->d_batch, items.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const int nchunks = (lats[0]->cols + 15) >> 4, tasks = lats[0]->rows * nchunks;
-    const unsigned threads = tasks >= 1024 ? 1024u : (unsigned)((tasks + 63) / 64 * 64);
-    k1_small_batch<<<(unsigned)n_lats, threads, (size_t)tasks * 16, ctx->stream>>>((const K1BatchItem*)L0->d_batch, n_sweeps);
-    TSU_HIP_TRY(ctx, hipGetLastError());
-    for (int i = 0; i < n_lats; ++i) lats[i]->launches += 1;
-    return TSU_OK;
+    for (int i = 0; i < used; ++i) TSU_HIP_TRY(ctx, hipStreamWaitEvent(ctx->pool[i], ctx->fork_ev, 0));
+    int rc = TSU_OK;
+    ctx->in_batch = 1;
+    for (int i = 0; i < n_lats && rc == TSU_OK; ++i) {
+        ctx->stream = ctx->pool[i % used];
+        rc = tsu_ising2d_sweep(lats[i], n_sweeps, seeds[i], sweep0s[i], replicas[i]);
+    }
+    ctx->in_batch = 0;
+    ctx->stream = main_stream;
+    for (int i = 0; i < used; ++i) {
+        hipError_t e = hipEventRecord(ctx->pool_ev[i], ctx->pool[i]);
+        if (e == hipSuccess) e = hipStreamWaitEvent(main_stream, ctx->pool_ev[i], 0);
+        if (e != hipSuccess && rc == TSU_OK) rc = tsu_fail(ctx, TSU_E_HIP, "ising2d_sweep_batch: %s", hipGetErrorString(e));
+    }
+    return rc;
 }
 
 int tsu_ising2d_observables_batch(tsu_ising2d* const* lats, int n_lats, int64_t* sum_s, int64_t* sum_bonds) {
@@ -852,13 +728,7 @@ int tsu_ising2d_observables_batch(tsu_ising2d* const* lats, int n_lats, int64_t*
     // one accumulator array for the batch (with its first lattice): one memset, one launch per lattice, one copy back
     tsu_ising2d* L0 = lats[0];
     const size_t bytes = h.size() * sizeof(int64_t);
-    if (L0->obs_batch_cap < bytes) {
-        if (L0->d_obs_batch) (void)hipFree(L0->d_obs_batch);
-        L0->d_obs_batch = nullptr;
-        L0->obs_batch_cap = 0;
-        TSU_HIP_TRY(ctx, hipMalloc(&L0->d_obs_batch, bytes));
-        L0->obs_batch_cap = bytes;
-    }
+    TSU_HIP_TRY(ctx, ising2d_grow(L0->d_obs_batch, L0->obs_batch_cap, bytes));
     TSU_HIP_TRY(ctx, hipMemsetAsync(L0->d_obs_batch, 0, bytes, ctx->stream));
     for (int i = 0; i < n_lats; ++i) {
         tsu_ising2d* L = lats[i];

@@ -840,7 +840,7 @@ struct TileVariant {
     void (*open)(TiledParams);       // open-boundary form (nullptr: not built for this shape)
     void (*resident_open)(ResidentLaunch);
     int nib;                         // colour planes at 4 bits per site (periodic lattices, width a multiple of 16)
-    int per_cu;                      // workgroups of this shape one CU is meant to hold (LDS share of a stretched slab tile)
+    int per_cu;                      // workgroups of this shape one CU is meant to hold (tiles per round; LDS share of a stretched tile)
 };
 
 // LDS of one workgroup: guard octet, two colour planes of TR x NO octets (+ one spare row), 25 thresholds
@@ -848,20 +848,20 @@ size_t tile_lds_bytes(const TileVariant& tv, int TR) {
     const size_t es = tv.nib ? 4 : 8, NO = (size_t)tv.WO + 2;
     return 8 + (((size_t)2 * TR * NO + NO + 1) * es + 7) / 8 * 8 + 8 + 25 * sizeof(uint64_t);
 }
-// the tile shapes the chooser (pick_variant) can reach.  Round 1's table had 32 entries, 24 of them reachable only through
+// the tile shapes the chooser (plan_call) can reach.  Round 1's table had 32 entries, 24 of them reachable only through
 // the TSU_TILE_VARIANT development switch; numbers quoted in profiles/r01_* map as 6 -> 0, 8 -> 1, 9 -> 2, 22 -> 3, 23 -> 4,
 // 25 -> 5, 26 -> 6, 27 -> 7
 enum { V_64x512_T512 = 0, V_128x512_T512, V_128x512_T1024, V_256x512_T1024, V_128x256_T1024, V_64x512_T1024, V_64x256_T1024, V_32x256_T1024,
        V_N512x512_T1024, V_N256x512_T512 };
 const TileVariant kVariants[] = {
-    {64, 32, 512, k1_tiled2<64, 32, 512>, k1_resident<64, 32, 512>, k1_tiled2<64, 32, 512, 1, true>},
-    {128, 32, 512, k1_tiled2<128, 32, 512>, k1_resident<128, 32, 512>, k1_tiled2<128, 32, 512, 1, true>},
-    {128, 32, 1024, k1_tiled2<128, 32, 1024>, k1_resident<128, 32, 1024>, k1_tiled2<128, 32, 1024, 1, true>, k1_resident<128, 32, 1024, 1, true>},
-    {256, 32, 1024, k1_tiled2<256, 32, 1024, 4>, k1_resident<256, 32, 1024, 4>, k1_tiled2<256, 32, 1024, 4, true>, k1_resident<256, 32, 1024, 4, true>},  // one 148 KB workgroup per CU
-    {128, 16, 1024, k1_tiled2<128, 16, 1024>, k1_resident<128, 16, 1024>, k1_tiled2<128, 16, 1024, 1, true>, k1_resident<128, 16, 1024, 1, true>},  // narrower tiles for mid-size lattices
-    {64, 32, 1024, k1_tiled2<64, 32, 1024>, k1_resident<64, 32, 1024>, k1_tiled2<64, 32, 1024, 1, true>, k1_resident<64, 32, 1024, 1, true>},
-    {64, 16, 1024, k1_tiled2<64, 16, 1024>, k1_resident<64, 16, 1024>, k1_tiled2<64, 16, 1024, 1, true>, k1_resident<64, 16, 1024, 1, true>},
-    {32, 16, 1024, k1_tiled2<32, 16, 1024>, k1_resident<32, 16, 1024>, k1_tiled2<32, 16, 1024, 1, true>, k1_resident<32, 16, 1024, 1, true>},
+    {64, 32, 512, k1_tiled2<64, 32, 512>, k1_resident<64, 32, 512>, k1_tiled2<64, 32, 512, 1, true>, nullptr, 0, 2},
+    {128, 32, 512, k1_tiled2<128, 32, 512>, k1_resident<128, 32, 512>, k1_tiled2<128, 32, 512, 1, true>, nullptr, 0, 2},
+    {128, 32, 1024, k1_tiled2<128, 32, 1024>, k1_resident<128, 32, 1024>, k1_tiled2<128, 32, 1024, 1, true>, k1_resident<128, 32, 1024, 1, true>, 0, 1},
+    {256, 32, 1024, k1_tiled2<256, 32, 1024, 4>, k1_resident<256, 32, 1024, 4>, k1_tiled2<256, 32, 1024, 4, true>, k1_resident<256, 32, 1024, 4, true>, 0, 1},  // one 148 KB workgroup per CU
+    {128, 16, 1024, k1_tiled2<128, 16, 1024>, k1_resident<128, 16, 1024>, k1_tiled2<128, 16, 1024, 1, true>, k1_resident<128, 16, 1024, 1, true>, 0, 1},  // narrower tiles for mid-size lattices
+    {64, 32, 1024, k1_tiled2<64, 32, 1024>, k1_resident<64, 32, 1024>, k1_tiled2<64, 32, 1024, 1, true>, k1_resident<64, 32, 1024, 1, true>, 0, 1},
+    {64, 16, 1024, k1_tiled2<64, 16, 1024>, k1_resident<64, 16, 1024>, k1_tiled2<64, 16, 1024, 1, true>, k1_resident<64, 16, 1024, 1, true>, 0, 1},
+    {32, 16, 1024, k1_tiled2<32, 16, 1024>, k1_resident<32, 16, 1024>, k1_tiled2<32, 16, 1024, 1, true>, k1_resident<32, 16, 1024, 1, true>, 0, 1},
     // nibble planes: 512 x 512 sites per CU (148 KB) -- 8192^2 tile-resident; 256 x 512, two workgroups per CU, for what is larger still
     {512, 32, 1024, k1_tiled2<512, 32, 1024, 4, false, true>, k1_resident<512, 32, 1024, 4, false, true>, k1_tiled2<512, 32, 1024, 4, true, true>,
      k1_resident<512, 32, 1024, 4, true, true>, 1, 1},
@@ -888,36 +888,62 @@ int ragged_shift(const tsu_ising2d* L, int WO) {
     return -1;
 }
 
+// LDS of one workgroup of this shape when per_cu of them share a CU
+size_t lds_share(const TileVariant& tv) { return (size_t)(160 / tv.per_cu) * 1024; }
+
+// CUs of the lattice's device (256 when unknown)
+int chip_cus(const tsu_ising2d* L) { return L->ctx->cus > 0 ? L->ctx->cus : 256; }
+
+// an integer switch from the environment (unset: dflt)
+int lattice_env(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+// Generation time (us) of k = 8 sweeps on tiles of h rows, fitted to measurements (4096^2, 2048^2, 1024^2, 4096 x 8192, open
+// 1000^2; profiles/r01_k1_experiments.txt): a half-sweep costs 0.25 us + 0.225 us per wave-iteration of the busiest SIMD (6 %
+// more on nibble planes); between generations `between` us: the strip exchange costs 4.3 us when the tiles stay resident in LDS,
+// the tile store + launch gap + stage about 12 us when they do not.
+double gen_time_us(const TileVariant& c, int h, double between) {
+    const int pairs = (h + 4 * 8 - 2) / 2, waves = (pairs * (c.WO + 2) + 63) / 64;
+    return 16.0 * (0.25 + (c.nib ? 1.06 : 1.0) * 0.225 * ((waves + 3) / 4)) + between;
+}
+
+// thresholds of a TiledParams / PlanesItem: the full table (tie path) and its top 16 bits, min(thr >> 16, 65535) ^ 0x8000, as byte
+// tables for degree 4 (tbl*) and, for open lattices, degree 3 (t3*, entries 0..3) and degree 2 (entries 4..6)
+template <typename P>
+void pack_thresholds(P& p, const uint64_t table[25]) {
+    for (int c = 0; c < 25; ++c) p.thr[c] = table[c];
+    auto top16 = [](uint64_t thr) {
+        uint32_t thi = (uint32_t)(thr >> 16);
+        if (thi > 65535u) thi = 65535u;
+        return thi ^ 0x8000u;
+    };
+    uint32_t t16[5], t3[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int c = 0; c < 5; ++c) t16[c] = top16(table[4 * 5 + c]);
+    for (int c = 0; c < 4; ++c) t3[c] = top16(table[3 * 5 + c]);      // degree 3: an edge
+    for (int c = 0; c < 3; ++c) t3[4 + c] = top16(table[2 * 5 + c]);  // degree 2: a corner
+    p.t3L0 = (t3[0] & 0xFF) | ((t3[1] & 0xFF) << 8) | ((t3[2] & 0xFF) << 16) | ((t3[3] & 0xFF) << 24);
+    p.t3L1 = (t3[4] & 0xFF) | ((t3[5] & 0xFF) << 8) | ((t3[6] & 0xFF) << 16);
+    p.t3H0 = (t3[0] >> 8) | ((t3[1] >> 8) << 8) | ((t3[2] >> 8) << 16) | ((t3[3] >> 8) << 24);
+    p.t3H1 = (t3[4] >> 8) | ((t3[5] >> 8) << 8) | ((t3[6] >> 8) << 16);
+    p.tblL0 = (t16[0] & 0xFF) | ((t16[1] & 0xFF) << 8) | ((t16[2] & 0xFF) << 16) | ((t16[3] & 0xFF) << 24);
+    p.tblL1 = (t16[4] & 0xFF);
+    p.tblH0 = (t16[0] >> 8) | ((t16[1] >> 8) << 8) | ((t16[2] >> 8) << 16) | ((t16[3] >> 8) << 24);
+    p.tblH1 = (t16[4] >> 8);
+}
+
 // Tile-resident runs of whole lattices of any shape (flexible cut; periodic ones need even height and width): the rows are
 // cut into tiles_y tile rows of (nearly) equal even heights and the last tile column may hold fewer octets than the others, so
 // the lattice need not divide into whole tiles.  As many tile rows as the chip has room for (every tile needs its own
-// workgroup; more tiles = shorter tiles = a shorter generation), the tile shape by the generation-time model of pick_variant.
+// workgroup; more tiles = shorter tiles = a shorter generation), the tile shape by the generation-time model.
 // Returns tiles_y (0: no such cut) for variant v, or searches the variants when v < 0 and returns the best through *v_out.
-int flex_plan(const tsu_ising2d* L, int v, int* v_out, int* hmax_out, double* t_out = nullptr) {
-    static int flexible = -1;
-    if (flexible < 0) {
-        const char* e = getenv("TSU_K1_FLEX_TILES");
-        flexible = e ? atoi(e) : 1;
-    }
-    if (!flexible || L->ghost != 0 || L->total_rows != L->rows) return 0;
+int flex_cut(const tsu_ising2d* L, int v, int* v_out, int* hmax_out, double* t_out) {
+    if (L->ghost != 0 || L->total_rows != L->rows) return 0;
     if (L->periodic && ((L->cols & 1) || (L->rows & 1))) return 0;  // (odd periodic lattices are not bipartite: generic kernel)
-    static int use_nib = -1;
-    if (use_nib < 0) {
-        const char* e = getenv("TSU_K1_NIBBLE");
-        use_nib = e ? atoi(e) : 1;
-    }
-    static int FLEX_HMIN = -1;  // shortest tile row of a cut (the strips are 2k = 16 rows deep)
-    if (FLEX_HMIN < 0) {
-        const char* e = getenv("TSU_K1_FLEX_HMIN");
-        FLEX_HMIN = e ? atoi(e) : 16;
-        if (FLEX_HMIN < 16) FLEX_HMIN = 16;
-    }
-    static int max_tiles = -1;  // development / test switch: pretend the chip has room for this many tiles only
-    if (max_tiles < 0) {
-        const char* e = getenv("TSU_K1_FLEX_MAX_TILES");
-        max_tiles = e ? atoi(e) : 0;
-    }
-    int cus = L->ctx->cus > 0 ? L->ctx->cus : 256;
+    const int FLEX_HMIN = 16;  // shortest tile row of a cut (the strips are 2k = 16 rows deep)
+    static const int max_tiles = lattice_env("TSU_K1_FLEX_MAX_TILES", 0);  // test switch: pretend the chip has room for this many tiles only
+    int cus = chip_cus(L);
     if (max_tiles > 0 && max_tiles < cus) cus = max_tiles;
     const int nch = (L->cols + 15) / 16;
     static const int cand[] = {V_256x512_T1024, V_128x256_T1024, V_N512x512_T1024};
@@ -926,7 +952,7 @@ int flex_plan(const tsu_ising2d* L, int v, int* v_out, int* hmax_out, double* t_
     for (int ci = 0; ci < (int)(sizeof(cand) / sizeof(cand[0])); ++ci) {
         if (v >= 0 && cand[ci] != v) continue;
         const TileVariant& c = kVariants[cand[ci]];
-        if (!(L->periodic ? c.resident : c.resident_open) || (c.nib && !use_nib) || 2 * nch < c.WO || ragged_shift(L, c.WO) < 0) continue;
+        if (!(L->periodic ? c.resident : c.resident_open) || 2 * nch < c.WO || ragged_shift(L, c.WO) < 0) continue;
         // (an open lattice may have an odd number of rows: the cut is made over rows + 1, the last tile row holds one row less)
         const int tiles_x = (nch + c.WO - 1) / c.WO, half = (L->rows + 1) / 2;
         int tiles_y = cus / tiles_x;
@@ -934,81 +960,69 @@ int flex_plan(const tsu_ising2d* L, int v, int* v_out, int* hmax_out, double* t_
         if (tiles_y < 1) continue;
         const int hmax = 2 * ((half + tiles_y - 1) / tiles_y), hmin = 2 * (half / tiles_y);
         if (hmin < FLEX_HMIN || L->total_rows < hmax + 4 * KMAX || tile_lds_bytes(c, hmax + 4 * KMAX) > 160 * 1024) continue;
-        const int pairs = (hmax + 4 * 8 - 2) / 2, waves = (pairs * (c.WO + 2) + 63) / 64;
-        const double t_gen = 16.0 * (0.25 + (c.nib ? 1.06 : 1.0) * 0.225 * ((waves + 3) / 4)) + 4.3;
+        const double t_gen = gen_time_us(c, hmax, 4.3);
         if (t_gen < best) {
             best = t_gen;
             best_ty = tiles_y;
-            if (v_out) *v_out = cand[ci];
-            if (hmax_out) *hmax_out = hmax;
+            *v_out = cand[ci];
+            *hmax_out = hmax;
         }
     }
-    if (t_out) *t_out = best;
+    *t_out = best;
     return best_ty;
 }
 
-struct TilePlan {
-    int v;        // index into kVariants, -1: none fits (generic kernel)
-    int flex_ty;  // > 0: tile-resident runs use the flexible cut with this many tile rows ...
-    int flex_h;   // ... whose tallest is this high
+// Everything a tiled call of n_sweeps sweeps over `part` needs.  The first half is the lattice's: its tile shape and flexible cut
+// (tsu_ising2d_tiled_tiles / _supported / _part_supported read those); the second half the call's.
+struct CallPlan {
+    int v;                // index into kVariants; -1: no tile shape fits (the generic kernel takes the lattice)
+    int flex_ty, flex_h;  // the lattice's flexible cut: tile rows and the tallest of them (0: none; whole lattices only)
+    int kmax;             // sweeps per launch, or per generation of a tile-resident run
+    bool resident;        // tile-resident generations, if every tile finds its workgroup on the chip (checked at launch)
+    int tile_h, tiles_y;  // the resident run's tiles: the flexible cut, whole tiles, or a slab's tiles stretched over ...
+    int res_ext;          // ... this many ghost rows on each side
 };
 
-TilePlan tile_plan(const tsu_ising2d* L) {
-    int flex_ty = 0, flex_h = 0;
-    static int env = -2;
-    if (env == -2) {
-        const char* e = getenv("TSU_TILE_VARIANT");
-        env = e ? atoi(e) : -1;
-    }
+CallPlan plan_call(const tsu_ising2d* L, int n_sweeps, int part) {
+    CallPlan c{};
+    static const int env = lattice_env("TSU_TILE_VARIANT", -1);  // test switch: force a tile shape
+    const bool forced = env >= 0 && env < kNumVariants;
+    const int cus = chip_cus(L), nch = (L->cols + 15) / 16;
+    const bool whole_lattice = L->ghost == 0 && L->total_rows == L->rows;
     int v;
-    if (env >= 0 && env < kNumVariants) {
+    if (forced) {
         v = env;
     } else {
         // measured on MI355X (profiles/r01_k1_experiments.txt): 128-row tiles with two 512-thread workgroups per CU
         // when the lattice gives every CU several tiles; a lattice with at most one such tile per CU needs all 16
         // waves of the CU in one workgroup; one with ABOUT TWO per CU (2048 x 16384, 4096 x 8192: everything starts
         // and ends together, nothing hides the stage/store phases) does better with 256-row tiles, one per CU
-        const int cus = L->ctx->cus > 0 ? L->ctx->cus : 256;
-        const long long tx = (((L->cols + 15) / 16) + 31) / 32;
+        const long long tx = (nch + 31) / 32;
         const long long n128 = ((L->rows + 127) / 128) * tx, n256 = ((L->rows + 255) / 256) * tx;
         if (n128 <= cus) v = V_128x512_T1024;
         else if (n128 <= 2 * cus && n256 <= cus && 10 * n256 >= 7 * cus) v = V_256x512_T1024;
         else v = V_128x512_T512;
         if (L->rows < 256) v = V_64x512_T512;
-        // Nibble planes (whole periodic lattices, width a multiple of 16): a lattice of exactly one 512 x 512 tile per CU
-        // (8192^2 on 256 CUs) stays resident in LDS; larger lattices take 256 x 512 tiles, two workgroups per CU, 8 sweeps
-        // per launch (half the halo rows of the 128-row byte tiles and fewer stage/store passes)
-        static int use_nib = -1;
-        if (use_nib < 0) {
-            const char* e = getenv("TSU_K1_NIBBLE");
-            use_nib = e ? atoi(e) : 1;
-        }
-        // (any width: an open lattice's ragged last octet is masked like every site beyond the edge, a periodic one's takes the SEAM form)
-        const bool nib_ok = use_nib && L->ghost == 0 && L->total_rows == L->rows;
-        if (nib_ok && n128 > 2 * cus) {
-            const int nch_ = (L->cols + 15) / 16;
-            const long long n512 = (long long)(L->rows / 512) * (nch_ / 32);
-            if (L->rows % 512 == 0 && nch_ % 32 == 0 && n512 <= cus && 2 * n512 > cus) v = V_N512x512_T1024;
+        // Nibble planes (whole lattices; any width: an open lattice's ragged last octet is masked like every site beyond the
+        // edge, a periodic one's takes the SEAM form): a lattice of exactly one 512 x 512 tile per CU (8192^2 on 256 CUs) stays
+        // resident in LDS; larger lattices take 256 x 512 tiles, two workgroups per CU, 8 sweeps per launch (half the halo rows
+        // of the 128-row byte tiles and fewer stage/store passes)
+        if (whole_lattice && n128 > 2 * cus) {
+            const long long n512 = (long long)(L->rows / 512) * (nch / 32);
+            if (L->rows % 512 == 0 && nch % 32 == 0 && n512 <= cus && 2 * n512 > cus) v = V_N512x512_T1024;
             else if (L->rows >= 512) v = V_N256x512_T512;
         }
-        // Lattices that give every CU at most one tile: the tile shape that finishes a generation of 8 sweeps soonest.
-        // Model fitted to measurements (4096^2, 2048^2, 1024^2, 4096 x 8192, open 1000^2; profiles/r01_k1_experiments.txt):
-        // a half-sweep costs 0.25 us + 0.225 us per wave-iteration of the busiest SIMD; between generations the strip
-        // exchange costs 4.3 us when the tiles stay resident in LDS (the lattice divides into whole tiles), the tile
-        // store + launch gap + stage about 12 us when they do not.
+        // Lattices that give every CU at most one tile: the tile shape that finishes a generation of 8 sweeps soonest
         static const int cand[] = {V_256x512_T1024, V_128x512_T1024, V_128x256_T1024, V_64x512_T1024, V_64x256_T1024, V_32x256_T1024};
         double best = 1e30;
-        const bool whole = L->ghost == 0 && L->total_rows == L->rows;
-        const int nch = (L->cols + 15) / 16;
-        for (int ci = 0; whole && ci < (int)(sizeof(cand) / sizeof(cand[0])); ++ci) {
-            const TileVariant& c = kVariants[cand[ci]];
-            if (!(L->periodic ? c.kernel : c.open)) continue;
-            if (2 * nch < c.WO || L->total_rows < c.H + 4 * KMAX || ragged_shift(L, c.WO) < 0) continue;
-            const long long nt = (long long)((L->rows + c.H - 1) / c.H) * ((nch + c.WO - 1) / c.WO);
+        for (int ci = 0; whole_lattice && ci < (int)(sizeof(cand) / sizeof(cand[0])); ++ci) {
+            const TileVariant& t = kVariants[cand[ci]];
+            if (!(L->periodic ? t.kernel : t.open)) continue;
+            if (2 * nch < t.WO || L->total_rows < t.H + 4 * KMAX || ragged_shift(L, t.WO) < 0) continue;
+            const long long nt = (long long)((L->rows + t.H - 1) / t.H) * ((nch + t.WO - 1) / t.WO);
             if (nt > cus) continue;
-            const bool resident = (L->periodic ? c.resident : c.resident_open) && L->rows % c.H == 0 && nch % c.WO == 0;
-            const int pairs = (c.H + 4 * 8 - 2) / 2, waves = (pairs * (c.WO + 2) + 63) / 64;
-            const double t_gen = 16.0 * (0.25 + 0.225 * ((waves + 3) / 4)) + (resident ? 4.3 : 12.0);
+            const bool resident = (L->periodic ? t.resident : t.resident_open) && L->rows % t.H == 0 && nch % t.WO == 0;
+            const double t_gen = gen_time_us(t, t.H, resident ? 4.3 : 12.0);
             if (t_gen < best) {
                 best = t_gen;
                 v = cand[ci];
@@ -1020,361 +1034,252 @@ TilePlan tile_plan(const tsu_ising2d* L) {
     // ... and so does one that the pick above keeps resident in fewer, taller tiles than the chip has room for (6144^2 in 512-row
     // nibble tiles: 144 tiles on 256 CUs) when the model gives the flexible cut a generation that is at least 3 % shorter.
     {
-        const TileVariant& c = kVariants[v];
-        const int nch = (L->cols + 15) / 16, cus = L->ctx->cus > 0 ? L->ctx->cus : 256;
-        const long long nt = (long long)((L->rows + c.H - 1) / c.H) * ((nch + c.WO - 1) / c.WO);
-        const int per_cu = c.per_cu ? c.per_cu : (c.threads >= 1024 ? 1 : 2);
-        const bool divides = L->rows % c.H == 0 && nch % c.WO == 0;
-        const bool standard_resident = (L->periodic ? c.resident : c.resident_open) && divides && nt <= (long long)per_cu * cus;
-        const bool forced = env >= 0 && env < kNumVariants;
+        const TileVariant& t = kVariants[v];
+        const long long nt = (long long)((L->rows + t.H - 1) / t.H) * ((nch + t.WO - 1) / t.WO);
+        const bool divides = L->rows % t.H == 0 && nch % t.WO == 0;
+        const bool standard_resident = (L->periodic ? t.resident : t.resident_open) && divides && nt <= (long long)t.per_cu * cus;
         int fv = -1, fh = 0;
         double t_flex = 0;
-        const int fty = forced ? (divides ? 0 : flex_plan(L, v, &fv, &fh, &t_flex)) : flex_plan(L, -1, &fv, &fh, &t_flex);
+        const int fty = forced ? (divides ? 0 : flex_cut(L, v, &fv, &fh, &t_flex)) : flex_cut(L, -1, &fv, &fh, &t_flex);
         bool take = fty > 0 && !standard_resident;
         // a batch of lattices (a temperature scan on side streams) wants many lattices in flight, not the shortest generation of
         // one: lattices that leave half the chip to the others keep the tuned, compact shapes (32 temperatures at 1024^2: 120 ms;
         // with every lattice cut into 256 tiles 182 ms)
         const bool compact = L->ctx->in_batch && 2 * nt <= cus;
         if (compact) take = false;
-        if (fty > 0 && standard_resident && !forced && per_cu == 1 && !compact) {
-            const int pairs = (c.H + 4 * 8 - 2) / 2, waves = (pairs * (c.WO + 2) + 63) / 64;
-            const double t_std = 16.0 * (0.25 + (c.nib ? 1.06 : 1.0) * 0.225 * ((waves + 3) / 4)) + 4.3;
-            take = t_flex < 0.97 * t_std;
-        }
+        if (fty > 0 && standard_resident && !forced && t.per_cu == 1 && !compact) take = t_flex < 0.97 * gen_time_us(t, t.H, 4.3);
         if (take) {
             v = fv;
-            flex_ty = fty;
-            flex_h = fh;
+            c.flex_ty = fty;
+            c.flex_h = fh;
         }
     }
     // a variant must fit the lattice (a tile is a window on the lattice's periodic extension: its octet and row indices
     // wrap at most twice / once) and, for an open lattice, have the OPEN form built; -1 = none does (generic kernel)
     auto fits = [&](int vv) {
-        return 2 * ((L->cols + 15) / 16) >= kVariants[vv].WO && L->total_rows >= kVariants[vv].H + 4 * KMAX && (L->periodic || kVariants[vv].open) &&
+        return 2 * nch >= kVariants[vv].WO && L->total_rows >= kVariants[vv].H + 4 * KMAX && (L->periodic || kVariants[vv].open) &&
                ragged_shift(L, kVariants[vv].WO) >= 0;
     };
     if (!fits(v)) {
         static const int fallback[] = {V_64x512_T512, V_64x256_T1024, V_32x256_T1024};
         v = -1;
-        flex_ty = flex_h = 0;
+        c.flex_ty = c.flex_h = 0;
         for (int f : fallback)
             if (fits(f)) {
                 v = f;
                 break;
             }
     }
-    return TilePlan{v, flex_ty, flex_h};
-}
+    c.v = v;
+    if (v < 0) return c;
 
-int pick_variant(const tsu_ising2d* L) { return tile_plan(L).v; }
-// Tile height of a launch-per-k-sweeps run over a WHOLE lattice: any even height the variant's LDS share holds gives the same
-// results, so it is chosen for the schedule.  The chip runs `slots` tiles at a time and a tile costs about (th + 2k + 12) row
-// times (its trapezoid of halo rows, its stage and store), so a lattice costs ceil(tiles / slots) rounds of that: 10000^2 in
-// 256-row nibble tiles is 800 tiles on 512 slots -- two rounds, the second 56 % full; in 198-row tiles it is 1020 tiles, two
-// full rounds of shorter tiles (-21 %).  Lattices with fewer tiles than slots get shorter tiles so that every slot has one.
-int schedule_tile_h(const tsu_ising2d* L, const TileVariant& tv, int k, int tiles_x) {
-    static int flexible = -1;
-    if (flexible < 0) {
-        const char* e = getenv("TSU_K1_FLEX_TILES");
-        flexible = e ? atoi(e) : 1;
-    }
-    if (!flexible) return tv.H;
-    const int per_cu = tv.per_cu ? tv.per_cu : (tv.threads >= 1024 ? 1 : 2);
-    const long long slots = (long long)per_cu * (L->ctx->cus > 0 ? L->ctx->cus : 256);
-    const size_t lds_share = (size_t)(160 / per_cu) * 1024;
-    int best_th = tv.H;
-    double best = 1e300;
-    for (int th = 32; th <= 1024; th += 2) {
-        if (th + 4 * KMAX > L->total_rows || tile_lds_bytes(tv, th + 4 * k) > lds_share) continue;
-        const long long nt = (long long)((L->rows + th - 1) / th) * tiles_x, rounds = (nt + slots - 1) / slots;
-        const double cost = (double)rounds * (th + 2 * k + 12);
-        if (cost < best * (1.0 - 1e-9) || (cost <= best * (1.0 + 1e-9) && th > best_th)) {
-            best = cost;
-            best_th = th;
-        }
-    }
-    return best_th;
-}
-}  // namespace
-
-int tsu_ising2d_tiled_supported(const tsu_ising2d* L) {
-    if (pick_variant(L) < 0) return 0;                        // no tile shape fits (too narrow / too few rows): generic kernel
-    const bool open_whole = !L->periodic && L->ghost == 0 && L->total_rows == L->rows;  // beyond its edges: nothing
-    if (!L->wrap_rows && !open_whole && L->ghost < 2) return 0;
-    return 1;
-}
-
-// number of tiles (= workgroups of a tile-resident launch) the lattice is cut into; 0 if the tiled kernel does not apply
-int tsu_ising2d_tiled_tiles(const tsu_ising2d* L) {
-    if (!tsu_ising2d_tiled_supported(L)) return 0;
-    const TilePlan plan = tile_plan(L);
-    const TileVariant& tv = kVariants[plan.v];
-    const int tiles_x = (((L->cols + 15) / 16) + tv.WO - 1) / tv.WO;
-    return (plan.flex_ty > 0 ? plan.flex_ty : (L->rows + tv.H - 1) / tv.H) * tiles_x;
-}
-
-// split (interior / boundary) launches: ghost-row slabs whose tile rows are all full
-int tsu_ising2d_tiled_part_supported(const tsu_ising2d* L) {
-    return tsu_ising2d_tiled_supported(L) && !L->wrap_rows && (L->rows % kVariants[pick_variant(L)].H) == 0;
-}
-
-int tsu_ising2d_tiled_sweep(tsu_ising2d* L, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, int part) {
-    tsu_ctx* ctx = L->ctx;
-    const TilePlan plan = tile_plan(L);
-    const TileVariant& tv = kVariants[plan.v];
-    const int TILE_H = tv.H, TILE_WO = tv.WO;
-    if (!L->alloc[1]) {
-        size_t bytes = (size_t)(L->rows + 2 * L->ghost) * L->pitch;
-        TSU_HIP_TRY(ctx, hipMalloc(&L->alloc[1], bytes));
-        TSU_HIP_TRY(ctx, hipMemsetAsync(L->alloc[1], 0, bytes, ctx->stream));
-    }
+    const TileVariant& tv = kVariants[v];
     // sweeps per launch: more sweeps amortise the tile load/store and the launch gap, fewer carry less halo work
     // (one workgroup per CU, or a small lattice: 8; large lattices with two workgroups per CU that overlap each other's
     // stage/store phases: 5)
-    int kmax = L->sweeps_per_launch > 0 ? L->sweeps_per_launch
-                                        : ((tv.nib || tv.threads >= 1024 || (long long)L->rows * L->cols <= 4096ll * 4096ll) ? 8 : 5);
-    if (kmax > KMAX) kmax = KMAX;
-    const bool open_whole = !L->periodic && L->ghost == 0 && L->total_rows == L->rows;
-    const bool slab = !L->wrap_rows && !open_whole;
-    if (slab) {
-        // A slab may sweep ghost/2 times between two ghost refreshes.  When that takes several launches, every launch
-        // but the last also computes the ghost rows the following launches will read (2 rows per remaining sweep on
-        // each side, from input that is still exact there), instead of waiting for the neighbours.
-        TSU_REQUIRE(ctx, 2 * n_sweeps <= L->ghost, "ising2d_sweep (tiled, slab): %d sweeps per ghost refresh exceed ghost/2 = %d",
-                    n_sweeps, L->ghost / 2);
-        TSU_REQUIRE(ctx, part == TSU_PART_ALL || n_sweeps <= kmax, "ising2d_sweep_part: split sweeps take at most %d sweeps", kmax);
+    c.kmax = L->sweeps_per_launch > 0 ? L->sweeps_per_launch : ((tv.nib || tv.threads >= 1024 || (long long)L->rows * L->cols <= 4096ll * 4096ll) ? 8 : 5);
+    if (c.kmax > KMAX) c.kmax = KMAX;
+    c.tile_h = tv.H;
+    c.tiles_y = (L->rows + tv.H - 1) / tv.H;
+    static const int use_resident = lattice_env("TSU_K1_RESIDENT", 1);
+    c.resident = use_resident && (L->periodic ? tv.resident : tv.resident_open) && part == TSU_PART_ALL && n_sweeps > c.kmax;
+    const bool whole = L->wrap_rows || (!L->periodic && whole_lattice);
+    if (!c.resident) return c;
+    if (whole && c.flex_ty > 0) {  // the flexible cut: balanced tile rows, a partial last tile column
+        c.tile_h = c.flex_h;
+        c.tiles_y = c.flex_ty;
+    } else if (whole) {  // whole tiles of tv.H x tv.WO
+        c.resident = nch % tv.WO == 0 && L->rows % tv.H == 0;
+    } else {
+        // periodic slab: its tiles stretched over the ghost rows that the call's later generations need (uniform even height
+        // th, th * tiles_y = rows + 2 ext, 2 (n_sweeps - k) <= ext <= ghost)
+        const int need = L->rows + 4 * (n_sweeps - c.kmax);
+        int th = (need + c.tiles_y - 1) / c.tiles_y;
+        th += th & 1;
+        if (th < tv.H) th = tv.H;
+        const int extra = th * c.tiles_y - L->rows;
+        c.tile_h = th;
+        c.res_ext = extra / 2;
+        c.resident = nch % tv.WO == 0 && extra % 2 == 0 && c.res_ext <= L->ghost && tile_lds_bytes(tv, th + 4 * c.kmax) <= lds_share(tv);
     }
-    TiledParams p;
-    p.pitch = (long long)L->pitch;
-    p.rows = L->rows;
-    p.nchunks = (L->cols + 15) / 16;
-    p.cols = L->cols;
-    p.row0 = L->row0;
-    p.total_rows = L->total_rows;
-    p.wrap_rows = L->wrap_rows;
-    p.ghost = L->ghost;
-    p.tiles_x = (p.nchunks + TILE_WO - 1) / TILE_WO;
-    p.q_shift = ragged_shift(L, TILE_WO);
+    return c;
+}
+
+// Tile rows of one launch of k sweeps in the launch-per-generation form, `left` sweeps of the call still to do: sets p.tile_h,
+// p.r_begin and p.r_end and returns the number of tile rows.
+int launch_tiles(const tsu_ising2d* L, const TileVariant& tv, int k, int left, int part, bool slab, TiledParams& p) {
+    p.tile_h = tv.H;
     p.r_begin = 0;
     p.r_end = L->rows;
-    p.tile_h = TILE_H;
-    p.flex_ty = 0;
-    int tiles_y = (L->rows + TILE_H - 1) / TILE_H;
-    p.k0 = (uint32_t)seed;
-    p.k1 = (uint32_t)(seed >> 32);
-    p.tag_hi = TSU_TAG_ISING_HI | (replica << 8);
-    p.tag_lo = TSU_TAG_ISING_LO | (replica << 8);
-    for (int c = 0; c < 25; ++c) p.thr[c] = L->table[c];
-    p.open = L->periodic ? 0 : 1;
-    auto top16 = [](uint64_t thr) {
-        uint32_t thi = (uint32_t)(thr >> 16);
-        if (thi > 65535u) thi = 65535u;
-        return thi ^ 0x8000u;
-    };
-    uint32_t t16[5], t3[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int c = 0; c < 5; ++c) t16[c] = top16(L->table[4 * 5 + c]);
-    for (int c = 0; c < 4; ++c) t3[c] = top16(L->table[3 * 5 + c]);      // degree 3: an edge
-    for (int c = 0; c < 3; ++c) t3[4 + c] = top16(L->table[2 * 5 + c]);  // degree 2: a corner
-    p.t3L0 = (t3[0] & 0xFF) | ((t3[1] & 0xFF) << 8) | ((t3[2] & 0xFF) << 16) | ((t3[3] & 0xFF) << 24);
-    p.t3L1 = (t3[4] & 0xFF) | ((t3[5] & 0xFF) << 8) | ((t3[6] & 0xFF) << 16);
-    p.t3H0 = (t3[0] >> 8) | ((t3[1] >> 8) << 8) | ((t3[2] >> 8) << 16) | ((t3[3] >> 8) << 24);
-    p.t3H1 = (t3[4] >> 8) | ((t3[5] >> 8) << 8) | ((t3[6] >> 8) << 16);
-    p.tblL0 = (t16[0] & 0xFF) | ((t16[1] & 0xFF) << 8) | ((t16[2] & 0xFF) << 16) | ((t16[3] & 0xFF) << 24);
-    p.tblL1 = (t16[4] & 0xFF);
-    p.tblH0 = (t16[0] >> 8) | ((t16[1] >> 8) << 8) | ((t16[2] >> 8) << 16) | ((t16[3] >> 8) << 24);
-    p.tblH1 = (t16[4] >> 8);
-    void (*const kern)(TiledParams) = L->periodic ? tv.kernel : tv.open;
-    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)kern, 160 * 1024));
-    static int use_resident = -1;
-    if (use_resident < 0) {
-        const char* e = getenv("TSU_K1_RESIDENT");
-        use_resident = e ? atoi(e) : 1;
-    }
-    int ntiles = p.tiles_x * tiles_y;
-    // whole periodic lattice: tiles of TILE_H rows; periodic slab: its tiles stretched over the ghost rows that the call's
-    // later generations need (uniform even height th, th * tiles_y = rows + 2 ext, 2 (n_sweeps - k) <= ext <= ghost)
-    int res_th = TILE_H, res_ext = 0;
-    void (*const res_kern)(ResidentLaunch) = L->periodic ? tv.resident : tv.resident_open;
-    bool res_ok = use_resident && res_kern && part == TSU_PART_ALL && n_sweeps > kmax;
-    // whole lattice that does not divide into TILE_H x TILE_WO tiles: the flexible cut (balanced tile rows, partial last column)
-    const int flex_ty = res_ok && (L->wrap_rows || open_whole) ? plan.flex_ty : 0, flex_h = plan.flex_h;
-    if (flex_ty > 0) {
-        tiles_y = flex_ty;
-        ntiles = p.tiles_x * tiles_y;
-        res_th = flex_h;
-    } else if (res_ok) res_ok = p.nchunks % TILE_WO == 0;
-    if (flex_ty > 0) {
-        // (res_th = the tallest tile row of the cut)
-    } else if (res_ok && (L->wrap_rows || open_whole)) res_ok = L->rows % TILE_H == 0;
-    else if (res_ok) {
-        const int need = L->rows + 4 * (n_sweeps - kmax);
-        res_th = (need + tiles_y - 1) / tiles_y;
-        res_th += res_th & 1;
-        if (res_th < TILE_H) res_th = TILE_H;
-        const int extra = res_th * tiles_y - L->rows;
-        res_ext = extra / 2;
-        const size_t lds_share = (tv.per_cu ? 160u / (unsigned)tv.per_cu : (tv.threads >= 1024 ? 160u : 80u)) * 1024u;
-        const size_t lds_need = tile_lds_bytes(tv, res_th + 4 * kmax);
-        res_ok = (extra % 2 == 0) && res_ext <= L->ghost && lds_need <= lds_share;
-    }
-    if (res_ok) {
-        // ---- tile-resident generations: every tile has its own workgroup on the chip for the whole call
-        const int vi = (int)(&tv - kVariants);
-        const size_t lds_bytes = tile_lds_bytes(tv, res_th + 4 * kmax);
-        TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)res_kern, 160 * 1024));
-        int fit_per_cu = 0;
-        // (occupancy for the standard tile height; a stretched slab tile was checked against the variant's LDS share)
-        TSU_HIP_TRY(ctx, tsu_func_blocks_per_cu(ctx, (const void*)res_kern, tv.threads,
-                                                tile_lds_bytes(tv, (flex_ty > 0 ? res_th : TILE_H) + 4 * KMAX), &fit_per_cu));
-        if ((long long)ntiles <= (long long)fit_per_cu * ctx->cus) {
-            const size_t xstride = (size_t)2 * (2 * kmax * TILE_WO) + (size_t)2 * res_th;  // TOP, BOTTOM, LEFT, RIGHT of colour plane 1
-            const size_t xneed = (size_t)2 * ntiles * xstride;
-            if (L->xbuf_cap < xneed) {
-                if (L->d_xbuf) (void)hipFree(L->d_xbuf);
-                L->d_xbuf = nullptr;
-                L->xbuf_cap = 0;
-                TSU_HIP_TRY(ctx, hipMalloc(&L->d_xbuf, xneed * sizeof(uint64_t)));
-                L->xbuf_cap = xneed;
-                L->xsig = 0;  // fresh memory: cleared before its first use below
+    if (part != TSU_PART_ALL) return (L->rows + tv.H - 1) / tv.H;
+    if (!slab) {
+        // A whole lattice: any even height the variant's LDS share holds gives the same results, so it is chosen for the schedule.
+        // The chip runs `slots` tiles at a time and a tile costs about (th + 2k + 12) row times (its trapezoid of halo rows, its
+        // stage and store), so a lattice costs ceil(tiles / slots) rounds of that: 10000^2 in 256-row nibble tiles is 800 tiles on
+        // 512 slots -- two rounds, the second 56 % full; in 198-row tiles it is 1020 tiles, two full rounds of shorter tiles
+        // (-21 %).  Lattices with fewer tiles than slots get shorter tiles so that every slot has one.
+        const long long slots = (long long)tv.per_cu * chip_cus(L);
+        double best = 1e300;
+        for (int th = 32; th <= 1024; th += 2) {
+            if (th + 4 * KMAX > L->total_rows || tile_lds_bytes(tv, th + 4 * k) > lds_share(tv)) continue;
+            const long long nt = (long long)((L->rows + th - 1) / th) * p.tiles_x, rounds = (nt + slots - 1) / slots;
+            const double cost = (double)rounds * (th + 2 * k + 12);
+            if (cost < best * (1.0 - 1e-9) || (cost <= best * (1.0 + 1e-9) && th > p.tile_h)) {
+                best = cost;
+                p.tile_h = th;
             }
-            // strip layout of this call: the element numbering may only run on while it stays the same
-            const uint64_t xsig = ((uint64_t)(vi + 1) << 48) ^ ((uint64_t)ntiles << 28) ^ ((uint64_t)kmax << 20) ^ ((uint64_t)res_th << 4) ^ ((uint64_t)flex_ty << 36) ^ (uint64_t)p.open;
-            if (!L->h_err) {
-                TSU_HIP_TRY(ctx, hipHostMalloc(&L->h_err, sizeof(int), hipHostMallocMapped));
-                *L->h_err = 0;
-            }
-            int* d_err = nullptr;
-            TSU_HIP_TRY(ctx, hipHostGetDevicePointer((void**)&d_err, L->h_err, 0));
-            const char* vb = getenv("TSU_K1_VERBOSE");
-            // one launch per 1024 generations at most (a whole lattice may be asked for millions of sweeps; a slab's call
-            // is one refresh period anyway)
-            const int chunk_max = (L->wrap_rows || open_whole) ? 1024 * kmax : n_sweeps;
-            for (int done = 0; done < n_sweeps;) {
-                const int chunk = n_sweeps - done < chunk_max ? n_sweeps - done : chunk_max;
-                ResidentLaunch P;
-                p.k = kmax;
-                p.sweep0 = sweep0 + (uint32_t)done;
-                p.ty_first = 0;
-                p.ty_stride = 1;
-                p.src = L->alloc[L->cur] + (size_t)L->ghost * L->pitch;
-                p.dst = L->alloc[L->cur ^ 1] + (size_t)L->ghost * L->pitch;
-                p.tile_h = res_th;
-                p.flex_ty = flex_ty;
-                p.r_begin = -res_ext;
-                p.r_end = L->rows + res_ext;
-                P.t = p;
-                P.r.wrap_y = L->wrap_rows ? 1 : 0;
-                P.r.wrap_x = L->periodic ? 1 : 0;
-                P.r.xbuf = L->d_xbuf;
-                const bool renumber = L->xsig != xsig || L->xgen + (uint32_t)((chunk + kmax - 1) / kmax) + 2u >= 16383u;
-                if (renumber) {
-                    L->xsig = xsig;
-                    L->xgen = 0;
-                }
-                P.r.gen0 = L->xgen + 1u;
-                L->xgen += (uint32_t)((chunk + kmax - 1) / kmax);
-                P.r.err = d_err;
-                P.r.n_gen = (chunk + kmax - 1) / kmax;
-                P.r.k_last = chunk - (P.r.n_gen - 1) * kmax;
-                P.r.tiles_y = tiles_y;
-                P.r.dbg = nullptr;
-                long long* d_dbg = nullptr;
-                if (vb && atoi(vb) >= 2) {
-                    TSU_HIP_TRY(ctx, hipMalloc(&d_dbg, (size_t)4 * ntiles * sizeof(long long)));
-                    P.r.dbg = d_dbg;
-                }
-                if (vb)
-                    fprintf(stderr, "[tsu] k1_resident variant %d: %d tiles (%d per CU fit), %d generations of %d sweeps, %zu KB of strips\n",
-                            vi, ntiles, fit_per_cu, P.r.n_gen, kmax, xneed * 8 / 1024);
-                {
-                    const int rcx = tsu_grid_exclusive_begin(ctx);
-                    if (rcx != TSU_OK) return rcx;
-                }
-                // the numbering restarts (or another strip layout starts): no element may look like one of the new run
-                // (after the chaining above: an earlier launch of this lattice on another stream has finished with the buffer)
-                if (renumber) TSU_HIP_TRY(ctx, hipMemsetAsync(L->d_xbuf, 0, L->xbuf_cap * sizeof(uint64_t), ctx->stream));
-                // (a slab's launches alternate with the halo exchange's RCCL kernels on this stream: ordinary launch, see tsu_launch_grid_sync)
-                TSU_HIP_TRY(ctx, tsu_launch_grid_sync(ctx, (const void*)res_kern, dim3((unsigned)ntiles), dim3((unsigned)tv.threads), &P, lds_bytes, ctx->stream,
-                                                      slab));
-                L->launches += 1;
-                L->cur ^= 1;
-                {
-                    const int rcx = tsu_grid_exclusive_end(ctx);
-                    if (rcx != TSU_OK) return rcx;
-                }
-                if (d_dbg) {
-                    std::vector<long long> h((size_t)4 * ntiles);
-                    (void)hipMemcpy(h.data(), d_dbg, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
-                    (void)hipFree(d_dbg);
-                    static const char* const what[4] = {"sweeps", "publish", "wait", "fetch"};
-                    fprintf(stderr, "[tsu]   us per generation over %d tiles (mean / min / max):", ntiles);
-                    for (int q = 0; q < 4; ++q) {
-                        double sum = 0, lo = 1e30, hi = 0;
-                        for (int t = 0; t < ntiles; ++t) {
-                            const double v = h[(size_t)4 * t + q] / 100.0 / P.r.n_gen;
-                            sum += v;
-                            lo = v < lo ? v : lo;
-                            hi = v > hi ? v : hi;
-                        }
-                        fprintf(stderr, " %s %.1f / %.1f / %.1f%s", what[q], sum / ntiles, lo, hi, q < 3 ? "," : "\n");
-                    }
-                    if (atoi(vb) >= 3) {  // by XCD (workgroup index mod 8): does one die run behind the others?
-                        for (int x = 0; x < 8; ++x) {
-                            double sw = 0, wt = 0;
-                            int cnt = 0;
-                            for (int t = x; t < ntiles; t += 8, ++cnt) {
-                                sw += h[(size_t)4 * t] / 100.0 / P.r.n_gen;
-                                wt += h[(size_t)4 * t + 2] / 100.0 / P.r.n_gen;
-                            }
-                            if (cnt) fprintf(stderr, "[tsu]   xcd %d: sweeps %.2f wait %.2f\n", x, sw / cnt, wt / cnt);
-                        }
-                        if (atoi(vb) >= 4)  // the whole map: sweeps / wait per tile, one line per tile row
-                            for (int y = 0; y < tiles_y; ++y) {
-                                fprintf(stderr, "[tsu]   row %3d:", y);
-                                for (int x = 0; x < p.tiles_x; ++x)
-                                    fprintf(stderr, " %.1f/%.1f", h[(size_t)4 * (y * p.tiles_x + x)] / 100.0 / P.r.n_gen,
-                                            h[(size_t)4 * (y * p.tiles_x + x) + 2] / 100.0 / P.r.n_gen);
-                                fprintf(stderr, "\n");
-                            }
-                    }
-                }
-                done += chunk;
-            }
-            return TSU_OK;
         }
+        return (L->rows + p.tile_h - 1) / p.tile_h;
     }
+    // A slab computes the ghost rows its remaining sweeps of this refresh period need, 2 per sweep on each side.  It keeps the
+    // number of tile rows (an extra, nearly empty tile row can cost a whole extra round of tiles): the tiles stretch instead, if
+    // the taller tile still fits the LDS share this variant runs with
+    const int ext = 2 * (left - k);
+    p.r_begin = -ext;
+    p.r_end = L->rows + ext;
+    const int base_ty = (L->rows + tv.H - 1) / tv.H;
+    int th = (p.r_end - p.r_begin + base_ty - 1) / base_ty;
+    th += th & 1;
+    if (th >= tv.H && tile_lds_bytes(tv, th + 4 * k) <= lds_share(tv)) p.tile_h = th;
+    return (p.r_end - p.r_begin + p.tile_h - 1) / p.tile_h;
+}
+
+// TSU_K1_VERBOSE >= 2: the in-kernel timeline of a tile-resident launch, [ntiles][4] clock counts (10 ns) per tile
+void print_resident_timeline(const long long* d_dbg, int ntiles, int tiles_x, int tiles_y, int n_gen, int verbose) {
+    std::vector<long long> h((size_t)4 * ntiles);
+    (void)hipMemcpy(h.data(), d_dbg, h.size() * sizeof(long long), hipMemcpyDeviceToHost);
+    static const char* const what[4] = {"sweeps", "publish", "wait", "fetch"};
+    fprintf(stderr, "[tsu]   us per generation over %d tiles (mean / min / max):", ntiles);
+    for (int q = 0; q < 4; ++q) {
+        double sum = 0, lo = 1e30, hi = 0;
+        for (int t = 0; t < ntiles; ++t) {
+            const double v = h[(size_t)4 * t + q] / 100.0 / n_gen;
+            sum += v;
+            lo = v < lo ? v : lo;
+            hi = v > hi ? v : hi;
+        }
+        fprintf(stderr, " %s %.1f / %.1f / %.1f%s", what[q], sum / ntiles, lo, hi, q < 3 ? "," : "\n");
+    }
+    if (verbose < 3) return;
+    for (int x = 0; x < 8; ++x) {  // by XCD (workgroup index mod 8): does one die run behind the others?
+        double sw = 0, wt = 0;
+        int cnt = 0;
+        for (int t = x; t < ntiles; t += 8, ++cnt) {
+            sw += h[(size_t)4 * t] / 100.0 / n_gen;
+            wt += h[(size_t)4 * t + 2] / 100.0 / n_gen;
+        }
+        if (cnt) fprintf(stderr, "[tsu]   xcd %d: sweeps %.2f wait %.2f\n", x, sw / cnt, wt / cnt);
+    }
+    if (verbose < 4) return;
+    for (int y = 0; y < tiles_y; ++y) {  // the whole map: sweeps / wait per tile, one line per tile row
+        fprintf(stderr, "[tsu]   row %3d:", y);
+        for (int x = 0; x < tiles_x; ++x)
+            fprintf(stderr, " %.1f/%.1f", h[(size_t)4 * (y * tiles_x + x)] / 100.0 / n_gen, h[(size_t)4 * (y * tiles_x + x) + 2] / 100.0 / n_gen);
+        fprintf(stderr, "\n");
+    }
+}
+
+// ---- tile-resident generations: every tile has its own workgroup on the chip for the whole call (fit_per_cu: the occupancy check's)
+int run_resident(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps, uint32_t sweep0, int fit_per_cu) {
+    tsu_ctx* ctx = L->ctx;
+    const TileVariant& tv = kVariants[c.v];
+    void (*const res_kern)(ResidentLaunch) = L->periodic ? tv.resident : tv.resident_open;
+    const int kmax = c.kmax, ntiles = p.tiles_x * c.tiles_y;
+    const bool whole = L->wrap_rows || (!L->periodic && L->ghost == 0 && L->total_rows == L->rows);
+    const size_t lds_bytes = tile_lds_bytes(tv, c.tile_h + 4 * kmax);
+    const size_t xstride = (size_t)2 * (2 * kmax * tv.WO) + (size_t)2 * c.tile_h;  // TOP, BOTTOM, LEFT, RIGHT of colour plane 1
+    const size_t xneed = (size_t)2 * ntiles * xstride;
+    if (L->xbuf_cap < xneed * sizeof(uint64_t)) L->xsig = 0;  // fresh memory: cleared before its first use below
+    TSU_HIP_TRY(ctx, ising2d_grow(L->d_xbuf, L->xbuf_cap, xneed * sizeof(uint64_t)));
+    // strip layout of this call: the element numbering may only run on while it stays the same
+    const uint64_t xsig = ((uint64_t)(c.v + 1) << 48) ^ ((uint64_t)ntiles << 28) ^ ((uint64_t)kmax << 20) ^ ((uint64_t)c.tile_h << 4) ^
+                          ((uint64_t)c.flex_ty << 36) ^ (uint64_t)p.open;
+    if (!L->h_err) {
+        TSU_HIP_TRY(ctx, hipHostMalloc(&L->h_err, sizeof(int), hipHostMallocMapped));
+        *L->h_err = 0;
+    }
+    int* d_err = nullptr;
+    TSU_HIP_TRY(ctx, hipHostGetDevicePointer((void**)&d_err, L->h_err, 0));
+    const int verbose = lattice_env("TSU_K1_VERBOSE", 0);
+    // one launch per 1024 generations at most (a whole lattice may be asked for millions of sweeps; a slab's call
+    // is one refresh period anyway)
+    const int chunk_max = whole ? 1024 * kmax : n_sweeps;
     for (int done = 0; done < n_sweeps;) {
-        int k = n_sweeps - done < kmax ? n_sweeps - done : kmax;
+        const int chunk = n_sweeps - done < chunk_max ? n_sweeps - done : chunk_max;
+        ResidentLaunch P;
+        p.k = kmax;
+        p.sweep0 = sweep0 + (uint32_t)done;
+        p.ty_first = 0;
+        p.ty_stride = 1;
+        p.src = L->alloc[L->cur] + (size_t)L->ghost * L->pitch;
+        p.dst = L->alloc[L->cur ^ 1] + (size_t)L->ghost * L->pitch;
+        p.tile_h = c.tile_h;
+        p.flex_ty = c.flex_ty;
+        p.r_begin = -c.res_ext;
+        p.r_end = L->rows + c.res_ext;
+        P.t = p;
+        P.r.wrap_y = L->wrap_rows ? 1 : 0;
+        P.r.wrap_x = L->periodic ? 1 : 0;
+        P.r.xbuf = L->d_xbuf;
+        const bool renumber = L->xsig != xsig || L->xgen + (uint32_t)((chunk + kmax - 1) / kmax) + 2u >= 16383u;
+        if (renumber) {
+            L->xsig = xsig;
+            L->xgen = 0;
+        }
+        P.r.gen0 = L->xgen + 1u;
+        L->xgen += (uint32_t)((chunk + kmax - 1) / kmax);
+        P.r.err = d_err;
+        P.r.n_gen = (chunk + kmax - 1) / kmax;
+        P.r.k_last = chunk - (P.r.n_gen - 1) * kmax;
+        P.r.tiles_y = c.tiles_y;
+        P.r.dbg = nullptr;
+        long long* d_dbg = nullptr;
+        if (verbose >= 2) {
+            TSU_HIP_TRY(ctx, hipMalloc(&d_dbg, (size_t)4 * ntiles * sizeof(long long)));
+            P.r.dbg = d_dbg;
+        }
+        if (verbose)
+            fprintf(stderr, "[tsu] k1_resident variant %d: %d tiles (%d per CU fit), %d generations of %d sweeps, %zu KB of strips\n",
+                    c.v, ntiles, fit_per_cu, P.r.n_gen, kmax, xneed * 8 / 1024);
+        {
+            const int rcx = tsu_grid_exclusive_begin(ctx);
+            if (rcx != TSU_OK) return rcx;
+        }
+        // the numbering restarts (or another strip layout starts): no element may look like one of the new run
+        // (after the chaining above: an earlier launch of this lattice on another stream has finished with the buffer)
+        if (renumber) TSU_HIP_TRY(ctx, hipMemsetAsync(L->d_xbuf, 0, L->xbuf_cap, ctx->stream));
+        // (a slab's launches alternate with the halo exchange's RCCL kernels on this stream: ordinary launch, see tsu_launch_grid_sync)
+        TSU_HIP_TRY(ctx, tsu_launch_grid_sync(ctx, (const void*)res_kern, dim3((unsigned)ntiles), dim3((unsigned)tv.threads), &P, lds_bytes, ctx->stream,
+                                              !whole));
+        L->launches += 1;
+        L->cur ^= 1;
+        {
+            const int rcx = tsu_grid_exclusive_end(ctx);
+            if (rcx != TSU_OK) return rcx;
+        }
+        if (d_dbg) {
+            print_resident_timeline(d_dbg, ntiles, p.tiles_x, c.tiles_y, P.r.n_gen, verbose);
+            (void)hipFree(d_dbg);
+        }
+        done += chunk;
+    }
+    return TSU_OK;
+}
+
+// ---- one launch per k <= kmax sweeps, out of place (the host ping-pongs the lattice buffers)
+int run_generations(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps, uint32_t sweep0, int part) {
+    tsu_ctx* ctx = L->ctx;
+    const TileVariant& tv = kVariants[c.v];
+    void (*const kern)(TiledParams) = L->periodic ? tv.kernel : tv.open;
+    const bool slab = !(L->wrap_rows || (!L->periodic && L->ghost == 0 && L->total_rows == L->rows));
+    for (int done = 0; done < n_sweeps;) {
+        const int k = n_sweeps - done < c.kmax ? n_sweeps - done : c.kmax;
         p.k = k;
         p.sweep0 = sweep0 + (uint32_t)done;
         p.src = L->alloc[L->cur] + (size_t)L->ghost * L->pitch;
         p.dst = L->alloc[L->cur ^ 1] + (size_t)L->ghost * L->pitch;
-        int TR = TILE_H + 4 * k;
-        size_t lds_bytes = tile_lds_bytes(tv, TR);
-        if (!slab && part == TSU_PART_ALL) {
-            const int th = schedule_tile_h(L, tv, k, p.tiles_x);
-            p.tile_h = th;
-            tiles_y = (L->rows + th - 1) / th;
-            TR = th + 4 * k;
-            lds_bytes = tile_lds_bytes(tv, TR);
-        }
-        if (slab && part == TSU_PART_ALL) {
-            const int ext = 2 * (n_sweeps - done - k);  // rows of ghost the remaining sweeps of this refresh period need
-            p.r_begin = -ext;
-            p.r_end = L->rows + ext;
-            // keep the number of tile rows (an extra, nearly empty tile row can cost a whole extra round of tiles):
-            // stretch the tiles instead, if the taller tile still fits the LDS share this variant runs with
-            const int base_ty = (L->rows + TILE_H - 1) / TILE_H;
-            int th = (p.r_end - p.r_begin + base_ty - 1) / base_ty;
-            th += th & 1;
-            const size_t lds_share = (tv.per_cu ? 160u / (unsigned)tv.per_cu : (tv.threads >= 1024 ? 160u : 80u)) * 1024u;
-            const size_t need = tile_lds_bytes(tv, th + 4 * k);
-            if (need > lds_share || th < TILE_H) th = TILE_H;
-            p.tile_h = th;
-            tiles_y = (p.r_end - p.r_begin + th - 1) / th;
-            TR = th + 4 * k;
-            lds_bytes = tile_lds_bytes(tv, TR);
-        }
+        const int tiles_y = launch_tiles(L, tv, k, n_sweeps - done, part, slab, p);
+        const size_t lds_bytes = tile_lds_bytes(tv, p.tile_h + 4 * k);
         // tile rows 0 and tiles_y-1 read ghost rows (2k <= H); the others only read owned rows
         int n_ty = tiles_y;
         p.ty_first = 0;
@@ -1395,6 +1300,76 @@ int tsu_ising2d_tiled_sweep(tsu_ising2d* L, int n_sweeps, uint64_t seed, uint32_
     }
     TSU_HIP_TRY(ctx, hipGetLastError());
     return TSU_OK;
+}
+}  // namespace
+
+int tsu_ising2d_tiled_supported(const tsu_ising2d* L) {
+    if (plan_call(L, 0, TSU_PART_ALL).v < 0) return 0;       // no tile shape fits (too narrow / too few rows): generic kernel
+    const bool open_whole = !L->periodic && L->ghost == 0 && L->total_rows == L->rows;  // beyond its edges: nothing
+    if (!L->wrap_rows && !open_whole && L->ghost < 2) return 0;
+    return 1;
+}
+
+// number of tiles (= workgroups of a tile-resident launch) the lattice is cut into; 0 if the tiled kernel does not apply
+int tsu_ising2d_tiled_tiles(const tsu_ising2d* L) {
+    if (!tsu_ising2d_tiled_supported(L)) return 0;
+    const CallPlan c = plan_call(L, 0, TSU_PART_ALL);
+    const TileVariant& tv = kVariants[c.v];
+    const int tiles_x = (((L->cols + 15) / 16) + tv.WO - 1) / tv.WO;
+    return (c.flex_ty > 0 ? c.flex_ty : (L->rows + tv.H - 1) / tv.H) * tiles_x;
+}
+
+// split (interior / boundary) launches: ghost-row slabs whose tile rows are all full
+int tsu_ising2d_tiled_part_supported(const tsu_ising2d* L) {
+    return tsu_ising2d_tiled_supported(L) && !L->wrap_rows && (L->rows % kVariants[plan_call(L, 0, TSU_PART_ALL).v].H) == 0;
+}
+
+int tsu_ising2d_tiled_sweep(tsu_ising2d* L, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, int part) {
+    tsu_ctx* ctx = L->ctx;
+    const CallPlan c = plan_call(L, n_sweeps, part);
+    const TileVariant& tv = kVariants[c.v];
+    if (!L->alloc[1]) {
+        size_t bytes = (size_t)(L->rows + 2 * L->ghost) * L->pitch;
+        TSU_HIP_TRY(ctx, hipMalloc(&L->alloc[1], bytes));
+        TSU_HIP_TRY(ctx, hipMemsetAsync(L->alloc[1], 0, bytes, ctx->stream));
+    }
+    if (!L->wrap_rows && !(!L->periodic && L->ghost == 0 && L->total_rows == L->rows)) {
+        // A slab may sweep ghost/2 times between two ghost refreshes.  When that takes several launches, every launch
+        // but the last also computes the ghost rows the following launches will read (2 rows per remaining sweep on
+        // each side, from input that is still exact there), instead of waiting for the neighbours.
+        TSU_REQUIRE(ctx, 2 * n_sweeps <= L->ghost, "ising2d_sweep (tiled, slab): %d sweeps per ghost refresh exceed ghost/2 = %d",
+                    n_sweeps, L->ghost / 2);
+        TSU_REQUIRE(ctx, part == TSU_PART_ALL || n_sweeps <= c.kmax, "ising2d_sweep_part: split sweeps take at most %d sweeps", c.kmax);
+    }
+    TiledParams p;
+    p.pitch = (long long)L->pitch;
+    p.rows = L->rows;
+    p.nchunks = (L->cols + 15) / 16;
+    p.cols = L->cols;
+    p.row0 = L->row0;
+    p.total_rows = L->total_rows;
+    p.wrap_rows = L->wrap_rows;
+    p.ghost = L->ghost;
+    p.tiles_x = (p.nchunks + tv.WO - 1) / tv.WO;
+    p.q_shift = ragged_shift(L, tv.WO);
+    p.r_begin = 0;
+    p.r_end = L->rows;
+    p.tile_h = tv.H;
+    p.flex_ty = 0;
+    ising2d_set_keys(p, seed, replica);
+    pack_thresholds(p, L->table);
+    p.open = L->periodic ? 0 : 1;
+    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)(L->periodic ? tv.kernel : tv.open), 160 * 1024));
+    if (c.resident) {
+        void (*const res_kern)(ResidentLaunch) = L->periodic ? tv.resident : tv.resident_open;
+        TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)res_kern, 160 * 1024));
+        int fit_per_cu = 0;
+        // (occupancy for the standard tile height; a stretched slab tile was checked against the variant's LDS share)
+        TSU_HIP_TRY(ctx, tsu_func_blocks_per_cu(ctx, (const void*)res_kern, tv.threads, tile_lds_bytes(tv, (c.flex_ty > 0 ? c.tile_h : tv.H) + 4 * KMAX),
+                                                &fit_per_cu));
+        if ((long long)p.tiles_x * c.tiles_y <= (long long)fit_per_cu * ctx->cus) return run_resident(L, c, p, n_sweeps, sweep0, fit_per_cu);
+    }
+    return run_generations(L, c, p, n_sweeps, sweep0, part);
 }
 
 // ================================================================== one-workgroup colour-plane kernel (small lattices)
@@ -1513,15 +1488,10 @@ __global__ __launch_bounds__(1024) void k1_planes(const PlanesItem* __restrict__
     }
 }
 
-// whole lattices of at most 1024 octets, any width; an open lattice needs two rows and two columns (the packed compare
-// knows degrees 4, 3 and 2).  TSU_K1_PLANES=0: never (k1_small).
+// whole lattices of at most 1024 octets, any width; a lattice needs two rows and two columns (the packed compare knows
+// degrees 4, 3 and 2): one-row and one-column lattices take k1_generic
 int tsu_ising2d_planes_supported(const tsu_ising2d* L) {
-    static int enabled = -1;
-    if (enabled < 0) {
-        const char* e = getenv("TSU_K1_PLANES");
-        enabled = e ? atoi(e) : 1;
-    }
-    if (!enabled || L->ghost != 0 || L->total_rows != L->rows || L->row0 != 0) return 0;
+    if (L->ghost != 0 || L->total_rows != L->rows || L->row0 != 0) return 0;
     if ((long long)L->rows * ((L->cols + 15) / 16) > 1024) return 0;
     return L->rows >= 2 && L->cols >= 2;
 }
@@ -1539,29 +1509,9 @@ int tsu_ising2d_planes_sweep(tsu_ising2d* const* lats, int n, int n_sweeps, cons
         it.rows = L->rows;
         it.cols = L->cols;
         it.periodic = L->periodic;
-        it.k0 = (uint32_t)seeds[i];
-        it.k1 = (uint32_t)(seeds[i] >> 32);
-        it.tag_hi = TSU_TAG_ISING_HI | (replicas[i] << 8);
-        it.tag_lo = TSU_TAG_ISING_LO | (replicas[i] << 8);
+        ising2d_set_keys(it, seeds[i], replicas[i]);
         it.sweep0 = sweep0s[i];
-        for (int c = 0; c < 25; ++c) it.thr[c] = L->table[c];
-        auto top16 = [](uint64_t thr) {
-            uint32_t thi = (uint32_t)(thr >> 16);
-            if (thi > 65535u) thi = 65535u;
-            return thi ^ 0x8000u;
-        };
-        uint32_t t16[5], t3[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int c = 0; c < 5; ++c) t16[c] = top16(L->table[4 * 5 + c]);
-        for (int c = 0; c < 4; ++c) t3[c] = top16(L->table[3 * 5 + c]);
-        for (int c = 0; c < 3; ++c) t3[4 + c] = top16(L->table[2 * 5 + c]);
-        it.t3L0 = (t3[0] & 0xFF) | ((t3[1] & 0xFF) << 8) | ((t3[2] & 0xFF) << 16) | ((t3[3] & 0xFF) << 24);
-        it.t3L1 = (t3[4] & 0xFF) | ((t3[5] & 0xFF) << 8) | ((t3[6] & 0xFF) << 16);
-        it.t3H0 = (t3[0] >> 8) | ((t3[1] >> 8) << 8) | ((t3[2] >> 8) << 16) | ((t3[3] >> 8) << 24);
-        it.t3H1 = (t3[4] >> 8) | ((t3[5] >> 8) << 8) | ((t3[6] >> 8) << 16);
-        it.tblL0 = (t16[0] & 0xFF) | ((t16[1] & 0xFF) << 8) | ((t16[2] & 0xFF) << 16) | ((t16[3] & 0xFF) << 24);
-        it.tblL1 = (t16[4] & 0xFF);
-        it.tblH0 = (t16[0] >> 8) | ((t16[1] >> 8) << 8) | ((t16[2] >> 8) << 16) | ((t16[3] >> 8) << 24);
-        it.tblH1 = (t16[4] >> 8);
+        pack_thresholds(it, L->table);
     }
     const tsu_ising2d* L0c = lats[0];
     const int tasks = L0c->rows * ((L0c->cols + 15) / 16);
@@ -1572,13 +1522,7 @@ int tsu_ising2d_planes_sweep(tsu_ising2d* const* lats, int n, int n_sweeps, cons
     } else {
         tsu_ising2d* L0 = lats[0];  // the staging buffer for the items lives with the first lattice of the batch
         const size_t bytes = items.size() * sizeof(PlanesItem);
-        if (L0->batch_cap < bytes) {
-            if (L0->d_batch) (void)hipFree(L0->d_batch);
-            L0->d_batch = nullptr;
-            L0->batch_cap = 0;
-            TSU_HIP_TRY(ctx, hipMalloc(&L0->d_batch, bytes));
-            L0->batch_cap = bytes;
-        }
+        TSU_HIP_TRY(ctx, ising2d_grow(L0->d_batch, L0->batch_cap, bytes));
         // stream order keeps a previous batch launch from still reading the buffer; the host array dies with this call,
         // so the copy is waited for (a few KB); the launch itself stays asynchronous
         TSU_HIP_TRY(ctx, hipMemcpyAsync(L0->d_batch, items.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
