@@ -2,7 +2,7 @@
 """bench.py -- the contract benchmark: spin-updates/s of the checkerboard Gibbs sweep on an L x L Ising lattice.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--L 4096] [--sweeps-per-step 256] [--sweeps-per-launch 8]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extra]]
 
 N = 1: BASELINE.json configs[1] (IsingModel2D 4096 x 4096 at T_c, periodic, physical bias mode) on one MI355X.
 N > 1 (one rank per GPU, started by torch.distributed.run -- by the caller, or by bench.py itself as a child process
@@ -14,6 +14,11 @@ A step = `sweeps-per-step` full lattice sweeps (each sweep updates every spin on
 Inputs are resident in HBM before the timed region.  One JSON line is printed by rank 0.
 `--dump-outputs DIR` writes the lattice the last timed step left behind to DIR/*.npy (see dump_outputs): the start state,
 seeds and sweep counters depend on the arguments alone, so two builds run with the same arguments can be compared file by file.
+
+A plain run does only what its line needs: set up, warm up, time the steps, dump, print.  `--full` adds the measurements that
+run on their own after the timed steps (see side_plan): the CPU baselines, and in `extra` the other lattice sizes, Langevin,
+dense, sparse and Python-surface figures (N = 1) or the strong-scaling line (N > 1); `--no-cpu-baseline` / `--no-extra` drop
+a part of those again.
 """
 import argparse
 import json
@@ -463,11 +468,32 @@ def build_parser():
     ap.add_argument("--strong", action="store_true",
                     help="N>1: ONE L x L lattice cut into N slabs of L/N rows (BASELINE configs[3]: --L 16384 --gpus 8) "
                          "instead of the default weak scaling (L x L per GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the main line's steps, also run the CPU baselines and the side measurements (other sizes, "
+                         "kernels and precisions; N>1: the strong-scaling line) into the record")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: leave out the side measurements")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the lattice after the last timed step to DIR/*.npy (float32 spins, float64 observables; <= 32 MiB)")
     return ap
+
+
+def side_plan(args, world):
+    """Which measurements beyond the main line a run makes, all after its timed steps: none in a plain run.  With --full:
+      "cpu"    the CPU baselines (N = 1, unless --no-cpu-baseline),
+      "extra"  the side measurements on other lattices and kernels (N = 1, unless --no-extra),
+      "strong" the strong-scaling line of BASELINE configs[3] (N > 1 in weak scaling, unless --no-extra)."""
+    if not args.full:
+        return set()
+    plan = set()
+    if world == 1:
+        if not args.no_cpu_baseline:
+            plan.add("cpu")
+        if not args.no_extra:
+            plan.add("extra")
+    elif not args.no_extra and not args.strong:
+        plan.add("strong")
+    return plan
 
 
 def launch_plan(gpus, env, argv, free_port=None):
@@ -652,8 +678,9 @@ def main():
         dump_outputs(args.dump_outputs, lat.get_spins() if world == 1 else slab.local_spins(), (s, b) if rank == 0 else None,
                      name="spins" if world == 1 else f"spins_rank{rank}", budget=DUMP_SPIN_BYTES // world)
 
+    sides = side_plan(args, world)
     multi_extra = None
-    if world > 1 and not args.no_extra and not args.strong:
+    if "strong" in sides:
         # BASELINE configs[3] in the same record: ONE 16384 x 16384 lattice cut into `world` row slabs (strong scaling), with both
         # halo transports (torch.distributed point-to-point ops; the library's own RCCL calls below the C ABI)
         multi_extra = {}
@@ -697,12 +724,12 @@ def main():
         }
         if multi_extra is not None:
             out["extra"] = multi_extra
-        if not args.no_cpu_baseline and world == 1:
+        if "cpu" in sides:
             out["cpu_baseline"] = cpu_baseline(L)
             out["cpu_reference_order"] = cpu_reference_order()
             out["cpu_numpy_checkerboard"] = cpu_numpy_checkerboard(min(L, 2048))
             out["cpu_numpy_langevin"] = cpu_numpy_langevin()
-        if not args.no_extra and world == 1:
+        if "extra" in sides:
             lat.close()
             extra = {}
 
