@@ -15,6 +15,7 @@ Contents
     twins (checkerboard + Philox) that define the bit-exact contract for the HIP kernels.
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -388,3 +389,257 @@ def ising2d_sweep_window(block, row_global0, total_rows, periodic, table, n_swee
                                    C.c_int64(total_rows), C.c_int(int(bool(periodic))), _p(t, C.c_uint64), C.c_int(n_sweeps),
                                    C.c_uint64(seed), C.c_uint32(sweep0), C.c_uint32(replica))
     return s
+
+
+# ============================================================================ near-tie chains for the dense decision rule
+# The dense kernels decide u < sigmoid(h/T) as x > logit(u) and hand the close calls to the reference's float64 expression:
+# inside 1e-9 (1 + |logit|) of the logit and 1e-9 of the +-20 clamp (k2_block, k2_pipe, k2_coop, k2_own), or inside a float32
+# band of 1e-4 (1 + |logit|) and 1e-3 of the clamp (k2_small, k2_small_replicas, k2_wg).  Random draws land there about once per
+# 1e9 decisions; the generators below put them there on purpose, on systems whose fields are exact in any summation order.
+
+U53 = 2.0 ** -53
+BAND_EXACT = 1e-9   # |x - logit(u)| <= BAND_EXACT (1 + |logit(u)|): the large kernels' float64 fallback
+BAND_FLOAT = 1e-4   # |x - logit(u)| <= BAND_FLOAT (1 + |logit(u)|): the one-wave / one-workgroup kernels' fallback
+CLAMP_BAND_FLOAT = 1e-3
+# clamp ladder (class D): x = 2 b at T = 0.5, one value per ladder site
+LADDER_X = (20.0, -20.0, 20.0 + 2.0 ** -40, -20.0 - 2.0 ** -40, 20.0 - 2.0 ** -40, -20.0 + 2.0 ** -40, 20.0 + 5e-4, -20.0 - 5e-4,
+            20.0 - 5e-4, -20.0 + 5e-4, 20.0 + 2e-3, -20.0 - 2e-3, 20.0 - 2e-3, -20.0 + 2e-3, 25.0, -25.0)
+EXTREME_U = (0.0, U53, 1.0 - U53)
+
+
+def logit(u):
+    return math.log(u) - math.log1p(-u) if 0.0 < u < 1.0 else (-math.inf if u <= 0.0 else math.inf)
+
+
+def _sig(x):
+    """ora_sigmoid in Python floats (math.exp is the C library's exp, as in tsu_oracle.c)."""
+    if x > 20.0:
+        return 1.0
+    if x < -20.0:
+        return 0.0
+    return 1.0 / (1.0 + math.exp(-x))
+
+
+def ladder_u(x):
+    """Class D: the uniform for a clamp-ladder site at x, chosen where the clamped and the unclamped sigmoid disagree (or, just
+    inside the clamp, where only the unclamped value is right)."""
+    if abs(x) >= 25.0:
+        return 1.0 - U53 if x > 0 else U53
+    return 1.0 - 2.0 ** -30 if x > 0 else 2.0 ** -30
+
+
+def dyadic_system(n, seed, sym=True, bias=True, ladder=0, diag=True, mmax=3, rounding=0):
+    """A dense system on the grid 2^-K, K = 4 + ceil(log2 sqrt n): J_ij = m_ij 2^-K with integers |m| <= mmax (nonzero diagonal),
+    b_i = m_i 2^-K.  Every field J[i,:].s + b_i is exact in float64 and the couplings are exact in float32, so the device's field
+    and the oracle's are the same number in any summation order.  The first `ladder` sites have a zero row (their field is their
+    bias: the clamp ladder, x = 2 b at T = 0.5) and keep their column; their biases are LADDER_X / 2 (cycled), off the grid.  The
+    next `rounding` sites are built the same way with x from rounding_sites (class F at T = 0.5).
+    Returns (J float64 (n, n), b float64 (n,) or None, K)."""
+    rng = np.random.default_rng(seed)
+    K = 4 + int(math.ceil(math.log2(math.sqrt(max(n, 1)))))
+    m = rng.integers(-mmax, mmax + 1, size=(n, n))
+    if sym:
+        m = np.triu(m) + np.triu(m, 1).T
+    if diag:
+        d = rng.integers(1, mmax + 1, size=n) * rng.choice([-1, 1], size=n)
+        m[np.arange(n), np.arange(n)] = d
+    J = m.astype(np.float64) * 2.0 ** -K
+    b = rng.integers(-4 * mmax, 4 * mmax + 1, size=n).astype(np.float64) * 2.0 ** -K if (bias or ladder or rounding) else None
+    if ladder or rounding:
+        if b is None:
+            b = np.zeros(n)
+        xs = [LADDER_X[i % len(LADDER_X)] for i in range(ladder)] + rounding_sites(rounding)
+        for i, x in enumerate(xs[:n]):
+            J[i, :] = 0.0
+            b[i] = x / 2.0
+    return J, b, K
+
+
+def energy_is_exact(J, b):
+    """True when -1/2 s^T J s - b^T s is exact in float64 for every 0/1 state in any summation order: J and b on one grid 2^-K
+    and sum |terms| < 2^(53 - K)."""
+    vals = np.abs(np.concatenate([np.ravel(J), [] if b is None else np.ravel(b)]))
+    vals = vals[vals > 0]
+    if vals.size == 0:
+        return True
+    K = 0
+    while K < 60 and not np.all(vals * 2.0 ** K == np.floor(vals * 2.0 ** K)):
+        K += 1
+    return K < 60 and float(vals.sum()) < 2.0 ** (52 - K)
+
+
+def _place(cls, x, o, rng):
+    """The uniform for a visit at x with outcome o (1: u < sigmoid(x)) in placement class cls, or None where the class cannot
+    land at this x.  Multiples of 2^-53 only."""
+    p = _sig(x)
+    if cls == "A":  # 64 ... 1024 units of 2^-53 from p: inside every band
+        if abs(x) > 12.0:
+            return None
+        kmax = min(1024, int(0.4 * BAND_EXACT * (1.0 + abs(x)) * p * (1.0 - p) / U53))
+        if kmax < 64:
+            return None
+        k = int(rng.integers(64, kmax + 1))
+        u = (math.floor(p / U53) - k) * U53 if o else (math.ceil(p / U53) + k) * U53
+        return u if 0.0 < u < 1.0 else None
+    if cls in "BC":  # 3e-9 (1 + |x|): between the two bands; 2e-4 (1 + |x|): just outside the float band
+        if abs(x) > 15.0:
+            return None
+        dx = (3e-9 if cls == "B" else 2e-4) * (1.0 + abs(x))
+        u = round(_sig(x - dx if o else x + dx) / U53) * U53
+        return u if 0.0 < u < 1.0 else None
+    if cls == "E":
+        return EXTREME_U[int(rng.integers(0, 3))]
+    if cls == "F":
+        return rounding_u(x)
+    return None
+
+
+def rounding_u(x):
+    """Class F: for 10 <= x <= 18 the reference's p = 1 / (1 + exp(-x)) is the exact sigmoid rounded twice (1 + e to 2^-52, then
+    the division), an error of up to ~1.5 units of 2^-53 in p, i.e. up to ~1e-8 in x: inside the float64 band.  Returns the
+    multiple of 2^-53 on which the reference's expression and the exact comparison x > logit(u) disagree, or None where there is
+    none with room to spare or where p would change if exp(-x) were off by up to 16 ulp."""
+    if not 10.0 <= x <= 18.0:
+        return None
+    e = math.exp(-x)
+    p = 1.0 / (1.0 + e)
+    if any(1.0 / (1.0 + e * (1.0 + k * 2.0 ** -52)) != p for k in range(-16, 17)):
+        return None
+    d = (p - 1.0) + e / (1.0 + e)  # p minus the exact sigmoid (p - 1 is exact; e / (1 + e) = 1 - sigmoid to ~1e-16 relative)
+    if d < -0.25 * U53:
+        return p  # reference: u < p is false -> 0; exact: u < sigmoid(x) -> 1
+    if d > 1.25 * U53:
+        return p - U53  # reference -> 1; exact -> 0
+    return None
+
+
+def rounding_sites(count, step=2.0 ** -7):
+    """`count` values of x on [10, 18) (multiples of `step`) where class F has a uniform (rounding_u), half of them where the
+    reference's outcome is 0 and half where it is 1: for the zero-row sites at T = 0.5."""
+    out = {0: [], 1: []}
+    for j in range(int(8.0 / step)):
+        x = 10.0 + ((j * 97) % int(8.0 / step)) * step
+        u = rounding_u(x)
+        if u is not None:
+            out[1 if u < _sig(x) else 0].append(x)
+    half = (count + 1) // 2
+    return (out[0][:half] + out[1][:count - half])[:count]
+
+
+def classify(x, u):
+    """Where a decision at x with uniform u lies: 'A' inside the float64 band, 'B' outside it and inside the float band, 'C' outside
+    both bands, with |x - logit(u)| itself; the clamp bands are reported apart ('D': within 1e-3 of +-20)."""
+    lg = logit(u)
+    dist = abs(x - lg)
+    if abs(abs(x) - 20.0) < CLAMP_BAND_FLOAT:
+        return "D", dist
+    if dist <= BAND_EXACT * (1.0 + abs(lg)):
+        return "A", dist
+    if dist <= BAND_FLOAT * (1.0 + abs(lg)):
+        return "B", dist
+    return "C", dist
+
+
+def dense_tie_chain(J, b, temps, order=None, rng=None, classes="ABCDEF", state=None, ladder=0):
+    """Replayed-uniform near-tie chain: the reference's sequential loop (gibbs.py:128-162) with one temperature per sweep
+    (temps, length = sweeps) and an optional visiting order ((sweeps, n)), where every draw is placed on purpose.
+
+    At each visit the exact field h (one row dot product: J must be dyadic, see dyadic_system, so any order gives the oracle's
+    number) gives x = h / T;
+    a target outcome and a placement class are drawn and the uniform chosen (classes: 'A' within 64 ... 1024 units of 2^-53 of p,
+    'B' 3e-9 (1 + |x|) from the logit, 'C' 2e-4 (1 + |x|), 'D' the clamp ladder (sites < `ladder` at T = 0.5), 'E' u in {0, 2^-53,
+    1 - 2^-53}, 'F' where the reference's rounded sigmoid and the exact comparison disagree (10 <= x <= 18, see rounding_u; the
+    zero-row sites after the ladder sit there at T = 0.5); 'R' an ordinary draw where no requested class fits).
+    Returns dict(uniforms (sweeps, n) in visiting order, states (sweeps + 1, n) int8, cls (sweeps, n) str by position,
+    x (sweeps, n) float64 by position)."""
+    rng = np.random.default_rng(0) if rng is None else rng
+    J = np.asarray(J, dtype=np.float64)
+    n = J.shape[0]
+    temps = [float(t) for t in temps]
+    S = len(temps)
+    s = (rng.integers(0, 2, size=n) if state is None else np.asarray(state)).astype(np.int8).copy()
+    sf = s.astype(np.float64)
+    bb = None if b is None else np.asarray(b, dtype=np.float64)
+    ordinary = [c for c in classes if c in "ABCEF"]
+    out_u = np.zeros((S, n))
+    out_x = np.zeros((S, n))
+    out_c = np.full((S, n), "R", dtype="<U1")
+    states = np.zeros((S + 1, n), dtype=np.int8)
+    states[0] = s
+    for t in range(S):
+        T = temps[t]
+        idx = range(n) if order is None else [int(v) for v in order[t]]
+        picks = rng.integers(0, 1 << 30, size=n)
+        outs = rng.integers(0, 2, size=n)
+        for k, i in enumerate(idx):
+            x = (float(J[i] @ sf) + (0.0 if bb is None else float(bb[i]))) / T
+            o = int(outs[k])
+            u, c = None, "R"
+            if i < ladder and T == 0.5 and "D" in classes:
+                u, c = ladder_u(x), "D"
+            elif "F" in classes and rounding_u(x) is not None:  # (rare but for the zero-row sites after the ladder)
+                u, c = rounding_u(x), "F"
+            elif ordinary:
+                first = int(picks[k]) % len(ordinary)
+                for j in range(len(ordinary)):
+                    c = ordinary[(first + j) % len(ordinary)]
+                    u = _place(c, x, o, rng)
+                    if u is not None:
+                        break
+            if u is None:
+                u, c = float(rng.random()), "R"
+            new = 1 if u < _sig(x) else 0
+            out_u[t, k], out_x[t, k], out_c[t, k] = u, x, c
+            s[i] = sf[i] = new
+        states[t + 1] = s
+    return {"uniforms": out_u, "states": states, "cls": out_c, "x": out_x}
+
+
+def dense_tie_bias(J, T, order, seed, sweep0, replica, state, rng=None, classes="ABC"):
+    """Philox-mode near ties: a bias b (non-dyadic) such that the FIRST sweep of a call at temperature T from `state` (visiting
+    order `order` (n,) or None; uniforms dense_uniform(site, sweep0, seed, replica)) puts every site near its own uniform: within
+    class-A distance (64 ... 1024 units of 2^-53 of p, i.e. inside the float64 band) plus a margin of 2^10 ulp of the largest partial
+    sum of its field (the device adds the bias first and may round differently by an ulp or so), or at class B / C distance.
+    J must be dyadic (J s exact).  Returns (b, cls (n,) by position, first-sweep state)."""
+    rng = np.random.default_rng(0) if rng is None else rng
+    J = np.asarray(J, dtype=np.float64)
+    n = J.shape[0]
+    s = np.asarray(state).astype(np.int8).copy()
+    sf = s.astype(np.float64)
+    rowabs = np.abs(J).sum(axis=1)
+    b = np.zeros(n)
+    cls = np.full(n, "R", dtype="<U1")
+    idx = range(n) if order is None else [int(v) for v in order]
+    picks = rng.integers(0, 1 << 30, size=n)
+    outs = rng.integers(0, 2, size=n)
+    for k, i in enumerate(idx):
+        u = dense_uniform(i, sweep0, seed, replica)
+        ci = float(J[i] @ sf)  # exact: J is dyadic
+        lg = logit(u)
+        o = int(outs[k])
+        sgn = 1.0 if o else -1.0
+        bound = abs(ci) + rowabs[i] + 40.0 * T  # largest |partial sum| of the field, bias included (|x| <= 40)
+        margin = 2.0 ** 10 * 2.0 ** -52 * bound / T
+        xt, cl = None, "R"
+        if abs(lg) <= 12.0:
+            first = int(picks[k]) % len(classes)
+            for j in range(len(classes)):
+                cl = classes[(first + j) % len(classes)]
+                if cl == "A":
+                    kmax = min(1024, int((0.4 * BAND_EXACT * (1.0 + abs(lg)) - margin) * u * (1.0 - u) / U53))
+                    if kmax >= 64:
+                        xt = lg + sgn * (int(rng.integers(64, kmax + 1)) * U53 / (u * (1.0 - u)) + margin)
+                elif cl in "BC":
+                    xt = lg + sgn * (3e-9 if cl == "B" else 2e-4) * (1.0 + abs(lg))
+                if xt is not None:
+                    break
+        if xt is None:
+            xt, cl = float(rng.normal()) * 3.0, "R"
+        b[i] = xt * T - ci
+        h = ci + b[i]
+        new = 1 if u < _sig(h / T) else 0
+        if cl != "R":
+            assert new == o and (h / T > lg) == bool(o), (i, cl)
+        cls[k] = cl
+        s[i] = sf[i] = new
+    return b, cls, s

@@ -86,22 +86,6 @@ static __device__ __forceinline__ double sigmoid_clamped(double x) {
 }
 
 
-// u < sigmoid(x) <=> x > logit(u): the logit is computed once per site and sweep, so a decision is one compare
-// instead of a float64 exp.  The reference's own expression (gibbs.py:73-77,126) decides whenever x is within a
-// safety margin of the logit and at the +-20 clamp, so outcomes are unchanged.
-static __device__ __forceinline__ int dense_decide(double F, double lg, double T, double invT, uint32_t site,
-                                                   const double* __restrict__ uniforms, uint32_t sweep, uint32_t tag,
-                                                   uint32_t k0, uint32_t k1) {
-    const double xa = F * invT;
-    if (fabs(fabs(xa) - 20.0) < 1e-9 || fabs(xa - lg) <= 1e-9 * (1.0 + fabs(lg))) {
-        const double u = uniforms ? uniforms[site] : dense_uniform(site, sweep, tag, k0, k1);
-        return (u < sigmoid_clamped(F / T)) ? 1 : 0;
-    }
-    if (xa > 20.0) return 1;
-    if (xa < -20.0) return 0;
-    return xa > lg ? 1 : 0;
-}
-
 // grow-only device buffer: reallocated (contents dropped) only when it holds fewer than `bytes`; no memset, no synchronisation
 template <typename T>
 static inline hipError_t dense_grow(T*& p, size_t& cap, size_t bytes) {

@@ -32,8 +32,10 @@ static __device__ __forceinline__ bool bar_wait(unsigned* bar, const unsigned* w
     }
 }
 
-// dense_decide (dense.h) with the rare close call out of line: the float64 exp and the Philox block it needs would
-// otherwise be inlined at every decision site and push the kernel past its 128 VGPRs
+// u < sigmoid(x) <=> x > logit(u): the logit is computed once per site and sweep, so a decision is one compare instead of a
+// float64 exp.  The reference's own expression (gibbs.py:73-77,126) decides whenever x is within 1e-9 (1 + |logit|) of the logit
+// or within 1e-9 of the +-20 clamp, so outcomes are unchanged.  That close call is out of line: the float64 exp and the Philox
+// block it needs would otherwise be inlined at every decision site and push the kernel past its 128 VGPRs
 static __device__ __noinline__ int co_decide_exact(double F, double T, uint32_t site, const double* __restrict__ uniforms,
                                                    uint32_t sweep, uint32_t tag, uint32_t k0, uint32_t k1) {
     const double u = uniforms ? uniforms[site] : dense_uniform(site, sweep, tag, k0, k1);
