@@ -263,6 +263,16 @@ int tsu_langevin_set_energy(tsu_langevin* l, const float* k_host, const float* m
  * (tsu/api.py:94); dim <= 65536.  tsu_langevin_step then makes one launch per step (every new element needs the whole old
  * state); restart / set_state / get_state / trajectories as for the separable energy. */
 int tsu_langevin_set_coupling(tsu_langevin* l, const float* A_host, const float* b_host);
+/* GAUSSIAN-MIXTURE energy E(x) = -log(sum_i exp(a_i(x)) + eps), a_i(x) = log w_i - ||x - mu_i||^2 inv_var_i / 2: the reference's
+ * multimodal demo (tsu/demos.py:73-87) and MultimodalSampler (tsu/api.py:143-149), whose gradient replaces _numerical_gradient
+ * (tsu/core.py:82-98).  centers n_components*dim row-major, log_w and inv_var (= 1 / sigma_i^2 > 0) n_components each, log_eps = log eps
+ * (-INFINITY: eps = 0); weights are NOT renormalised.  1 <= n_components <= 64, dim <= 65536; non-finite inputs refused.
+ * Evaluated in the log domain: m = max_i a_i, r_i = exp(a_i - m), Z = sum_i r_i + exp(log_eps - m),
+ * grad E = sum_i r_i inv_var_i (x - mu_i) / Z.  tsu_langevin_step then runs every step of a call in ONE launch (split by
+ * tsu_langevin_set_kernel as for the separable energy), with the separable kernel's noise stream and update expression;
+ * restart / set_state / get_state / trajectories unchanged.  A later set_energy / set_coupling switches the handle back. */
+int tsu_langevin_set_mixture(tsu_langevin* l, int n_components, const float* centers, const float* log_w, const float* inv_var,
+                             float log_eps);
 /* x <- x_init + amp * N(0,1) per chain (core.py:142-143); chain c uses Philox chain id chain0+c */
 int tsu_langevin_restart(tsu_langevin* l, const float* x_init_host /*dim*/, float amp, uint64_t seed,
                          uint32_t chain0);

@@ -12,6 +12,7 @@ __version__ = "0.1.0"
 
 from .core import (  # noqa: F401
     ConfigurationError,
+    MixtureEnergy,
     ProbabilisticNeuron,
     QuadraticEnergy,
     QuadraticForm,
@@ -33,7 +34,7 @@ from .models import (  # noqa: F401
 
 __all__ = [
     "ThermalSamplingUnit", "TSU", "TSUConfig", "ProbabilisticNeuron", "validate_distribution", "TSUError",
-    "ConfigurationError", "SamplingError", "QuadraticEnergy", "QuadraticForm",
+    "ConfigurationError", "SamplingError", "QuadraticEnergy", "QuadraticForm", "MixtureEnergy",
     "GibbsSampler", "GibbsConfig", "HardwareEmulator",
     "IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "demonstrate_phase_transition",
 ]

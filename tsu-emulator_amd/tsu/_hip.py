@@ -105,6 +105,7 @@ SIGNATURES = {
     "tsu_langevin_get_state": (C.c_int, [_vp, _f32p]),
     "tsu_langevin_set_energy": (C.c_int, [_vp, _f32p, _f32p]),
     "tsu_langevin_set_coupling": (C.c_int, [_vp, _f32p, _f32p]),
+    "tsu_langevin_set_mixture": (C.c_int, [_vp, C.c_int, _f32p, _f32p, _f32p, C.c_float]),
     "tsu_langevin_restart": (C.c_int, [_vp, _f32p, C.c_float, C.c_uint64, C.c_uint32]),
     "tsu_langevin_step": (C.c_int, [_vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_uint32,
                                     C.c_uint32, _f32p]),
@@ -568,7 +569,7 @@ class SparseSystem:
 
 
 class LangevinChains:
-    """tsu_langevin handle: n_chains x dim float32 states with a separable quadratic energy."""
+    """tsu_langevin handle: n_chains x dim float32 states with a separable quadratic, coupled quadratic or Gaussian-mixture energy."""
 
     def __init__(self, n_chains, dim, ctx=None):
         self.ctx = ctx or Context.default()
@@ -606,6 +607,28 @@ class LangevinChains:
         aa = np.ascontiguousarray(A, dtype=np.float32).reshape(self.dim, self.dim)
         bb = None if b is None else np.ascontiguousarray(np.broadcast_to(np.asarray(b, dtype=np.float32), (self.dim,)))
         self.ctx.check(self.lib.tsu_langevin_set_coupling(self.h, _ptr(aa, _f32p), None if bb is None else _ptr(bb, _f32p)))
+
+    def set_mixture(self, centers, weights, sigma=1.0, eps=1e-10):
+        """E = -log(sum_i w_i exp(-||x - mu_i||^2 / (2 sigma_i^2)) + eps) (weights not renormalised): the steps that follow run the
+        mixture kernels.  log w, 1/sigma^2 and log eps are formed in float64 and rounded to float32 once."""
+        cc = np.asarray(centers, dtype=np.float64)
+        if cc.ndim != 2 or cc.shape[1] != self.dim:
+            raise ValueError(f"set_mixture: centers must have shape (K, {self.dim}), got {cc.shape}")
+        K = cc.shape[0]
+        w = np.broadcast_to(np.asarray(weights, dtype=np.float64), (K,))
+        sg = np.broadcast_to(np.asarray(sigma, dtype=np.float64), (K,))
+        eps = float(eps)
+        if not (np.all(np.isfinite(w)) and np.all(w > 0)):
+            raise ValueError("set_mixture: weights must be finite and > 0")
+        if not (np.all(np.isfinite(sg)) and np.all(sg > 0)):
+            raise ValueError("set_mixture: sigma must be finite and > 0")
+        if not (np.isfinite(eps) and eps >= 0):
+            raise ValueError("set_mixture: eps must be finite and >= 0")
+        c32 = np.ascontiguousarray(cc, dtype=np.float32)
+        lw = np.ascontiguousarray(np.log(w), dtype=np.float32)
+        iv = np.ascontiguousarray(1.0 / sg ** 2, dtype=np.float32)
+        leps = float(np.float32(np.log(eps))) if eps > 0 else float("-inf")
+        self.ctx.check(self.lib.tsu_langevin_set_mixture(self.h, int(K), _ptr(c32, _f32p), _ptr(lw, _f32p), _ptr(iv, _f32p), leps))
 
     def restart(self, x_init, amp, seed, chain0=0):
         xi = np.ascontiguousarray(np.broadcast_to(np.asarray(x_init, dtype=np.float32), (self.dim,)))

@@ -2,7 +2,8 @@
 
 Same classes, signatures and exceptions as the reference (file:line cited per symbol).  The overdamped
 Langevin update  x <- x - grad E(x) dt/gamma + sqrt(2 T dt/gamma) xi  (core.py:74-80) runs in the fused HIP
-kernel K3 of ``libtsu_hip.so`` whenever the energy is a *separable quadratic*
+kernel K3 of ``libtsu_hip.so`` whenever the energy is a Gaussian mixture (:class:`MixtureEnergy`, or the reference's own
+multimodal demo / ``MultimodalSampler`` energies, recognised from their bound methods) or a *separable quadratic*
 E(x) = sum_i 1/2 k_i (x_i - mu_i)^2 + c  -- either given as a :class:`QuadraticEnergy` descriptor or recognised
 by probing the callable (the reference's README example ``(x**2).sum()`` and ``sample_gaussian`` are of this
 form).  The gradient is then analytic and fused into the kernel; the reference's finite-difference gradient
@@ -99,6 +100,105 @@ class QuadraticForm:
 
     def gradient(self, x) -> np.ndarray:
         return self.A @ np.atleast_1d(np.asarray(x, dtype=np.float64)) + self.b
+
+
+class MixtureEnergy:
+    """Gaussian-mixture energy E(x) = -log(sum_i w_i exp(-||x - mu_i||^2 / (2 sigma_i^2)) + eps), callable like any reference
+    energy_fn -- the reference's multimodal demo (tsu/demos.py:73-87) and ``MultimodalSampler`` (tsu/api.py:143-149) are the
+    case sigma = 1, eps = 1e-10.  ``centers`` (K, d); ``weights`` (K,), > 0, NOT renormalised (``eps`` makes their scale matter);
+    ``sigma`` a scalar or (K,), > 0; ``eps`` >= 0.  Evaluated in the log domain (a_i = log w_i - ||x - mu_i||^2 / (2 sigma_i^2),
+    m = max a_i): finite far from every centre even with eps = 0.  On the device: `csrc/langevin.hip` k3_mixture_*, K <= 64."""
+
+    MAX_COMPONENTS = 64
+
+    def __init__(self, centers, weights, sigma=1.0, eps: float = 1e-10):
+        c = np.asarray(centers, dtype=np.float64)
+        if c.ndim != 2 or c.shape[0] < 1 or c.shape[1] < 1:
+            raise ConfigurationError(f"MixtureEnergy needs centers of shape (K, dim), got shape {c.shape}")
+        K = c.shape[0]
+        if K > self.MAX_COMPONENTS:
+            raise ConfigurationError(f"MixtureEnergy supports at most {self.MAX_COMPONENTS} components, got {K}")
+        w = np.asarray(weights, dtype=np.float64)
+        if w.shape != (K,):
+            raise ConfigurationError(f"MixtureEnergy needs weights of shape ({K},), got shape {w.shape}")
+        sg = np.asarray(sigma, dtype=np.float64)
+        if sg.ndim not in (0, 1) or (sg.ndim == 1 and sg.shape != (K,)):
+            raise ConfigurationError(f"MixtureEnergy needs sigma as a scalar or of shape ({K},), got shape {sg.shape}")
+        if not np.all(np.isfinite(c)):
+            raise ConfigurationError("MixtureEnergy needs finite centers")
+        if not (np.all(np.isfinite(w)) and np.all(w > 0)):
+            raise ConfigurationError("MixtureEnergy needs finite weights > 0")
+        if not (np.all(np.isfinite(sg)) and np.all(sg > 0)):
+            raise ConfigurationError("MixtureEnergy needs finite sigma > 0")
+        eps = float(eps)
+        if not (np.isfinite(eps) and eps >= 0):
+            raise ConfigurationError(f"MixtureEnergy needs finite eps >= 0, got {eps}")
+        self.centers, self.weights, self.eps = c, w, eps
+        self.sigma = np.broadcast_to(sg, (K,)).copy()
+        self._logw = np.log(w)
+        self._iv = 1.0 / self.sigma ** 2
+        self._leps = np.log(eps) if eps > 0 else -np.inf
+
+    @property
+    def dim(self) -> int:
+        return self.centers.shape[1]
+
+    def _terms(self, x):
+        x = np.atleast_1d(np.asarray(x, dtype=np.float64))
+        a = self._logw - 0.5 * self._iv * np.sum((x[None, :] - self.centers) ** 2, axis=1)
+        m = max(float(np.max(a)), float(self._leps))  # (eps enters the log-sum-exp as one more term: far out it is the largest)
+        r = np.exp(a - m)
+        z = float(np.sum(r)) + (np.exp(self._leps - m) if self.eps > 0 else 0.0)
+        return x, m, r, z
+
+    def __call__(self, x) -> float:
+        _, m, _, z = self._terms(x)
+        return float(-(m + np.log(z)))
+
+    def gradient(self, x) -> np.ndarray:
+        x, _, r, z = self._terms(x)
+        c = r * self._iv / z
+        return c @ (x[None, :] - self.centers)
+
+
+def _recognise_mixture(energy_fn: Callable, x0: np.ndarray) -> Optional[MixtureEnergy]:
+    """A ``MixtureEnergy`` as is; a bound method of an object carrying ``mode_centers`` / ``mode_weights`` (the reference's
+    MultimodalDistribution.energy, tsu/demos.py:73-87) or ``centers`` / ``weights`` (MultimodalSampler.energy_function,
+    tsu/api.py:143-149) as the mixture they describe with sigma = 1 and eps = 1e-10 -- admitted only if that candidate reproduces the
+    callable to 1e-9 relative at max(K, 5) points near the centres (each centre at least once) and three on the eps plateau.  Anything
+    else: None.  Probing draws from a private stream
+    (the caller's np.random is left as it was)."""
+    if isinstance(energy_fn, MixtureEnergy):
+        return energy_fn
+    owner = getattr(energy_fn, "__self__", None)
+    if owner is None:
+        return None
+    for cn, wn in (("mode_centers", "mode_weights"), ("centers", "weights")):
+        if hasattr(owner, cn) and hasattr(owner, wn):
+            break
+    else:
+        return None
+    x0 = np.atleast_1d(np.asarray(x0, dtype=np.float64))
+    try:
+        centers = np.asarray(getattr(owner, cn), dtype=np.float64)
+        weights = np.asarray(getattr(owner, wn), dtype=np.float64)
+        if centers.ndim != 2 or centers.shape[1] != x0.size or weights.shape != (centers.shape[0],):
+            return None
+        cand = MixtureEnergy(centers, weights, 1.0, 1e-10)
+        rng = np.random.RandomState(24680)
+        K = centers.shape[0]
+        n_near = max(K, 5)  # (at least 8 points in all: a few components get several near points each)
+        pts = [centers[i % K] + 0.3 * rng.normal(size=x0.size) for i in range(n_near)]  # near each centre
+        spread = 1.0 + float(np.max(np.abs(centers)))
+        pts += [x0 + 0.1 * rng.normal(size=x0.size), x0 + 3.0 * spread * rng.normal(size=x0.size),
+                centers.mean(axis=0) + 10.0 * spread * rng.normal(size=x0.size)]  # plateau
+        for xt in pts:
+            want, got = float(energy_fn(xt.copy())), cand(xt)
+            if not abs(want - got) <= 1e-9 * max(1.0, abs(want)):
+                return None
+        return cand
+    except Exception:
+        return None
 
 
 _PROBE_FULL_MAX = 4096  # up to this dimension every coordinate is probed (2 d + 1 evaluations of O(d) work each)
@@ -261,8 +361,9 @@ class ThermalSamplingUnit:
         return grad
 
     # ------------------------------------------------------------------ sampling
-    def _sample_quadratic_device(self, q: QuadraticEnergy, x_init: np.ndarray, n_samples: int, return_trajectory: bool):
-        """All ``n_samples`` restarts of core.py:140-159 as independent chains of one fused launch sequence."""
+    def _sample_device(self, q, x_init: np.ndarray, n_samples: int, return_trajectory: bool):
+        """All ``n_samples`` restarts of core.py:140-159 as independent chains of one fused launch sequence, for a separable
+        (``QuadraticEnergy``), coupled (``QuadraticForm``) or Gaussian-mixture (``MixtureEnergy``) energy."""
         cfg = self.config
         x0 = np.atleast_1d(np.asarray(x_init, dtype=np.float64))
         d = x0.size
@@ -271,7 +372,11 @@ class ThermalSamplingUnit:
         self._call_counter += n_samples
         lc = _hip.LangevinChains(n_samples, d)
         try:
-            if isinstance(q, QuadraticForm):
+            if isinstance(q, MixtureEnergy):
+                if q.dim != d:
+                    raise SamplingError(f"MixtureEnergy of dimension {q.dim} on a state of dimension {d}")
+                lc.set_mixture(q.centers, q.weights, q.sigma, q.eps)
+            elif isinstance(q, QuadraticForm):
                 if q.A.shape[0] != d:
                     raise SamplingError(f"QuadraticForm of dimension {q.A.shape[0]} on a state of dimension {d}")
                 lc.set_coupling(q.A.astype(np.float32), q.b.astype(np.float32))
@@ -308,9 +413,11 @@ class ThermalSamplingUnit:
         except Exception as e:
             raise SamplingError(f"Energy function failed on initial state: {e}")
 
-        q = _recognise_quadratic(energy_fn, np.atleast_1d(x_init))
+        q = _recognise_mixture(energy_fn, np.atleast_1d(x_init))
+        if q is None:
+            q = _recognise_quadratic(energy_fn, np.atleast_1d(x_init))
         if q is not None:
-            return self._sample_quadratic_device(q, x_init, n_samples, return_trajectory)
+            return self._sample_device(q, x_init, n_samples, return_trajectory)
 
         # arbitrary Python energy: the reference algorithm as written (host by necessity, see module docstring): finite differences
         # with 2 d energy calls per step, i.e. O(d^2) work per step -- hours from a few thousand dimensions on.  Never started
@@ -321,8 +428,8 @@ class ThermalSamplingUnit:
             raise SamplingError(
                 f"energy_fn is not a uniform separable quadratic and dim = {d_}: the reference's finite-difference Langevin loop "
                 f"would make {2 * d_ * steps:.3g} energy calls of O(dim) work on the host.  Pass a tsu.core.QuadraticEnergy(k, mu) "
-                f"descriptor (k, mu scalars or arrays of length dim) to run on the GPU, or set TSU_LANGEVIN_HOST=1 to run the "
-                f"host loop anyway.")
+                f"descriptor (k, mu scalars or arrays of length dim) or a tsu.core.MixtureEnergy(centers, weights) to run on the GPU, "
+                f"or set TSU_LANGEVIN_HOST=1 to run the host loop anyway.")
         cfg = self.config
         x_init = np.asarray(x_init, dtype=float)
         x = np.atleast_1d(x_init).copy()
