@@ -153,6 +153,32 @@ int tsu_ising2d_last_sweep_ms(tsu_ising2d* lat, float* ms);
 /* sweep-kernel launches issued for this lattice so far (a tile-resident launch runs many generations of sweeps) */
 int tsu_ising2d_launch_count(tsu_ising2d* lat, uint64_t* n_launches);
 
+/* ------------------------------------------------------------------ Swendsen-Wang cluster steps (K6)
+ * No reference counterpart (the reference has local updates only).  One step samples exp(J sum_<ij> s_i s_j / T) at zero
+ * field: every bond (right and down neighbour; wrap bonds on a periodic lattice) with J s_i s_j > 0 is active with probability
+ * p = 1 - exp(-2|J|/T); the connected components of the active bonds are labelled by their smallest site index row*cols + col;
+ * every cluster flips with probability 1/2, decided once at that root.  Random words: step t, site
+ * (r, c): W = Philox(c >> 1, r, t, TAG_SW_BOND | replica << 8), key = seed; right bond active iff J s s' > 0 and
+ * W[2 (c & 1)] < thr, down bond likewise with W[2 (c & 1) + 1]; the cluster rooted at (r, c) flips iff the top bit of word
+ * c & 3 of Philox(c >> 2, r, t, TAG_SW_FLIP | replica << 8) is set.  The spins after n steps are therefore a deterministic
+ * function of (spins, J, T, seed, step0, replica), whatever the launch geometry.
+ * Whole lattices only (a slab: TSU_E_UNSUPPORTED); T <= 0: TSU_E_INVALID; J = 0 is legal (every site its own cluster).
+ * Heat-bath sweeps and cluster steps may be interleaved; they share the spins and nothing else.  Asynchronous like the
+ * sweeps: a union / find loop that hits its iteration cap is reported by the next call that synchronises. */
+/* thr = floor(p 2^32), p = -expm1(-2|J|/T) in float64 (may equal 2^32).  Pure host arithmetic. */
+int tsu_ising2d_cluster_threshold(double J, double T, uint64_t* thr);
+/* n_steps steps with step counters step0 .. step0+n_steps-1.  A lattice of at most 16384 sites: all steps in ONE launch of
+ * one workgroup (the lattice in LDS); larger ones: three launches per step (tile-local labels, merge across tile edges,
+ * resolve + flip). */
+int tsu_ising2d_cluster_sweep(tsu_ising2d* lat, double J, double T, int n_steps, uint64_t seed, uint32_t step0,
+                              uint32_t replica);
+/* the same for n_lats lattices (a temperature scan); lattices of one shape and boundary that all take the one-workgroup
+ * kernel run as ONE launch, one workgroup each; otherwise one call per lattice.  Same results as n_lats calls. */
+int tsu_ising2d_cluster_sweep_batch(tsu_ising2d* const* lats, int n_lats, int n_steps, const double* Js, const double* Ts,
+                                    const uint64_t* seeds, const uint32_t* step0s, const uint32_t* replicas);
+/* cluster-kernel launches issued for this lattice so far (separate from tsu_ising2d_launch_count) */
+int tsu_ising2d_cluster_launch_count(tsu_ising2d* lat, uint64_t* n_launches);
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

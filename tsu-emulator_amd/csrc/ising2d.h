@@ -28,7 +28,13 @@ struct tsu_ising2d {
     size_t batch_cap;
     void* d_obs_batch;   // tsu_ising2d_observables_batch: [n][2] sums of the batch (lives with its first lattice)
     size_t obs_batch_cap;
-    int* h_err;          // host-mapped flag the tile-resident kernel sets if a bounded wait expires
+    int* h_err;          // host-mapped flag: 1 = a bounded wait of the tile-resident kernel expired, 2 = a capped union / find
+                         // loop of a cluster kernel expired (results invalid either way)
+    int32_t* d_labels;   // K6 cluster labels, rows x cols int32 (ising2d_grow; 1 GiB at 16384^2)
+    size_t labels_cap;
+    void* d_sw_batch;    // tsu_ising2d_cluster_sweep_batch: device copy of the per-lattice items (lives with its first lattice)
+    size_t sw_batch_cap;
+    unsigned long long sw_launches;  // cluster-kernel launches so far (not counted in `launches`)
 };
 
 // grow-only device buffer: reallocated (contents dropped) only when it holds fewer than `bytes`; no memset, no synchronisation
@@ -51,6 +57,9 @@ static inline void ising2d_set_keys(P& p, uint64_t seed, uint32_t replica) {
     p.tag_hi = TSU_TAG_ISING_HI | (replica << 8);
     p.tag_lo = TSU_TAG_ISING_LO | (replica << 8);
 }
+
+// ising2d.hip: report (and clear) a flag a kernel left in h_err
+int ising2d_check_err(tsu_ising2d* L);
 
 // ising2d_tiled.hip
 int tsu_ising2d_tiled_supported(const tsu_ising2d* L);

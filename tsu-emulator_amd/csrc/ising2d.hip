@@ -387,6 +387,11 @@ int tsu_ising2d_create_slab(tsu_ctx* ctx, int64_t total_rows, int cols, int peri
     L->d_obs_batch = nullptr;
     L->obs_batch_cap = 0;
     L->h_err = nullptr;
+    L->d_labels = nullptr;
+    L->labels_cap = 0;
+    L->d_sw_batch = nullptr;
+    L->sw_batch_cap = 0;
+    L->sw_launches = 0;
     size_t bytes = (size_t)(rows + 2 * ghost) * L->pitch;
     hipError_t e = hipMalloc(&L->alloc[0], bytes);
     if (e == hipSuccess) e = hipMemsetAsync(L->alloc[0], 0, bytes, ctx->stream);
@@ -421,6 +426,8 @@ int tsu_ising2d_destroy(tsu_ising2d* L) {
     if (L->d_batch) (void)hipFree(L->d_batch);
     if (L->d_obs_batch) (void)hipFree(L->d_obs_batch);
     if (L->h_err) (void)hipHostFree(L->h_err);
+    if (L->d_labels) (void)hipFree(L->d_labels);
+    if (L->d_sw_batch) (void)hipFree(L->d_sw_batch);
     (void)hipEventDestroy(L->ev0);
     (void)hipEventDestroy(L->ev1);
     delete L;
@@ -444,7 +451,10 @@ int tsu_ising2d_set_spins(tsu_ising2d* L, const int8_t* host, int row_first, int
 
 static int check_persist_error(tsu_ising2d* L) {
     if (L->h_err && *L->h_err) {
+        const int code = *L->h_err;
         *L->h_err = 0;
+        if (code == 2)
+            return tsu_fail(L->ctx, TSU_E_HIP, "ising2d: a cluster kernel's union / find loop hit its iteration cap; results invalid");
         return tsu_fail(L->ctx, TSU_E_HIP, "ising2d: tile-resident sweep kernel timed out waiting for a neighbouring tile (GPU shared?); results invalid");
     }
     return TSU_OK;
@@ -759,3 +769,5 @@ int tsu_ising2d_row_ptr(tsu_ising2d* L, int local_row, void** device_ptr, size_t
 }
 
 }  // extern "C"
+
+int ising2d_check_err(tsu_ising2d* L) { return check_persist_error(L); }

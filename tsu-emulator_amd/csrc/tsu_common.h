@@ -100,7 +100,9 @@ enum : uint32_t {
     TSU_TAG_INIT = 2,
     TSU_TAG_LANGEVIN = 3,
     TSU_TAG_DENSE = 4,
-    TSU_TAG_LANGEVIN_RESTART = 5
+    TSU_TAG_LANGEVIN_RESTART = 5,
+    TSU_TAG_SW_BOND = 6,
+    TSU_TAG_SW_FLIP = 7
 };
 
 struct u32x4 {

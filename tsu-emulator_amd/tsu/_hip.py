@@ -75,6 +75,11 @@ SIGNATURES = {
     "tsu_ising2d_set_timing": (C.c_int, [_vp, C.c_int]),
     "tsu_ising2d_last_sweep_ms": (C.c_int, [_vp, _f32p]),
     "tsu_ising2d_launch_count": (C.c_int, [_vp, _u64p]),
+    "tsu_ising2d_cluster_threshold": (C.c_int, [C.c_double, C.c_double, _u64p]),
+    "tsu_ising2d_cluster_sweep": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_ising2d_cluster_sweep_batch": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tsu_ising2d_cluster_launch_count": (C.c_int, [_vp, _u64p]),
     "tsu_comm_unique_id": (C.c_int, [_u8p]),
     "tsu_comm_create": (C.c_int, [_vp, C.c_int, C.c_int, _u8p, C.POINTER(_vp)]),
     "tsu_comm_destroy": (C.c_int, [_vp]),
@@ -239,6 +244,16 @@ def ising2d_thresholds(J, h, T, mode=MODE_PHYSICAL):
     return t
 
 
+def cluster_threshold(J, T):
+    """Host helper of the library (no GPU needed): the Swendsen-Wang bond threshold floor(p 2^32), p = -expm1(-2|J|/T)."""
+    lib = load_library()
+    t = C.c_uint64(0)
+    rc = lib.tsu_ising2d_cluster_threshold(float(J), float(T), C.byref(t))
+    if rc != TSU_OK:
+        raise ValueError("Temperature must be positive" if not T > 0 else "invalid cluster threshold arguments")
+    return t.value
+
+
 class Lattice:
     """tsu_ising2d handle: a rows x cols lattice (or a row slab of one) of +-1 int8 spins on the GPU."""
 
@@ -326,6 +341,16 @@ class Lattice:
         self.ctx.check(self.lib.tsu_ising2d_last_sweep_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def cluster_sweep(self, J, T, n_steps, seed, step0=0, replica=0):
+        """n_steps Swendsen-Wang steps at coupling J, temperature T, zero field (step counters step0 ..)."""
+        self.ctx.check(self.lib.tsu_ising2d_cluster_sweep(self.h, float(J), float(T), int(n_steps), int(seed), int(step0),
+                                                          int(replica)))
+
+    def cluster_launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_ising2d_cluster_launch_count(self.h, C.byref(n)))
+        return n.value
+
 
 def sweep_batch(lattices, n_sweeps, seeds, sweep0s, replicas=None):
     """n_sweeps sweeps of every lattice (own thresholds, seed, sweep counter, replica id); lattices that fit the
@@ -339,6 +364,22 @@ def sweep_batch(lattices, n_sweeps, seeds, sweep0s, replicas=None):
     s0 = (C.c_uint32 * n)(*[int(v) for v in sweep0s])
     rp = (C.c_uint32 * n)(*([0] * n if replicas is None else [int(v) for v in replicas]))
     ctx.check(lattices[0].lib.tsu_ising2d_sweep_batch(hs, n, int(n_sweeps), sd, s0, rp))
+
+
+def cluster_sweep_batch(lattices, n_steps, Js, Ts, seeds, step0s, replicas=None):
+    """n_steps Swendsen-Wang steps of every lattice (own J, T, seed, step counter, replica id); small lattices of one shape
+    and boundary run in one launch.  Same results as stepping them one by one."""
+    n = len(lattices)
+    if n == 0:
+        return
+    ctx = lattices[0].ctx
+    hs = (_vp * n)(*[l.h for l in lattices])
+    js = (C.c_double * n)(*[float(v) for v in Js])
+    ts = (C.c_double * n)(*[float(v) for v in Ts])
+    sd = (C.c_uint64 * n)(*[int(v) for v in seeds])
+    s0 = (C.c_uint32 * n)(*[int(v) for v in step0s])
+    rp = (C.c_uint32 * n)(*([0] * n if replicas is None else [int(v) for v in replicas]))
+    ctx.check(lattices[0].lib.tsu_ising2d_cluster_sweep_batch(hs, n, int(n_steps), js, ts, sd, s0, rp))
 
 
 def observables_batch(lattices):

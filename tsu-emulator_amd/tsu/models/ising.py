@@ -409,12 +409,30 @@ class IsingGrid(IsingModel):
         return (horizontal_boundaries + vertical_boundaries) // 2 + 1
 
 
+_ALGORITHMS = ("gibbs", "swendsen_wang")
+
+
+def _check_algorithm(algorithm: str) -> None:
+    if algorithm not in _ALGORITHMS:
+        raise ValueError(f"algorithm must be one of {_ALGORITHMS}, got {algorithm!r}")
+
+
+def _check_cluster_model(external_field: float, bias_mode: str) -> None:
+    """Swendsen-Wang samples the physical zero-field measure: refuse anything else before the device is touched."""
+    if external_field != 0:
+        raise _hip.UnsupportedError("Swendsen-Wang cluster updates need external_field == 0 (a field would need a ghost spin)")
+    if bias_mode != "physical":
+        raise _hip.UnsupportedError("Swendsen-Wang cluster updates need bias_mode='physical' (compat mode's bias is not the "
+                                    "zero-field Ising measure)")
+
+
 class IsingModel2D:
     """README facade (README.md:116-131): a lattice that lives on the GPU between calls.
 
     ``IsingModel2D(size=50, coupling=1.0, temperature=2.5)``; ``gibbs_update()`` = one checkerboard sweep;
+    ``cluster_update()`` = one Swendsen-Wang step (zero field, physical mode; its own counter ``cluster_count``);
     ``magnetization()`` / ``energy()`` = observables of the current state by a device reduction;
-    ``equilibrate(T)`` sets the temperature, runs ``n_sweeps`` sweeps and returns ``self``.
+    ``equilibrate(T)`` sets the temperature, runs ``n_sweeps`` sweeps (or SW steps) and returns ``self``.
     """
 
     def __init__(self, size, coupling: float = 1.0, temperature: float = 1.0, periodic: bool = True,
@@ -433,6 +451,7 @@ class IsingModel2D:
         self.seed = int(seed) if seed is not None else (
             int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
         self.sweep_count = 0
+        self.cluster_count = 0
         self._lat = _hip.Lattice(self.rows, self.cols, self.periodic)
         if initial == "random":
             self._lat.randomize(self.seed)
@@ -447,11 +466,22 @@ class IsingModel2D:
         self.sweep_count += int(n_sweeps)
         return self
 
-    def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000) -> "IsingModel2D":
+    def cluster_update(self, n_steps: int = 1) -> "IsingModel2D":
+        """n_steps Swendsen-Wang steps (K6); the heat-bath stream and ``sweep_count`` are not touched."""
+        _check_cluster_model(self.external_field, self.bias_mode)
+        self._lat.cluster_sweep(self.coupling, self.temperature, int(n_steps), self.seed, self.cluster_count)
+        self.cluster_count += int(n_steps)
+        return self
+
+    def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000,
+                    algorithm: str = "gibbs") -> "IsingModel2D":
+        _check_algorithm(algorithm)
         if temperature is not None:
             if temperature <= 0:
                 raise ValueError("Temperature must be positive")
             self.temperature = float(temperature)
+        if algorithm == "swendsen_wang":
+            return self.cluster_update(n_sweeps)
         return self.gibbs_update(n_sweeps)
 
     def magnetization(self) -> float:
@@ -503,12 +533,16 @@ def demonstrate_phase_transition(sizes: List[int] = [8, 16, 32], temperatures: O
 
 def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                      measure_every: int = 10, periodic: bool = True, seed: int = 0, bias_mode: str = "physical",
-                     initial: str = "up") -> dict:
+                     initial: str = "up", algorithm: str = "gibbs") -> dict:
     """GPU-resident form of :func:`demonstrate_phase_transition` (reference: ising.py:424-476) for lattices far
     beyond what a samples array can hold: one :class:`IsingModel2D` per temperature stays on the device, and
     |M|, E/N, chi = (<M^2> - <M>^2) N / T and C = (<E^2> - <E>^2) / (T^2 N) come from the device reductions
     (``tsu_ising2d_observables``) -- no spin ever crosses PCIe.  Returns arrays indexed like ``temperatures``.
+    ``algorithm="swendsen_wang"``: ``n_equilibrate`` and ``measure_every`` count Swendsen-Wang steps (physical mode only).
     """
+    _check_algorithm(algorithm)
+    if algorithm == "swendsen_wang":
+        _check_cluster_model(0.0, bias_mode)
     temperatures = np.asarray(temperatures, dtype=float)
     out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
     out["temperatures"] = temperatures
@@ -519,6 +553,12 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
                            bias_mode=bias_mode, initial=initial) for i, T in enumerate(temperatures)]
 
     def advance(n_sweeps):
+        if algorithm == "swendsen_wang":
+            _hip.cluster_sweep_batch([m._lat for m in models], n_sweeps, [m.coupling for m in models],
+                                     [m.temperature for m in models], [m.seed for m in models], [m.cluster_count for m in models])
+            for m in models:
+                m.cluster_count += int(n_sweeps)
+            return
         for m in models:
             m._lat.set_model(m.coupling, m.external_field, m.temperature, m._mode)
         _hip.sweep_batch([m._lat for m in models], n_sweeps, [m.seed for m in models], [m.sweep_count for m in models])
