@@ -179,6 +179,30 @@ int tsu_ising2d_cluster_sweep_batch(tsu_ising2d* const* lats, int n_lats, int n_
 /* cluster-kernel launches issued for this lattice so far (separate from tsu_ising2d_launch_count) */
 int tsu_ising2d_cluster_launch_count(tsu_ising2d* lat, uint64_t* n_launches);
 
+/* ------------------------------------------------------------------ K7: quenched disorder on the lattice
+ * Per-bond couplings and per-site fields for heat-bath sweeps of a whole lattice (physical mode).  Row-major (rows, cols)
+ * fp32 arrays: J_right[r, c] is the bond (r, c)-(r, c+1) (wrapping to column 0 on a periodic lattice), J_down[r, c] the bond
+ * (r, c)-(r+1, c) (wrapping to row 0), h[r, c] the field of site (r, c).  Decision rule:
+ * f = (((J_down[r-1,c] s_up + J_down[r,c] s_down) + J_right[r,c-1] s_left) + J_right[r,c] s_right) + h[r,c] in float64 (a
+ * missing neighbour of an open lattice skipped), x = 2 f / T, p = sigmoid(x) clamped at +-20, thr = floor(p 2^32 + 1/2);
+ * the site becomes +1 iff u < thr, u = K1's 32-bit site uniform (same counters and tags as tsu_ising2d_sweep).  The spins
+ * stay those of the handle: set_spins / get_spins / randomize / fill / observables and K1 / K6 calls keep working. */
+/* Copy the disorder to the device (buffers allocated on first use, freed by tsu_ising2d_destroy).  h == NULL: zero field.
+ * Non-finite values, or a nonzero J_right in the last column / J_down in the last row of an open lattice: TSU_E_INVALID.
+ * A slab: TSU_E_UNSUPPORTED.  Synchronous. */
+int tsu_ising2d_set_disorder(tsu_ising2d* lat, const float* J_right, const float* J_down, const float* h);
+/* Forget the disorder (tsu_ising2d_disorder_sweep / _energy refuse until the next set_disorder). */
+int tsu_ising2d_clear_disorder(tsu_ising2d* lat);
+/* n_sweeps sweeps at temperature T with sweep counters sweep0 .. sweep0+n_sweeps-1: colour 0 ((r + c) even), then colour 1,
+ * one launch per half-sweep.  Asynchronous. */
+int tsu_ising2d_disorder_sweep(tsu_ising2d* lat, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica);
+/* E = -sum_bonds J_b s_i s_j - sum_i h_i s_i in float64, summed in a fixed order (the same bits on every call). */
+int tsu_ising2d_disorder_energy(tsu_ising2d* lat, double* E);
+/* q = sum_i s^a_i s^b_i of two whole lattices of one shape and context (disorder or not). */
+int tsu_ising2d_overlap(tsu_ising2d* a, tsu_ising2d* b, int64_t* q);
+/* K7 sweep-kernel launches issued for this lattice so far (separate from tsu_ising2d_launch_count) */
+int tsu_ising2d_disorder_launch_count(tsu_ising2d* lat, uint64_t* n_launches);
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -35,6 +35,11 @@ struct tsu_ising2d {
     void* d_sw_batch;    // tsu_ising2d_cluster_sweep_batch: device copy of the per-lattice items (lives with its first lattice)
     size_t sw_batch_cap;
     unsigned long long sw_launches;  // cluster-kernel launches so far (not counted in `launches`)
+    float* d_dis;        // K7 quenched disorder: J_right, J_down, h planes of rows x pitch fp32 each (pads 0), first set_disorder
+    int have_disorder;   // set_disorder called and not cleared since
+    double* d_dis_part;  // K7 energy: per-workgroup partials + the total
+    size_t dis_part_cap;
+    unsigned long long dis_launches;  // K7 sweep-kernel launches so far (not counted in `launches`)
 };
 
 // grow-only device buffer: reallocated (contents dropped) only when it holds fewer than `bytes`; no memset, no synchronisation

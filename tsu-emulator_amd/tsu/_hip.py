@@ -80,6 +80,12 @@ SIGNATURES = {
     "tsu_ising2d_cluster_sweep_batch": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tsu_ising2d_cluster_launch_count": (C.c_int, [_vp, _u64p]),
+    "tsu_ising2d_set_disorder": (C.c_int, [_vp, _f32p, _f32p, _f32p]),
+    "tsu_ising2d_clear_disorder": (C.c_int, [_vp]),
+    "tsu_ising2d_disorder_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_ising2d_disorder_energy": (C.c_int, [_vp, _f64p]),
+    "tsu_ising2d_overlap": (C.c_int, [_vp, _vp, _i64p]),
+    "tsu_ising2d_disorder_launch_count": (C.c_int, [_vp, _u64p]),
     "tsu_comm_unique_id": (C.c_int, [_u8p]),
     "tsu_comm_create": (C.c_int, [_vp, C.c_int, C.c_int, _u8p, C.POINTER(_vp)]),
     "tsu_comm_destroy": (C.c_int, [_vp]),
@@ -349,6 +355,38 @@ class Lattice:
     def cluster_launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_ising2d_cluster_launch_count(self.h, C.byref(n)))
+        return n.value
+
+    def set_disorder(self, J_right, J_down, h=None):
+        """K7 quenched disorder: (rows, cols) arrays, rounded once to fp32 (h=None: zero field)."""
+        shape = (self.rows, self.cols)
+        jr = np.ascontiguousarray(J_right, dtype=np.float32).reshape(shape)
+        jd = np.ascontiguousarray(J_down, dtype=np.float32).reshape(shape)
+        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float32).reshape(shape)
+        self.ctx.check(self.lib.tsu_ising2d_set_disorder(self.h, _ptr(jr, _f32p), _ptr(jd, _f32p),
+                                                         None if hh is None else _ptr(hh, _f32p)))
+
+    def clear_disorder(self):
+        self.ctx.check(self.lib.tsu_ising2d_clear_disorder(self.h))
+
+    def disorder_sweep(self, T, n_sweeps, seed, sweep0=0, replica=0):
+        """n_sweeps K7 heat-bath sweeps at temperature T (sweep counters sweep0 ..), K1's site uniforms."""
+        self.ctx.check(self.lib.tsu_ising2d_disorder_sweep(self.h, float(T), int(n_sweeps), int(seed), int(sweep0), int(replica)))
+
+    def disorder_energy(self):
+        e = C.c_double(0)
+        self.ctx.check(self.lib.tsu_ising2d_disorder_energy(self.h, C.byref(e)))
+        return e.value
+
+    def overlap(self, other):
+        """sum_i s_i s'_i with another lattice of the same shape."""
+        q = C.c_int64(0)
+        self.ctx.check(self.lib.tsu_ising2d_overlap(self.h, other.h, C.byref(q)))
+        return q.value
+
+    def disorder_launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_ising2d_disorder_launch_count(self.h, C.byref(n)))
         return n.value
 
 

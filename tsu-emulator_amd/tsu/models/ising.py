@@ -16,6 +16,12 @@ What differs is where the work happens:
 an Ising model with effective field ``h_eff = 2 rowsum(J) - h``.  ``bias_mode="compat"`` (default for the
 reference-named classes, bug-for-bug drop-in) reproduces that; ``bias_mode="physical"`` uses the corrected
 conversion (default of the README-named :class:`IsingModel2D`).
+
+Quenched disorder (K7).  ``IsingModel2D(..., couplings=(J_right, J_down), field=h)`` keeps per-bond couplings and per-site
+fields on the device (fp32, physical mode only) -- Edwards-Anderson spin glasses, random-field and Mattis magnets, Ising-prior
+denoising -- and ``gibbs_update`` then runs the disordered heat-bath kernel with K1's own site uniforms and sweep counter.
+``energy()`` is the disordered energy, ``overlap(other)`` the spin-glass overlap q / N, and ``temperature_scan(...,
+couplings=, field=, replicas=2)`` adds <|q|>, <q^2> and the Binder ratio of two replicas per temperature.
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -426,6 +432,48 @@ def _check_cluster_model(external_field: float, bias_mode: str) -> None:
                                     "zero-field Ising measure)")
 
 
+def _disorder_arrays(rows: int, cols: int, periodic: bool, coupling: float, external_field: float, bias_mode: str,
+                     couplings, field):
+    """Validate K7 disorder (before any device call) and round it once to fp32: (J_right, J_down, h or None)."""
+    if bias_mode != "physical":
+        raise ValueError("couplings / field arrays need bias_mode='physical'")
+    if couplings is not None and coupling != 1.0:
+        raise ValueError("give either couplings=(J_right, J_down) or a scalar coupling, not both")
+    if field is not None and external_field != 0.0:
+        raise ValueError("give either field= or a non-zero external_field, not both")
+    shape = (rows, cols)
+
+    def arr(a, name):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{name} must be finite")
+        with np.errstate(over="ignore"):
+            a32 = a.astype(np.float32)
+        if not np.all(np.isfinite(a32)):
+            raise ValueError(f"{name} overflows float32")
+        return a32
+
+    if couplings is not None:
+        if len(couplings) != 2:
+            raise ValueError("couplings must be a pair (J_right, J_down)")
+        jr, jd = arr(couplings[0], "J_right"), arr(couplings[1], "J_down")
+    else:
+        jr = np.full(shape, coupling, dtype=np.float32)
+        jd = np.full(shape, coupling, dtype=np.float32)
+        if not periodic:
+            jr[:, -1] = 0.0
+            jd[-1, :] = 0.0
+    if not periodic and (np.any(jr[:, -1] != 0) or np.any(jd[-1, :] != 0)):
+        raise ValueError("open lattice: the last column of J_right and the last row of J_down must be 0")
+    if field is not None:
+        h = arr(field, "field")
+    else:
+        h = np.full(shape, external_field, dtype=np.float32) if external_field != 0.0 else None
+    return jr, jd, h
+
+
 class IsingModel2D:
     """README facade (README.md:116-131): a lattice that lives on the GPU between calls.
 
@@ -433,11 +481,19 @@ class IsingModel2D:
     ``cluster_update()`` = one Swendsen-Wang step (zero field, physical mode; its own counter ``cluster_count``);
     ``magnetization()`` / ``energy()`` = observables of the current state by a device reduction;
     ``equilibrate(T)`` sets the temperature, runs ``n_sweeps`` sweeps (or SW steps) and returns ``self``.
+
+    ``couplings=(J_right, J_down)`` and ``field`` (``(rows, cols)`` arrays, physical mode) make the lattice disordered (K7):
+    ``J_right[r, c]`` couples (r, c) to (r, c+1), ``J_down[r, c]`` couples (r, c) to (r+1, c) (both wrap on a periodic
+    lattice; on an open one the last column / row must be 0), ``field[r, c]`` is the field of site (r, c).  The arrays are
+    rounded once to float32 (``disorder`` returns the rounded copies).  ``set_disorder`` replaces them and keeps the spins
+    and counters, ``clear_disorder`` returns to the uniform model.  Cluster updates refuse a disordered lattice.
     """
+
+    _disorder = None  # (J_right, J_down, h or None) float32 while the lattice is disordered
 
     def __init__(self, size, coupling: float = 1.0, temperature: float = 1.0, periodic: bool = True,
                  external_field: float = 0.0, seed: Optional[int] = None, bias_mode: str = "physical",
-                 initial: str = "random"):
+                 initial: str = "random", *, couplings=None, field=None):
         if temperature <= 0:
             raise ValueError("Temperature must be positive")
         self.rows, self.cols = (size, size) if np.isscalar(size) else tuple(size)
@@ -448,6 +504,12 @@ class IsingModel2D:
         self.periodic = bool(periodic)
         self.bias_mode = bias_mode
         self._mode = _mode_id(bias_mode)
+        if initial not in ("random", "up", "down"):
+            raise ValueError("initial must be 'random', 'up' or 'down'")
+        self._disorder = None
+        if couplings is not None or field is not None:
+            self._disorder = _disorder_arrays(self.rows, self.cols, self.periodic, self.coupling, self.external_field,
+                                              bias_mode, couplings, field)
         self.seed = int(seed) if seed is not None else (
             int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
         self.sweep_count = 0
@@ -457,17 +519,44 @@ class IsingModel2D:
             self._lat.randomize(self.seed)
         elif initial in ("up", "down"):
             self._lat.fill(1 if initial == "up" else -1)
-        else:
-            raise ValueError("initial must be 'random', 'up' or 'down'")
+        if self._disorder is not None:
+            self._lat.set_disorder(*self._disorder)
+
+    @property
+    def disorder(self):
+        """(J_right, J_down, h or None) as stored on the device (float32), or None for the uniform model."""
+        if self._disorder is None:
+            return None
+        return tuple(None if a is None else a.copy() for a in self._disorder)
+
+    def set_disorder(self, couplings=None, field=None) -> "IsingModel2D":
+        """Replace the quenched disorder (``couplings=None``: uniform ``coupling``; ``field=None``: ``external_field``);
+        the spins and counters are kept."""
+        d = _disorder_arrays(self.rows, self.cols, self.periodic, self.coupling, self.external_field, self.bias_mode,
+                             couplings, field)
+        self._lat.set_disorder(*d)
+        self._disorder = d
+        return self
+
+    def clear_disorder(self) -> "IsingModel2D":
+        """Back to the uniform model (K1 sweeps, same seed and sweep counter)."""
+        self._lat.clear_disorder()
+        self._disorder = None
+        return self
 
     def gibbs_update(self, n_sweeps: int = 1) -> "IsingModel2D":
-        self._lat.set_model(self.coupling, self.external_field, self.temperature, self._mode)
-        self._lat.sweep(int(n_sweeps), self.seed, self.sweep_count)
+        if self._disorder is not None:
+            self._lat.disorder_sweep(self.temperature, int(n_sweeps), self.seed, self.sweep_count)
+        else:
+            self._lat.set_model(self.coupling, self.external_field, self.temperature, self._mode)
+            self._lat.sweep(int(n_sweeps), self.seed, self.sweep_count)
         self.sweep_count += int(n_sweeps)
         return self
 
     def cluster_update(self, n_steps: int = 1) -> "IsingModel2D":
         """n_steps Swendsen-Wang steps (K6); the heat-bath stream and ``sweep_count`` are not touched."""
+        if self._disorder is not None:
+            raise _hip.UnsupportedError("Swendsen-Wang cluster updates do not take a disordered lattice (couplings / field)")
         _check_cluster_model(self.external_field, self.bias_mode)
         self._lat.cluster_sweep(self.coupling, self.temperature, int(n_steps), self.seed, self.cluster_count)
         self.cluster_count += int(n_steps)
@@ -489,8 +578,16 @@ class IsingModel2D:
         return sum_s / self.n_spins
 
     def energy(self) -> float:
+        if self._disorder is not None:
+            return self._lat.disorder_energy()
         sum_s, sum_bonds = self._lat.observables()
         return -self.coupling * float(sum_bonds) - self.external_field * float(sum_s)
+
+    def overlap(self, other: "IsingModel2D") -> float:
+        """q / N = sum_i s_i s'_i / N with another model of the same shape (a device reduction)."""
+        if (other.rows, other.cols) != (self.rows, self.cols):
+            raise ValueError(f"overlap needs equal shapes, got {(self.rows, self.cols)} and {(other.rows, other.cols)}")
+        return self._lat.overlap(other._lat) / self.n_spins
 
     @property
     def spins(self) -> np.ndarray:
@@ -533,24 +630,40 @@ def demonstrate_phase_transition(sizes: List[int] = [8, 16, 32], temperatures: O
 
 def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                      measure_every: int = 10, periodic: bool = True, seed: int = 0, bias_mode: str = "physical",
-                     initial: str = "up", algorithm: str = "gibbs") -> dict:
+                     initial: str = "up", algorithm: str = "gibbs", *, couplings=None, field=None, replicas: int = 1) -> dict:
     """GPU-resident form of :func:`demonstrate_phase_transition` (reference: ising.py:424-476) for lattices far
     beyond what a samples array can hold: one :class:`IsingModel2D` per temperature stays on the device, and
     |M|, E/N, chi = (<M^2> - <M>^2) N / T and C = (<E^2> - <E>^2) / (T^2 N) come from the device reductions
     (``tsu_ising2d_observables``) -- no spin ever crosses PCIe.  Returns arrays indexed like ``temperatures``.
     ``algorithm="swendsen_wang"``: ``n_equilibrate`` and ``measure_every`` count Swendsen-Wang steps (physical mode only).
+    ``couplings`` / ``field``: the same quenched disorder (K7) at every temperature.  ``replicas=2``: a second model per
+    temperature (seed ``seed + len(temperatures) + i``) runs beside the first, and the result gains the spin-glass
+    observables ``overlap`` = <|q|>, ``overlap_sq`` = <q^2> and ``binder`` = (3 - <q^4> / <q^2>^2) / 2 of q = overlap / N;
+    the other keys are those of the first replica, as with ``replicas=1``.
     """
     _check_algorithm(algorithm)
+    if replicas not in (1, 2):
+        raise ValueError("replicas must be 1 or 2")
+    disordered = couplings is not None or field is not None
     if algorithm == "swendsen_wang":
+        if disordered:
+            raise _hip.UnsupportedError("Swendsen-Wang cluster updates do not take a disordered lattice (couplings / field)")
         _check_cluster_model(0.0, bias_mode)
     temperatures = np.asarray(temperatures, dtype=float)
+    rows, cols = (size, size) if np.isscalar(size) else tuple(size)
+    disorder = None
+    if disordered:  # validated once, before any device call
+        disorder = _disorder_arrays(rows, cols, bool(periodic), float(coupling), 0.0, bias_mode, couplings, field)
     out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
     out["temperatures"] = temperatures
     # all temperatures advance together: lattices small enough for the one-workgroup kernel share ONE launch per
     # batch of sweeps (one workgroup per temperature) and one synchronisation per measurement; the streams (seed + i,
     # own sweep counter) and hence the results are those of sweeping the models one after the other
-    models = [IsingModel2D(size, coupling=coupling, temperature=float(T), periodic=periodic, seed=seed + i,
-                           bias_mode=bias_mode, initial=initial) for i, T in enumerate(temperatures)]
+    nT = len(temperatures)
+    kw = {} if disorder is None else {"couplings": (disorder[0], disorder[1]), "field": disorder[2]}
+    models = [IsingModel2D(size, coupling=coupling if disorder is None else 1.0, temperature=float(T), periodic=periodic,
+                           seed=seed + k * nT + i, bias_mode=bias_mode, initial=initial, **kw)
+              for k in range(replicas) for i, T in enumerate(temperatures)]
 
     def advance(n_sweeps):
         if algorithm == "swendsen_wang":
@@ -558,6 +671,10 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
                                      [m.temperature for m in models], [m.seed for m in models], [m.cluster_count for m in models])
             for m in models:
                 m.cluster_count += int(n_sweeps)
+            return
+        if disorder is not None:
+            for m in models:
+                m.gibbs_update(int(n_sweeps))
             return
         for m in models:
             m._lat.set_model(m.coupling, m.external_field, m.temperature, m._mode)
@@ -567,17 +684,29 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
 
     if models:
         advance(int(n_equilibrate))
-    Ms, Es = np.zeros((len(models), n_measure)), np.zeros((len(models), n_measure))
+    Ms, Es = np.zeros((nT, n_measure)), np.zeros((nT, n_measure))
+    Qs = np.zeros((nT, n_measure))
     for j in range(n_measure if models else 0):
         advance(int(measure_every))
-        for i, (sum_s, sum_bonds) in enumerate(_hip.observables_batch([m._lat for m in models])):
+        for i, (sum_s, sum_bonds) in enumerate(_hip.observables_batch([m._lat for m in models[:nT]])):
             Ms[i, j] = sum_s / models[i].n_spins
-            Es[i, j] = -models[i].coupling * float(sum_bonds) - models[i].external_field * float(sum_s)
+            if disorder is not None:
+                Es[i, j] = models[i].energy()
+            else:
+                Es[i, j] = -models[i].coupling * float(sum_bonds) - models[i].external_field * float(sum_s)
+            if replicas == 2:
+                Qs[i, j] = models[i].overlap(models[nT + i])
     for i, T in enumerate(temperatures):
         N = models[i].n_spins
         out["magnetization"][i] = np.mean(np.abs(Ms[i]))
         out["energy"][i] = np.mean(Es[i]) / N
         out["susceptibility"][i] = (np.mean(Ms[i] ** 2) - np.mean(np.abs(Ms[i])) ** 2) * N / T
         out["specific_heat"][i] = (np.mean(Es[i] ** 2) - np.mean(Es[i]) ** 2) / (T ** 2 * N)
+    if replicas == 2:
+        q2 = np.mean(Qs ** 2, axis=1)
+        out["overlap"] = np.mean(np.abs(Qs), axis=1)
+        out["overlap_sq"] = q2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["binder"] = 0.5 * (3.0 - np.mean(Qs ** 4, axis=1) / q2 ** 2)
     del models
     return out
