@@ -203,6 +203,44 @@ int tsu_ising2d_overlap(tsu_ising2d* a, tsu_ising2d* b, int64_t* q);
 /* K7 sweep-kernel launches issued for this lattice so far (separate from tsu_ising2d_launch_count) */
 int tsu_ising2d_disorder_launch_count(tsu_ising2d* lat, uint64_t* n_launches);
 
+/* ------------------------------------------------------------------ K7: parallel tempering (replica exchange) on one disorder
+ * Replaces, for a disordered lattice, GibbsSampler.parallel_tempering tsu/gibbs.py:238-338.  n_ladders (1 or 2) ladders of n_temps
+ * (2 .. 256) walkers; every walker is a whole K7 lattice (any shape tsu_ising2d_create takes), all share ONE disorder.  Walker w of
+ * ladder k has Philox key seed + k n_temps + w, replica 0, the shared sweep counter, and starts at slot (temperature) w: without
+ * swaps a walker is model k n_temps + w of temperature_scan(seed=seed) bit for bit.  A round (tsu_pt2d_run) = swap_interval K7
+ * sweeps of every walker at the temperature of its slot, every walker's energy (the bits of tsu_ising2d_disorder_energy), then per
+ * ladder one swap pass in the reference's order (gibbs.py:309-323): for i = 0 .. n_temps-2, a / b = the walkers at slots i / i+1,
+ * delta = (1/T_i - 1/T_{i+1}) (E_a - E_b) in float64 (the reference writes E_b - E_a, which inverts the detailed-balance ratio),
+ * accept iff delta >= 0 or u < exp(delta), u = the 53-bit uniform of
+ * Philox(i >> 1, 0, t, TAG_PT_SWAP | k << 8) with key seed (t = the round counter); an accepted swap exchanges the two walkers'
+ * slots, never their spins.  Round trips: a walker reaching slot 0 becomes "bottom" (the walker starting there starts so), a bottom
+ * walker reaching the last slot becomes "top", a top walker reaching slot 0 counts one round trip.  DESIGN.md section 3. */
+typedef struct tsu_pt2d tsu_pt2d;
+int tsu_pt2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int n_temps, int n_ladders, tsu_pt2d** out);
+int tsu_pt2d_destroy(tsu_pt2d* pt);
+/* the same arrays, validation and messages as tsu_ising2d_set_disorder; stored once for all walkers */
+int tsu_pt2d_set_disorder(tsu_pt2d* pt, const float* J_right, const float* J_down, const float* h);
+/* T[slot], n_temps values, each > 0 and finite */
+int tsu_pt2d_set_temperatures(tsu_pt2d* pt, const double* T);
+/* initial 0: every walker from tsu_ising2d_randomize(seed + its index); +1 / -1: all up / down.  Resets slots, counters, statistics. */
+int tsu_pt2d_init(tsu_pt2d* pt, uint64_t seed, int initial);
+/* n_rounds rounds, all enqueued (no synchronisation).  do_swap = 0: sweeps only, no swap pass.  record: after each round's pass, per
+ * slot, E (float64) and sum s (int64) of the walker there, which walker it is, and with two ladders q = sum s^a s^b of the two
+ * ladders' walkers at that slot (the rows of this run replace those of the previous one). */
+int tsu_pt2d_run(tsu_pt2d* pt, int n_rounds, int swap_interval, int do_swap, int record);
+/* the rows of the last run: E, M, walker [round][ladder][slot]; q [round][slot] (two ladders); any pointer may be NULL */
+int tsu_pt2d_history(tsu_pt2d* pt, double* E, int64_t* M, int64_t* q, int32_t* walker);
+/* attempts, accepts [ladder][pair]; round_trips [ladder][walker]; walker_at_slot [ladder][slot]; any pointer may be NULL */
+int tsu_pt2d_stats(tsu_pt2d* pt, int64_t* attempts, int64_t* accepts, int64_t* round_trips, int32_t* walker_at_slot,
+                   uint64_t* sweep_count, uint64_t* round_count);
+/* every walker's E and sum of spins now, indexed [ladder][walker] (synchronises) */
+int tsu_pt2d_energies(tsu_pt2d* pt, double* E, int64_t* sum_s);
+/* spins of the walker now at (ladder, slot): rows x cols int8, row-major */
+int tsu_pt2d_get_spins(tsu_pt2d* pt, int ladder, int slot, int8_t* host);
+int tsu_pt2d_set_spins(tsu_pt2d* pt, int ladder, int slot, const int8_t* host);
+/* sweep-kernel launches so far (one per half-sweep for all walkers) */
+int tsu_pt2d_launch_count(tsu_pt2d* pt, uint64_t* n_launches);
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -102,7 +102,8 @@ enum : uint32_t {
     TSU_TAG_DENSE = 4,
     TSU_TAG_LANGEVIN_RESTART = 5,
     TSU_TAG_SW_BOND = 6,
-    TSU_TAG_SW_FLIP = 7
+    TSU_TAG_SW_FLIP = 7,
+    TSU_TAG_PT_SWAP = 8
 };
 
 struct u32x4 {

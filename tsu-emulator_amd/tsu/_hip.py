@@ -86,6 +86,18 @@ SIGNATURES = {
     "tsu_ising2d_disorder_energy": (C.c_int, [_vp, _f64p]),
     "tsu_ising2d_overlap": (C.c_int, [_vp, _vp, _i64p]),
     "tsu_ising2d_disorder_launch_count": (C.c_int, [_vp, _u64p]),
+    "tsu_pt2d_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "tsu_pt2d_destroy": (C.c_int, [_vp]),
+    "tsu_pt2d_set_disorder": (C.c_int, [_vp, _f32p, _f32p, _f32p]),
+    "tsu_pt2d_set_temperatures": (C.c_int, [_vp, _f64p]),
+    "tsu_pt2d_init": (C.c_int, [_vp, C.c_uint64, C.c_int]),
+    "tsu_pt2d_run": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tsu_pt2d_history": (C.c_int, [_vp, _f64p, _i64p, _i64p, _i32p]),
+    "tsu_pt2d_stats": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i32p, _u64p, _u64p]),
+    "tsu_pt2d_energies": (C.c_int, [_vp, _f64p, _i64p]),
+    "tsu_pt2d_get_spins": (C.c_int, [_vp, C.c_int, C.c_int, _i8p]),
+    "tsu_pt2d_set_spins": (C.c_int, [_vp, C.c_int, C.c_int, _i8p]),
+    "tsu_pt2d_launch_count": (C.c_int, [_vp, _u64p]),
     "tsu_comm_unique_id": (C.c_int, [_u8p]),
     "tsu_comm_create": (C.c_int, [_vp, C.c_int, C.c_int, _u8p, C.POINTER(_vp)]),
     "tsu_comm_destroy": (C.c_int, [_vp]),
@@ -387,6 +399,96 @@ class Lattice:
     def disorder_launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_ising2d_disorder_launch_count(self.h, C.byref(n)))
+        return n.value
+
+
+class TemperingLattice:
+    """tsu_pt2d handle (K7 parallel tempering): n_ladders ladders of n_temps walkers of one rows x cols lattice sharing one
+    disorder.  Walker w of ladder k has Philox key seed + k n_temps + w and starts at slot w."""
+
+    def __init__(self, rows, cols, periodic, n_temps, n_ladders=1, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.rows, self.cols, self.periodic = int(rows), int(cols), bool(periodic)
+        self.n_temps, self.n_ladders = int(n_temps), int(n_ladders)
+        self._recorded = 0
+        h = _vp()
+        self.ctx.check(self.lib.tsu_pt2d_create(self.ctx.h, self.rows, self.cols, int(self.periodic), self.n_temps,
+                                                self.n_ladders, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_pt2d_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def set_disorder(self, J_right, J_down, h=None):
+        shape = (self.rows, self.cols)
+        jr = np.ascontiguousarray(J_right, dtype=np.float32).reshape(shape)
+        jd = np.ascontiguousarray(J_down, dtype=np.float32).reshape(shape)
+        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float32).reshape(shape)
+        self.ctx.check(self.lib.tsu_pt2d_set_disorder(self.h, _ptr(jr, _f32p), _ptr(jd, _f32p),
+                                                      None if hh is None else _ptr(hh, _f32p)))
+
+    def set_temperatures(self, T):
+        t = np.ascontiguousarray(T, dtype=np.float64).ravel()
+        if t.size != self.n_temps:
+            raise ValueError(f"need {self.n_temps} temperatures, got {t.size}")
+        self.ctx.check(self.lib.tsu_pt2d_set_temperatures(self.h, _ptr(t, _f64p)))
+
+    def init(self, seed, initial=0):
+        """initial 0: random (tsu_ising2d_randomize(seed + walker index)); +1 / -1: all up / down."""
+        self.ctx.check(self.lib.tsu_pt2d_init(self.h, int(seed), int(initial)))
+        self._recorded = 0
+
+    def run(self, n_rounds, swap_interval, swap=True, record=True):
+        self.ctx.check(self.lib.tsu_pt2d_run(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record))))
+        self._recorded = int(n_rounds) if record else 0
+
+    def history(self):
+        """The last run's rows: E, M (sum of spins), walker as (n_rounds, n_ladders, n_temps); q as (n_rounds, n_temps) or None."""
+        n, nl, R = self._recorded, self.n_ladders, self.n_temps
+        E = np.zeros((n, nl, R))
+        M = np.zeros((n, nl, R), np.int64)
+        W = np.zeros((n, nl, R), np.int32)
+        q = np.zeros((n, R), np.int64) if nl == 2 else None
+        self.ctx.check(self.lib.tsu_pt2d_history(self.h, _ptr(E, _f64p), _ptr(M, _i64p), None if q is None else _ptr(q, _i64p),
+                                                 _ptr(W, _i32p)))
+        return {"E": E, "M": M, "walker": W, "q": q}
+
+    def stats(self):
+        nl, R = self.n_ladders, self.n_temps
+        att, acc = np.zeros((nl, R - 1), np.int64), np.zeros((nl, R - 1), np.int64)
+        trips, was = np.zeros((nl, R), np.int64), np.zeros((nl, R), np.int32)
+        sw, rd = C.c_uint64(0), C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_pt2d_stats(self.h, _ptr(att, _i64p), _ptr(acc, _i64p), _ptr(trips, _i64p), _ptr(was, _i32p),
+                                               C.byref(sw), C.byref(rd)))
+        return {"attempts": att, "accepts": acc, "round_trips": trips, "walker_at_slot": was, "sweep_count": sw.value,
+                "round_count": rd.value}
+
+    def energies(self):
+        """(E, sum of spins) of every walker now, as (n_ladders, n_temps) arrays indexed by walker."""
+        E = np.zeros((self.n_ladders, self.n_temps))
+        M = np.zeros((self.n_ladders, self.n_temps), np.int64)
+        self.ctx.check(self.lib.tsu_pt2d_energies(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
+        return E, M
+
+    def get_spins(self, ladder, slot):
+        out = np.empty((self.rows, self.cols), dtype=np.int8)
+        self.ctx.check(self.lib.tsu_pt2d_get_spins(self.h, int(ladder), int(slot), _ptr(out, _i8p)))
+        return out
+
+    def set_spins(self, ladder, slot, spins):
+        s = np.ascontiguousarray(spins, dtype=np.int8).reshape(self.rows, self.cols)
+        self.ctx.check(self.lib.tsu_pt2d_set_spins(self.h, int(ladder), int(slot), _ptr(s, _i8p)))
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_pt2d_launch_count(self.h, C.byref(n)))
         return n.value
 
 
