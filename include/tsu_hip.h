@@ -241,6 +241,28 @@ int tsu_pt2d_set_spins(tsu_pt2d* pt, int ladder, int slot, const int8_t* host);
 /* sweep-kernel launches so far (one per half-sweep for all walkers) */
 int tsu_pt2d_launch_count(tsu_pt2d* pt, uint64_t* n_launches);
 
+/* Replica cluster moves (Houdayer's isoenergetic cluster move) between the two ladders' walkers at one slot; needs n_ladders = 2.
+ * One pass, per participating slot i, a / b = the walkers of ladder 0 / 1 now at slot i, q_x = a_x b_x: the sites with q = -1 are
+ * joined to their right and down lattice neighbours with q = -1 (wrapping on a periodic lattice; whatever J is on the bond); the
+ * cluster whose smallest site index r cols + c is (r, c) flips in BOTH walkers iff bit 31 of word c & 3 of
+ * Philox(c >> 2, r, m, TAG_PT_ICM | slot << 8) is set, key = the seed of tsu_pt2d_init, m = the handle's cluster-pass counter (0 at
+ * init, + 1 per pass, one value for all slots of a pass).  E_a + E_b and every q_x are unchanged, so no accept / reject step exists.
+ * The pass helps only while the q = -1 sites do not percolate (site threshold 0.593 of the square lattice); above it one cluster
+ * spans the lattice and the pass comes close to exchanging the two walkers: hence t_max and the statistics.  DESIGN.md section 3.
+ *
+ * every = 0 (the state after create): off, tsu_pt2d_run is what it was, launch for launch.  every >= 1: round t (the handle's round
+ * counter) ends its sweeps with a pass iff t % every == 0, before the energies.  A slot takes part iff T[slot] <= t_max (t_max > 0;
+ * +inf: every slot).  The setting survives tsu_pt2d_init; tsu_pt2d_set_temperatures re-evaluates which slots take part.  Switching
+ * the move off drops its statistics. */
+int tsu_pt2d_set_cluster_moves(tsu_pt2d* pt, int every, double t_max);
+/* one pass now over the participating slots (counter m, then m + 1), enqueued, no synchronisation */
+int tsu_pt2d_cluster_move(tsu_pt2d* pt);
+/* per slot since init: passes taken, clusters found, sites flipped (per walker); flipped / (passes rows cols) near 1/2 says the
+ * q = -1 sites percolate at that slot.  pass_count = m; n_launches = cluster-kernel launches (1 per pass for lattices of at most
+ * 16384 sites, else 3; not counted by tsu_pt2d_launch_count).  Any pointer may be NULL.  Synchronises. */
+int tsu_pt2d_cluster_stats(tsu_pt2d* pt, int64_t* passes, int64_t* clusters, int64_t* flipped, uint64_t* pass_count,
+                           uint64_t* n_launches);
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "ising2d.h"
+#include "uf_dev.h"
 
 namespace {
 
@@ -27,64 +28,10 @@ constexpr int kSmallSites = 16384;   // k6_small: rows * cols at most this (80 K
 constexpr int kSmallThreads = 1024;
 constexpr int kTile = 64;            // default tile edge of the multi-tile route
 constexpr int kLocalThreads = 256;
-constexpr int kBudget = 1 << 20;     // union / find steps one lane may take per call of a union
-
-// ---------------------------------------------------------------- union-find with min-index roots (LDS or HBM)
-template <int SCOPE>
-__device__ __forceinline__ int uf_load(const int* L, int x) {
-    return __hip_atomic_load(L + x, __ATOMIC_RELAXED, SCOPE);
-}
-
-// root of x, halving the path on the way (each halving step is an atomicMin to an ancestor: it can only shorten the path)
-template <int SCOPE>
-__device__ __forceinline__ int uf_find(int* L, int x, int& budget) {
-    int p = uf_load<SCOPE>(L, x);
-    while (p != x) {
-        const int gp = uf_load<SCOPE>(L, p);
-        if (gp == p) return p;
-        __hip_atomic_fetch_min(L + x, gp, __ATOMIC_RELAXED, SCOPE);
-        x = gp;
-        p = uf_load<SCOPE>(L, x);
-        if (--budget < 0) return x;
-    }
-    return x;
-}
-
-// join the trees of a and b: link the larger root under the smaller one.  If that root got a parent meanwhile, atomicMin
-// returned the parent it had: join that parent with the smaller root next (nothing is lost, every index only falls).
-template <int SCOPE>
-__device__ __forceinline__ bool uf_union(int* L, int a, int b, int& budget) {
-    for (;;) {
-        a = uf_find<SCOPE>(L, a, budget);
-        b = uf_find<SCOPE>(L, b, budget);
-        if (budget < 0) return false;
-        if (a == b) return true;
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, SCOPE);
-        if (old == a) return true;
-        a = old;
-        if (--budget < 0) return false;
-    }
-}
-
-__device__ __forceinline__ void raise_err(int* err) {
-    __hip_atomic_store(err, 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // J s s' > 0 and u < thr (thr may be 2^32: 64-bit compare)
 __device__ __forceinline__ bool bond_on(int jsign, int sa, int sb, uint32_t u, uint64_t thr) {
     return jsign * sa * sb > 0 && (uint64_t)u < thr;
-}
-
-__device__ __forceinline__ bool flip_bit(int r, int c, uint32_t t, uint32_t tag, uint32_t k0, uint32_t k1) {
-    const u32x4 w = tsu_philox((uint32_t)c >> 2, (uint32_t)r, t, tag, k0, k1);
-    const int m = c & 3;
-    const uint32_t v = m == 0 ? w.x : (m == 1 ? w.y : (m == 2 ? w.z : w.w));
-    return (v >> 31) != 0;
 }
 
 // ---------------------------------------------------------------- one workgroup per lattice

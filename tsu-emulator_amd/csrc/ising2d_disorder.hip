@@ -30,13 +30,15 @@
 // a sweep reads are shared by W walkers.  k7_pt_energy / k7_pt_energy_final run k7_energy's decomposition per walker (the same
 // bits as the single-lattice call) and sum the spins alongside; k7_pt_swap makes the reference's sequential swap pass per ladder
 // on the device; k7_pt_overlap records q of the two ladders' walkers at each slot.  No host value changes between rounds: a
-// run of many rounds is enqueued without a synchronisation.
+// run of many rounds is enqueued without a synchronisation.  The handle itself is declared in ising2d_pt.h; the replica cluster
+// moves a round may end its sweeps with live in ising2d_icm.hip (the pt2d_icm_* hooks below).
 #include <cmath>
 #include <cstdlib>
 #include <vector>
 
 #include "dense.h"
 #include "ising2d.h"
+#include "ising2d_pt.h"
 
 namespace {
 
@@ -277,7 +279,6 @@ __global__ __launch_bounds__(256) void k7_overlap(const int8_t* __restrict__ a, 
 }
 
 // ------------------------------------------------------------------ parallel tempering
-constexpr int kPtMaxTemps = 256;
 enum : int { kPtNone = 0, kPtBottom = 1, kPtTop = 2 };  // round-trip flag of a walker
 
 struct PTParams {
@@ -548,36 +549,6 @@ unsigned blocks_for(const tsu_ising2d* L) {
 
 }  // namespace
 
-struct tsu_pt2d {
-    tsu_ctx* ctx;
-    int R, nl, nw;                 // temperatures, ladders, walkers (R * nl)
-    tsu_ising2d** lat;             // walker g = ladder * R + w; lat[0] also holds the one disorder
-    int have_T, have_init;
-    uint32_t sweeps, rounds;       // sweeps of every walker and rounds since init
-    unsigned long long launches;   // k7_pt_sweep launches
-    int hist_rounds;               // rows recorded by the last run
-    size_t hist_cap;               // rows the history buffers hold
-    int8_t** d_s;                  // walker -> alloc[cur] of its lattice
-    uint32_t* d_key;               // walker -> (k0, k1)
-    int32_t* d_slot;               // [ladder][walker] -> slot
-    int32_t* d_was;                // [ladder][slot] -> walker
-    int32_t* d_flag;               // [ladder][walker] -> round-trip flag
-    double* d_T;                   // slot -> T
-    float* d_c32;                  // slot -> fl32(2 / T)
-    long long* d_att;              // [ladder][pair]
-    long long* d_acc;
-    long long* d_trips;            // [ladder][walker]
-    double* d_part;                // [walker][kEnergyBlocks] energy partials
-    long long* d_ipart;            // [walker][kEnergyBlocks] sum-of-spin partials
-    double* d_E;                   // walker -> E of the last energy pass
-    long long* d_M;                // walker -> sum of spins
-    double* d_hE;                  // [round][ladder][slot]
-    long long* d_hM;
-    int32_t* d_hW;
-    long long* d_hq;               // [round][slot] (two ladders)
-    uint32_t key0, key1;           // Philox key of the swap uniforms (the seed)
-};
-
 namespace {
 
 void pt_free_history(tsu_pt2d* P) {
@@ -597,6 +568,7 @@ void pt_free(tsu_pt2d* P) {
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     pt_free_history(P);
+    pt2d_icm_free(P);
     if (P->lat) {
         for (int g = 0; g < P->nw; ++g)
             if (P->lat[g]) (void)tsu_ising2d_destroy(P->lat[g]);
@@ -894,11 +866,12 @@ int tsu_pt2d_set_temperatures(tsu_pt2d* P, const double* T) {
         t[i] = T[i];
         c[i] = (float)(2.0 / T[i]);
     }
+    for (int i = 0; i < P->R; ++i) P->h_T[i] = t[i];
     TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_T, t, P->R * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_c32, c, P->R * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     P->have_T = 1;
-    return TSU_OK;
+    return pt2d_icm_slots(P);  // which slots take part in the cluster moves (nothing to do while they are off)
 }
 
 int tsu_pt2d_init(tsu_pt2d* P, uint64_t seed, int initial) {
@@ -916,7 +889,9 @@ int tsu_pt2d_init(tsu_pt2d* P, uint64_t seed, int initial) {
         if (rc != TSU_OK) return rc;
     }
     TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_key, key.data(), key.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    const int rc = pt_reset(P);  // synchronises before `key` goes
+    int rc = pt_reset(P);  // synchronises before `key` goes
+    if (rc != TSU_OK) return rc;
+    rc = pt2d_icm_reset(P);
     if (rc != TSU_OK) return rc;
     P->key0 = (uint32_t)seed;
     P->key1 = (uint32_t)(seed >> 32);
@@ -936,6 +911,7 @@ int tsu_pt2d_run(tsu_pt2d* P, int n_rounds, int swap_interval, int do_swap, int 
                 swap_interval);
     TSU_REQUIRE(ctx, (uint64_t)P->sweeps + (uint64_t)n_rounds * (uint64_t)swap_interval <= (1ull << 31), "pt2d_run: sweep counter overflow");
     TSU_REQUIRE(ctx, (uint64_t)P->rounds + (uint64_t)n_rounds <= 0xFFFFFFFFull, "pt2d_run: round counter overflow");
+    TSU_REQUIRE(ctx, (uint64_t)P->icm_passes + (uint64_t)n_rounds <= 0xFFFFFFFFull, "pt2d_run: cluster-pass counter overflow");
     const int R = P->R, nl = P->nl;
     if (record && P->hist_cap < (size_t)n_rounds) {
         pt_free_history(P);
@@ -976,6 +952,10 @@ int tsu_pt2d_run(tsu_pt2d* P, int n_rounds, int swap_interval, int do_swap, int 
                 P->launches += 1;
             }
         P->sweeps += (uint32_t)swap_interval;
+        if (P->icm_every >= 1 && P->rounds % (uint32_t)P->icm_every == 0) {  // replica cluster moves: the energies see the moved spins
+            const int rc = pt2d_icm_enqueue(P);
+            if (rc != TSU_OK) return rc;
+        }
         if (do_swap || record) {
             pt_enqueue_energies(P, p);
             const size_t row = (size_t)t * nl * R;

@@ -98,6 +98,9 @@ SIGNATURES = {
     "tsu_pt2d_get_spins": (C.c_int, [_vp, C.c_int, C.c_int, _i8p]),
     "tsu_pt2d_set_spins": (C.c_int, [_vp, C.c_int, C.c_int, _i8p]),
     "tsu_pt2d_launch_count": (C.c_int, [_vp, _u64p]),
+    "tsu_pt2d_set_cluster_moves": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "tsu_pt2d_cluster_move": (C.c_int, [_vp]),
+    "tsu_pt2d_cluster_stats": (C.c_int, [_vp, _i64p, _i64p, _i64p, _u64p, _u64p]),
     "tsu_comm_unique_id": (C.c_int, [_u8p]),
     "tsu_comm_create": (C.c_int, [_vp, C.c_int, C.c_int, _u8p, C.POINTER(_vp)]),
     "tsu_comm_destroy": (C.c_int, [_vp]),
@@ -490,6 +493,23 @@ class TemperingLattice:
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_pt2d_launch_count(self.h, C.byref(n)))
         return n.value
+
+    def set_cluster_moves(self, every, t_max=float("inf")):
+        """Replica cluster moves between the two ladders: a pass after the sweeps of every round t with t % every == 0 over the
+        slots with T <= t_max; every = 0 switches them off."""
+        self.ctx.check(self.lib.tsu_pt2d_set_cluster_moves(self.h, int(every), float(t_max)))
+
+    def cluster_move(self):
+        """One pass now (enqueued)."""
+        self.ctx.check(self.lib.tsu_pt2d_cluster_move(self.h))
+
+    def cluster_stats(self):
+        R = self.n_temps
+        passes, clusters, flipped = np.zeros(R, np.int64), np.zeros(R, np.int64), np.zeros(R, np.int64)
+        m, nl = C.c_uint64(0), C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_pt2d_cluster_stats(self.h, _ptr(passes, _i64p), _ptr(clusters, _i64p), _ptr(flipped, _i64p),
+                                                       C.byref(m), C.byref(nl)))
+        return {"passes": passes, "clusters": clusters, "flipped": flipped, "pass_count": m.value, "launches": nl.value}
 
 
 def sweep_batch(lattices, n_sweeps, seeds, sweep0s, replicas=None):

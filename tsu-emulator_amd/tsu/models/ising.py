@@ -721,6 +721,23 @@ def _scan_summary(out: dict, N: int, Ms, Es, Qs=None) -> dict:
 _PT_INITIAL = {"random": 0, "up": 1, "down": -1}
 
 
+def _cluster_move_args(cluster_moves, cluster_max_temperature, ladders: int):
+    """(every, t_max) of the replica cluster moves, validated on the host."""
+    if isinstance(cluster_moves, bool) or not isinstance(cluster_moves, (int, np.integer)) or cluster_moves < 0:
+        raise ValueError("cluster_moves must be an integer >= 0 (0: off; n: a pass after the sweeps of every n-th round)")
+    t_max = float("inf")
+    if cluster_max_temperature is not None:
+        try:
+            t_max = float(cluster_max_temperature)
+        except (TypeError, ValueError):
+            raise ValueError("cluster_max_temperature must be a positive number") from None
+        if not t_max > 0:
+            raise ValueError("cluster_max_temperature must be a positive number")
+    if cluster_moves >= 1 and ladders != 2:
+        raise ValueError("cluster moves exchange clusters between the two replicas at one temperature: they need ladders=2")
+    return int(cluster_moves), t_max
+
+
 class LatticeTempering:
     """Parallel tempering (replica exchange) of a disordered lattice on the GPU (K7, physical mode).
 
@@ -731,10 +748,20 @@ class LatticeTempering:
     ``swap_interval`` times at the temperature of its slot, computes every energy and makes one pass of swap attempts over the
     adjacent slots of each ladder in the reference's order and rule (``GibbsSampler.parallel_tempering``, gibbs.py:309-323), all on
     the device without a host synchronisation.  A swap exchanges the walkers' temperatures, never their spins.
+
+    ``cluster_moves=n >= 1`` (needs ``ladders=2``) adds Houdayer's isoenergetic cluster move (Eur. Phys. J. B 22, 479 (2001)): every
+    n-th round, after the sweeps and before the energies, the two replicas at each temperature ``<= cluster_max_temperature``
+    (default: all) exchange randomly chosen connected clusters of the sites where they differ (``q_x = a_x b_x = -1``), each
+    cluster with probability 1/2.  The sum of the two energies and every ``q_x`` are unchanged, so the move needs no accept / reject
+    step; it is a rearrangement between the replicas that the single-spin sweeps would take very long to find.  It is useful only
+    while the ``q = -1`` sites do not percolate (site threshold of the square lattice, 0.593): above that one cluster spans the
+    lattice and the move is close to exchanging the two replicas, which changes nothing.  That is physics, not a fault; it is why
+    the cut-off exists, and ``cluster_stats`` shows it: ``flipped / (passes * N)`` near 1/2 at a slot says it percolates there.
     """
 
     def __init__(self, size, temperatures, *, couplings=None, field=None, coupling: float = 1.0, external_field: float = 0.0,
-                 periodic: bool = True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1):
+                 periodic: bool = True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1,
+                 cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None):
         self.rows, self.cols = (size, size) if np.isscalar(size) else tuple(size)
         self.n_spins = self.rows * self.cols
         T = np.asarray(temperatures, dtype=float).ravel()
@@ -746,6 +773,7 @@ class LatticeTempering:
             raise ValueError("ladders must be 1 or 2")
         if initial not in _PT_INITIAL:
             raise ValueError("initial must be 'random', 'up' or 'down'")
+        self.cluster_moves, self.cluster_max_temperature = _cluster_move_args(cluster_moves, cluster_max_temperature, ladders)
         self.periodic = bool(periodic)
         self._disorder = _disorder_arrays(self.rows, self.cols, self.periodic, float(coupling), float(external_field), "physical",
                                           couplings, field)
@@ -756,6 +784,8 @@ class LatticeTempering:
         self._pt = _hip.TemperingLattice(self.rows, self.cols, self.periodic, T.size, self.ladders)
         self._pt.set_disorder(*self._disorder)
         self._pt.set_temperatures(T)
+        if self.cluster_moves:
+            self._pt.set_cluster_moves(self.cluster_moves, self.cluster_max_temperature)
         self._pt.init(self.seed, _PT_INITIAL[initial])
 
     def run(self, n_rounds: int, swap_interval: int = 10, swap: bool = True, record: bool = True):
@@ -772,6 +802,16 @@ class LatticeTempering:
         if h["q"] is not None:
             out["q"] = h["q"]
         return out
+
+    def cluster_move(self) -> None:
+        """One replica cluster pass now over the participating slots (needs ``cluster_moves >= 1``)."""
+        self._pt.cluster_move()
+
+    @property
+    def cluster_stats(self) -> dict:
+        """Per slot since the start: ``passes`` taken, ``clusters`` found and sites ``flipped`` (per replica) by the cluster moves."""
+        st = self._pt.cluster_stats()
+        return {k: st[k] for k in ("passes", "clusters", "flipped")}
 
     @property
     def acceptance(self) -> np.ndarray:
@@ -812,24 +852,27 @@ class LatticeTempering:
 
 def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                    measure_every: int = 10, periodic: bool = True, seed: int = 0, bias_mode: str = "physical",
-                   initial: str = "up", *, couplings=None, field=None, replicas: int = 1, swap: bool = True) -> dict:
+                   initial: str = "up", *, couplings=None, field=None, replicas: int = 1, swap: bool = True,
+                   cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None) -> dict:
     """:func:`temperature_scan` of a disordered lattice with replica exchange between the temperatures (:class:`LatticeTempering`).
 
     One round = ``measure_every`` sweeps of every walker + one swap pass; ``n_equilibrate`` (a multiple of ``measure_every``)
     sweeps of rounds, then ``n_measure`` recorded rounds.  Returns temperature_scan's keys, computed with the same expressions from
     the walker at each temperature (``overlap``, ``overlap_sq``, ``binder`` for ``replicas=2``), plus ``swap_acceptance`` (per
     adjacent pair, ladders pooled) and ``round_trips`` (all walkers).  ``swap=False`` reproduces ``temperature_scan`` with the same
-    arguments exactly.
+    arguments exactly.  ``cluster_moves`` / ``cluster_max_temperature`` as for :class:`LatticeTempering` (``replicas=2``); they add
+    ``cluster_flipped``: the mean fraction of the sites a pass flipped per temperature, NaN where the slot does not take part.
     """
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
+    _cluster_move_args(cluster_moves, cluster_max_temperature, replicas)
     if int(measure_every) < 1 or int(n_equilibrate) % int(measure_every):
         raise ValueError("n_equilibrate must be a multiple of measure_every")
     rows, cols = (size, size) if np.isscalar(size) else tuple(size)
     jr, jd, h = _disorder_arrays(rows, cols, bool(periodic), float(coupling), 0.0, bias_mode, couplings, field)
     temperatures = np.asarray(temperatures, dtype=float)
     pt = LatticeTempering((rows, cols), temperatures, couplings=(jr, jd), field=h, periodic=periodic, seed=seed, initial=initial,
-                          ladders=replicas)
+                          ladders=replicas, cluster_moves=cluster_moves, cluster_max_temperature=cluster_max_temperature)
     try:
         pt.run(int(n_equilibrate) // int(measure_every), int(measure_every), swap=swap, record=False)
         pt.run(int(n_measure), int(measure_every), swap=swap, record=True)
@@ -843,6 +886,10 @@ def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int
         out = _scan_summary(out, N, Ms, Es, Qs)
         out["swap_acceptance"] = pt.acceptance
         out["round_trips"] = pt.round_trips
+        if pt.cluster_moves:
+            st = pt.cluster_stats
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out["cluster_flipped"] = st["flipped"] / (st["passes"] * float(N))
     finally:
         pt._pt.close()
     return out
