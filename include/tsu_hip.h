@@ -263,6 +263,47 @@ int tsu_pt2d_cluster_move(tsu_pt2d* pt);
 int tsu_pt2d_cluster_stats(tsu_pt2d* pt, int64_t* passes, int64_t* clusters, int64_t* flipped, uint64_t* pass_count,
                            uint64_t* n_launches);
 
+/* ------------------------------------------------------------------ K8: 3-D lattice with quenched disorder
+ * No reference counterpart (the reference's IsingGrid is 2-D).  Heat-bath sweeps of a whole depth x rows x cols (D x R x C) cubic
+ * lattice of +-1 int8 spins with per-bond couplings and per-site fields, physical mode.  Site (z, r, c), row-major with c fastest.
+ * fp32 arrays of shape (D, R, C): J_right[z,r,c] couples (z,r,c)-(z,r,c+1), J_down[z,r,c] couples (z,r,c)-(z,r+1,c),
+ * J_layer[z,r,c] couples (z,r,c)-(z+1,r,c), h[z,r,c] is the site's field.  periodic_mask has one bit per axis; a periodic axis
+ * wraps to index 0 and must have an even length >= 4 (2-colourability; length 2 would make a double bond: TSU_E_UNSUPPORTED);
+ * on an open axis the last slice of that axis's J must be 0 (TSU_E_INVALID otherwise).  D R < 2^31, C <= 2^30.
+ * Decision rule (bit-exact):
+ *   colour of a site = (z + r + c) & 1; sweep t = half-sweep hs = 2 t (colour 0), then hs = 2 t + 1 (colour 1);
+ *   f = ((((((J_layer[z-1] s[z-1]) + J_layer[z] s[z+1]) + J_down[r-1] s[r-1]) + J_down[r] s[r+1]) + J_right[c-1] s[c-1])
+ *       + J_right[c] s[c+1]) + h in float64, in this order, a neighbour missing on an open axis skipped (no +0.0);
+ *   x = 2 f / T, p = sigmoid(x) clamped at +-20, thr = floor(p 2^32 + 1/2); the site becomes +1 iff u < thr;
+ *   u = K1's 32-bit site uniform with the global row rho = z R + r in place of r: hi16 / lo16 from
+ *       Philox(c >> 4, rho, hs, TAG_ISING_HI / TAG_ISING_LO | replica << 8), key = seed, halves and the flipped top bit as in K7.
+ * With D = 1 and an open z axis the rule is K7's: the spins equal tsu_ising2d_disorder_sweep's bit for bit. */
+#define TSU_PERIODIC_Z 1
+#define TSU_PERIODIC_R 2
+#define TSU_PERIODIC_C 4
+typedef struct tsu_ising3d tsu_ising3d;
+int tsu_ising3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_mask, tsu_ising3d** out);
+int tsu_ising3d_destroy(tsu_ising3d* lat);
+/* +-1 int8 spins of the whole lattice, (D, R, C) row-major, no padding.  Synchronous. */
+int tsu_ising3d_set_spins(tsu_ising3d* lat, const int8_t* host);
+int tsu_ising3d_get_spins(tsu_ising3d* lat, int8_t* host);
+/* the spins tsu_ising2d_randomize gives a (D R) x C lattice, reshaped (asynchronous) */
+int tsu_ising3d_randomize(tsu_ising3d* lat, uint64_t seed, uint32_t replica);
+int tsu_ising3d_fill(tsu_ising3d* lat, int8_t value);
+/* Copy the disorder to the device (buffers allocated on first use, freed by tsu_ising3d_destroy).  h == NULL: zero field.
+ * Non-finite values, or a nonzero last slice of an open axis's J: TSU_E_INVALID.  Synchronous. */
+int tsu_ising3d_set_disorder(tsu_ising3d* lat, const float* J_right, const float* J_down, const float* J_layer, const float* h /*nullable*/);
+/* n_sweeps sweeps at temperature T with sweep counters sweep0 .. sweep0+n_sweeps-1, one launch per half-sweep.  Asynchronous. */
+int tsu_ising3d_sweep(tsu_ising3d* lat, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica);
+/* E = -sum_bonds J_b s_i s_j - sum_i h_i s_i in float64, summed in an order that depends on the shape only (the same bits on
+ * every call). */
+int tsu_ising3d_energy(tsu_ising3d* lat, double* E);
+int tsu_ising3d_sum_spins(tsu_ising3d* lat, int64_t* sum_s);
+/* q = sum_i s^a_i s^b_i of two lattices of one shape and context */
+int tsu_ising3d_overlap(tsu_ising3d* a, tsu_ising3d* b, int64_t* q);
+/* k8_sweep launches issued for this lattice so far */
+int tsu_ising3d_launch_count(tsu_ising3d* lat, uint64_t* n_launches);
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "dense.h"
+#include "disorder_dev.h"
 #include "ising2d.h"
 #include "ising2d_pt.h"
 
@@ -56,48 +57,7 @@ struct K7Params {
     uint32_t k0, k1, hs, tag_hi, tag_lo;
 };
 
-__device__ __forceinline__ int sbyte(const uint4& v, int i) {
-    const uint32_t w = i < 4 ? v.x : (i < 8 ? v.y : (i < 12 ? v.z : v.w));
-    return (int)(int8_t)((w >> (8 * (i & 3))) & 0xFFu);
-}
-
-__device__ __forceinline__ float fat(const float4* a, int i) {
-    const float4 v = a[i >> 2];
-    const int k = i & 3;
-    return k == 0 ? v.x : (k == 1 ? v.y : (k == 2 ? v.z : v.w));
-}
-
-__device__ __forceinline__ void load16f(const float* p, float4* a) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] = reinterpret_cast<const float4*>(p)[k];
-}
-
-// Threshold of the contract in float64 (sigmoid clamped at +-20 as tsu_ising2d_thresholds / gibbs.py:73-77)
-__device__ __forceinline__ uint64_t exact_thr(double f, double T) {
-    const double x = (2.0 * f) / T;
-    const double p = x > 20.0 ? 1.0 : (x < -20.0 ? 0.0 : 1.0 / (1.0 + exp(-x)));
-    return (uint64_t)floor(p * 4294967296.0 + 0.5);
-}
-
-// fp32 screen.  Returns +1 (u < thr for every low half), -1 (u >= thr for every low half) or 0 (decide exactly).
-// t = p32 2^16 is compared with the hi16 uniform: u in [hi 2^16, hi 2^16 + 65535] is below thr for sure when
-// t - dt >= hi + 1 and not below it when t + dt <= hi, dt a bound of |t - thr / 2^16|.  With u = 2^-24, S = the sum of the
-// |terms| and A = 2 S / T:  four fp32 additions err by <= 4 u S; times fl(2 / T) adds 2 u |x|: |dx| <= 7 u A.  __expf
-// (v_exp_f32 on x log2 e) errs by <= (|x| + 2) u relative, so e = exp(-x) by <= (9 A + 4) u relative (|x| <= A);
-// p = rcp(1 + e) moves by p (1 - p) <= 1/4 of that plus 3 u p of its own rounding: |dp| <= (2.25 A + 4) u + 3 u.  The
-// +-20 clamp of the exact p adds 2.1e-9 = 2^-28.9, and the rounding of thr half a unit of 2^-32.  In units of 2^-16:
-// dt <= ((2.25 A + 7) + 2^-4.9) / 256 + 2^-17 < (A + 4) / 64 = the margin below (a factor >= 1.7 to spare).  Non-finite
-// A or t (huge disorder, tiny T) fail both comparisons and go to the exact branch.
-__device__ __forceinline__ int screen(float f32, float a32, float c32, uint32_t hi) {
-    const float x = f32 * c32;
-    const float A = a32 * fabsf(c32);
-    const float t = __builtin_amdgcn_rcpf(1.0f + __expf(-x)) * 65536.0f;
-    const float m = (A + 4.0f) * (1.0f / 64.0f);
-    const float h = (float)hi;
-    if (t >= h + 1.0f + m) return 1;
-    if (t <= h - m) return -1;
-    return 0;
-}
+// sbyte, fat, load16f, exact_thr and screen (with the derivation of its margin) live in disorder_dev.h, shared with K8
 
 // one octet of the colour whose sites sit at chunk positions PAR, PAR + 2, ..
 template <int PAR>

@@ -29,7 +29,9 @@ from .models import (  # noqa: F401
     IsingGrid,
     IsingModel,
     IsingModel2D,
+    IsingModel3D,
     demonstrate_phase_transition,
+    temperature_scan_3d,
 )
 
 __all__ = [
@@ -37,4 +39,5 @@ __all__ = [
     "ConfigurationError", "SamplingError", "QuadraticEnergy", "QuadraticForm", "MixtureEnergy",
     "GibbsSampler", "GibbsConfig", "HardwareEmulator",
     "IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "demonstrate_phase_transition",
+    "IsingModel3D", "temperature_scan_3d",
 ]

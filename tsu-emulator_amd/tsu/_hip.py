@@ -101,6 +101,18 @@ SIGNATURES = {
     "tsu_pt2d_set_cluster_moves": (C.c_int, [_vp, C.c_int, C.c_double]),
     "tsu_pt2d_cluster_move": (C.c_int, [_vp]),
     "tsu_pt2d_cluster_stats": (C.c_int, [_vp, _i64p, _i64p, _i64p, _u64p, _u64p]),
+    "tsu_ising3d_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "tsu_ising3d_destroy": (C.c_int, [_vp]),
+    "tsu_ising3d_set_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_ising3d_get_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_ising3d_randomize": (C.c_int, [_vp, C.c_uint64, C.c_uint32]),
+    "tsu_ising3d_fill": (C.c_int, [_vp, C.c_int8]),
+    "tsu_ising3d_set_disorder": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p]),
+    "tsu_ising3d_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_ising3d_energy": (C.c_int, [_vp, _f64p]),
+    "tsu_ising3d_sum_spins": (C.c_int, [_vp, _i64p]),
+    "tsu_ising3d_overlap": (C.c_int, [_vp, _vp, _i64p]),
+    "tsu_ising3d_launch_count": (C.c_int, [_vp, _u64p]),
     "tsu_comm_unique_id": (C.c_int, [_u8p]),
     "tsu_comm_create": (C.c_int, [_vp, C.c_int, C.c_int, _u8p, C.POINTER(_vp)]),
     "tsu_comm_destroy": (C.c_int, [_vp]),
@@ -402,6 +414,88 @@ class Lattice:
     def disorder_launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_ising2d_disorder_launch_count(self.h, C.byref(n)))
+        return n.value
+
+
+def periodic_axes(periodic):
+    """(p_z, p_r, p_c) from a bool (all three axes) or a triple of bools."""
+    if isinstance(periodic, (bool, np.bool_)):
+        return (bool(periodic),) * 3
+    p = tuple(bool(x) for x in periodic)
+    if len(p) != 3:
+        raise ValueError("periodic must be a bool or a triple (p_z, p_r, p_c)")
+    return p
+
+
+class Lattice3D:
+    """tsu_ising3d handle (K8): a depth x rows x cols lattice of +-1 int8 spins with per-bond couplings and per-site fields.
+    ``periodic``: a bool or a triple (p_z, p_r, p_c)."""
+
+    def __init__(self, depth, rows, cols, periodic=False, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.depth, self.rows, self.cols = int(depth), int(rows), int(cols)
+        self.shape = (self.depth, self.rows, self.cols)
+        self.periodic = periodic_axes(periodic)
+        mask = sum(1 << a for a in range(3) if self.periodic[a])
+        h = _vp()
+        self.ctx.check(self.lib.tsu_ising3d_create(self.ctx.h, self.depth, self.rows, self.cols, mask, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_ising3d_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():  # at interpreter exit the process teardown frees the device memory
+            self.close()
+
+    def set_spins(self, spins):
+        s = np.ascontiguousarray(spins, dtype=np.int8).reshape(self.shape)
+        self.ctx.check(self.lib.tsu_ising3d_set_spins(self.h, _ptr(s, _i8p)))
+
+    def get_spins(self):
+        out = np.empty(self.shape, dtype=np.int8)
+        self.ctx.check(self.lib.tsu_ising3d_get_spins(self.h, _ptr(out, _i8p)))
+        return out
+
+    def randomize(self, seed, replica=0):
+        self.ctx.check(self.lib.tsu_ising3d_randomize(self.h, int(seed), int(replica)))
+
+    def fill(self, value):
+        self.ctx.check(self.lib.tsu_ising3d_fill(self.h, int(value)))
+
+    def set_disorder(self, J_right, J_down, J_layer, h=None):
+        """K8 quenched disorder: (depth, rows, cols) arrays, rounded once to fp32 (h=None: zero field)."""
+        jr, jd, jl = (np.ascontiguousarray(a, dtype=np.float32).reshape(self.shape) for a in (J_right, J_down, J_layer))
+        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float32).reshape(self.shape)
+        self.ctx.check(self.lib.tsu_ising3d_set_disorder(self.h, _ptr(jr, _f32p), _ptr(jd, _f32p), _ptr(jl, _f32p),
+                                                         None if hh is None else _ptr(hh, _f32p)))
+
+    def sweep(self, T, n_sweeps, seed, sweep0=0, replica=0):
+        """n_sweeps K8 heat-bath sweeps at temperature T (sweep counters sweep0 ..)."""
+        self.ctx.check(self.lib.tsu_ising3d_sweep(self.h, float(T), int(n_sweeps), int(seed), int(sweep0), int(replica)))
+
+    def energy(self):
+        e = C.c_double(0)
+        self.ctx.check(self.lib.tsu_ising3d_energy(self.h, C.byref(e)))
+        return e.value
+
+    def sum_spins(self):
+        m = C.c_int64(0)
+        self.ctx.check(self.lib.tsu_ising3d_sum_spins(self.h, C.byref(m)))
+        return m.value
+
+    def overlap(self, other):
+        """sum_i s_i s'_i with another lattice of the same shape."""
+        q = C.c_int64(0)
+        self.ctx.check(self.lib.tsu_ising3d_overlap(self.h, other.h, C.byref(q)))
+        return q.value
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_ising3d_launch_count(self.h, C.byref(n)))
         return n.value
 
 

@@ -718,6 +718,186 @@ def _scan_summary(out: dict, N: int, Ms, Es, Qs=None) -> dict:
     return out
 
 
+def _disorder_arrays_3d(shape, periodic, coupling: float, external_field: float, couplings, field):
+    """Validate K8 disorder (before any device call) and round it once to fp32: (J_right, J_down, J_layer, h or None).
+    ``periodic`` is the triple (p_z, p_r, p_c)."""
+    if couplings is not None and coupling != 1.0:
+        raise ValueError("give either couplings=(J_right, J_down, J_layer) or a scalar coupling, not both")
+    if field is not None and external_field != 0.0:
+        raise ValueError("give either field= or a non-zero external_field, not both")
+    for p, n, name in zip(periodic, shape, ("depth", "rows", "cols")):
+        if p and (n % 2 or n < 4):
+            raise _hip.UnsupportedError(f"a periodic axis needs an even length >= 4 ({name} = {n})")
+
+    def arr(a, name):
+        a = np.asarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"{name} must be finite")
+        with np.errstate(over="ignore"):
+            a32 = a.astype(np.float32)
+        if not np.all(np.isfinite(a32)):
+            raise ValueError(f"{name} overflows float32")
+        return a32
+
+    if couplings is not None:
+        if len(couplings) != 3:
+            raise ValueError("couplings must be a triple (J_right, J_down, J_layer)")
+        jr, jd, jl = arr(couplings[0], "J_right"), arr(couplings[1], "J_down"), arr(couplings[2], "J_layer")
+    else:
+        if not np.isfinite(np.float32(coupling)):
+            raise ValueError("coupling must be finite in float32")
+        jr, jd, jl = (np.full(shape, coupling, dtype=np.float32) for _ in range(3))
+        if not periodic[2]:
+            jr[:, :, -1] = 0.0
+        if not periodic[1]:
+            jd[:, -1, :] = 0.0
+        if not periodic[0]:
+            jl[-1, :, :] = 0.0
+    if not periodic[2] and np.any(jr[:, :, -1] != 0):
+        raise ValueError("open cols axis: the last column of J_right must be 0")
+    if not periodic[1] and np.any(jd[:, -1, :] != 0):
+        raise ValueError("open rows axis: the last row of J_down must be 0")
+    if not periodic[0] and np.any(jl[-1, :, :] != 0):
+        raise ValueError("open depth axis: the last layer of J_layer must be 0")
+    if field is not None:
+        h = arr(field, "field")
+    else:
+        if not np.isfinite(np.float32(external_field)):
+            raise ValueError("external_field must be finite in float32")
+        h = np.full(shape, external_field, dtype=np.float32) if external_field != 0.0 else None
+    return jr, jd, jl, h
+
+
+def _shape_3d(size):
+    shape = (size,) * 3 if np.isscalar(size) else tuple(int(n) for n in size)
+    if len(shape) != 3 or min(shape) < 1:
+        raise ValueError(f"size must be an int or (depth, rows, cols) of positive ints, got {size!r}")
+    return tuple(int(n) for n in shape)
+
+
+class IsingModel3D:
+    """A cubic lattice with quenched disorder that lives on the GPU between calls (K8; physical mode).
+
+    ``IsingModel3D(size=(D, R, C), couplings=(J_right, J_down, J_layer), field=h, temperature=T)``: ``(D, R, C)`` arrays,
+    ``J_right[z, r, c]`` couples (z, r, c) to (z, r, c+1), ``J_down`` to (z, r+1, c), ``J_layer`` to (z+1, r, c), ``field`` is the
+    site's field.  ``periodic`` is a bool or a triple (p_z, p_r, p_c); a periodic axis wraps and needs an even length >= 4, on an
+    open axis the last slice of that axis's J must be 0.  Uniform ``coupling=`` / ``external_field=`` are the constant-array case
+    of the same kernel.  The arrays are rounded once to float32 (``disorder`` returns the rounded copies).
+    ``gibbs_update()`` = one checkerboard heat-bath sweep; ``energy()`` / ``magnetization()`` / ``overlap(other)`` are device
+    reductions; ``equilibrate(T)`` sets the temperature, runs ``n_sweeps`` sweeps and returns ``self``.
+    """
+
+    def __init__(self, size, coupling: float = 1.0, temperature: float = 1.0, periodic=True, external_field: float = 0.0,
+                 seed: Optional[int] = None, initial: str = "random", *, couplings=None, field=None):
+        if not temperature > 0:
+            raise ValueError("Temperature must be positive")
+        self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
+        self.n_spins = self.depth * self.rows * self.cols
+        self.coupling = float(coupling)
+        self.temperature = float(temperature)
+        self.external_field = float(external_field)
+        self.periodic = _hip.periodic_axes(periodic)
+        if initial not in ("random", "up", "down"):
+            raise ValueError("initial must be 'random', 'up' or 'down'")
+        self._disorder = _disorder_arrays_3d(self.shape, self.periodic, self.coupling, self.external_field, couplings, field)
+        self.seed = int(seed) if seed is not None else (
+            int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
+        self.sweep_count = 0
+        self._lat = _hip.Lattice3D(self.depth, self.rows, self.cols, self.periodic)
+        if initial == "random":
+            self._lat.randomize(self.seed)
+        else:
+            self._lat.fill(1 if initial == "up" else -1)
+        self._lat.set_disorder(*self._disorder)
+
+    @property
+    def disorder(self):
+        """(J_right, J_down, J_layer, h or None) as stored on the device (float32 copies)."""
+        return tuple(None if a is None else a.copy() for a in self._disorder)
+
+    def set_disorder(self, couplings=None, field=None) -> "IsingModel3D":
+        """Replace the quenched disorder (``couplings=None``: uniform ``coupling``; ``field=None``: ``external_field``);
+        the spins and counters are kept."""
+        d = _disorder_arrays_3d(self.shape, self.periodic, self.coupling, self.external_field, couplings, field)
+        self._lat.set_disorder(*d)
+        self._disorder = d
+        return self
+
+    def gibbs_update(self, n_sweeps: int = 1) -> "IsingModel3D":
+        self._lat.sweep(self.temperature, int(n_sweeps), self.seed, self.sweep_count)
+        self.sweep_count += int(n_sweeps)
+        return self
+
+    def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000) -> "IsingModel3D":
+        if temperature is not None:
+            if not temperature > 0:
+                raise ValueError("Temperature must be positive")
+            self.temperature = float(temperature)
+        return self.gibbs_update(n_sweeps)
+
+    def magnetization(self) -> float:
+        return self._lat.sum_spins() / self.n_spins
+
+    def energy(self) -> float:
+        return self._lat.energy()
+
+    def overlap(self, other: "IsingModel3D") -> float:
+        """q / N = sum_i s_i s'_i / N with another model of the same shape (a device reduction)."""
+        if other.shape != self.shape:
+            raise ValueError(f"overlap needs equal shapes, got {self.shape} and {other.shape}")
+        return self._lat.overlap(other._lat) / self.n_spins
+
+    @property
+    def spins(self) -> np.ndarray:
+        return self._lat.get_spins()
+
+    @spins.setter
+    def spins(self, value):
+        v = np.asarray(value).reshape(self.shape)
+        if not np.all((v == 1) | (v == -1)):
+            raise ValueError("spins must be +1 / -1")
+        self._lat.set_spins(v.astype(np.int8))
+
+
+def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
+                        measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", *, couplings=None, field=None,
+                        replicas: int = 1) -> dict:
+    """:func:`temperature_scan` for a cubic lattice (K8): one :class:`IsingModel3D` per temperature stays on the device and
+    |M|, E/N, chi and C come from the device reductions.  ``couplings`` / ``field``: the same quenched disorder at every
+    temperature.  Model i of replica k has seed ``seed + k len(temperatures) + i``.  ``replicas=2``: the result gains
+    ``overlap`` = <|q|>, ``overlap_sq`` = <q^2> and ``binder`` = (3 - <q^4> / <q^2>^2) / 2 of q = overlap / N; the other keys are
+    those of the first replica."""
+    if replicas not in (1, 2):
+        raise ValueError("replicas must be 1 or 2")
+    temperatures = np.asarray(temperatures, dtype=float)
+    if np.any(~(temperatures > 0)):
+        raise ValueError("Temperature must be positive")
+    shape = _shape_3d(size)
+    # validated once, before any device call
+    disorder = _disorder_arrays_3d(shape, _hip.periodic_axes(periodic), float(coupling), 0.0, couplings, field)
+    out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
+    out["temperatures"] = temperatures
+    nT = len(temperatures)
+    models = [IsingModel3D(shape, temperature=float(T), periodic=periodic, seed=seed + k * nT + i, initial=initial,
+                           couplings=disorder[:3], field=disorder[3])
+              for k in range(replicas) for i, T in enumerate(temperatures)]
+    for m in models:
+        m.gibbs_update(int(n_equilibrate))
+    Ms, Es, Qs = np.zeros((nT, n_measure)), np.zeros((nT, n_measure)), np.zeros((nT, n_measure))
+    for j in range(n_measure if models else 0):
+        for m in models:
+            m.gibbs_update(int(measure_every))
+        for i in range(nT):
+            Ms[i, j] = models[i].magnetization()
+            Es[i, j] = models[i].energy()
+            if replicas == 2:
+                Qs[i, j] = models[i].overlap(models[nT + i])
+    del models
+    return _scan_summary(out, shape[0] * shape[1] * shape[2], Ms, Es, Qs if replicas == 2 else None)
+
+
 _PT_INITIAL = {"random": 0, "up": 1, "down": -1}
 
 
