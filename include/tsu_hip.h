@@ -304,6 +304,34 @@ int tsu_ising3d_overlap(tsu_ising3d* a, tsu_ising3d* b, int64_t* q);
 /* k8_sweep launches issued for this lattice so far */
 int tsu_ising3d_launch_count(tsu_ising3d* lat, uint64_t* n_launches);
 
+/* ------------------------------------------------------------------ K8: parallel tempering of 3-D lattices on one disorder
+ * tsu_pt2d for cubic lattices: n_ladders (1 or 2) ladders of n_temps (2 .. 256) walkers, every walker a whole K8 lattice (any
+ * shape and periodic_mask tsu_ising3d_create takes, with its validation and messages), all sharing ONE disorder.  Walker w of
+ * ladder k has Philox key seed + k n_temps + w, replica 0, the shared sweep counter, the initial draw of tsu_ising3d_randomize,
+ * and starts at slot (temperature) w: without swaps a walker is model k n_temps + w of temperature_scan_3d(seed=seed) bit for
+ * bit.  A round (tsu_pt3d_run) = swap_interval K8 sweeps of every walker at the temperature of its slot (one launch per
+ * half-sweep for all walkers), every walker's energy (the bits of tsu_ising3d_energy), then per ladder the swap pass of
+ * tsu_pt2d_run, rule, uniforms (TAG_PT_SWAP | k << 8, key = seed, counter = the round counter) and round-trip bookkeeping
+ * unchanged, then the record.  No new Philox tag.  Argument meanings, array layouts and error codes are those of the
+ * tsu_pt2d_* counterparts; spins are (D, R, C) int8 row-major.  An allocation that does not fit returns TSU_E_NOMEM and leaves
+ * nothing behind.  DESIGN.md section 3. */
+typedef struct tsu_pt3d tsu_pt3d;
+int tsu_pt3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_mask, int n_temps, int n_ladders, tsu_pt3d** out);
+int tsu_pt3d_destroy(tsu_pt3d* pt);
+/* the same arrays, validation and messages as tsu_ising3d_set_disorder; stored once for all walkers */
+int tsu_pt3d_set_disorder(tsu_pt3d* pt, const float* J_right, const float* J_down, const float* J_layer, const float* h /*nullable*/);
+int tsu_pt3d_set_temperatures(tsu_pt3d* pt, const double* T);
+int tsu_pt3d_init(tsu_pt3d* pt, uint64_t seed, int initial);
+int tsu_pt3d_run(tsu_pt3d* pt, int n_rounds, int swap_interval, int do_swap, int record);
+int tsu_pt3d_history(tsu_pt3d* pt, double* E, int64_t* M, int64_t* q, int32_t* walker);
+int tsu_pt3d_stats(tsu_pt3d* pt, int64_t* attempts, int64_t* accepts, int64_t* round_trips, int32_t* walker_at_slot,
+                   uint64_t* sweep_count, uint64_t* round_count);
+int tsu_pt3d_energies(tsu_pt3d* pt, double* E, int64_t* sum_s);
+int tsu_pt3d_get_spins(tsu_pt3d* pt, int ladder, int slot, int8_t* host);
+int tsu_pt3d_set_spins(tsu_pt3d* pt, int ladder, int slot, const int8_t* host);
+/* k8_pt_sweep launches so far (one per half-sweep for all walkers of all ladders) */
+int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

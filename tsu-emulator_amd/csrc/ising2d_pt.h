@@ -2,8 +2,7 @@
 // (replica cluster moves between the two ladders).
 #pragma once
 #include "ising2d.h"
-
-constexpr int kPtMaxTemps = 256;
+#include "pt_dev.h"  // kPtMaxTemps and the swap pass both ladder handles share
 
 struct tsu_pt2d {
     tsu_ctx* ctx;

@@ -33,11 +33,22 @@
 // k8_energy + k8_energy_final: E = -sum_bonds J s s' - sum h s in float64, a fixed number of per-workgroup partials then one
 // workgroup summing them in a fixed order (the same bits on every call).  k8_sum / k8_overlap: sum s and q = sum s^a s^b
 // (integers, one 64-bit vector atomic per workgroup).  No cooperative launch, no waiting, no atomics on the sweep path.
+//
+// Parallel tempering (tsu_pt3d_*): ladders of R walkers on ONE disorder ("Parallel tempering in 3-D (K8)").
+// k8_pt_sweep is k8_sweep for a group of W walkers per lane (the walker group is the grid's z dimension): the octet's six
+// couplings, field and screen bound are staged once and every walker of the group takes k8_octet's decision at the temperature
+// of its slot, so the 32 B per site of disorder a sweep reads are shared by W walkers.  k8_pt_energy / k8_pt_energy_final run
+// k8_energy's decomposition per walker through the same device helpers (the bits of tsu_ising3d_energy) and sum the spins
+// alongside; the swap pass is the 2-D ladders' kernel (pt_dev.h); k8_pt_overlap records q of the two ladders' walkers at each
+// slot.  No host value changes between rounds: a run of many rounds is enqueued without a synchronisation.
 #include <cmath>
+#include <cstdlib>
 #include <new>
+#include <vector>
 
 #include "disorder_dev.h"
 #include "ising2d.h"
+#include "pt_dev.h"
 
 struct tsu_ising3d {
     tsu_ctx* ctx;
@@ -50,6 +61,37 @@ struct tsu_ising3d {
     double* d_part;      // energy: per-workgroup partials + the total
     long long* d_acc;    // sum of spins / overlap accumulator
     unsigned long long launches;  // k8_sweep launches so far
+};
+
+// Parallel tempering: n_ladders ladders of R walkers (whole K8 lattices) on ONE disorder, the 3-D counterpart of tsu_pt2d
+struct tsu_pt3d {
+    tsu_ctx* ctx;
+    int R, nl, nw;                 // temperatures, ladders, walkers (R * nl)
+    tsu_ising3d** lat;             // walker g = ladder * R + w; lat[0] also holds the one disorder
+    int have_T, have_init;
+    uint32_t sweeps, rounds;       // sweeps of every walker and rounds since init
+    unsigned long long launches;   // k8_pt_sweep launches
+    int hist_rounds;               // rows recorded by the last run
+    size_t hist_cap;               // rows the history buffers hold
+    int8_t** d_s;                  // walker -> its spins
+    uint32_t* d_key;               // walker -> (k0, k1)
+    int32_t* d_slot;               // [ladder][walker] -> slot
+    int32_t* d_was;                // [ladder][slot] -> walker
+    int32_t* d_flag;               // [ladder][walker] -> round-trip flag
+    double* d_T;                   // slot -> T
+    float* d_c32;                  // slot -> fl32(2 / T)
+    long long* d_att;              // [ladder][pair]
+    long long* d_acc;
+    long long* d_trips;            // [ladder][walker]
+    double* d_part;                // [walker][kEnergyBlocks] energy partials
+    long long* d_ipart;            // [walker][kEnergyBlocks] sum-of-spin partials
+    double* d_E;                   // walker -> E of the last energy pass
+    long long* d_M;                // walker -> sum of spins
+    double* d_hE;                  // [round][ladder][slot]
+    long long* d_hM;
+    int32_t* d_hW;
+    long long* d_hq;               // [round][slot] (two ladders)
+    uint32_t key0, key1;           // Philox key of the swap uniforms (the seed)
 };
 
 namespace {
@@ -169,7 +211,8 @@ __device__ __forceinline__ void k8_octet(const K8Params& p, int z, int r, int q)
 
 // (row rho, octet q) of a lane: grid (ceil(nrows / (256 >> lshift)), ceil(nchunks / 64)), 256 lanes.  Local row slot j of the
 // workgroup's 256 >> lshift rows: the first half of the slots take the even local rows, the second half the odd ones.
-__device__ __forceinline__ bool k8_lane(const K8Params& p, long long& rho, int& q) {
+template <class P>
+__device__ __forceinline__ bool k8_lane(const P& p, long long& rho, int& q) {
     const int t = threadIdx.x;
     const int rpb = 256 >> p.lshift, half = rpb >> 1;
     const int j = t >> p.lshift;
@@ -247,12 +290,14 @@ __device__ __forceinline__ long long k8_block_isum(long long v) {
     return wpart[0] + wpart[1] + wpart[2] + wpart[3];
 }
 
-// E partials, one per workgroup: lane = chunk (rho, q), grid-stride in a fixed order; a site adds
-// s (((h + J_right s_right) + J_down s_down) + J_layer s_layer), a bond missing on an open axis skipped
-__global__ __launch_bounds__(256) void k8_energy(K8Params p, double* __restrict__ part) {
+// E partial of a lane: lane = chunk (rho, q), grid-stride over blockIdx.x in a fixed order; a site adds
+// s (((h + J_right s_right) + J_down s_down) + J_layer s_layer), a bond missing on an open axis skipped; ssum = the lane's sum
+// of spins.  Shared by the single-lattice and the ladder kernels: the lane order is part of the contract.
+__device__ __forceinline__ double k8_energy_lane(const K8Params& p, long long& ssum) {
     const int nchunks = (p.cols + 15) >> 4;
     const long long total = p.nrows * nchunks;
     double e = 0.0;
+    long long m = 0;
     for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
         const long long rho = t / nchunks;
         const int q = (int)(t - rho * nchunks);
@@ -270,17 +315,30 @@ __global__ __launch_bounds__(256) void k8_energy(K8Params p, double* __restrict_
             if (has_dn) l += (double)p.jd[row + c] * p.s[rowd + c];
             if (has_fw) l += (double)p.jl[row + c] * p.s[rowf + c];
             e += s * l;
+            m += s;
         }
     }
-    e = k8_block_sum(e);
+    ssum = m;
+    return e;
+}
+
+// E partials: one per workgroup
+__global__ __launch_bounds__(256) void k8_energy(K8Params p, double* __restrict__ part) {
+    long long m;
+    const double e = k8_block_sum(k8_energy_lane(p, m));
     if (threadIdx.x == 0) part[blockIdx.x] = e;
 }
 
-// one workgroup: out[0] = -(sum of the n partials), in a fixed order
-__global__ __launch_bounds__(256) void k8_energy_final(const double* __restrict__ part, int n, double* __restrict__ out) {
+// -(sum of the n partials), in a fixed order (every thread gets it)
+__device__ __forceinline__ double k8_final_sum(const double* __restrict__ part, int n) {
     double e = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) e += part[i];
-    e = -k8_block_sum(e);
+    return -k8_block_sum(e);
+}
+
+// one workgroup: out[0] = E
+__global__ __launch_bounds__(256) void k8_energy_final(const double* __restrict__ part, int n, double* __restrict__ out) {
+    const double e = k8_final_sum(part, n);
     if (threadIdx.x == 0) out[0] = e;
 }
 
@@ -322,6 +380,203 @@ __global__ __launch_bounds__(256) void k8_sum(const int8_t* __restrict__ a, long
                                               long long* __restrict__ acc) {
     const long long v = k8_block_isum(k8_pair_lane(a, nullptr, pitch, nrows, cols));
     if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)v);
+}
+
+// ------------------------------------------------------------------ parallel tempering
+struct PT3Params {
+    int8_t* const* s;     // walker g = ladder * R + w -> its spins (one pitch for all)
+    const uint32_t* key;  // walker -> Philox key (k0, k1) of seed + g
+    const int32_t* slot;  // walker -> its slot in its ladder
+    const double* T;      // slot -> T
+    const float* c32;     // slot -> fl32(2 / T)
+    const float* jr;      // the one disorder (K8Params layout)
+    const float* jd;
+    const float* jl;
+    const float* h;
+    long long pitch;
+    long long nrows;
+    int depth, rows, cols;
+    int pz, pr, pc;
+    int lshift;
+    int nw, W;            // walkers; walkers per lane (group z of the grid: walkers [z W, z W + W))
+    uint32_t hs;
+};
+
+// k8_octet for the walkers [g0, g1): the colour's couplings, fields and the screen's sum of |terms| are staged once, then each
+// walker takes the same decision as k8_octet at the temperature of its slot, with its own key (replica 0)
+template <int PAR>
+__device__ __forceinline__ void k8_pt_octet(const PT3Params& p, int z, int r, int q, int g0, int g1) {
+    const long long rho = (long long)z * p.rows + r;
+    const long long row = rho * p.pitch;
+    const int c0 = 16 * q;
+    const bool has_bk = z > 0 || p.pz, has_fw = z + 1 < p.depth || p.pz;
+    const bool has_up = r > 0 || p.pr, has_dn = r + 1 < p.rows || p.pr;
+    const long long rowb = ((long long)(z > 0 ? z - 1 : p.depth - 1) * p.rows + r) * p.pitch;
+    const long long rowf = ((long long)(z + 1 < p.depth ? z + 1 : 0) * p.rows + r) * p.pitch;
+    const long long rowu = ((long long)z * p.rows + (r > 0 ? r - 1 : p.rows - 1)) * p.pitch;
+    const long long rowd = ((long long)z * p.rows + (r + 1 < p.rows ? r + 1 : 0)) * p.pitch;
+    const bool has_prev = q > 0 || p.pc;
+    const int cprev = q > 0 ? c0 - 1 : p.cols - 1;
+    // the colour's 8 sites: J to the six neighbours (0 where one is missing), h, and the screen's sum of |terms|
+    float Jb[8], Jf[8], Ju[8], Jd[8], Jl[8], Jr[8], hf[8], a32[8];
+    {
+        float4 jr[4], jd[4], jl[4], ju[4], jb[4], hh[4];
+        load16f(p.jr + row + c0, jr);
+        load16f(p.jd + row + c0, jd);
+        load16f(p.jl + row + c0, jl);
+        load16f(p.h + row + c0, hh);
+        if (has_up) load16f(p.jd + rowu + c0, ju);
+        else zero16f(ju);
+        if (has_bk) load16f(p.jl + rowb + c0, jb);
+        else zero16f(jb);
+        const float j_prev = has_prev ? p.jr[row + cprev] : 0.0f;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int i = 2 * m + PAR, c = c0 + i;
+            const bool has_left = i > 0 || has_prev, has_right = c + 1 < p.cols || p.pc;
+            Jb[m] = has_bk ? fat(jb, i) : 0.0f;
+            Jf[m] = has_fw ? fat(jl, i) : 0.0f;
+            Ju[m] = has_up ? fat(ju, i) : 0.0f;
+            Jd[m] = has_dn ? fat(jd, i) : 0.0f;
+            Jl[m] = has_left ? (i > 0 ? fat(jr, i - 1) : j_prev) : 0.0f;
+            Jr[m] = has_right ? fat(jr, i) : 0.0f;
+            hf[m] = fat(hh, i);
+            a32[m] = fabsf(Jb[m]) + fabsf(Jf[m]) + fabsf(Ju[m]) + fabsf(Jd[m]) + fabsf(Jl[m]) + fabsf(Jr[m]) + fabsf(hf[m]);
+        }
+    }
+    const uint4 zero4 = make_uint4(0, 0, 0, 0);
+#pragma unroll 1
+    for (int g = g0; g < g1; ++g) {
+        int8_t* const s = p.s[g];
+        const int slot = p.slot[g];
+        const double T = p.T[slot];
+        const float c32 = p.c32[slot];
+        const uint32_t k0 = p.key[2 * g], k1 = p.key[2 * g + 1];
+        const uint4 C = *reinterpret_cast<const uint4*>(s + row + c0);
+        const uint4 B = has_bk ? *reinterpret_cast<const uint4*>(s + rowb + c0) : zero4;
+        const uint4 F = has_fw ? *reinterpret_cast<const uint4*>(s + rowf + c0) : zero4;
+        const uint4 U = has_up ? *reinterpret_cast<const uint4*>(s + rowu + c0) : zero4;
+        const uint4 D = has_dn ? *reinterpret_cast<const uint4*>(s + rowd + c0) : zero4;
+        const int s_prev = has_prev ? (int)s[row + cprev] : 0;
+        const int s_next = (c0 + 16 < p.cols) ? (int)s[row + c0 + 16] : 0;
+        const int s_first = p.pc ? (int)s[row] : 0;
+        const u32x4 w = tsu_philox((uint32_t)q, (uint32_t)rho, p.hs, TSU_TAG_ISING_HI, k0, k1);
+        const uint32_t wv[4] = {w.x, w.y, w.z, w.w};
+        bool have_lo = false;
+        uint32_t lv[4] = {0, 0, 0, 0};
+        uint32_t out[4] = {C.x, C.y, C.z, C.w};
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            const int i = 2 * m + PAR, c = c0 + i;
+            if (c >= p.cols) break;
+            const bool has_left = i > 0 || has_prev, has_right = c + 1 < p.cols || p.pc;
+            const int sb = sbyte(B, i), sf = sbyte(F, i), su = sbyte(U, i), sd = sbyte(D, i);
+            const int sl = i > 0 ? sbyte(C, i - 1) : s_prev;
+            const int sr = c + 1 < p.cols ? (i < 15 ? sbyte(C, i + 1) : s_next) : s_first;
+            const float f32 =
+                (((((Jb[m] * (float)sb + Jf[m] * (float)sf) + Ju[m] * (float)su) + Jd[m] * (float)sd) + Jl[m] * (float)sl) + Jr[m] * (float)sr) +
+                hf[m];
+            const uint32_t hi = ((wv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu) ^ 0x8000u;
+            int dec = screen(f32, a32[m], c32, hi);
+            if (dec == 0) {
+                // the contract's sum: neighbours in the order z-1, z+1, r-1, r+1, c-1, c+1, a missing one skipped, then h
+                double f = 0.0;
+                bool any = false;
+                if (has_bk) { f = (double)Jb[m] * sb; any = true; }
+                if (has_fw) { f = any ? f + (double)Jf[m] * sf : (double)Jf[m] * sf; any = true; }
+                if (has_up) { f = any ? f + (double)Ju[m] * su : (double)Ju[m] * su; any = true; }
+                if (has_dn) { f = any ? f + (double)Jd[m] * sd : (double)Jd[m] * sd; any = true; }
+                if (has_left) { f = any ? f + (double)Jl[m] * sl : (double)Jl[m] * sl; any = true; }
+                if (has_right) { f = any ? f + (double)Jr[m] * sr : (double)Jr[m] * sr; any = true; }
+                f = any ? f + (double)hf[m] : (double)hf[m];
+                const uint64_t thr = exact_thr(f, T);
+                const uint32_t thi = (uint32_t)(thr >> 16);
+                bool accept = hi < thi;
+                if (hi == thi) {  // tie on the top 16 bits: the low half, as K1 draws it
+                    if (!have_lo) {
+                        const u32x4 l = tsu_philox((uint32_t)q, (uint32_t)rho, p.hs, TSU_TAG_ISING_LO, k0, k1);
+                        lv[0] = l.x; lv[1] = l.y; lv[2] = l.z; lv[3] = l.w;
+                        have_lo = true;
+                    }
+                    const uint32_t lo = (lv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu;
+                    accept = (((uint64_t)hi << 16) | lo) < thr;
+                }
+                dec = accept ? 1 : -1;
+            }
+            const uint32_t b = dec > 0 ? 0x01u : 0xFFu;
+            const int sh = 8 * (i & 3);
+            out[i >> 2] = (out[i >> 2] & ~(0xFFu << sh)) | (b << sh);
+        }
+        *reinterpret_cast<uint4*>(s + row + c0) = make_uint4(out[0], out[1], out[2], out[3]);
+    }
+}
+
+// k8_sweep's grid with the walker group as its z dimension: lane = octet q of row rho (k8_lane) for the walkers of group z.
+// The 64 staged floats and five spin vectors fit 255 VGPRs without scratch; the second launch bound keeps the allocator from
+// spreading into AGPRs, which would halve the waves per SIMD for nothing.
+__global__ __launch_bounds__(256, 2) void k8_pt_sweep(PT3Params p, int colour) {
+    long long rho;
+    int q;
+    if (!k8_lane(p, rho, q)) return;
+    const int z = (int)(rho / p.rows), r = (int)(rho - (long long)z * p.rows);
+    const int g0 = blockIdx.z * p.W, g1 = min(g0 + p.W, p.nw);
+    if (((z + r + colour) & 1) == 0) k8_pt_octet<0>(p, z, r, q, g0, g1);
+    else k8_pt_octet<1>(p, z, r, q, g0, g1);
+}
+
+__device__ __forceinline__ K8Params pt_walker_params(const PT3Params& pp, int g) {
+    K8Params p;
+    p.s = pp.s[g];
+    p.jr = pp.jr;
+    p.jd = pp.jd;
+    p.jl = pp.jl;
+    p.h = pp.h;
+    p.pitch = pp.pitch;
+    p.nrows = pp.nrows;
+    p.depth = pp.depth;
+    p.rows = pp.rows;
+    p.cols = pp.cols;
+    p.pz = pp.pz;
+    p.pr = pp.pr;
+    p.pc = pp.pc;
+    p.lshift = pp.lshift;
+    p.c32 = 0.0f;
+    p.T = 0.0;
+    p.k0 = p.k1 = p.hs = p.tag_hi = p.tag_lo = 0;
+    return p;
+}
+
+// grid (blocks_for(lattice), nw): workgroup x of walker y computes k8_energy's partial x of that walker alone, and its sum of spins
+__global__ __launch_bounds__(256) void k8_pt_energy(PT3Params pp, double* __restrict__ part, long long* __restrict__ ipart) {
+    long long m;
+    const double e = k8_block_sum(k8_energy_lane(pt_walker_params(pp, blockIdx.y), m));
+    const long long ms = k8_block_isum(m);
+    if (threadIdx.x == 0) {
+        part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
+        ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
+    }
+}
+
+// one workgroup per walker: E as k8_energy_final sums it, and the sum of spins
+__global__ __launch_bounds__(256) void k8_pt_energy_final(const double* __restrict__ part, const long long* __restrict__ ipart, int n,
+                                                          double* __restrict__ E, long long* __restrict__ M) {
+    const size_t base = (size_t)blockIdx.x * kEnergyBlocks;
+    const double e = k8_final_sum(part + base, n);
+    long long m = 0;
+    for (int i = threadIdx.x; i < n; i += 256) m += ipart[base + i];
+    const long long ms = k8_block_isum(m);
+    if (threadIdx.x == 0) {
+        E[blockIdx.x] = e;
+        M[blockIdx.x] = ms;
+    }
+}
+
+// grid (blocks_for(lattice), R): q of the two ladders' walkers at slot y, added into out[y] (a zeroed history row)
+__global__ __launch_bounds__(256) void k8_pt_overlap(int8_t* const* __restrict__ s, const int32_t* __restrict__ was, int R,
+                                                     long long pitch, long long nrows, int cols, long long* __restrict__ out) {
+    const int i = blockIdx.y;
+    const long long v = k8_block_isum(k8_pair_lane(s[was[i]], s[R + was[R + i]], pitch, nrows, cols));
+    if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out + i), (unsigned long long)v);
 }
 
 K8Params make_params(const tsu_ising3d* L) {
@@ -369,6 +624,116 @@ int read_acc(tsu_ising3d* L, int64_t* out) {
     TSU_HIP_TRY(ctx, hipMemcpyAsync(&h, L->d_acc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *out = h;
+    return TSU_OK;
+}
+
+void pt_free_history(tsu_pt3d* P) {
+    void* bufs[] = {P->d_hE, P->d_hM, P->d_hW, P->d_hq};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    P->d_hE = nullptr;
+    P->d_hM = nullptr;
+    P->d_hW = nullptr;
+    P->d_hq = nullptr;
+    P->hist_cap = 0;
+}
+
+void pt_free(tsu_pt3d* P) {
+    void* bufs[] = {P->d_s, P->d_key, P->d_slot, P->d_was, P->d_flag, P->d_T, P->d_c32, P->d_att, P->d_acc,
+                    P->d_trips, P->d_part, P->d_ipart, P->d_E, P->d_M};
+    for (void* b : bufs)
+        if (b) (void)hipFree(b);
+    pt_free_history(P);
+    if (P->lat) {
+        for (int g = 0; g < P->nw; ++g)
+            if (P->lat[g]) (void)tsu_ising3d_destroy(P->lat[g]);
+        delete[] P->lat;
+    }
+    delete P;
+}
+
+// every walker at its own slot, the walker at slot 0 "bottom", no attempts, accepts or round trips (synchronises)
+int pt_reset(tsu_pt3d* P) {
+    tsu_ctx* ctx = P->ctx;
+    const int R = P->R, nl = P->nl;
+    std::vector<int32_t> ident((size_t)nl * R), flag((size_t)nl * R, kPtNone);
+    for (int k = 0; k < nl; ++k) {
+        for (int w = 0; w < R; ++w) ident[(size_t)k * R + w] = w;
+        flag[(size_t)k * R] = kPtBottom;
+    }
+    const size_t b = (size_t)nl * R * sizeof(int32_t);
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_slot, ident.data(), b, hipMemcpyHostToDevice, ctx->stream));
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_was, ident.data(), b, hipMemcpyHostToDevice, ctx->stream));
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_flag, flag.data(), b, hipMemcpyHostToDevice, ctx->stream));
+    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_att, 0, (size_t)nl * (R - 1) * sizeof(long long), ctx->stream));
+    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_acc, 0, (size_t)nl * (R - 1) * sizeof(long long), ctx->stream));
+    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_trips, 0, (size_t)nl * R * sizeof(long long), ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    P->sweeps = P->rounds = 0;
+    P->hist_rounds = 0;
+    return TSU_OK;
+}
+
+// Walkers per lane of k8_pt_sweep, chosen as the 2-D ladders choose it: the fewest groups that still give >= 1024 lanes per CU
+// (a lane per octet and group), so a large lattice reads each octet's disorder once for many walkers and a small one spreads its
+// walkers over the chip.  TSU_PT_GROUP=w (read per call) forces w.
+int pt_group(const tsu_pt3d* P) {
+    if (const char* e = getenv("TSU_PT_GROUP")) {
+        const int w = atoi(e);
+        if (w >= 1) return w < P->nw ? w : P->nw;
+    }
+    const tsu_ising3d* L = P->lat[0];
+    const long long lanes = (long long)L->depth * L->rows * ((L->cols + 15) / 16);
+    const long long want = (long long)(P->ctx->cus > 0 ? P->ctx->cus : 256) * 1024;
+    const long long groups = (want + lanes - 1) / lanes;
+    if (groups >= P->nw) return 1;
+    return (int)((P->nw + groups - 1) / groups);
+}
+
+PT3Params pt_params(const tsu_pt3d* P) {
+    const K8Params k = make_params(P->lat[0]);
+    PT3Params p;
+    p.s = P->d_s;
+    p.key = P->d_key;
+    p.slot = P->d_slot;
+    p.T = P->d_T;
+    p.c32 = P->d_c32;
+    p.jr = k.jr;
+    p.jd = k.jd;
+    p.jl = k.jl;
+    p.h = k.h;
+    p.pitch = k.pitch;
+    p.nrows = k.nrows;
+    p.depth = k.depth;
+    p.rows = k.rows;
+    p.cols = k.cols;
+    p.pz = k.pz;
+    p.pr = k.pr;
+    p.pc = k.pc;
+    p.lshift = k.lshift;
+    p.nw = P->nw;
+    p.W = 1;
+    p.hs = 0;
+    return p;
+}
+
+// every walker's E and sum of spins into d_E / d_M (asynchronous)
+void pt_enqueue_energies(tsu_pt3d* P, const PT3Params& p) {
+    const unsigned blocks = blocks_for(P->lat[0]);
+    k8_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart);
+    k8_pt_energy_final<<<(unsigned)P->nw, 256, 0, P->ctx->stream>>>(P->d_part, P->d_ipart, (int)blocks, P->d_E, P->d_M);
+}
+
+// the lattice of the walker now at (ladder, slot) (synchronises)
+int pt_at(tsu_pt3d* P, int ladder, int slot, const char* what, tsu_ising3d** out) {
+    tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, ladder >= 0 && ladder < P->nl && slot >= 0 && slot < P->R,
+                "%s: ladder %d, slot %d out of range (%d ladder(s) of %d temperatures)", what, ladder, slot, P->nl, P->R);
+    int32_t w = -1;
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(&w, P->d_was + (size_t)ladder * P->R + slot, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (w < 0 || w >= P->R) return tsu_fail(ctx, TSU_E_HIP, "%s: corrupt slot table (walker %d)", what, (int)w);
+    *out = P->lat[ladder * P->R + w];
     return TSU_OK;
 }
 
@@ -578,6 +943,276 @@ int tsu_ising3d_launch_count(tsu_ising3d* L, uint64_t* n) {
     TSU_ENTER(L ? L->ctx : nullptr);
     if (!L || !n) return TSU_E_INVALID;
     *n = L->launches;
+    return TSU_OK;
+}
+
+// ------------------------------------------------------------------ parallel tempering
+int tsu_pt3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_mask, int n_temps, int n_ladders, tsu_pt3d** out) {
+    TSU_ENTER(ctx);
+    if (!ctx || !out) return TSU_E_INVALID;
+    *out = nullptr;
+    TSU_REQUIRE(ctx, n_temps >= 2 && n_temps <= kPtMaxTemps, "pt3d_create: n_temps must be in [2, %d], got %d", kPtMaxTemps, n_temps);
+    TSU_REQUIRE(ctx, n_ladders == 1 || n_ladders == 2, "pt3d_create: n_ladders must be 1 or 2, got %d", n_ladders);
+    tsu_pt3d* P = new (std::nothrow) tsu_pt3d();
+    if (!P) return tsu_fail(ctx, TSU_E_NOMEM, "pt3d_create: host allocation failed");
+    P->ctx = ctx;
+    P->R = n_temps;
+    P->nl = n_ladders;
+    P->nw = n_temps * n_ladders;
+    P->lat = new (std::nothrow) tsu_ising3d*[P->nw]();
+    if (!P->lat) {
+        pt_free(P);
+        return tsu_fail(ctx, TSU_E_NOMEM, "pt3d_create: host allocation failed");
+    }
+    for (int g = 0; g < P->nw; ++g) {  // the shape checks and messages of tsu_ising3d_create
+        const int rc = tsu_ising3d_create(ctx, depth, rows, cols, periodic_mask, &P->lat[g]);
+        if (rc != TSU_OK) {  // the walkers made so far go too: a ladder that does not fit leaves nothing behind
+            pt_free(P);
+            (void)hipGetLastError();
+            return rc;
+        }
+    }
+    const size_t nw = (size_t)P->nw, nlR = (size_t)P->nl * P->R, R = (size_t)P->R;
+    hipError_t e = hipSuccess;
+    auto alloc = [&e](auto*& ptr, size_t bytes) {
+        if (e == hipSuccess) e = hipMalloc((void**)&ptr, bytes);
+    };
+    alloc(P->d_s, nw * sizeof(int8_t*));
+    alloc(P->d_key, 2 * nw * sizeof(uint32_t));
+    alloc(P->d_slot, nlR * sizeof(int32_t));
+    alloc(P->d_was, nlR * sizeof(int32_t));
+    alloc(P->d_flag, nlR * sizeof(int32_t));
+    alloc(P->d_T, R * sizeof(double));
+    alloc(P->d_c32, R * sizeof(float));
+    alloc(P->d_att, (size_t)P->nl * (R - 1) * sizeof(long long));
+    alloc(P->d_acc, (size_t)P->nl * (R - 1) * sizeof(long long));
+    alloc(P->d_trips, nlR * sizeof(long long));
+    alloc(P->d_part, nw * kEnergyBlocks * sizeof(double));
+    alloc(P->d_ipart, nw * kEnergyBlocks * sizeof(long long));
+    alloc(P->d_E, nw * sizeof(double));
+    alloc(P->d_M, nw * sizeof(long long));
+    std::vector<int8_t*> planes(nw);
+    for (size_t g = 0; g < nw; ++g) planes[g] = P->lat[g]->s;
+    if (e == hipSuccess) e = hipMemcpyAsync(P->d_s, planes.data(), nw * sizeof(int8_t*), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(P->d_key, 0, 2 * nw * sizeof(uint32_t), ctx->stream);
+    if (e != hipSuccess) {
+        const int rc = tsu_fail(ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP, "pt3d_create: %s", hipGetErrorString(e));
+        (void)hipStreamSynchronize(ctx->stream);
+        pt_free(P);
+        (void)hipGetLastError();
+        return rc;
+    }
+    const int rc = pt_reset(P);  // synchronises before `planes` goes
+    if (rc != TSU_OK) {
+        pt_free(P);
+        return rc;
+    }
+    *out = P;
+    return TSU_OK;
+}
+
+int tsu_pt3d_destroy(tsu_pt3d* P) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_OK;
+    (void)hipStreamSynchronize(P->ctx->stream);
+    pt_free(P);
+    return TSU_OK;
+}
+
+int tsu_pt3d_set_disorder(tsu_pt3d* P, const float* J_right, const float* J_down, const float* J_layer, const float* h) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    return tsu_ising3d_set_disorder(P->lat[0], J_right, J_down, J_layer, h);  // stored once, with walker 0's lattice
+}
+
+int tsu_pt3d_set_temperatures(tsu_pt3d* P, const double* T) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, T, "pt3d_set_temperatures: NULL temperatures");
+    double t[kPtMaxTemps];
+    float c[kPtMaxTemps];
+    for (int i = 0; i < P->R; ++i) {
+        TSU_REQUIRE(ctx, T[i] > 0.0 && std::isfinite(T[i]), "Temperature must be positive (pt3d_set_temperatures: T[%d] = %g)", i, T[i]);
+        t[i] = T[i];
+        c[i] = (float)(2.0 / T[i]);
+    }
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_T, t, P->R * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_c32, c, P->R * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    P->have_T = 1;
+    return TSU_OK;
+}
+
+int tsu_pt3d_init(tsu_pt3d* P, uint64_t seed, int initial) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, initial == 0 || initial == 1 || initial == -1, "pt3d_init: initial must be 0 (random), 1 (up) or -1 (down), got %d",
+                initial);
+    std::vector<uint32_t> key(2 * (size_t)P->nw);
+    for (int g = 0; g < P->nw; ++g) {
+        const uint64_t s = seed + (uint64_t)g;  // temperature_scan_3d's model g
+        key[2 * g] = (uint32_t)s;
+        key[2 * g + 1] = (uint32_t)(s >> 32);
+        const int rc = initial == 0 ? tsu_ising3d_randomize(P->lat[g], s, 0) : tsu_ising3d_fill(P->lat[g], (int8_t)initial);
+        if (rc != TSU_OK) return rc;
+    }
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_key, key.data(), key.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    const int rc = pt_reset(P);  // synchronises before `key` goes
+    if (rc != TSU_OK) return rc;
+    P->key0 = (uint32_t)seed;
+    P->key1 = (uint32_t)(seed >> 32);
+    P->have_init = 1;
+    return TSU_OK;
+}
+
+int tsu_pt3d_run(tsu_pt3d* P, int n_rounds, int swap_interval, int do_swap, int record) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    tsu_ctx* ctx = P->ctx;
+    tsu_ising3d* L = P->lat[0];
+    TSU_REQUIRE(ctx, L->have_disorder, "pt3d_run: call tsu_pt3d_set_disorder first");
+    TSU_REQUIRE(ctx, P->have_T, "pt3d_run: call tsu_pt3d_set_temperatures first");
+    TSU_REQUIRE(ctx, P->have_init, "pt3d_run: call tsu_pt3d_init first");
+    TSU_REQUIRE(ctx, n_rounds >= 0 && swap_interval >= 1, "pt3d_run: need n_rounds >= 0 and swap_interval >= 1 (got %d, %d)", n_rounds,
+                swap_interval);
+    TSU_REQUIRE(ctx, (uint64_t)P->sweeps + (uint64_t)n_rounds * (uint64_t)swap_interval <= (1ull << 31), "pt3d_run: sweep counter overflow");
+    TSU_REQUIRE(ctx, (uint64_t)P->rounds + (uint64_t)n_rounds <= 0xFFFFFFFFull, "pt3d_run: round counter overflow");
+    const int R = P->R, nl = P->nl;
+    if (record && P->hist_cap < (size_t)n_rounds) {
+        pt_free_history(P);
+        const size_t n = (size_t)n_rounds * nl * R;
+        hipError_t e = hipMalloc((void**)&P->d_hE, n * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void**)&P->d_hM, n * sizeof(long long));
+        if (e == hipSuccess) e = hipMalloc((void**)&P->d_hW, n * sizeof(int32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&P->d_hq, (size_t)n_rounds * R * sizeof(long long));
+        if (e != hipSuccess) {  // nothing of a history that does not fit stays behind
+            pt_free_history(P);
+            P->hist_rounds = 0;
+            (void)hipGetLastError();
+            return tsu_fail(ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP, "pt3d_run: history of %d rounds: %s", n_rounds,
+                            hipGetErrorString(e));
+        }
+        P->hist_cap = (size_t)n_rounds;
+    }
+    // k8_pt_overlap adds into its row: every q row of this run starts at 0
+    if (record && nl == 2 && n_rounds > 0)
+        TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hq, 0, (size_t)n_rounds * R * sizeof(long long), ctx->stream));
+    P->hist_rounds = record ? n_rounds : 0;
+    PT3Params p = pt_params(P);
+    p.W = pt_group(P);
+    const dim3 og = octet_grid(make_params(L));
+    const dim3 grid(og.x, og.y, (unsigned)((P->nw + p.W - 1) / p.W));
+    PTSwap sw;
+    sw.E = P->d_E;
+    sw.M = P->d_M;
+    sw.T = P->d_T;
+    sw.was = P->d_was;
+    sw.slot = P->d_slot;
+    sw.flag = P->d_flag;
+    sw.att = P->d_att;
+    sw.acc = P->d_acc;
+    sw.trips = P->d_trips;
+    sw.R = R;
+    sw.do_swap = do_swap ? 1 : 0;
+    sw.k0 = P->key0;
+    sw.k1 = P->key1;
+    for (int t = 0; t < n_rounds; ++t) {
+        for (int s = 0; s < swap_interval; ++s)
+            for (int colour = 0; colour < 2; ++colour) {
+                p.hs = 2u * (P->sweeps + (uint32_t)s) + (uint32_t)colour;
+                k8_pt_sweep<<<grid, 256, 0, ctx->stream>>>(p, colour);
+                P->launches += 1;
+            }
+        P->sweeps += (uint32_t)swap_interval;
+        if (do_swap || record) {
+            pt_enqueue_energies(P, p);
+            const size_t row = (size_t)t * nl * R;
+            sw.hE = record ? P->d_hE + row : nullptr;
+            sw.hM = record ? P->d_hM + row : nullptr;
+            sw.hW = record ? P->d_hW + row : nullptr;
+            sw.t = P->rounds;
+            k7_pt_swap<<<(unsigned)nl, 64, 0, ctx->stream>>>(sw);  // the 2-D ladders' pass, unchanged (pt_dev.h)
+            if (record && nl == 2)
+                k8_pt_overlap<<<dim3(blocks_for(L), (unsigned)R, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, (long long)L->pitch,
+                                                                                           (long long)L->depth * L->rows, L->cols,
+                                                                                           P->d_hq + (size_t)t * R);
+        }
+        P->rounds += 1;
+    }
+    TSU_HIP_TRY(ctx, hipGetLastError());
+    return TSU_OK;
+}
+
+int tsu_pt3d_history(tsu_pt3d* P, double* E, int64_t* M, int64_t* q, int32_t* walker) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    tsu_ctx* ctx = P->ctx;
+    const size_t n = (size_t)P->hist_rounds * P->nl * P->R;
+    if (n) {
+        if (E) TSU_HIP_TRY(ctx, hipMemcpyAsync(E, P->d_hE, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        if (M) TSU_HIP_TRY(ctx, hipMemcpyAsync(M, P->d_hM, n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (walker) TSU_HIP_TRY(ctx, hipMemcpyAsync(walker, P->d_hW, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (q && P->nl == 2)
+            TSU_HIP_TRY(ctx, hipMemcpyAsync(q, P->d_hq, (size_t)P->hist_rounds * P->R * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSU_OK;
+}
+
+int tsu_pt3d_stats(tsu_pt3d* P, int64_t* attempts, int64_t* accepts, int64_t* round_trips, int32_t* walker_at_slot, uint64_t* sweep_count,
+                   uint64_t* round_count) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    tsu_ctx* ctx = P->ctx;
+    const size_t pairs = (size_t)P->nl * (P->R - 1), nlR = (size_t)P->nl * P->R;
+    if (attempts) TSU_HIP_TRY(ctx, hipMemcpyAsync(attempts, P->d_att, pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (accepts) TSU_HIP_TRY(ctx, hipMemcpyAsync(accepts, P->d_acc, pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (round_trips) TSU_HIP_TRY(ctx, hipMemcpyAsync(round_trips, P->d_trips, nlR * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (walker_at_slot)
+        TSU_HIP_TRY(ctx, hipMemcpyAsync(walker_at_slot, P->d_was, nlR * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (sweep_count) *sweep_count = P->sweeps;
+    if (round_count) *round_count = P->rounds;
+    return TSU_OK;
+}
+
+int tsu_pt3d_energies(tsu_pt3d* P, double* E, int64_t* sum_s) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, P->lat[0]->have_disorder, "pt3d_energies: call tsu_pt3d_set_disorder first");
+    pt_enqueue_energies(P, pt_params(P));
+    TSU_HIP_TRY(ctx, hipGetLastError());
+    if (E) TSU_HIP_TRY(ctx, hipMemcpyAsync(E, P->d_E, (size_t)P->nw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (sum_s) TSU_HIP_TRY(ctx, hipMemcpyAsync(sum_s, P->d_M, (size_t)P->nw * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSU_OK;
+}
+
+int tsu_pt3d_get_spins(tsu_pt3d* P, int ladder, int slot, int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    TSU_REQUIRE(P->ctx, host, "pt3d_get_spins: NULL output");
+    tsu_ising3d* L = nullptr;
+    const int rc = pt_at(P, ladder, slot, "pt3d_get_spins", &L);
+    return rc != TSU_OK ? rc : tsu_ising3d_get_spins(L, host);
+}
+
+int tsu_pt3d_set_spins(tsu_pt3d* P, int ladder, int slot, const int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    TSU_REQUIRE(P->ctx, host, "pt3d_set_spins: NULL input");
+    tsu_ising3d* L = nullptr;
+    const int rc = pt_at(P, ladder, slot, "pt3d_set_spins", &L);
+    return rc != TSU_OK ? rc : tsu_ising3d_set_spins(L, host);
+}
+
+int tsu_pt3d_launch_count(tsu_pt3d* P, uint64_t* n) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P || !n) return TSU_E_INVALID;
+    *n = P->launches;
     return TSU_OK;
 }
 

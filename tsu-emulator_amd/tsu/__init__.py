@@ -30,8 +30,10 @@ from .models import (  # noqa: F401
     IsingModel,
     IsingModel2D,
     IsingModel3D,
+    LatticeTempering3D,
     demonstrate_phase_transition,
     temperature_scan_3d,
+    tempering_scan_3d,
 )
 
 __all__ = [
@@ -39,5 +41,5 @@ __all__ = [
     "ConfigurationError", "SamplingError", "QuadraticEnergy", "QuadraticForm", "MixtureEnergy",
     "GibbsSampler", "GibbsConfig", "HardwareEmulator",
     "IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "demonstrate_phase_transition",
-    "IsingModel3D", "temperature_scan_3d",
+    "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d",
 ]

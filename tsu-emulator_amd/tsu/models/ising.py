@@ -23,7 +23,8 @@ denoising -- and ``gibbs_update`` then runs the disordered heat-bath kernel with
 ``energy()`` is the disordered energy, ``overlap(other)`` the spin-glass overlap q / N, and ``temperature_scan(...,
 couplings=, field=, replicas=2)`` adds <|q|>, <q^2> and the Binder ratio of two replicas per temperature.
 :class:`LatticeTempering` / :func:`tempering_scan` run such a scan as replica exchange: ladders of walkers on one disorder, swept
-in batches and swapped between temperatures on the device.
+in batches and swapped between temperatures on the device; :class:`LatticeTempering3D` / :func:`tempering_scan_3d` do the same
+for the cubic lattices of :class:`IsingModel3D` (K8).
 """
 from dataclasses import dataclass
 from typing import List, Optional, Tuple
@@ -1070,6 +1071,147 @@ def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int
             st = pt.cluster_stats
             with np.errstate(divide="ignore", invalid="ignore"):
                 out["cluster_flipped"] = st["flipped"] / (st["passes"] * float(N))
+    finally:
+        pt._pt.close()
+    return out
+
+
+class _PeriodicAxisError(_hip.UnsupportedError, ValueError):
+    """The periodic-axis rule of K8 refused by the 3-D ladders on the host: the UnsupportedError every K8 entry point raises for
+    it, and a ValueError like the rest of the ladders' argument validation."""
+
+
+def _tempering_disorder_3d(shape, periodic, coupling, external_field, couplings, field):
+    try:
+        return _disorder_arrays_3d(shape, periodic, coupling, external_field, couplings, field)
+    except _hip.UnsupportedError as e:
+        raise _PeriodicAxisError(str(e)) from None
+
+
+class LatticeTempering3D:
+    """Parallel tempering (replica exchange) of a disordered cubic lattice on the GPU (K8, physical mode): :class:`LatticeTempering`
+    for the lattices of :class:`IsingModel3D`.
+
+    ``ladders`` (1 or 2) ladders of ``R = len(temperatures)`` walkers (2 ... 256) share one quenched disorder:
+    ``couplings=(J_right, J_down, J_layer)`` and ``field`` as for :class:`IsingModel3D`, or the uniform ``coupling`` /
+    ``external_field``; ``periodic`` is a bool or a triple (p_z, p_r, p_c).  Everything is validated and rounded to float32 before
+    any device call.  Walker w of ladder k is model ``k R + w`` of ``temperature_scan_3d(seed=seed)`` (same Philox key, initial
+    draw and sweep counter) and starts at slot w.  ``run(n_rounds, swap_interval)``: each round sweeps every walker
+    ``swap_interval`` times at the temperature of its slot (one launch per half-sweep for all walkers), computes every energy and
+    makes one pass of swap attempts over the adjacent slots of each ladder by the rule of :class:`LatticeTempering`, all on the
+    device without a host synchronisation.  A swap exchanges the walkers' temperatures, never their spins.  There are no replica
+    cluster moves in 3-D: the q = -1 sites of a cubic lattice percolate (site threshold 0.3116) at every temperature of interest.
+    """
+
+    def __init__(self, size, temperatures, *, couplings=None, field=None, coupling: float = 1.0, external_field: float = 0.0,
+                 periodic=True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1):
+        self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
+        self.n_spins = self.depth * self.rows * self.cols
+        T = np.asarray(temperatures, dtype=float).ravel()
+        if not 2 <= T.size <= 256:
+            raise ValueError(f"parallel tempering needs 2 to 256 temperatures, got {T.size}")
+        if not np.all(np.isfinite(T) & (T > 0)):
+            raise ValueError("Temperature must be positive")
+        if ladders not in (1, 2):
+            raise ValueError("ladders must be 1 or 2")
+        if initial not in _PT_INITIAL:
+            raise ValueError("initial must be 'random', 'up' or 'down'")
+        self.periodic = _hip.periodic_axes(periodic)
+        self._disorder = _tempering_disorder_3d(self.shape, self.periodic, float(coupling), float(external_field), couplings, field)
+        self.temperatures = T
+        self.ladders = int(ladders)
+        self.seed = int(seed) if seed is not None else (
+            int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
+        self._pt = _hip.TemperingLattice3D(self.depth, self.rows, self.cols, self.periodic, T.size, self.ladders)
+        self._pt.set_disorder(*self._disorder)
+        self._pt.set_temperatures(T)
+        self._pt.init(self.seed, _PT_INITIAL[initial])
+
+    def run(self, n_rounds: int, swap_interval: int = 10, swap: bool = True, record: bool = True):
+        """n_rounds rounds of swap_interval sweeps each; with ``record`` returns ``history()`` (ladder 0), else None."""
+        self._pt.run(int(n_rounds), int(swap_interval), swap, record)
+        return self.history() if record else None
+
+    def history(self, ladder: int = 0) -> dict:
+        """The rounds recorded by the last ``run`` as (n_rounds, R) arrays, per slot: ``E`` (float64 energy), ``M`` (int64 sum of
+        spins), ``walker`` (which walker of the ladder sat there) and, with two ladders, ``q`` (int64 overlap of the two ladders'
+        walkers at that slot)."""
+        h = self._pt.history()
+        out = {k: np.ascontiguousarray(h[k][:, ladder]) for k in ("E", "M", "walker")}
+        if h["q"] is not None:
+            out["q"] = h["q"]
+        return out
+
+    @property
+    def acceptance(self) -> np.ndarray:
+        """Accepted / attempted swaps per adjacent pair of slots, ladders pooled (NaN before the first attempt)."""
+        st = self._pt.stats()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return st["accepts"].sum(axis=0) / st["attempts"].sum(axis=0)
+
+    @property
+    def round_trips(self) -> int:
+        """Round trips (slot 0 -> last slot -> slot 0) completed by all walkers of all ladders."""
+        return int(self._pt.stats()["round_trips"].sum())
+
+    @property
+    def walker_at_slot(self) -> np.ndarray:
+        """(ladders, R): which walker sits at each slot."""
+        return self._pt.stats()["walker_at_slot"]
+
+    @property
+    def sweep_count(self) -> int:
+        return int(self._pt.stats()["sweep_count"])
+
+    def _check_slot(self, slot, ladder):
+        if not (0 <= slot < self.temperatures.size and 0 <= ladder < self.ladders):
+            raise ValueError(f"slot {slot} / ladder {ladder} out of range ({self.ladders} ladder(s) of {self.temperatures.size})")
+
+    def spins(self, slot: int, ladder: int = 0) -> np.ndarray:
+        """(D, R, C) spins of the walker now at ``slot``."""
+        self._check_slot(slot, ladder)
+        return self._pt.get_spins(ladder, slot)
+
+    def energy(self, slot: int, ladder: int = 0) -> float:
+        """Energy of the walker now at ``slot`` (the device's fixed-order float64 sum)."""
+        self._check_slot(slot, ladder)
+        E, _ = self._pt.energies()
+        return float(E[ladder, self._pt.stats()["walker_at_slot"][ladder, slot]])
+
+
+def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
+                      measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", *, couplings=None, field=None,
+                      replicas: int = 1, swap: bool = True) -> dict:
+    """:func:`temperature_scan_3d` with replica exchange between the temperatures (:class:`LatticeTempering3D`).
+
+    One round = ``measure_every`` sweeps of every walker + one swap pass; ``n_equilibrate`` (a multiple of ``measure_every``)
+    sweeps of rounds, then ``n_measure`` recorded rounds.  Returns temperature_scan_3d's keys, computed with the same expressions
+    from the walker at each temperature (``overlap``, ``overlap_sq``, ``binder`` for ``replicas=2``), plus ``swap_acceptance`` (per
+    adjacent pair, ladders pooled) and ``round_trips`` (all walkers).  ``swap=False`` reproduces ``temperature_scan_3d`` with the
+    same arguments exactly.
+    """
+    if replicas not in (1, 2):
+        raise ValueError("replicas must be 1 or 2")
+    if int(measure_every) < 1 or int(n_equilibrate) % int(measure_every):
+        raise ValueError("n_equilibrate must be a multiple of measure_every")
+    shape = _shape_3d(size)
+    jr, jd, jl, h = _tempering_disorder_3d(shape, _hip.periodic_axes(periodic), float(coupling), 0.0, couplings, field)
+    temperatures = np.asarray(temperatures, dtype=float)
+    pt = LatticeTempering3D(shape, temperatures, couplings=(jr, jd, jl), field=h, periodic=periodic, seed=seed, initial=initial,
+                            ladders=replicas)
+    try:
+        pt.run(int(n_equilibrate) // int(measure_every), int(measure_every), swap=swap, record=False)
+        pt.run(int(n_measure), int(measure_every), swap=swap, record=True)
+        hist = pt._pt.history()
+        N = pt.n_spins
+        out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
+        out["temperatures"] = temperatures
+        Ms = np.ascontiguousarray(hist["M"][:, 0].T) / N
+        Es = np.ascontiguousarray(hist["E"][:, 0].T)
+        Qs = np.ascontiguousarray(hist["q"].T) / N if replicas == 2 else None
+        out = _scan_summary(out, N, Ms, Es, Qs)
+        out["swap_acceptance"] = pt.acceptance
+        out["round_trips"] = pt.round_trips
     finally:
         pt._pt.close()
     return out
