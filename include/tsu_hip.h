@@ -304,6 +304,10 @@ int tsu_ising3d_overlap(tsu_ising3d* a, tsu_ising3d* b, int64_t* q);
 /* k8_sweep launches issued for this lattice so far */
 int tsu_ising3d_launch_count(tsu_ising3d* lat, uint64_t* n_launches);
 
+/* K8: Swendsen-Wang cluster steps on the 3-D handle (tsu_ising3d_cluster_sweep / _cluster_sweep_batch / _cluster_launch_count):
+ * declared in tsu_hip_ising3d_cluster.h, which this header includes; its prototypes are _hip.CLUSTER3D_SIGNATURES in Python. */
+#include "tsu_hip_ising3d_cluster.h"
+
 /* ------------------------------------------------------------------ K8: parallel tempering of 3-D lattices on one disorder
  * tsu_pt2d for cubic lattices: n_ladders (1 or 2) ladders of n_temps (2 .. 256) walkers, every walker a whole K8 lattice (any
  * shape and periodic_mask tsu_ising3d_create takes, with its validation and messages), all sharing ONE disorder.  Walker w of

@@ -48,20 +48,8 @@
 
 #include "disorder_dev.h"
 #include "ising2d.h"
+#include "ising3d.h"
 #include "pt_dev.h"
-
-struct tsu_ising3d {
-    tsu_ctx* ctx;
-    int depth, rows, cols;
-    int pz, pr, pc;      // periodic flag per axis
-    size_t pitch;        // elements per row, spins and disorder alike (cols rounded up to 16)
-    int8_t* s;           // (depth * rows) x pitch spins, pad bytes 0
-    float* d_dis;        // J_right, J_down, J_layer, h: four planes of (depth * rows) x pitch fp32, pads 0 (first set_disorder)
-    int have_disorder;
-    double* d_part;      // energy: per-workgroup partials + the total
-    long long* d_acc;    // sum of spins / overlap accumulator
-    unsigned long long launches;  // k8_sweep launches so far
-};
 
 // Parallel tempering: n_ladders ladders of R walkers (whole K8 lattices) on ONE disorder, the 3-D counterpart of tsu_pt2d
 struct tsu_pt3d {
@@ -624,7 +612,7 @@ int read_acc(tsu_ising3d* L, int64_t* out) {
     TSU_HIP_TRY(ctx, hipMemcpyAsync(&h, L->d_acc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *out = h;
-    return TSU_OK;
+    return ising3d_check_err(L);
 }
 
 void pt_free_history(tsu_pt3d* P) {
@@ -790,6 +778,7 @@ int tsu_ising3d_destroy(tsu_ising3d* L) {
     if (L->d_dis) (void)hipFree(L->d_dis);
     if (L->d_part) (void)hipFree(L->d_part);
     if (L->d_acc) (void)hipFree(L->d_acc);
+    ising3d_cluster_free(L);
     delete L;
     return TSU_OK;
 }
@@ -813,7 +802,7 @@ int tsu_ising3d_get_spins(tsu_ising3d* L, int8_t* host) {
     TSU_HIP_TRY(ctx, hipMemcpy2DAsync(host, (size_t)L->cols, L->s, L->pitch, (size_t)L->cols, (size_t)L->depth * L->rows,
                                       hipMemcpyDeviceToHost, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TSU_OK;
+    return ising3d_check_err(L);
 }
 
 int tsu_ising3d_randomize(tsu_ising3d* L, uint64_t seed, uint32_t replica) {
@@ -858,6 +847,9 @@ int tsu_ising3d_set_disorder(tsu_ising3d* L, const float* J_right, const float* 
                 TSU_REQUIRE(ctx, L->pz || z + 1 < depth || J_layer[i] == 0.0f,
                             "ising3d_set_disorder: open axis: J_layer[%d, %d, %d] (last layer) must be 0, got %g", z, r, c, (double)J_layer[i]);
             }
+    int have_field = 0;
+    if (h)
+        for (size_t i = 0, n = (size_t)depth * rows * cols; i < n && !have_field; ++i) have_field = h[i] != 0.0f;
     const size_t nrows = (size_t)depth * rows, plane = nrows * L->pitch;
     if (!L->d_dis) {
         TSU_HIP_TRY(ctx, hipMalloc((void**)&L->d_dis, 4 * plane * sizeof(float)));
@@ -871,6 +863,7 @@ int tsu_ising3d_set_disorder(tsu_ising3d* L, const float* J_right, const float* 
     else TSU_HIP_TRY(ctx, hipMemsetAsync(L->d_dis + 3 * plane, 0, plane * sizeof(float), ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     L->have_disorder = 1;
+    L->have_field = have_field;
     return TSU_OK;
 }
 
@@ -913,7 +906,7 @@ int tsu_ising3d_energy(tsu_ising3d* L, double* E) {
     TSU_HIP_TRY(ctx, hipMemcpyAsync(&e, L->d_part + kEnergyBlocks, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *E = e;
-    return TSU_OK;
+    return ising3d_check_err(L);
 }
 
 int tsu_ising3d_sum_spins(tsu_ising3d* L, int64_t* sum_s) {

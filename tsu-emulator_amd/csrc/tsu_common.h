@@ -104,7 +104,8 @@ enum : uint32_t {
     TSU_TAG_SW_BOND = 6,
     TSU_TAG_SW_FLIP = 7,
     TSU_TAG_PT_SWAP = 8,
-    TSU_TAG_PT_ICM = 9
+    TSU_TAG_PT_ICM = 9,
+    TSU_TAG_SW_LAYER = 10
 };
 
 struct u32x4 {

@@ -162,6 +162,14 @@ SIGNATURES = {
     "tsu_langevin_set_kernel": (C.c_int, [_vp, C.c_int]),
 }
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_ising3d_cluster.h (the header tsu_hip.h includes) one to one
+CLUSTER3D_SIGNATURES = {
+    "tsu_ising3d_cluster_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_ising3d_cluster_sweep_batch": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64),
+                                                  C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tsu_ising3d_cluster_launch_count": (C.c_int, [_vp, _u64p]),
+}
+
 _lib = None
 
 
@@ -178,7 +186,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailableError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -510,6 +518,15 @@ class Lattice3D:
         self.ctx.check(self.lib.tsu_ising3d_launch_count(self.h, C.byref(n)))
         return n.value
 
+    def cluster_sweep(self, T, n_steps, seed, step0=0, replica=0):
+        """n_steps Swendsen-Wang steps on the stored couplings at temperature T, zero field (step counters step0 ..)."""
+        self.ctx.check(self.lib.tsu_ising3d_cluster_sweep(self.h, float(T), int(n_steps), int(seed), int(step0), int(replica)))
+
+    def cluster_launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_ising3d_cluster_launch_count(self.h, C.byref(n)))
+        return n.value
+
 
 class TemperingLattice:
     """tsu_pt2d handle (K7 parallel tempering): n_ladders ladders of n_temps walkers of one rows x cols lattice sharing one
@@ -738,6 +755,21 @@ def cluster_sweep_batch(lattices, n_steps, Js, Ts, seeds, step0s, replicas=None)
     s0 = (C.c_uint32 * n)(*[int(v) for v in step0s])
     rp = (C.c_uint32 * n)(*([0] * n if replicas is None else [int(v) for v in replicas]))
     ctx.check(lattices[0].lib.tsu_ising2d_cluster_sweep_batch(hs, n, int(n_steps), js, ts, sd, s0, rp))
+
+
+def cluster_sweep_batch_3d(lattices, n_steps, Ts, seeds, step0s, replicas=None):
+    """n_steps Swendsen-Wang steps of every 3-D lattice (own disorder, T, seed, step counter, replica id); small lattices of one
+    shape and boundary run in one launch.  Same results as stepping them one by one."""
+    n = len(lattices)
+    if n == 0:
+        return
+    ctx = lattices[0].ctx
+    hs = (_vp * n)(*[l.h for l in lattices])
+    ts = (C.c_double * n)(*[float(v) for v in Ts])
+    sd = (C.c_uint64 * n)(*[int(v) for v in seeds])
+    s0 = (C.c_uint32 * n)(*[int(v) for v in step0s])
+    rp = (C.c_uint32 * n)(*([0] * n if replicas is None else [int(v) for v in replicas]))
+    ctx.check(lattices[0].lib.tsu_ising3d_cluster_sweep_batch(hs, n, int(n_steps), ts, sd, s0, rp))
 
 
 def observables_batch(lattices):

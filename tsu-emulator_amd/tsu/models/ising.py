@@ -771,6 +771,12 @@ def _disorder_arrays_3d(shape, periodic, coupling: float, external_field: float,
     return jr, jd, jl, h
 
 
+def _check_cluster_field_3d(h) -> None:
+    """Swendsen-Wang samples the zero-field measure: refuse a stored field before the device is touched."""
+    if h is not None and np.any(h != 0):
+        raise _hip.UnsupportedError("Swendsen-Wang cluster updates need zero field (a field would need a ghost spin)")
+
+
 def _shape_3d(size):
     shape = (size,) * 3 if np.isscalar(size) else tuple(int(n) for n in size)
     if len(shape) != 3 or min(shape) < 1:
@@ -786,8 +792,9 @@ class IsingModel3D:
     site's field.  ``periodic`` is a bool or a triple (p_z, p_r, p_c); a periodic axis wraps and needs an even length >= 4, on an
     open axis the last slice of that axis's J must be 0.  Uniform ``coupling=`` / ``external_field=`` are the constant-array case
     of the same kernel.  The arrays are rounded once to float32 (``disorder`` returns the rounded copies).
-    ``gibbs_update()`` = one checkerboard heat-bath sweep; ``energy()`` / ``magnetization()`` / ``overlap(other)`` are device
-    reductions; ``equilibrate(T)`` sets the temperature, runs ``n_sweeps`` sweeps and returns ``self``.
+    ``gibbs_update()`` = one checkerboard heat-bath sweep; ``cluster_update()`` = one Swendsen-Wang step on the stored couplings
+    (zero field only; its own counter ``cluster_count``); ``energy()`` / ``magnetization()`` / ``overlap(other)`` are device
+    reductions; ``equilibrate(T)`` sets the temperature, runs ``n_sweeps`` sweeps (or SW steps) and returns ``self``.
     """
 
     def __init__(self, size, coupling: float = 1.0, temperature: float = 1.0, periodic=True, external_field: float = 0.0,
@@ -806,6 +813,7 @@ class IsingModel3D:
         self.seed = int(seed) if seed is not None else (
             int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
         self.sweep_count = 0
+        self.cluster_count = 0
         self._lat = _hip.Lattice3D(self.depth, self.rows, self.cols, self.periodic)
         if initial == "random":
             self._lat.randomize(self.seed)
@@ -831,11 +839,24 @@ class IsingModel3D:
         self.sweep_count += int(n_sweeps)
         return self
 
-    def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000) -> "IsingModel3D":
+    def cluster_update(self, n_steps: int = 1) -> "IsingModel3D":
+        """n_steps Swendsen-Wang steps on the stored couplings; the heat-bath stream and ``sweep_count`` are not touched."""
+        _check_cluster_field_3d(self._disorder[3])
+        self._lat.cluster_sweep(self.temperature, int(n_steps), self.seed, self.cluster_count)
+        self.cluster_count += int(n_steps)
+        return self
+
+    def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000,
+                    algorithm: str = "gibbs") -> "IsingModel3D":
+        _check_algorithm(algorithm)
+        if algorithm == "swendsen_wang":
+            _check_cluster_field_3d(self._disorder[3])
         if temperature is not None:
             if not temperature > 0:
                 raise ValueError("Temperature must be positive")
             self.temperature = float(temperature)
+        if algorithm == "swendsen_wang":
+            return self.cluster_update(n_sweeps)
         return self.gibbs_update(n_sweeps)
 
     def magnetization(self) -> float:
@@ -863,13 +884,15 @@ class IsingModel3D:
 
 
 def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
-                        measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", *, couplings=None, field=None,
-                        replicas: int = 1) -> dict:
+                        measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", algorithm: str = "gibbs", *,
+                        couplings=None, field=None, replicas: int = 1) -> dict:
     """:func:`temperature_scan` for a cubic lattice (K8): one :class:`IsingModel3D` per temperature stays on the device and
     |M|, E/N, chi and C come from the device reductions.  ``couplings`` / ``field``: the same quenched disorder at every
     temperature.  Model i of replica k has seed ``seed + k len(temperatures) + i``.  ``replicas=2``: the result gains
     ``overlap`` = <|q|>, ``overlap_sq`` = <q^2> and ``binder`` = (3 - <q^4> / <q^2>^2) / 2 of q = overlap / N; the other keys are
-    those of the first replica."""
+    those of the first replica.  ``algorithm="swendsen_wang"``: ``n_equilibrate`` and ``measure_every`` count Swendsen-Wang steps
+    on the couplings (zero field only); lattices of at most 16384 sites advance together, one launch per batch of steps."""
+    _check_algorithm(algorithm)
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
     temperatures = np.asarray(temperatures, dtype=float)
@@ -878,18 +901,30 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
     shape = _shape_3d(size)
     # validated once, before any device call
     disorder = _disorder_arrays_3d(shape, _hip.periodic_axes(periodic), float(coupling), 0.0, couplings, field)
+    if algorithm == "swendsen_wang":
+        _check_cluster_field_3d(disorder[3])
     out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
     out["temperatures"] = temperatures
     nT = len(temperatures)
     models = [IsingModel3D(shape, temperature=float(T), periodic=periodic, seed=seed + k * nT + i, initial=initial,
                            couplings=disorder[:3], field=disorder[3])
               for k in range(replicas) for i, T in enumerate(temperatures)]
-    for m in models:
-        m.gibbs_update(int(n_equilibrate))
+
+    def advance(n):
+        if algorithm == "swendsen_wang":  # the streams (seed, own step counter) are those of stepping the models one by one
+            _hip.cluster_sweep_batch_3d([m._lat for m in models], n, [m.temperature for m in models], [m.seed for m in models],
+                                        [m.cluster_count for m in models])
+            for m in models:
+                m.cluster_count += int(n)
+            return
+        for m in models:
+            m.gibbs_update(int(n))
+
+    if models:
+        advance(int(n_equilibrate))
     Ms, Es, Qs = np.zeros((nT, n_measure)), np.zeros((nT, n_measure)), np.zeros((nT, n_measure))
     for j in range(n_measure if models else 0):
-        for m in models:
-            m.gibbs_update(int(measure_every))
+        advance(int(measure_every))
         for i in range(nT):
             Ms[i, j] = models[i].magnetization()
             Es[i, j] = models[i].energy()
