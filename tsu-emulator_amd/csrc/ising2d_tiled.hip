@@ -196,15 +196,21 @@ static __device__ __forceinline__ uint64_t pack_flags(const u32x4& d) {
 
 // EDGE tiles: global rows of the pair at tile rows (tr, tr + 1).  The lattice's last row falls at ONE tile row (wrap_tr), so a
 // wave's lanes (a few consecutive row lanes: tile rows tr_wave .. tr_wave + SPAN) lie on one side of it in all but one
-// wave-iteration per half-sweep: the offset is a scalar select and the per-lane compares run in that one iteration only
-// (they cost the edge tiles +4.7 % when every lane made them every time -- and the edge tiles set every tile's pace).
+// wave-iteration per half-sweep: the offset is a scalar select and the per-lane compares run in that one iteration only.
+// The wave carries to_wrap = wrap_tr - tr_wave, counted down from pair to pair, so that both questions are one scalar
+// compare each: "past the wrap" is to_wrap <= 0, "this iteration straddles it" is 0 < to_wrap <= SPAN, i.e.
+// (unsigned)(to_wrap - 1) < SPAN -- 5 scalar instructions per pair where comparing tr_wave with wrap_tr twice and combining
+// the two conditions took 10, on a dependent chain in front of the branch.  The edge tiles set every tile's pace (each
+// generation's strips wait for them: profiles/resident_exchange_parent_timeline.txt), so what they lose all 256 tiles lose.
+// (Tried instead: the wrapped row itself carried per lane, a subtract and an unsigned minimum per step and per row, no scalar
+// work and no branch: as good on byte planes, 2.5 % slower on the nibble planes of 8192^2: profiles/resident_exchange_ab.txt.)
 template <int NO>
-static __device__ __forceinline__ void edge_rows(const Rows2Ctx& c, int tr_wave, int tr, int& rga, int& rgb) {
+static __device__ __forceinline__ void edge_rows(const Rows2Ctx& c, int to_wrap, int tr, int& rga, int& rgb) {
     constexpr int SPAN = 2 * ((NO - 1 + 63) / NO) + 1;  // tile rows below the first lane's that a wave's 64 lanes can reach
-    const int s_off = tr_wave >= c.wrap_tr ? c.rg_tile0 - c.total_rows : c.rg_tile0;
+    const int s_off = to_wrap > 0 ? c.rg_tile0 : c.rg_tile0 - c.total_rows;
     rga = tr + s_off;
     rgb = rga + 1;
-    if (__builtin_expect(tr_wave < c.wrap_tr && tr_wave + SPAN >= c.wrap_tr, 0)) {  // wave-uniform
+    if (__builtin_expect((uint32_t)(to_wrap - 1) < (uint32_t)SPAN, 0)) {  // wave-uniform
         rga = tr + c.rg_tile0;
         asm volatile("" : "+v"(rga));  // a real branch: as selects this would cost every iteration 9 instructions
         rgb = rga + 1;
@@ -227,9 +233,9 @@ static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const Phil
     int off = (tr_first * NO + oct) * 8;
     // EDGE (the tile's window crosses the lattice's last row): rg counts tile rows and the wrap is applied per wave, see edge_rows
     int rg = EDGE ? tr_first : c.rgf + (tr_first - c.tr_lo);
-    int tr_wave = EDGE ? __builtin_amdgcn_readfirstlane(rg) : 0;  // tile row of the wave's first lane (lanes ascend in rows)
+    int to_wrap = EDGE ? c.wrap_tr - __builtin_amdgcn_readfirstlane(rg) : 0;  // from the wave's first lane (lanes ascend in rows)
 #pragma unroll 1
-    for (; off < off_end; off += off_step, rg += step_rows, tr_wave += step_rows) {
+    for (; off < off_end; off += off_step, rg += step_rows, to_wrap -= step_rows) {
         asm volatile("" : "+v"(off), "+v"(rg));
         // issue the six LDS reads, run the two Philox blocks (which do not depend on them) while they are in flight,
         // and only then consume the neighbour rows
@@ -246,7 +252,7 @@ static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const Phil
         const uint64_t Nb = SEAM ? *reinterpret_cast<const uint64_t*>(ps + NO * 8 + (P0 ? -8 : 8)) : 0ull;
         __builtin_amdgcn_sched_barrier(0);  // the reads stay above the Philox blocks ...
         int rga = rg, rgb = rg + 1;
-        if (EDGE) edge_rows<NO>(c, tr_wave, rg, rga, rgb);
+        if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
         const u32x4 w0 = philox_vk(cq, (uint32_t)rga, c.hs, c.tag_hi, K);
         const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.hs, c.tag_hi, K);
         __builtin_amdgcn_sched_barrier(0);  // ... and their first use stays below
@@ -344,9 +350,9 @@ static __device__ __forceinline__ void sweep_pairs_nib(const Rows2Ctx& c, const 
     const int off_step = step_rows * NO * 4;
     int off = (tr_first * NO + oct) * 4;
     int rg = EDGE ? tr_first : c.rgf + (tr_first - c.tr_lo);
-    int tr_wave = EDGE ? __builtin_amdgcn_readfirstlane(rg) : 0;
+    int to_wrap = EDGE ? c.wrap_tr - __builtin_amdgcn_readfirstlane(rg) : 0;
 #pragma unroll 1
-    for (; off < off_end; off += off_step, rg += step_rows, tr_wave += step_rows) {
+    for (; off < off_end; off += off_step, rg += step_rows, to_wrap -= step_rows) {
         asm volatile("" : "+v"(off), "+v"(rg));
         const char* ps = ps0 + off;
         const uint32_t R0 = *reinterpret_cast<const uint32_t*>(ps - NO * 4), R1 = *reinterpret_cast<const uint32_t*>(ps);
@@ -355,7 +361,7 @@ static __device__ __forceinline__ void sweep_pairs_nib(const Rows2Ctx& c, const 
         const uint32_t A1 = *reinterpret_cast<const uint32_t*>(ps + NO * 4 + (P0 ? -4 : 4));  // row b: the other side
         __builtin_amdgcn_sched_barrier(0);
         int rga = rg, rgb = rg + 1;
-        if (EDGE) edge_rows<NO>(c, tr_wave, rg, rga, rgb);
+        if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
         const u32x4 w0 = philox_vk(cq, (uint32_t)rga, c.hs, c.tag_hi, K);
         const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.hs, c.tag_hi, K);
         __builtin_amdgcn_sched_barrier(0);
@@ -903,7 +909,8 @@ int lattice_env(const char* name, int dflt) {
 // Generation time (us) of k = 8 sweeps on tiles of h rows, fitted to measurements (4096^2, 2048^2, 1024^2, 4096 x 8192, open
 // 1000^2; profiles/r01_k1_experiments.txt): a half-sweep costs 0.25 us + 0.225 us per wave-iteration of the busiest SIMD (6 %
 // more on nibble planes); between generations `between` us: the strip exchange costs 4.3 us when the tiles stay resident in LDS,
-// the tile store + launch gap + stage about 12 us when they do not.
+// the tile store + launch gap + stage about 12 us when they do not.  (The fit is older than the counted-down EDGE form of
+// edge_rows, which took about 0.1 us per sweep off 4096^2 and 0.2 us off 8192^2; it has not been re-fitted since.)
 double gen_time_us(const TileVariant& c, int h, double between) {
     const int pairs = (h + 4 * 8 - 2) / 2, waves = (pairs * (c.WO + 2) + 63) / 64;
     return 16.0 * (0.25 + (c.nib ? 1.06 : 1.0) * 0.225 * ((waves + 3) / 4)) + between;
