@@ -237,12 +237,20 @@ def test_symbols_in_header_and_library():
 
 
 def test_swap_kernel_is_defined_once():
-    """Both handle types launch the one swap kernel of pt_dev.h; neither source file defines a swap kernel of its own."""
+    """Both handle types run the one ladder core: over all of csrc the swap kernel is launched once, in pt_host.h, and the swap,
+    pt_energy_final and pt_overlap kernels are defined once each; neither source file defines a swap kernel of its own."""
     csrc = os.path.join(ROOT, "tsu-emulator_amd", "csrc")
     pat = re.compile(r"__global__[^;{]*\bk\d_pt_swap\b")
     assert len(pat.findall(open(os.path.join(csrc, "pt_dev.h")).read())) == 1
     for name in ("ising2d_disorder.hip", "ising3d.hip", "ising2d_icm.hip"):
         src = open(os.path.join(csrc, name)).read()
         assert not pat.search(src), name
-    assert "k7_pt_swap<<<" in open(os.path.join(csrc, "ising3d.hip")).read()
-    assert "pt_dev.h" in open(os.path.join(csrc, "build.sh")).read()
+    sources = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    launches = {f: len(re.findall(r"\bk\d_pt_swap\s*<<<", s)) for f, s in sources.items()}
+    assert {f: n for f, n in launches.items() if n} == {"pt_host.h": 1}
+    for kernel in (r"k\d_pt_swap", r"(?:k\d_)?pt_energy_final", r"(?:k\d_)?pt_overlap"):
+        defs = re.compile(rf"__global__[^;{{]*\b{kernel}\s*\(")
+        assert sum(len(defs.findall(s)) for s in sources.values()) == 1, kernel
+    build = open(os.path.join(csrc, "build.sh")).read()
+    for header in ("pt_dev.h", "pt_host.h", "reduce_dev.h"):
+        assert header in build, header

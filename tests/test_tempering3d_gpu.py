@@ -179,7 +179,9 @@ def test_without_swaps_equals_temperature_scan_3d(hip, shape, periodic, replicas
 
 @pytest.mark.parametrize("rows,cols,periodic", [(6, 40, True), (5, 37, False)])
 def test_one_layer_ladder_has_the_2d_ladders_spins(hip, rows, cols, periodic):
-    """D = 1, open z, swap=False: the spins of the 2-D TemperingLattice on the same arrays."""
+    """D = 1, open z, swap=False: the spins of the 2-D TemperingLattice on the same arrays.  Then four swapping, recorded rounds
+    on both: with one open layer k8_energy_lane adds h, J_right and J_down in k7_energy_lane's order over the same lanes, so the
+    energies, and with them the swaps, the history, the counters and the spins at every slot, are equal exactly."""
     shape = (1, rows, cols)
     jr, jd, _, h = _disorder(shape, (False, periodic, periodic), 11)
     seed = 21
@@ -195,6 +197,20 @@ def test_one_layer_ladder_has_the_2d_ladders_spins(hip, rows, cols, periodic):
         for k in range(2):
             for w in range(len(TS)):
                 _same(p3.get_spins(k, w).reshape(rows, cols), p2.get_spins(k, w), f"ladder {k} walker {w}")
+        p3.run(4, 3, swap=True, record=True)
+        p2.run(4, 3, swap=True, record=True)
+        h3, h2 = p3.history(), p2.history()
+        for key in ("E", "M", "walker", "q"):
+            assert np.array_equal(h3[key], h2[key]), key
+        s3, s2 = p3.stats(), p2.stats()
+        assert set(s3) == set(s2)
+        for key in s3:
+            assert np.array_equal(s3[key], s2[key]), key
+        for a3, a2 in zip(p3.energies(), p2.energies()):
+            assert np.array_equal(a3, a2)
+        for k in range(2):
+            for slot in range(len(TS)):
+                _same(p3.get_spins(k, slot).reshape(rows, cols), p2.get_spins(k, slot), f"ladder {k} slot {slot}")
     finally:
         p3.close()
         p2.close()

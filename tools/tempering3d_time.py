@@ -47,7 +47,7 @@ def bytes_per_walker_sweep(L, W):
 
 
 def group_of(L, nw, cus):
-    """The walker-group size csrc/ising3d.hip (pt_group) picks."""
+    """The walker-group size pt_group (csrc/pt_host.h, the one both ladder types call) picks."""
     lanes = L * L * ((L + 15) // 16)
     groups = -(-cus * 1024 // lanes)
     return 1 if groups >= nw else -(-nw // groups)

@@ -30,17 +30,20 @@
 // J_layer[z-1] are the own rows of other lanes of the launch and come from L2) and the spins (1 B per site from HBM, the four
 // neighbour rows from L2), and writes 1 B per site: ~36 B per site and sweep.
 //
-// k8_energy + k8_energy_final: E = -sum_bonds J s s' - sum h s in float64, a fixed number of per-workgroup partials then one
+// k8_energy + energy_final: E = -sum_bonds J s s' - sum h s in float64, a fixed number of per-workgroup partials then one
 // workgroup summing them in a fixed order (the same bits on every call).  k8_sum / k8_overlap: sum s and q = sum s^a s^b
-// (integers, one 64-bit vector atomic per workgroup).  No cooperative launch, no waiting, no atomics on the sweep path.
+// (integers, one 64-bit vector atomic per workgroup).  The workgroup sums, the final sums and the pair lane are reduce_dev.h's,
+// shared with K7.  No cooperative launch, no waiting, no atomics on the sweep path.
 //
 // Parallel tempering (tsu_pt3d_*): ladders of R walkers on ONE disorder ("Parallel tempering in 3-D (K8)").
 // k8_pt_sweep is k8_sweep for a group of W walkers per lane (the walker group is the grid's z dimension): the octet's six
 // couplings, field and screen bound are staged once and every walker of the group takes k8_octet's decision at the temperature
-// of its slot, so the 32 B per site of disorder a sweep reads are shared by W walkers.  k8_pt_energy / k8_pt_energy_final run
-// k8_energy's decomposition per walker through the same device helpers (the bits of tsu_ising3d_energy) and sum the spins
-// alongside; the swap pass is the 2-D ladders' kernel (pt_dev.h); k8_pt_overlap records q of the two ladders' walkers at each
-// slot.  No host value changes between rounds: a run of many rounds is enqueued without a synchronisation.
+// of its slot, so the 32 B per site of disorder a sweep reads are shared by W walkers.  k8_pt_energy runs k8_energy's
+// decomposition per walker through the same device helper (the bits of tsu_ising3d_energy) and sums the spins alongside.  The
+// rest of a ladder does not know the dimension and is the 2-D ladders': the handle's tables and the host side of every entry point
+// (pt_host.h), the final sums and q per slot (pt_energy_final, pt_overlap, reduce_dev.h) and the swap pass (pt_dev.h).  This file
+// passes in how a half-sweep and an energy partial pass are launched.  No host value changes between rounds: a run of many rounds
+// is enqueued without a synchronisation.
 #include <cmath>
 #include <cstdlib>
 #include <new>
@@ -49,42 +52,15 @@
 #include "disorder_dev.h"
 #include "ising2d.h"
 #include "ising3d.h"
-#include "pt_dev.h"
+#include "pt_host.h"
+#include "reduce_dev.h"
 
-// Parallel tempering: n_ladders ladders of R walkers (whole K8 lattices) on ONE disorder, the 3-D counterpart of tsu_pt2d
-struct tsu_pt3d {
-    tsu_ctx* ctx;
-    int R, nl, nw;                 // temperatures, ladders, walkers (R * nl)
-    tsu_ising3d** lat;             // walker g = ladder * R + w; lat[0] also holds the one disorder
-    int have_T, have_init;
-    uint32_t sweeps, rounds;       // sweeps of every walker and rounds since init
-    unsigned long long launches;   // k8_pt_sweep launches
-    int hist_rounds;               // rows recorded by the last run
-    size_t hist_cap;               // rows the history buffers hold
-    int8_t** d_s;                  // walker -> its spins
-    uint32_t* d_key;               // walker -> (k0, k1)
-    int32_t* d_slot;               // [ladder][walker] -> slot
-    int32_t* d_was;                // [ladder][slot] -> walker
-    int32_t* d_flag;               // [ladder][walker] -> round-trip flag
-    double* d_T;                   // slot -> T
-    float* d_c32;                  // slot -> fl32(2 / T)
-    long long* d_att;              // [ladder][pair]
-    long long* d_acc;
-    long long* d_trips;            // [ladder][walker]
-    double* d_part;                // [walker][kEnergyBlocks] energy partials
-    long long* d_ipart;            // [walker][kEnergyBlocks] sum-of-spin partials
-    double* d_E;                   // walker -> E of the last energy pass
-    long long* d_M;                // walker -> sum of spins
-    double* d_hE;                  // [round][ladder][slot]
-    long long* d_hM;
-    int32_t* d_hW;
-    long long* d_hq;               // [round][slot] (two ladders)
-    uint32_t key0, key1;           // Philox key of the swap uniforms (the seed)
+// Parallel tempering: pt_ladder.h's ladder with whole K8 lattices as its walkers, the 3-D counterpart of tsu_pt2d
+struct tsu_pt3d : pt_ladder {
+    tsu_ising3d** lat;  // walker g = ladder * R + w; lat[0] also holds the one disorder
 };
 
 namespace {
-
-constexpr int kEnergyBlocks = 1024;  // fixed partial count: the summation order depends on the shape only
 
 struct K8Params {
     int8_t* s;
@@ -261,23 +237,6 @@ __global__ __launch_bounds__(256) void k8_fill(K8Params p, int value) {
     *reinterpret_cast<uint4*>(p.s + rho * p.pitch + 16 * q) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
-// workgroup sum of 256 lanes: fixed shuffle tree, then the four waves in a fixed order (every thread gets it)
-__device__ __forceinline__ double k8_block_sum(double e) {
-    for (int off = 32; off > 0; off >>= 1) e += __shfl_down(e, off, 64);
-    __shared__ double wpart[4];
-    if ((threadIdx.x & 63) == 0) wpart[threadIdx.x >> 6] = e;
-    __syncthreads();
-    return (wpart[0] + wpart[1]) + (wpart[2] + wpart[3]);
-}
-
-__device__ __forceinline__ long long k8_block_isum(long long v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __shared__ long long wpart[4];
-    if ((threadIdx.x & 63) == 0) wpart[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return wpart[0] + wpart[1] + wpart[2] + wpart[3];
-}
-
 // E partial of a lane: lane = chunk (rho, q), grid-stride over blockIdx.x in a fixed order; a site adds
 // s (((h + J_right s_right) + J_down s_down) + J_layer s_layer), a bond missing on an open axis skipped; ssum = the lane's sum
 // of spins.  Shared by the single-lattice and the ladder kernels: the lane order is part of the contract.
@@ -313,60 +272,21 @@ __device__ __forceinline__ double k8_energy_lane(const K8Params& p, long long& s
 // E partials: one per workgroup
 __global__ __launch_bounds__(256) void k8_energy(K8Params p, double* __restrict__ part) {
     long long m;
-    const double e = k8_block_sum(k8_energy_lane(p, m));
+    const double e = block_sum(k8_energy_lane(p, m));
     if (threadIdx.x == 0) part[blockIdx.x] = e;
-}
-
-// -(sum of the n partials), in a fixed order (every thread gets it)
-__device__ __forceinline__ double k8_final_sum(const double* __restrict__ part, int n) {
-    double e = 0.0;
-    for (int i = threadIdx.x; i < n; i += 256) e += part[i];
-    return -k8_block_sum(e);
-}
-
-// one workgroup: out[0] = E
-__global__ __launch_bounds__(256) void k8_energy_final(const double* __restrict__ part, int n, double* __restrict__ out) {
-    const double e = k8_final_sum(part, n);
-    if (threadIdx.x == 0) out[0] = e;
-}
-
-// sum over sites of s^a s^b (columns < cols only); both lattices have the same shape and pitch
-__device__ __forceinline__ long long k8_pair_lane(const int8_t* __restrict__ a, const int8_t* __restrict__ b, long long pitch,
-                                                  long long nrows, int cols) {
-    const int nchunks = (cols + 15) >> 4;
-    const long long total = nrows * nchunks;
-    long long sum = 0;
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
-        const long long rho = t / nchunks;
-        const int q = (int)(t - rho * nchunks);
-        const uint4 va = *reinterpret_cast<const uint4*>(a + rho * pitch + 16 * q);
-        int cs = 0;
-        if (b) {
-            const uint4 vb = *reinterpret_cast<const uint4*>(b + rho * pitch + 16 * q);
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if (16 * q + i < cols) cs += sbyte(va, i) * sbyte(vb, i);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-                if (16 * q + i < cols) cs += sbyte(va, i);
-        }
-        sum += cs;
-    }
-    return sum;
 }
 
 // q = sum s^a s^b, one 64-bit vector atomic per workgroup
 __global__ __launch_bounds__(256) void k8_overlap(const int8_t* __restrict__ a, const int8_t* __restrict__ b, long long pitch,
                                                   long long nrows, int cols, long long* __restrict__ acc) {
-    const long long v = k8_block_isum(k8_pair_lane(a, b, pitch, nrows, cols));
+    const long long v = block_isum(pair_lane(a, b, pitch, pitch, nrows, cols));
     if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)v);
 }
 
 // sum s
 __global__ __launch_bounds__(256) void k8_sum(const int8_t* __restrict__ a, long long pitch, long long nrows, int cols,
                                               long long* __restrict__ acc) {
-    const long long v = k8_block_isum(k8_pair_lane(a, nullptr, pitch, nrows, cols));
+    const long long v = block_isum(pair_lane(a, nullptr, pitch, pitch, nrows, cols));
     if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(acc), (unsigned long long)v);
 }
 
@@ -537,34 +457,12 @@ __device__ __forceinline__ K8Params pt_walker_params(const PT3Params& pp, int g)
 // grid (blocks_for(lattice), nw): workgroup x of walker y computes k8_energy's partial x of that walker alone, and its sum of spins
 __global__ __launch_bounds__(256) void k8_pt_energy(PT3Params pp, double* __restrict__ part, long long* __restrict__ ipart) {
     long long m;
-    const double e = k8_block_sum(k8_energy_lane(pt_walker_params(pp, blockIdx.y), m));
-    const long long ms = k8_block_isum(m);
+    const double e = block_sum(k8_energy_lane(pt_walker_params(pp, blockIdx.y), m));
+    const long long ms = block_isum(m);
     if (threadIdx.x == 0) {
         part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
         ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
     }
-}
-
-// one workgroup per walker: E as k8_energy_final sums it, and the sum of spins
-__global__ __launch_bounds__(256) void k8_pt_energy_final(const double* __restrict__ part, const long long* __restrict__ ipart, int n,
-                                                          double* __restrict__ E, long long* __restrict__ M) {
-    const size_t base = (size_t)blockIdx.x * kEnergyBlocks;
-    const double e = k8_final_sum(part + base, n);
-    long long m = 0;
-    for (int i = threadIdx.x; i < n; i += 256) m += ipart[base + i];
-    const long long ms = k8_block_isum(m);
-    if (threadIdx.x == 0) {
-        E[blockIdx.x] = e;
-        M[blockIdx.x] = ms;
-    }
-}
-
-// grid (blocks_for(lattice), R): q of the two ladders' walkers at slot y, added into out[y] (a zeroed history row)
-__global__ __launch_bounds__(256) void k8_pt_overlap(int8_t* const* __restrict__ s, const int32_t* __restrict__ was, int R,
-                                                     long long pitch, long long nrows, int cols, long long* __restrict__ out) {
-    const int i = blockIdx.y;
-    const long long v = k8_block_isum(k8_pair_lane(s[was[i]], s[R + was[R + i]], pitch, nrows, cols));
-    if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out + i), (unsigned long long)v);
 }
 
 K8Params make_params(const tsu_ising3d* L) {
@@ -599,11 +497,7 @@ dim3 octet_grid(const K8Params& p) {
     return dim3((unsigned)((p.nrows + rpb - 1) / rpb), (unsigned)((nchunks + 63) / 64), 1);
 }
 
-unsigned blocks_for(const tsu_ising3d* L) {
-    const long long work = (long long)L->depth * L->rows * ((L->cols + 15) / 16);
-    const long long b = (work + 255) / 256;
-    return (unsigned)(b < kEnergyBlocks ? b : kEnergyBlocks);
-}
+unsigned blocks_for(const tsu_ising3d* L) { return reduce_blocks((long long)L->depth * L->rows * ((L->cols + 15) / 16)); }
 
 int read_acc(tsu_ising3d* L, int64_t* out) {
     tsu_ctx* ctx = L->ctx;
@@ -615,68 +509,7 @@ int read_acc(tsu_ising3d* L, int64_t* out) {
     return ising3d_check_err(L);
 }
 
-void pt_free_history(tsu_pt3d* P) {
-    void* bufs[] = {P->d_hE, P->d_hM, P->d_hW, P->d_hq};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    P->d_hE = nullptr;
-    P->d_hM = nullptr;
-    P->d_hW = nullptr;
-    P->d_hq = nullptr;
-    P->hist_cap = 0;
-}
-
-void pt_free(tsu_pt3d* P) {
-    void* bufs[] = {P->d_s, P->d_key, P->d_slot, P->d_was, P->d_flag, P->d_T, P->d_c32, P->d_att, P->d_acc,
-                    P->d_trips, P->d_part, P->d_ipart, P->d_E, P->d_M};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
-    pt_free_history(P);
-    if (P->lat) {
-        for (int g = 0; g < P->nw; ++g)
-            if (P->lat[g]) (void)tsu_ising3d_destroy(P->lat[g]);
-        delete[] P->lat;
-    }
-    delete P;
-}
-
-// every walker at its own slot, the walker at slot 0 "bottom", no attempts, accepts or round trips (synchronises)
-int pt_reset(tsu_pt3d* P) {
-    tsu_ctx* ctx = P->ctx;
-    const int R = P->R, nl = P->nl;
-    std::vector<int32_t> ident((size_t)nl * R), flag((size_t)nl * R, kPtNone);
-    for (int k = 0; k < nl; ++k) {
-        for (int w = 0; w < R; ++w) ident[(size_t)k * R + w] = w;
-        flag[(size_t)k * R] = kPtBottom;
-    }
-    const size_t b = (size_t)nl * R * sizeof(int32_t);
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_slot, ident.data(), b, hipMemcpyHostToDevice, ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_was, ident.data(), b, hipMemcpyHostToDevice, ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_flag, flag.data(), b, hipMemcpyHostToDevice, ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_att, 0, (size_t)nl * (R - 1) * sizeof(long long), ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_acc, 0, (size_t)nl * (R - 1) * sizeof(long long), ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_trips, 0, (size_t)nl * R * sizeof(long long), ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    P->sweeps = P->rounds = 0;
-    P->hist_rounds = 0;
-    return TSU_OK;
-}
-
-// Walkers per lane of k8_pt_sweep, chosen as the 2-D ladders choose it: the fewest groups that still give >= 1024 lanes per CU
-// (a lane per octet and group), so a large lattice reads each octet's disorder once for many walkers and a small one spreads its
-// walkers over the chip.  TSU_PT_GROUP=w (read per call) forces w.
-int pt_group(const tsu_pt3d* P) {
-    if (const char* e = getenv("TSU_PT_GROUP")) {
-        const int w = atoi(e);
-        if (w >= 1) return w < P->nw ? w : P->nw;
-    }
-    const tsu_ising3d* L = P->lat[0];
-    const long long lanes = (long long)L->depth * L->rows * ((L->cols + 15) / 16);
-    const long long want = (long long)(P->ctx->cus > 0 ? P->ctx->cus : 256) * 1024;
-    const long long groups = (want + lanes - 1) / lanes;
-    if (groups >= P->nw) return 1;
-    return (int)((P->nw + groups - 1) / groups);
-}
+void pt_free(tsu_pt3d* P) { pt_delete(P, tsu_ising3d_destroy); }
 
 PT3Params pt_params(const tsu_pt3d* P) {
     const K8Params k = make_params(P->lat[0]);
@@ -705,24 +538,9 @@ PT3Params pt_params(const tsu_pt3d* P) {
     return p;
 }
 
-// every walker's E and sum of spins into d_E / d_M (asynchronous)
-void pt_enqueue_energies(tsu_pt3d* P, const PT3Params& p) {
-    const unsigned blocks = blocks_for(P->lat[0]);
-    k8_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart);
-    k8_pt_energy_final<<<(unsigned)P->nw, 256, 0, P->ctx->stream>>>(P->d_part, P->d_ipart, (int)blocks, P->d_E, P->d_M);
-}
-
-// the lattice of the walker now at (ladder, slot) (synchronises)
-int pt_at(tsu_pt3d* P, int ladder, int slot, const char* what, tsu_ising3d** out) {
-    tsu_ctx* ctx = P->ctx;
-    TSU_REQUIRE(ctx, ladder >= 0 && ladder < P->nl && slot >= 0 && slot < P->R,
-                "%s: ladder %d, slot %d out of range (%d ladder(s) of %d temperatures)", what, ladder, slot, P->nl, P->R);
-    int32_t w = -1;
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(&w, P->d_was + (size_t)ladder * P->R + slot, sizeof(w), hipMemcpyDeviceToHost, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (w < 0 || w >= P->R) return tsu_fail(ctx, TSU_E_HIP, "%s: corrupt slot table (walker %d)", what, (int)w);
-    *out = P->lat[ladder * P->R + w];
-    return TSU_OK;
+// k8_pt_energy into d_part / d_ipart (asynchronous): the partial pass pt_host.h's energies take
+auto pt_partials(tsu_pt3d* P, const PT3Params& p) {
+    return [P, &p](unsigned blocks) { k8_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
 }
 
 }  // namespace
@@ -900,7 +718,7 @@ int tsu_ising3d_energy(tsu_ising3d* L, double* E) {
     const unsigned blocks = blocks_for(L);
     const K8Params p = make_params(L);
     k8_energy<<<blocks, 256, 0, ctx->stream>>>(p, L->d_part);
-    k8_energy_final<<<1, 256, 0, ctx->stream>>>(L->d_part, (int)blocks, L->d_part + kEnergyBlocks);
+    energy_final<<<1, 256, 0, ctx->stream>>>(L->d_part, (int)blocks, L->d_part + kEnergyBlocks);
     TSU_HIP_TRY(ctx, hipGetLastError());
     double e = 0.0;
     TSU_HIP_TRY(ctx, hipMemcpyAsync(&e, L->d_part + kEnergyBlocks, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -943,65 +761,16 @@ int tsu_ising3d_launch_count(tsu_ising3d* L, uint64_t* n) {
 int tsu_pt3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_mask, int n_temps, int n_ladders, tsu_pt3d** out) {
     TSU_ENTER(ctx);
     if (!ctx || !out) return TSU_E_INVALID;
-    *out = nullptr;
-    TSU_REQUIRE(ctx, n_temps >= 2 && n_temps <= kPtMaxTemps, "pt3d_create: n_temps must be in [2, %d], got %d", kPtMaxTemps, n_temps);
-    TSU_REQUIRE(ctx, n_ladders == 1 || n_ladders == 2, "pt3d_create: n_ladders must be 1 or 2, got %d", n_ladders);
-    tsu_pt3d* P = new (std::nothrow) tsu_pt3d();
-    if (!P) return tsu_fail(ctx, TSU_E_NOMEM, "pt3d_create: host allocation failed");
-    P->ctx = ctx;
-    P->R = n_temps;
-    P->nl = n_ladders;
-    P->nw = n_temps * n_ladders;
-    P->lat = new (std::nothrow) tsu_ising3d*[P->nw]();
-    if (!P->lat) {
-        pt_free(P);
-        return tsu_fail(ctx, TSU_E_NOMEM, "pt3d_create: host allocation failed");
-    }
-    for (int g = 0; g < P->nw; ++g) {  // the shape checks and messages of tsu_ising3d_create
-        const int rc = tsu_ising3d_create(ctx, depth, rows, cols, periodic_mask, &P->lat[g]);
-        if (rc != TSU_OK) {  // the walkers made so far go too: a ladder that does not fit leaves nothing behind
-            pt_free(P);
-            (void)hipGetLastError();
-            return rc;
-        }
-    }
-    const size_t nw = (size_t)P->nw, nlR = (size_t)P->nl * P->R, R = (size_t)P->R;
-    hipError_t e = hipSuccess;
-    auto alloc = [&e](auto*& ptr, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc((void**)&ptr, bytes);
-    };
-    alloc(P->d_s, nw * sizeof(int8_t*));
-    alloc(P->d_key, 2 * nw * sizeof(uint32_t));
-    alloc(P->d_slot, nlR * sizeof(int32_t));
-    alloc(P->d_was, nlR * sizeof(int32_t));
-    alloc(P->d_flag, nlR * sizeof(int32_t));
-    alloc(P->d_T, R * sizeof(double));
-    alloc(P->d_c32, R * sizeof(float));
-    alloc(P->d_att, (size_t)P->nl * (R - 1) * sizeof(long long));
-    alloc(P->d_acc, (size_t)P->nl * (R - 1) * sizeof(long long));
-    alloc(P->d_trips, nlR * sizeof(long long));
-    alloc(P->d_part, nw * kEnergyBlocks * sizeof(double));
-    alloc(P->d_ipart, nw * kEnergyBlocks * sizeof(long long));
-    alloc(P->d_E, nw * sizeof(double));
-    alloc(P->d_M, nw * sizeof(long long));
-    std::vector<int8_t*> planes(nw);
-    for (size_t g = 0; g < nw; ++g) planes[g] = P->lat[g]->s;
-    if (e == hipSuccess) e = hipMemcpyAsync(P->d_s, planes.data(), nw * sizeof(int8_t*), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(P->d_key, 0, 2 * nw * sizeof(uint32_t), ctx->stream);
-    if (e != hipSuccess) {
-        const int rc = tsu_fail(ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP, "pt3d_create: %s", hipGetErrorString(e));
-        (void)hipStreamSynchronize(ctx->stream);
-        pt_free(P);
-        (void)hipGetLastError();
-        return rc;
-    }
-    const int rc = pt_reset(P);  // synchronises before `planes` goes
-    if (rc != TSU_OK) {
-        pt_free(P);
-        return rc;
-    }
-    *out = P;
-    return TSU_OK;
+    return pt_create(
+        ctx, "pt3d", n_temps, n_ladders, out,
+        [=](tsu_ising3d** L) { return tsu_ising3d_create(ctx, depth, rows, cols, periodic_mask, L); },
+        [](tsu_pt3d* P, int8_t** planes) {
+            P->nrows = (long long)P->lat[0]->depth * P->lat[0]->rows;
+            P->pitch = (long long)P->lat[0]->pitch;
+            P->cols = P->lat[0]->cols;
+            for (int g = 0; g < P->nw; ++g) planes[g] = P->lat[g]->s;
+        },
+        pt_free);
 }
 
 int tsu_pt3d_destroy(tsu_pt3d* P) {
@@ -1020,44 +789,18 @@ int tsu_pt3d_set_disorder(tsu_pt3d* P, const float* J_right, const float* J_down
 
 int tsu_pt3d_set_temperatures(tsu_pt3d* P, const double* T) {
     TSU_ENTER(P ? P->ctx : nullptr);
-    if (!P) return TSU_E_INVALID;
-    tsu_ctx* ctx = P->ctx;
-    TSU_REQUIRE(ctx, T, "pt3d_set_temperatures: NULL temperatures");
-    double t[kPtMaxTemps];
-    float c[kPtMaxTemps];
-    for (int i = 0; i < P->R; ++i) {
-        TSU_REQUIRE(ctx, T[i] > 0.0 && std::isfinite(T[i]), "Temperature must be positive (pt3d_set_temperatures: T[%d] = %g)", i, T[i]);
-        t[i] = T[i];
-        c[i] = (float)(2.0 / T[i]);
-    }
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_T, t, P->R * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_c32, c, P->R * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    P->have_T = 1;
-    return TSU_OK;
+    return P ? pt_set_temperatures(P, T) : TSU_E_INVALID;
 }
 
 int tsu_pt3d_init(tsu_pt3d* P, uint64_t seed, int initial) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
-    tsu_ctx* ctx = P->ctx;
-    TSU_REQUIRE(ctx, initial == 0 || initial == 1 || initial == -1, "pt3d_init: initial must be 0 (random), 1 (up) or -1 (down), got %d",
-                initial);
-    std::vector<uint32_t> key(2 * (size_t)P->nw);
-    for (int g = 0; g < P->nw; ++g) {
-        const uint64_t s = seed + (uint64_t)g;  // temperature_scan_3d's model g
-        key[2 * g] = (uint32_t)s;
-        key[2 * g + 1] = (uint32_t)(s >> 32);
-        const int rc = initial == 0 ? tsu_ising3d_randomize(P->lat[g], s, 0) : tsu_ising3d_fill(P->lat[g], (int8_t)initial);
-        if (rc != TSU_OK) return rc;
-    }
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_key, key.data(), key.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    const int rc = pt_reset(P);  // synchronises before `key` goes
-    if (rc != TSU_OK) return rc;
-    P->key0 = (uint32_t)seed;
-    P->key1 = (uint32_t)(seed >> 32);
-    P->have_init = 1;
-    return TSU_OK;
+    return pt_init(
+        P, seed, initial,
+        [=](int g, uint64_t s) {  // temperature_scan_3d's model g
+            return initial == 0 ? tsu_ising3d_randomize(P->lat[g], s, 0) : tsu_ising3d_fill(P->lat[g], (int8_t)initial);
+        },
+        [] { return (int)TSU_OK; });
 }
 
 int tsu_pt3d_run(tsu_pt3d* P, int n_rounds, int swap_interval, int do_swap, int record) {
@@ -1065,148 +808,60 @@ int tsu_pt3d_run(tsu_pt3d* P, int n_rounds, int swap_interval, int do_swap, int 
     if (!P) return TSU_E_INVALID;
     tsu_ctx* ctx = P->ctx;
     tsu_ising3d* L = P->lat[0];
-    TSU_REQUIRE(ctx, L->have_disorder, "pt3d_run: call tsu_pt3d_set_disorder first");
-    TSU_REQUIRE(ctx, P->have_T, "pt3d_run: call tsu_pt3d_set_temperatures first");
-    TSU_REQUIRE(ctx, P->have_init, "pt3d_run: call tsu_pt3d_init first");
-    TSU_REQUIRE(ctx, n_rounds >= 0 && swap_interval >= 1, "pt3d_run: need n_rounds >= 0 and swap_interval >= 1 (got %d, %d)", n_rounds,
-                swap_interval);
-    TSU_REQUIRE(ctx, (uint64_t)P->sweeps + (uint64_t)n_rounds * (uint64_t)swap_interval <= (1ull << 31), "pt3d_run: sweep counter overflow");
-    TSU_REQUIRE(ctx, (uint64_t)P->rounds + (uint64_t)n_rounds <= 0xFFFFFFFFull, "pt3d_run: round counter overflow");
-    const int R = P->R, nl = P->nl;
-    if (record && P->hist_cap < (size_t)n_rounds) {
-        pt_free_history(P);
-        const size_t n = (size_t)n_rounds * nl * R;
-        hipError_t e = hipMalloc((void**)&P->d_hE, n * sizeof(double));
-        if (e == hipSuccess) e = hipMalloc((void**)&P->d_hM, n * sizeof(long long));
-        if (e == hipSuccess) e = hipMalloc((void**)&P->d_hW, n * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&P->d_hq, (size_t)n_rounds * R * sizeof(long long));
-        if (e != hipSuccess) {  // nothing of a history that does not fit stays behind
-            pt_free_history(P);
-            P->hist_rounds = 0;
-            (void)hipGetLastError();
-            return tsu_fail(ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP, "pt3d_run: history of %d rounds: %s", n_rounds,
-                            hipGetErrorString(e));
-        }
-        P->hist_cap = (size_t)n_rounds;
-    }
-    // k8_pt_overlap adds into its row: every q row of this run starts at 0
-    if (record && nl == 2 && n_rounds > 0)
-        TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hq, 0, (size_t)n_rounds * R * sizeof(long long), ctx->stream));
-    P->hist_rounds = record ? n_rounds : 0;
+    const int rc = pt_run_check(P, L->have_disorder, n_rounds, swap_interval);
+    if (rc != TSU_OK) return rc;
     PT3Params p = pt_params(P);
     p.W = pt_group(P);
     const dim3 og = octet_grid(make_params(L));
     const dim3 grid(og.x, og.y, (unsigned)((P->nw + p.W - 1) / p.W));
-    PTSwap sw;
-    sw.E = P->d_E;
-    sw.M = P->d_M;
-    sw.T = P->d_T;
-    sw.was = P->d_was;
-    sw.slot = P->d_slot;
-    sw.flag = P->d_flag;
-    sw.att = P->d_att;
-    sw.acc = P->d_acc;
-    sw.trips = P->d_trips;
-    sw.R = R;
-    sw.do_swap = do_swap ? 1 : 0;
-    sw.k0 = P->key0;
-    sw.k1 = P->key1;
-    for (int t = 0; t < n_rounds; ++t) {
-        for (int s = 0; s < swap_interval; ++s)
-            for (int colour = 0; colour < 2; ++colour) {
-                p.hs = 2u * (P->sweeps + (uint32_t)s) + (uint32_t)colour;
-                k8_pt_sweep<<<grid, 256, 0, ctx->stream>>>(p, colour);
-                P->launches += 1;
-            }
-        P->sweeps += (uint32_t)swap_interval;
-        if (do_swap || record) {
-            pt_enqueue_energies(P, p);
-            const size_t row = (size_t)t * nl * R;
-            sw.hE = record ? P->d_hE + row : nullptr;
-            sw.hM = record ? P->d_hM + row : nullptr;
-            sw.hW = record ? P->d_hW + row : nullptr;
-            sw.t = P->rounds;
-            k7_pt_swap<<<(unsigned)nl, 64, 0, ctx->stream>>>(sw);  // the 2-D ladders' pass, unchanged (pt_dev.h)
-            if (record && nl == 2)
-                k8_pt_overlap<<<dim3(blocks_for(L), (unsigned)R, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, (long long)L->pitch,
-                                                                                           (long long)L->depth * L->rows, L->cols,
-                                                                                           P->d_hq + (size_t)t * R);
-        }
-        P->rounds += 1;
-    }
-    TSU_HIP_TRY(ctx, hipGetLastError());
-    return TSU_OK;
+    return pt_run(
+        P, n_rounds, swap_interval, do_swap, record,
+        [&](uint32_t hs, int colour) {
+            p.hs = hs;
+            k8_pt_sweep<<<grid, 256, 0, ctx->stream>>>(p, colour);
+        },
+        pt_partials(P, p), [] { return (int)TSU_OK; });
 }
 
 int tsu_pt3d_history(tsu_pt3d* P, double* E, int64_t* M, int64_t* q, int32_t* walker) {
     TSU_ENTER(P ? P->ctx : nullptr);
-    if (!P) return TSU_E_INVALID;
-    tsu_ctx* ctx = P->ctx;
-    const size_t n = (size_t)P->hist_rounds * P->nl * P->R;
-    if (n) {
-        if (E) TSU_HIP_TRY(ctx, hipMemcpyAsync(E, P->d_hE, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        if (M) TSU_HIP_TRY(ctx, hipMemcpyAsync(M, P->d_hM, n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (walker) TSU_HIP_TRY(ctx, hipMemcpyAsync(walker, P->d_hW, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (q && P->nl == 2)
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(q, P->d_hq, (size_t)P->hist_rounds * P->R * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    }
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TSU_OK;
+    return P ? pt_history(P, E, M, q, walker) : TSU_E_INVALID;
 }
 
 int tsu_pt3d_stats(tsu_pt3d* P, int64_t* attempts, int64_t* accepts, int64_t* round_trips, int32_t* walker_at_slot, uint64_t* sweep_count,
                    uint64_t* round_count) {
     TSU_ENTER(P ? P->ctx : nullptr);
-    if (!P) return TSU_E_INVALID;
-    tsu_ctx* ctx = P->ctx;
-    const size_t pairs = (size_t)P->nl * (P->R - 1), nlR = (size_t)P->nl * P->R;
-    if (attempts) TSU_HIP_TRY(ctx, hipMemcpyAsync(attempts, P->d_att, pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (accepts) TSU_HIP_TRY(ctx, hipMemcpyAsync(accepts, P->d_acc, pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (round_trips) TSU_HIP_TRY(ctx, hipMemcpyAsync(round_trips, P->d_trips, nlR * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (walker_at_slot)
-        TSU_HIP_TRY(ctx, hipMemcpyAsync(walker_at_slot, P->d_was, nlR * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (sweep_count) *sweep_count = P->sweeps;
-    if (round_count) *round_count = P->rounds;
-    return TSU_OK;
+    return P ? pt_stats(P, attempts, accepts, round_trips, walker_at_slot, sweep_count, round_count) : TSU_E_INVALID;
 }
 
 int tsu_pt3d_energies(tsu_pt3d* P, double* E, int64_t* sum_s) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
-    tsu_ctx* ctx = P->ctx;
-    TSU_REQUIRE(ctx, P->lat[0]->have_disorder, "pt3d_energies: call tsu_pt3d_set_disorder first");
-    pt_enqueue_energies(P, pt_params(P));
-    TSU_HIP_TRY(ctx, hipGetLastError());
-    if (E) TSU_HIP_TRY(ctx, hipMemcpyAsync(E, P->d_E, (size_t)P->nw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (sum_s) TSU_HIP_TRY(ctx, hipMemcpyAsync(sum_s, P->d_M, (size_t)P->nw * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return TSU_OK;
+    const PT3Params p = pt_params(P);
+    return pt_energies(P, P->lat[0]->have_disorder, E, sum_s, pt_partials(P, p));
 }
 
 int tsu_pt3d_get_spins(tsu_pt3d* P, int ladder, int slot, int8_t* host) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
     TSU_REQUIRE(P->ctx, host, "pt3d_get_spins: NULL output");
-    tsu_ising3d* L = nullptr;
-    const int rc = pt_at(P, ladder, slot, "pt3d_get_spins", &L);
-    return rc != TSU_OK ? rc : tsu_ising3d_get_spins(L, host);
+    int g = 0;
+    const int rc = pt_at(P, ladder, slot, "get_spins", &g);
+    return rc != TSU_OK ? rc : tsu_ising3d_get_spins(P->lat[g], host);
 }
 
 int tsu_pt3d_set_spins(tsu_pt3d* P, int ladder, int slot, const int8_t* host) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
     TSU_REQUIRE(P->ctx, host, "pt3d_set_spins: NULL input");
-    tsu_ising3d* L = nullptr;
-    const int rc = pt_at(P, ladder, slot, "pt3d_set_spins", &L);
-    return rc != TSU_OK ? rc : tsu_ising3d_set_spins(L, host);
+    int g = 0;
+    const int rc = pt_at(P, ladder, slot, "set_spins", &g);
+    return rc != TSU_OK ? rc : tsu_ising3d_set_spins(P->lat[g], host);
 }
 
 int tsu_pt3d_launch_count(tsu_pt3d* P, uint64_t* n) {
     TSU_ENTER(P ? P->ctx : nullptr);
-    if (!P || !n) return TSU_E_INVALID;
-    *n = P->launches;
-    return TSU_OK;
+    return pt_launch_count(P, n);
 }
 
 }  // extern "C"

@@ -1,0 +1,39 @@
+// pt_ladder.h -- what the 2-D and the 3-D parallel-tempering handles (tsu_pt2d, tsu_pt3d) have in common, as a plain struct both
+// derive from: the tables, counters and history buffers of the ladders and the shape the dimension-blind kernels see (pt_dev.h,
+// reduce_dev.h).  The functions on it are pt_host.h's; a unit that only reads the handle (ising2d_icm.hip) includes this alone.
+#pragma once
+#include "pt_dev.h"  // kPtMaxTemps
+
+// n_ladders ladders of R walkers (whole lattices) on ONE disorder
+struct pt_ladder {
+    tsu_ctx* ctx;
+    const char* name;              // "pt2d" / "pt3d": the prefix of the messages
+    int R, nl, nw;                 // temperatures, ladders, walkers (R * nl)
+    int have_T, have_init;
+    uint32_t sweeps, rounds;       // sweeps of every walker and rounds since init
+    unsigned long long launches;   // half-sweep launches
+    int hist_rounds;               // rows recorded by the last run
+    size_t hist_cap;               // rows the history buffers hold
+    long long nrows, pitch;        // a walker's spin plane: nrows rows (2-D: rows, 3-D: depth * rows) of pitch bytes,
+    int cols;                      // the first cols of each counting
+    int8_t** d_s;                  // walker g = ladder * R + w -> its spin plane
+    uint32_t* d_key;               // walker -> (k0, k1)
+    int32_t* d_slot;               // [ladder][walker] -> slot
+    int32_t* d_was;                // [ladder][slot] -> walker
+    int32_t* d_flag;               // [ladder][walker] -> round-trip flag
+    double* d_T;                   // slot -> T
+    float* d_c32;                  // slot -> fl32(2 / T)
+    long long* d_att;              // [ladder][pair]
+    long long* d_acc;
+    long long* d_trips;            // [ladder][walker]
+    double* d_part;                // [walker][kEnergyBlocks] energy partials
+    long long* d_ipart;            // [walker][kEnergyBlocks] sum-of-spin partials
+    double* d_E;                   // walker -> E of the last energy pass
+    long long* d_M;                // walker -> sum of spins
+    double* d_hE;                  // [round][ladder][slot]
+    long long* d_hM;
+    int32_t* d_hW;
+    long long* d_hq;               // [round][slot] (two ladders)
+    uint32_t key0, key1;           // Philox key of the swap uniforms (the seed)
+    double h_T[kPtMaxTemps];       // host copy of d_T
+};

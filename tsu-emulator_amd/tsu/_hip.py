@@ -528,51 +528,49 @@ class Lattice3D:
         return n.value
 
 
-class TemperingLattice:
-    """tsu_pt2d handle (K7 parallel tempering): n_ladders ladders of n_temps walkers of one rows x cols lattice sharing one
-    disorder.  Walker w of ladder k has Philox key seed + k n_temps + w and starts at slot w."""
+class _TemperingHandle:
+    """What the tsu_pt2d and tsu_pt3d handles share: every call but create, set_disorder and the 2-D cluster moves.  A subclass
+    sets ``_prefix`` (the C symbols' prefix) and, in its constructor, ``shape``, ``n_temps`` and ``n_ladders``, then calls
+    ``_create`` with the shape arguments of its create function."""
 
-    def __init__(self, rows, cols, periodic, n_temps, n_ladders=1, ctx=None):
-        self.ctx = ctx or Context.default()
-        self.lib = self.ctx.lib
-        self.rows, self.cols, self.periodic = int(rows), int(cols), bool(periodic)
-        self.n_temps, self.n_ladders = int(n_temps), int(n_ladders)
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def _create(self, *shape_args):
         self._recorded = 0
         h = _vp()
-        self.ctx.check(self.lib.tsu_pt2d_create(self.ctx.h, self.rows, self.cols, int(self.periodic), self.n_temps,
-                                                self.n_ladders, C.byref(h)))
+        self.ctx.check(self._fn("create")(self.ctx.h, *shape_args, self.n_temps, self.n_ladders, C.byref(h)))
         self.h = h
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.tsu_pt2d_destroy(self.h)
+            self._fn("destroy")(self.h)
             self.h = None
 
     def __del__(self, _finalizing=sys.is_finalizing):
         if not _finalizing():
             self.close()
 
-    def set_disorder(self, J_right, J_down, h=None):
-        shape = (self.rows, self.cols)
-        jr = np.ascontiguousarray(J_right, dtype=np.float32).reshape(shape)
-        jd = np.ascontiguousarray(J_down, dtype=np.float32).reshape(shape)
-        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float32).reshape(shape)
-        self.ctx.check(self.lib.tsu_pt2d_set_disorder(self.h, _ptr(jr, _f32p), _ptr(jd, _f32p),
-                                                      None if hh is None else _ptr(hh, _f32p)))
+    def _set_disorder(self, arrays, h):
+        a = [np.ascontiguousarray(x, dtype=np.float32).reshape(self.shape) for x in arrays]
+        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float32).reshape(self.shape)
+        self.ctx.check(self._fn("set_disorder")(self.h, *[_ptr(x, _f32p) for x in a], None if hh is None else _ptr(hh, _f32p)))
 
     def set_temperatures(self, T):
         t = np.ascontiguousarray(T, dtype=np.float64).ravel()
         if t.size != self.n_temps:
             raise ValueError(f"need {self.n_temps} temperatures, got {t.size}")
-        self.ctx.check(self.lib.tsu_pt2d_set_temperatures(self.h, _ptr(t, _f64p)))
+        self.ctx.check(self._fn("set_temperatures")(self.h, _ptr(t, _f64p)))
 
     def init(self, seed, initial=0):
-        """initial 0: random (tsu_ising2d_randomize(seed + walker index)); +1 / -1: all up / down."""
-        self.ctx.check(self.lib.tsu_pt2d_init(self.h, int(seed), int(initial)))
+        """initial 0: random (the lattice's randomize(seed + walker index)); +1 / -1: all up / down."""
+        self.ctx.check(self._fn("init")(self.h, int(seed), int(initial)))
         self._recorded = 0
 
     def run(self, n_rounds, swap_interval, swap=True, record=True):
-        self.ctx.check(self.lib.tsu_pt2d_run(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record))))
+        self.ctx.check(self._fn("run")(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record))))
         self._recorded = int(n_rounds) if record else 0
 
     def history(self):
@@ -582,8 +580,8 @@ class TemperingLattice:
         M = np.zeros((n, nl, R), np.int64)
         W = np.zeros((n, nl, R), np.int32)
         q = np.zeros((n, R), np.int64) if nl == 2 else None
-        self.ctx.check(self.lib.tsu_pt2d_history(self.h, _ptr(E, _f64p), _ptr(M, _i64p), None if q is None else _ptr(q, _i64p),
-                                                 _ptr(W, _i32p)))
+        self.ctx.check(self._fn("history")(self.h, _ptr(E, _f64p), _ptr(M, _i64p), None if q is None else _ptr(q, _i64p),
+                                           _ptr(W, _i32p)))
         return {"E": E, "M": M, "walker": W, "q": q}
 
     def stats(self):
@@ -591,8 +589,8 @@ class TemperingLattice:
         att, acc = np.zeros((nl, R - 1), np.int64), np.zeros((nl, R - 1), np.int64)
         trips, was = np.zeros((nl, R), np.int64), np.zeros((nl, R), np.int32)
         sw, rd = C.c_uint64(0), C.c_uint64(0)
-        self.ctx.check(self.lib.tsu_pt2d_stats(self.h, _ptr(att, _i64p), _ptr(acc, _i64p), _ptr(trips, _i64p), _ptr(was, _i32p),
-                                               C.byref(sw), C.byref(rd)))
+        self.ctx.check(self._fn("stats")(self.h, _ptr(att, _i64p), _ptr(acc, _i64p), _ptr(trips, _i64p), _ptr(was, _i32p),
+                                         C.byref(sw), C.byref(rd)))
         return {"attempts": att, "accepts": acc, "round_trips": trips, "walker_at_slot": was, "sweep_count": sw.value,
                 "round_count": rd.value}
 
@@ -600,22 +598,40 @@ class TemperingLattice:
         """(E, sum of spins) of every walker now, as (n_ladders, n_temps) arrays indexed by walker."""
         E = np.zeros((self.n_ladders, self.n_temps))
         M = np.zeros((self.n_ladders, self.n_temps), np.int64)
-        self.ctx.check(self.lib.tsu_pt2d_energies(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
+        self.ctx.check(self._fn("energies")(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
         return E, M
 
     def get_spins(self, ladder, slot):
-        out = np.empty((self.rows, self.cols), dtype=np.int8)
-        self.ctx.check(self.lib.tsu_pt2d_get_spins(self.h, int(ladder), int(slot), _ptr(out, _i8p)))
+        out = np.empty(self.shape, dtype=np.int8)
+        self.ctx.check(self._fn("get_spins")(self.h, int(ladder), int(slot), _ptr(out, _i8p)))
         return out
 
     def set_spins(self, ladder, slot, spins):
-        s = np.ascontiguousarray(spins, dtype=np.int8).reshape(self.rows, self.cols)
-        self.ctx.check(self.lib.tsu_pt2d_set_spins(self.h, int(ladder), int(slot), _ptr(s, _i8p)))
+        s = np.ascontiguousarray(spins, dtype=np.int8).reshape(self.shape)
+        self.ctx.check(self._fn("set_spins")(self.h, int(ladder), int(slot), _ptr(s, _i8p)))
 
     def launch_count(self):
         n = C.c_uint64(0)
-        self.ctx.check(self.lib.tsu_pt2d_launch_count(self.h, C.byref(n)))
+        self.ctx.check(self._fn("launch_count")(self.h, C.byref(n)))
         return n.value
+
+
+class TemperingLattice(_TemperingHandle):
+    """tsu_pt2d handle (K7 parallel tempering): n_ladders ladders of n_temps walkers of one rows x cols lattice sharing one
+    disorder.  Walker w of ladder k has Philox key seed + k n_temps + w and starts at slot w."""
+
+    _prefix = "tsu_pt2d_"
+
+    def __init__(self, rows, cols, periodic, n_temps, n_ladders=1, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.rows, self.cols, self.periodic = int(rows), int(cols), bool(periodic)
+        self.shape = (self.rows, self.cols)
+        self.n_temps, self.n_ladders = int(n_temps), int(n_ladders)
+        self._create(self.rows, self.cols, int(self.periodic))
+
+    def set_disorder(self, J_right, J_down, h=None):
+        self._set_disorder((J_right, J_down), h)
 
     def set_cluster_moves(self, every, t_max=float("inf")):
         """Replica cluster moves between the two ladders: a pass after the sweeps of every round t with t % every == 0 over the
@@ -635,10 +651,12 @@ class TemperingLattice:
         return {"passes": passes, "clusters": clusters, "flipped": flipped, "pass_count": m.value, "launches": nl.value}
 
 
-class TemperingLattice3D:
+class TemperingLattice3D(_TemperingHandle):
     """tsu_pt3d handle (K8 parallel tempering): n_ladders ladders of n_temps walkers of one depth x rows x cols lattice sharing one
     disorder.  Walker w of ladder k has Philox key seed + k n_temps + w and starts at slot w.  ``periodic``: a bool or a triple
     (p_z, p_r, p_c)."""
+
+    _prefix = "tsu_pt3d_"
 
     def __init__(self, depth, rows, cols, periodic, n_temps, n_ladders=1, ctx=None):
         self.ctx = ctx or Context.default()
@@ -647,84 +665,10 @@ class TemperingLattice3D:
         self.shape = (self.depth, self.rows, self.cols)
         self.periodic = periodic_axes(periodic)
         self.n_temps, self.n_ladders = int(n_temps), int(n_ladders)
-        self._recorded = 0
-        mask = sum(1 << a for a in range(3) if self.periodic[a])
-        h = _vp()
-        self.ctx.check(self.lib.tsu_pt3d_create(self.ctx.h, self.depth, self.rows, self.cols, mask, self.n_temps, self.n_ladders,
-                                                C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.tsu_pt3d_destroy(self.h)
-            self.h = None
-
-    def __del__(self, _finalizing=sys.is_finalizing):
-        if not _finalizing():
-            self.close()
+        self._create(self.depth, self.rows, self.cols, sum(1 << a for a in range(3) if self.periodic[a]))
 
     def set_disorder(self, J_right, J_down, J_layer, h=None):
-        jr, jd, jl = (np.ascontiguousarray(a, dtype=np.float32).reshape(self.shape) for a in (J_right, J_down, J_layer))
-        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float32).reshape(self.shape)
-        self.ctx.check(self.lib.tsu_pt3d_set_disorder(self.h, _ptr(jr, _f32p), _ptr(jd, _f32p), _ptr(jl, _f32p),
-                                                      None if hh is None else _ptr(hh, _f32p)))
-
-    def set_temperatures(self, T):
-        t = np.ascontiguousarray(T, dtype=np.float64).ravel()
-        if t.size != self.n_temps:
-            raise ValueError(f"need {self.n_temps} temperatures, got {t.size}")
-        self.ctx.check(self.lib.tsu_pt3d_set_temperatures(self.h, _ptr(t, _f64p)))
-
-    def init(self, seed, initial=0):
-        """initial 0: random (tsu_ising3d_randomize(seed + walker index)); +1 / -1: all up / down."""
-        self.ctx.check(self.lib.tsu_pt3d_init(self.h, int(seed), int(initial)))
-        self._recorded = 0
-
-    def run(self, n_rounds, swap_interval, swap=True, record=True):
-        self.ctx.check(self.lib.tsu_pt3d_run(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record))))
-        self._recorded = int(n_rounds) if record else 0
-
-    def history(self):
-        """The last run's rows: E, M (sum of spins), walker as (n_rounds, n_ladders, n_temps); q as (n_rounds, n_temps) or None."""
-        n, nl, R = self._recorded, self.n_ladders, self.n_temps
-        E = np.zeros((n, nl, R))
-        M = np.zeros((n, nl, R), np.int64)
-        W = np.zeros((n, nl, R), np.int32)
-        q = np.zeros((n, R), np.int64) if nl == 2 else None
-        self.ctx.check(self.lib.tsu_pt3d_history(self.h, _ptr(E, _f64p), _ptr(M, _i64p), None if q is None else _ptr(q, _i64p),
-                                                 _ptr(W, _i32p)))
-        return {"E": E, "M": M, "walker": W, "q": q}
-
-    def stats(self):
-        nl, R = self.n_ladders, self.n_temps
-        att, acc = np.zeros((nl, R - 1), np.int64), np.zeros((nl, R - 1), np.int64)
-        trips, was = np.zeros((nl, R), np.int64), np.zeros((nl, R), np.int32)
-        sw, rd = C.c_uint64(0), C.c_uint64(0)
-        self.ctx.check(self.lib.tsu_pt3d_stats(self.h, _ptr(att, _i64p), _ptr(acc, _i64p), _ptr(trips, _i64p), _ptr(was, _i32p),
-                                               C.byref(sw), C.byref(rd)))
-        return {"attempts": att, "accepts": acc, "round_trips": trips, "walker_at_slot": was, "sweep_count": sw.value,
-                "round_count": rd.value}
-
-    def energies(self):
-        """(E, sum of spins) of every walker now, as (n_ladders, n_temps) arrays indexed by walker."""
-        E = np.zeros((self.n_ladders, self.n_temps))
-        M = np.zeros((self.n_ladders, self.n_temps), np.int64)
-        self.ctx.check(self.lib.tsu_pt3d_energies(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
-        return E, M
-
-    def get_spins(self, ladder, slot):
-        out = np.empty(self.shape, dtype=np.int8)
-        self.ctx.check(self.lib.tsu_pt3d_get_spins(self.h, int(ladder), int(slot), _ptr(out, _i8p)))
-        return out
-
-    def set_spins(self, ladder, slot, spins):
-        s = np.ascontiguousarray(spins, dtype=np.int8).reshape(self.shape)
-        self.ctx.check(self.lib.tsu_pt3d_set_spins(self.h, int(ladder), int(slot), _ptr(s, _i8p)))
-
-    def launch_count(self):
-        n = C.c_uint64(0)
-        self.ctx.check(self.lib.tsu_pt3d_launch_count(self.h, C.byref(n)))
-        return n.value
+        self._set_disorder((J_right, J_down, J_layer), h)
 
 
 def sweep_batch(lattices, n_sweeps, seeds, sweep0s, replicas=None):

@@ -954,7 +954,112 @@ def _cluster_move_args(cluster_moves, cluster_max_temperature, ladders: int):
     return int(cluster_moves), t_max
 
 
-class LatticeTempering:
+class _LatticeTempering:
+    """What :class:`LatticeTempering` and :class:`LatticeTempering3D` share: everything but the shape, the disorder and the 2-D
+    cluster moves.  A subclass parses its shape, calls ``_check_ladder``, validates its disorder into ``self._disorder`` and hands
+    its new handle to ``_start``."""
+
+    def _check_ladder(self, temperatures, ladders, initial):
+        T = np.asarray(temperatures, dtype=float).ravel()
+        if not 2 <= T.size <= 256:
+            raise ValueError(f"parallel tempering needs 2 to 256 temperatures, got {T.size}")
+        if not np.all(np.isfinite(T) & (T > 0)):
+            raise ValueError("Temperature must be positive")
+        if ladders not in (1, 2):
+            raise ValueError("ladders must be 1 or 2")
+        if initial not in _PT_INITIAL:
+            raise ValueError("initial must be 'random', 'up' or 'down'")
+        self.temperatures = T
+        self.ladders = int(ladders)
+
+    def _start(self, pt, seed, initial):
+        self._pt = pt
+        self.seed = int(seed) if seed is not None else (
+            int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
+        pt.set_disorder(*self._disorder)
+        pt.set_temperatures(self.temperatures)
+        if getattr(self, "cluster_moves", 0):  # 2-D only
+            pt.set_cluster_moves(self.cluster_moves, self.cluster_max_temperature)
+        pt.init(self.seed, _PT_INITIAL[initial])
+
+    def run(self, n_rounds: int, swap_interval: int = 10, swap: bool = True, record: bool = True):
+        """n_rounds rounds of swap_interval sweeps each; with ``record`` returns ``history()`` (ladder 0), else None."""
+        self._pt.run(int(n_rounds), int(swap_interval), swap, record)
+        return self.history() if record else None
+
+    def history(self, ladder: int = 0) -> dict:
+        """The rounds recorded by the last ``run`` as (n_rounds, R) arrays, per slot: ``E`` (float64 energy), ``M`` (int64 sum of
+        spins), ``walker`` (which walker of the ladder sat there) and, with two ladders, ``q`` (int64 overlap of the two ladders'
+        walkers at that slot)."""
+        h = self._pt.history()
+        out = {k: np.ascontiguousarray(h[k][:, ladder]) for k in ("E", "M", "walker")}
+        if h["q"] is not None:
+            out["q"] = h["q"]
+        return out
+
+    @property
+    def acceptance(self) -> np.ndarray:
+        """Accepted / attempted swaps per adjacent pair of slots, ladders pooled (NaN before the first attempt)."""
+        st = self._pt.stats()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return st["accepts"].sum(axis=0) / st["attempts"].sum(axis=0)
+
+    @property
+    def round_trips(self) -> int:
+        """Round trips (slot 0 -> last slot -> slot 0) completed by all walkers of all ladders."""
+        return int(self._pt.stats()["round_trips"].sum())
+
+    @property
+    def walker_at_slot(self) -> np.ndarray:
+        """(ladders, R): which walker sits at each slot."""
+        return self._pt.stats()["walker_at_slot"]
+
+    @property
+    def sweep_count(self) -> int:
+        return int(self._pt.stats()["sweep_count"])
+
+    def _check_slot(self, slot, ladder):
+        if not (0 <= slot < self.temperatures.size and 0 <= ladder < self.ladders):
+            raise ValueError(f"slot {slot} / ladder {ladder} out of range ({self.ladders} ladder(s) of {self.temperatures.size})")
+
+    def spins(self, slot: int, ladder: int = 0) -> np.ndarray:
+        """Spins of the walker now at ``slot``, in the lattice's shape."""
+        self._check_slot(slot, ladder)
+        return self._pt.get_spins(ladder, slot)
+
+    def energy(self, slot: int, ladder: int = 0) -> float:
+        """Energy of the walker now at ``slot`` (the device's fixed-order float64 sum)."""
+        self._check_slot(slot, ladder)
+        E, _ = self._pt.energies()
+        return float(E[ladder, self._pt.stats()["walker_at_slot"][ladder, slot]])
+
+
+def _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap) -> dict:
+    """The body of the tempering scans on a fresh ladder ``pt``, closed at the end: the equilibration rounds, the recorded rounds
+    and temperature_scan's summary of them, plus ``cluster_flipped`` where the ladder makes cluster moves (2-D only)."""
+    try:
+        pt.run(int(n_equilibrate) // int(measure_every), int(measure_every), swap=swap, record=False)
+        pt.run(int(n_measure), int(measure_every), swap=swap, record=True)
+        hist = pt._pt.history()
+        N = pt.n_spins
+        out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
+        out["temperatures"] = temperatures
+        Ms = np.ascontiguousarray(hist["M"][:, 0].T) / N
+        Es = np.ascontiguousarray(hist["E"][:, 0].T)
+        Qs = np.ascontiguousarray(hist["q"].T) / N if pt.ladders == 2 else None
+        out = _scan_summary(out, N, Ms, Es, Qs)
+        out["swap_acceptance"] = pt.acceptance
+        out["round_trips"] = pt.round_trips
+        if getattr(pt, "cluster_moves", 0):
+            st = pt.cluster_stats
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out["cluster_flipped"] = st["flipped"] / (st["passes"] * float(N))
+    finally:
+        pt._pt.close()
+    return out
+
+
+class LatticeTempering(_LatticeTempering):
     """Parallel tempering (replica exchange) of a disordered lattice on the GPU (K7, physical mode).
 
     ``ladders`` (1 or 2) ladders of ``R = len(temperatures)`` walkers (2 ... 256) share one quenched disorder: ``couplings=(J_right,
@@ -980,44 +1085,12 @@ class LatticeTempering:
                  cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None):
         self.rows, self.cols = (size, size) if np.isscalar(size) else tuple(size)
         self.n_spins = self.rows * self.cols
-        T = np.asarray(temperatures, dtype=float).ravel()
-        if not 2 <= T.size <= 256:
-            raise ValueError(f"parallel tempering needs 2 to 256 temperatures, got {T.size}")
-        if not np.all(np.isfinite(T) & (T > 0)):
-            raise ValueError("Temperature must be positive")
-        if ladders not in (1, 2):
-            raise ValueError("ladders must be 1 or 2")
-        if initial not in _PT_INITIAL:
-            raise ValueError("initial must be 'random', 'up' or 'down'")
+        self._check_ladder(temperatures, ladders, initial)
         self.cluster_moves, self.cluster_max_temperature = _cluster_move_args(cluster_moves, cluster_max_temperature, ladders)
         self.periodic = bool(periodic)
         self._disorder = _disorder_arrays(self.rows, self.cols, self.periodic, float(coupling), float(external_field), "physical",
                                           couplings, field)
-        self.temperatures = T
-        self.ladders = int(ladders)
-        self.seed = int(seed) if seed is not None else (
-            int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
-        self._pt = _hip.TemperingLattice(self.rows, self.cols, self.periodic, T.size, self.ladders)
-        self._pt.set_disorder(*self._disorder)
-        self._pt.set_temperatures(T)
-        if self.cluster_moves:
-            self._pt.set_cluster_moves(self.cluster_moves, self.cluster_max_temperature)
-        self._pt.init(self.seed, _PT_INITIAL[initial])
-
-    def run(self, n_rounds: int, swap_interval: int = 10, swap: bool = True, record: bool = True):
-        """n_rounds rounds of swap_interval sweeps each; with ``record`` returns ``history()`` (ladder 0), else None."""
-        self._pt.run(int(n_rounds), int(swap_interval), swap, record)
-        return self.history() if record else None
-
-    def history(self, ladder: int = 0) -> dict:
-        """The rounds recorded by the last ``run`` as (n_rounds, R) arrays, per slot: ``E`` (float64 energy), ``M`` (int64 sum of
-        spins), ``walker`` (which walker of the ladder sat there) and, with two ladders, ``q`` (int64 overlap of the two ladders'
-        walkers at that slot)."""
-        h = self._pt.history()
-        out = {k: np.ascontiguousarray(h[k][:, ladder]) for k in ("E", "M", "walker")}
-        if h["q"] is not None:
-            out["q"] = h["q"]
-        return out
+        self._start(_hip.TemperingLattice(self.rows, self.cols, self.periodic, self.temperatures.size, self.ladders), seed, initial)
 
     def cluster_move(self) -> None:
         """One replica cluster pass now over the participating slots (needs ``cluster_moves >= 1``)."""
@@ -1028,42 +1101,6 @@ class LatticeTempering:
         """Per slot since the start: ``passes`` taken, ``clusters`` found and sites ``flipped`` (per replica) by the cluster moves."""
         st = self._pt.cluster_stats()
         return {k: st[k] for k in ("passes", "clusters", "flipped")}
-
-    @property
-    def acceptance(self) -> np.ndarray:
-        """Accepted / attempted swaps per adjacent pair of slots, ladders pooled (NaN before the first attempt)."""
-        st = self._pt.stats()
-        with np.errstate(divide="ignore", invalid="ignore"):
-            return st["accepts"].sum(axis=0) / st["attempts"].sum(axis=0)
-
-    @property
-    def round_trips(self) -> int:
-        """Round trips (slot 0 -> last slot -> slot 0) completed by all walkers of all ladders."""
-        return int(self._pt.stats()["round_trips"].sum())
-
-    @property
-    def walker_at_slot(self) -> np.ndarray:
-        """(ladders, R): which walker sits at each slot."""
-        return self._pt.stats()["walker_at_slot"]
-
-    @property
-    def sweep_count(self) -> int:
-        return int(self._pt.stats()["sweep_count"])
-
-    def _check_slot(self, slot, ladder):
-        if not (0 <= slot < self.temperatures.size and 0 <= ladder < self.ladders):
-            raise ValueError(f"slot {slot} / ladder {ladder} out of range ({self.ladders} ladder(s) of {self.temperatures.size})")
-
-    def spins(self, slot: int, ladder: int = 0) -> np.ndarray:
-        """Spins of the walker now at ``slot``."""
-        self._check_slot(slot, ladder)
-        return self._pt.get_spins(ladder, slot)
-
-    def energy(self, slot: int, ladder: int = 0) -> float:
-        """Energy of the walker now at ``slot`` (the device's fixed-order float64 sum)."""
-        self._check_slot(slot, ladder)
-        E, _ = self._pt.energies()
-        return float(E[ladder, self._pt.stats()["walker_at_slot"][ladder, slot]])
 
 
 def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
@@ -1089,26 +1126,7 @@ def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int
     temperatures = np.asarray(temperatures, dtype=float)
     pt = LatticeTempering((rows, cols), temperatures, couplings=(jr, jd), field=h, periodic=periodic, seed=seed, initial=initial,
                           ladders=replicas, cluster_moves=cluster_moves, cluster_max_temperature=cluster_max_temperature)
-    try:
-        pt.run(int(n_equilibrate) // int(measure_every), int(measure_every), swap=swap, record=False)
-        pt.run(int(n_measure), int(measure_every), swap=swap, record=True)
-        hist = pt._pt.history()
-        N = rows * cols
-        out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
-        out["temperatures"] = temperatures
-        Ms = np.ascontiguousarray(hist["M"][:, 0].T) / N
-        Es = np.ascontiguousarray(hist["E"][:, 0].T)
-        Qs = np.ascontiguousarray(hist["q"].T) / N if replicas == 2 else None
-        out = _scan_summary(out, N, Ms, Es, Qs)
-        out["swap_acceptance"] = pt.acceptance
-        out["round_trips"] = pt.round_trips
-        if pt.cluster_moves:
-            st = pt.cluster_stats
-            with np.errstate(divide="ignore", invalid="ignore"):
-                out["cluster_flipped"] = st["flipped"] / (st["passes"] * float(N))
-    finally:
-        pt._pt.close()
-    return out
+    return _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
 
 
 class _PeriodicAxisError(_hip.UnsupportedError, ValueError):
@@ -1123,7 +1141,7 @@ def _tempering_disorder_3d(shape, periodic, coupling, external_field, couplings,
         raise _PeriodicAxisError(str(e)) from None
 
 
-class LatticeTempering3D:
+class LatticeTempering3D(_LatticeTempering):
     """Parallel tempering (replica exchange) of a disordered cubic lattice on the GPU (K8, physical mode): :class:`LatticeTempering`
     for the lattices of :class:`IsingModel3D`.
 
@@ -1142,76 +1160,11 @@ class LatticeTempering3D:
                  periodic=True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1):
         self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
         self.n_spins = self.depth * self.rows * self.cols
-        T = np.asarray(temperatures, dtype=float).ravel()
-        if not 2 <= T.size <= 256:
-            raise ValueError(f"parallel tempering needs 2 to 256 temperatures, got {T.size}")
-        if not np.all(np.isfinite(T) & (T > 0)):
-            raise ValueError("Temperature must be positive")
-        if ladders not in (1, 2):
-            raise ValueError("ladders must be 1 or 2")
-        if initial not in _PT_INITIAL:
-            raise ValueError("initial must be 'random', 'up' or 'down'")
+        self._check_ladder(temperatures, ladders, initial)
         self.periodic = _hip.periodic_axes(periodic)
         self._disorder = _tempering_disorder_3d(self.shape, self.periodic, float(coupling), float(external_field), couplings, field)
-        self.temperatures = T
-        self.ladders = int(ladders)
-        self.seed = int(seed) if seed is not None else (
-            int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
-        self._pt = _hip.TemperingLattice3D(self.depth, self.rows, self.cols, self.periodic, T.size, self.ladders)
-        self._pt.set_disorder(*self._disorder)
-        self._pt.set_temperatures(T)
-        self._pt.init(self.seed, _PT_INITIAL[initial])
-
-    def run(self, n_rounds: int, swap_interval: int = 10, swap: bool = True, record: bool = True):
-        """n_rounds rounds of swap_interval sweeps each; with ``record`` returns ``history()`` (ladder 0), else None."""
-        self._pt.run(int(n_rounds), int(swap_interval), swap, record)
-        return self.history() if record else None
-
-    def history(self, ladder: int = 0) -> dict:
-        """The rounds recorded by the last ``run`` as (n_rounds, R) arrays, per slot: ``E`` (float64 energy), ``M`` (int64 sum of
-        spins), ``walker`` (which walker of the ladder sat there) and, with two ladders, ``q`` (int64 overlap of the two ladders'
-        walkers at that slot)."""
-        h = self._pt.history()
-        out = {k: np.ascontiguousarray(h[k][:, ladder]) for k in ("E", "M", "walker")}
-        if h["q"] is not None:
-            out["q"] = h["q"]
-        return out
-
-    @property
-    def acceptance(self) -> np.ndarray:
-        """Accepted / attempted swaps per adjacent pair of slots, ladders pooled (NaN before the first attempt)."""
-        st = self._pt.stats()
-        with np.errstate(divide="ignore", invalid="ignore"):
-            return st["accepts"].sum(axis=0) / st["attempts"].sum(axis=0)
-
-    @property
-    def round_trips(self) -> int:
-        """Round trips (slot 0 -> last slot -> slot 0) completed by all walkers of all ladders."""
-        return int(self._pt.stats()["round_trips"].sum())
-
-    @property
-    def walker_at_slot(self) -> np.ndarray:
-        """(ladders, R): which walker sits at each slot."""
-        return self._pt.stats()["walker_at_slot"]
-
-    @property
-    def sweep_count(self) -> int:
-        return int(self._pt.stats()["sweep_count"])
-
-    def _check_slot(self, slot, ladder):
-        if not (0 <= slot < self.temperatures.size and 0 <= ladder < self.ladders):
-            raise ValueError(f"slot {slot} / ladder {ladder} out of range ({self.ladders} ladder(s) of {self.temperatures.size})")
-
-    def spins(self, slot: int, ladder: int = 0) -> np.ndarray:
-        """(D, R, C) spins of the walker now at ``slot``."""
-        self._check_slot(slot, ladder)
-        return self._pt.get_spins(ladder, slot)
-
-    def energy(self, slot: int, ladder: int = 0) -> float:
-        """Energy of the walker now at ``slot`` (the device's fixed-order float64 sum)."""
-        self._check_slot(slot, ladder)
-        E, _ = self._pt.energies()
-        return float(E[ladder, self._pt.stats()["walker_at_slot"][ladder, slot]])
+        self._start(_hip.TemperingLattice3D(self.depth, self.rows, self.cols, self.periodic, self.temperatures.size, self.ladders),
+                    seed, initial)
 
 
 def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
@@ -1234,19 +1187,4 @@ def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: 
     temperatures = np.asarray(temperatures, dtype=float)
     pt = LatticeTempering3D(shape, temperatures, couplings=(jr, jd, jl), field=h, periodic=periodic, seed=seed, initial=initial,
                             ladders=replicas)
-    try:
-        pt.run(int(n_equilibrate) // int(measure_every), int(measure_every), swap=swap, record=False)
-        pt.run(int(n_measure), int(measure_every), swap=swap, record=True)
-        hist = pt._pt.history()
-        N = pt.n_spins
-        out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
-        out["temperatures"] = temperatures
-        Ms = np.ascontiguousarray(hist["M"][:, 0].T) / N
-        Es = np.ascontiguousarray(hist["E"][:, 0].T)
-        Qs = np.ascontiguousarray(hist["q"].T) / N if replicas == 2 else None
-        out = _scan_summary(out, N, Ms, Es, Qs)
-        out["swap_acceptance"] = pt.acceptance
-        out["round_trips"] = pt.round_trips
-    finally:
-        pt._pt.close()
-    return out
+    return _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
