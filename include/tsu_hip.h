@@ -336,6 +336,11 @@ int tsu_pt3d_set_spins(tsu_pt3d* pt, int ladder, int slot, const int8_t* host);
 /* k8_pt_sweep launches so far (one per half-sweep for all walkers of all ladders) */
 int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
 
+/* K7 / K8: axis profiles and k_min Fourier modes for the correlation length (tsu_ising2d_profiles / tsu_ising3d_profiles and the
+ * ladders' set_correlation / history_modes / profiles): declared in tsu_hip_correlation.h, which this header includes; its
+ * prototypes are _hip.CORRELATION_SIGNATURES in Python. */
+#include "tsu_hip_correlation.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

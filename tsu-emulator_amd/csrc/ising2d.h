@@ -40,6 +40,8 @@ struct tsu_ising2d {
     double* d_dis_part;  // K7 energy: per-workgroup partials + the total
     size_t dis_part_cap;
     unsigned long long dis_launches;  // K7 sweep-kernel launches so far (not counted in `launches`)
+    long long* d_prof;   // tsu_ising2d_profiles: rows + cols int64 bins (ising2d_grow)
+    size_t prof_cap;
 };
 
 // grow-only device buffer: reallocated (contents dropped) only when it holds fewer than `bytes`; no memset, no synchronisation

@@ -397,6 +397,8 @@ int tsu_ising2d_create_slab(tsu_ctx* ctx, int64_t total_rows, int cols, int peri
     L->d_dis_part = nullptr;
     L->dis_part_cap = 0;
     L->dis_launches = 0;
+    L->d_prof = nullptr;
+    L->prof_cap = 0;
     size_t bytes = (size_t)(rows + 2 * ghost) * L->pitch;
     hipError_t e = hipMalloc(&L->alloc[0], bytes);
     if (e == hipSuccess) e = hipMemsetAsync(L->alloc[0], 0, bytes, ctx->stream);
@@ -435,6 +437,7 @@ int tsu_ising2d_destroy(tsu_ising2d* L) {
     if (L->d_sw_batch) (void)hipFree(L->d_sw_batch);
     if (L->d_dis) (void)hipFree(L->d_dis);
     if (L->d_dis_part) (void)hipFree(L->d_dis_part);
+    if (L->d_prof) (void)hipFree(L->d_prof);
     (void)hipEventDestroy(L->ev0);
     (void)hipEventDestroy(L->ev1);
     delete L;

@@ -42,6 +42,7 @@
 #include "disorder_dev.h"
 #include "ising2d.h"
 #include "ising2d_pt.h"
+#include "corr_dev.h"
 #include "pt_host.h"
 #include "reduce_dev.h"
 
@@ -506,6 +507,31 @@ int tsu_ising2d_overlap(tsu_ising2d* A, tsu_ising2d* B, int64_t* q) {
     return rc != TSU_OK ? rc : ising2d_check_err(B);
 }
 
+int tsu_ising2d_profiles(tsu_ising2d* A, tsu_ising2d* B, int64_t* p_row, int64_t* p_col) {
+    TSU_ENTER(A ? A->ctx : nullptr);
+    if (!A) return TSU_E_INVALID;
+    tsu_ctx* ctx = A->ctx;
+    TSU_REQUIRE(ctx, p_row && p_col, "ising2d_profiles: NULL output");
+    if (!whole_lattice(A) || (B && !whole_lattice(B))) return tsu_fail(ctx, TSU_E_UNSUPPORTED, "ising2d_profiles: whole lattices only (not slabs)");
+    if (B) {
+        TSU_REQUIRE(ctx, B->ctx == ctx, "ising2d_profiles: the two lattices belong to different contexts");
+        TSU_REQUIRE(ctx, A->rows == B->rows && A->cols == B->cols, "ising2d_profiles: shapes differ (%d x %d against %d x %d)", A->rows,
+                    A->cols, B->rows, B->cols);
+    }
+    const size_t n = (size_t)A->rows + (size_t)A->cols;
+    TSU_HIP_TRY(ctx, ising2d_grow(A->d_prof, A->prof_cap, n * sizeof(long long)));
+    TSU_HIP_TRY(ctx, hipMemsetAsync(A->d_prof, 0, n * sizeof(long long), ctx->stream));
+    ProfArgs pa;
+    const dim3 grid = profile_plan(pa, (long long)A->pitch, B ? (long long)B->pitch : 0, A->rows, A->rows, A->cols, 0, 1);
+    profile_pass<<<grid, 256, 0, ctx->stream>>>(A->alloc[A->cur], B ? B->alloc[B->cur] : nullptr, pa, A->d_prof);
+    TSU_HIP_TRY(ctx, hipGetLastError());
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(p_row, A->d_prof, (size_t)A->rows * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(p_col, A->d_prof + A->rows, (size_t)A->cols * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const int rc = ising2d_check_err(A);
+    return rc != TSU_OK || !B ? rc : ising2d_check_err(B);
+}
+
 int tsu_ising2d_disorder_launch_count(tsu_ising2d* L, uint64_t* n) {
     TSU_ENTER(L ? L->ctx : nullptr);
     if (!L || !n) return TSU_E_INVALID;
@@ -524,6 +550,11 @@ int tsu_pt2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int n_temps,
             P->nrows = P->lat[0]->rows;
             P->pitch = (long long)P->lat[0]->pitch;
             P->cols = P->lat[0]->cols;
+            P->n_axes = 2;
+            P->lrows = P->lat[0]->rows;
+            P->axis_len[0] = P->lat[0]->rows;
+            P->axis_len[1] = P->lat[0]->cols;
+            P->axis_per[0] = P->axis_per[1] = P->lat[0]->periodic;
             for (int g = 0; g < P->nw; ++g) planes[g] = P->lat[g]->alloc[P->lat[g]->cur];
         },
         pt_free);
@@ -624,6 +655,27 @@ int tsu_pt2d_set_spins(tsu_pt2d* P, int ladder, int slot, const int8_t* host) {
 int tsu_pt2d_launch_count(tsu_pt2d* P, uint64_t* n) {
     TSU_ENTER(P ? P->ctx : nullptr);
     return pt_launch_count(P, n);
+}
+
+int tsu_pt2d_set_correlation(tsu_pt2d* P, int enable, const double* cos_row, const double* sin_row, const double* cos_col,
+                             const double* sin_col) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const double* cs[2] = {cos_row, cos_col};
+    const double* sn[2] = {sin_row, sin_col};
+    return pt_set_correlation(P, enable, cs, sn);
+}
+
+int tsu_pt2d_history_modes(tsu_pt2d* P, double* modes) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history_modes(P, modes) : TSU_E_INVALID;
+}
+
+int tsu_pt2d_profiles(tsu_pt2d* P, int slot, int64_t* p_row, int64_t* p_col) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    int64_t* out[2] = {p_row, p_col};
+    return pt_profiles(P, slot, out);
 }
 
 }  // extern "C"

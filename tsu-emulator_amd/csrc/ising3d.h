@@ -21,6 +21,7 @@ struct tsu_ising3d {
     size_t sw_batch_cap;
     int* h_err;          // host-mapped flag: 2 = a capped union / find loop of a cluster kernel expired (results invalid)
     unsigned long long sw_launches;  // cluster-kernel launches so far (not counted in `launches`)
+    long long* d_prof;   // tsu_ising3d_profiles: depth + rows + cols int64 bins (first call)
 };
 
 // ising3d_cluster.hip: report (and clear) a flag a cluster kernel left in h_err; release what the cluster calls allocated

@@ -52,6 +52,7 @@
 #include "disorder_dev.h"
 #include "ising2d.h"
 #include "ising3d.h"
+#include "corr_dev.h"
 #include "pt_host.h"
 #include "reduce_dev.h"
 
@@ -596,6 +597,7 @@ int tsu_ising3d_destroy(tsu_ising3d* L) {
     if (L->d_dis) (void)hipFree(L->d_dis);
     if (L->d_part) (void)hipFree(L->d_part);
     if (L->d_acc) (void)hipFree(L->d_acc);
+    if (L->d_prof) (void)hipFree(L->d_prof);
     ising3d_cluster_free(L);
     delete L;
     return TSU_OK;
@@ -750,6 +752,35 @@ int tsu_ising3d_overlap(tsu_ising3d* A, tsu_ising3d* B, int64_t* q) {
     return read_acc(A, q);
 }
 
+int tsu_ising3d_profiles(tsu_ising3d* A, tsu_ising3d* B, int64_t* p_z, int64_t* p_r, int64_t* p_c) {
+    TSU_ENTER(A ? A->ctx : nullptr);
+    if (!A) return TSU_E_INVALID;
+    tsu_ctx* ctx = A->ctx;
+    TSU_REQUIRE(ctx, p_z && p_r && p_c, "ising3d_profiles: NULL output");
+    if (B) {
+        TSU_REQUIRE(ctx, B->ctx == ctx, "ising3d_profiles: the two lattices belong to different contexts");
+        TSU_REQUIRE(ctx, A->depth == B->depth && A->rows == B->rows && A->cols == B->cols,
+                    "ising3d_profiles: shapes differ (%d x %d x %d against %d x %d x %d)", A->depth, A->rows, A->cols, B->depth, B->rows,
+                    B->cols);
+    }
+    const size_t n = (size_t)A->depth + (size_t)A->rows + (size_t)A->cols;
+    if (!A->d_prof) TSU_HIP_TRY(ctx, hipMalloc((void**)&A->d_prof, n * sizeof(long long)));
+    TSU_HIP_TRY(ctx, hipMemsetAsync(A->d_prof, 0, n * sizeof(long long), ctx->stream));
+    ProfArgs pa;
+    const dim3 grid = profile_plan(pa, (long long)A->pitch, B ? (long long)B->pitch : 0, (long long)A->depth * A->rows, A->rows, A->cols, 1, 1);
+    profile_pass<<<grid, 256, 0, ctx->stream>>>(A->s, B ? B->s : nullptr, pa, A->d_prof);
+    TSU_HIP_TRY(ctx, hipGetLastError());
+    int64_t* out[3] = {p_z, p_r, p_c};
+    const int len[3] = {A->depth, A->rows, A->cols};
+    const long long* src = A->d_prof;
+    for (int a = 0; a < 3; ++a) {
+        TSU_HIP_TRY(ctx, hipMemcpyAsync(out[a], src, (size_t)len[a] * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        src += len[a];
+    }
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return ising3d_check_err(A);
+}
+
 int tsu_ising3d_launch_count(tsu_ising3d* L, uint64_t* n) {
     TSU_ENTER(L ? L->ctx : nullptr);
     if (!L || !n) return TSU_E_INVALID;
@@ -768,6 +799,14 @@ int tsu_pt3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_ma
             P->nrows = (long long)P->lat[0]->depth * P->lat[0]->rows;
             P->pitch = (long long)P->lat[0]->pitch;
             P->cols = P->lat[0]->cols;
+            P->n_axes = 3;
+            P->lrows = P->lat[0]->rows;
+            P->axis_len[0] = P->lat[0]->depth;
+            P->axis_len[1] = P->lat[0]->rows;
+            P->axis_len[2] = P->lat[0]->cols;
+            P->axis_per[0] = P->lat[0]->pz;
+            P->axis_per[1] = P->lat[0]->pr;
+            P->axis_per[2] = P->lat[0]->pc;
             for (int g = 0; g < P->nw; ++g) planes[g] = P->lat[g]->s;
         },
         pt_free);
@@ -862,6 +901,27 @@ int tsu_pt3d_set_spins(tsu_pt3d* P, int ladder, int slot, const int8_t* host) {
 int tsu_pt3d_launch_count(tsu_pt3d* P, uint64_t* n) {
     TSU_ENTER(P ? P->ctx : nullptr);
     return pt_launch_count(P, n);
+}
+
+int tsu_pt3d_set_correlation(tsu_pt3d* P, int enable, const double* cos_z, const double* sin_z, const double* cos_r, const double* sin_r,
+                             const double* cos_c, const double* sin_c) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const double* cs[3] = {cos_z, cos_r, cos_c};
+    const double* sn[3] = {sin_z, sin_r, sin_c};
+    return pt_set_correlation(P, enable, cs, sn);
+}
+
+int tsu_pt3d_history_modes(tsu_pt3d* P, double* modes) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history_modes(P, modes) : TSU_E_INVALID;
+}
+
+int tsu_pt3d_profiles(tsu_pt3d* P, int slot, int64_t* p_z, int64_t* p_r, int64_t* p_c) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    int64_t* out[3] = {p_z, p_r, p_c};
+    return pt_profiles(P, slot, out);
 }
 
 }  // extern "C"

@@ -11,19 +11,21 @@
 #include <type_traits>
 #include <vector>
 
+#include "corr_dev.h"
 #include "pt_ladder.h"
 #include "reduce_dev.h"
 
 namespace {
 
 void pt_free_history(pt_ladder* P) {
-    void* bufs[] = {P->d_hE, P->d_hM, P->d_hW, P->d_hq};
+    void* bufs[] = {P->d_hE, P->d_hM, P->d_hW, P->d_hq, P->d_hF};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     P->d_hE = nullptr;
     P->d_hM = nullptr;
     P->d_hW = nullptr;
     P->d_hq = nullptr;
+    P->d_hF = nullptr;
     P->hist_cap = 0;
 }
 
@@ -31,7 +33,7 @@ void pt_free_history(pt_ladder* P) {
 template <class H, class Destroy>
 void pt_delete(H* P, Destroy destroy) {
     void* bufs[] = {P->d_s, P->d_key, P->d_slot, P->d_was, P->d_flag, P->d_T, P->d_c32, P->d_att, P->d_acc,
-                    P->d_trips, P->d_part, P->d_ipart, P->d_E, P->d_M};
+                    P->d_trips, P->d_part, P->d_ipart, P->d_E, P->d_M, P->d_prof, P->d_tab};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     pt_free_history(P);
@@ -200,6 +202,133 @@ void pt_enqueue_energies(pt_ladder* P, unsigned blocks, Partials&& partials) {
     pt_energy_final<<<(unsigned)P->nw, 256, 0, P->ctx->stream>>>(P->d_part, P->d_ipart, (int)blocks, P->d_E, P->d_M);
 }
 
+// ---------------------------------------------------------------- correlation recording (corr_dev.h)
+long long pt_prof_len(const pt_ladder* P) {
+    long long n = 0;
+    for (int a = 0; a < P->n_axes; ++a) n += P->axis_len[a];
+    return n;
+}
+
+int pt_periodic_axes(const pt_ladder* P) {
+    int n = 0;
+    for (int a = 0; a < P->n_axes; ++a) n += P->axis_per[a] ? 1 : 0;
+    return n;
+}
+
+// doubles of a slot's modes: (re, im) per periodic axis
+size_t pt_mode_doubles(const pt_ladder* P) { return 2 * (size_t)pt_periodic_axes(P); }
+
+dim3 pt_profile_plan(const pt_ladder* P, ProfArgs& pa) {
+    return profile_plan(pa, P->pitch, P->pitch, P->nrows, P->lrows, P->cols, P->n_axes == 3, (unsigned)P->R);
+}
+
+// where the mode pass finds each periodic axis's profile and tables
+ModeArgs pt_mode_args(const pt_ladder* P) {
+    ModeArgs m = {};
+    int off = 0;
+    const double* tab = P->d_tab;
+    for (int a = 0; a < P->n_axes; ++a) {
+        if (P->axis_per[a]) {
+            m.off[m.n] = off;
+            m.len[m.n] = P->axis_len[a];
+            m.cs[m.n] = tab;
+            m.sn[m.n] = tab + P->axis_len[a];
+            tab += 2 * (size_t)P->axis_len[a];
+            m.n += 1;
+        }
+        off += P->axis_len[a];
+    }
+    return m;
+}
+
+int pt_prof_scratch(pt_ladder* P, const char* op) {
+    if (P->d_prof) return TSU_OK;
+    const hipError_t e = hipMalloc((void**)&P->d_prof, (size_t)P->R * pt_prof_len(P) * sizeof(long long));
+    if (e == hipSuccess) return TSU_OK;
+    (void)hipGetLastError();
+    return tsu_fail(P->ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP, "%s_%s: %s", P->name, op, hipGetErrorString(e));
+}
+
+// set_correlation: cs[a] / sn[a] = the host's cos / sin tables of axis a (both NULL exactly on an open axis).  Switching it on drops
+// the recorded history (its buffers gain the modes with the next run); switching it off leaves a run what it was (synchronises)
+int pt_set_correlation(pt_ladder* P, int enable, const double* const* cs, const double* const* sn) {
+    tsu_ctx* ctx = P->ctx;
+    if (!enable) {
+        P->corr = 0;
+        return TSU_OK;
+    }
+    TSU_REQUIRE(ctx, pt_periodic_axes(P) > 0, "%s_set_correlation: the lattice has no periodic axis (no k_min mode is defined)", P->name);
+    size_t n = 0;
+    for (int a = 0; a < P->n_axes; ++a) {
+        if (P->axis_per[a]) {
+            TSU_REQUIRE(ctx, cs[a] && sn[a], "%s_set_correlation: NULL table of periodic axis %d", P->name, a);
+            n += 2 * (size_t)P->axis_len[a];
+        } else {
+            TSU_REQUIRE(ctx, !cs[a] && !sn[a], "%s_set_correlation: axis %d is open: its tables must be NULL", P->name, a);
+        }
+    }
+    int rc = pt_prof_scratch(P, "set_correlation");
+    if (rc != TSU_OK) return rc;
+    if (!P->d_tab) {
+        const hipError_t e = hipMalloc((void**)&P->d_tab, n * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return tsu_fail(ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP, "%s_set_correlation: %s", P->name, hipGetErrorString(e));
+        }
+    }
+    double* tab = P->d_tab;
+    for (int a = 0; a < P->n_axes; ++a)
+        if (P->axis_per[a]) {
+            const size_t len = (size_t)P->axis_len[a];
+            TSU_HIP_TRY(ctx, hipMemcpyAsync(tab, cs[a], len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            TSU_HIP_TRY(ctx, hipMemcpyAsync(tab + len, sn[a], len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            tab += 2 * len;
+        }
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // before the caller's tables go
+    if (!P->corr) {
+        pt_free_history(P);
+        P->hist_rounds = 0;
+        P->hist_modes = 0;
+    }
+    P->corr = 1;
+    return TSU_OK;
+}
+
+// the modes of the last run's rows, [round][slot][periodic axis][re, im] (synchronises)
+int pt_history_modes(pt_ladder* P, double* modes) {
+    tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, modes, "%s_history_modes: NULL output", P->name);
+    TSU_REQUIRE(ctx, P->hist_modes, "%s_history_modes: the last run recorded no modes (call tsu_%s_set_correlation before a recording run)",
+                P->name, P->name);
+    const size_t n = (size_t)P->hist_rounds * P->R * pt_mode_doubles(P);
+    if (n) TSU_HIP_TRY(ctx, hipMemcpyAsync(modes, P->d_hF, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSU_OK;
+}
+
+// the profiles of the walkers now at `slot` (the product of the two ladders' walkers if there are two), axis a into out[a]
+// (synchronises)
+int pt_profiles(pt_ladder* P, int slot, int64_t* const* out) {
+    tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, slot >= 0 && slot < P->R, "%s_profiles: slot %d out of range (%d temperatures)", P->name, slot, P->R);
+    for (int a = 0; a < P->n_axes; ++a) TSU_REQUIRE(ctx, out[a], "%s_profiles: NULL output", P->name);
+    const int rc = pt_prof_scratch(P, "profiles");
+    if (rc != TSU_OK) return rc;
+    const long long len = pt_prof_len(P);
+    ProfArgs pa;
+    const dim3 grid = pt_profile_plan(P, pa);
+    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_prof, 0, (size_t)P->R * len * sizeof(long long), ctx->stream));
+    pt_profile<<<grid, 256, 0, ctx->stream>>>(P->d_s, P->d_was, P->R, P->nl, pa, P->d_prof, len);
+    TSU_HIP_TRY(ctx, hipGetLastError());
+    const long long* row = P->d_prof + (size_t)slot * len;
+    for (int a = 0; a < P->n_axes; ++a) {
+        TSU_HIP_TRY(ctx, hipMemcpyAsync(out[a], row, (size_t)P->axis_len[a] * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+        row += P->axis_len[a];
+    }
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSU_OK;
+}
+
 // what a run needs, in the order the messages are promised
 int pt_run_check(pt_ladder* P, int have_disorder, int n_rounds, int swap_interval) {
     tsu_ctx* ctx = P->ctx;
@@ -228,6 +357,7 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hM, n * sizeof(long long));
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hW, n * sizeof(int32_t));
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hq, (size_t)n_rounds * R * sizeof(long long));
+        if (e == hipSuccess && P->corr) e = hipMalloc((void**)&P->d_hF, (size_t)n_rounds * R * pt_mode_doubles(P) * sizeof(double));
         if (e != hipSuccess) {  // nothing of a history that does not fit stays behind
             pt_free_history(P);
             P->hist_rounds = 0;
@@ -241,7 +371,12 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
     if (record && nl == 2 && n_rounds > 0)
         TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hq, 0, (size_t)n_rounds * R * sizeof(long long), ctx->stream));
     P->hist_rounds = record ? n_rounds : 0;
+    P->hist_modes = record && P->corr;
     const unsigned blocks = reduce_blocks(pt_lanes(P));
+    ProfArgs pa;
+    ModeArgs ma = {};
+    const dim3 pgrid = pt_profile_plan(P, pa);
+    if (P->hist_modes) ma = pt_mode_args(P);
     PTSwap sw;
     sw.E = P->d_E;
     sw.M = P->d_M;
@@ -276,6 +411,12 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
             if (record && nl == 2)
                 pt_overlap<<<dim3(blocks, (unsigned)R, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, P->pitch, P->nrows, P->cols,
                                                                                  P->d_hq + (size_t)t * R);
+            if (P->hist_modes) {  // the walkers the pass left at each slot: their profiles, then the modes of the periodic axes
+                TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_prof, 0, (size_t)R * pt_prof_len(P) * sizeof(long long), ctx->stream));
+                pt_profile<<<pgrid, 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, nl, pa, P->d_prof, pt_prof_len(P));
+                pt_modes<<<dim3(2u * (unsigned)ma.n, (unsigned)R, 1), 256, 0, ctx->stream>>>(
+                    P->d_prof, pt_prof_len(P), ma, P->d_hF + (size_t)t * R * pt_mode_doubles(P));
+            }
         }
         P->rounds += 1;
     }

@@ -35,5 +35,13 @@ struct pt_ladder {
     int32_t* d_hW;
     long long* d_hq;               // [round][slot] (two ladders)
     uint32_t key0, key1;           // Philox key of the swap uniforms (the seed)
+    // correlation recording (corr_dev.h): the lattice's axes as the handle's create fills them in, then what set_correlation adds
+    int n_axes, lrows;             // axes (2 or 3) and the rows of a layer (2-D: nrows)
+    int axis_len[3], axis_per[3];  // length and periodic flag per axis, in axis order (2-D: rows, cols; 3-D: depth, rows, cols)
+    int corr;                      // a recording round also records the k_min modes
+    int hist_modes;                // the last run's rows have them
+    long long* d_prof;             // [slot][sum of axis_len] profile scratch (first set_correlation / profiles call)
+    double* d_tab;                 // per periodic axis, in axis order: cos[len], sin[len] (first set_correlation)
+    double* d_hF;                  // [round][slot][periodic axis][re, im]
     double h_T[kPtMaxTemps];       // host copy of d_T
 };

@@ -170,6 +170,18 @@ CLUSTER3D_SIGNATURES = {
     "tsu_ising3d_cluster_launch_count": (C.c_int, [_vp, _u64p]),
 }
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_correlation.h (the header tsu_hip.h includes) one to one
+CORRELATION_SIGNATURES = {
+    "tsu_ising2d_profiles": (C.c_int, [_vp, _vp, _i64p, _i64p]),
+    "tsu_ising3d_profiles": (C.c_int, [_vp, _vp, _i64p, _i64p, _i64p]),
+    "tsu_pt2d_set_correlation": (C.c_int, [_vp, C.c_int, _f64p, _f64p, _f64p, _f64p]),
+    "tsu_pt3d_set_correlation": (C.c_int, [_vp, C.c_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
+    "tsu_pt2d_history_modes": (C.c_int, [_vp, _f64p]),
+    "tsu_pt3d_history_modes": (C.c_int, [_vp, _f64p]),
+    "tsu_pt2d_profiles": (C.c_int, [_vp, C.c_int, _i64p, _i64p]),
+    "tsu_pt3d_profiles": (C.c_int, [_vp, C.c_int, _i64p, _i64p, _i64p]),
+}
+
 _lib = None
 
 
@@ -186,7 +198,7 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailableError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -436,6 +448,12 @@ class Lattice:
         self.ctx.check(self.lib.tsu_ising2d_disorder_launch_count(self.h, C.byref(n)))
         return n.value
 
+    def profiles(self, other=None):
+        """(P_row, P_col): exact int64 sums of s (or of s s' with another lattice of the same shape) over the columns / rows."""
+        pr, pc = np.zeros(self.rows, np.int64), np.zeros(self.cols, np.int64)
+        self.ctx.check(self.lib.tsu_ising2d_profiles(self.h, None if other is None else other.h, _ptr(pr, _i64p), _ptr(pc, _i64p)))
+        return pr, pc
+
 
 def periodic_axes(periodic):
     """(p_z, p_r, p_c) from a bool (all three axes) or a triple of bools."""
@@ -518,6 +536,12 @@ class Lattice3D:
         self.ctx.check(self.lib.tsu_ising3d_launch_count(self.h, C.byref(n)))
         return n.value
 
+    def profiles(self, other=None):
+        """(P_z, P_r, P_c): exact int64 sums of s (or of s s' with another lattice of the same shape) over the other two axes."""
+        out = tuple(np.zeros(n, np.int64) for n in self.shape)
+        self.ctx.check(self.lib.tsu_ising3d_profiles(self.h, None if other is None else other.h, *[_ptr(a, _i64p) for a in out]))
+        return out
+
     def cluster_sweep(self, T, n_steps, seed, step0=0, replica=0):
         """n_steps Swendsen-Wang steps on the stored couplings at temperature T, zero field (step counters step0 ..)."""
         self.ctx.check(self.lib.tsu_ising3d_cluster_sweep(self.h, float(T), int(n_steps), int(seed), int(step0), int(replica)))
@@ -540,6 +564,7 @@ class _TemperingHandle:
 
     def _create(self, *shape_args):
         self._recorded = 0
+        self._correlation = self._modes_recorded = False
         h = _vp()
         self.ctx.check(self._fn("create")(self.ctx.h, *shape_args, self.n_temps, self.n_ladders, C.byref(h)))
         self.h = h
@@ -572,6 +597,47 @@ class _TemperingHandle:
     def run(self, n_rounds, swap_interval, swap=True, record=True):
         self.ctx.check(self._fn("run")(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record))))
         self._recorded = int(n_rounds) if record else 0
+        self._modes_recorded = bool(record) and self._correlation
+
+    def _periodic_flags(self):
+        p = self.periodic
+        return (bool(p),) * len(self.shape) if isinstance(p, (bool, np.bool_)) else tuple(bool(x) for x in p)
+
+    def set_correlation(self, enable, tables=None):
+        """Record the k_min modes of the periodic axes in every recording round.  ``tables``: per axis ``(cos, sin)`` float64 arrays of
+        the axis's length made on the host, or None for an open axis."""
+        n_axes = len(self.shape)
+        tables = list(tables) if tables is not None else [None] * n_axes
+        if len(tables) != n_axes:
+            raise ValueError(f"need one table pair (or None) per axis, {n_axes} in all")
+        keep, args = [], []
+        for n, t in zip(self.shape, tables):
+            if t is None:
+                args += [None, None]
+                continue
+            pair = [np.ascontiguousarray(a, dtype=np.float64).ravel() for a in t]
+            if len(pair) != 2 or pair[0].size != n or pair[1].size != n:
+                raise ValueError(f"a table pair must be (cos, sin) of the axis's length {n}")
+            keep += pair
+            args += [_ptr(a, _f64p) for a in pair]
+        self.ctx.check(self._fn("set_correlation")(self.h, int(bool(enable)), *args))
+        if enable and not self._correlation:
+            self._recorded = 0  # switching it on drops the previous run's rows
+        self._correlation = bool(enable)
+
+    def history_modes(self):
+        """The last run's modes as complex128 (n_rounds, n_temps, n_periodic_axes); raises if that run recorded none."""
+        n_per = sum(self._periodic_flags())
+        n = self._recorded if self._modes_recorded else 0
+        out = np.zeros((n, self.n_temps, n_per, 2))
+        self.ctx.check(self._fn("history_modes")(self.h, _ptr(out, _f64p)))
+        return out[..., 0] + 1j * out[..., 1]
+
+    def profiles(self, slot):
+        """Axis profiles (int64) of the walker now at ``slot``: of its spins, or with two ladders of the product of the two."""
+        out = tuple(np.zeros(n, np.int64) for n in self.shape)
+        self.ctx.check(self._fn("profiles")(self.h, int(slot), *[_ptr(a, _i64p) for a in out]))
+        return out
 
     def history(self):
         """The last run's rows: E, M (sum of spins), walker as (n_rounds, n_ladders, n_temps); q as (n_rounds, n_temps) or None."""

@@ -477,6 +477,62 @@ def _disorder_arrays(rows: int, cols: int, periodic: bool, coupling: float, exte
     return jr, jd, h
 
 
+# ---------------------------------------------------------------- correlation length: k_min modes of the axis profiles
+def _kmin_tables(L: int):
+    """(cos, sin) of 2 pi x / L for x = 0 .. L - 1 in float64: the tables the host hands to the device."""
+    ang = 2.0 * np.pi * np.arange(int(L), dtype=np.float64) / float(L)
+    return np.cos(ang), np.sin(ang)
+
+
+def _ordered_sum(terms: np.ndarray) -> float:
+    """The sum of float64 terms in the order of the device's mode pass (csrc/corr_dev.h): partial t of 256 adds the terms t, t + 256,
+    ... in ascending order from 0.0; the 64 partials of each of the four groups fold by halves (32, 16, .., 1); (g0 + g1) + (g2 + g3)."""
+    acc = np.zeros(256)
+    for lo in range(0, terms.size, 256):
+        chunk = terms[lo:lo + 256]
+        acc[:chunk.size] += chunk
+    w = acc.reshape(4, 64)
+    for off in (32, 16, 8, 4, 2, 1):
+        w = w[:, :off] + w[:, off:2 * off]
+    return float((w[0, 0] + w[1, 0]) + (w[2, 0] + w[3, 0]))
+
+
+def _kmin_modes(profiles, periodic) -> np.ndarray:
+    """complex128 F_d = sum_x P_d[x] (cos(2 pi x / L_d) + i sin(2 pi x / L_d)) per axis, NaN on an open axis."""
+    out = np.full(len(profiles), complex(np.nan, np.nan), dtype=np.complex128)
+    for d, (P, per) in enumerate(zip(profiles, periodic)):
+        if per:
+            c, sn = _kmin_tables(len(P))
+            Pf = np.asarray(P, dtype=np.int64).astype(np.float64)
+            out[d] = complex(_ordered_sum(Pf * c), _ordered_sum(Pf * sn))
+    return out
+
+
+def _check_correlation(periodic) -> None:
+    if not any(periodic):
+        raise ValueError("correlation=True needs at least one periodic axis (no k_min mode is defined on an open axis)")
+
+
+def correlation_length(f2, F2, lengths) -> np.ndarray:
+    """xi_d = sqrt(<f_tot^2> / <|F_d|^2> - 1) / (2 sin(pi / L_d)) per axis (last index of F2); NaN where the radicand is negative
+    or the axis has no mode."""
+    f2 = np.asarray(f2, dtype=np.float64)[..., None]
+    F2 = np.asarray(F2, dtype=np.float64)
+    L = np.asarray(lengths, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rad = f2 / F2 - 1.0
+        return np.where(rad >= 0, np.sqrt(np.where(rad >= 0, rad, 0.0)), np.nan) / (2.0 * np.sin(np.pi / L))
+
+
+def _correlation_summary(out: dict, N: int, lengths, periodic, f2, F2) -> dict:
+    """chi_k, xi and xi_over_L from <f_tot^2> (n_T,) and <|F_d|^2> (n_T, n_axes; NaN on open axes)."""
+    per = np.asarray(periodic, dtype=bool)
+    out["chi_k"] = np.asarray(F2, dtype=np.float64) / N
+    out["xi"] = correlation_length(f2, F2, lengths)
+    out["xi_over_L"] = np.mean(out["xi"][:, per] / np.asarray(lengths, dtype=np.float64)[per], axis=1)
+    return out
+
+
 class IsingModel2D:
     """README facade (README.md:116-131): a lattice that lives on the GPU between calls.
 
@@ -592,6 +648,17 @@ class IsingModel2D:
             raise ValueError(f"overlap needs equal shapes, got {(self.rows, self.cols)} and {(other.rows, other.cols)}")
         return self._lat.overlap(other._lat) / self.n_spins
 
+    def axis_profiles(self, other: Optional["IsingModel2D"] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """(P_row, P_col): exact int64 sums of the spins (of s s' with ``other``) over the columns / the rows, on the device."""
+        if other is not None and (other.rows, other.cols) != (self.rows, self.cols):
+            raise ValueError(f"axis_profiles needs equal shapes, got {(self.rows, self.cols)} and {(other.rows, other.cols)}")
+        return self._lat.profiles(None if other is None else other._lat)
+
+    def fourier_modes(self, other: Optional["IsingModel2D"] = None) -> np.ndarray:
+        """complex128 (2,): the k_min = 2 pi / L modes of the row and the column profile (NaN on an open lattice), summed on the
+        host from the device's profiles in the fixed order of the ladders' mode pass."""
+        return _kmin_modes(self.axis_profiles(other), (self.periodic, self.periodic))
+
     @property
     def spins(self) -> np.ndarray:
         return self._lat.get_spins()
@@ -633,7 +700,8 @@ def demonstrate_phase_transition(sizes: List[int] = [8, 16, 32], temperatures: O
 
 def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                      measure_every: int = 10, periodic: bool = True, seed: int = 0, bias_mode: str = "physical",
-                     initial: str = "up", algorithm: str = "gibbs", *, couplings=None, field=None, replicas: int = 1) -> dict:
+                     initial: str = "up", algorithm: str = "gibbs", *, couplings=None, field=None, replicas: int = 1,
+                     correlation: bool = False) -> dict:
     """GPU-resident form of :func:`demonstrate_phase_transition` (reference: ising.py:424-476) for lattices far
     beyond what a samples array can hold: one :class:`IsingModel2D` per temperature stays on the device, and
     |M|, E/N, chi = (<M^2> - <M>^2) N / T and C = (<E^2> - <E>^2) / (T^2 N) come from the device reductions
@@ -643,10 +711,15 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
     temperature (seed ``seed + len(temperatures) + i``) runs beside the first, and the result gains the spin-glass
     observables ``overlap`` = <|q|>, ``overlap_sq`` = <q^2> and ``binder`` = (3 - <q^4> / <q^2>^2) / 2 of q = overlap / N;
     the other keys are those of the first replica, as with ``replicas=1``.
+    ``correlation=True`` (a periodic lattice): the result gains ``chi_k`` = <|F_d|^2> / N and ``xi`` (both ``(n_T, 2)``, per axis) and
+    ``xi_over_L`` = the mean of xi_d / L_d, from the k_min modes F_d of the spins (``replicas=1``) or of the overlap field
+    (``replicas=2``) taken with every measurement (:meth:`IsingModel2D.fourier_modes`).
     """
     _check_algorithm(algorithm)
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
+    if correlation:
+        _check_correlation((bool(periodic),))
     disordered = couplings is not None or field is not None
     if algorithm == "swendsen_wang":
         if disordered:
@@ -689,6 +762,7 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
         advance(int(n_equilibrate))
     Ms, Es = np.zeros((nT, n_measure)), np.zeros((nT, n_measure))
     Qs = np.zeros((nT, n_measure))
+    F2s = np.zeros((nT, n_measure, 2))
     for j in range(n_measure if models else 0):
         advance(int(measure_every))
         for i, (sum_s, sum_bonds) in enumerate(_hip.observables_batch([m._lat for m in models[:nT]])):
@@ -699,8 +773,15 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
                 Es[i, j] = -models[i].coupling * float(sum_bonds) - models[i].external_field * float(sum_s)
             if replicas == 2:
                 Qs[i, j] = models[i].overlap(models[nT + i])
+            if correlation:
+                F2s[i, j] = np.abs(models[i].fourier_modes(models[nT + i] if replicas == 2 else None)) ** 2
     del models
-    return _scan_summary(out, rows * cols, Ms, Es, Qs if replicas == 2 else None)
+    out = _scan_summary(out, rows * cols, Ms, Es, Qs if replicas == 2 else None)
+    if correlation:
+        N = rows * cols
+        f2 = np.mean((Qs if replicas == 2 else Ms) ** 2, axis=1) * float(N) ** 2
+        _correlation_summary(out, N, (rows, cols), (bool(periodic),) * 2, f2, np.mean(F2s, axis=1))
+    return out
 
 
 def _scan_summary(out: dict, N: int, Ms, Es, Qs=None) -> dict:
@@ -871,6 +952,17 @@ class IsingModel3D:
             raise ValueError(f"overlap needs equal shapes, got {self.shape} and {other.shape}")
         return self._lat.overlap(other._lat) / self.n_spins
 
+    def axis_profiles(self, other: Optional["IsingModel3D"] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(P_z, P_r, P_c): exact int64 sums of the spins (of s s' with ``other``) over the other two axes, on the device."""
+        if other is not None and other.shape != self.shape:
+            raise ValueError(f"axis_profiles needs equal shapes, got {self.shape} and {other.shape}")
+        return self._lat.profiles(None if other is None else other._lat)
+
+    def fourier_modes(self, other: Optional["IsingModel3D"] = None) -> np.ndarray:
+        """complex128 (3,): the k_min = 2 pi / L_d modes of the three axis profiles (NaN on an open axis), summed on the host from
+        the device's profiles in the fixed order of the ladders' mode pass."""
+        return _kmin_modes(self.axis_profiles(other), self.periodic)
+
     @property
     def spins(self) -> np.ndarray:
         return self._lat.get_spins()
@@ -885,13 +977,16 @@ class IsingModel3D:
 
 def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                         measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", algorithm: str = "gibbs", *,
-                        couplings=None, field=None, replicas: int = 1) -> dict:
+                        couplings=None, field=None, replicas: int = 1, correlation: bool = False) -> dict:
     """:func:`temperature_scan` for a cubic lattice (K8): one :class:`IsingModel3D` per temperature stays on the device and
     |M|, E/N, chi and C come from the device reductions.  ``couplings`` / ``field``: the same quenched disorder at every
     temperature.  Model i of replica k has seed ``seed + k len(temperatures) + i``.  ``replicas=2``: the result gains
     ``overlap`` = <|q|>, ``overlap_sq`` = <q^2> and ``binder`` = (3 - <q^4> / <q^2>^2) / 2 of q = overlap / N; the other keys are
     those of the first replica.  ``algorithm="swendsen_wang"``: ``n_equilibrate`` and ``measure_every`` count Swendsen-Wang steps
-    on the couplings (zero field only); lattices of at most 16384 sites advance together, one launch per batch of steps."""
+    on the couplings (zero field only); lattices of at most 16384 sites advance together, one launch per batch of steps.
+    ``correlation=True`` (at least one periodic axis): the result gains ``chi_k`` = <|F_d|^2> / N and ``xi`` (both ``(n_T, 3)``, NaN on
+    an open axis) and ``xi_over_L`` = the mean of xi_d / L_d over the periodic axes, from the k_min modes of the spins
+    (``replicas=1``) or of the overlap field (``replicas=2``) taken with every measurement."""
     _check_algorithm(algorithm)
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
@@ -899,6 +994,8 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
     if np.any(~(temperatures > 0)):
         raise ValueError("Temperature must be positive")
     shape = _shape_3d(size)
+    if correlation:
+        _check_correlation(_hip.periodic_axes(periodic))
     # validated once, before any device call
     disorder = _disorder_arrays_3d(shape, _hip.periodic_axes(periodic), float(coupling), 0.0, couplings, field)
     if algorithm == "swendsen_wang":
@@ -923,6 +1020,7 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
     if models:
         advance(int(n_equilibrate))
     Ms, Es, Qs = np.zeros((nT, n_measure)), np.zeros((nT, n_measure)), np.zeros((nT, n_measure))
+    F2s = np.zeros((nT, n_measure, 3))
     for j in range(n_measure if models else 0):
         advance(int(measure_every))
         for i in range(nT):
@@ -930,8 +1028,15 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
             Es[i, j] = models[i].energy()
             if replicas == 2:
                 Qs[i, j] = models[i].overlap(models[nT + i])
+            if correlation:
+                F2s[i, j] = np.abs(models[i].fourier_modes(models[nT + i] if replicas == 2 else None)) ** 2
     del models
-    return _scan_summary(out, shape[0] * shape[1] * shape[2], Ms, Es, Qs if replicas == 2 else None)
+    N = shape[0] * shape[1] * shape[2]
+    out = _scan_summary(out, N, Ms, Es, Qs if replicas == 2 else None)
+    if correlation:
+        f2 = np.mean((Qs if replicas == 2 else Ms) ** 2, axis=1) * float(N) ** 2
+        _correlation_summary(out, N, shape, _hip.periodic_axes(periodic), f2, np.mean(F2s, axis=1))
+    return out
 
 
 _PT_INITIAL = {"random": 0, "up": 1, "down": -1}
@@ -980,7 +1085,19 @@ class _LatticeTempering:
         pt.set_temperatures(self.temperatures)
         if getattr(self, "cluster_moves", 0):  # 2-D only
             pt.set_cluster_moves(self.cluster_moves, self.cluster_max_temperature)
+        if self.correlation:  # the tables are made here, on the host
+            pt.set_correlation(True, [_kmin_tables(n) if per else None for n, per in zip(pt.shape, self._axes_periodic())])
         pt.init(self.seed, _PT_INITIAL[initial])
+
+    def _axes_periodic(self):
+        p = self.periodic
+        return tuple(p) if isinstance(p, tuple) else (bool(p),) * 2
+
+    def _set_correlation(self, correlation):
+        """Before any device call: keep the flag, refuse a lattice without a periodic axis."""
+        self.correlation = bool(correlation)
+        if self.correlation:
+            _check_correlation(self._axes_periodic())
 
     def run(self, n_rounds: int, swap_interval: int = 10, swap: bool = True, record: bool = True):
         """n_rounds rounds of swap_interval sweeps each; with ``record`` returns ``history()`` (ladder 0), else None."""
@@ -990,12 +1107,24 @@ class _LatticeTempering:
     def history(self, ladder: int = 0) -> dict:
         """The rounds recorded by the last ``run`` as (n_rounds, R) arrays, per slot: ``E`` (float64 energy), ``M`` (int64 sum of
         spins), ``walker`` (which walker of the ladder sat there) and, with two ladders, ``q`` (int64 overlap of the two ladders'
-        walkers at that slot)."""
+        walkers at that slot).  With ``correlation=True`` also ``modes``: complex128 (n_rounds, R, n_axes), the k_min mode of each
+        axis profile of the walker at that slot (one ladder: of its spins; two: of the overlap field; NaN on an open axis)."""
         h = self._pt.history()
         out = {k: np.ascontiguousarray(h[k][:, ladder]) for k in ("E", "M", "walker")}
         if h["q"] is not None:
             out["q"] = h["q"]
+        if self.correlation:
+            per = np.asarray(self._axes_periodic(), dtype=bool)
+            got = self._pt.history_modes()
+            modes = np.full(got.shape[:2] + (per.size,), complex(np.nan, np.nan), dtype=np.complex128)
+            modes[:, :, per] = got
+            out["modes"] = modes
         return out
+
+    def axis_profiles(self, slot: int) -> tuple:
+        """int64 axis profiles of the walker now at ``slot`` (two ladders: of the product of the two walkers there)."""
+        self._check_slot(slot, 0)
+        return self._pt.profiles(slot)
 
     @property
     def acceptance(self) -> np.ndarray:
@@ -1048,6 +1177,10 @@ def _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, s
         Es = np.ascontiguousarray(hist["E"][:, 0].T)
         Qs = np.ascontiguousarray(hist["q"].T) / N if pt.ladders == 2 else None
         out = _scan_summary(out, N, Ms, Es, Qs)
+        if pt.correlation:
+            F2 = np.mean(np.abs(pt.history()["modes"]) ** 2, axis=0)
+            f2 = np.mean((Qs if pt.ladders == 2 else Ms) ** 2, axis=1) * float(N) ** 2
+            _correlation_summary(out, N, pt._pt.shape, pt._axes_periodic(), f2, F2)
         out["swap_acceptance"] = pt.acceptance
         out["round_trips"] = pt.round_trips
         if getattr(pt, "cluster_moves", 0):
@@ -1082,12 +1215,13 @@ class LatticeTempering(_LatticeTempering):
 
     def __init__(self, size, temperatures, *, couplings=None, field=None, coupling: float = 1.0, external_field: float = 0.0,
                  periodic: bool = True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1,
-                 cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None):
+                 cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None, correlation: bool = False):
         self.rows, self.cols = (size, size) if np.isscalar(size) else tuple(size)
         self.n_spins = self.rows * self.cols
         self._check_ladder(temperatures, ladders, initial)
         self.cluster_moves, self.cluster_max_temperature = _cluster_move_args(cluster_moves, cluster_max_temperature, ladders)
         self.periodic = bool(periodic)
+        self._set_correlation(correlation)
         self._disorder = _disorder_arrays(self.rows, self.cols, self.periodic, float(coupling), float(external_field), "physical",
                                           couplings, field)
         self._start(_hip.TemperingLattice(self.rows, self.cols, self.periodic, self.temperatures.size, self.ladders), seed, initial)
@@ -1106,7 +1240,7 @@ class LatticeTempering(_LatticeTempering):
 def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                    measure_every: int = 10, periodic: bool = True, seed: int = 0, bias_mode: str = "physical",
                    initial: str = "up", *, couplings=None, field=None, replicas: int = 1, swap: bool = True,
-                   cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None) -> dict:
+                   cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None, correlation: bool = False) -> dict:
     """:func:`temperature_scan` of a disordered lattice with replica exchange between the temperatures (:class:`LatticeTempering`).
 
     One round = ``measure_every`` sweeps of every walker + one swap pass; ``n_equilibrate`` (a multiple of ``measure_every``)
@@ -1115,9 +1249,13 @@ def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int
     adjacent pair, ladders pooled) and ``round_trips`` (all walkers).  ``swap=False`` reproduces ``temperature_scan`` with the same
     arguments exactly.  ``cluster_moves`` / ``cluster_max_temperature`` as for :class:`LatticeTempering` (``replicas=2``); they add
     ``cluster_flipped``: the mean fraction of the sites a pass flipped per temperature, NaN where the slot does not take part.
+    ``correlation=True``: ``chi_k``, ``xi`` and ``xi_over_L`` as for :func:`temperature_scan`, from the modes the ladder records on the
+    device in every recorded round.
     """
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
+    if correlation:
+        _check_correlation((bool(periodic),))
     _cluster_move_args(cluster_moves, cluster_max_temperature, replicas)
     if int(measure_every) < 1 or int(n_equilibrate) % int(measure_every):
         raise ValueError("n_equilibrate must be a multiple of measure_every")
@@ -1125,7 +1263,8 @@ def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int
     jr, jd, h = _disorder_arrays(rows, cols, bool(periodic), float(coupling), 0.0, bias_mode, couplings, field)
     temperatures = np.asarray(temperatures, dtype=float)
     pt = LatticeTempering((rows, cols), temperatures, couplings=(jr, jd), field=h, periodic=periodic, seed=seed, initial=initial,
-                          ladders=replicas, cluster_moves=cluster_moves, cluster_max_temperature=cluster_max_temperature)
+                          ladders=replicas, cluster_moves=cluster_moves, cluster_max_temperature=cluster_max_temperature,
+                          correlation=correlation)
     return _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
 
 
@@ -1157,11 +1296,12 @@ class LatticeTempering3D(_LatticeTempering):
     """
 
     def __init__(self, size, temperatures, *, couplings=None, field=None, coupling: float = 1.0, external_field: float = 0.0,
-                 periodic=True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1):
+                 periodic=True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1, correlation: bool = False):
         self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
         self.n_spins = self.depth * self.rows * self.cols
         self._check_ladder(temperatures, ladders, initial)
         self.periodic = _hip.periodic_axes(periodic)
+        self._set_correlation(correlation)
         self._disorder = _tempering_disorder_3d(self.shape, self.periodic, float(coupling), float(external_field), couplings, field)
         self._start(_hip.TemperingLattice3D(self.depth, self.rows, self.cols, self.periodic, self.temperatures.size, self.ladders),
                     seed, initial)
@@ -1169,22 +1309,25 @@ class LatticeTempering3D(_LatticeTempering):
 
 def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                       measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", *, couplings=None, field=None,
-                      replicas: int = 1, swap: bool = True) -> dict:
+                      replicas: int = 1, swap: bool = True, correlation: bool = False) -> dict:
     """:func:`temperature_scan_3d` with replica exchange between the temperatures (:class:`LatticeTempering3D`).
 
     One round = ``measure_every`` sweeps of every walker + one swap pass; ``n_equilibrate`` (a multiple of ``measure_every``)
     sweeps of rounds, then ``n_measure`` recorded rounds.  Returns temperature_scan_3d's keys, computed with the same expressions
     from the walker at each temperature (``overlap``, ``overlap_sq``, ``binder`` for ``replicas=2``), plus ``swap_acceptance`` (per
     adjacent pair, ladders pooled) and ``round_trips`` (all walkers).  ``swap=False`` reproduces ``temperature_scan_3d`` with the
-    same arguments exactly.
+    same arguments exactly.  ``correlation=True``: ``chi_k``, ``xi`` and ``xi_over_L`` as for :func:`temperature_scan_3d`, from the
+    modes the ladder records on the device in every recorded round.
     """
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
     if int(measure_every) < 1 or int(n_equilibrate) % int(measure_every):
         raise ValueError("n_equilibrate must be a multiple of measure_every")
     shape = _shape_3d(size)
+    if correlation:
+        _check_correlation(_hip.periodic_axes(periodic))
     jr, jd, jl, h = _tempering_disorder_3d(shape, _hip.periodic_axes(periodic), float(coupling), 0.0, couplings, field)
     temperatures = np.asarray(temperatures, dtype=float)
     pt = LatticeTempering3D(shape, temperatures, couplings=(jr, jd, jl), field=h, periodic=periodic, seed=seed, initial=initial,
-                            ladders=replicas)
+                            ladders=replicas, correlation=correlation)
     return _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
