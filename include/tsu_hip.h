@@ -341,6 +341,10 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * prototypes are _hip.CORRELATION_SIGNATURES in Python. */
 #include "tsu_hip_correlation.h"
 
+/* K7 / K8: population annealing of disordered lattices with the resampling on the device (the tsu_pa2d and tsu_pa3d handles):
+ * declared in tsu_hip_population.h, which this header includes; its prototypes are _hip.POPULATION_SIGNATURES in Python. */
+#include "tsu_hip_population.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

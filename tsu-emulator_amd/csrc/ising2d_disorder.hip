@@ -34,6 +34,11 @@
 // final sums and q per slot (pt_energy_final, pt_overlap, reduce_dev.h) and the swap pass (k7_pt_swap, pt_dev.h).  This file
 // passes in how a half-sweep and an energy partial pass are launched, and the hook that ends a round's sweeps with the replica
 // cluster moves of ising2d_icm.hip (pt2d_icm_*).  The handle itself is declared in ising2d_pt.h.
+//
+// Population annealing (tsu_pa2d_*): R walkers on ONE disorder annealed along a schedule of inverse temperatures, resampled on the
+// device between the steps ("Population annealing").  The sweeps and the energies are k7_pt_sweep and
+// k7_pt_energy as they stand: every walker sits at slot 0 and the kernels get the schedule's tables offset by the step.  The
+// resampling kernels (pop_dev.h) and the host side (pop_host.h) do not know the dimension and are shared with ising3d.hip.
 #include <cmath>
 #include <cstdlib>
 #include <vector>
@@ -43,8 +48,14 @@
 #include "ising2d.h"
 #include "ising2d_pt.h"
 #include "corr_dev.h"
+#include "pop_host.h"
 #include "pt_host.h"
 #include "reduce_dev.h"
+
+// Population annealing: pop_host.h's population of K7 lattices, all planes in one allocation; `lat` owns the one disorder
+struct tsu_pa2d : pop_handle {
+    tsu_ising2d* lat;
+};
 
 namespace {
 
@@ -394,6 +405,47 @@ auto pt_partials(tsu_pt2d* P, const PTParams& p) {
     return [P, &p](unsigned blocks) { k7_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
 }
 
+void pa_free(tsu_pa2d* P) { pop_delete(P, tsu_ising2d_destroy); }
+
+// the ladders' parameters for a population: walker -> plane, key and slot 0; T / c32 are set per step
+PTParams pa_params(const tsu_pa2d* P) {
+    const tsu_ising2d* L = P->lat;
+    const size_t plane = (size_t)L->rows * L->pitch;
+    PTParams p;
+    p.s = P->d_s;
+    p.key = P->d_key;
+    p.slot = P->d_slot;
+    p.T = P->d_T;
+    p.c32 = P->d_c32;
+    p.jr = L->d_dis;
+    p.jd = L->d_dis ? L->d_dis + plane : nullptr;
+    p.h = L->d_dis ? L->d_dis + 2 * plane : nullptr;
+    p.pitch = (long long)L->pitch;
+    p.rows = L->rows;
+    p.cols = L->cols;
+    p.periodic = L->periodic;
+    p.nw = P->R;
+    p.W = pop_group(P);
+    p.hs = 0;
+    return p;
+}
+
+// half-sweep hs of every walker at step k's temperature / the energy partial pass: what pop_host.h's init and run take
+auto pa_sweep(tsu_pa2d* P, PTParams& p) {
+    const int nchunks = (P->lat->cols + 15) >> 4;
+    const dim3 grid((unsigned)((nchunks + 63) / 64), (unsigned)((P->lat->rows + 3) / 4), (unsigned)((P->R + p.W - 1) / p.W));
+    return [P, &p, grid](uint32_t hs, int colour, int k) {
+        p.hs = hs;
+        p.T = P->d_T + k;
+        p.c32 = P->d_c32 + k;
+        k7_pt_sweep<<<grid, dim3(64, 4, 1), 0, P->ctx->stream>>>(p, colour);
+    };
+}
+
+auto pa_partials(tsu_pa2d* P, const PTParams& p) {
+    return [P, &p](unsigned blocks) { k7_pt_energy<<<dim3(blocks, (unsigned)P->R, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
+}
+
 }  // namespace
 
 extern "C" {
@@ -676,6 +728,86 @@ int tsu_pt2d_profiles(tsu_pt2d* P, int slot, int64_t* p_row, int64_t* p_col) {
     if (!P) return TSU_E_INVALID;
     int64_t* out[2] = {p_row, p_col};
     return pt_profiles(P, slot, out);
+}
+
+// ------------------------------------------------------------------ population annealing
+int tsu_pa2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int population, tsu_pa2d** out) {
+    TSU_ENTER(ctx);
+    if (!ctx || !out) return TSU_E_INVALID;
+    return pop_create(
+        ctx, "pa2d", population, out,
+        [=](tsu_pa2d* P) {  // every whole lattice K7 takes
+            const int rc = tsu_ising2d_create(ctx, rows, cols, periodic, &P->lat);
+            if (rc != TSU_OK) return rc;
+            P->nrows = P->lat->rows;
+            P->pitch = (long long)P->lat->pitch;
+            P->cols = P->lat->cols;
+            return (int)TSU_OK;
+        },
+        pa_free);
+}
+
+int tsu_pa2d_destroy(tsu_pa2d* P) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_OK;
+    (void)hipStreamSynchronize(P->ctx->stream);
+    pa_free(P);
+    return TSU_OK;
+}
+
+int tsu_pa2d_set_disorder(tsu_pa2d* P, const float* J_right, const float* J_down, const float* h) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    P->have_E = 0;
+    return tsu_ising2d_set_disorder(P->lat, J_right, J_down, h);
+}
+
+int tsu_pa2d_set_schedule(tsu_pa2d* P, const double* betas, int n) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_set_schedule(P, betas, n) : TSU_E_INVALID;
+}
+
+int tsu_pa2d_init(tsu_pa2d* P, uint64_t seed, int initial_sweeps) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    PTParams p = pa_params(P);
+    return pop_init(P, P->lat->have_disorder, seed, initial_sweeps, pa_sweep(P, p), pa_partials(P, p));
+}
+
+int tsu_pa2d_run(tsu_pa2d* P, int n_steps, int sweeps_per_step, int resample, int record) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const int rc = pop_run_check(P, P->lat->have_disorder, n_steps, sweeps_per_step);
+    if (rc != TSU_OK) return rc;
+    PTParams p = pa_params(P);
+    return pop_run(P, n_steps, sweeps_per_step, resample, record, pa_sweep(P, p), pa_partials(P, p));
+}
+
+int tsu_pa2d_history(tsu_pa2d* P, double* E, int64_t* M, uint32_t* W, int32_t* parent, uint64_t* S, uint64_t* U, double* E_min) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_history(P, E, M, W, parent, S, U, E_min) : TSU_E_INVALID;
+}
+
+int tsu_pa2d_energies(tsu_pa2d* P, double* E, int64_t* sum_s) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const PTParams p = pa_params(P);
+    return pop_energies(P, P->lat->have_disorder, E, sum_s, pa_partials(P, p));
+}
+
+int tsu_pa2d_get_spins(tsu_pa2d* P, int i, int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_get_spins(P, i, host) : TSU_E_INVALID;
+}
+
+int tsu_pa2d_set_spins(tsu_pa2d* P, int i, const int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_set_spins(P, i, host) : TSU_E_INVALID;
+}
+
+int tsu_pa2d_launch_count(tsu_pa2d* P, uint64_t* n) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return pop_launch_count(P, n);
 }
 
 }  // extern "C"

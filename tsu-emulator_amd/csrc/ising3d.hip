@@ -53,12 +53,20 @@
 #include "ising2d.h"
 #include "ising3d.h"
 #include "corr_dev.h"
+#include "pop_host.h"
 #include "pt_host.h"
 #include "reduce_dev.h"
 
 // Parallel tempering: pt_ladder.h's ladder with whole K8 lattices as its walkers, the 3-D counterpart of tsu_pt2d
 struct tsu_pt3d : pt_ladder {
     tsu_ising3d** lat;  // walker g = ladder * R + w; lat[0] also holds the one disorder
+};
+
+// Population annealing: pop_host.h's population of K8 lattices, all planes in one allocation; `lat` owns the one disorder.  The
+// sweeps and the energies are k8_pt_sweep and k8_pt_energy as they stand (every walker at slot 0, the schedule's tables offset by the
+// step); the resampling kernels (pop_dev.h) are the 2-D populations' ("Population annealing")
+struct tsu_pa3d : pop_handle {
+    tsu_ising3d* lat;
 };
 
 namespace {
@@ -544,6 +552,52 @@ auto pt_partials(tsu_pt3d* P, const PT3Params& p) {
     return [P, &p](unsigned blocks) { k8_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
 }
 
+void pa_free(tsu_pa3d* P) { pop_delete(P, tsu_ising3d_destroy); }
+
+// the ladders' parameters for a population: walker -> plane, key and slot 0; T / c32 are set per step
+PT3Params pa_params(const tsu_pa3d* P) {
+    const K8Params k = make_params(P->lat);
+    PT3Params p;
+    p.s = P->d_s;
+    p.key = P->d_key;
+    p.slot = P->d_slot;
+    p.T = P->d_T;
+    p.c32 = P->d_c32;
+    p.jr = k.jr;
+    p.jd = k.jd;
+    p.jl = k.jl;
+    p.h = k.h;
+    p.pitch = k.pitch;
+    p.nrows = k.nrows;
+    p.depth = k.depth;
+    p.rows = k.rows;
+    p.cols = k.cols;
+    p.pz = k.pz;
+    p.pr = k.pr;
+    p.pc = k.pc;
+    p.lshift = k.lshift;
+    p.nw = P->R;
+    p.W = pop_group(P);
+    p.hs = 0;
+    return p;
+}
+
+// half-sweep hs of every walker at step k's temperature / the energy partial pass: what pop_host.h's init and run take
+auto pa_sweep(tsu_pa3d* P, PT3Params& p) {
+    const dim3 og = octet_grid(make_params(P->lat));
+    const dim3 grid(og.x, og.y, (unsigned)((P->R + p.W - 1) / p.W));
+    return [P, &p, grid](uint32_t hs, int colour, int k) {
+        p.hs = hs;
+        p.T = P->d_T + k;
+        p.c32 = P->d_c32 + k;
+        k8_pt_sweep<<<grid, 256, 0, P->ctx->stream>>>(p, colour);
+    };
+}
+
+auto pa_partials(tsu_pa3d* P, const PT3Params& p) {
+    return [P, &p](unsigned blocks) { k8_pt_energy<<<dim3(blocks, (unsigned)P->R, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
+}
+
 }  // namespace
 
 extern "C" {
@@ -922,6 +976,86 @@ int tsu_pt3d_profiles(tsu_pt3d* P, int slot, int64_t* p_z, int64_t* p_r, int64_t
     if (!P) return TSU_E_INVALID;
     int64_t* out[3] = {p_z, p_r, p_c};
     return pt_profiles(P, slot, out);
+}
+
+// ------------------------------------------------------------------ population annealing
+int tsu_pa3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_mask, int population, tsu_pa3d** out) {
+    TSU_ENTER(ctx);
+    if (!ctx || !out) return TSU_E_INVALID;
+    return pop_create(
+        ctx, "pa3d", population, out,
+        [=](tsu_pa3d* P) {
+            const int rc = tsu_ising3d_create(ctx, depth, rows, cols, periodic_mask, &P->lat);
+            if (rc != TSU_OK) return rc;
+            P->nrows = (long long)P->lat->depth * P->lat->rows;
+            P->pitch = (long long)P->lat->pitch;
+            P->cols = P->lat->cols;
+            return (int)TSU_OK;
+        },
+        pa_free);
+}
+
+int tsu_pa3d_destroy(tsu_pa3d* P) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_OK;
+    (void)hipStreamSynchronize(P->ctx->stream);
+    pa_free(P);
+    return TSU_OK;
+}
+
+int tsu_pa3d_set_disorder(tsu_pa3d* P, const float* J_right, const float* J_down, const float* J_layer, const float* h) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    P->have_E = 0;
+    return tsu_ising3d_set_disorder(P->lat, J_right, J_down, J_layer, h);
+}
+
+int tsu_pa3d_set_schedule(tsu_pa3d* P, const double* betas, int n) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_set_schedule(P, betas, n) : TSU_E_INVALID;
+}
+
+int tsu_pa3d_init(tsu_pa3d* P, uint64_t seed, int initial_sweeps) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    PT3Params p = pa_params(P);
+    return pop_init(P, P->lat->have_disorder, seed, initial_sweeps, pa_sweep(P, p), pa_partials(P, p));
+}
+
+int tsu_pa3d_run(tsu_pa3d* P, int n_steps, int sweeps_per_step, int resample, int record) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const int rc = pop_run_check(P, P->lat->have_disorder, n_steps, sweeps_per_step);
+    if (rc != TSU_OK) return rc;
+    PT3Params p = pa_params(P);
+    return pop_run(P, n_steps, sweeps_per_step, resample, record, pa_sweep(P, p), pa_partials(P, p));
+}
+
+int tsu_pa3d_history(tsu_pa3d* P, double* E, int64_t* M, uint32_t* W, int32_t* parent, uint64_t* S, uint64_t* U, double* E_min) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_history(P, E, M, W, parent, S, U, E_min) : TSU_E_INVALID;
+}
+
+int tsu_pa3d_energies(tsu_pa3d* P, double* E, int64_t* sum_s) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const PT3Params p = pa_params(P);
+    return pop_energies(P, P->lat->have_disorder, E, sum_s, pa_partials(P, p));
+}
+
+int tsu_pa3d_get_spins(tsu_pa3d* P, int i, int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_get_spins(P, i, host) : TSU_E_INVALID;
+}
+
+int tsu_pa3d_set_spins(tsu_pa3d* P, int i, const int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_set_spins(P, i, host) : TSU_E_INVALID;
+}
+
+int tsu_pa3d_launch_count(tsu_pa3d* P, uint64_t* n) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return pop_launch_count(P, n);
 }
 
 }  // extern "C"

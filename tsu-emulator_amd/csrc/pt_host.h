@@ -137,17 +137,18 @@ long long pt_lanes(const pt_ladder* P) { return P->nrows * ((P->cols + 15) / 16)
 // Walkers per lane of the ladder sweeps (k7_pt_sweep, k8_pt_sweep): the fewest groups that still give >= 1024 lanes per CU (a
 // lane per octet and group), so a large lattice reads each octet's disorder once for many walkers and a small one spreads its
 // walkers over the chip.  TSU_PT_GROUP=w (read per call) forces w.
-int pt_group(const pt_ladder* P) {
+int pt_group_of(const tsu_ctx* ctx, long long lanes, int nw) {
     if (const char* e = getenv("TSU_PT_GROUP")) {
         const int w = atoi(e);
-        if (w >= 1) return w < P->nw ? w : P->nw;
+        if (w >= 1) return w < nw ? w : nw;
     }
-    const long long lanes = pt_lanes(P);
-    const long long want = (long long)(P->ctx->cus > 0 ? P->ctx->cus : 256) * 1024;
+    const long long want = (long long)(ctx->cus > 0 ? ctx->cus : 256) * 1024;
     const long long groups = (want + lanes - 1) / lanes;
-    if (groups >= P->nw) return 1;
-    return (int)((P->nw + groups - 1) / groups);
+    if (groups >= nw) return 1;
+    return (int)((nw + groups - 1) / groups);
 }
+
+int pt_group(const pt_ladder* P) { return pt_group_of(P->ctx, pt_lanes(P), P->nw); }
 
 int pt_set_temperatures(pt_ladder* P, const double* T) {
     tsu_ctx* ctx = P->ctx;

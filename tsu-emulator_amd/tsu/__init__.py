@@ -31,6 +31,8 @@ from .models import (  # noqa: F401
     IsingModel2D,
     IsingModel3D,
     LatticeTempering3D,
+    PopulationAnnealing,
+    PopulationAnnealing3D,
     demonstrate_phase_transition,
     temperature_scan_3d,
     tempering_scan_3d,
@@ -42,4 +44,5 @@ __all__ = [
     "GibbsSampler", "GibbsConfig", "HardwareEmulator",
     "IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "demonstrate_phase_transition",
     "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d",
+    "PopulationAnnealing", "PopulationAnnealing3D",
 ]

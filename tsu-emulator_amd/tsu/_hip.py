@@ -182,6 +182,23 @@ CORRELATION_SIGNATURES = {
     "tsu_pt3d_profiles": (C.c_int, [_vp, C.c_int, _i64p, _i64p, _i64p]),
 }
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_population.h (the header tsu_hip.h includes) one to one
+POPULATION_SIGNATURES = {}
+for _pre, _shape, _nj in (("tsu_pa2d_", [C.c_int, C.c_int, C.c_int], 2), ("tsu_pa3d_", [C.c_int, C.c_int, C.c_int, C.c_int], 3)):
+    POPULATION_SIGNATURES.update({
+        _pre + "create": (C.c_int, [_vp] + _shape + [C.c_int, C.POINTER(_vp)]),
+        _pre + "destroy": (C.c_int, [_vp]),
+        _pre + "set_disorder": (C.c_int, [_vp] + [_f32p] * (_nj + 1)),
+        _pre + "set_schedule": (C.c_int, [_vp, _f64p, C.c_int]),
+        _pre + "init": (C.c_int, [_vp, C.c_uint64, C.c_int]),
+        _pre + "run": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        _pre + "history": (C.c_int, [_vp, _f64p, _i64p, _u32p, _i32p, _u64p, _u64p, _f64p]),
+        _pre + "energies": (C.c_int, [_vp, _f64p, _i64p]),
+        _pre + "get_spins": (C.c_int, [_vp, C.c_int, _i8p]),
+        _pre + "set_spins": (C.c_int, [_vp, C.c_int, _i8p]),
+        _pre + "launch_count": (C.c_int, [_vp, _u64p]),
+    })
+
 _lib = None
 
 
@@ -198,7 +215,8 @@ def load_library():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailableError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items())
+                              + list(POPULATION_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -731,6 +749,134 @@ class TemperingLattice3D(_TemperingHandle):
         self.shape = (self.depth, self.rows, self.cols)
         self.periodic = periodic_axes(periodic)
         self.n_temps, self.n_ladders = int(n_temps), int(n_ladders)
+        self._create(self.depth, self.rows, self.cols, sum(1 << a for a in range(3) if self.periodic[a]))
+
+    def set_disorder(self, J_right, J_down, J_layer, h=None):
+        self._set_disorder((J_right, J_down, J_layer), h)
+
+
+POPULATION_MAX = 65535
+
+
+class _PopulationHandle:
+    """What the tsu_pa2d and tsu_pa3d handles share: every call but create and set_disorder.  A subclass sets ``_prefix`` and, in
+    its constructor, ``shape`` and ``population``, then calls ``_create`` with the shape arguments of its create function."""
+
+    _prefix = None
+
+    def _fn(self, name):
+        return getattr(self.lib, self._prefix + name)
+
+    def _create(self, *shape_args):
+        self._recorded = None  # steps of the last run if it recorded
+        self.n_steps = None    # steps of the schedule
+        self.step_count = self.sweep_count = 0
+        self._beta0 = 0.0
+        self._resampled = False
+        h = _vp()
+        self.ctx.check(self._fn("create")(self.ctx.h, *shape_args, self.population, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._fn("destroy")(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def _set_disorder(self, arrays, h):
+        a = [np.ascontiguousarray(x, dtype=np.float32).reshape(self.shape) for x in arrays]
+        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float32).reshape(self.shape)
+        self.ctx.check(self._fn("set_disorder")(self.h, *[_ptr(x, _f32p) for x in a], None if hh is None else _ptr(hh, _f32p)))
+
+    def set_schedule(self, betas):
+        b = np.ascontiguousarray(betas, dtype=np.float64).ravel()
+        self.ctx.check(self._fn("set_schedule")(self.h, _ptr(b, _f64p), int(b.size)))
+        self.n_steps = int(b.size) - 1
+        self._beta0 = float(b[0])
+
+    def init(self, seed, initial_sweeps=0):
+        """Walker i: key seed + i and the lattice's randomize(seed + i); initial_sweeps sweeps at 1 / beta[0] if beta[0] > 0."""
+        self.ctx.check(self._fn("init")(self.h, int(seed), int(initial_sweeps)))
+        self._recorded = None
+        self.step_count = 0
+        self.sweep_count = int(initial_sweeps) if self._beta0 > 0 else 0
+
+    def run(self, n_steps, sweeps_per_step, resample=True, record=True):
+        self.ctx.check(self._fn("run")(self.h, int(n_steps), int(sweeps_per_step), int(bool(resample)), int(bool(record))))
+        self._recorded = int(n_steps) if record else None
+        self._resampled = bool(resample)
+        self.step_count += int(n_steps)
+        self.sweep_count += int(n_steps) * int(sweeps_per_step)
+
+    def history(self):
+        """The last run's rows: E, M (n + 1, R), row 0 the population the run started from; W (uint32), parent (int32) (n, R);
+        S, U (uint64), E_min (n,); resampled (n,) bool, whether that run resampled."""
+        if self._recorded is None:
+            raise ValueError("the last run recorded nothing")
+        n, R = self._recorded, self.population
+        out = {"E": np.zeros((n + 1, R)), "M": np.zeros((n + 1, R), np.int64), "W": np.zeros((n, R), np.uint32),
+               "parent": np.zeros((n, R), np.int32), "S": np.zeros(n, np.uint64), "U": np.zeros(n, np.uint64), "E_min": np.zeros(n)}
+        self.ctx.check(self._fn("history")(self.h, _ptr(out["E"], _f64p), _ptr(out["M"], _i64p), _ptr(out["W"], _u32p),
+                                           _ptr(out["parent"], _i32p), _ptr(out["S"], _u64p), _ptr(out["U"], _u64p),
+                                           _ptr(out["E_min"], _f64p)))
+        out["resampled"] = np.full(n, self._resampled)
+        return out
+
+    def energies(self):
+        """(E, sum of spins) of every walker now, by walker."""
+        E, M = np.zeros(self.population), np.zeros(self.population, np.int64)
+        self.ctx.check(self._fn("energies")(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
+        return E, M
+
+    def get_spins(self, i):
+        out = np.empty(self.shape, dtype=np.int8)
+        self.ctx.check(self._fn("get_spins")(self.h, int(i), _ptr(out, _i8p)))
+        return out
+
+    def set_spins(self, i, spins):
+        s = np.ascontiguousarray(spins, dtype=np.int8).reshape(self.shape)
+        self.ctx.check(self._fn("set_spins")(self.h, int(i), _ptr(s, _i8p)))
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self._fn("launch_count")(self.h, C.byref(n)))
+        return n.value
+
+
+class PopulationLattice(_PopulationHandle):
+    """tsu_pa2d handle (K7 population annealing): ``population`` walkers of one rows x cols lattice sharing one disorder.  Walker i
+    has Philox key seed + i."""
+
+    _prefix = "tsu_pa2d_"
+
+    def __init__(self, rows, cols, periodic, population, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.rows, self.cols, self.periodic = int(rows), int(cols), bool(periodic)
+        self.shape = (self.rows, self.cols)
+        self.population = int(population)
+        self._create(self.rows, self.cols, int(self.periodic))
+
+    def set_disorder(self, J_right, J_down, h=None):
+        self._set_disorder((J_right, J_down), h)
+
+
+class PopulationLattice3D(_PopulationHandle):
+    """tsu_pa3d handle (K8 population annealing): ``population`` walkers of one depth x rows x cols lattice sharing one disorder.
+    ``periodic``: a bool or a triple (p_z, p_r, p_c)."""
+
+    _prefix = "tsu_pa3d_"
+
+    def __init__(self, depth, rows, cols, periodic, population, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.depth, self.rows, self.cols = int(depth), int(rows), int(cols)
+        self.shape = (self.depth, self.rows, self.cols)
+        self.periodic = periodic_axes(periodic)
+        self.population = int(population)
         self._create(self.depth, self.rows, self.cols, sum(1 << a for a in range(3) if self.periodic[a]))
 
     def set_disorder(self, J_right, J_down, J_layer, h=None):

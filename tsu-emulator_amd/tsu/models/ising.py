@@ -1331,3 +1331,249 @@ def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: 
     pt = LatticeTempering3D(shape, temperatures, couplings=(jr, jd, jl), field=h, periodic=periodic, seed=seed, initial=initial,
                             ladders=replicas, correlation=correlation)
     return _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
+
+
+# ---------------------------------------------------------------------------------------------------- population annealing
+POPULATION_WEIGHT_ONE = 1 << 30  # the weight of a step's minimum-energy walker
+
+
+def _population_schedule(betas, temperatures) -> np.ndarray:
+    """The schedule as ascending inverse temperatures, from exactly one of ``betas`` (ascending, betas[0] >= 0) and ``temperatures``
+    (descending, ``inf`` allowed first), validated on the host."""
+    if (betas is None) == (temperatures is None):
+        raise ValueError("give exactly one of betas= (ascending) and temperatures= (descending)")
+    if betas is not None:
+        b = np.asarray(betas, dtype=float).ravel()
+    else:
+        T = np.asarray(temperatures, dtype=float).ravel()
+        if not np.all(T > 0):  # refuses NaN too
+            raise ValueError("Temperature must be positive")
+        b = 1.0 / T
+    if b.size < 2:
+        raise ValueError("population annealing needs at least two inverse temperatures (one step)")
+    if not np.all(np.isfinite(b)) or b[0] < 0:
+        raise ValueError("betas must be finite and >= 0")
+    if not np.all(np.diff(b) > 0):
+        raise ValueError("betas must increase (temperatures must decrease) along the schedule")
+    return b
+
+
+def _check_population(population) -> int:
+    if isinstance(population, bool) or not isinstance(population, (int, np.integer)) or not 2 <= population <= _hip.POPULATION_MAX:
+        raise ValueError(f"population must be an integer in [2, {_hip.POPULATION_MAX}], got {population!r}")
+    return int(population)
+
+
+def population_free_energy(betas, S, E_min, mean_E, population: int, n_spins: int) -> dict:
+    """The free-energy estimator of a recorded anneal.  Step j multiplies the partition function by Q_j with
+    ``ln Q_j = -db_j E_min_j + ln(S_j / (R 2^30))``; ``ln_Z[k] = N ln 2 + sum_{j <= k} ln Q_j`` when ``betas[0] == 0`` (the uniform
+    measure), else the difference ``ln Z(betas[k]) - ln Z(betas[0])``.  ``F = -ln_Z / beta`` and ``entropy = beta <E> + ln_Z`` (NaN
+    where beta[0] > 0 leaves only differences; F is NaN at beta = 0)."""
+    betas = np.asarray(betas, dtype=float)
+    db = np.diff(betas)
+    lnQ = -db * np.asarray(E_min, dtype=float) + np.log(np.asarray(S, dtype=float) / (float(population) * POPULATION_WEIGHT_ONE))
+    absolute = betas[0] == 0.0
+    ln_Z = np.concatenate([[0.0], np.cumsum(lnQ)]) + (n_spins * np.log(2.0) if absolute else 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        F = np.where(betas > 0, -ln_Z / betas, np.nan) if absolute else np.full(betas.size, np.nan)
+    entropy = betas * np.asarray(mean_E, dtype=float) + ln_Z if absolute else np.full(betas.size, np.nan)
+    return {"betas": betas, "ln_Q": lnQ, "ln_Z": ln_Z, "F": F, "entropy": entropy}
+
+
+def population_family_stats(parent) -> dict:
+    """Families by chaining ``parent`` (n_steps, R) from the first step: walker i of the start founds family i.  Per step (row 0: the
+    start) ``rho_t = R sum_f (n_f / R)^2``, ``rho_s = exp(-sum_f (n_f / R) ln(n_f / R))`` (Wang, Machta & Katzgraber 2015) and
+    ``families``, the number that survive."""
+    parent = np.asarray(parent)
+    R = parent.shape[1]
+    fam = np.arange(R)
+    rho_t, rho_s, alive = [1.0], [float(R)], [R]
+    for row in parent:
+        fam = fam[row]
+        p = np.bincount(fam, minlength=R)
+        p = p[p > 0] / float(R)
+        rho_t.append(float(R * np.sum(p * p)))
+        rho_s.append(float(np.exp(-np.sum(p * np.log(p)))))
+        alive.append(int(p.size))
+    return {"rho_t": np.array(rho_t), "rho_s": np.array(rho_s), "families": np.array(alive)}
+
+
+class _PopulationAnnealing:
+    """What :class:`PopulationAnnealing` and :class:`PopulationAnnealing3D` share: everything but the shape and the disorder.  A
+    subclass parses its shape, calls ``_check``, validates its disorder into ``self._disorder`` and hands its handle to ``_start``."""
+
+    def _check(self, population, betas, temperatures, sweeps_per_step, initial_sweeps):
+        self.population = _check_population(population)
+        self.betas = _population_schedule(betas, temperatures)
+        if int(sweeps_per_step) < 0 or int(initial_sweeps) < 0:
+            raise ValueError("sweeps_per_step and initial_sweeps must be >= 0")
+        self.sweeps_per_step, self.initial_sweeps = int(sweeps_per_step), int(initial_sweeps)
+
+    def _start(self, pa, seed):
+        self._pa = pa
+        self.seed = int(seed) if seed is not None else (
+            int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
+        pa.set_disorder(*self._disorder)
+        pa.set_schedule(self.betas)
+        pa.init(self.seed, self.initial_sweeps)
+        self._record = None    # the rows since init while every run recorded, else None
+        self._complete = True  # no run since init went unrecorded
+
+    @property
+    def n_steps(self) -> int:
+        """Steps of the schedule."""
+        return self.betas.size - 1
+
+    @property
+    def step_count(self) -> int:
+        return self._pa.step_count
+
+    @property
+    def sweep_count(self) -> int:
+        return self._pa.sweep_count
+
+    def run(self, n_steps: Optional[int] = None, resample: bool = True, record: bool = True):
+        """``n_steps`` further steps of the schedule (default: all that are left); with ``record`` returns ``history()``."""
+        left = self.n_steps - self.step_count
+        n = left if n_steps is None else int(n_steps)
+        if not 0 <= n <= left:
+            raise ValueError(f"n_steps = {n} runs past the schedule ({left} of {self.n_steps} steps left)")
+        self._pa.run(n, self.sweeps_per_step, resample, record)
+        if not record:
+            self._complete, self._record = False, None
+            return None
+        h = self._pa.history()
+        if self._complete:
+            if self._record is None:
+                self._record = h
+            else:  # row 0 of a later run repeats the last row of the one before
+                r = self._record
+                self._record = {k: np.concatenate([r[k], h[k][1:] if k in ("E", "M") else h[k]]) for k in h}
+        return self.history()
+
+    def history(self) -> dict:
+        """Every step since the start, if every run recorded (else the last run's steps): ``E`` (float64), ``M`` (int64 sum of spins)
+        as (n + 1, R) arrays by walker index, row 0 the start; ``W`` (uint32 weights), ``parent`` (int32) (n, R); ``S``, ``U``
+        (uint64), ``E_min`` (n,); ``resampled`` (n,) bool.  Steps taken with ``resample=False`` have ``parent`` = identity and zeros in
+        ``W``, ``S``, ``U``, ``E_min``."""
+        if self._complete and self._record is not None:
+            return dict(self._record)
+        return self._pa.history()
+
+    def _full_record(self, what):
+        if not (self._complete and self._record is not None):
+            raise ValueError(f"{what} needs the record of every step since the start: run with record=True throughout")
+        return self._record
+
+    def free_energy(self) -> dict:
+        """``ln_Z``, ``F`` and ``entropy`` at every recorded beta (:func:`population_free_energy`); needs resampled steps."""
+        r = self._full_record("free_energy")
+        if not np.all(r["resampled"]):
+            raise ValueError("free_energy needs resampled steps (run(resample=True))")
+        k = r["S"].size
+        return population_free_energy(self.betas[:k + 1], r["S"], r["E_min"], r["E"].mean(axis=1), self.population, self.n_spins)
+
+    def observables(self) -> dict:
+        """Population means per recorded beta: ``energy`` (<E>), ``energy_sq``, ``abs_magnetization`` (<|M|> / N),
+        ``magnetization_sq`` (<M^2> / N^2), with ``betas``."""
+        r = self._full_record("observables")
+        m = r["M"] / float(self.n_spins)
+        return {"betas": self.betas[:r["E"].shape[0]], "energy": r["E"].mean(axis=1), "energy_sq": (r["E"] ** 2).mean(axis=1),
+                "abs_magnetization": np.abs(m).mean(axis=1), "magnetization_sq": (m ** 2).mean(axis=1)}
+
+    def family_stats(self) -> dict:
+        """``rho_t``, ``rho_s`` and ``families`` per recorded beta (:func:`population_family_stats`)."""
+        return population_family_stats(self._full_record("family_stats")["parent"])
+
+    def spins(self, i: int) -> np.ndarray:
+        """Spins of walker ``i``, in the lattice's shape."""
+        if not 0 <= i < self.population:
+            raise ValueError(f"walker {i} out of range (population {self.population})")
+        return self._pa.get_spins(i)
+
+    def energies(self) -> np.ndarray:
+        """Every walker's energy now (the device's fixed-order float64 sums)."""
+        return self._pa.energies()[0]
+
+
+class PopulationAnnealing(_PopulationAnnealing):
+    """Population annealing of a disordered lattice on the GPU (K7, physical mode; Hukushima & Iba 2003, Machta 2010).
+
+    ``population`` walkers (2 ... 65535) share one quenched disorder, ``couplings=(J_right, J_down)`` and ``field`` as for
+    :class:`IsingModel2D` or the uniform ``coupling`` / ``external_field``, validated and rounded to float32 before any device call.
+    The schedule is exactly one of ``betas`` (ascending, first >= 0) and ``temperatures`` (descending, ``inf`` allowed first).
+    Walker i is ``IsingModel2D(seed=seed + i)``: same Philox key, initial draw and sweep counter; a first beta of 0 makes that draw
+    the equilibrium start, a larger one takes ``initial_sweeps`` sweeps there.  Each step reweights the population from beta[k-1]
+    to beta[k] by systematic resampling at fixed size with 30-bit integer weights (walkers lighter than 2^-31 of the step's
+    heaviest are dropped), copies the planes of the walkers that multiply over those that die, sweeps every walker
+    ``sweeps_per_step`` times at 1 / beta[k] and computes every energy, all on the device without a host synchronisation.
+    ``run(resample=False)`` anneals the walkers independently (the single lattices, bit for bit).  From the record:
+    ``free_energy()``, ``observables()`` and ``family_stats()``.  Fixed population, one GPU, fixed schedule.
+    """
+
+    def __init__(self, size, population, *, betas=None, temperatures=None, couplings=None, field=None, coupling: float = 1.0,
+                 external_field: float = 0.0, periodic: bool = True, seed: Optional[int] = None, sweeps_per_step: int = 10,
+                 initial_sweeps: int = 0):
+        self.rows, self.cols = (size, size) if np.isscalar(size) else tuple(size)
+        self.n_spins = self.rows * self.cols
+        self._check(population, betas, temperatures, sweeps_per_step, initial_sweeps)
+        self.periodic = bool(periodic)
+        self._disorder = _disorder_arrays(self.rows, self.cols, self.periodic, float(coupling), float(external_field), "physical",
+                                          couplings, field)
+        self._start(_hip.PopulationLattice(self.rows, self.cols, self.periodic, self.population), seed)
+
+
+class PopulationAnnealing3D(_PopulationAnnealing):
+    """Population annealing of a disordered cubic lattice on the GPU (K8): :class:`PopulationAnnealing` for the lattices of
+    :class:`IsingModel3D` (``couplings=(J_right, J_down, J_layer)``; ``periodic`` a bool or a triple (p_z, p_r, p_c)).  Walker i is
+    ``IsingModel3D(seed=seed + i)``."""
+
+    def __init__(self, size, population, *, betas=None, temperatures=None, couplings=None, field=None, coupling: float = 1.0,
+                 external_field: float = 0.0, periodic=True, seed: Optional[int] = None, sweeps_per_step: int = 10,
+                 initial_sweeps: int = 0):
+        self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
+        self.n_spins = self.depth * self.rows * self.cols
+        self._check(population, betas, temperatures, sweeps_per_step, initial_sweeps)
+        self.periodic = _hip.periodic_axes(periodic)
+        self._disorder = _tempering_disorder_3d(self.shape, self.periodic, float(coupling), float(external_field), couplings, field)
+        self._start(_hip.PopulationLattice3D(self.depth, self.rows, self.cols, self.periodic, self.population), seed)
+
+
+def _population_scan(pa) -> dict:
+    """The body of the population scans on a fresh population ``pa``, closed at the end: the whole schedule, then
+    temperature_scan's keys per temperature from the population at that temperature, plus ``ln_Z``, ``rho_t`` and ``rho_s``."""
+    try:
+        h = pa.run()
+        N = pa.n_spins
+        with np.errstate(divide="ignore"):
+            temperatures = 1.0 / pa.betas
+        out = {k: np.zeros(temperatures.size) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
+        out["temperatures"] = temperatures
+        out = _scan_summary(out, N, h["M"] / float(N), h["E"])
+        out["betas"] = pa.betas.copy()
+        out["ln_Z"] = pa.free_energy()["ln_Z"]
+        fam = pa.family_stats()
+        out["rho_t"], out["rho_s"] = fam["rho_t"], fam["rho_s"]
+    finally:
+        pa._pa.close()
+    return out
+
+
+def population_annealing_scan(size, population, *, betas=None, temperatures=None, coupling: float = 1.0, couplings=None, field=None,
+                              external_field: float = 0.0, periodic: bool = True, seed: int = 0, sweeps_per_step: int = 10,
+                              initial_sweeps: int = 0) -> dict:
+    """:func:`temperature_scan`'s keys (``temperatures``, ``magnetization``, ``energy``, ``susceptibility``, ``specific_heat``) per
+    temperature of the schedule, as population means of one :class:`PopulationAnnealing` run, plus ``betas``, ``ln_Z`` (differences
+    from the first beta unless it is 0), ``rho_t`` and ``rho_s``."""
+    return _population_scan(PopulationAnnealing(size, population, betas=betas, temperatures=temperatures, couplings=couplings,
+                                                field=field, coupling=coupling, external_field=external_field, periodic=periodic,
+                                                seed=seed, sweeps_per_step=sweeps_per_step, initial_sweeps=initial_sweeps))
+
+
+def population_annealing_scan_3d(size, population, *, betas=None, temperatures=None, coupling: float = 1.0, couplings=None,
+                                 field=None, external_field: float = 0.0, periodic=True, seed: int = 0, sweeps_per_step: int = 10,
+                                 initial_sweeps: int = 0) -> dict:
+    """:func:`population_annealing_scan` for the cubic lattices of :class:`PopulationAnnealing3D`."""
+    return _population_scan(PopulationAnnealing3D(size, population, betas=betas, temperatures=temperatures, couplings=couplings,
+                                                  field=field, coupling=coupling, external_field=external_field, periodic=periodic,
+                                                  seed=seed, sweeps_per_step=sweeps_per_step, initial_sweeps=initial_sweeps))
