@@ -345,6 +345,10 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * declared in tsu_hip_population.h, which this header includes; its prototypes are _hip.POPULATION_SIGNATURES in Python. */
 #include "tsu_hip_population.h"
 
+/* K7 / K8: the link overlap of two replicas (lattice pairs, two-ladder tempering handles) and the overlaps of a population's walker
+ * pairs: declared in tsu_hip_overlap.h, which this header includes; its prototypes are _hip.OVERLAP_SIGNATURES in Python. */
+#include "tsu_hip_overlap.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

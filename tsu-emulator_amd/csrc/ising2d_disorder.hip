@@ -23,7 +23,8 @@
 //
 // k7_energy + energy_final: E = -sum_bonds J s s' - sum h s in float64, per-workgroup partials then one workgroup summing them in
 // a fixed order (the same bits on every call).  k7_overlap: q = sum s^a s^b (integer, vector atomics).  The workgroup sums, the
-// final sums and the pair lane are reduce_dev.h's, shared with K8.
+// final sums and the pair lane are reduce_dev.h's, shared with K8; the link overlap (tsu_ising2d_link_overlap, the ladders' and the
+// populations' rows) is link_dev.h's, a 2-D lattice being its one-layer case.
 //
 // Parallel tempering (tsu_pt2d_*): ladders of R walkers on ONE disorder ("Parallel tempering (K7)").
 // k7_pt_sweep is k7_sweep for a group of W walkers per lane: the octet's disorder is loaded once and every walker of the group
@@ -48,6 +49,7 @@
 #include "ising2d.h"
 #include "ising2d_pt.h"
 #include "corr_dev.h"
+#include "link_dev.h"
 #include "pop_host.h"
 #include "pt_host.h"
 #include "reduce_dev.h"
@@ -584,6 +586,30 @@ int tsu_ising2d_profiles(tsu_ising2d* A, tsu_ising2d* B, int64_t* p_row, int64_t
     return rc != TSU_OK || !B ? rc : ising2d_check_err(B);
 }
 
+int tsu_ising2d_link_overlap(tsu_ising2d* A, tsu_ising2d* B, int64_t* Lout, int64_t* n_bonds) {
+    TSU_ENTER(A ? A->ctx : nullptr);
+    if (!A || !B) return TSU_E_INVALID;
+    tsu_ctx* ctx = A->ctx;
+    TSU_REQUIRE(ctx, Lout && n_bonds, "ising2d_link_overlap: NULL output");
+    TSU_REQUIRE(ctx, B->ctx == ctx, "ising2d_link_overlap: the two lattices belong to different contexts");
+    if (!whole_lattice(A) || !whole_lattice(B)) return tsu_fail(ctx, TSU_E_UNSUPPORTED, "ising2d_link_overlap: whole lattices only (not slabs)");
+    TSU_REQUIRE(ctx, A->rows == B->rows && A->cols == B->cols, "ising2d_link_overlap: shapes differ (%d x %d against %d x %d)", A->rows,
+                A->cols, B->rows, B->cols);
+    TSU_REQUIRE(ctx, A->periodic == B->periodic, "ising2d_link_overlap: one lattice is periodic and the other is open");
+    LinkArgs la;
+    const unsigned blocks = link_plan(la, (long long)A->pitch, (long long)B->pitch, A->rows, A->rows, A->cols, 0, A->periodic, A->periodic);
+    TSU_HIP_TRY(ctx, hipMemsetAsync(A->d_obs, 0, sizeof(int64_t), ctx->stream));
+    link_pass<<<blocks, 256, 0, ctx->stream>>>(A->alloc[A->cur], B->alloc[B->cur], la, (long long*)A->d_obs);
+    TSU_HIP_TRY(ctx, hipGetLastError());
+    int64_t h = 0;
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(&h, A->d_obs, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *Lout = h;
+    *n_bonds = link_bonds(1, A->rows, A->cols, 0, A->periodic, A->periodic);
+    const int rc = ising2d_check_err(A);
+    return rc != TSU_OK ? rc : ising2d_check_err(B);
+}
+
 int tsu_ising2d_disorder_launch_count(tsu_ising2d* L, uint64_t* n) {
     TSU_ENTER(L ? L->ctx : nullptr);
     if (!L || !n) return TSU_E_INVALID;
@@ -730,6 +756,16 @@ int tsu_pt2d_profiles(tsu_pt2d* P, int slot, int64_t* p_row, int64_t* p_col) {
     return pt_profiles(P, slot, out);
 }
 
+int tsu_pt2d_set_link_overlap(tsu_pt2d* P, int enable) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_set_link_overlap(P, enable) : TSU_E_INVALID;
+}
+
+int tsu_pt2d_history_link(tsu_pt2d* P, int64_t* L) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history_link(P, L) : TSU_E_INVALID;
+}
+
 // ------------------------------------------------------------------ population annealing
 int tsu_pa2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int population, tsu_pa2d** out) {
     TSU_ENTER(ctx);
@@ -742,6 +778,11 @@ int tsu_pa2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int populati
             P->nrows = P->lat->rows;
             P->pitch = (long long)P->lat->pitch;
             P->cols = P->lat->cols;
+            P->n_axes = 2;
+            P->lrows = P->lat->rows;
+            P->axis_len[0] = P->lat->rows;
+            P->axis_len[1] = P->lat->cols;
+            P->axis_per[0] = P->axis_per[1] = P->lat->periodic;
             return (int)TSU_OK;
         },
         pa_free);
@@ -808,6 +849,19 @@ int tsu_pa2d_set_spins(tsu_pa2d* P, int i, const int8_t* host) {
 int tsu_pa2d_launch_count(tsu_pa2d* P, uint64_t* n) {
     TSU_ENTER(P ? P->ctx : nullptr);
     return pop_launch_count(P, n);
+}
+
+int tsu_pa2d_set_overlap(tsu_pa2d* P, int enable, const double* cos_row, const double* sin_row, const double* cos_col, const double* sin_col) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const double* cs[2] = {cos_row, cos_col};
+    const double* sn[2] = {sin_row, sin_col};
+    return pop_set_overlap(P, enable, cs, sn);
+}
+
+int tsu_pa2d_history_overlap(tsu_pa2d* P, int64_t* q, int64_t* L, double* modes) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_history_overlap(P, q, L, modes) : TSU_E_INVALID;
 }
 
 }  // extern "C"

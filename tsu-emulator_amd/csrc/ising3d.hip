@@ -806,6 +806,24 @@ int tsu_ising3d_overlap(tsu_ising3d* A, tsu_ising3d* B, int64_t* q) {
     return read_acc(A, q);
 }
 
+int tsu_ising3d_link_overlap(tsu_ising3d* A, tsu_ising3d* B, int64_t* Lout, int64_t* n_bonds) {
+    TSU_ENTER(A ? A->ctx : nullptr);
+    if (!A || !B) return TSU_E_INVALID;
+    tsu_ctx* ctx = A->ctx;
+    TSU_REQUIRE(ctx, Lout && n_bonds, "ising3d_link_overlap: NULL output");
+    TSU_REQUIRE(ctx, B->ctx == ctx, "ising3d_link_overlap: the two lattices belong to different contexts");
+    TSU_REQUIRE(ctx, A->depth == B->depth && A->rows == B->rows && A->cols == B->cols,
+                "ising3d_link_overlap: shapes differ (%d x %d x %d against %d x %d x %d)", A->depth, A->rows, A->cols, B->depth, B->rows,
+                B->cols);
+    TSU_REQUIRE(ctx, A->pz == B->pz && A->pr == B->pr && A->pc == B->pc, "ising3d_link_overlap: the periodic axes of the two lattices differ");
+    LinkArgs la;
+    const unsigned blocks = link_plan(la, (long long)A->pitch, (long long)B->pitch, (long long)A->depth * A->rows, A->rows, A->cols, A->pz, A->pr, A->pc);
+    TSU_HIP_TRY(ctx, hipMemsetAsync(A->d_acc, 0, sizeof(long long), ctx->stream));
+    link_pass<<<blocks, 256, 0, ctx->stream>>>(A->s, B->s, la, A->d_acc);
+    *n_bonds = link_bonds(A->depth, A->rows, A->cols, A->pz, A->pr, A->pc);
+    return read_acc(A, Lout);
+}
+
 int tsu_ising3d_profiles(tsu_ising3d* A, tsu_ising3d* B, int64_t* p_z, int64_t* p_r, int64_t* p_c) {
     TSU_ENTER(A ? A->ctx : nullptr);
     if (!A) return TSU_E_INVALID;
@@ -978,6 +996,16 @@ int tsu_pt3d_profiles(tsu_pt3d* P, int slot, int64_t* p_z, int64_t* p_r, int64_t
     return pt_profiles(P, slot, out);
 }
 
+int tsu_pt3d_set_link_overlap(tsu_pt3d* P, int enable) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_set_link_overlap(P, enable) : TSU_E_INVALID;
+}
+
+int tsu_pt3d_history_link(tsu_pt3d* P, int64_t* L) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history_link(P, L) : TSU_E_INVALID;
+}
+
 // ------------------------------------------------------------------ population annealing
 int tsu_pa3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_mask, int population, tsu_pa3d** out) {
     TSU_ENTER(ctx);
@@ -990,6 +1018,14 @@ int tsu_pa3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_ma
             P->nrows = (long long)P->lat->depth * P->lat->rows;
             P->pitch = (long long)P->lat->pitch;
             P->cols = P->lat->cols;
+            P->n_axes = 3;
+            P->lrows = P->lat->rows;
+            P->axis_len[0] = P->lat->depth;
+            P->axis_len[1] = P->lat->rows;
+            P->axis_len[2] = P->lat->cols;
+            P->axis_per[0] = P->lat->pz;
+            P->axis_per[1] = P->lat->pr;
+            P->axis_per[2] = P->lat->pc;
             return (int)TSU_OK;
         },
         pa_free);
@@ -1056,6 +1092,20 @@ int tsu_pa3d_set_spins(tsu_pa3d* P, int i, const int8_t* host) {
 int tsu_pa3d_launch_count(tsu_pa3d* P, uint64_t* n) {
     TSU_ENTER(P ? P->ctx : nullptr);
     return pop_launch_count(P, n);
+}
+
+int tsu_pa3d_set_overlap(tsu_pa3d* P, int enable, const double* cos_z, const double* sin_z, const double* cos_r, const double* sin_r,
+                         const double* cos_c, const double* sin_c) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const double* cs[3] = {cos_z, cos_r, cos_c};
+    const double* sn[3] = {sin_z, sin_r, sin_c};
+    return pop_set_overlap(P, enable, cs, sn);
+}
+
+int tsu_pa3d_history_overlap(tsu_pa3d* P, int64_t* q, int64_t* L, double* modes) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pop_history_overlap(P, q, L, modes) : TSU_E_INVALID;
 }
 
 }  // extern "C"

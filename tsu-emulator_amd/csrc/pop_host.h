@@ -8,6 +8,10 @@
 // Memory: all R spin planes are one allocation (R nrows pitch bytes) with a device table of the planes' addresses beside it; the
 // energy partials keep the kernels' fixed stride of kEnergyBlocks per walker (16 KiB per walker for E and sum of spins together,
 // 1 GiB at R = 65535).
+//
+// Overlaps of walker pairs (set_overlap; DESIGN.md section 3, "Overlaps of walker pairs"): the pairs are (i, i + P), P = R / 2, and the
+// ladders' passes compute them as they stand: pt_overlap, pt_link, pt_profile and pt_modes find their two planes as
+// s[was[i]] and s[R' + was[R' + i]], so with R' := P and the table was = (0 .. P - 1, 0 .. P - 1) they read walkers i and P + i.
 #pragma once
 #include <cmath>
 #include <new>
@@ -54,13 +58,24 @@ struct pop_handle {
     unsigned long long* d_hU;
     double* d_hEmin;
     uint32_t key0, key1;           // Philox key of the resampling offset (the seed)
+    // overlaps of the walker pairs: the lattice's axes as the handle's create fills them in, then what set_overlap adds
+    int n_axes, lrows;             // axes (2 or 3) and the rows of a layer (2-D: nrows)
+    int axis_len[3], axis_per[3];  // length and periodic flag per axis, in axis order
+    int ovl, ovl_modes;            // a recording run also records q and L per pair / and the k_min modes
+    int hist_ovl, hist_ovl_modes;  // the last run's rows have them
+    int32_t* d_was;                // [2][P] -> 0 .. P - 1: the slot table that makes the ladders' passes read the pairs
+    long long* d_prof;             // [pair][sum of axis_len] profile scratch
+    double* d_tab;                 // per periodic axis, in axis order: cos[len], sin[len]
+    long long* d_hq;               // [step + 1][pair]
+    long long* d_hL;
+    double* d_hF;                  // [step + 1][pair][periodic axis][re, im]
     std::vector<double> beta;      // host copy of the schedule
 };
 
 namespace {
 
 void pop_free_history(pop_handle* P) {
-    void* bufs[] = {P->d_hE, P->d_hM, P->d_hW, P->d_hP, P->d_hS, P->d_hU, P->d_hEmin};
+    void* bufs[] = {P->d_hE, P->d_hM, P->d_hW, P->d_hP, P->d_hS, P->d_hU, P->d_hEmin, P->d_hq, P->d_hL, P->d_hF};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     P->d_hE = nullptr;
@@ -70,6 +85,9 @@ void pop_free_history(pop_handle* P) {
     P->d_hS = nullptr;
     P->d_hU = nullptr;
     P->d_hEmin = nullptr;
+    P->d_hq = nullptr;
+    P->d_hL = nullptr;
+    P->d_hF = nullptr;
     P->hist_cap = 0;
 }
 
@@ -77,7 +95,7 @@ void pop_free_history(pop_handle* P) {
 template <class H, class Destroy>
 void pop_delete(H* P, Destroy destroy) {
     void* bufs[] = {P->d_pool, P->d_s, P->d_key, P->d_slot, P->d_T, P->d_c32, P->d_part, P->d_ipart, P->d_E,
-                    P->d_M, P->d_W, P->d_parent, P->d_xs, P->d_dead, P->d_pairs, P->d_npairs};
+                    P->d_M, P->d_W, P->d_parent, P->d_xs, P->d_dead, P->d_pairs, P->d_npairs, P->d_was, P->d_prof, P->d_tab};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     pop_free_history(P);
@@ -269,7 +287,7 @@ int pop_run_check(pop_handle* P, int have_disorder, int n_steps, int sweeps_per_
 template <class Sweep, class Partials>
 int pop_run(pop_handle* P, int n_steps, int theta, int resample, int record, Sweep&& sweep, Partials&& partials) {
     tsu_ctx* ctx = P->ctx;
-    const size_t R = (size_t)P->R, n = (size_t)n_steps;
+    const size_t R = (size_t)P->R, n = (size_t)n_steps, np = R / 2;
     if (record && (P->hist_cap < n || !P->d_hE)) {
         pop_free_history(P);
         const size_t cap = n ? n : 1;
@@ -280,6 +298,9 @@ int pop_run(pop_handle* P, int n_steps, int theta, int resample, int record, Swe
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hS, cap * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hU, cap * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hEmin, cap * sizeof(double));
+        if (e == hipSuccess && P->ovl) e = hipMalloc((void**)&P->d_hq, (cap + 1) * np * sizeof(long long));
+        if (e == hipSuccess && P->ovl) e = hipMalloc((void**)&P->d_hL, (cap + 1) * np * sizeof(long long));
+        if (e == hipSuccess && P->ovl_modes) e = hipMalloc((void**)&P->d_hF, (cap + 1) * np * pt_mode_doubles(P) * sizeof(double));
         if (e != hipSuccess) {  // nothing of a history that does not fit stays behind
             pop_free_history(P);
             P->hist_steps = 0;
@@ -291,6 +312,37 @@ int pop_run(pop_handle* P, int n_steps, int theta, int resample, int record, Swe
     }
     P->hist_steps = record ? n_steps : -1;
     P->hist_resampled = record && resample;
+    P->hist_ovl = record && P->ovl;
+    P->hist_ovl_modes = record && P->ovl_modes;
+    // the overlap rows of this run: pt_overlap and pt_link add into theirs, so q and L start at 0
+    LinkArgs la;
+    ProfArgs pa;
+    ModeArgs ma = {};
+    const unsigned lblocks = pt_link_plan(P, la), oblocks = reduce_blocks(pop_lanes(P));
+    const dim3 pgrid = profile_plan(pa, P->pitch, P->pitch, P->nrows, P->lrows, P->cols, P->n_axes == 3, (unsigned)np);
+    const long long plen = pt_prof_len(P);
+    const size_t md = pt_mode_doubles(P);
+    if (P->hist_ovl) {
+        TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hq, 0, (n + 1) * np * sizeof(long long), ctx->stream));
+        TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hL, 0, (n + 1) * np * sizeof(long long), ctx->stream));
+        if (P->hist_ovl_modes) ma = pt_mode_args(P);
+    }
+    // row `row` of the overlap record from the planes as they are (asynchronous)
+    auto overlaps = [&](size_t row) -> int {
+        pt_overlap<<<dim3(oblocks, (unsigned)np, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, (int)np, P->pitch, P->nrows, P->cols,
+                                                                           P->d_hq + row * np);
+        pt_link<<<dim3(lblocks, (unsigned)np, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, (int)np, la, P->d_hL + row * np);
+        if (P->hist_ovl_modes) {
+            TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_prof, 0, np * (size_t)plen * sizeof(long long), ctx->stream));
+            pt_profile<<<pgrid, 256, 0, ctx->stream>>>(P->d_s, P->d_was, (int)np, 2, pa, P->d_prof, plen);
+            pt_modes<<<dim3(2u * (unsigned)ma.n, (unsigned)np, 1), 256, 0, ctx->stream>>>(P->d_prof, plen, ma, P->d_hF + row * np * md);
+        }
+        return TSU_OK;
+    };
+    if (P->hist_ovl) {
+        const int rc = overlaps(0);
+        if (rc != TSU_OK) return rc;
+    }
     if (!P->have_E) {  // the planes or the disorder changed since the last pass
         pop_enqueue_energies(P, partials, P->d_E, P->d_M);
         P->have_E = 1;
@@ -339,6 +391,10 @@ int pop_run(pop_handle* P, int n_steps, int theta, int resample, int record, Swe
         pop_enqueue_energies(P, partials, E, record ? P->d_hM + (j + 1) * R : P->d_M);
         curE = E;
         P->step += 1;
+        if (P->hist_ovl) {
+            const int rc = overlaps(j + 1);
+            if (rc != TSU_OK) return rc;
+        }
     }
     if (record && n) {  // between runs the current energies live in d_E / d_M
         TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_E, P->d_hE + n * R, R * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -363,6 +419,87 @@ int pop_history(pop_handle* P, double* E, int64_t* M, uint32_t* W, int32_t* pare
         if (U) TSU_HIP_TRY(ctx, hipMemcpyAsync(U, P->d_hU, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         if (Emin) TSU_HIP_TRY(ctx, hipMemcpyAsync(Emin, P->d_hEmin, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     }
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSU_OK;
+}
+
+// set_overlap: cs[a] / sn[a] = the host's cos / sin tables of axis a (all NULL: q and L only; else both NULL exactly on an open
+// axis).  Switching it on, or changing whether the modes are recorded, drops the recorded history (its buffers gain the overlap rows
+// with the next run); a buffer that does not fit leaves the handle as it was (synchronises)
+int pop_set_overlap(pop_handle* P, int enable, const double* const* cs, const double* const* sn) {
+    tsu_ctx* ctx = P->ctx;
+    if (!enable) {
+        P->ovl = P->ovl_modes = 0;
+        return TSU_OK;
+    }
+    int given = 0;
+    for (int a = 0; a < P->n_axes; ++a) given += (cs[a] || sn[a]) ? 1 : 0;
+    size_t ntab = 0;
+    if (given) {
+        TSU_REQUIRE(ctx, pt_periodic_axes(P) > 0, "%s_set_overlap: the lattice has no periodic axis (no k_min mode is defined)", P->name);
+        for (int a = 0; a < P->n_axes; ++a) {
+            if (P->axis_per[a]) {
+                TSU_REQUIRE(ctx, cs[a] && sn[a], "%s_set_overlap: NULL table of periodic axis %d", P->name, a);
+                ntab += 2 * (size_t)P->axis_len[a];
+            } else {
+                TSU_REQUIRE(ctx, !cs[a] && !sn[a], "%s_set_overlap: axis %d is open: its tables must be NULL", P->name, a);
+            }
+        }
+    }
+    const size_t np = (size_t)P->R / 2;
+    int32_t* was = nullptr;
+    long long* prof = nullptr;
+    double* tab = nullptr;
+    hipError_t e = hipSuccess;
+    if (!P->d_was) e = hipMalloc((void**)&was, 2 * np * sizeof(int32_t));
+    if (e == hipSuccess && given && !P->d_prof) e = hipMalloc((void**)&prof, np * (size_t)pt_prof_len(P) * sizeof(long long));
+    if (e == hipSuccess && given && !P->d_tab) e = hipMalloc((void**)&tab, ntab * sizeof(double));
+    if (e != hipSuccess) {  // nothing of this call stays behind
+        void* bufs[] = {was, prof, tab};
+        for (void* b : bufs)
+            if (b) (void)hipFree(b);
+        (void)hipGetLastError();
+        return tsu_fail(ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP, "%s_set_overlap: scratch of %zu pairs: %s", P->name, np,
+                        hipGetErrorString(e));
+    }
+    if (was) P->d_was = was;
+    if (prof) P->d_prof = prof;
+    if (tab) P->d_tab = tab;
+    std::vector<int32_t> ident(2 * np);
+    for (size_t i = 0; i < 2 * np; ++i) ident[i] = (int32_t)(i % np);
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(P->d_was, ident.data(), ident.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    if (given) {
+        double* t = P->d_tab;
+        for (int a = 0; a < P->n_axes; ++a)
+            if (P->axis_per[a]) {
+                const size_t len = (size_t)P->axis_len[a];
+                TSU_HIP_TRY(ctx, hipMemcpyAsync(t, cs[a], len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+                TSU_HIP_TRY(ctx, hipMemcpyAsync(t + len, sn[a], len * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+                t += 2 * len;
+            }
+    }
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // before `ident` and the caller's tables go; no kernel still writes the rows
+    if (!P->ovl || P->ovl_modes != (given ? 1 : 0)) {
+        pop_free_history(P);
+        P->hist_steps = -1;
+        P->hist_ovl = P->hist_ovl_modes = 0;
+    }
+    P->ovl = 1;
+    P->ovl_modes = given ? 1 : 0;
+    return TSU_OK;
+}
+
+// the last recording run's overlap rows: q, L [n + 1][P]; modes [n + 1][P][periodic axis][re, im] (any may be NULL; synchronises)
+int pop_history_overlap(pop_handle* P, int64_t* q, int64_t* L, double* modes) {
+    tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, P->hist_steps >= 0 && P->hist_ovl && P->d_hq,
+                "%s_history_overlap: the last run recorded no overlaps (call tsu_%s_set_overlap before a recording run)", P->name, P->name);
+    TSU_REQUIRE(ctx, !modes || P->hist_ovl_modes, "%s_history_overlap: the last run recorded no modes (tsu_%s_set_overlap was given no tables)",
+                P->name, P->name);
+    const size_t n = ((size_t)P->hist_steps + 1) * ((size_t)P->R / 2);
+    if (q) TSU_HIP_TRY(ctx, hipMemcpyAsync(q, P->d_hq, n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (L) TSU_HIP_TRY(ctx, hipMemcpyAsync(L, P->d_hL, n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (modes) TSU_HIP_TRY(ctx, hipMemcpyAsync(modes, P->d_hF, n * pt_mode_doubles(P) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSU_OK;
 }

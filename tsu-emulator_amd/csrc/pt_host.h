@@ -12,13 +12,14 @@
 #include <vector>
 
 #include "corr_dev.h"
+#include "link_dev.h"
 #include "pt_ladder.h"
 #include "reduce_dev.h"
 
 namespace {
 
 void pt_free_history(pt_ladder* P) {
-    void* bufs[] = {P->d_hE, P->d_hM, P->d_hW, P->d_hq, P->d_hF};
+    void* bufs[] = {P->d_hE, P->d_hM, P->d_hW, P->d_hq, P->d_hF, P->d_hL};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     P->d_hE = nullptr;
@@ -26,6 +27,7 @@ void pt_free_history(pt_ladder* P) {
     P->d_hW = nullptr;
     P->d_hq = nullptr;
     P->d_hF = nullptr;
+    P->d_hL = nullptr;
     P->hist_cap = 0;
 }
 
@@ -204,27 +206,32 @@ void pt_enqueue_energies(pt_ladder* P, unsigned blocks, Partials&& partials) {
 }
 
 // ---------------------------------------------------------------- correlation recording (corr_dev.h)
-long long pt_prof_len(const pt_ladder* P) {
+// (templates: the population handle, pop_host.h, keeps its axes under the same names)
+template <class H>
+long long pt_prof_len(const H* P) {
     long long n = 0;
     for (int a = 0; a < P->n_axes; ++a) n += P->axis_len[a];
     return n;
 }
 
-int pt_periodic_axes(const pt_ladder* P) {
+template <class H>
+int pt_periodic_axes(const H* P) {
     int n = 0;
     for (int a = 0; a < P->n_axes; ++a) n += P->axis_per[a] ? 1 : 0;
     return n;
 }
 
 // doubles of a slot's modes: (re, im) per periodic axis
-size_t pt_mode_doubles(const pt_ladder* P) { return 2 * (size_t)pt_periodic_axes(P); }
+template <class H>
+size_t pt_mode_doubles(const H* P) { return 2 * (size_t)pt_periodic_axes(P); }
 
 dim3 pt_profile_plan(const pt_ladder* P, ProfArgs& pa) {
     return profile_plan(pa, P->pitch, P->pitch, P->nrows, P->lrows, P->cols, P->n_axes == 3, (unsigned)P->R);
 }
 
 // where the mode pass finds each periodic axis's profile and tables
-ModeArgs pt_mode_args(const pt_ladder* P) {
+template <class H>
+ModeArgs pt_mode_args(const H* P) {
     ModeArgs m = {};
     int off = 0;
     const double* tab = P->d_tab;
@@ -330,6 +337,46 @@ int pt_profiles(pt_ladder* P, int slot, int64_t* const* out) {
     return TSU_OK;
 }
 
+// ---------------------------------------------------------------- link-overlap recording (link_dev.h)
+// the launch shape of a link pass over the handle's planes (H: a ladder or a population)
+template <class H>
+unsigned pt_link_plan(const H* P, LinkArgs& la) {
+    const int three = P->n_axes == 3;
+    return link_plan(la, P->pitch, P->pitch, P->nrows, P->lrows, P->cols, three ? P->axis_per[0] : 0, P->axis_per[three ? 1 : 0],
+                     P->axis_per[three ? 2 : 1]);
+}
+
+// set_link_overlap: switching it on drops the recorded history (its buffers gain the L rows with the next run)
+int pt_set_link_overlap(pt_ladder* P, int enable) {
+    tsu_ctx* ctx = P->ctx;
+    if (!enable) {
+        P->link = 0;
+        return TSU_OK;
+    }
+    TSU_REQUIRE(ctx, P->nl == 2, "%s_set_link_overlap: the link overlap needs two ladders (this handle has %d)", P->name, P->nl);
+    if (!P->link) {
+        TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // no kernel still writes the rows
+        pt_free_history(P);
+        P->hist_rounds = 0;
+        P->hist_modes = 0;
+        P->hist_link = 0;
+    }
+    P->link = 1;
+    return TSU_OK;
+}
+
+// L of the last run's rows, [round][slot] (synchronises)
+int pt_history_link(pt_ladder* P, int64_t* L) {
+    tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, L, "%s_history_link: NULL output", P->name);
+    TSU_REQUIRE(ctx, P->hist_link, "%s_history_link: the last run recorded no link overlap (call tsu_%s_set_link_overlap before a recording run)",
+                P->name, P->name);
+    const size_t n = (size_t)P->hist_rounds * P->R;
+    if (n) TSU_HIP_TRY(ctx, hipMemcpyAsync(L, P->d_hL, n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return TSU_OK;
+}
+
 // what a run needs, in the order the messages are promised
 int pt_run_check(pt_ladder* P, int have_disorder, int n_rounds, int swap_interval) {
     tsu_ctx* ctx = P->ctx;
@@ -359,6 +406,7 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hW, n * sizeof(int32_t));
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hq, (size_t)n_rounds * R * sizeof(long long));
         if (e == hipSuccess && P->corr) e = hipMalloc((void**)&P->d_hF, (size_t)n_rounds * R * pt_mode_doubles(P) * sizeof(double));
+        if (e == hipSuccess && P->link) e = hipMalloc((void**)&P->d_hL, (size_t)n_rounds * R * sizeof(long long));
         if (e != hipSuccess) {  // nothing of a history that does not fit stays behind
             pt_free_history(P);
             P->hist_rounds = 0;
@@ -373,6 +421,10 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
         TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hq, 0, (size_t)n_rounds * R * sizeof(long long), ctx->stream));
     P->hist_rounds = record ? n_rounds : 0;
     P->hist_modes = record && P->corr;
+    P->hist_link = record && P->link && nl == 2;
+    if (P->hist_link && n_rounds > 0) TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hL, 0, (size_t)n_rounds * R * sizeof(long long), ctx->stream));
+    LinkArgs la;
+    const unsigned lblocks = pt_link_plan(P, la);
     const unsigned blocks = reduce_blocks(pt_lanes(P));
     ProfArgs pa;
     ModeArgs ma = {};
@@ -412,6 +464,7 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
             if (record && nl == 2)
                 pt_overlap<<<dim3(blocks, (unsigned)R, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, P->pitch, P->nrows, P->cols,
                                                                                  P->d_hq + (size_t)t * R);
+            if (P->hist_link) pt_link<<<dim3(lblocks, (unsigned)R, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, la, P->d_hL + (size_t)t * R);
             if (P->hist_modes) {  // the walkers the pass left at each slot: their profiles, then the modes of the periodic axes
                 TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_prof, 0, (size_t)R * pt_prof_len(P) * sizeof(long long), ctx->stream));
                 pt_profile<<<pgrid, 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, nl, pa, P->d_prof, pt_prof_len(P));

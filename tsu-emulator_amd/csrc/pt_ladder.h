@@ -43,5 +43,9 @@ struct pt_ladder {
     long long* d_prof;             // [slot][sum of axis_len] profile scratch (first set_correlation / profiles call)
     double* d_tab;                 // per periodic axis, in axis order: cos[len], sin[len] (first set_correlation)
     double* d_hF;                  // [round][slot][periodic axis][re, im]
+    // link overlap (link_dev.h): set_link_overlap, two ladders only
+    int link;                      // a recording round also records L per slot
+    int hist_link;                 // the last run's rows have it
+    long long* d_hL;               // [round][slot]
     double h_T[kPtMaxTemps];       // host copy of d_T
 };

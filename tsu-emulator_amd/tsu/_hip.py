@@ -199,6 +199,20 @@ for _pre, _shape, _nj in (("tsu_pa2d_", [C.c_int, C.c_int, C.c_int], 2), ("tsu_p
         _pre + "launch_count": (C.c_int, [_vp, _u64p]),
     })
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_overlap.h (the header tsu_hip.h includes) one to one
+OVERLAP_SIGNATURES = {
+    "tsu_ising2d_link_overlap": (C.c_int, [_vp, _vp, _i64p, _i64p]),
+    "tsu_ising3d_link_overlap": (C.c_int, [_vp, _vp, _i64p, _i64p]),
+    "tsu_pt2d_set_link_overlap": (C.c_int, [_vp, C.c_int]),
+    "tsu_pt3d_set_link_overlap": (C.c_int, [_vp, C.c_int]),
+    "tsu_pt2d_history_link": (C.c_int, [_vp, _i64p]),
+    "tsu_pt3d_history_link": (C.c_int, [_vp, _i64p]),
+    "tsu_pa2d_set_overlap": (C.c_int, [_vp, C.c_int, _f64p, _f64p, _f64p, _f64p]),
+    "tsu_pa3d_set_overlap": (C.c_int, [_vp, C.c_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
+    "tsu_pa2d_history_overlap": (C.c_int, [_vp, _i64p, _i64p, _f64p]),
+    "tsu_pa3d_history_overlap": (C.c_int, [_vp, _i64p, _i64p, _f64p]),
+}
+
 _lib = None
 
 
@@ -216,7 +230,7 @@ def load_library():
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailableError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items())
-                              + list(POPULATION_SIGNATURES.items())):
+                              + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -461,6 +475,13 @@ class Lattice:
         self.ctx.check(self.lib.tsu_ising2d_overlap(self.h, other.h, C.byref(q)))
         return q.value
 
+    def link_overlap(self, other):
+        """(L, N_b): L = sum over the energy's bonds (i, j) of s_i s'_i s_j s'_j with another lattice of the same shape, and the
+        number of those bonds."""
+        L, nb = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.lib.tsu_ising2d_link_overlap(self.h, other.h, C.byref(L), C.byref(nb)))
+        return L.value, nb.value
+
     def disorder_launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_ising2d_disorder_launch_count(self.h, C.byref(n)))
@@ -549,6 +570,13 @@ class Lattice3D:
         self.ctx.check(self.lib.tsu_ising3d_overlap(self.h, other.h, C.byref(q)))
         return q.value
 
+    def link_overlap(self, other):
+        """(L, N_b): L = sum over the energy's bonds (i, j) of s_i s'_i s_j s'_j with another lattice of the same shape, and the
+        number of those bonds."""
+        L, nb = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(self.lib.tsu_ising3d_link_overlap(self.h, other.h, C.byref(L), C.byref(nb)))
+        return L.value, nb.value
+
     def launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_ising3d_launch_count(self.h, C.byref(n)))
@@ -583,6 +611,7 @@ class _TemperingHandle:
     def _create(self, *shape_args):
         self._recorded = 0
         self._correlation = self._modes_recorded = False
+        self._link = self._link_recorded = False
         h = _vp()
         self.ctx.check(self._fn("create")(self.ctx.h, *shape_args, self.n_temps, self.n_ladders, C.byref(h)))
         self.h = h
@@ -616,6 +645,7 @@ class _TemperingHandle:
         self.ctx.check(self._fn("run")(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record))))
         self._recorded = int(n_rounds) if record else 0
         self._modes_recorded = bool(record) and self._correlation
+        self._link_recorded = bool(record) and self._link
 
     def _periodic_flags(self):
         p = self.periodic
@@ -643,6 +673,13 @@ class _TemperingHandle:
             self._recorded = 0  # switching it on drops the previous run's rows
         self._correlation = bool(enable)
 
+    def set_link_overlap(self, enable):
+        """Record L, the link overlap of the two ladders' walkers at every slot, in every recording round (two ladders only)."""
+        self.ctx.check(self._fn("set_link_overlap")(self.h, int(bool(enable))))
+        if enable and not self._link:
+            self._recorded = 0  # switching it on drops the previous run's rows
+        self._link = bool(enable)
+
     def history_modes(self):
         """The last run's modes as complex128 (n_rounds, n_temps, n_periodic_axes); raises if that run recorded none."""
         n_per = sum(self._periodic_flags())
@@ -658,7 +695,8 @@ class _TemperingHandle:
         return out
 
     def history(self):
-        """The last run's rows: E, M (sum of spins), walker as (n_rounds, n_ladders, n_temps); q as (n_rounds, n_temps) or None."""
+        """The last run's rows: E, M (sum of spins), walker as (n_rounds, n_ladders, n_temps); q as (n_rounds, n_temps) or None; q_link
+        (n_rounds, n_temps), only if that run recorded the link overlap."""
         n, nl, R = self._recorded, self.n_ladders, self.n_temps
         E = np.zeros((n, nl, R))
         M = np.zeros((n, nl, R), np.int64)
@@ -666,7 +704,11 @@ class _TemperingHandle:
         q = np.zeros((n, R), np.int64) if nl == 2 else None
         self.ctx.check(self._fn("history")(self.h, _ptr(E, _f64p), _ptr(M, _i64p), None if q is None else _ptr(q, _i64p),
                                            _ptr(W, _i32p)))
-        return {"E": E, "M": M, "walker": W, "q": q}
+        out = {"E": E, "M": M, "walker": W, "q": q}
+        if self._link_recorded:
+            out["q_link"] = np.zeros((n, R), np.int64)
+            self.ctx.check(self._fn("history_link")(self.h, _ptr(out["q_link"], _i64p)))
+        return out
 
     def stats(self):
         nl, R = self.n_ladders, self.n_temps
@@ -760,7 +802,7 @@ POPULATION_MAX = 65535
 
 class _PopulationHandle:
     """What the tsu_pa2d and tsu_pa3d handles share: every call but create and set_disorder.  A subclass sets ``_prefix`` and, in
-    its constructor, ``shape`` and ``population``, then calls ``_create`` with the shape arguments of its create function."""
+    its constructor, ``shape``, ``periodic`` and ``population``, then calls ``_create`` with the shape arguments of its create function."""
 
     _prefix = None
 
@@ -773,6 +815,8 @@ class _PopulationHandle:
         self.step_count = self.sweep_count = 0
         self._beta0 = 0.0
         self._resampled = False
+        self._overlap = self._overlap_modes = False          # the switch
+        self._overlap_recorded = self._modes_recorded = False  # what the last run recorded
         h = _vp()
         self.ctx.check(self._fn("create")(self.ctx.h, *shape_args, self.population, C.byref(h)))
         self.h = h
@@ -808,6 +852,8 @@ class _PopulationHandle:
         self.ctx.check(self._fn("run")(self.h, int(n_steps), int(sweeps_per_step), int(bool(resample)), int(bool(record))))
         self._recorded = int(n_steps) if record else None
         self._resampled = bool(resample)
+        self._overlap_recorded = bool(record) and self._overlap
+        self._modes_recorded = bool(record) and self._overlap_modes
         self.step_count += int(n_steps)
         self.sweep_count += int(n_steps) * int(sweeps_per_step)
 
@@ -823,7 +869,44 @@ class _PopulationHandle:
                                            _ptr(out["parent"], _i32p), _ptr(out["S"], _u64p), _ptr(out["U"], _u64p),
                                            _ptr(out["E_min"], _f64p)))
         out["resampled"] = np.full(n, self._resampled)
+        if self._overlap_recorded:
+            P = R // 2
+            out["q"], out["q_link"] = np.zeros((n + 1, P), np.int64), np.zeros((n + 1, P), np.int64)
+            modes = np.zeros((n + 1, P, sum(self._periodic_flags()), 2)) if self._modes_recorded else None
+            self.ctx.check(self._fn("history_overlap")(self.h, _ptr(out["q"], _i64p), _ptr(out["q_link"], _i64p),
+                                                       None if modes is None else _ptr(modes, _f64p)))
+            if modes is not None:
+                out["modes"] = modes[..., 0] + 1j * modes[..., 1]
         return out
+
+    def _periodic_flags(self):
+        p = self.periodic
+        return (bool(p),) * len(self.shape) if isinstance(p, (bool, np.bool_)) else tuple(bool(x) for x in p)
+
+    def set_overlap(self, enable, tables=None):
+        """Record, in every recording run, q N and L of the walker pairs (i, i + population // 2) for the population the run starts
+        from and after every step.  ``tables``: per axis ``(cos, sin)`` float64 arrays of the axis's length made on the host, or None
+        for an open axis: then also the k_min modes of each pair's overlap field; ``tables=None``: q and L only."""
+        n_axes = len(self.shape)
+        with_modes = tables is not None
+        tables = list(tables) if with_modes else [None] * n_axes
+        if len(tables) != n_axes:
+            raise ValueError(f"need one table pair (or None) per axis, {n_axes} in all")
+        keep, args = [], []
+        for n, t in zip(self.shape, tables):
+            if t is None:
+                args += [None, None]
+                continue
+            pair = [np.ascontiguousarray(a, dtype=np.float64).ravel() for a in t]
+            if len(pair) != 2 or pair[0].size != n or pair[1].size != n:
+                raise ValueError(f"a table pair must be (cos, sin) of the axis's length {n}")
+            keep += pair
+            args += [_ptr(a, _f64p) for a in pair]
+        self.ctx.check(self._fn("set_overlap")(self.h, int(bool(enable)), *args))
+        modes = bool(enable) and any(a is not None for a in args)
+        if enable and (not self._overlap or modes != self._overlap_modes):
+            self._recorded = None  # switching it on drops the previous run's rows
+        self._overlap, self._overlap_modes = bool(enable), modes
 
     def energies(self):
         """(E, sum of spins) of every walker now, by walker."""

@@ -533,6 +533,15 @@ def _correlation_summary(out: dict, N: int, lengths, periodic, f2, F2) -> dict:
     return out
 
 
+def lattice_bond_count(shape, periodic) -> int:
+    """N_b: the bonds of the lattice's energy, every site's bond along each axis, the last one of an open axis dropped and the wrap
+    bond of a periodic axis kept (a periodic axis of length 1 or 2 counts its wrap bond as the energy does)."""
+    shape = tuple(int(n) for n in shape)
+    per = (bool(periodic),) * len(shape) if isinstance(periodic, (bool, np.bool_)) else tuple(bool(p) for p in periodic)
+    N = int(np.prod(shape))
+    return sum(N if p else N - N // n for n, p in zip(shape, per))
+
+
 class IsingModel2D:
     """README facade (README.md:116-131): a lattice that lives on the GPU between calls.
 
@@ -647,6 +656,14 @@ class IsingModel2D:
         if (other.rows, other.cols) != (self.rows, self.cols):
             raise ValueError(f"overlap needs equal shapes, got {(self.rows, self.cols)} and {(other.rows, other.cols)}")
         return self._lat.overlap(other._lat) / self.n_spins
+
+    def link_overlap(self, other: "IsingModel2D") -> float:
+        """q_l = L / N_b with another model of the same shape and boundary: L = sum over the energy's bonds (i, j) of
+        s_i s'_i s_j s'_j (an exact integer, a device reduction), N_b the number of those bonds."""
+        if (other.rows, other.cols) != (self.rows, self.cols) or other.periodic != self.periodic:
+            raise ValueError(f"link_overlap needs equal shapes and boundaries, got {(self.rows, self.cols)} and {(other.rows, other.cols)}")
+        L, nb = self._lat.link_overlap(other._lat)
+        return L / nb
 
     def axis_profiles(self, other: Optional["IsingModel2D"] = None) -> Tuple[np.ndarray, np.ndarray]:
         """(P_row, P_col): exact int64 sums of the spins (of s s' with ``other``) over the columns / the rows, on the device."""
@@ -952,6 +969,13 @@ class IsingModel3D:
             raise ValueError(f"overlap needs equal shapes, got {self.shape} and {other.shape}")
         return self._lat.overlap(other._lat) / self.n_spins
 
+    def link_overlap(self, other: "IsingModel3D") -> float:
+        """q_l = L / N_b with another model of the same shape and periodic axes (:meth:`IsingModel2D.link_overlap`)."""
+        if other.shape != self.shape or tuple(other.periodic) != tuple(self.periodic):
+            raise ValueError(f"link_overlap needs equal shapes and periodic axes, got {self.shape} and {other.shape}")
+        L, nb = self._lat.link_overlap(other._lat)
+        return L / nb
+
     def axis_profiles(self, other: Optional["IsingModel3D"] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(P_z, P_r, P_c): exact int64 sums of the spins (of s s' with ``other``) over the other two axes, on the device."""
         if other is not None and other.shape != self.shape:
@@ -1085,6 +1109,8 @@ class _LatticeTempering:
         pt.set_temperatures(self.temperatures)
         if getattr(self, "cluster_moves", 0):  # 2-D only
             pt.set_cluster_moves(self.cluster_moves, self.cluster_max_temperature)
+        if self.link_overlap:
+            pt.set_link_overlap(True)
         if self.correlation:  # the tables are made here, on the host
             pt.set_correlation(True, [_kmin_tables(n) if per else None for n, per in zip(pt.shape, self._axes_periodic())])
         pt.init(self.seed, _PT_INITIAL[initial])
@@ -1092,6 +1118,14 @@ class _LatticeTempering:
     def _axes_periodic(self):
         p = self.periodic
         return tuple(p) if isinstance(p, tuple) else (bool(p),) * 2
+
+    link_overlap = False  # history() also has q_link
+
+    def _set_link_overlap(self, link_overlap):
+        """Before any device call: keep the flag, refuse a single ladder."""
+        self.link_overlap = bool(link_overlap)
+        if self.link_overlap and self.ladders != 2:
+            raise ValueError("link_overlap=True compares the two replicas at one temperature: it needs ladders=2")
 
     def _set_correlation(self, correlation):
         """Before any device call: keep the flag, refuse a lattice without a periodic axis."""
@@ -1108,11 +1142,14 @@ class _LatticeTempering:
         """The rounds recorded by the last ``run`` as (n_rounds, R) arrays, per slot: ``E`` (float64 energy), ``M`` (int64 sum of
         spins), ``walker`` (which walker of the ladder sat there) and, with two ladders, ``q`` (int64 overlap of the two ladders'
         walkers at that slot).  With ``correlation=True`` also ``modes``: complex128 (n_rounds, R, n_axes), the k_min mode of each
-        axis profile of the walker at that slot (one ladder: of its spins; two: of the overlap field; NaN on an open axis)."""
+        axis profile of the walker at that slot (one ladder: of its spins; two: of the overlap field; NaN on an open axis).  With
+        ``link_overlap=True`` also ``q_link``: int64 (n_rounds, R), L of the two walkers at that slot (q_l = L / N_b)."""
         h = self._pt.history()
         out = {k: np.ascontiguousarray(h[k][:, ladder]) for k in ("E", "M", "walker")}
         if h["q"] is not None:
             out["q"] = h["q"]
+        if "q_link" in h:
+            out["q_link"] = h["q_link"]
         if self.correlation:
             per = np.asarray(self._axes_periodic(), dtype=bool)
             got = self._pt.history_modes()
@@ -1177,6 +1214,8 @@ def _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, s
         Es = np.ascontiguousarray(hist["E"][:, 0].T)
         Qs = np.ascontiguousarray(hist["q"].T) / N if pt.ladders == 2 else None
         out = _scan_summary(out, N, Ms, Es, Qs)
+        if pt.link_overlap:
+            out["link_overlap"] = np.mean(hist["q_link"], axis=0) / lattice_bond_count(pt._pt.shape, pt._axes_periodic())
         if pt.correlation:
             F2 = np.mean(np.abs(pt.history()["modes"]) ** 2, axis=0)
             f2 = np.mean((Qs if pt.ladders == 2 else Ms) ** 2, axis=1) * float(N) ** 2
@@ -1215,13 +1254,15 @@ class LatticeTempering(_LatticeTempering):
 
     def __init__(self, size, temperatures, *, couplings=None, field=None, coupling: float = 1.0, external_field: float = 0.0,
                  periodic: bool = True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1,
-                 cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None, correlation: bool = False):
+                 cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None, correlation: bool = False,
+                 link_overlap: bool = False):
         self.rows, self.cols = (size, size) if np.isscalar(size) else tuple(size)
         self.n_spins = self.rows * self.cols
         self._check_ladder(temperatures, ladders, initial)
         self.cluster_moves, self.cluster_max_temperature = _cluster_move_args(cluster_moves, cluster_max_temperature, ladders)
         self.periodic = bool(periodic)
         self._set_correlation(correlation)
+        self._set_link_overlap(link_overlap)
         self._disorder = _disorder_arrays(self.rows, self.cols, self.periodic, float(coupling), float(external_field), "physical",
                                           couplings, field)
         self._start(_hip.TemperingLattice(self.rows, self.cols, self.periodic, self.temperatures.size, self.ladders), seed, initial)
@@ -1240,7 +1281,8 @@ class LatticeTempering(_LatticeTempering):
 def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                    measure_every: int = 10, periodic: bool = True, seed: int = 0, bias_mode: str = "physical",
                    initial: str = "up", *, couplings=None, field=None, replicas: int = 1, swap: bool = True,
-                   cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None, correlation: bool = False) -> dict:
+                   cluster_moves: int = 0, cluster_max_temperature: Optional[float] = None, correlation: bool = False,
+                   link_overlap: bool = False) -> dict:
     """:func:`temperature_scan` of a disordered lattice with replica exchange between the temperatures (:class:`LatticeTempering`).
 
     One round = ``measure_every`` sweeps of every walker + one swap pass; ``n_equilibrate`` (a multiple of ``measure_every``)
@@ -1250,10 +1292,13 @@ def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int
     arguments exactly.  ``cluster_moves`` / ``cluster_max_temperature`` as for :class:`LatticeTempering` (``replicas=2``); they add
     ``cluster_flipped``: the mean fraction of the sites a pass flipped per temperature, NaN where the slot does not take part.
     ``correlation=True``: ``chi_k``, ``xi`` and ``xi_over_L`` as for :func:`temperature_scan`, from the modes the ladder records on the
-    device in every recorded round.
+    device in every recorded round.  ``link_overlap=True`` (``replicas=2``) adds ``link_overlap``: the mean of q_l = L / N_b per
+    temperature.
     """
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
+    if link_overlap and replicas != 2:
+        raise ValueError("link_overlap=True compares the two replicas at one temperature: it needs replicas=2")
     if correlation:
         _check_correlation((bool(periodic),))
     _cluster_move_args(cluster_moves, cluster_max_temperature, replicas)
@@ -1264,7 +1309,7 @@ def tempering_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int
     temperatures = np.asarray(temperatures, dtype=float)
     pt = LatticeTempering((rows, cols), temperatures, couplings=(jr, jd), field=h, periodic=periodic, seed=seed, initial=initial,
                           ladders=replicas, cluster_moves=cluster_moves, cluster_max_temperature=cluster_max_temperature,
-                          correlation=correlation)
+                          correlation=correlation, link_overlap=link_overlap)
     return _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
 
 
@@ -1296,12 +1341,14 @@ class LatticeTempering3D(_LatticeTempering):
     """
 
     def __init__(self, size, temperatures, *, couplings=None, field=None, coupling: float = 1.0, external_field: float = 0.0,
-                 periodic=True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1, correlation: bool = False):
+                 periodic=True, seed: Optional[int] = None, initial: str = "random", ladders: int = 1, correlation: bool = False,
+                 link_overlap: bool = False):
         self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
         self.n_spins = self.depth * self.rows * self.cols
         self._check_ladder(temperatures, ladders, initial)
         self.periodic = _hip.periodic_axes(periodic)
         self._set_correlation(correlation)
+        self._set_link_overlap(link_overlap)
         self._disorder = _tempering_disorder_3d(self.shape, self.periodic, float(coupling), float(external_field), couplings, field)
         self._start(_hip.TemperingLattice3D(self.depth, self.rows, self.cols, self.periodic, self.temperatures.size, self.ladders),
                     seed, initial)
@@ -1309,7 +1356,7 @@ class LatticeTempering3D(_LatticeTempering):
 
 def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                       measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", *, couplings=None, field=None,
-                      replicas: int = 1, swap: bool = True, correlation: bool = False) -> dict:
+                      replicas: int = 1, swap: bool = True, correlation: bool = False, link_overlap: bool = False) -> dict:
     """:func:`temperature_scan_3d` with replica exchange between the temperatures (:class:`LatticeTempering3D`).
 
     One round = ``measure_every`` sweeps of every walker + one swap pass; ``n_equilibrate`` (a multiple of ``measure_every``)
@@ -1317,10 +1364,13 @@ def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: 
     from the walker at each temperature (``overlap``, ``overlap_sq``, ``binder`` for ``replicas=2``), plus ``swap_acceptance`` (per
     adjacent pair, ladders pooled) and ``round_trips`` (all walkers).  ``swap=False`` reproduces ``temperature_scan_3d`` with the
     same arguments exactly.  ``correlation=True``: ``chi_k``, ``xi`` and ``xi_over_L`` as for :func:`temperature_scan_3d`, from the
-    modes the ladder records on the device in every recorded round.
+    modes the ladder records on the device in every recorded round.  ``link_overlap=True`` (``replicas=2``) adds ``link_overlap``: the
+    mean of q_l = L / N_b per temperature.
     """
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
+    if link_overlap and replicas != 2:
+        raise ValueError("link_overlap=True compares the two replicas at one temperature: it needs replicas=2")
     if int(measure_every) < 1 or int(n_equilibrate) % int(measure_every):
         raise ValueError("n_equilibrate must be a multiple of measure_every")
     shape = _shape_3d(size)
@@ -1329,7 +1379,7 @@ def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: 
     jr, jd, jl, h = _tempering_disorder_3d(shape, _hip.periodic_axes(periodic), float(coupling), 0.0, couplings, field)
     temperatures = np.asarray(temperatures, dtype=float)
     pt = LatticeTempering3D(shape, temperatures, couplings=(jr, jd, jl), field=h, periodic=periodic, seed=seed, initial=initial,
-                            ladders=replicas, correlation=correlation)
+                            ladders=replicas, correlation=correlation, link_overlap=link_overlap)
     return _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
 
 
@@ -1398,6 +1448,64 @@ def population_family_stats(parent) -> dict:
     return {"rho_t": np.array(rho_t), "rho_s": np.array(rho_s), "families": np.array(alive)}
 
 
+def population_pair_mask(parent) -> np.ndarray:
+    """bool (n_steps + 1, P), P = R // 2: whether the walkers of the pair (i, i + P) belong to different families at each recorded
+    step (row 0: the start, where every walker is a family), the families chained from ``parent`` (n_steps, R) as
+    :func:`population_family_stats` chains them.  Two walkers of one family share an ancestor of the start: they are correlated
+    copies, not two replicas, and their overlap is left out of every mean."""
+    parent = np.asarray(parent)
+    R = parent.shape[1]
+    P = R // 2
+    fam = np.arange(R)
+    rows = [fam[:P] != fam[P:2 * P]]
+    for row in parent:
+        fam = fam[row]
+        rows.append(fam[:P] != fam[P:2 * P])
+    return np.array(rows, dtype=bool).reshape(parent.shape[0] + 1, P)
+
+
+def _masked_mean(x, mask) -> np.ndarray:
+    """Row means of x (rows, P, ...) over the pairs with mask (rows, P) set; NaN for a row without one."""
+    x = np.asarray(x, dtype=np.float64)
+    n = mask.sum(axis=1).astype(np.float64)
+    m = mask.reshape(mask.shape + (1,) * (x.ndim - 2))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(m, x, 0.0).sum(axis=1) / n.reshape((-1,) + (1,) * (x.ndim - 2))
+
+
+def population_overlap_stats(parent, q, q_link, n_spins: int, n_bonds: int, modes=None, lengths=None, periodic=None) -> dict:
+    """Per recorded step, over the pairs (i, i + P) of different families (:func:`population_pair_mask`) only, NaN where there is
+    none: ``pairs`` (their number), ``overlap`` (<|q|>), ``overlap_sq`` (<q^2>), ``binder`` (1/2 (3 - <q^4> / <q^2>^2)), with
+    q = (sum_i s_i s'_i) / N as in :func:`temperature_scan`, and ``link_overlap`` (<L> / N_b).  With ``modes`` (rows, P, n_axes;
+    NaN on open axes), ``lengths`` and ``periodic`` also ``chi_k``, ``xi`` and ``xi_over_L`` of the overlap field."""
+    mask = population_pair_mask(parent)
+    Q = np.asarray(q, dtype=np.float64) / float(n_spins)
+    out = {"pairs": mask.sum(axis=1), "overlap": _masked_mean(np.abs(Q), mask), "overlap_sq": _masked_mean(Q ** 2, mask)}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["binder"] = 0.5 * (3.0 - _masked_mean(Q ** 4, mask) / out["overlap_sq"] ** 2)
+    out["link_overlap"] = _masked_mean(np.asarray(q_link, dtype=np.float64), mask) / float(n_bonds)
+    if modes is not None:
+        F2 = _masked_mean(np.abs(np.asarray(modes)) ** 2, mask)
+        _correlation_summary(out, n_spins, lengths, periodic, out["overlap_sq"] * float(n_spins) ** 2, F2)
+    return out
+
+
+def population_overlap_histogram(parent, q, n_spins: int, bins: int = 50) -> dict:
+    """P(q) per recorded step: the histogram of q = (sum_i s_i s'_i) / N over the pairs of different families, ``bins`` equal bins
+    on [-1, 1], normalised to integrate to 1 (NaN for a step without such a pair).  ``edges`` (bins + 1,), ``P`` (rows, bins),
+    ``pairs`` (rows,)."""
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or bins < 1:
+        raise ValueError("bins must be an integer >= 1")
+    mask = population_pair_mask(parent)
+    Q = np.asarray(q, dtype=np.float64) / float(n_spins)
+    edges = np.linspace(-1.0, 1.0, int(bins) + 1)
+    Pq = np.full((mask.shape[0], int(bins)), np.nan)
+    for k, (row, m) in enumerate(zip(Q, mask)):
+        if m.any():
+            Pq[k] = np.histogram(row[m], bins=edges)[0] / (m.sum() * (2.0 / int(bins)))
+    return {"edges": edges, "P": Pq, "pairs": mask.sum(axis=1)}
+
+
 class _PopulationAnnealing:
     """What :class:`PopulationAnnealing` and :class:`PopulationAnnealing3D` share: everything but the shape and the disorder.  A
     subclass parses its shape, calls ``_check``, validates its disorder into ``self._disorder`` and hands its handle to ``_start``."""
@@ -1409,12 +1517,29 @@ class _PopulationAnnealing:
             raise ValueError("sweeps_per_step and initial_sweeps must be >= 0")
         self.sweeps_per_step, self.initial_sweeps = int(sweeps_per_step), int(initial_sweeps)
 
+    overlap = correlation = False
+
+    def _axes_periodic(self):
+        p = self.periodic
+        return tuple(p) if isinstance(p, tuple) else (bool(p),) * 2
+
+    def _set_overlap(self, overlap, correlation):
+        """Before any device call: keep the flags; the modes belong to the overlap field and need a periodic axis."""
+        self.overlap, self.correlation = bool(overlap), bool(correlation)
+        if self.correlation:
+            if not self.overlap:
+                raise ValueError("correlation=True records the k_min modes of the pairs' overlap field: it needs overlap=True")
+            _check_correlation(self._axes_periodic())
+
     def _start(self, pa, seed):
         self._pa = pa
         self.seed = int(seed) if seed is not None else (
             int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
         pa.set_disorder(*self._disorder)
         pa.set_schedule(self.betas)
+        if self.overlap:  # the tables are made here, on the host
+            pa.set_overlap(True, [_kmin_tables(n) if per else None for n, per in zip(pa.shape, self._axes_periodic())]
+                           if self.correlation else None)
         pa.init(self.seed, self.initial_sweeps)
         self._record = None    # the rows since init while every run recorded, else None
         self._complete = True  # no run since init went unrecorded
@@ -1442,23 +1567,35 @@ class _PopulationAnnealing:
         if not record:
             self._complete, self._record = False, None
             return None
-        h = self._pa.history()
+        h = self._history_rows()
         if self._complete:
             if self._record is None:
                 self._record = h
             else:  # row 0 of a later run repeats the last row of the one before
                 r = self._record
-                self._record = {k: np.concatenate([r[k], h[k][1:] if k in ("E", "M") else h[k]]) for k in h}
+                self._record = {k: np.concatenate([r[k], h[k][1:] if k in ("E", "M", "q", "q_link", "modes") else h[k]]) for k in h}
         return self.history()
 
     def history(self) -> dict:
         """Every step since the start, if every run recorded (else the last run's steps): ``E`` (float64), ``M`` (int64 sum of spins)
         as (n + 1, R) arrays by walker index, row 0 the start; ``W`` (uint32 weights), ``parent`` (int32) (n, R); ``S``, ``U``
         (uint64), ``E_min`` (n,); ``resampled`` (n,) bool.  Steps taken with ``resample=False`` have ``parent`` = identity and zeros in
-        ``W``, ``S``, ``U``, ``E_min``."""
+        ``W``, ``S``, ``U``, ``E_min``.  With ``overlap=True`` also, per pair (i, i + R // 2): ``q`` (int64 sum_i s_i s'_i) and ``q_link``
+        (int64 L; q_l = L / N_b) as (n + 1, R // 2) and, with ``correlation=True``, ``modes``: complex128 (n + 1, R // 2, n_axes), the
+        k_min mode of each axis profile of the pair's overlap field (NaN on an open axis)."""
         if self._complete and self._record is not None:
             return dict(self._record)
-        return self._pa.history()
+        return self._history_rows()
+
+    def _history_rows(self) -> dict:
+        """The handle's rows of the last run, the modes spread over all axes."""
+        h = self._pa.history()
+        if "modes" in h:
+            per = np.asarray(self._axes_periodic(), dtype=bool)
+            modes = np.full(h["modes"].shape[:2] + (per.size,), complex(np.nan, np.nan), dtype=np.complex128)
+            modes[:, :, per] = h["modes"]
+            h["modes"] = modes
+        return h
 
     def _full_record(self, what):
         if not (self._complete and self._record is not None):
@@ -1485,6 +1622,30 @@ class _PopulationAnnealing:
         """``rho_t``, ``rho_s`` and ``families`` per recorded beta (:func:`population_family_stats`)."""
         return population_family_stats(self._full_record("family_stats")["parent"])
 
+    def _overlap_record(self, what):
+        r = self._full_record(what)
+        if "q" not in r:
+            raise ValueError(f"{what} needs the overlaps of the walker pairs: create the population with overlap=True")
+        return r
+
+    def overlap_stats(self) -> dict:
+        """Per recorded beta, over the pairs (i, i + R // 2) whose walkers belong to different families only (NaN where there is
+        none): ``pairs``, ``overlap``, ``overlap_sq``, ``binder``, ``link_overlap`` and, with ``correlation=True``, ``chi_k``, ``xi``
+        and ``xi_over_L`` of the overlap field (:func:`population_overlap_stats`), with ``betas``."""
+        r = self._overlap_record("overlap_stats")
+        shape = self._pa.shape
+        out = population_overlap_stats(r["parent"], r["q"], r["q_link"], self.n_spins, lattice_bond_count(shape, self._axes_periodic()),
+                                       r.get("modes"), shape, self._axes_periodic())
+        out["betas"] = self.betas[:r["q"].shape[0]]
+        return out
+
+    def overlap_histogram(self, bins: int = 50) -> dict:
+        """P(q) per recorded beta over the pairs of different families (:func:`population_overlap_histogram`), with ``betas``."""
+        r = self._overlap_record("overlap_histogram")
+        out = population_overlap_histogram(r["parent"], r["q"], self.n_spins, bins)
+        out["betas"] = self.betas[:r["q"].shape[0]]
+        return out
+
     def spins(self, i: int) -> np.ndarray:
         """Spins of walker ``i``, in the lattice's shape."""
         if not 0 <= i < self.population:
@@ -1509,15 +1670,22 @@ class PopulationAnnealing(_PopulationAnnealing):
     ``sweeps_per_step`` times at 1 / beta[k] and computes every energy, all on the device without a host synchronisation.
     ``run(resample=False)`` anneals the walkers independently (the single lattices, bit for bit).  From the record:
     ``free_energy()``, ``observables()`` and ``family_stats()``.  Fixed population, one GPU, fixed schedule.
+
+    ``overlap=True`` also records, for the start and after every step, the spin overlap ``q`` and the link overlap ``q_link`` of the
+    walker pairs (i, i + population // 2), and ``correlation=True`` (needs ``overlap=True`` and a periodic axis) the k_min modes of
+    each pair's overlap field, all on the device within the same run.  Two walkers are two replicas of the disorder only while they
+    descend from different walkers of the start: ``overlap_stats()`` and ``overlap_histogram()`` average over those pairs alone.
+    One partner per walker, a fixed pairing, P(q) binned on the host.
     """
 
     def __init__(self, size, population, *, betas=None, temperatures=None, couplings=None, field=None, coupling: float = 1.0,
                  external_field: float = 0.0, periodic: bool = True, seed: Optional[int] = None, sweeps_per_step: int = 10,
-                 initial_sweeps: int = 0):
+                 initial_sweeps: int = 0, overlap: bool = False, correlation: bool = False):
         self.rows, self.cols = (size, size) if np.isscalar(size) else tuple(size)
         self.n_spins = self.rows * self.cols
         self._check(population, betas, temperatures, sweeps_per_step, initial_sweeps)
         self.periodic = bool(periodic)
+        self._set_overlap(overlap, correlation)
         self._disorder = _disorder_arrays(self.rows, self.cols, self.periodic, float(coupling), float(external_field), "physical",
                                           couplings, field)
         self._start(_hip.PopulationLattice(self.rows, self.cols, self.periodic, self.population), seed)
@@ -1530,11 +1698,12 @@ class PopulationAnnealing3D(_PopulationAnnealing):
 
     def __init__(self, size, population, *, betas=None, temperatures=None, couplings=None, field=None, coupling: float = 1.0,
                  external_field: float = 0.0, periodic=True, seed: Optional[int] = None, sweeps_per_step: int = 10,
-                 initial_sweeps: int = 0):
+                 initial_sweeps: int = 0, overlap: bool = False, correlation: bool = False):
         self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
         self.n_spins = self.depth * self.rows * self.cols
         self._check(population, betas, temperatures, sweeps_per_step, initial_sweeps)
         self.periodic = _hip.periodic_axes(periodic)
+        self._set_overlap(overlap, correlation)
         self._disorder = _tempering_disorder_3d(self.shape, self.periodic, float(coupling), float(external_field), couplings, field)
         self._start(_hip.PopulationLattice3D(self.depth, self.rows, self.cols, self.periodic, self.population), seed)
 
@@ -1554,6 +1723,8 @@ def _population_scan(pa) -> dict:
         out["ln_Z"] = pa.free_energy()["ln_Z"]
         fam = pa.family_stats()
         out["rho_t"], out["rho_s"] = fam["rho_t"], fam["rho_s"]
+        if pa.overlap:
+            out.update({k: v for k, v in pa.overlap_stats().items() if k != "betas"})
     finally:
         pa._pa.close()
     return out
@@ -1561,19 +1732,22 @@ def _population_scan(pa) -> dict:
 
 def population_annealing_scan(size, population, *, betas=None, temperatures=None, coupling: float = 1.0, couplings=None, field=None,
                               external_field: float = 0.0, periodic: bool = True, seed: int = 0, sweeps_per_step: int = 10,
-                              initial_sweeps: int = 0) -> dict:
+                              initial_sweeps: int = 0, overlap: bool = False, correlation: bool = False) -> dict:
     """:func:`temperature_scan`'s keys (``temperatures``, ``magnetization``, ``energy``, ``susceptibility``, ``specific_heat``) per
     temperature of the schedule, as population means of one :class:`PopulationAnnealing` run, plus ``betas``, ``ln_Z`` (differences
-    from the first beta unless it is 0), ``rho_t`` and ``rho_s``."""
+    from the first beta unless it is 0), ``rho_t`` and ``rho_s``.  ``overlap=True`` (and ``correlation=True``) add the keys of
+    :meth:`PopulationAnnealing.overlap_stats`."""
     return _population_scan(PopulationAnnealing(size, population, betas=betas, temperatures=temperatures, couplings=couplings,
                                                 field=field, coupling=coupling, external_field=external_field, periodic=periodic,
-                                                seed=seed, sweeps_per_step=sweeps_per_step, initial_sweeps=initial_sweeps))
+                                                seed=seed, sweeps_per_step=sweeps_per_step, initial_sweeps=initial_sweeps,
+                                                overlap=overlap, correlation=correlation))
 
 
 def population_annealing_scan_3d(size, population, *, betas=None, temperatures=None, coupling: float = 1.0, couplings=None,
                                  field=None, external_field: float = 0.0, periodic=True, seed: int = 0, sweeps_per_step: int = 10,
-                                 initial_sweeps: int = 0) -> dict:
+                                 initial_sweeps: int = 0, overlap: bool = False, correlation: bool = False) -> dict:
     """:func:`population_annealing_scan` for the cubic lattices of :class:`PopulationAnnealing3D`."""
     return _population_scan(PopulationAnnealing3D(size, population, betas=betas, temperatures=temperatures, couplings=couplings,
                                                   field=field, coupling=coupling, external_field=external_field, periodic=periodic,
-                                                  seed=seed, sweeps_per_step=sweeps_per_step, initial_sweeps=initial_sweeps))
+                                                  seed=seed, sweeps_per_step=sweeps_per_step, initial_sweeps=initial_sweeps,
+                                                  overlap=overlap, correlation=correlation))
