@@ -349,6 +349,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * pairs: declared in tsu_hip_overlap.h, which this header includes; its prototypes are _hip.OVERLAP_SIGNATURES in Python. */
 #include "tsu_hip_overlap.h"
 
+/* K7 / K8: tempering ensembles, the ladders of many disorder samples in one handle and one launch per pass (the tsu_pte2d and
+ * tsu_pte3d handles): declared in tsu_hip_ensemble.h, which this header includes; its prototypes are _hip.ENSEMBLE_SIGNATURES in
+ * Python. */
+#include "tsu_hip_ensemble.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -117,12 +117,14 @@ __global__ __launch_bounds__(256) void profile_pass(const int8_t* __restrict__ a
     profile_block(a, b, p, out);
 }
 
-// grid (column tiles, row bands, R): the walker of ladder 0 at slot z, times the walker of ladder 1 there if there are two ladders,
-// into out[z * stride ..] (zeroed scratch)
+// grid (column tiles, row bands, S R): the walker of ladder 0 of sample z / R at slot z % R, times the walker of ladder 1 there if
+// there are two ladders, into out[z * stride ..] (zeroed scratch [sample][slot]); the tables are [sample][ladder][..]
 __global__ __launch_bounds__(256) void pt_profile(int8_t* const* __restrict__ s, const int32_t* __restrict__ was, int R, int nl,
                                                   ProfArgs p, long long* __restrict__ out, long long stride) {
-    const int i = blockIdx.z;
-    profile_block(s[was[i]], nl == 2 ? s[R + was[R + i]] : nullptr, p, out + i * stride);
+    const int z = blockIdx.z, smp = z / R, i = z - smp * R;
+    s += (size_t)smp * nl * R;
+    was += (size_t)smp * nl * R;
+    profile_block(s[was[i]], nl == 2 ? s[R + was[R + i]] : nullptr, p, out + z * stride);
 }
 
 struct ModeArgs {
@@ -132,7 +134,7 @@ struct ModeArgs {
     const double* sn[3];
 };
 
-// grid (2 n, R): block (2 k + im, slot) writes Re / Im F of periodic axis k into out[slot][k][im]
+// grid (2 n, S R): block (2 k + im, y = (sample, slot)) writes Re / Im F of periodic axis k into out[y][k][im]
 __global__ __launch_bounds__(256) void pt_modes(const long long* __restrict__ prof, long long stride, ModeArgs m,
                                                 double* __restrict__ out) {
 #pragma clang fp contract(off)

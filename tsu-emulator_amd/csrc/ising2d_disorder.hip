@@ -52,10 +52,17 @@
 #include "link_dev.h"
 #include "pop_host.h"
 #include "pt_host.h"
+#include "pte_host.h"
 #include "reduce_dev.h"
 
 // Population annealing: pop_host.h's population of K7 lattices, all planes in one allocation; `lat` owns the one disorder
 struct tsu_pa2d : pop_handle {
+    tsu_ising2d* lat;
+};
+
+// Tempering ensemble: pte_host.h's S samples x ladders of K7 lattices, all planes in one allocation and all disorder in another;
+// `lat` gives the shape its checks and each sample's disorder its validation ("Tempering ensembles")
+struct tsu_pte2d : pte_handle {
     tsu_ising2d* lat;
 };
 
@@ -327,6 +334,35 @@ __global__ __launch_bounds__(256) void k7_pt_sweep(PTParams p, int colour) {
     else k7_pt_octet<1>(p, r, q, g0, g1);
 }
 
+// The ensemble's sample index: grid z of the sweep = sample * groups + walker group, walkers [base + group W, ..) clipped to the
+// sample's own [base, base + nper), base = sample * nper; the sample's disorder sits dstride floats after its predecessor's
+struct PTEns {
+    long long dstride;  // floats of a sample's disorder (3 planes)
+    int nper;           // walkers of a sample (nl * R)
+    int groups;         // walker groups of a sample: ceil(nper / W)
+};
+
+__device__ __forceinline__ void pte_sample(PTParams& p, const PTEns& e, int sample) {
+    const long long off = (long long)sample * e.dstride;
+    p.jr += off;
+    p.jd += off;
+    p.h += off;
+}
+
+// k7_pt_sweep for an ensemble, a kernel of its own so that the ladders' code object stays what it was: the same lane and the same
+// octet, for the walkers of one group of one sample on that sample's disorder.  The sample and its offsets are wave-uniform.
+__global__ __launch_bounds__(256) void k7_pte_sweep(PTParams p, PTEns e, int colour) {
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    const int r = blockIdx.y * 4 + threadIdx.y;
+    if (r >= p.rows || 16 * q >= p.cols) return;
+    const int sample = blockIdx.z / e.groups, group = blockIdx.z - sample * e.groups;
+    const int base = sample * e.nper;
+    const int g0 = base + group * p.W, g1 = min(g0 + p.W, base + e.nper);
+    pte_sample(p, e, sample);
+    if (((r + colour) & 1) == 0) k7_pt_octet<0>(p, r, q, g0, g1);
+    else k7_pt_octet<1>(p, r, q, g0, g1);
+}
+
 __device__ __forceinline__ K7Params pt_walker_params(const PTParams& pp, int g) {
     K7Params p;
     p.s = pp.s[g];
@@ -345,6 +381,18 @@ __device__ __forceinline__ K7Params pt_walker_params(const PTParams& pp, int g) 
 
 // grid (blocks_for(lattice), nw): workgroup x of walker y computes k7_energy's partial x of that walker alone, and its sum of spins
 __global__ __launch_bounds__(256) void k7_pt_energy(PTParams pp, double* __restrict__ part, long long* __restrict__ ipart) {
+    long long m;
+    const double e = block_sum(k7_energy_lane(pt_walker_params(pp, blockIdx.y), m));
+    const long long ms = block_isum(m);
+    if (threadIdx.x == 0) {
+        part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
+        ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
+    }
+}
+
+// k7_pt_energy for an ensemble: walker y on the disorder of its sample y / nper
+__global__ __launch_bounds__(256) void k7_pte_energy(PTParams pp, PTEns en, double* __restrict__ part, long long* __restrict__ ipart) {
+    pte_sample(pp, en, blockIdx.y / en.nper);
     long long m;
     const double e = block_sum(k7_energy_lane(pt_walker_params(pp, blockIdx.y), m));
     const long long ms = block_isum(m);
@@ -405,6 +453,44 @@ PTParams pt_params(const tsu_pt2d* P) {
 // k7_pt_energy into d_part / d_ipart (asynchronous): the partial pass pt_host.h's energies take
 auto pt_partials(tsu_pt2d* P, const PTParams& p) {
     return [P, &p](unsigned blocks) { k7_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
+}
+
+void pte_free(tsu_pte2d* P) { pte_delete(P, tsu_ising2d_destroy); }
+
+// the ladders' parameters for an ensemble: sample 0's disorder (the kernels add the sample's offset), the walkers of all samples
+PTParams pte_params(const tsu_pte2d* P) {
+    PTParams p;
+    p.s = P->d_s;
+    p.key = P->d_key;
+    p.slot = P->d_slot;
+    p.T = P->d_T;
+    p.c32 = P->d_c32;
+    p.jr = P->d_dis;
+    p.jd = P->d_dis + P->plane;
+    p.h = P->d_dis + 2 * P->plane;
+    p.pitch = P->pitch;
+    p.rows = P->lat->rows;
+    p.cols = P->lat->cols;
+    p.periodic = P->lat->periodic;
+    p.nw = P->nw;
+    p.W = 1;
+    p.hs = 0;
+    return p;
+}
+
+PTEns pte_ens(const tsu_pte2d* P, int W) {
+    PTEns e;
+    e.dstride = 3 * (long long)P->plane;
+    e.nper = P->nl * P->R;
+    e.groups = (int)pte_groups(P, W);
+    return e;
+}
+
+// k7_pte_energy into d_part / d_ipart (asynchronous)
+auto pte_partials(tsu_pte2d* P, const PTParams& p, const PTEns& e) {
+    return [P, &p, &e](unsigned blocks) {
+        k7_pte_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, e, P->d_part, P->d_ipart);
+    };
 }
 
 void pa_free(tsu_pa2d* P) { pop_delete(P, tsu_ising2d_destroy); }
@@ -764,6 +850,141 @@ int tsu_pt2d_set_link_overlap(tsu_pt2d* P, int enable) {
 int tsu_pt2d_history_link(tsu_pt2d* P, int64_t* L) {
     TSU_ENTER(P ? P->ctx : nullptr);
     return P ? pt_history_link(P, L) : TSU_E_INVALID;
+}
+
+// ------------------------------------------------------------------ tempering ensembles
+int tsu_pte2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int n_samples, int n_temps, int n_ladders, tsu_pte2d** out) {
+    TSU_ENTER(ctx);
+    if (!ctx || !out) return TSU_E_INVALID;
+    return pte_create(
+        ctx, "pte2d", n_samples, n_temps, n_ladders, out,
+        [=](tsu_pte2d* P) {  // every whole lattice K7 takes
+            const int rc = tsu_ising2d_create(ctx, rows, cols, periodic, &P->lat);
+            if (rc != TSU_OK) return rc;
+            P->nrows = P->lat->rows;
+            P->pitch = (long long)P->lat->pitch;
+            P->cols = P->lat->cols;
+            P->n_axes = 2;
+            P->lrows = P->lat->rows;
+            P->axis_len[0] = P->lat->rows;
+            P->axis_len[1] = P->lat->cols;
+            P->axis_per[0] = P->axis_per[1] = P->lat->periodic;
+            P->n_dis = 3;
+            return (int)TSU_OK;
+        },
+        pte_free);
+}
+
+int tsu_pte2d_destroy(tsu_pte2d* P) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_OK;
+    (void)hipStreamSynchronize(P->ctx->stream);
+    pte_free(P);
+    return TSU_OK;
+}
+
+int tsu_pte2d_set_disorder(tsu_pte2d* P, const float* J_right, const float* J_down, const float* h) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const float* src[3] = {J_right, J_down, h};
+    return pte_set_disorder(
+        P, src, (size_t)P->nrows * P->cols, [](tsu_pte2d* E) { return E->lat->d_dis; },
+        [](tsu_ising2d* L, const float* const* a) { return tsu_ising2d_set_disorder(L, a[0], a[1], a[2]); });
+}
+
+int tsu_pte2d_set_temperatures(tsu_pte2d* P, const double* T) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_set_temperatures(P, T) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_init(tsu_pte2d* P, const uint64_t* seeds, int initial) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pte_init(P, seeds, initial) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_run(tsu_pte2d* P, int n_rounds, int swap_interval, int do_swap, int record) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    tsu_ctx* ctx = P->ctx;
+    const int rc = pt_run_check(P, P->have_disorder, n_rounds, swap_interval);
+    if (rc != TSU_OK) return rc;
+    PTParams p = pte_params(P);
+    p.W = pt_group(P);
+    const PTEns e = pte_ens(P, p.W);
+    const int nchunks = (p.cols + 15) >> 4;
+    const dim3 grid((unsigned)((nchunks + 63) / 64), (unsigned)((p.rows + 3) / 4), (unsigned)P->S * (unsigned)e.groups);
+    return pt_run(
+        P, n_rounds, swap_interval, do_swap, record,
+        [&](uint32_t hs, int colour) {
+            p.hs = hs;
+            k7_pte_sweep<<<grid, dim3(64, 4, 1), 0, ctx->stream>>>(p, e, colour);
+        },
+        pte_partials(P, p, e), [] { return (int)TSU_OK; });
+}
+
+int tsu_pte2d_history(tsu_pte2d* P, double* E, int64_t* M, int64_t* q, int32_t* walker) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history(P, E, M, q, walker) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_stats(tsu_pte2d* P, int64_t* attempts, int64_t* accepts, int64_t* round_trips, int32_t* walker_at_slot,
+                    uint64_t* sweep_count, uint64_t* round_count) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_stats(P, attempts, accepts, round_trips, walker_at_slot, sweep_count, round_count) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_energies(tsu_pte2d* P, double* E, int64_t* sum_s) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const PTParams p = pte_params(P);
+    const PTEns e = pte_ens(P, 1);
+    return pt_energies(P, P->have_disorder, E, sum_s, pte_partials(P, p, e));
+}
+
+int tsu_pte2d_get_spins(tsu_pte2d* P, int sample, int ladder, int slot, int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pte_get_spins(P, sample, ladder, slot, host) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_set_spins(tsu_pte2d* P, int sample, int ladder, int slot, const int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pte_set_spins(P, sample, ladder, slot, host) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_launch_count(tsu_pte2d* P, uint64_t* n) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return pt_launch_count(P, n);
+}
+
+int tsu_pte2d_set_correlation(tsu_pte2d* P, int enable, const double* cos_row, const double* sin_row, const double* cos_col,
+                              const double* sin_col) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const double* cs[3] = {cos_row, cos_col, nullptr};
+    const double* sn[3] = {sin_row, sin_col, nullptr};
+    return pt_set_correlation(P, enable, cs, sn);
+}
+
+int tsu_pte2d_history_modes(tsu_pte2d* P, double* modes) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history_modes(P, modes) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_set_link_overlap(tsu_pte2d* P, int enable) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_set_link_overlap(P, enable) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_history_link(tsu_pte2d* P, int64_t* L) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history_link(P, L) : TSU_E_INVALID;
+}
+
+int tsu_pte2d_profiles(tsu_pte2d* P, int sample, int slot, int64_t* p_row, int64_t* p_col) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    int64_t* out[3] = {p_row, p_col, nullptr};
+    return pt_profiles(P, slot, out, sample);
 }
 
 // ------------------------------------------------------------------ population annealing

@@ -55,6 +55,7 @@
 #include "corr_dev.h"
 #include "pop_host.h"
 #include "pt_host.h"
+#include "pte_host.h"
 #include "reduce_dev.h"
 
 // Parallel tempering: pt_ladder.h's ladder with whole K8 lattices as its walkers, the 3-D counterpart of tsu_pt2d
@@ -66,6 +67,12 @@ struct tsu_pt3d : pt_ladder {
 // sweeps and the energies are k8_pt_sweep and k8_pt_energy as they stand (every walker at slot 0, the schedule's tables offset by the
 // step); the resampling kernels (pop_dev.h) are the 2-D populations' ("Population annealing")
 struct tsu_pa3d : pop_handle {
+    tsu_ising3d* lat;
+};
+
+// Tempering ensemble: pte_host.h's S samples x ladders of K8 lattices, all planes in one allocation and all disorder in another;
+// `lat` gives the shape its checks and each sample's disorder its validation ("Tempering ensembles")
+struct tsu_pte3d : pte_handle {
     tsu_ising3d* lat;
 };
 
@@ -441,6 +448,37 @@ __global__ __launch_bounds__(256, 2) void k8_pt_sweep(PT3Params p, int colour) {
     else k8_pt_octet<1>(p, z, r, q, g0, g1);
 }
 
+// The ensemble's sample index: grid z of the sweep = sample * groups + walker group, walkers [base + group W, ..) clipped to the
+// sample's own [base, base + nper), base = sample * nper; the sample's disorder sits dstride floats after its predecessor's
+struct PTEns {
+    long long dstride;  // floats of a sample's disorder (4 planes)
+    int nper;           // walkers of a sample (nl * R)
+    int groups;         // walker groups of a sample: ceil(nper / W)
+};
+
+__device__ __forceinline__ void pte_sample(PT3Params& p, const PTEns& e, int sample) {
+    const long long off = (long long)sample * e.dstride;
+    p.jr += off;
+    p.jd += off;
+    p.jl += off;
+    p.h += off;
+}
+
+// k8_pt_sweep for an ensemble, a kernel of its own so that the ladders' code object stays what it was: the same lane and the same
+// octet, for the walkers of one group of one sample on that sample's disorder.  The sample and its offsets are wave-uniform.
+__global__ __launch_bounds__(256, 2) void k8_pte_sweep(PT3Params p, PTEns e, int colour) {
+    long long rho;
+    int q;
+    if (!k8_lane(p, rho, q)) return;
+    const int z = (int)(rho / p.rows), r = (int)(rho - (long long)z * p.rows);
+    const int sample = blockIdx.z / e.groups, group = blockIdx.z - sample * e.groups;
+    const int base = sample * e.nper;
+    const int g0 = base + group * p.W, g1 = min(g0 + p.W, base + e.nper);
+    pte_sample(p, e, sample);
+    if (((z + r + colour) & 1) == 0) k8_pt_octet<0>(p, z, r, q, g0, g1);
+    else k8_pt_octet<1>(p, z, r, q, g0, g1);
+}
+
 __device__ __forceinline__ K8Params pt_walker_params(const PT3Params& pp, int g) {
     K8Params p;
     p.s = pp.s[g];
@@ -465,6 +503,18 @@ __device__ __forceinline__ K8Params pt_walker_params(const PT3Params& pp, int g)
 
 // grid (blocks_for(lattice), nw): workgroup x of walker y computes k8_energy's partial x of that walker alone, and its sum of spins
 __global__ __launch_bounds__(256) void k8_pt_energy(PT3Params pp, double* __restrict__ part, long long* __restrict__ ipart) {
+    long long m;
+    const double e = block_sum(k8_energy_lane(pt_walker_params(pp, blockIdx.y), m));
+    const long long ms = block_isum(m);
+    if (threadIdx.x == 0) {
+        part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
+        ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
+    }
+}
+
+// k8_pt_energy for an ensemble: walker y on the disorder of its sample y / nper
+__global__ __launch_bounds__(256) void k8_pte_energy(PT3Params pp, PTEns en, double* __restrict__ part, long long* __restrict__ ipart) {
+    pte_sample(pp, en, blockIdx.y / en.nper);
     long long m;
     const double e = block_sum(k8_energy_lane(pt_walker_params(pp, blockIdx.y), m));
     const long long ms = block_isum(m);
@@ -550,6 +600,51 @@ PT3Params pt_params(const tsu_pt3d* P) {
 // k8_pt_energy into d_part / d_ipart (asynchronous): the partial pass pt_host.h's energies take
 auto pt_partials(tsu_pt3d* P, const PT3Params& p) {
     return [P, &p](unsigned blocks) { k8_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
+}
+
+void pte_free(tsu_pte3d* P) { pte_delete(P, tsu_ising3d_destroy); }
+
+// the ladders' parameters for an ensemble: sample 0's disorder (the kernels add the sample's offset), the walkers of all samples
+PT3Params pte_params(const tsu_pte3d* P) {
+    const K8Params k = make_params(P->lat);
+    PT3Params p;
+    p.s = P->d_s;
+    p.key = P->d_key;
+    p.slot = P->d_slot;
+    p.T = P->d_T;
+    p.c32 = P->d_c32;
+    p.jr = P->d_dis;
+    p.jd = P->d_dis + P->plane;
+    p.jl = P->d_dis + 2 * P->plane;
+    p.h = P->d_dis + 3 * P->plane;
+    p.pitch = k.pitch;
+    p.nrows = k.nrows;
+    p.depth = k.depth;
+    p.rows = k.rows;
+    p.cols = k.cols;
+    p.pz = k.pz;
+    p.pr = k.pr;
+    p.pc = k.pc;
+    p.lshift = k.lshift;
+    p.nw = P->nw;
+    p.W = 1;
+    p.hs = 0;
+    return p;
+}
+
+PTEns pte_ens(const tsu_pte3d* P, int W) {
+    PTEns e;
+    e.dstride = 4 * (long long)P->plane;
+    e.nper = P->nl * P->R;
+    e.groups = (int)pte_groups(P, W);
+    return e;
+}
+
+// k8_pte_energy into d_part / d_ipart (asynchronous)
+auto pte_partials(tsu_pte3d* P, const PT3Params& p, const PTEns& e) {
+    return [P, &p, &e](unsigned blocks) {
+        k8_pte_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, e, P->d_part, P->d_ipart);
+    };
 }
 
 void pa_free(tsu_pa3d* P) { pop_delete(P, tsu_ising3d_destroy); }
@@ -1004,6 +1099,145 @@ int tsu_pt3d_set_link_overlap(tsu_pt3d* P, int enable) {
 int tsu_pt3d_history_link(tsu_pt3d* P, int64_t* L) {
     TSU_ENTER(P ? P->ctx : nullptr);
     return P ? pt_history_link(P, L) : TSU_E_INVALID;
+}
+
+// ------------------------------------------------------------------ tempering ensembles
+int tsu_pte3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_mask, int n_samples, int n_temps, int n_ladders,
+                     tsu_pte3d** out) {
+    TSU_ENTER(ctx);
+    if (!ctx || !out) return TSU_E_INVALID;
+    return pte_create(
+        ctx, "pte3d", n_samples, n_temps, n_ladders, out,
+        [=](tsu_pte3d* P) {
+            const int rc = tsu_ising3d_create(ctx, depth, rows, cols, periodic_mask, &P->lat);
+            if (rc != TSU_OK) return rc;
+            P->nrows = (long long)P->lat->depth * P->lat->rows;
+            P->pitch = (long long)P->lat->pitch;
+            P->cols = P->lat->cols;
+            P->n_axes = 3;
+            P->lrows = P->lat->rows;
+            P->axis_len[0] = P->lat->depth;
+            P->axis_len[1] = P->lat->rows;
+            P->axis_len[2] = P->lat->cols;
+            P->axis_per[0] = P->lat->pz;
+            P->axis_per[1] = P->lat->pr;
+            P->axis_per[2] = P->lat->pc;
+            P->n_dis = 4;
+            return (int)TSU_OK;
+        },
+        pte_free);
+}
+
+int tsu_pte3d_destroy(tsu_pte3d* P) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_OK;
+    (void)hipStreamSynchronize(P->ctx->stream);
+    pte_free(P);
+    return TSU_OK;
+}
+
+int tsu_pte3d_set_disorder(tsu_pte3d* P, const float* J_right, const float* J_down, const float* J_layer, const float* h) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const float* src[4] = {J_right, J_down, J_layer, h};
+    return pte_set_disorder(
+        P, src, (size_t)P->nrows * P->cols, [](tsu_pte3d* E) { return E->lat->d_dis; },
+        [](tsu_ising3d* L, const float* const* a) { return tsu_ising3d_set_disorder(L, a[0], a[1], a[2], a[3]); });
+}
+
+int tsu_pte3d_set_temperatures(tsu_pte3d* P, const double* T) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_set_temperatures(P, T) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_init(tsu_pte3d* P, const uint64_t* seeds, int initial) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pte_init(P, seeds, initial) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_run(tsu_pte3d* P, int n_rounds, int swap_interval, int do_swap, int record) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    tsu_ctx* ctx = P->ctx;
+    const int rc = pt_run_check(P, P->have_disorder, n_rounds, swap_interval);
+    if (rc != TSU_OK) return rc;
+    PT3Params p = pte_params(P);
+    p.W = pt_group(P);
+    const PTEns e = pte_ens(P, p.W);
+    const dim3 og = octet_grid(make_params(P->lat));
+    const dim3 grid(og.x, og.y, (unsigned)P->S * (unsigned)e.groups);
+    return pt_run(
+        P, n_rounds, swap_interval, do_swap, record,
+        [&](uint32_t hs, int colour) {
+            p.hs = hs;
+            k8_pte_sweep<<<grid, 256, 0, ctx->stream>>>(p, e, colour);
+        },
+        pte_partials(P, p, e), [] { return (int)TSU_OK; });
+}
+
+int tsu_pte3d_history(tsu_pte3d* P, double* E, int64_t* M, int64_t* q, int32_t* walker) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history(P, E, M, q, walker) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_stats(tsu_pte3d* P, int64_t* attempts, int64_t* accepts, int64_t* round_trips, int32_t* walker_at_slot,
+                    uint64_t* sweep_count, uint64_t* round_count) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_stats(P, attempts, accepts, round_trips, walker_at_slot, sweep_count, round_count) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_energies(tsu_pte3d* P, double* E, int64_t* sum_s) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const PT3Params p = pte_params(P);
+    const PTEns e = pte_ens(P, 1);
+    return pt_energies(P, P->have_disorder, E, sum_s, pte_partials(P, p, e));
+}
+
+int tsu_pte3d_get_spins(tsu_pte3d* P, int sample, int ladder, int slot, int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pte_get_spins(P, sample, ladder, slot, host) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_set_spins(tsu_pte3d* P, int sample, int ladder, int slot, const int8_t* host) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pte_set_spins(P, sample, ladder, slot, host) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_launch_count(tsu_pte3d* P, uint64_t* n) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return pt_launch_count(P, n);
+}
+
+int tsu_pte3d_set_correlation(tsu_pte3d* P, int enable, const double* cos_z, const double* sin_z, const double* cos_r,
+                              const double* sin_r, const double* cos_c, const double* sin_c) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    const double* cs[3] = {cos_z, cos_r, cos_c};
+    const double* sn[3] = {sin_z, sin_r, sin_c};
+    return pt_set_correlation(P, enable, cs, sn);
+}
+
+int tsu_pte3d_history_modes(tsu_pte3d* P, double* modes) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history_modes(P, modes) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_set_link_overlap(tsu_pte3d* P, int enable) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_set_link_overlap(P, enable) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_history_link(tsu_pte3d* P, int64_t* L) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    return P ? pt_history_link(P, L) : TSU_E_INVALID;
+}
+
+int tsu_pte3d_profiles(tsu_pte3d* P, int sample, int slot, int64_t* p_z, int64_t* p_r, int64_t* p_c) {
+    TSU_ENTER(P ? P->ctx : nullptr);
+    if (!P) return TSU_E_INVALID;
+    int64_t* out[3] = {p_z, p_r, p_c};
+    return pt_profiles(P, slot, out, sample);
 }
 
 // ------------------------------------------------------------------ population annealing

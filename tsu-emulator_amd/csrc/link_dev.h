@@ -109,13 +109,15 @@ __global__ __launch_bounds__(256) void link_pass(const int8_t* __restrict__ a, c
     if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out), (unsigned long long)v);
 }
 
-// grid (blocks, R): L of the two ladders' walkers at slot y (a population: of the walkers y and y + R), added into out[y] (a zeroed
-// history row); the planes are found as pt_overlap finds them
+// grid (blocks, S R): L of the two ladders' walkers of sample y / R at slot y % R (a population: one sample, the walkers y and
+// y + R), added into out[y] (a zeroed history row [sample][slot]); the planes are found as pt_overlap finds them
 __global__ __launch_bounds__(256) void pt_link(int8_t* const* __restrict__ s, const int32_t* __restrict__ was, int R, LinkArgs p,
                                                long long* __restrict__ out) {
-    const int i = blockIdx.y;
+    const int y = blockIdx.y, smp = y / R, i = y - smp * R;
+    s += (size_t)smp * 2 * R;
+    was += (size_t)smp * 2 * R;
     const long long v = block_isum(link_lane(s[was[i]], s[R + was[R + i]], p));
-    if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out + i), (unsigned long long)v);
+    if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out + y), (unsigned long long)v);
 }
 
 // The launch shape of a link pass: the workgroups per plane pair.  Bands of 8 rows where that still leaves a lane for every thread

@@ -4,6 +4,10 @@
 // dimension passes in how it launches a half-sweep and an energy partial pass, and a hook a round runs between the two;
 // everything else of create, set_temperatures, init, run, history, stats and energies is here.  Messages carry the ladder's name
 // ("pt2d" / "pt3d") as their prefix.  Internal linkage throughout, as pt_dev.h.
+//
+// A pt_ladder holds S disorder samples (pt_ladder.h): 1 for the two ladder handles, any number for a tempering ensemble (pte_host.h,
+// "pte2d" / "pte3d"), which brings its own create, set_disorder and init and shares everything else here.  Every table, history row
+// and launch below is sized by S, with the sample as the leading index; with S = 1 they are what they were.
 #pragma once
 #include <cmath>
 #include <cstdlib>
@@ -31,14 +35,19 @@ void pt_free_history(pt_ladder* P) {
     P->hist_cap = 0;
 }
 
-// the handle with its tables, history and walkers (destroy(lat[g]) frees one)
-template <class H, class Destroy>
-void pt_delete(H* P, Destroy destroy) {
+// the tables and the history
+void pt_free_tables(pt_ladder* P) {
     void* bufs[] = {P->d_s, P->d_key, P->d_slot, P->d_was, P->d_flag, P->d_T, P->d_c32, P->d_att, P->d_acc,
-                    P->d_trips, P->d_part, P->d_ipart, P->d_E, P->d_M, P->d_prof, P->d_tab};
+                    P->d_trips, P->d_part, P->d_ipart, P->d_E, P->d_M, P->d_prof, P->d_tab, P->d_skey};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     pt_free_history(P);
+}
+
+// the handle with its tables, history and walkers (destroy(lat[g]) frees one)
+template <class H, class Destroy>
+void pt_delete(H* P, Destroy destroy) {
+    pt_free_tables(P);
     if (P->lat) {
         for (int g = 0; g < P->nw; ++g)
             if (P->lat[g]) (void)destroy(P->lat[g]);
@@ -50,7 +59,7 @@ void pt_delete(H* P, Destroy destroy) {
 // every walker at its own slot, the walker at slot 0 "bottom", no attempts, accepts or round trips (synchronises)
 int pt_reset(pt_ladder* P) {
     tsu_ctx* ctx = P->ctx;
-    const int R = P->R, nl = P->nl;
+    const int R = P->R, nl = P->S * P->nl;  // the ladders of all samples
     std::vector<int32_t> ident((size_t)nl * R), flag((size_t)nl * R, kPtNone);
     for (int k = 0; k < nl; ++k) {
         for (int w = 0; w < R; ++w) ident[(size_t)k * R + w] = w;
@@ -72,7 +81,7 @@ int pt_reset(pt_ladder* P) {
 // the device tables of a ladder whose walkers exist (planes[g] = walker g's spin plane), reset (synchronises)
 int pt_alloc_tables(pt_ladder* P, int8_t* const* planes) {
     tsu_ctx* ctx = P->ctx;
-    const size_t nw = (size_t)P->nw, nlR = (size_t)P->nl * P->R, R = (size_t)P->R;
+    const size_t nw = (size_t)P->nw, nlR = nw, R = (size_t)P->R;
     hipError_t e = hipSuccess;
     auto alloc = [&e](auto*& ptr, size_t bytes) {
         if (e == hipSuccess) e = hipMalloc((void**)&ptr, bytes);
@@ -84,8 +93,8 @@ int pt_alloc_tables(pt_ladder* P, int8_t* const* planes) {
     alloc(P->d_flag, nlR * sizeof(int32_t));
     alloc(P->d_T, R * sizeof(double));
     alloc(P->d_c32, R * sizeof(float));
-    alloc(P->d_att, (size_t)P->nl * (R - 1) * sizeof(long long));
-    alloc(P->d_acc, (size_t)P->nl * (R - 1) * sizeof(long long));
+    alloc(P->d_att, (size_t)P->S * P->nl * (R - 1) * sizeof(long long));
+    alloc(P->d_acc, (size_t)P->S * P->nl * (R - 1) * sizeof(long long));
     alloc(P->d_trips, nlR * sizeof(long long));
     alloc(P->d_part, nw * kEnergyBlocks * sizeof(double));
     alloc(P->d_ipart, nw * kEnergyBlocks * sizeof(long long));
@@ -115,6 +124,7 @@ int pt_create(tsu_ctx* ctx, const char* name, int n_temps, int n_ladders, H** ou
     P->name = name;
     P->R = n_temps;
     P->nl = n_ladders;
+    P->S = 1;
     P->nw = n_temps * n_ladders;
     P->lat = new (std::nothrow) std::remove_pointer_t<decltype(P->lat)>[P->nw]();
     int rc = P->lat ? TSU_OK : tsu_fail(ctx, TSU_E_NOMEM, "%s_create: host allocation failed", name);
@@ -138,7 +148,8 @@ long long pt_lanes(const pt_ladder* P) { return P->nrows * ((P->cols + 15) / 16)
 
 // Walkers per lane of the ladder sweeps (k7_pt_sweep, k8_pt_sweep): the fewest groups that still give >= 1024 lanes per CU (a
 // lane per octet and group), so a large lattice reads each octet's disorder once for many walkers and a small one spreads its
-// walkers over the chip.  TSU_PT_GROUP=w (read per call) forces w.
+// walkers over the chip.  TSU_PT_GROUP=w (read per call) forces w.  An ensemble counts the walkers of all its samples here and
+// keeps a group within one sample's walkers (pt_group).
 int pt_group_of(const tsu_ctx* ctx, long long lanes, int nw) {
     if (const char* e = getenv("TSU_PT_GROUP")) {
         const int w = atoi(e);
@@ -150,7 +161,10 @@ int pt_group_of(const tsu_ctx* ctx, long long lanes, int nw) {
     return (int)((nw + groups - 1) / groups);
 }
 
-int pt_group(const pt_ladder* P) { return pt_group_of(P->ctx, pt_lanes(P), P->nw); }
+int pt_group(const pt_ladder* P) {
+    const int w = pt_group_of(P->ctx, pt_lanes(P), P->nw), per = P->nl * P->R;
+    return w < per ? w : per;
+}
 
 int pt_set_temperatures(pt_ladder* P, const double* T) {
     tsu_ctx* ctx = P->ctx;
@@ -226,7 +240,7 @@ template <class H>
 size_t pt_mode_doubles(const H* P) { return 2 * (size_t)pt_periodic_axes(P); }
 
 dim3 pt_profile_plan(const pt_ladder* P, ProfArgs& pa) {
-    return profile_plan(pa, P->pitch, P->pitch, P->nrows, P->lrows, P->cols, P->n_axes == 3, (unsigned)P->R);
+    return profile_plan(pa, P->pitch, P->pitch, P->nrows, P->lrows, P->cols, P->n_axes == 3, (unsigned)(P->S * P->R));
 }
 
 // where the mode pass finds each periodic axis's profile and tables
@@ -251,7 +265,7 @@ ModeArgs pt_mode_args(const H* P) {
 
 int pt_prof_scratch(pt_ladder* P, const char* op) {
     if (P->d_prof) return TSU_OK;
-    const hipError_t e = hipMalloc((void**)&P->d_prof, (size_t)P->R * pt_prof_len(P) * sizeof(long long));
+    const hipError_t e = hipMalloc((void**)&P->d_prof, (size_t)P->S * P->R * pt_prof_len(P) * sizeof(long long));
     if (e == hipSuccess) return TSU_OK;
     (void)hipGetLastError();
     return tsu_fail(P->ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP, "%s_%s: %s", P->name, op, hipGetErrorString(e));
@@ -302,22 +316,23 @@ int pt_set_correlation(pt_ladder* P, int enable, const double* const* cs, const 
     return TSU_OK;
 }
 
-// the modes of the last run's rows, [round][slot][periodic axis][re, im] (synchronises)
+// the modes of the last run's rows, [round][sample][slot][periodic axis][re, im] (synchronises)
 int pt_history_modes(pt_ladder* P, double* modes) {
     tsu_ctx* ctx = P->ctx;
     TSU_REQUIRE(ctx, modes, "%s_history_modes: NULL output", P->name);
     TSU_REQUIRE(ctx, P->hist_modes, "%s_history_modes: the last run recorded no modes (call tsu_%s_set_correlation before a recording run)",
                 P->name, P->name);
-    const size_t n = (size_t)P->hist_rounds * P->R * pt_mode_doubles(P);
+    const size_t n = (size_t)P->hist_rounds * P->S * P->R * pt_mode_doubles(P);
     if (n) TSU_HIP_TRY(ctx, hipMemcpyAsync(modes, P->d_hF, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSU_OK;
 }
 
-// the profiles of the walkers now at `slot` (the product of the two ladders' walkers if there are two), axis a into out[a]
-// (synchronises)
-int pt_profiles(pt_ladder* P, int slot, int64_t* const* out) {
+// the profiles of the walkers of `sample` now at `slot` (the product of the two ladders' walkers if there are two), axis a into
+// out[a] (synchronises)
+int pt_profiles(pt_ladder* P, int slot, int64_t* const* out, int sample = 0) {
     tsu_ctx* ctx = P->ctx;
+    TSU_REQUIRE(ctx, sample >= 0 && sample < P->S, "%s_profiles: sample %d out of range (%d samples)", P->name, sample, P->S);
     TSU_REQUIRE(ctx, slot >= 0 && slot < P->R, "%s_profiles: slot %d out of range (%d temperatures)", P->name, slot, P->R);
     for (int a = 0; a < P->n_axes; ++a) TSU_REQUIRE(ctx, out[a], "%s_profiles: NULL output", P->name);
     const int rc = pt_prof_scratch(P, "profiles");
@@ -325,10 +340,10 @@ int pt_profiles(pt_ladder* P, int slot, int64_t* const* out) {
     const long long len = pt_prof_len(P);
     ProfArgs pa;
     const dim3 grid = pt_profile_plan(P, pa);
-    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_prof, 0, (size_t)P->R * len * sizeof(long long), ctx->stream));
+    TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_prof, 0, (size_t)P->S * P->R * len * sizeof(long long), ctx->stream));
     pt_profile<<<grid, 256, 0, ctx->stream>>>(P->d_s, P->d_was, P->R, P->nl, pa, P->d_prof, len);
     TSU_HIP_TRY(ctx, hipGetLastError());
-    const long long* row = P->d_prof + (size_t)slot * len;
+    const long long* row = P->d_prof + ((size_t)sample * P->R + slot) * len;
     for (int a = 0; a < P->n_axes; ++a) {
         TSU_HIP_TRY(ctx, hipMemcpyAsync(out[a], row, (size_t)P->axis_len[a] * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
         row += P->axis_len[a];
@@ -365,13 +380,13 @@ int pt_set_link_overlap(pt_ladder* P, int enable) {
     return TSU_OK;
 }
 
-// L of the last run's rows, [round][slot] (synchronises)
+// L of the last run's rows, [round][sample][slot] (synchronises)
 int pt_history_link(pt_ladder* P, int64_t* L) {
     tsu_ctx* ctx = P->ctx;
     TSU_REQUIRE(ctx, L, "%s_history_link: NULL output", P->name);
     TSU_REQUIRE(ctx, P->hist_link, "%s_history_link: the last run recorded no link overlap (call tsu_%s_set_link_overlap before a recording run)",
                 P->name, P->name);
-    const size_t n = (size_t)P->hist_rounds * P->R;
+    const size_t n = (size_t)P->hist_rounds * P->S * P->R;
     if (n) TSU_HIP_TRY(ctx, hipMemcpyAsync(L, P->d_hL, n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSU_OK;
@@ -393,20 +408,22 @@ int pt_run_check(pt_ladder* P, int have_disorder, int n_rounds, int swap_interva
 
 // n_rounds rounds after pt_run_check: swap_interval sweeps (sweep(hs, colour) enqueues half-sweep hs of all walkers), hook() (what
 // the dimension ends a round's sweeps with; returns a status), then, if the round swaps or records, the energies (partials as for
-// pt_enqueue_energies), the swap pass and q.  Nothing here waits for the device.
+// pt_enqueue_energies), the swap pass and q.  Every pass covers the S samples of the handle in its one launch: the sample is part
+// of a grid index and of the rows (history rows [round][sample][..]).  Nothing here waits for the device.
 template <class Sweep, class Partials, class Hook>
 int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int record, Sweep&& sweep, Partials&& partials, Hook&& hook) {
     tsu_ctx* ctx = P->ctx;
     const int R = P->R, nl = P->nl;
+    const size_t S = (size_t)P->S, SR = S * R;  // samples; the (sample, slot) rows of q, L and the modes
     if (record && P->hist_cap < (size_t)n_rounds) {
         pt_free_history(P);
-        const size_t n = (size_t)n_rounds * nl * R;
+        const size_t n = (size_t)n_rounds * SR * nl;
         hipError_t e = hipMalloc((void**)&P->d_hE, n * sizeof(double));
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hM, n * sizeof(long long));
         if (e == hipSuccess) e = hipMalloc((void**)&P->d_hW, n * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc((void**)&P->d_hq, (size_t)n_rounds * R * sizeof(long long));
-        if (e == hipSuccess && P->corr) e = hipMalloc((void**)&P->d_hF, (size_t)n_rounds * R * pt_mode_doubles(P) * sizeof(double));
-        if (e == hipSuccess && P->link) e = hipMalloc((void**)&P->d_hL, (size_t)n_rounds * R * sizeof(long long));
+        if (e == hipSuccess) e = hipMalloc((void**)&P->d_hq, (size_t)n_rounds * SR * sizeof(long long));
+        if (e == hipSuccess && P->corr) e = hipMalloc((void**)&P->d_hF, (size_t)n_rounds * SR * pt_mode_doubles(P) * sizeof(double));
+        if (e == hipSuccess && P->link) e = hipMalloc((void**)&P->d_hL, (size_t)n_rounds * SR * sizeof(long long));
         if (e != hipSuccess) {  // nothing of a history that does not fit stays behind
             pt_free_history(P);
             P->hist_rounds = 0;
@@ -418,11 +435,11 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
     }
     // pt_overlap adds into its row: every q row of this run starts at 0
     if (record && nl == 2 && n_rounds > 0)
-        TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hq, 0, (size_t)n_rounds * R * sizeof(long long), ctx->stream));
+        TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hq, 0, (size_t)n_rounds * SR * sizeof(long long), ctx->stream));
     P->hist_rounds = record ? n_rounds : 0;
     P->hist_modes = record && P->corr;
     P->hist_link = record && P->link && nl == 2;
-    if (P->hist_link && n_rounds > 0) TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hL, 0, (size_t)n_rounds * R * sizeof(long long), ctx->stream));
+    if (P->hist_link && n_rounds > 0) TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_hL, 0, (size_t)n_rounds * SR * sizeof(long long), ctx->stream));
     LinkArgs la;
     const unsigned lblocks = pt_link_plan(P, la);
     const unsigned blocks = reduce_blocks(pt_lanes(P));
@@ -444,6 +461,8 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
     sw.do_swap = do_swap ? 1 : 0;
     sw.k0 = P->key0;
     sw.k1 = P->key1;
+    sw.nl = nl;
+    sw.skey = P->d_skey;
     for (int t = 0; t < n_rounds; ++t) {
         for (int s = 0; s < swap_interval; ++s)
             for (int colour = 0; colour < 2; ++colour) {
@@ -455,21 +474,21 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
         if (rc != TSU_OK) return rc;
         if (do_swap || record) {
             pt_enqueue_energies(P, blocks, partials);
-            const size_t row = (size_t)t * nl * R;
+            const size_t row = (size_t)t * SR * nl;
             sw.hE = record ? P->d_hE + row : nullptr;
             sw.hM = record ? P->d_hM + row : nullptr;
             sw.hW = record ? P->d_hW + row : nullptr;
             sw.t = P->rounds;
-            k7_pt_swap<<<(unsigned)nl, 64, 0, ctx->stream>>>(sw);
+            k7_pt_swap<<<(unsigned)(S * nl), 64, 0, ctx->stream>>>(sw);
             if (record && nl == 2)
-                pt_overlap<<<dim3(blocks, (unsigned)R, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, P->pitch, P->nrows, P->cols,
-                                                                                 P->d_hq + (size_t)t * R);
-            if (P->hist_link) pt_link<<<dim3(lblocks, (unsigned)R, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, la, P->d_hL + (size_t)t * R);
+                pt_overlap<<<dim3(blocks, (unsigned)SR, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, P->pitch, P->nrows, P->cols,
+                                                                                  P->d_hq + (size_t)t * SR);
+            if (P->hist_link) pt_link<<<dim3(lblocks, (unsigned)SR, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, la, P->d_hL + (size_t)t * SR);
             if (P->hist_modes) {  // the walkers the pass left at each slot: their profiles, then the modes of the periodic axes
-                TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_prof, 0, (size_t)R * pt_prof_len(P) * sizeof(long long), ctx->stream));
+                TSU_HIP_TRY(ctx, hipMemsetAsync(P->d_prof, 0, SR * pt_prof_len(P) * sizeof(long long), ctx->stream));
                 pt_profile<<<pgrid, 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, nl, pa, P->d_prof, pt_prof_len(P));
-                pt_modes<<<dim3(2u * (unsigned)ma.n, (unsigned)R, 1), 256, 0, ctx->stream>>>(
-                    P->d_prof, pt_prof_len(P), ma, P->d_hF + (size_t)t * R * pt_mode_doubles(P));
+                pt_modes<<<dim3(2u * (unsigned)ma.n, (unsigned)SR, 1), 256, 0, ctx->stream>>>(
+                    P->d_prof, pt_prof_len(P), ma, P->d_hF + (size_t)t * SR * pt_mode_doubles(P));
             }
         }
         P->rounds += 1;
@@ -480,13 +499,13 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
 
 int pt_history(pt_ladder* P, double* E, int64_t* M, int64_t* q, int32_t* walker) {
     tsu_ctx* ctx = P->ctx;
-    const size_t n = (size_t)P->hist_rounds * P->nl * P->R;
+    const size_t n = (size_t)P->hist_rounds * P->nw;
     if (n) {
         if (E) TSU_HIP_TRY(ctx, hipMemcpyAsync(E, P->d_hE, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         if (M) TSU_HIP_TRY(ctx, hipMemcpyAsync(M, P->d_hM, n * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
         if (walker) TSU_HIP_TRY(ctx, hipMemcpyAsync(walker, P->d_hW, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         if (q && P->nl == 2)
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(q, P->d_hq, (size_t)P->hist_rounds * P->R * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+            TSU_HIP_TRY(ctx, hipMemcpyAsync(q, P->d_hq, (size_t)P->hist_rounds * P->S * P->R * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     }
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return TSU_OK;
@@ -495,7 +514,7 @@ int pt_history(pt_ladder* P, double* E, int64_t* M, int64_t* q, int32_t* walker)
 int pt_stats(pt_ladder* P, int64_t* attempts, int64_t* accepts, int64_t* round_trips, int32_t* walker_at_slot, uint64_t* sweep_count,
              uint64_t* round_count) {
     tsu_ctx* ctx = P->ctx;
-    const size_t pairs = (size_t)P->nl * (P->R - 1), nlR = (size_t)P->nl * P->R;
+    const size_t pairs = (size_t)P->S * P->nl * (P->R - 1), nlR = (size_t)P->nw;
     if (attempts) TSU_HIP_TRY(ctx, hipMemcpyAsync(attempts, P->d_att, pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (accepts) TSU_HIP_TRY(ctx, hipMemcpyAsync(accepts, P->d_acc, pairs * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
     if (round_trips) TSU_HIP_TRY(ctx, hipMemcpyAsync(round_trips, P->d_trips, nlR * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));

@@ -4,11 +4,13 @@
 #pragma once
 #include "pt_dev.h"  // kPtMaxTemps
 
-// n_ladders ladders of R walkers (whole lattices) on ONE disorder
+// S samples of n_ladders ladders of R walkers (whole lattices); a sample is ONE disorder.  The ladder handles have S = 1; a tempering
+// ensemble (pte_host.h) has S >= 1, and every table below gains the sample as its leading index: walker g = (s * nl + k) * R + w
 struct pt_ladder {
     tsu_ctx* ctx;
     const char* name;              // "pt2d" / "pt3d": the prefix of the messages
-    int R, nl, nw;                 // temperatures, ladders, walkers (R * nl)
+    int R, nl, nw;                 // temperatures, ladders, walkers (S * nl * R)
+    int S;                         // disorder samples (the ladder handles: 1)
     int have_T, have_init;
     uint32_t sweeps, rounds;       // sweeps of every walker and rounds since init
     unsigned long long launches;   // half-sweep launches
@@ -35,6 +37,7 @@ struct pt_ladder {
     int32_t* d_hW;
     long long* d_hq;               // [round][slot] (two ladders)
     uint32_t key0, key1;           // Philox key of the swap uniforms (the seed)
+    uint32_t* d_skey;              // sample -> (k0, k1) of the swap uniforms (ensembles; NULL: key0, key1)
     // correlation recording (corr_dev.h): the lattice's axes as the handle's create fills them in, then what set_correlation adds
     int n_axes, lrows;             // axes (2 or 3) and the rows of a layer (2-D: nrows)
     int axis_len[3], axis_per[3];  // length and periodic flag per axis, in axis order (2-D: rows, cols; 3-D: depth, rows, cols)

@@ -83,12 +83,15 @@ __device__ __forceinline__ long long pair_lane(const int8_t* __restrict__ a, con
     return sum;
 }
 
-// grid (blocks, R): q of the two ladders' walkers at slot y, added into out[y] (a zeroed history row)
+// grid (blocks, S R): q of the two ladders' walkers of sample y / R at slot y % R, added into out[y] (a zeroed history row
+// [sample][slot]); the tables are [sample][ladder][..] (a ladder handle and a population's pairs: one sample)
 __global__ __launch_bounds__(256) void pt_overlap(int8_t* const* __restrict__ s, const int32_t* __restrict__ was, int R,
                                                   long long pitch, long long nrows, int cols, long long* __restrict__ out) {
-    const int i = blockIdx.y;
+    const int y = blockIdx.y, smp = y / R, i = y - smp * R;
+    s += (size_t)smp * 2 * R;
+    was += (size_t)smp * 2 * R;
     const long long v = block_isum(pair_lane(s[was[i]], s[R + was[R + i]], pitch, pitch, nrows, cols));
-    if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out + i), (unsigned long long)v);
+    if (threadIdx.x == 0) atomicAdd(reinterpret_cast<unsigned long long*>(out + y), (unsigned long long)v);
 }
 
 // workgroups of an energy / overlap pass over `lanes` chunks of 16 columns

@@ -31,10 +31,16 @@ from .models import (  # noqa: F401
     IsingModel2D,
     IsingModel3D,
     LatticeTempering3D,
+    LatticeTemperingEnsemble,
+    LatticeTemperingEnsemble3D,
     PopulationAnnealing,
     PopulationAnnealing3D,
     demonstrate_phase_transition,
+    edwards_anderson_samples,
+    ensemble_summary,
     temperature_scan_3d,
+    tempering_ensemble_scan,
+    tempering_ensemble_scan_3d,
     tempering_scan_3d,
 )
 
@@ -45,4 +51,6 @@ __all__ = [
     "IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "demonstrate_phase_transition",
     "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d",
     "PopulationAnnealing", "PopulationAnnealing3D",
+    "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
+    "tempering_ensemble_scan", "tempering_ensemble_scan_3d",
 ]

@@ -213,6 +213,29 @@ OVERLAP_SIGNATURES = {
     "tsu_pa3d_history_overlap": (C.c_int, [_vp, _i64p, _i64p, _f64p]),
 }
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_ensemble.h (the header tsu_hip.h includes) one to one
+ENSEMBLE_SIGNATURES = {}
+for _pre, _shape, _nj in (("tsu_pte2d_", [C.c_int, C.c_int, C.c_int], 2), ("tsu_pte3d_", [C.c_int, C.c_int, C.c_int, C.c_int], 3)):
+    ENSEMBLE_SIGNATURES.update({
+        _pre + "create": (C.c_int, [_vp] + _shape + [C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+        _pre + "destroy": (C.c_int, [_vp]),
+        _pre + "set_disorder": (C.c_int, [_vp] + [_f32p] * (_nj + 1)),
+        _pre + "set_temperatures": (C.c_int, [_vp, _f64p]),
+        _pre + "init": (C.c_int, [_vp, _u64p, C.c_int]),
+        _pre + "run": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        _pre + "history": (C.c_int, [_vp, _f64p, _i64p, _i64p, _i32p]),
+        _pre + "stats": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i32p, _u64p, _u64p]),
+        _pre + "energies": (C.c_int, [_vp, _f64p, _i64p]),
+        _pre + "get_spins": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i8p]),
+        _pre + "set_spins": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _i8p]),
+        _pre + "launch_count": (C.c_int, [_vp, _u64p]),
+        _pre + "set_correlation": (C.c_int, [_vp, C.c_int] + [_f64p] * (2 * (_nj if _nj == 2 else 3))),
+        _pre + "history_modes": (C.c_int, [_vp, _f64p]),
+        _pre + "set_link_overlap": (C.c_int, [_vp, C.c_int]),
+        _pre + "history_link": (C.c_int, [_vp, _i64p]),
+        _pre + "profiles": (C.c_int, [_vp, C.c_int, C.c_int] + [_i64p] * _nj),
+    })
+
 _lib = None
 
 
@@ -230,7 +253,8 @@ def load_library():
     except OSError as e:  # missing ROCm runtime etc.
         raise HipUnavailableError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items())
-                              + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())):
+                              + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())
+                              + list(ENSEMBLE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -794,6 +818,137 @@ class TemperingLattice3D(_TemperingHandle):
         self._create(self.depth, self.rows, self.cols, sum(1 << a for a in range(3) if self.periodic[a]))
 
     def set_disorder(self, J_right, J_down, J_layer, h=None):
+        self._set_disorder((J_right, J_down, J_layer), h)
+
+
+ENSEMBLE_MAX_WALKERS = 65535
+
+
+class _EnsembleHandle(_TemperingHandle):
+    """What the tsu_pte2d and tsu_pte3d handles share: the ladders' calls with a leading sample axis on every array.  A subclass
+    sets ``_prefix`` and, in its constructor, ``shape``, ``periodic``, ``n_samples``, ``n_temps`` and ``n_ladders``, then calls
+    ``_create`` with the shape arguments of its create function."""
+
+    def _create(self, *shape_args):
+        self._recorded = 0
+        self._correlation = self._modes_recorded = False
+        self._link = self._link_recorded = False
+        h = _vp()
+        self.ctx.check(self._fn("create")(self.ctx.h, *shape_args, self.n_samples, self.n_temps, self.n_ladders, C.byref(h)))
+        self.h = h
+
+    def _set_disorder(self, arrays, h):
+        full = (self.n_samples,) + tuple(self.shape)
+        a = [np.ascontiguousarray(x, dtype=np.float32) for x in arrays]
+        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float32)
+        for x in a + ([] if hh is None else [hh]):
+            if x.shape != full:
+                raise ValueError(f"disorder arrays must have shape {full}, got {x.shape}")
+        self.ctx.check(self._fn("set_disorder")(self.h, *[_ptr(x, _f32p) for x in a], None if hh is None else _ptr(hh, _f32p)))
+
+    def init(self, seeds, initial=0):
+        """seeds: one uint64 per sample.  initial 0: random (walker (s, k, w) draws as the lattice's randomize(seeds[s] + k R + w));
+        +1 / -1: all up / down."""
+        sd = np.ascontiguousarray([int(x) & 0xFFFFFFFFFFFFFFFF for x in seeds], dtype=np.uint64)
+        if sd.shape != (self.n_samples,):
+            raise ValueError(f"need {self.n_samples} seeds, got {sd.size}")
+        self.ctx.check(self._fn("init")(self.h, _ptr(sd, _u64p), int(initial)))
+        self._recorded = 0
+
+    def history_modes(self):
+        """The last run's modes as complex128 (n_rounds, n_samples, n_temps, n_periodic_axes); raises if that run recorded none."""
+        n_per = sum(self._periodic_flags())
+        n = self._recorded if self._modes_recorded else 0
+        out = np.zeros((n, self.n_samples, self.n_temps, n_per, 2))
+        self.ctx.check(self._fn("history_modes")(self.h, _ptr(out, _f64p)))
+        return out[..., 0] + 1j * out[..., 1]
+
+    def profiles(self, sample, slot):
+        """Axis profiles (int64) of the walker of ``sample`` now at ``slot``: of its spins, or with two ladders of the product."""
+        out = tuple(np.zeros(n, np.int64) for n in self.shape)
+        self.ctx.check(self._fn("profiles")(self.h, int(sample), int(slot), *[_ptr(a, _i64p) for a in out]))
+        return out
+
+    def history(self):
+        """The last run's rows: E, M (sum of spins), walker as (n_rounds, n_samples, n_ladders, n_temps); q as (n_rounds, n_samples,
+        n_temps) or None; q_link like q, only if that run recorded the link overlap."""
+        n, S, nl, R = self._recorded, self.n_samples, self.n_ladders, self.n_temps
+        E = np.zeros((n, S, nl, R))
+        M = np.zeros((n, S, nl, R), np.int64)
+        W = np.zeros((n, S, nl, R), np.int32)
+        q = np.zeros((n, S, R), np.int64) if nl == 2 else None
+        self.ctx.check(self._fn("history")(self.h, _ptr(E, _f64p), _ptr(M, _i64p), None if q is None else _ptr(q, _i64p),
+                                           _ptr(W, _i32p)))
+        out = {"E": E, "M": M, "walker": W, "q": q}
+        if self._link_recorded:
+            out["q_link"] = np.zeros((n, S, R), np.int64)
+            self.ctx.check(self._fn("history_link")(self.h, _ptr(out["q_link"], _i64p)))
+        return out
+
+    def stats(self):
+        S, nl, R = self.n_samples, self.n_ladders, self.n_temps
+        att, acc = np.zeros((S, nl, R - 1), np.int64), np.zeros((S, nl, R - 1), np.int64)
+        trips, was = np.zeros((S, nl, R), np.int64), np.zeros((S, nl, R), np.int32)
+        sw, rd = C.c_uint64(0), C.c_uint64(0)
+        self.ctx.check(self._fn("stats")(self.h, _ptr(att, _i64p), _ptr(acc, _i64p), _ptr(trips, _i64p), _ptr(was, _i32p),
+                                         C.byref(sw), C.byref(rd)))
+        return {"attempts": att, "accepts": acc, "round_trips": trips, "walker_at_slot": was, "sweep_count": sw.value,
+                "round_count": rd.value}
+
+    def energies(self):
+        """(E, sum of spins) of every walker now, as (n_samples, n_ladders, n_temps) arrays indexed by walker."""
+        E = np.zeros((self.n_samples, self.n_ladders, self.n_temps))
+        M = np.zeros((self.n_samples, self.n_ladders, self.n_temps), np.int64)
+        self.ctx.check(self._fn("energies")(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
+        return E, M
+
+    def get_spins(self, sample, ladder, slot):
+        out = np.empty(self.shape, dtype=np.int8)
+        self.ctx.check(self._fn("get_spins")(self.h, int(sample), int(ladder), int(slot), _ptr(out, _i8p)))
+        return out
+
+    def set_spins(self, sample, ladder, slot, spins):
+        s = np.ascontiguousarray(spins, dtype=np.int8).reshape(self.shape)
+        self.ctx.check(self._fn("set_spins")(self.h, int(sample), int(ladder), int(slot), _ptr(s, _i8p)))
+
+
+class TemperingEnsemble(_EnsembleHandle):
+    """tsu_pte2d handle (K7 tempering ensemble): n_samples disorder samples x n_ladders ladders x n_temps walkers of one rows x cols
+    lattice, every pass of a round one launch for all samples.  Walker w of ladder k of sample s has Philox key
+    seeds[s] + k n_temps + w and starts at slot w: sample s is a TemperingLattice on its disorder with seed seeds[s], bit for bit."""
+
+    _prefix = "tsu_pte2d_"
+
+    def __init__(self, rows, cols, periodic, n_samples, n_temps, n_ladders=1, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.rows, self.cols, self.periodic = int(rows), int(cols), bool(periodic)
+        self.shape = (self.rows, self.cols)
+        self.n_samples, self.n_temps, self.n_ladders = int(n_samples), int(n_temps), int(n_ladders)
+        self._create(self.rows, self.cols, int(self.periodic))
+
+    def set_disorder(self, J_right, J_down, h=None):
+        """(n_samples, rows, cols) arrays, rounded once to fp32 (h=None: zero field)."""
+        self._set_disorder((J_right, J_down), h)
+
+
+class TemperingEnsemble3D(_EnsembleHandle):
+    """tsu_pte3d handle (K8 tempering ensemble): TemperingEnsemble for depth x rows x cols lattices; sample s is a
+    TemperingLattice3D on its disorder with seed seeds[s], bit for bit.  ``periodic``: a bool or a triple (p_z, p_r, p_c)."""
+
+    _prefix = "tsu_pte3d_"
+
+    def __init__(self, depth, rows, cols, periodic, n_samples, n_temps, n_ladders=1, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.depth, self.rows, self.cols = int(depth), int(rows), int(cols)
+        self.shape = (self.depth, self.rows, self.cols)
+        self.periodic = periodic_axes(periodic)
+        self.n_samples, self.n_temps, self.n_ladders = int(n_samples), int(n_temps), int(n_ladders)
+        self._create(self.depth, self.rows, self.cols, sum(1 << a for a in range(3) if self.periodic[a]))
+
+    def set_disorder(self, J_right, J_down, J_layer, h=None):
+        """(n_samples, depth, rows, cols) arrays, rounded once to fp32 (h=None: zero field)."""
         self._set_disorder((J_right, J_down, J_layer), h)
 
 

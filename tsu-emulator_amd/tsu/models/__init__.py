@@ -1,8 +1,12 @@
 """Energy-based models (reference: tsu/models/__init__.py:11-13) plus the README's IsingModel2D facade."""
 from .ising import (IsingChain, IsingConfig, IsingGrid, IsingModel, IsingModel2D, IsingModel3D, LatticeTempering, LatticeTempering3D, PopulationAnnealing,
                     PopulationAnnealing3D, population_annealing_scan, population_annealing_scan_3d,
-                    demonstrate_phase_transition, temperature_scan, temperature_scan_3d, tempering_scan, tempering_scan_3d)
+                    demonstrate_phase_transition, temperature_scan, temperature_scan_3d, tempering_scan, tempering_scan_3d,
+                    LatticeTemperingEnsemble, LatticeTemperingEnsemble3D, edwards_anderson_samples, ensemble_summary,
+                    tempering_ensemble_scan, tempering_ensemble_scan_3d)
 
 __all__ = ["IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "IsingConfig", "demonstrate_phase_transition", "temperature_scan",
            "LatticeTempering", "tempering_scan", "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d",
-           "PopulationAnnealing", "PopulationAnnealing3D", "population_annealing_scan", "population_annealing_scan_3d"]
+           "PopulationAnnealing", "PopulationAnnealing3D", "population_annealing_scan", "population_annealing_scan_3d",
+           "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
+           "tempering_ensemble_scan", "tempering_ensemble_scan_3d"]

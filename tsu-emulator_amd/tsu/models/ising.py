@@ -1383,6 +1383,353 @@ def tempering_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: 
     return _tempering_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
 
 
+# ---------------------------------------------------------------------------------------------------- tempering ensembles
+ENSEMBLE_MAX_WALKERS = 65535  # samples x ladders x temperatures one launch covers
+
+
+def edwards_anderson_samples(size, n_samples: int, kind: str = "bimodal", seed: int = 0, dims: int = 3, periodic=True):
+    """Couplings of ``n_samples`` Edwards-Anderson disorder samples: a tuple ``(J_right, J_down)`` (``dims=2``) or ``(J_right, J_down,
+    J_layer)`` (``dims=3``) of float32 arrays of shape ``(n_samples, *lattice)``, the ``couplings=`` of the ensembles.
+
+    Sample s is drawn from ``np.random.default_rng([seed, s])`` in the order J_right, J_down, (J_layer), every bond of every site:
+    ``kind="bimodal"`` gives +-1 with equal probability, ``"gaussian"`` a standard normal.  So sample s does not depend on
+    ``n_samples``, and not on the boundary either: the bonds that would cross an open boundary (the last column of J_right, the last
+    row of J_down, the last layer of J_layer) are drawn like the others, so the stream stays the same, and then stored as 0 where
+    ``periodic`` (a bool, or one flag per axis in the lattice's axis order) says the axis is open, because the lattices refuse a
+    non-zero bond there; on a periodic axis they are the wrap bonds."""
+    if dims not in (2, 3):
+        raise ValueError("dims must be 2 or 3")
+    if kind not in ("bimodal", "gaussian"):
+        raise ValueError("kind must be 'bimodal' or 'gaussian'")
+    shape = (size,) * dims if np.isscalar(size) else tuple(int(n) for n in size)
+    if len(shape) != dims or min(shape) < 1:
+        raise ValueError(f"size must be an int or {dims} positive ints, got {size!r}")
+    S = int(n_samples)
+    if S < 1:
+        raise ValueError("n_samples must be >= 1")
+    per = (bool(periodic),) * dims if isinstance(periodic, (bool, np.bool_)) else tuple(bool(x) for x in periodic)
+    if len(per) != dims:
+        raise ValueError(f"periodic must be a bool or {dims} flags")
+    out = [np.zeros((S,) + shape, np.float32) for _ in range(dims)]
+    for smp in range(S):
+        rng = np.random.default_rng([int(seed), smp])
+        for a in out:
+            a[smp] = (2.0 * rng.integers(0, 2, size=shape) - 1.0) if kind == "bimodal" else rng.standard_normal(shape)
+    # out[j] holds the bonds along lattice axis dims - 1 - j (J_right: the last axis)
+    for j, a in enumerate(out):
+        axis = dims - 1 - j
+        if not per[axis]:
+            a[(slice(None),) * (axis + 1) + (-1,)] = 0.0
+    return tuple(out)
+
+
+def ensemble_seeds(seed: int, n_samples: int, ladders: int, n_temps: int) -> List[int]:
+    """``seeds[s] = seed + s * ladders * n_temps``: the walkers of sample s take the keys seeds[s] .. seeds[s] + ladders * n_temps - 1,
+    so no two walkers of the ensemble share a key."""
+    return [int(seed) + s * int(ladders) * int(n_temps) for s in range(int(n_samples))]
+
+
+def _sem(x) -> np.ndarray:
+    """Standard error of the mean over the leading (sample) axis; NaN for a single sample."""
+    x = np.asarray(x, dtype=np.float64)
+    if x.shape[0] < 2:
+        return np.full(x.shape[1:], np.nan)
+    return np.std(x, axis=0, ddof=1) / np.sqrt(x.shape[0])
+
+
+def _jackknife(fn, *arrays):
+    """(estimate, error) of ``fn(mean over samples of each array)``: the estimate from the full means, the error from the
+    delete-one jackknife over the leading (sample) axis, sqrt((S - 1) / S * sum_i (theta_i - mean theta)^2); NaN for one sample."""
+    arrays = [np.asarray(a, dtype=np.float64) for a in arrays]
+    S = arrays[0].shape[0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        est = np.asarray(fn(*[a.mean(axis=0) for a in arrays]), dtype=np.float64)
+        if S < 2:
+            return est, np.full(est.shape, np.nan)
+        tot = [a.sum(axis=0) for a in arrays]
+        th = np.stack([np.asarray(fn(*[(t - a[i]) / (S - 1) for t, a in zip(tot, arrays)]), dtype=np.float64) for i in range(S)])
+        return est, np.sqrt((S - 1) / S * np.sum((th - th.mean(axis=0)) ** 2, axis=0))
+
+
+def ensemble_summary(samples: dict, n_spins: Optional[int] = None, lengths=None, periodic=None) -> dict:
+    """Disorder averages [.]_J over the leading sample axis of the per-sample arrays of a tempering-ensemble scan.
+
+    Plain means, each with ``<key>_err`` = the standard error of the mean over samples, of whichever of these ``samples`` holds:
+    ``energy`` [<e>], ``magnetization``, ``overlap`` [<|q|>], ``overlap_sq`` [<q^2>], ``link_overlap`` [q_l].  Ratios, averaged first
+    and divided afterwards, each with a delete-one jackknife error over samples: ``binder`` = (3 - [<q^4>] / [<q^2>]^2) / 2 from
+    ``overlap_4`` and ``overlap_sq``; and, from ``F2`` (<|F(k_min)|^2> per axis, NaN on open axes) and ``f2`` (<f_tot^2>) with
+    ``n_spins``, ``lengths`` and ``periodic``: ``chi_k`` = [F2] / N (a plain mean, with its standard error), ``xi`` =
+    :func:`correlation_length` of ([f2], [F2]) per axis and ``xi_over_L`` = its mean over the periodic axes of xi_d / L_d."""
+    out = {}
+    for k in ("energy", "magnetization", "overlap", "overlap_sq", "link_overlap"):
+        if k in samples:
+            x = np.asarray(samples[k], dtype=np.float64)
+            out[k] = x.mean(axis=0)
+            out[k + "_err"] = _sem(x)
+    if "overlap_4" in samples and "overlap_sq" in samples:
+        out["binder"], out["binder_err"] = _jackknife(lambda q4, q2: 0.5 * (3.0 - q4 / q2 ** 2), samples["overlap_4"], samples["overlap_sq"])
+    if "F2" in samples and "f2" in samples:
+        if n_spins is None or lengths is None or periodic is None:
+            raise ValueError("the correlation averages need n_spins, lengths and periodic")
+        per = np.asarray(periodic, dtype=bool)
+        L = np.asarray(lengths, dtype=np.float64)
+        F2 = np.asarray(samples["F2"], dtype=np.float64)
+        out["chi_k"] = F2.mean(axis=0) / n_spins
+        out["chi_k_err"] = _sem(F2) / n_spins
+        out["xi"], out["xi_err"] = _jackknife(lambda f, F: correlation_length(f, F, L), samples["f2"], F2)
+        out["xi_over_L"], out["xi_over_L_err"] = _jackknife(
+            lambda f, F: np.mean(correlation_length(f, F, L)[..., per] / L[per], axis=-1), samples["f2"], F2)
+    return out
+
+
+class _LatticeTemperingEnsemble(_LatticeTempering):
+    """What :class:`LatticeTemperingEnsemble` and :class:`LatticeTemperingEnsemble3D` share.  A subclass parses its shape into
+    ``self.shape``, sets ``self.periodic`` and names the per-sample validation of its disorder (``_sample_disorder``) and its handle
+    (``_handle``)."""
+
+    def __init__(self, size, temperatures, *, couplings, field=None, periodic=True, seeds=None, seed: Optional[int] = None,
+                 initial: str = "random", ladders: int = 1, correlation: bool = False, link_overlap: bool = False):
+        self._parse_shape(size, periodic)
+        self.n_spins = int(np.prod(self.shape))
+        self._check_ladder(temperatures, ladders, initial)
+        self._set_correlation(correlation)
+        self._set_link_overlap(link_overlap)
+        self._disorder = self._ensemble_disorder(couplings, field)
+        S, R = self.n_samples, self.temperatures.size
+        if S * self.ladders * R > ENSEMBLE_MAX_WALKERS:
+            raise ValueError(f"{S} samples x {self.ladders} ladder(s) x {R} temperatures = {S * self.ladders * R} walkers: one ensemble "
+                             f"holds at most {ENSEMBLE_MAX_WALKERS}")
+        if seeds is not None and seed is not None:
+            raise ValueError("give either seeds= (one per sample) or seed=, not both")
+        if seeds is None:
+            if seed is None:
+                seed = int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31)
+            seeds = ensemble_seeds(seed, S, self.ladders, R)
+        seeds = [int(x) for x in seeds]
+        if len(seeds) != S:
+            raise ValueError(f"need one seed per sample ({S}), got {len(seeds)}")
+        if any(not 0 <= x < 2 ** 64 for x in seeds):
+            raise ValueError("seeds must fit an unsigned 64-bit integer")
+        self.seeds = seeds
+        pt = self._pt = self._handle()
+        pt.set_disorder(*self._disorder)
+        pt.set_temperatures(self.temperatures)
+        if self.link_overlap:
+            pt.set_link_overlap(True)
+        if self.correlation:
+            pt.set_correlation(True, [_kmin_tables(n) if per else None for n, per in zip(pt.shape, self._axes_periodic())])
+        pt.init(self.seeds, _PT_INITIAL[initial])
+
+    def _ensemble_disorder(self, couplings, field):
+        """Before any device call: the sample count from the leading axis, then every sample through the ladders' validation."""
+        nj = len(self.shape)
+        if couplings is None or len(couplings) != nj:
+            raise ValueError(f"couplings must be {nj} arrays of shape (n_samples,) + {self.shape}")
+        arrs = [np.asarray(a) for a in couplings] + ([] if field is None else [np.asarray(field)])
+        names = ["J_right", "J_down", "J_layer"][:nj] + ["field"]
+        for a, name in zip(arrs, names):
+            if a.ndim != nj + 1 or a.shape[1:] != self.shape:
+                raise ValueError(f"{name} must have shape (n_samples,) + {self.shape}, got {a.shape}")
+        S = arrs[0].shape[0]
+        if S < 1:
+            raise ValueError("an ensemble needs at least one disorder sample")
+        for a, name in zip(arrs, names):
+            if a.shape[0] != S:
+                raise ValueError(f"{name} has {a.shape[0]} samples, J_right has {S}")
+        self.n_samples = int(S)
+        per = [self._sample_disorder(tuple(a[s] for a in arrs[:nj]), None if field is None else arrs[nj][s]) for s in range(S)]
+        out = [np.stack([p[j] for p in per]) for j in range(nj)]
+        return tuple(out) + (None if field is None else np.stack([p[nj] for p in per]),)
+
+    def close(self) -> None:
+        self._pt.close()
+
+    def _check_sample(self, sample):
+        if not 0 <= sample < self.n_samples:
+            raise ValueError(f"sample {sample} out of range ({self.n_samples} samples)")
+
+    def history(self, sample: Optional[int] = None, ladder: int = 0) -> dict:
+        """The rounds recorded by the last ``run``, the keys of :meth:`LatticeTempering.history`: for one ``sample`` its ladder's
+        arrays, (n_rounds, R) (``modes``: (n_rounds, R, n_axes)); for ``sample=None`` all samples, with a leading sample axis."""
+        if sample is not None:
+            self._check_sample(sample)
+        h = self._pt.history()
+        out = {k: np.ascontiguousarray(np.moveaxis(h[k][:, :, ladder], 1, 0)) for k in ("E", "M", "walker")}
+        for k in ("q", "q_link"):
+            if h.get(k) is not None:
+                out[k] = np.ascontiguousarray(np.moveaxis(h[k], 1, 0))
+        if self.correlation:
+            per = np.asarray(self._axes_periodic(), dtype=bool)
+            got = np.moveaxis(self._pt.history_modes(), 1, 0)
+            modes = np.full(got.shape[:3] + (per.size,), complex(np.nan, np.nan), dtype=np.complex128)
+            modes[..., per] = got
+            out["modes"] = modes
+        return out if sample is None else {k: np.ascontiguousarray(v[sample]) for k, v in out.items()}
+
+    def axis_profiles(self, sample: int, slot: int) -> tuple:
+        self._check_sample(sample)
+        self._check_slot(slot, 0)
+        return self._pt.profiles(sample, slot)
+
+    @property
+    def acceptance(self) -> np.ndarray:
+        """(n_samples, R - 1): accepted / attempted swaps per adjacent pair of slots of each sample, its ladders pooled."""
+        st = self._pt.stats()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return st["accepts"].sum(axis=1) / st["attempts"].sum(axis=1)
+
+    @property
+    def acceptance_pooled(self) -> np.ndarray:
+        """(R - 1,): the same with all samples pooled."""
+        st = self._pt.stats()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return st["accepts"].sum(axis=(0, 1)) / st["attempts"].sum(axis=(0, 1))
+
+    @property
+    def round_trips(self) -> np.ndarray:
+        """(n_samples,): round trips completed by all walkers of all ladders of each sample."""
+        return self._pt.stats()["round_trips"].sum(axis=(1, 2))
+
+    @property
+    def walker_at_slot(self) -> np.ndarray:
+        """(n_samples, ladders, R): which walker sits at each slot."""
+        return self._pt.stats()["walker_at_slot"]
+
+    def spins(self, sample: int, slot: int, ladder: int = 0) -> np.ndarray:
+        self._check_sample(sample)
+        self._check_slot(slot, ladder)
+        return self._pt.get_spins(sample, ladder, slot)
+
+    def energy(self, sample: int, slot: int, ladder: int = 0) -> float:
+        self._check_sample(sample)
+        self._check_slot(slot, ladder)
+        E, _ = self._pt.energies()
+        return float(E[sample, ladder, self._pt.stats()["walker_at_slot"][sample, ladder, slot]])
+
+
+class LatticeTemperingEnsemble(_LatticeTemperingEnsemble):
+    """Parallel tempering of many disorder samples of one 2-D lattice at once (K7): sample s is :class:`LatticeTempering` on
+    ``couplings[j][s]`` / ``field[s]`` with ``seed=seeds[s]``, bit for bit, but every kernel of a round covers all samples in one
+    launch, which is what fills the chip at the lattice sizes a disorder average uses.
+
+    ``couplings=(J_right, J_down)`` of shape ``(S, rows, cols)``, ``field`` ``(S, rows, cols)`` or None; one temperature table for
+    all samples; ``seeds`` a length-S sequence, or ``seed`` for ``seeds[s] = seed + s * ladders * R``.  Everything is validated and
+    rounded to float32 before any device call.  At most 65535 walkers (S x ladders x R).  No replica cluster moves."""
+
+    def _parse_shape(self, size, periodic):
+        self.rows, self.cols = self.shape = tuple(int(n) for n in ((size, size) if np.isscalar(size) else size))
+        self.periodic = bool(periodic)
+
+    def _sample_disorder(self, couplings, field):
+        return _disorder_arrays(self.rows, self.cols, self.periodic, 1.0, 0.0, "physical", couplings, field)
+
+    def _handle(self):
+        return _hip.TemperingEnsemble(self.rows, self.cols, self.periodic, self.n_samples, self.temperatures.size, self.ladders)
+
+
+class LatticeTemperingEnsemble3D(_LatticeTemperingEnsemble):
+    """:class:`LatticeTemperingEnsemble` for the cubic lattices of :class:`IsingModel3D` (K8): sample s is
+    :class:`LatticeTempering3D` on its disorder with ``seed=seeds[s]``, bit for bit.  ``couplings=(J_right, J_down, J_layer)`` of
+    shape ``(S, depth, rows, cols)``; ``periodic`` a bool or a triple (p_z, p_r, p_c)."""
+
+    def _parse_shape(self, size, periodic):
+        self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
+        self.periodic = _hip.periodic_axes(periodic)
+
+    def _sample_disorder(self, couplings, field):
+        return _tempering_disorder_3d(self.shape, self.periodic, 1.0, 0.0, couplings, field)
+
+    def _handle(self):
+        return _hip.TemperingEnsemble3D(self.depth, self.rows, self.cols, self.periodic, self.n_samples, self.temperatures.size,
+                                        self.ladders)
+
+
+def _ensemble_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap) -> dict:
+    """The body of the ensemble scans on a fresh ensemble ``pt``, closed at the end: per sample the expressions of
+    ``_tempering_scan`` on that sample's rows, stacked, then ``ensemble_summary`` of them under ``"average"``."""
+    try:
+        pt.run(int(n_equilibrate) // int(measure_every), int(measure_every), swap=swap, record=False)
+        pt.run(int(n_measure), int(measure_every), swap=swap, record=True)
+        hist = pt._pt.history()
+        modes = pt.history()["modes"] if pt.correlation else None
+        st = pt._pt.stats()
+        N, S = pt.n_spins, pt.n_samples
+        per_sample = []
+        for s in range(S):
+            out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
+            out["temperatures"] = temperatures
+            Ms = np.ascontiguousarray(hist["M"][:, s, 0].T) / N
+            Es = np.ascontiguousarray(hist["E"][:, s, 0].T)
+            Qs = np.ascontiguousarray(hist["q"][:, s].T) / N if pt.ladders == 2 else None
+            out = _scan_summary(out, N, Ms, Es, Qs)
+            if Qs is not None:
+                out["overlap_4"] = np.mean(Qs ** 4, axis=1)
+            if pt.link_overlap:
+                out["link_overlap"] = np.mean(np.ascontiguousarray(hist["q_link"][:, s]), axis=0) / lattice_bond_count(
+                    pt._pt.shape, pt._axes_periodic())
+            if pt.correlation:
+                out["F2"] = np.mean(np.abs(np.ascontiguousarray(modes[s])) ** 2, axis=0)
+                out["f2"] = np.mean((Qs if pt.ladders == 2 else Ms) ** 2, axis=1) * float(N) ** 2
+                _correlation_summary(out, N, pt._pt.shape, pt._axes_periodic(), out["f2"], out["F2"])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out["swap_acceptance"] = st["accepts"][s].sum(axis=0) / st["attempts"][s].sum(axis=0)
+            out["round_trips"] = int(st["round_trips"][s].sum())
+            del out["temperatures"]
+            per_sample.append(out)
+        res = {k: np.stack([np.asarray(o[k]) for o in per_sample]) for k in per_sample[0]}
+        res["temperatures"] = temperatures
+        res["average"] = ensemble_summary(res, N, pt._pt.shape, pt._axes_periodic())
+    finally:
+        pt.close()
+    return res
+
+
+def _ensemble_scan_args(measure_every, n_equilibrate, replicas, link_overlap):
+    if replicas not in (1, 2):
+        raise ValueError("replicas must be 1 or 2")
+    if link_overlap and replicas != 2:
+        raise ValueError("link_overlap=True compares the two replicas at one temperature: it needs replicas=2")
+    if int(measure_every) < 1 or int(n_equilibrate) % int(measure_every):
+        raise ValueError("n_equilibrate must be a multiple of measure_every")
+
+
+def tempering_ensemble_scan(size, temperatures, *, couplings, field=None, n_equilibrate: int = 1000, n_measure: int = 50,
+                            measure_every: int = 10, periodic: bool = True, seeds=None, seed: Optional[int] = None,
+                            initial: str = "up", replicas: int = 1, swap: bool = True, correlation: bool = False,
+                            link_overlap: bool = False) -> dict:
+    """:func:`tempering_scan` of S disorder samples at once (:class:`LatticeTemperingEnsemble`) and their disorder average.
+
+    Every key of ``tempering_scan(..., couplings=sample s, seed=seeds[s])`` comes back with a leading sample axis, ``(S, R)`` for the
+    per-temperature ones, equal to that call's bit for bit; plus per sample ``overlap_4`` (<q^4>) and, with ``correlation``, ``F2``
+    and ``f2`` (what the averages of the ratios need).  ``"average"``: :func:`ensemble_summary` of these arrays, the disorder
+    averages with their errors over samples.  ``seeds`` / ``seed`` as for the ensemble (default ``seed=0``)."""
+    _ensemble_scan_args(measure_every, n_equilibrate, replicas, link_overlap)
+    if correlation:
+        _check_correlation((bool(periodic),))
+    if seeds is None and seed is None:
+        seed = 0
+    temperatures = np.asarray(temperatures, dtype=float)
+    pt = LatticeTemperingEnsemble(size, temperatures, couplings=couplings, field=field, periodic=periodic, seeds=seeds, seed=seed,
+                                  initial=initial, ladders=replicas, correlation=correlation, link_overlap=link_overlap)
+    return _ensemble_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
+
+
+def tempering_ensemble_scan_3d(size, temperatures, *, couplings, field=None, n_equilibrate: int = 1000, n_measure: int = 50,
+                               measure_every: int = 10, periodic=True, seeds=None, seed: Optional[int] = None, initial: str = "up",
+                               replicas: int = 1, swap: bool = True, correlation: bool = False, link_overlap: bool = False) -> dict:
+    """:func:`tempering_ensemble_scan` for cubic lattices: :func:`tempering_scan_3d` of S disorder samples at once
+    (:class:`LatticeTemperingEnsemble3D`), per sample and disorder-averaged."""
+    _ensemble_scan_args(measure_every, n_equilibrate, replicas, link_overlap)
+    if correlation:
+        _check_correlation(_hip.periodic_axes(periodic))
+    if seeds is None and seed is None:
+        seed = 0
+    temperatures = np.asarray(temperatures, dtype=float)
+    pt = LatticeTemperingEnsemble3D(size, temperatures, couplings=couplings, field=field, periodic=periodic, seeds=seeds, seed=seed,
+                                    initial=initial, ladders=replicas, correlation=correlation, link_overlap=link_overlap)
+    return _ensemble_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
+
+
 # ---------------------------------------------------------------------------------------------------- population annealing
 POPULATION_WEIGHT_ONE = 1 << 30  # the weight of a step's minimum-energy walker
 
