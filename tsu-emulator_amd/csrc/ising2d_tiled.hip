@@ -4,6 +4,10 @@
 // identical); what changes is the schedule:
 //   * a workgroup stages a (H + 4k) x (16 WO + 32) tile of the int8 lattice into LDS, de-interleaved into two
 //     colour planes of 0/1 "up" flags (8 same-colour sites of a row = one octet = one uint64),
+//   * keeps the two planes interleaved row by row: behind one guard octet, tile row r is its NO = WO + 2 octets of plane 0
+//     followed by its NO octets of plane 1, then one spare row and the 25 thresholds of the tie path.  Row stride (2 NO octets)
+//     and plane distance (NO octets) are compile-time constants for a tile of any height, so the pair loop carries ONE LDS
+//     address and every read and write of a pair is that address plus an immediate (see pair_step),
 //   * runs 2k half-sweeps entirely in LDS (the region that is still exact shrinks by one site per half-sweep:
 //     2k halo rows, one halo octet = 16 columns >= 2k each side), and
 //   * writes the H x 16 WO interior to the OTHER lattice buffer (neighbouring tiles read this tile's pre-launch
@@ -14,6 +18,10 @@
 //   one Philox4x32-10 block -> 8 x 16 random bits; neighbour sums with packed byte adds; 16-bit thresholds
 //   picked per site with v_perm_b32 byte look-ups; v_pk_sub_i16 (saturating) compares two sites per
 //   instruction; only an exact tie of the top 16 bits (2^-16 per site) evaluates the low half.
+// The form of the pair loop (plain / EDGE / SEAM / OPEN) and par0, the column parity of the colour updated in a half-sweep's first
+// row, are fixed per tile: half-sweep hsi starts at tile row 1 + hsi and updates colour hsi & 1, whose sum is always odd, so par0
+// depends on the parity of the window's first global row alone (odd only for a row slab that starts on an odd row).  Both are
+// decided once per tile; the half-sweeps run two per trip, colour 0 then colour 1, with the colour a template parameter.
 #include "ising2d.h"
 
 #include <type_traits>
@@ -124,22 +132,19 @@ static __device__ __forceinline__ u32x4 philox_vk(uint32_t c0, uint32_t c1, uint
 }
 
 struct Rows2Ctx {
-    const void* Ps;  // source / destination colour plane (uint64 octets, or uint32 octets in the nibble form)
-    void* Pd;
     const uint64_t* s_thr;
-    int tr_lo, npairs;   // first tile row of the half-sweep's range, number of row pairs
-    int rgf;             // global row of tile row tr_lo (wrapped)
     int total_rows;
-    int rg_tile0, wrap_tr;  // EDGE tiles: global row of tile row 0 (wrapped); the tile row whose global row is 0 again
-    uint32_t hs, tag_hi, tag_lo, k0, k1;
+    int rg_tile0, wrap_tr;  // global row of tile row 0 (wrapped on a periodic lattice); EDGE tiles: the tile row whose global row is 0 again
+    uint32_t tag_hi, tag_lo, k0, k1;
     uint32_t tblH0, tblH1, tblL0, tblL1;
     uint32_t t3H0, t3H1, t3L0, t3L1;  // open lattices: degree 3 / degree 2 byte tables
     int last_row;                     // open lattices: global index of the lattice's bottom row
     bool lft, rgt;                    // open lattices: this thread's octet holds the lattice's first / last column
     uint32_t r_par, r_slot;           // open lattices: column parity of the last column and its site within the octet
     uint32_t rm_lo, rm_hi;            // 0xFF at that site's byte
-    uint64_t vm_e, vm_o;              // open lattices: 0x01 for the even / odd columns of this octet that exist
-    int sh_next, sh_prev;             // periodic lattices of ragged width (SEAM): where the wrap meets this octet, see sweep_pairs
+    uint64_t vm_e, vm_o;              // open lattices: 0x01 for the even / odd columns of this octet that exist (byte planes)
+    uint32_t nvm_e, nvm_o;            // the same in the nibble layout (nibble planes)
+    int sh_next, sh_prev;             // periodic lattices of ragged width (SEAM): where the wrap meets this octet, see pair_step
 };
 
 // thresholds for the 8 sites of one octet given their up-counts, compared with one Philox block: d < 0 = accept
@@ -219,93 +224,135 @@ static __device__ __forceinline__ void edge_rows(const Rows2Ctx& c, int to_wrap,
     }
 }
 
-// P0 = column parity of the updated colour in row tr_lo (and 1-P0 in the row below it)
-template <int NO, int P0, bool EDGE, bool OPEN, bool SEAM = false>
-static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const PhiloxKeys& K, int tr_first, int tr_end, int step_rows, int oct,
+// ---- LDS layout of a tile and the pair loop's addressing
+// The two colour planes are interleaved row by row: tile row r holds its NO octets of plane 0 and then its NO octets of
+// plane 1, so a row is 2 NO octets and the distance between the planes is NO octets -- compile-time constants whatever the
+// tile's height.  The pair loop keeps ONE address, the LDS byte address of (row tr - 1, its octet, source plane), and
+// reaches the four rows it reads, the two side octets and the two octets it writes through the offset field of the DS
+// instructions.  "Octet -1" and "octet NO" of a row are the last / first octet of the other plane's row next to it (for
+// plane 0 of row 0: the guard octet, for plane 1 of the last row: the spare row): 0/1 flags that, like every neighbour beyond
+// the tile, only feed the far side of a halo octet.  They lie in the plane that the half-sweep WRITES: the threads of octets 0 and
+// NO - 1 read them while another wave may be storing them, without synchronisation.  Either value is a 0/1 flag and the sites
+// it reaches never count, so results do not depend on it -- but the contents of the halo octets' far side (columns that a
+// tile computes along and discards) are not deterministic from run to run.  Nothing may rely on them: compare or dump interiors.
+#define TSU_LDS __attribute__((address_space(3)))
+static __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const TSU_LDS char*)p; }
+template <typename T>
+static __device__ __forceinline__ T lds_ld(uint32_t a) { return *(const TSU_LDS T*)(uintptr_t)a; }
+template <typename T>
+static __device__ __forceinline__ void lds_st(uint32_t a, T v) { *(TSU_LDS T*)(uintptr_t)a = v; }
+
+// every indexer of the colour planes outside the pair loop: octet o of tile row r of plane pl
+template <typename E, int NO>
+struct TilePlanes {
+    E* base;  // plane 0, row 0, octet 0
+    __device__ __forceinline__ E& at(int pl, int r, int o) const { return base[(2 * r + pl) * NO + o]; }
+};
+
+// One pair of rows (tr, tr + 1) of one octet column; a = LDS byte address of (row tr - 1, this octet, source plane).
+// KAPPA = colour of the half-sweep (the destination plane; the source is the other one)
+// P0 = column parity of the updated colour in row tr (and 1-P0 in the row below it); it is the same for every half-sweep of
+// a tile: the first row of half-sweep hsi is tile row 1 + hsi and its colour hsi & 1, and their sum is always odd
+template <int NO, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM>
+static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t a, int rg, int to_wrap,
+                                                 uint32_t cq) {
+    constexpr int RS = 2 * NO * 8;                    // row stride
+    constexpr int DO = (KAPPA ? NO : -NO) * 8;        // source plane -> destination plane
+    // issue the six LDS reads, run the two Philox blocks (which do not depend on them) while they are in flight,
+    // and only then consume the neighbour rows
+    const uint64_t R0 = lds_ld<uint64_t>(a), R1 = lds_ld<uint64_t>(a + RS);
+    const uint64_t R2 = lds_ld<uint64_t>(a + 2 * RS), R3 = lds_ld<uint64_t>(a + 3 * RS);
+    // side octets: the last site of the previous octet (the top byte of its high dword) or the first site of the next one.  One of
+    // the two reads is volatile so that they stay two ds_read_b32 with 16-bit offset fields: paired into a ds_read2_b32, whose
+    // offset fields are 8 bits of dwords, they would need a second base register for NO = 34, i.e. an add per iteration.
+    // (This steers the compiler's load pairing, which skips volatile accesses; results do not depend on it.  Whether it still
+    // holds after a compiler change shows in tools/k1_loop_counts.py: the plain byte loop then has 6 v_add_u32 instead of 5.
+    // Reading the one byte that is used, ds_read_u8, also avoids the pairing but cost a v_and in the EDGE loops.)
+    const uint32_t A0 = SEAM ? 0u : (P0 ? lds_ld<volatile uint32_t>(a + RS + 8) : lds_ld<uint32_t>(a + RS - 4));
+    const uint32_t A1 = SEAM ? 0u : (P0 ? lds_ld<uint32_t>(a + 2 * RS - 4) : lds_ld<volatile uint32_t>(a + 2 * RS + 8));
+    // SEAM (a periodic lattice whose width is not a multiple of 16, workgroups whose window holds the wrap): the last
+    // octet of a row has only v sites per colour, so the site after its last one is site 0 of octet 0, and the site
+    // before site 0 of octet 0 is that last one: the whole neighbouring octet is read and the one byte that crosses
+    // over is taken from / put at position v - 1 instead of 7 (sh_next / sh_prev; 56 for every other octet)
+    const uint64_t Na = SEAM ? lds_ld<uint64_t>(a + RS + (P0 ? 8 : -8)) : 0ull;
+    const uint64_t Nb = SEAM ? lds_ld<uint64_t>(a + 2 * RS + (P0 ? -8 : 8)) : 0ull;
+    __builtin_amdgcn_sched_barrier(0);  // the reads stay above the Philox blocks ...
+    int rga = rg, rgb = rg + 1;
+    if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
+    const u32x4 w0 = philox_vk(cq, (uint32_t)rga, hs, c.tag_hi, K);
+    const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, hs, c.tag_hi, K);
+    __builtin_amdgcn_sched_barrier(0);  // ... and their first use stays below
+    const uint32_t C0l = (uint32_t)R1, C0h = (uint32_t)(R1 >> 32), C1l = (uint32_t)R2, C1h = (uint32_t)(R2 >> 32);
+    // horizontal neighbours: compact bytes (j, j+1) when the parity is 1, (j-1, j) when it is 0
+    uint32_t S0l = P0 ? __builtin_amdgcn_alignbyte(C0h, C0l, 1) : __builtin_amdgcn_alignbyte(C0l, A0, 3);
+    uint32_t S0h = P0 ? __builtin_amdgcn_alignbyte(A0, C0h, 1) : __builtin_amdgcn_alignbyte(C0h, C0l, 3);
+    uint32_t S1l = P0 ? __builtin_amdgcn_alignbyte(C1l, A1, 3) : __builtin_amdgcn_alignbyte(C1h, C1l, 1);
+    uint32_t S1h = P0 ? __builtin_amdgcn_alignbyte(C1h, C1l, 3) : __builtin_amdgcn_alignbyte(A1, C1h, 1);
+    if (SEAM) {
+        const uint64_t nxa = (Na & 0xFFull) << c.sh_next, pva = (Na >> c.sh_prev) & 0xFFull;
+        const uint64_t nxb = (Nb & 0xFFull) << c.sh_next, pvb = (Nb >> c.sh_prev) & 0xFFull;
+        const uint64_t Sa = P0 ? ((R1 >> 8) | nxa) : ((R1 << 8) | pva);
+        const uint64_t Sb = P0 ? ((R2 << 8) | pvb) : ((R2 >> 8) | nxb);
+        S0l = (uint32_t)Sa; S0h = (uint32_t)(Sa >> 32);
+        S1l = (uint32_t)Sb; S1h = (uint32_t)(Sb >> 32);
+    }
+    // R1 + R2 is shared by both rows' vertical+centre sums
+    const uint32_t ml = C0l + C1l, mh = C0h + C1h;
+    const uint32_t cnt0l = (uint32_t)R0 + ml + S0l, cnt0h = (uint32_t)(R0 >> 32) + mh + S0h;
+    const uint32_t cnt1l = (uint32_t)R3 + ml + S1l, cnt1h = (uint32_t)(R3 >> 32) + mh + S1h;
+    u32x4 d0, d1;
+    uint32_t edge_a = 0, edge_b = 0;
+    if (OPEN) {
+        // row a updates the columns of parity P0, row b those of parity 1 - P0: the lattice's first column is site 0
+        // of octet 0 for parity 0, its last column site r_slot of the last octet for parity r_par
+        const bool ea = rga == 0 || rga == c.last_row, eb = rgb == 0 || rgb == c.last_row;
+        const bool la = !P0 && c.lft, ra = c.rgt && c.r_par == (uint32_t)P0, lb = P0 && c.lft, rb = c.rgt && c.r_par != (uint32_t)P0;
+        d0 = compare_octet_open(w0, cnt0l, cnt0h, c, ea, la, ra);
+        d1 = compare_octet_open(w1, cnt1l, cnt1h, c, eb, lb, rb);
+        edge_a = (ea ? 1u : 0u) | (la ? 2u : 0u) | (ra ? 4u : 0u) | (c.r_slot << 4);
+        edge_b = (eb ? 1u : 0u) | (lb ? 2u : 0u) | (rb ? 4u : 0u) | (c.r_slot << 4);
+    } else {
+        d0 = compare_octet(w0, cnt0l, cnt0h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
+        d1 = compare_octet(w1, cnt1l, cnt1h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
+    }
+    const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
+    if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
+        if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga, hs, c.tag_lo, c.k0, c.k1, edge_a);
+        if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb, hs, c.tag_lo, c.k0, c.k1, edge_b);
+    }
+    uint64_t n0 = pack_flags(d0), n1 = pack_flags(d1);
+    if (OPEN) {  // what lies beyond the open edge stays empty (it is a neighbour of the edge sites in the next half-sweep)
+        n0 = (rga < 0 || rga > c.last_row) ? 0 : (n0 & (P0 ? c.vm_o : c.vm_e));
+        n1 = (rgb < 0 || rgb > c.last_row) ? 0 : (n1 & (P0 ? c.vm_e : c.vm_o));
+    }
+    if (SEAM) {  // the sites the last octet does not have stay empty
+        n0 &= c.vm_e;
+        n1 &= c.vm_e;
+    }
+    lds_st<uint64_t>(a + RS + DO, n0);
+    lds_st<uint64_t>(a + 2 * RS + DO, n1);
+}
+
+// One half-sweep of one thread: the pairs at tile rows tr, tr + 2 RL, ... of its octet column.  Every thread of the workgroup
+// has n or n + 1 of them: n iterations run under scalar loop control (no per-lane trip count), the last one under the lane
+// mask `tail`, and a wave none of whose lanes has one skips it.
+// a = LDS byte address of (row tr - 1, this octet, source plane) and rg = row number of tile row tr are the only per-lane
+// induction variables (kept opaque so that the compiler neither re-derives them from the trip counter nor the trip counter
+// from them); every other address is an immediate, see pair_step.
+// EDGE (the tile's window crosses the lattice's last row): rg counts tile rows and the wrap is applied per wave, see edge_rows
+template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM = false>
+static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t a, int rg, int n, bool tail,
                                                    uint32_t cq) {
-    // One byte offset into the source plane and one row counter are the only induction variables (kept opaque so
-    // that the compiler does not re-derive them from a separate trip counter); everything else is an immediate.
-    const char* const ps0 = reinterpret_cast<const char*>(c.Ps);
-    const int d_off = (int)(reinterpret_cast<const char*>(c.Pd) - ps0);
-    // this thread: the pairs at tile rows tr_first, tr_first + step_rows, ... < tr_end (tr_first has the parity of c.tr_lo)
-    const int off_end = tr_end * NO * 8;
-    const int off_step = step_rows * NO * 8;
-    int off = (tr_first * NO + oct) * 8;
-    // EDGE (the tile's window crosses the lattice's last row): rg counts tile rows and the wrap is applied per wave, see edge_rows
-    int rg = EDGE ? tr_first : c.rgf + (tr_first - c.tr_lo);
     int to_wrap = EDGE ? c.wrap_tr - __builtin_amdgcn_readfirstlane(rg) : 0;  // from the wave's first lane (lanes ascend in rows)
+    bool live = true;  // the last of the n + 1 trips runs under the lane mask `tail`: one copy of the body, a wave without a lane skips it
 #pragma unroll 1
-    for (; off < off_end; off += off_step, rg += step_rows, to_wrap -= step_rows) {
-        asm volatile("" : "+v"(off), "+v"(rg));
-        // issue the six LDS reads, run the two Philox blocks (which do not depend on them) while they are in flight,
-        // and only then consume the neighbour rows
-        const char* ps = ps0 + off;
-        const uint64_t R0 = *reinterpret_cast<const uint64_t*>(ps - NO * 8), R1 = *reinterpret_cast<const uint64_t*>(ps);
-        const uint64_t R2 = *reinterpret_cast<const uint64_t*>(ps + NO * 8), R3 = *reinterpret_cast<const uint64_t*>(ps + 2 * NO * 8);
-        const uint32_t A0 = SEAM ? 0u : *reinterpret_cast<const uint32_t*>(ps + (P0 ? 8 : -4));
-        const uint32_t A1 = SEAM ? 0u : *reinterpret_cast<const uint32_t*>(ps + NO * 8 + (P0 ? -4 : 8));
-        // SEAM (a periodic lattice whose width is not a multiple of 16, workgroups whose window holds the wrap): the last
-        // octet of a row has only v sites per colour, so the site after its last one is site 0 of octet 0, and the site
-        // before site 0 of octet 0 is that last one: the whole neighbouring octet is read and the one byte that crosses
-        // over is taken from / put at position v - 1 instead of 7 (sh_next / sh_prev; 56 for every other octet)
-        const uint64_t Na = SEAM ? *reinterpret_cast<const uint64_t*>(ps + (P0 ? 8 : -8)) : 0ull;
-        const uint64_t Nb = SEAM ? *reinterpret_cast<const uint64_t*>(ps + NO * 8 + (P0 ? -8 : 8)) : 0ull;
-        __builtin_amdgcn_sched_barrier(0);  // the reads stay above the Philox blocks ...
-        int rga = rg, rgb = rg + 1;
-        if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
-        const u32x4 w0 = philox_vk(cq, (uint32_t)rga, c.hs, c.tag_hi, K);
-        const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.hs, c.tag_hi, K);
-        __builtin_amdgcn_sched_barrier(0);  // ... and their first use stays below
-        const uint32_t C0l = (uint32_t)R1, C0h = (uint32_t)(R1 >> 32), C1l = (uint32_t)R2, C1h = (uint32_t)(R2 >> 32);
-        // horizontal neighbours: compact bytes (j, j+1) when the parity is 1, (j-1, j) when it is 0
-        uint32_t S0l = P0 ? __builtin_amdgcn_alignbyte(C0h, C0l, 1) : __builtin_amdgcn_alignbyte(C0l, A0, 3);
-        uint32_t S0h = P0 ? __builtin_amdgcn_alignbyte(A0, C0h, 1) : __builtin_amdgcn_alignbyte(C0h, C0l, 3);
-        uint32_t S1l = P0 ? __builtin_amdgcn_alignbyte(C1l, A1, 3) : __builtin_amdgcn_alignbyte(C1h, C1l, 1);
-        uint32_t S1h = P0 ? __builtin_amdgcn_alignbyte(C1h, C1l, 3) : __builtin_amdgcn_alignbyte(A1, C1h, 1);
-        if (SEAM) {
-            const uint64_t nxa = (Na & 0xFFull) << c.sh_next, pva = (Na >> c.sh_prev) & 0xFFull;
-            const uint64_t nxb = (Nb & 0xFFull) << c.sh_next, pvb = (Nb >> c.sh_prev) & 0xFFull;
-            const uint64_t Sa = P0 ? ((R1 >> 8) | nxa) : ((R1 << 8) | pva);
-            const uint64_t Sb = P0 ? ((R2 << 8) | pvb) : ((R2 >> 8) | nxb);
-            S0l = (uint32_t)Sa; S0h = (uint32_t)(Sa >> 32);
-            S1l = (uint32_t)Sb; S1h = (uint32_t)(Sb >> 32);
-        }
-        // R1 + R2 is shared by both rows' vertical+centre sums
-        const uint32_t ml = C0l + C1l, mh = C0h + C1h;
-        const uint32_t cnt0l = (uint32_t)R0 + ml + S0l, cnt0h = (uint32_t)(R0 >> 32) + mh + S0h;
-        const uint32_t cnt1l = (uint32_t)R3 + ml + S1l, cnt1h = (uint32_t)(R3 >> 32) + mh + S1h;
-        u32x4 d0, d1;
-        uint32_t edge_a = 0, edge_b = 0;
-        if (OPEN) {
-            // row a updates the columns of parity P0, row b those of parity 1 - P0: the lattice's first column is site 0
-            // of octet 0 for parity 0, its last column site r_slot of the last octet for parity r_par
-            const bool ea = rga == 0 || rga == c.last_row, eb = rgb == 0 || rgb == c.last_row;
-            const bool la = !P0 && c.lft, ra = c.rgt && c.r_par == (uint32_t)P0, lb = P0 && c.lft, rb = c.rgt && c.r_par != (uint32_t)P0;
-            d0 = compare_octet_open(w0, cnt0l, cnt0h, c, ea, la, ra);
-            d1 = compare_octet_open(w1, cnt1l, cnt1h, c, eb, lb, rb);
-            edge_a = (ea ? 1u : 0u) | (la ? 2u : 0u) | (ra ? 4u : 0u) | (c.r_slot << 4);
-            edge_b = (eb ? 1u : 0u) | (lb ? 2u : 0u) | (rb ? 4u : 0u) | (c.r_slot << 4);
-        } else {
-            d0 = compare_octet(w0, cnt0l, cnt0h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
-            d1 = compare_octet(w1, cnt1l, cnt1h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
-        }
-        const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
-        if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
-            if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga, c.hs, c.tag_lo, c.k0, c.k1, edge_a);
-            if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb, c.hs, c.tag_lo, c.k0, c.k1, edge_b);
-        }
-        char* pd = const_cast<char*>(ps) + d_off;
-        uint64_t n0 = pack_flags(d0), n1 = pack_flags(d1);
-        if (OPEN) {  // what lies beyond the open edge stays empty (it is a neighbour of the edge sites in the next half-sweep)
-            n0 = (rga < 0 || rga > c.last_row) ? 0 : (n0 & (P0 ? c.vm_o : c.vm_e));
-            n1 = (rgb < 0 || rgb > c.last_row) ? 0 : (n1 & (P0 ? c.vm_e : c.vm_o));
-        }
-        if (SEAM) {  // the sites the last octet does not have stay empty
-            n0 &= c.vm_e;
-            n1 &= c.vm_e;
-        }
-        *reinterpret_cast<uint64_t*>(pd) = n0;
-        *reinterpret_cast<uint64_t*>(pd + NO * 8) = n1;
+    for (int i = n; i >= 0; --i) {
+        if (i == 0) live = tail;
+        asm volatile("" : "+v"(a), "+v"(rg));
+        if (live) pair_step<NO, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, a, rg, to_wrap, cq);
+        a += 2 * RL * 2 * NO * 8;
+        rg += 2 * RL;
+        to_wrap -= 2 * RL;
     }
 }
 
@@ -327,7 +374,7 @@ static __device__ __forceinline__ uint32_t nib_shift_prev(uint32_t X, uint32_t M
     const uint32_t w = ((X << 4) & 0x10000000u) | (M >> 4);
     return __builtin_amdgcn_alignbit(X, w, 24);
 }
-// SEAM (periodic width not a multiple of 16, see sweep_pairs): the octet that crosses over sits at site v - 1 of the ragged
+// SEAM (periodic width not a multiple of 16, see pair_step): the octet that crosses over sits at site v - 1 of the ragged
 // last octet instead of site 7 -- bit position `pos` = 8 (j & 3) + 4 (j >> 2) of site j (28 for every other octet)
 static __device__ __forceinline__ uint32_t nib_shift_next_seam(uint32_t X, uint32_t N, int pos) {
     return nib_shift_next(X, 0u) | ((N & 0xFu) << pos);  // (site v of a ragged octet is empty, so the slot is free)
@@ -341,70 +388,112 @@ static __device__ __forceinline__ uint32_t nib_pack(const u32x4& d) {
     return (uint32_t)f | ((uint32_t)(f >> 32) << 4);
 }
 
-template <int NO, int P0, bool EDGE, bool OPEN = false, bool SEAM = false>
-static __device__ __forceinline__ void sweep_pairs_nib(const Rows2Ctx& c, const PhiloxKeys& K, int tr_first, int tr_end, int step_rows, int oct,
+// pair_step on nibble planes: the same addressing with dword octets (every offset halves)
+template <int NO, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM>
+static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t a, int rg, int to_wrap,
+                                                     uint32_t cq) {
+    constexpr int RS = 2 * NO * 4;
+    constexpr int DO = (KAPPA ? NO : -NO) * 4;
+    const uint32_t R0 = lds_ld<uint32_t>(a), R1 = lds_ld<uint32_t>(a + RS);
+    const uint32_t R2 = lds_ld<uint32_t>(a + 2 * RS), R3 = lds_ld<uint32_t>(a + 3 * RS);
+    const uint32_t A0 = lds_ld<uint32_t>(a + RS + (P0 ? 4 : -4));      // row a: next octet if P0, else the previous one
+    const uint32_t A1 = lds_ld<uint32_t>(a + 2 * RS + (P0 ? -4 : 4));  // row b: the other side
+    __builtin_amdgcn_sched_barrier(0);
+    int rga = rg, rgb = rg + 1;
+    if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
+    const u32x4 w0 = philox_vk(cq, (uint32_t)rga, hs, c.tag_hi, K);
+    const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, hs, c.tag_hi, K);
+    __builtin_amdgcn_sched_barrier(0);
+    const uint32_t Sa = SEAM ? (P0 ? nib_shift_next_seam(R1, A0, c.sh_next) : nib_shift_prev_seam(R1, A0, c.sh_prev))
+                             : (P0 ? nib_shift_next(R1, A0) : nib_shift_prev(R1, A0));
+    const uint32_t Sb = SEAM ? (P0 ? nib_shift_prev_seam(R2, A1, c.sh_prev) : nib_shift_next_seam(R2, A1, c.sh_next))
+                             : (P0 ? nib_shift_prev(R2, A1) : nib_shift_next(R2, A1));
+    const uint32_t mid = R1 + R2;  // shared by both rows' vertical + centre sums
+    const uint32_t cnt0 = R0 + mid + Sa, cnt1 = R3 + mid + Sb;
+    const uint32_t cnt0l = cnt0 & 0x0F0F0F0Fu, cnt0h = (cnt0 >> 4) & 0x0F0F0F0Fu;
+    const uint32_t cnt1l = cnt1 & 0x0F0F0F0Fu, cnt1h = (cnt1 >> 4) & 0x0F0F0F0Fu;
+    u32x4 d0, d1;
+    uint32_t edge_a = 0, edge_b = 0;
+    if (OPEN) {  // as in pair_step: the counts are bytes by now, the degree-3 / degree-2 patches are the byte form's
+        const bool ea = rga == 0 || rga == c.last_row, eb = rgb == 0 || rgb == c.last_row;
+        const bool la = !P0 && c.lft, ra = c.rgt && c.r_par == (uint32_t)P0, lb = P0 && c.lft, rb = c.rgt && c.r_par != (uint32_t)P0;
+        d0 = compare_octet_open(w0, cnt0l, cnt0h, c, ea, la, ra);
+        d1 = compare_octet_open(w1, cnt1l, cnt1h, c, eb, lb, rb);
+        edge_a = (ea ? 1u : 0u) | (la ? 2u : 0u) | (ra ? 4u : 0u) | (c.r_slot << 4);
+        edge_b = (eb ? 1u : 0u) | (lb ? 2u : 0u) | (rb ? 4u : 0u) | (c.r_slot << 4);
+    } else {
+        d0 = compare_octet(w0, cnt0l, cnt0h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
+        d1 = compare_octet(w1, cnt1l, cnt1h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
+    }
+    const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
+    if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
+        if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga, hs, c.tag_lo, c.k0, c.k1, edge_a);
+        if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb, hs, c.tag_lo, c.k0, c.k1, edge_b);
+    }
+    uint32_t n0 = nib_pack(d0), n1 = nib_pack(d1);
+    if (OPEN) {  // what lies beyond the open edge stays empty (existing-site masks in the nibble layout)
+        n0 = (rga < 0 || rga > c.last_row) ? 0u : (n0 & (P0 ? c.nvm_o : c.nvm_e));
+        n1 = (rgb < 0 || rgb > c.last_row) ? 0u : (n1 & (P0 ? c.nvm_e : c.nvm_o));
+    }
+    if (SEAM) {  // the sites the last octet does not have stay empty
+        n0 &= c.nvm_e;
+        n1 &= c.nvm_e;
+    }
+    lds_st<uint32_t>(a + RS + DO, n0);
+    lds_st<uint32_t>(a + 2 * RS + DO, n1);
+}
+
+template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN = false, bool SEAM = false>
+static __device__ __forceinline__ void sweep_pairs_nib(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t a, int rg, int n, bool tail,
                                                        uint32_t cq) {
-    const char* const ps0 = reinterpret_cast<const char*>(c.Ps);
-    const int d_off = (int)(reinterpret_cast<const char*>(c.Pd) - ps0);
-    const int off_end = tr_end * NO * 4;
-    const int off_step = step_rows * NO * 4;
-    int off = (tr_first * NO + oct) * 4;
-    int rg = EDGE ? tr_first : c.rgf + (tr_first - c.tr_lo);
     int to_wrap = EDGE ? c.wrap_tr - __builtin_amdgcn_readfirstlane(rg) : 0;
+    bool live = true;  // the last of the n + 1 trips runs under the lane mask `tail`: one copy of the body, a wave without a lane skips it
 #pragma unroll 1
-    for (; off < off_end; off += off_step, rg += step_rows, to_wrap -= step_rows) {
-        asm volatile("" : "+v"(off), "+v"(rg));
-        const char* ps = ps0 + off;
-        const uint32_t R0 = *reinterpret_cast<const uint32_t*>(ps - NO * 4), R1 = *reinterpret_cast<const uint32_t*>(ps);
-        const uint32_t R2 = *reinterpret_cast<const uint32_t*>(ps + NO * 4), R3 = *reinterpret_cast<const uint32_t*>(ps + 2 * NO * 4);
-        const uint32_t A0 = *reinterpret_cast<const uint32_t*>(ps + (P0 ? 4 : -4));           // row a: next octet if P0, else the previous one
-        const uint32_t A1 = *reinterpret_cast<const uint32_t*>(ps + NO * 4 + (P0 ? -4 : 4));  // row b: the other side
-        __builtin_amdgcn_sched_barrier(0);
-        int rga = rg, rgb = rg + 1;
-        if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
-        const u32x4 w0 = philox_vk(cq, (uint32_t)rga, c.hs, c.tag_hi, K);
-        const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.hs, c.tag_hi, K);
-        __builtin_amdgcn_sched_barrier(0);
-        const uint32_t Sa = SEAM ? (P0 ? nib_shift_next_seam(R1, A0, c.sh_next) : nib_shift_prev_seam(R1, A0, c.sh_prev))
-                                 : (P0 ? nib_shift_next(R1, A0) : nib_shift_prev(R1, A0));
-        const uint32_t Sb = SEAM ? (P0 ? nib_shift_prev_seam(R2, A1, c.sh_prev) : nib_shift_next_seam(R2, A1, c.sh_next))
-                                 : (P0 ? nib_shift_prev(R2, A1) : nib_shift_next(R2, A1));
-        const uint32_t mid = R1 + R2;  // shared by both rows' vertical + centre sums
-        const uint32_t cnt0 = R0 + mid + Sa, cnt1 = R3 + mid + Sb;
-        const uint32_t cnt0l = cnt0 & 0x0F0F0F0Fu, cnt0h = (cnt0 >> 4) & 0x0F0F0F0Fu;
-        const uint32_t cnt1l = cnt1 & 0x0F0F0F0Fu, cnt1h = (cnt1 >> 4) & 0x0F0F0F0Fu;
-        u32x4 d0, d1;
-        uint32_t edge_a = 0, edge_b = 0;
-        if (OPEN) {  // as in sweep_pairs: the counts are bytes by now, the degree-3 / degree-2 patches are the byte form's
-            const bool ea = rga == 0 || rga == c.last_row, eb = rgb == 0 || rgb == c.last_row;
-            const bool la = !P0 && c.lft, ra = c.rgt && c.r_par == (uint32_t)P0, lb = P0 && c.lft, rb = c.rgt && c.r_par != (uint32_t)P0;
-            d0 = compare_octet_open(w0, cnt0l, cnt0h, c, ea, la, ra);
-            d1 = compare_octet_open(w1, cnt1l, cnt1h, c, eb, lb, rb);
-            edge_a = (ea ? 1u : 0u) | (la ? 2u : 0u) | (ra ? 4u : 0u) | (c.r_slot << 4);
-            edge_b = (eb ? 1u : 0u) | (lb ? 2u : 0u) | (rb ? 4u : 0u) | (c.r_slot << 4);
+    for (int i = n; i >= 0; --i) {
+        if (i == 0) live = tail;
+        asm volatile("" : "+v"(a), "+v"(rg));
+        if (live) pair_step_nib<NO, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, a, rg, to_wrap, cq);
+        a += 2 * RL * 2 * NO * 4;
+        rg += 2 * RL;
+        to_wrap -= 2 * RL;
+    }
+}
+
+// Half-sweep hsi = 2 s + KAPPA of a generation on one tile of TR rows: rows [1 + hsi, TR - 2 - hsi] in pairs (TR is even),
+// thread (al, octet) takes every RL-th pair from pair al on.  a_thr = LDS byte address of (row 2 al, the thread's octet, plane 0)
+template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM, bool NIB>
+static __device__ __forceinline__ void half_sweep(const Rows2Ctx& c, const PhiloxKeys& K, int TR, uint32_t sweep, int s, uint32_t a_thr, int al,
+                                                  uint32_t cq) {
+    constexpr int ES = NIB ? 4 : 8;
+    const int hsi = 2 * s + KAPPA;
+    __syncthreads();
+    if (al < RL) {
+        const int npairs = (TR - 2 - 2 * hsi) / 2;
+        const int n = __builtin_amdgcn_readfirstlane(npairs / RL);  // every thread has n pairs, row lanes [0, npairs - n RL) one more
+        const bool tail = al < npairs - n * RL;
+        const uint32_t a = a_thr + (uint32_t)(hsi * 2 * NO * ES + (KAPPA ? 0 : NO * ES));  // the source is the other colour's plane
+        int rg;  // row number of the thread's first row, tile row 1 + hsi + 2 al: its tile row (EDGE) or its global row
+        if (EDGE) {
+            rg = 1 + hsi + 2 * al;
         } else {
-            d0 = compare_octet(w0, cnt0l, cnt0h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
-            d1 = compare_octet(w1, cnt1l, cnt1h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
+            int rgf = c.rg_tile0 + 1 + hsi;
+            if (!OPEN && rgf >= c.total_rows) rgf -= c.total_rows;
+            rg = rgf + 2 * al;
         }
-        const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
-        if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
-            if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga, c.hs, c.tag_lo, c.k0, c.k1, edge_a);
-            if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb, c.hs, c.tag_lo, c.k0, c.k1, edge_b);
-        }
-        char* pd = const_cast<char*>(ps) + d_off;
-        uint32_t n0 = nib_pack(d0), n1 = nib_pack(d1);
-        if (OPEN) {  // what lies beyond the open edge stays empty (existing-site masks in the nibble layout)
-            const uint64_t ma = P0 ? c.vm_o : c.vm_e, mb = P0 ? c.vm_e : c.vm_o;
-            n0 = (rga < 0 || rga > c.last_row) ? 0u : (n0 & ((uint32_t)ma | ((uint32_t)(ma >> 32) << 4)));
-            n1 = (rgb < 0 || rgb > c.last_row) ? 0u : (n1 & ((uint32_t)mb | ((uint32_t)(mb >> 32) << 4)));
-        }
-        if (SEAM) {  // the sites the last octet does not have stay empty
-            const uint32_t m = (uint32_t)c.vm_e | ((uint32_t)(c.vm_e >> 32) << 4);
-            n0 &= m;
-            n1 &= m;
-        }
-        *reinterpret_cast<uint32_t*>(pd) = n0;
-        *reinterpret_cast<uint32_t*>(pd + NO * 4) = n1;
+        const uint32_t hs = 2u * sweep + (uint32_t)KAPPA;
+        if constexpr (NIB) sweep_pairs_nib<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, a, rg, n, tail, cq);
+        else sweep_pairs<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, a, rg, n, tail, cq);
+    }
+}
+
+// the kg sweeps of one generation, two half-sweeps per trip: colour 0, then colour 1
+template <int NO, int RL, int P0, bool EDGE, bool OPEN, bool SEAM, bool NIB>
+static __device__ __forceinline__ void sweep_generation(const Rows2Ctx& c, const PhiloxKeys& K, int TR, uint32_t sweep_g, int kg, uint32_t a_thr,
+                                                        int al, uint32_t cq) {
+#pragma unroll 1
+    for (int s = 0; s < kg; ++s) {
+        half_sweep<NO, RL, 0, P0, EDGE, OPEN, SEAM, NIB>(c, K, TR, sweep_g + (uint32_t)s, s, a_thr, al, cq);
+        half_sweep<NO, RL, 1, P0, EDGE, OPEN, SEAM, NIB>(c, K, TR, sweep_g + (uint32_t)s, s, a_thr, al, cq);
     }
 }
 
@@ -453,10 +542,10 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     // SIMDs (+5 % on 4096^2 against the smallest lane count that reaches the same iteration count).
     constexpr int RL = RLMAX;
     using E = typename std::conditional<NIB, uint32_t, uint64_t>::type;  // one octet of a colour plane
-    E* plane0 = reinterpret_cast<E*>(lds + 1);
-    E* plane1 = plane0 + TR * NO;
-    // one spare row: the pair loop reads row idx + 2 NO of the last pair (rounded up to the uint64 grid)
-    uint64_t* s_thr = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(plane1 + TR * NO + NO + 1) + 7u) & ~(uintptr_t)7u);
+    // the colour planes, interleaved row by row (see TilePlanes): plane 0 of row 0 starts behind the guard octet
+    const TilePlanes<E, NO> P{reinterpret_cast<E*>(lds + 1)};
+    // one spare row behind the planes: "octet NO" of plane 1 of the last row is read there (rounded up to the uint64 grid)
+    uint64_t* s_thr = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(P.base + 2 * TR * NO + NO + 1) + 7u) & ~(uintptr_t)7u);
     const int tid = threadIdx.x;
     if (tid < 25) s_thr[tid] = p.thr[tid];
 
@@ -513,14 +602,13 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
                         ev &= vm_e;
                         od &= vm_o;
                     }
-                    const int idx = tr * NO + oct;
                     const int gpar = (int)((p.row0 + Rb + tr) & 1);  // colour of the even columns of this row
                     if (NIB) {
-                        (gpar ? plane1 : plane0)[idx] = (E)((uint32_t)ev | ((uint32_t)(ev >> 32) << 4));
-                        (gpar ? plane0 : plane1)[idx] = (E)((uint32_t)od | ((uint32_t)(od >> 32) << 4));
+                        P.at(gpar, tr, oct) = (E)((uint32_t)ev | ((uint32_t)(ev >> 32) << 4));
+                        P.at(gpar ^ 1, tr, oct) = (E)((uint32_t)od | ((uint32_t)(od >> 32) << 4));
                     } else {
-                        (gpar ? plane1 : plane0)[idx] = (E)ev;
-                        (gpar ? plane0 : plane1)[idx] = (E)od;
+                        P.at(gpar, tr, oct) = (E)ev;
+                        P.at(gpar ^ 1, tr, oct) = (E)od;
                     }
                 }
             }
@@ -550,8 +638,10 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     c.r_slot = ((uint32_t)(p.cols - 1) & 15u) >> 1;
     c.rm_lo = c.r_slot < 4 ? 0xFFu << (8 * c.r_slot) : 0u;
     c.rm_hi = c.r_slot < 4 ? 0u : 0xFFu << (8 * (c.r_slot - 4));
-    c.vm_e = vm_e;
-    c.vm_o = vm_o;
+    c.vm_e = NIB ? 0 : vm_e;  // (each form of the planes keeps only its own masks alive through the sweeps)
+    c.vm_o = NIB ? 0 : vm_o;
+    c.nvm_e = NIB ? ((uint32_t)vm_e | ((uint32_t)(vm_e >> 32) << 4)) : 0u;
+    c.nvm_o = NIB ? ((uint32_t)vm_o | ((uint32_t)(vm_o >> 32) << 4)) : 0u;
     // periodic lattice of ragged width: v sites per colour in the last octet of a row (cols is even: the same for both)
     const int v_last = (p.cols >> 1) & 7;
     const bool ragged = !OPEN && v_last != 0;
@@ -579,7 +669,7 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
         tl0 = now_;                         \
     }
     // RESIDENT: "a neighbour wait expired in this workgroup" -- kept in the guard octet in front of plane 0 (only ever read
-    // as "octet -1" padding): a static __shared__ word would push a 160 KB workgroup past the CU's LDS
+    // as "octet -1" padding of row 0): a static __shared__ word would push a 160 KB workgroup past the CU's LDS
     volatile int& s_fail = *reinterpret_cast<volatile int*>(lds);
     if (RESIDENT && tid == 0) s_fail = 0;
 
@@ -612,12 +702,12 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
         const uint64_t tag = strip_tag(gen);
         for (int i = tid; i < n_tb; i += THREADS) {
             const int r = i / WO, o = i - r * WO;
-            xst(mine + i, (uint64_t)plane1[(2 * k + r) * NO + 1 + o] | tag);     // TOP: first 2k interior rows
-            xst(mine + n_tb + i, (uint64_t)plane1[(H + r) * NO + 1 + o] | tag);  // BOTTOM: last 2k interior rows
+            xst(mine + i, (uint64_t)P.at(1, 2 * k + r, 1 + o) | tag);     // TOP: first 2k interior rows
+            xst(mine + n_tb + i, (uint64_t)P.at(1, H + r, 1 + o) | tag);  // BOTTOM: last 2k interior rows
         }
         for (int i = tid; i < n_lr; i += THREADS) {
-            xst(mine + 2 * n_tb + i, (uint64_t)plane1[(2 * k + i) * NO + 1] | tag);          // LEFT: first interior octet
-            xst(mine + 2 * n_tb + n_lr + i, (uint64_t)plane1[(2 * k + i) * NO + wi] | tag);  // RIGHT: last interior octet
+            xst(mine + 2 * n_tb + i, (uint64_t)P.at(1, 2 * k + i, 1) | tag);          // LEFT: first interior octet
+            xst(mine + 2 * n_tb + n_lr + i, (uint64_t)P.at(1, 2 * k + i, wi) | tag);  // RIGHT: last interior octet
         }
         RES_MARK(1);
     };
@@ -701,73 +791,50 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
             const int i = tid + it * THREADS;
             if (i < 2 * k * NO) {
                 const int r = i / NO, o = i - r * NO;
-                if (nu[it]) plane1[r * NO + o] = (E)(vu[it] & FLAG_MASK);
-                if (nd[it]) plane1[(2 * k + H + r) * NO + o] = (E)(vd[it] & FLAG_MASK);
+                if (nu[it]) P.at(1, r, o) = (E)(vu[it] & FLAG_MASK);
+                if (nd[it]) P.at(1, 2 * k + H + r, o) = (E)(vd[it] & FLAG_MASK);
             }
         }
 #pragma unroll
         for (int it = 0; it < SI; ++it) {
             const int i = tid + it * THREADS;
             if (i < n_lr) {
-                if (nl[it]) plane1[(2 * k + i) * NO] = (E)(vl[it] & FLAG_MASK);
-                if (nr[it]) plane1[(2 * k + i) * NO + wi + 1] = (E)(vr[it] & FLAG_MASK);
+                if (nl[it]) P.at(1, 2 * k + i, 0) = (E)(vl[it] & FLAG_MASK);
+                if (nr[it]) P.at(1, 2 * k + i, wi + 1) = (E)(vr[it] & FLAG_MASK);
             }
         }
         RES_MARK(3);
     };
 
-    // one call site for every form of the pair loop: rows tr_first, tr_first + step, ... < tr_end of octet column oc
-    auto run = [&](int par0, int tr_first, int tr_end, int step, int oc, uint32_t cqq) {
-        if (NIB && OPEN) {
-            if (par0) sweep_pairs_nib<NO, 1, false, true>(c, K, tr_first, tr_end, step, oc, cqq);
-            else sweep_pairs_nib<NO, 0, false, true>(c, K, tr_first, tr_end, step, oc, cqq);
-        } else if (NIB && seam) {
-            if (par0) sweep_pairs_nib<NO, 1, true, false, true>(c, K, tr_first, tr_end, step, oc, cqq);
-            else sweep_pairs_nib<NO, 0, true, false, true>(c, K, tr_first, tr_end, step, oc, cqq);
-        } else if (NIB) {
-            if (edge) {
-                if (par0) sweep_pairs_nib<NO, 1, true>(c, K, tr_first, tr_end, step, oc, cqq);
-                else sweep_pairs_nib<NO, 0, true>(c, K, tr_first, tr_end, step, oc, cqq);
-            } else {
-                if (par0) sweep_pairs_nib<NO, 1, false>(c, K, tr_first, tr_end, step, oc, cqq);
-                else sweep_pairs_nib<NO, 0, false>(c, K, tr_first, tr_end, step, oc, cqq);
-            }
-        } else if (OPEN) {
-            if (par0) sweep_pairs<NO, 1, false, true>(c, K, tr_first, tr_end, step, oc, cqq);
-            else sweep_pairs<NO, 0, false, true>(c, K, tr_first, tr_end, step, oc, cqq);
-        } else if (seam) {
-            if (par0) sweep_pairs<NO, 1, true, false, true>(c, K, tr_first, tr_end, step, oc, cqq);
-            else sweep_pairs<NO, 0, true, false, true>(c, K, tr_first, tr_end, step, oc, cqq);
-        } else if (edge) {
-            if (par0) sweep_pairs<NO, 1, true, false>(c, K, tr_first, tr_end, step, oc, cqq);
-            else sweep_pairs<NO, 0, true, false>(c, K, tr_first, tr_end, step, oc, cqq);
+    // The form of the pair loop is decided once per tile: plain / EDGE / SEAM / OPEN and the column parity par0 of the colour
+    // updated in a half-sweep's first row.  Half-sweep hsi starts at tile row 1 + hsi and updates colour hsi & 1; the two always
+    // add up to an odd number, so par0 does not change during a launch.
+    const int par0 = (int)((p.row0 + Rb + 1) & 1);
+    const int form = 2 * (OPEN ? 0 : (seam ? 1 : (edge ? 2 : 3))) + par0;
+    // thread (al, oct): LDS byte address of (row 2 al, its octet, plane 0), the start of its pair loop in half-sweep 0
+    const uint32_t a_thr = lds_addr(P.base) + (uint32_t)((4 * al * NO + oct) * (int)sizeof(E));
+    auto run_generation = [&](uint32_t sweep_g, int kg) {
+#define TSU_FORM(P0, EDGE_, OPEN_, SEAM_) sweep_generation<NO, RL, P0, EDGE_, OPEN_, SEAM_, NIB>(c, K, TR, sweep_g, kg, a_thr, al, cq)
+        if constexpr (OPEN) {
+            if (par0) TSU_FORM(1, false, true, false);
+            else TSU_FORM(0, false, true, false);
         } else {
-            if (par0) sweep_pairs<NO, 1, false, false>(c, K, tr_first, tr_end, step, oc, cqq);
-            else sweep_pairs<NO, 0, false, false>(c, K, tr_first, tr_end, step, oc, cqq);
+            switch (form) {
+                case 2: TSU_FORM(0, true, false, true); break;
+                case 3: TSU_FORM(1, true, false, true); break;
+                case 4: TSU_FORM(0, true, false, false); break;
+                case 5: TSU_FORM(1, true, false, false); break;
+                case 6: TSU_FORM(0, false, false, false); break;
+                default: TSU_FORM(1, false, false, false); break;
+            }
         }
-    };
-    int par0 = 0;
-    auto set_half_sweep = [&](uint32_t sweep_g, int hsi) {
-        const int kappa = hsi & 1;
-        c.hs = 2u * (sweep_g + (uint32_t)(hsi >> 1)) + (uint32_t)kappa;
-        c.Pd = kappa ? plane1 : plane0;
-        c.Ps = kappa ? plane0 : plane1;
-        c.tr_lo = 1 + hsi;
-        c.npairs = (TR - 2 - 2 * hsi) / 2;  // rows [1 + hsi, TR - 2 - hsi] in pairs (TR is even)
-        int rgf = (int)rg0 + c.tr_lo;
-        if (!OPEN && rgf >= c.total_rows) rgf -= c.total_rows;
-        c.rgf = rgf;
-        par0 = (int)((p.row0 + Rb + c.tr_lo + kappa) & 1);
+#undef TSU_FORM
     };
     for (int gen = 0; gen < n_gen; ++gen) {
     const int kg = (RESIDENT && gen == n_gen - 1) ? R->k_last : k;  // sweeps of this generation (the tile keeps TR = H + 4k)
     const uint32_t sweep_g = sweep0 + (uint32_t)(gen * k);
-    for (int hsi = 0; hsi < 2 * kg; ++hsi) {
-        __syncthreads();
-        set_half_sweep(sweep_g, hsi);
-        // a thread stays on its own octet column and walks every RL-th row pair of the half-sweep's range
-        if (al < RL) run(par0, c.tr_lo + 2 * al, c.tr_lo + 2 * c.npairs, 2 * RL, oct, cq);
-    }
+    // a thread stays on its own octet column and walks every RL-th row pair of each half-sweep's range
+    run_generation(sweep_g, kg);
     __syncthreads();
     if (RESIDENT && gen + 1 < n_gen) {
         publish(gen);
@@ -788,8 +855,7 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
         for (int hr = al; hr < H; hr += RLMAX) {
             const int rl = r0 + hr;
             if (rl < p.r_end) {
-                const int li = (2 * k + hr) * NO + oct;
-                uint64_t ev = (gpar ? plane1 : plane0)[li], od = (gpar ? plane0 : plane1)[li];
+                uint64_t ev = P.at(gpar, 2 * k + hr, oct), od = P.at(gpar ^ 1, 2 * k + hr, oct);
                 if (NIB) {  // nibble octet -> byte-per-site flags
                     ev = (ev & 0x01010101ull) | (((ev >> 4) & 0x01010101ull) << 32);
                     od = (od & 0x01010101ull) | (((od >> 4) & 0x01010101ull) << 32);
