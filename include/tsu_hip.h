@@ -449,6 +449,21 @@ int tsu_sparse_sample(tsu_sparse* g, double T, int n_burnin, int n_sweeps, int n
 /* -1/2 s^T J s - b^T s of the resident state, and sum_i (2 s_i - 1) (the magnetisation numerator in spin language) */
 int tsu_sparse_energy(tsu_sparse* g, double* energy, int64_t* sum_spins);
 
+/* Which kernel a colour class takes (no reference counterpart: lets a caller or a test see the route of its sweeps).  A PLAN record is
+ * ten int32: route (0 = the generic kernel k5_color, 1 = the stencil kernels of regular classes, 2 = the whole system in one
+ * workgroup, k5_small), deg, lo, hi (irregular rows at either end of the class), site_stride, pair (0 = none, 1 = prepares the
+ * decisions of class `other`, 2 = consumes them), other (-1 without a pair), v4 (1 = four positions per thread), o_lo, o_n (pair = 1:
+ * the partner's leading irregular rows and the number of its regular rows).  A class that is not regular leaves the other fields 0
+ * and other -1; route 2 (n <= 32768) keeps what the classifier found for the class, with v4 = 0: no stencil kernel is launched.
+ * tsu_sparse_classify is pure host arithmetic (no context, no GPU): the validation and the classifier of tsu_sparse_create on the
+ * same arguments, under the switches TSU_K5_STENCIL, TSU_K5_PAIR, TSU_K5_V4 as they stand; plan receives n_colors records.  On
+ * failure the message is tsu_last_error(NULL).  tsu_sparse_class_plan returns the record of one class of a live handle: what the
+ * next sweep launches for it (TSU_K5_V4 is read at every launch). */
+#define TSU_SPARSE_PLAN_LEN 10
+int tsu_sparse_classify(int n, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* bias_host /*nullable*/,
+                        int n_colors, const int32_t* color_offsets, const int32_t* order, int32_t* plan /*n_colors*10*/);
+int tsu_sparse_class_plan(tsu_sparse* g, int color, int32_t* rec /*10*/);
+
 /* ------------------------------------------------------------------ Langevin (K3)
  * Replaces ThermalSamplingUnit._langevin_step (tsu/core.py:64-80) fused with the analytic gradient of a
  * separable quadratic energy E = 1/2 sum_i k_i (x_i - mu_i)^2 (replacing _numerical_gradient, :82-98),

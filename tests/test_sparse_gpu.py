@@ -176,15 +176,22 @@ def _regular(shape, n):
 
 @pytest.mark.parametrize("shape,n", [("chain", 300001), ("chain_edge_bias", 70001), ("ring", 100000), ("ladder", 80000)])
 def test_regular_colour_classes_on_the_stencil_kernel_match_the_oracle(shape, n):
-    """Uniform couplings and bias, neighbours at fixed position offsets (`IsingChain`, rings, ladders): the colour classes run
+    """Uniform couplings and bias, neighbours at fixed position offsets (`IsingChain`, rings): the colour classes run
     k5_stencil (no CSR streams, integer thresholds from the count of set neighbours) with their few end rows on the generic
-    kernel -- the same bits as the oracle's sequential loop on the CSR rows."""
+    kernel -- the same bits as the oracle's sequential loop on the CSR rows.  The two-leg ladder does NOT: its colour classes hold
+    sites 0, 3, 4, 7, 8, ... -- not affine in the position -- so both run the generic kernel k5_color (the plan says so; the
+    stencil routes of degree 3 and 4 are in tests/test_sparse_routes_gpu.py)."""
     from tsu import _hip
     from tsu.graph import color_graph
     A, bias = _regular(shape, n)
     st = np.random.default_rng(n).integers(0, 2, size=n).astype(np.int8)
     offsets, order = color_graph(A)
     g = _hip.SparseSystem(A.indptr, A.indices, A.data, bias, offsets, order)
+    plan = g.plan()
+    if shape == "ladder":
+        assert [r["route"] for r in plan] == [0, 0]
+    else:
+        assert [(r["route"], r["deg"]) for r in plan] == [(1, 2), (1, 2)]
     g.set_state(st)
     g.sweep(1.1, 4, seed=17, sweep0=3)
     want = ora.sparse_sweep_philox(st, A.indptr, A.indices, A.data, bias, 1.1, 4, 17, sweep0=3, order=order)
@@ -199,9 +206,10 @@ def test_regular_colour_classes_on_the_stencil_kernel_match_the_oracle(shape, n)
 @pytest.mark.parametrize("pair,v4,tie", [(1, 1, 0), (0, 1, 0), (1, 0, 0), (1, 1, 1), (0, 1, 1)])
 def test_chain_classes_in_pairs_and_four_positions_per_thread(n, pair, v4, tie, monkeypatch):
     """The two colour classes of a chain share their Philox blocks index by index: the first class's launch prepares the second
-    class's decisions by neighbour count (k5_stencil4<1> / <2>), four positions per thread when the classes start at multiples
-    of 4 (n = 300008, 262146: both; 300004: the second class starts at 150002 and runs one position per thread on codes written as
-    dwords).  Every combination of the two switches gives the oracle's bits; so does a chain just above the one-workgroup kernel's
+    class's decisions by neighbour count (k5_stencil4<1> / <2>), four positions per thread when BOTH classes start at multiples
+    of 4 (n = 300008; at 300004 and 262146 the second class starts at 150002 / 131073: both classes of the pair then run one position
+    per thread, k5_stencil1<1> / <2>, and without pairs only the first class runs k5_stencil4).  The plan is asserted per n and
+    switch.  Every combination of the two switches gives the oracle's bits; so does a chain just above the one-workgroup kernel's
     range (n = 4099 runs k5_small: the switches must not matter there).  tie = 1: every wave takes the 64-bit compares that a draw whose
     leading 27 bits equal a threshold's needs (one in 2^27: never met by chance in a test)."""
     from tsu import _hip
@@ -213,6 +221,14 @@ def test_chain_classes_in_pairs_and_four_positions_per_thread(n, pair, v4, tie, 
     st = np.random.default_rng(n).integers(0, 2, size=n).astype(np.int8)
     offsets, order = color_graph(A)
     g = _hip.SparseSystem(A.indptr, A.indices, A.data, bias, offsets, order)
+    plan = g.plan()
+    if n == 4099:
+        assert [(r["route"], r["v4"]) for r in plan] == [(2, 0), (2, 0)]
+    else:
+        assert [(r["route"], r["deg"], r["pair"]) for r in plan] == [(1, 2, 1 if pair else 0), (1, 2, 2 if pair else 0)]
+        # four positions per thread: the class starts at a multiple of 4 -- and, for the first class of a pair, so does its partner
+        second = {300008: True, 300004: False, 262144 + 2: False}[n]  # the second class starts at 150004 / 150002 / 131073
+        assert [r["v4"] for r in plan] == [int(bool(v4) and (second or not pair)), int(bool(v4) and second)]
     g.set_state(st)
     g.sweep(0.9, 3, seed=23, sweep0=1)
     want = ora.sparse_sweep_philox(st, A.indptr, A.indices, A.data, bias, 0.9, 3, 23, sweep0=1, order=order)

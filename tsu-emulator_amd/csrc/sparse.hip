@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "dense.h"
+#include "sparse_host.h"
 
 struct tsu_sparse {
     tsu_ctx* ctx;
@@ -30,38 +31,13 @@ struct tsu_sparse {
     double* d_red;      // [energy, sum_spins as double pair] reduction target
     int64_t nnz;
     // regular colour classes (k5_stencil): see K5Stencil
-    std::vector<struct K5Stencil> stencil;  // one per colour; deg < 0: the class is not regular
+    std::vector<K5Stencil> stencil;  // one per colour; deg < 0: the class is not regular
     unsigned long long* d_thr;              // [n_colors][K5_MAX_DEG + 1] acceptance thresholds of the current call
     uint8_t* d_code;                        // [n] (position space) decisions prepared for the second class of a PAIR, see K5Stencil::pair
 };
 
-// A REGULAR colour class (chains, rings, ladders ...: `IsingChain`, tsu/models/ising.py:265-286): apart from at most K5_EDGE rows at
-// either end of its position range, every row has the same degree, the same coupling on every edge, the same bias, neighbours at
-// fixed position offsets and a site number that is affine in the position.  Such a class needs no CSR streams at all: per update it
-// reads its neighbours' bits (deg bytes, contiguous across the lanes) and writes one byte -- ~3 B instead of 43 for a chain -- and
-// the field takes deg + 1 values only, so acceptance is one integer compare of the uniform's 53 bits with a threshold computed (on
-// the device, with the generic kernel's own expressions) from the number of set neighbours.  The end rows run on the generic kernel.
-#define K5_MAX_DEG 4
-#define K5_EDGE 64
+// (K5Stencil, the classifier of regular colour classes, the pairing pass and the launch rule: sparse_host.h)
 #define K5_THR_STRIDE (2 * (K5_MAX_DEG + 1))  // per class: the thresholds, then their leading 27 bits
-struct K5Stencil {
-    int deg;            // -1: not regular
-    int pb, pe;         // position range of the class
-    int lo, hi;         // rows [pb, pb + lo) and [pe - hi, pe) are irregular (generic kernel)
-    int off[K5_MAX_DEG];
-    double Jv, bias;
-    int site0, site_stride;  // site of position p = site0 + site_stride * (p - pb - lo)
-    // PAIRED classes.  The uniform of site i comes from the Philox block of i >> 1 (dense.h: words x, y for the even site, z, w for the
-    // odd one), and in a chain the two sites of a block sit in the two colour classes at the same index: the launch of the first class
-    // (pair = 1) has the second class's uniform in registers for free.  It cannot decide for that site yet -- its neighbours are being
-    // updated -- but the decision is a function of the neighbour count alone: bit k of code[p'] = "the site at position p' of the other
-    // class becomes 1 if k of its neighbours are set".  The second class's launch (pair = 2, k5_paired) computes no random numbers
-    // at all: count, shift, store.  Philox blocks per sweep: one per PAIR of sites instead of one per site.
-    int pair;                // 0: none; 1: prepares the codes of class `other`; 2: consumes them
-    int other;               // the partner class
-    int o_pb, o_lo, o_n;     // (pair = 1) the partner's first position, its leading irregular rows and the number of its REGULAR rows
-    int o_deg;
-};
 
 namespace {
 
@@ -277,9 +253,8 @@ __global__ __launch_bounds__(256) void k5_color(const int64_t* __restrict__ row_
     state[p] = (u < sigmoid_clamped(F / T)) ? 1 : 0;
 }
 
-// Small graphs (n <= K5S_MAX): the whole run in ONE launch of one workgroup, the state in LDS, colour after colour with
+// Small graphs (n <= K5S_MAX, sparse_host.h): the whole run in ONE launch of one workgroup, the state in LDS, colour after colour with
 // a workgroup barrier in between; optional recording of the state after every `rec_every` sweeps past `rec_from`.
-constexpr int K5S_MAX = 32768;
 constexpr int K5S_THREADS = 1024;
 __global__ __launch_bounds__(K5S_THREADS) void k5_small(const int64_t* __restrict__ row_ptr, const int32_t* __restrict__ col,
                                                         const double* __restrict__ val, const double* __restrict__ bias,
@@ -384,8 +359,7 @@ int run_sweeps(tsu_sparse* g, double T, int n_sweeps, uint64_t seed, uint32_t sw
                 A.k0 = k0;
                 A.k1 = k1;
                 A.force_tie = getenv("TSU_K5_TEST_TIE") && atoi(getenv("TSU_K5_TEST_TIE")) != 0;
-                const bool use_v4 = !(getenv("TSU_K5_V4") && atoi(getenv("TSU_K5_V4")) == 0);
-                const bool v4 = use_v4 && pb % 4 == 0 && (S.pair != 1 || S.o_pb % 4 == 0);
+                const bool v4 = k5_launch_v4(k5_env_on("TSU_K5_V4"), pb, S.pair, S.o_pb);
                 const dim3 grid((unsigned)(((pe - pb + (v4 ? 3 : 0)) / (v4 ? 4 : 1) + 255) / 256));
                 if (v4) {
                     if (S.pair == 2) hipLaunchKernelGGL(k5_stencil4<2>, grid, dim3(256), 0, ctx->stream, A, thr, thr_other);
@@ -424,47 +398,19 @@ int tsu_sparse_create(tsu_ctx* ctx, int n, const int64_t* row_ptr, const int32_t
                       int n_colors, const int32_t* color_offsets, const int32_t* order, tsu_sparse** out) {
     TSU_ENTER(ctx);
     if (!ctx) return TSU_E_INVALID;
-    TSU_REQUIRE(ctx, out && n > 0 && row_ptr && n_colors > 0 && color_offsets && order, "tsu_sparse_create: bad arguments");
+    TSU_REQUIRE(ctx, out, "tsu_sparse_create: bad arguments");
     *out = nullptr;
+    // validation, position-space CSR, regular classes and their pairs: host code of its own (sparse_host.h)
+    K5Host H;
+    char msg[256];
+    if (!k5_host_prepare("tsu_sparse_create", n, row_ptr, col_idx, values, bias_host, n_colors, color_offsets, order, H, msg, sizeof msg))
+        return tsu_fail(ctx, TSU_E_INVALID, "%s", msg);
     const int64_t nnz = row_ptr[n];
-    TSU_REQUIRE(ctx, row_ptr[0] == 0 && nnz >= 0 && (nnz == 0 || (col_idx && values)), "tsu_sparse_create: bad CSR arrays");
-    TSU_REQUIRE(ctx, color_offsets[0] == 0 && color_offsets[n_colors] == n, "tsu_sparse_create: colour offsets must run from 0 to n");
-    // validate: order is a permutation, rows ascending and in range, the colouring is proper
-    std::vector<int32_t> pos_of((size_t)n, -1), color_of((size_t)n, -1);
-    for (int c = 0; c < n_colors; ++c) {
-        TSU_REQUIRE(ctx, color_offsets[c] <= color_offsets[c + 1], "tsu_sparse_create: colour offsets must not decrease");
-        for (int p = color_offsets[c]; p < color_offsets[c + 1]; ++p) {
-            const int32_t i = order[p];
-            TSU_REQUIRE(ctx, i >= 0 && i < n && pos_of[(size_t)i] < 0, "tsu_sparse_create: order is not a permutation of 0..n-1");
-            pos_of[(size_t)i] = p;
-            color_of[(size_t)i] = c;
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        TSU_REQUIRE(ctx, row_ptr[i] <= row_ptr[i + 1], "tsu_sparse_create: row_ptr must not decrease");
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
-            const int32_t j = col_idx[e];
-            TSU_REQUIRE(ctx, j >= 0 && j < n, "tsu_sparse_create: column index out of range");
-            TSU_REQUIRE(ctx, e == row_ptr[i] || col_idx[e - 1] < j, "tsu_sparse_create: columns of a row must ascend");
-            TSU_REQUIRE(ctx, j == i || color_of[(size_t)j] != color_of[(size_t)i],
-                        "tsu_sparse_create: sites %d and %d are coupled but have the same colour", i, (int)j);
-        }
-    }
-    // position-space CSR
-    std::vector<int64_t> rp((size_t)n + 1);
-    std::vector<int32_t> cp((size_t)nnz);
-    std::vector<double> vp((size_t)nnz), bp((size_t)n, 0.0);
-    rp[0] = 0;
-    for (int p = 0; p < n; ++p) {
-        const int i = order[p];
-        int64_t w = rp[(size_t)p];
-        for (int64_t e = row_ptr[i]; e < row_ptr[i + 1]; ++e, ++w) {
-            cp[(size_t)w] = pos_of[(size_t)col_idx[e]];
-            vp[(size_t)w] = values[e];
-        }
-        rp[(size_t)p + 1] = w;
-        if (bias_host) bp[(size_t)p] = bias_host[i];
-    }
+    const std::vector<int32_t>& pos_of = H.pos_of;
+    const std::vector<int64_t>& rp = H.rp;
+    const std::vector<int32_t>& cp = H.cp;
+    const std::vector<double>&vp = H.vp, &bp = H.bp;
+    const bool any_pair = H.any_pair;
     tsu_sparse* g = new (std::nothrow) tsu_sparse();
     if (!g) return tsu_fail(ctx, TSU_E_NOMEM, "tsu_sparse_create: host allocation failed");
     g->ctx = ctx;
@@ -473,77 +419,7 @@ int tsu_sparse_create(tsu_ctx* ctx, int n, const int64_t* row_ptr, const int32_t
     g->nnz = nnz;
     g->d_thr = nullptr;
     g->d_code = nullptr;
-    // regular colour classes: the pattern of the class's middle row must hold for every row but at most K5_EDGE at either end
-    const bool use_stencil = !(getenv("TSU_K5_STENCIL") && atoi(getenv("TSU_K5_STENCIL")) == 0);
-    g->stencil.assign((size_t)n_colors, K5Stencil());
-    for (int c = 0; c < n_colors; ++c) {
-        K5Stencil& S = g->stencil[(size_t)c];
-        S.deg = -1;
-        const int pb = color_offsets[c], pe = color_offsets[c + 1];
-        if (!use_stencil || pe - pb < 4 * K5_EDGE + 2) continue;
-        const int pm = pb + (pe - pb) / 2;
-        const int deg = (int)(rp[(size_t)pm + 1] - rp[(size_t)pm]);
-        if (deg < 1 || deg > K5_MAX_DEG) continue;
-        K5Stencil T;
-        T.deg = deg;
-        T.pb = pb;
-        T.pe = pe;
-        T.Jv = vp[(size_t)rp[(size_t)pm]];
-        T.bias = bp[(size_t)pm];
-        for (int i = 0; i < K5_MAX_DEG; ++i) T.off[i] = i < deg ? cp[(size_t)rp[(size_t)pm] + i] - pm : 0;
-        T.site_stride = order[pm + 1] - order[pm];
-        auto fits = [&](int p) {
-            if (rp[(size_t)p + 1] - rp[(size_t)p] != deg || bp[(size_t)p] != T.bias) return false;
-            if ((long long)order[p] != (long long)order[pm] + (long long)T.site_stride * (p - pm)) return false;
-            for (int i = 0; i < deg; ++i) {
-                const int64_t e = rp[(size_t)p] + i;
-                if (vp[(size_t)e] != T.Jv || cp[(size_t)e] - p != T.off[i] || cp[(size_t)e] == p) return false;  // (no self-loops: the row's own bit is rewritten)
-            }
-            return true;
-        };
-        int lo = 0, hi = 0;
-        while (lo <= K5_EDGE && !fits(pb + lo)) ++lo;
-        while (hi <= K5_EDGE && !fits(pe - 1 - hi)) ++hi;
-        if (lo > K5_EDGE || hi > K5_EDGE) continue;
-        bool ok = true;
-        for (int p = pb + lo; p < pe - hi && ok; ++p) ok = fits(p);
-        if (!ok) continue;
-        T.lo = lo;
-        T.hi = hi;
-        T.site0 = order[pb + lo];
-        T.pair = 0;
-        T.other = -1;
-        T.o_pb = T.o_lo = T.o_n = T.o_deg = 0;
-        S = T;
-    }
-    // pairs of regular classes that share their Philox blocks index by index (K5Stencil::pair): sites ascending by 2 over the WHOLE
-    // class (end rows included), the first sites of the two classes are the two sites of one block, and every regular row of the
-    // second class has its partner in the first
-    const bool use_pairs = !(getenv("TSU_K5_PAIR") && atoi(getenv("TSU_K5_PAIR")) == 0);
-    bool any_pair = false;
-    for (int c = 0; c < n_colors && use_pairs; ++c) {
-        K5Stencil& A = g->stencil[(size_t)c];
-        if (A.deg <= 0 || A.pair || A.site_stride != 2) continue;
-        for (int c2 = c + 1; c2 < n_colors; ++c2) {
-            K5Stencil& B = g->stencil[(size_t)c2];
-            if (B.deg <= 0 || B.pair || B.site_stride != 2) continue;
-            if ((order[A.pb] ^ 1) != order[B.pb]) continue;
-            bool ok = true;
-            for (int q = A.pb; q < A.pe && ok; ++q) ok = order[q] == order[A.pb] + 2 * (q - A.pb);
-            for (int q = B.pb; q < B.pe && ok; ++q) ok = order[q] == order[B.pb] + 2 * (q - B.pb);
-            if (!ok || (B.pe - B.hi) - B.pb > A.pe - A.pb) continue;  // (a regular row of B beyond A's last index would have no code)
-            A.pair = 1;
-            A.other = c2;
-            A.o_pb = B.pb;
-            A.o_lo = B.lo;
-            A.o_n = (B.pe - B.hi) - (B.pb + B.lo);
-            A.o_deg = B.deg;
-            B.pair = 2;
-            B.other = c;
-            any_pair = true;
-            break;
-        }
-    }
+    g->stencil = H.stencil;
     g->color_off.assign(color_offsets, color_offsets + n_colors + 1);
     hipError_t e = hipSuccess;
     auto up = [&](void** dst, const void* src, size_t bytes) {
@@ -656,6 +532,25 @@ int tsu_sparse_energy(tsu_sparse* g, double* energy, int64_t* sum_spins) {
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     *energy = h[0];
     if (sum_spins) *sum_spins = (int64_t)llround(h[1]);
+    return TSU_OK;
+}
+
+int tsu_sparse_classify(int n, const int64_t* row_ptr, const int32_t* col_idx, const double* values, const double* bias_host, int n_colors,
+                        const int32_t* color_offsets, const int32_t* order, int32_t* plan) {
+    if (!plan) return tsu_fail(nullptr, TSU_E_INVALID, "tsu_sparse_classify: NULL output");
+    K5Host H;
+    char msg[256];
+    if (!k5_host_prepare("tsu_sparse_classify", n, row_ptr, col_idx, values, bias_host, n_colors, color_offsets, order, H, msg, sizeof msg))
+        return tsu_fail(nullptr, TSU_E_INVALID, "%s", msg);
+    const bool use_v4 = k5_env_on("TSU_K5_V4");
+    for (int c = 0; c < n_colors; ++c) k5_plan_record(n, H.stencil[(size_t)c], use_v4, plan + (size_t)c * K5_PLAN_LEN);
+    return TSU_OK;
+}
+
+int tsu_sparse_class_plan(tsu_sparse* g, int color, int32_t* rec) {
+    if (!g) return TSU_E_INVALID;
+    TSU_REQUIRE(g->ctx, rec && color >= 0 && color < g->n_colors, "tsu_sparse_class_plan: bad arguments");
+    k5_plan_record(g->n, g->stencil[(size_t)color], k5_env_on("TSU_K5_V4"), rec);
     return TSU_OK;
 }
 

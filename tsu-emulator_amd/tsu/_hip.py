@@ -149,6 +149,8 @@ SIGNATURES = {
     "tsu_sparse_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
     "tsu_sparse_sample": (C.c_int, [_vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32, _i8p]),
     "tsu_sparse_energy": (C.c_int, [_vp, _f64p, _i64p]),
+    "tsu_sparse_classify": (C.c_int, [C.c_int, _i64p, _i32p, _f64p, _f64p, C.c_int, _i32p, _i32p, _i32p]),
+    "tsu_sparse_class_plan": (C.c_int, [_vp, C.c_int, _i32p]),
     "tsu_langevin_create": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "tsu_langevin_destroy": (C.c_int, [_vp]),
     "tsu_langevin_set_state": (C.c_int, [_vp, _f32p]),
@@ -1337,6 +1339,33 @@ class Comm:
         return v
 
 
+SPARSE_PLAN_FIELDS = ("route", "deg", "lo", "hi", "site_stride", "pair", "other", "v4", "o_lo", "o_n")
+ROUTE_COLOR, ROUTE_STENCIL, ROUTE_SMALL = 0, 1, 2
+
+
+def _plan_dicts(rec):
+    return [dict(zip(SPARSE_PLAN_FIELDS, (int(v) for v in row))) for row in rec.reshape(-1, len(SPARSE_PLAN_FIELDS))]
+
+
+def sparse_classify(row_ptr, col_idx, values, bias, color_offsets, order):
+    """Host helper of the library (no GPU needed): the plan SparseSystem would get for this graph and colouring -- one dict per
+    colour class with the fields SPARSE_PLAN_FIELDS (route: ROUTE_COLOR / ROUTE_STENCIL / ROUTE_SMALL; include/tsu_hip.h)."""
+    lib = load_library()
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int64)
+    ci = np.ascontiguousarray(col_idx, dtype=np.int32)
+    va = np.ascontiguousarray(values, dtype=np.float64)
+    n = rp.size - 1
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float64).reshape(n)
+    co = np.ascontiguousarray(color_offsets, dtype=np.int32)
+    od = np.ascontiguousarray(order, dtype=np.int32).reshape(n)
+    rec = np.zeros((co.size - 1, len(SPARSE_PLAN_FIELDS)), dtype=np.int32)
+    rc = lib.tsu_sparse_classify(n, _ptr(rp, _i64p), _ptr(ci, _i32p), _ptr(va, _f64p), None if b is None else _ptr(b, _f64p),
+                                 co.size - 1, _ptr(co, _i32p), _ptr(od, _i32p), _ptr(rec, _i32p))
+    if rc != TSU_OK:
+        raise ValueError(lib.tsu_last_error(None).decode())
+    return _plan_dicts(rec)
+
+
 class SparseSystem:
     """tsu_sparse handle: a sparse coupling graph (CSR, bit couplings incl. an optional diagonal) with a proper colouring,
     swept one colour class at a time (K5).  ``order`` lists the sites colour by colour, ``color_offsets`` delimits the
@@ -1385,6 +1414,13 @@ class SparseSystem:
         self.ctx.check(self.lib.tsu_sparse_sample(self.h, float(T), int(n_burnin), int(n_sweeps), int(n_samples), int(seed),
                                                   int(sweep0), int(replica), _ptr(out, _i8p)))
         return out
+
+    def plan(self):
+        """One dict per colour class (fields SPARSE_PLAN_FIELDS): the kernel the next sweep launches for it."""
+        rec = np.zeros((self.n_colors, len(SPARSE_PLAN_FIELDS)), dtype=np.int32)
+        for c in range(self.n_colors):
+            self.ctx.check(self.lib.tsu_sparse_class_plan(self.h, c, _ptr(rec[c], _i32p)))
+        return _plan_dicts(rec)
 
     def energy(self):
         """(-1/2 s'Js - b's of the resident bits, sum of the spins 2b-1)."""
