@@ -54,6 +54,30 @@ struct TiledParams {
     uint64_t thr[25];                     // full thresholds, [deg * 5 + up], for the tie path
 };
 
+// tile row ty of a launch: rows [row_off, row_off + H) of the launch's range
+static __host__ __device__ __forceinline__ void tile_rows(const TiledParams& p, int ty, int& row_off, int& H) {
+    H = p.tile_h;
+    row_off = ty * p.tile_h;
+    if (p.flex_ty > 0) {
+        const long long half = (p.r_end - p.r_begin + 1) / 2;  // (an open lattice of odd height: the last tile row ends one row past it)
+        row_off = 2 * (int)(ty * half / p.flex_ty);
+        H = 2 * (int)((ty + 1) * half / p.flex_ty) - row_off;
+    }
+}
+// global row of tile row 0 of that tile in a launch of k sweeps (wrapped on a periodic lattice), and whether the tile's window of
+// H + 4k rows holds the lattice's wrap row (row total_rows - 1 followed by row 0; never on an open lattice)
+static __host__ __device__ __forceinline__ bool tile_holds_wrap(const TiledParams& p, int ty, int k, long long& rg0) {
+    int H, row_off;
+    tile_rows(p, ty, row_off, H);
+    rg0 = p.row0 + p.r_begin + row_off - 2 * k;
+    if (p.open) return false;
+    rg0 %= p.total_rows;
+    if (rg0 < 0) rg0 += p.total_rows;
+    return rg0 + H + 4 * k > p.total_rows;
+}
+// A lattice whose height is a power of two takes the wrap in the Philox head (philox_vk) at no cost
+static __host__ __device__ __forceinline__ bool wrap_by_mask(const TiledParams& p) { return (p.total_rows & (p.total_rows - 1)) == 0; }
+
 static __device__ __forceinline__ uint32_t perm(uint32_t s0, uint32_t s1, uint32_t sel) {
     return __builtin_amdgcn_perm(s0, s1, sel);
 }
@@ -108,7 +132,7 @@ static __device__ __forceinline__ PhiloxKeys make_keys(uint32_t k0, uint32_t k1)
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         uint32_t x = k0 + (uint32_t)r * TSU_PHILOX_W0, y = k1 + (uint32_t)r * TSU_PHILOX_W1;
-        asm volatile("v_mov_b32 %0, %1" : "=v"(x) : "s"(x));  // opaque: keep the keys in vector registers
+        if (r > 0) asm volatile("v_mov_b32 %0, %1" : "=v"(x) : "s"(x));  // opaque: keep the keys in vector registers (a[0]: see philox_y0)
         asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "s"(y));
         K.a[r] = x;
         K.b[r] = y;
@@ -116,9 +140,34 @@ static __device__ __forceinline__ PhiloxKeys make_keys(uint32_t k0, uint32_t k1)
     return K;
 }
 
-static __device__ __forceinline__ u32x4 philox_vk(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, const PhiloxKeys& K) {
+// (a & b) ^ c in one v_bitop3_b32 (truth table 0x6A)
+static __device__ __forceinline__ uint32_t and_xor(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_bitop3_b32(a, b, c, 0x6A); }
+
+// The row enters the block in round 0 alone, as n0 = hi(M1 hs) ^ row ^ key: y0 = hi(M1 hs) ^ key is uniform per half-sweep
+// (philox_y0) and the head is (row & rmask) ^ y0 -- the same single instruction as the XOR3 it replaces.  With
+// rmask = total_rows - 1 on a lattice whose height is a power of two the periodic row wrap costs nothing: the caller's row
+// counter runs on past the last row.  Everyone else passes all ones.  K.a[0] is not used: it lives in y0.
+static __device__ __forceinline__ uint32_t philox_y0(uint32_t hs, uint32_t k0) {
+    uint32_t y = (uint32_t)(((uint64_t)TSU_PHILOX_M1 * hs) >> 32) ^ k0;
+    asm volatile("v_mov_b32 %0, %1" : "=v"(y) : "s"(y));  // a vector register, like the round keys (see PhiloxKeys)
+    return y;
+}
+
+static __device__ __forceinline__ u32x4 philox_vk(uint32_t c0, uint32_t row, uint32_t rmask, uint32_t y0, uint32_t c2, uint32_t c3,
+                                                  const PhiloxKeys& K) {
+    uint32_t c1;
+    {
+        const uint64_t p0 = (uint64_t)TSU_PHILOX_M0 * c0;
+        const uint64_t p1 = (uint64_t)TSU_PHILOX_M1 * c2;
+        const uint32_t n0 = and_xor(row, rmask, y0);
+        const uint32_t n2 = tsu_xor3((uint32_t)(p0 >> 32), c3, K.b[0]);
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+    }
 #pragma unroll
-    for (int r = 0; r < 10; ++r) {
+    for (int r = 1; r < 10; ++r) {
         uint64_t p0 = (uint64_t)TSU_PHILOX_M0 * c0;
         uint64_t p1 = (uint64_t)TSU_PHILOX_M1 * c2;
         uint32_t n0 = tsu_xor3((uint32_t)(p1 >> 32), c1, K.a[r]);
@@ -135,6 +184,7 @@ struct Rows2Ctx {
     const uint64_t* s_thr;
     int total_rows;
     int rg_tile0, wrap_tr;  // global row of tile row 0 (wrapped on a periodic lattice); EDGE tiles: the tile row whose global row is 0 again
+    uint32_t rmask;         // total_rows - 1 where the Philox head takes the row wrap (see philox_vk and tile_body), else all ones
     uint32_t tag_hi, tag_lo, k0, k1;
     uint32_t tblH0, tblH1, tblL0, tblL1;
     uint32_t t3H0, t3H1, t3L0, t3L1;  // open lattices: degree 3 / degree 2 byte tables
@@ -254,7 +304,7 @@ struct TilePlanes {
 // P0 = column parity of the updated colour in row tr (and 1-P0 in the row below it); it is the same for every half-sweep of
 // a tile: the first row of half-sweep hsi is tile row 1 + hsi and its colour hsi & 1, and their sum is always odd
 template <int NO, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM>
-static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t a, int rg, int to_wrap,
+static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t y0, uint32_t a, int rg, int to_wrap,
                                                  uint32_t cq) {
     constexpr int RS = 2 * NO * 8;                    // row stride
     constexpr int DO = (KAPPA ? NO : -NO) * 8;        // source plane -> destination plane
@@ -279,8 +329,8 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
     __builtin_amdgcn_sched_barrier(0);  // the reads stay above the Philox blocks ...
     int rga = rg, rgb = rg + 1;
     if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
-    const u32x4 w0 = philox_vk(cq, (uint32_t)rga, hs, c.tag_hi, K);
-    const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, hs, c.tag_hi, K);
+    const u32x4 w0 = philox_vk(cq, (uint32_t)rga, c.rmask, y0, hs, c.tag_hi, K);
+    const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.rmask, y0, hs, c.tag_hi, K);
     __builtin_amdgcn_sched_barrier(0);  // ... and their first use stays below
     const uint32_t C0l = (uint32_t)R1, C0h = (uint32_t)(R1 >> 32), C1l = (uint32_t)R2, C1h = (uint32_t)(R2 >> 32);
     // horizontal neighbours: compact bytes (j, j+1) when the parity is 1, (j-1, j) when it is 0
@@ -317,8 +367,8 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
     }
     const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
     if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
-        if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga, hs, c.tag_lo, c.k0, c.k1, edge_a);
-        if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb, hs, c.tag_lo, c.k0, c.k1, edge_b);
+        if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga & c.rmask, hs, c.tag_lo, c.k0, c.k1, edge_a);
+        if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb & c.rmask, hs, c.tag_lo, c.k0, c.k1, edge_b);
     }
     uint64_t n0 = pack_flags(d0), n1 = pack_flags(d1);
     if (OPEN) {  // what lies beyond the open edge stays empty (it is a neighbour of the edge sites in the next half-sweep)
@@ -341,7 +391,7 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
 // from them); every other address is an immediate, see pair_step.
 // EDGE (the tile's window crosses the lattice's last row): rg counts tile rows and the wrap is applied per wave, see edge_rows
 template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM = false>
-static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t a, int rg, int n, bool tail,
+static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t y0, uint32_t a, int rg, int n, bool tail,
                                                    uint32_t cq) {
     int to_wrap = EDGE ? c.wrap_tr - __builtin_amdgcn_readfirstlane(rg) : 0;  // from the wave's first lane (lanes ascend in rows)
     bool live = true;  // the last of the n + 1 trips runs under the lane mask `tail`: one copy of the body, a wave without a lane skips it
@@ -349,7 +399,7 @@ static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const Phil
     for (int i = n; i >= 0; --i) {
         if (i == 0) live = tail;
         asm volatile("" : "+v"(a), "+v"(rg));
-        if (live) pair_step<NO, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, a, rg, to_wrap, cq);
+        if (live) pair_step<NO, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, y0, a, rg, to_wrap, cq);
         a += 2 * RL * 2 * NO * 8;
         rg += 2 * RL;
         to_wrap -= 2 * RL;
@@ -390,7 +440,7 @@ static __device__ __forceinline__ uint32_t nib_pack(const u32x4& d) {
 
 // pair_step on nibble planes: the same addressing with dword octets (every offset halves)
 template <int NO, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM>
-static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t a, int rg, int to_wrap,
+static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t y0, uint32_t a, int rg, int to_wrap,
                                                      uint32_t cq) {
     constexpr int RS = 2 * NO * 4;
     constexpr int DO = (KAPPA ? NO : -NO) * 4;
@@ -401,8 +451,8 @@ static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const Ph
     __builtin_amdgcn_sched_barrier(0);
     int rga = rg, rgb = rg + 1;
     if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
-    const u32x4 w0 = philox_vk(cq, (uint32_t)rga, hs, c.tag_hi, K);
-    const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, hs, c.tag_hi, K);
+    const u32x4 w0 = philox_vk(cq, (uint32_t)rga, c.rmask, y0, hs, c.tag_hi, K);
+    const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.rmask, y0, hs, c.tag_hi, K);
     __builtin_amdgcn_sched_barrier(0);
     const uint32_t Sa = SEAM ? (P0 ? nib_shift_next_seam(R1, A0, c.sh_next) : nib_shift_prev_seam(R1, A0, c.sh_prev))
                              : (P0 ? nib_shift_next(R1, A0) : nib_shift_prev(R1, A0));
@@ -427,8 +477,8 @@ static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const Ph
     }
     const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
     if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
-        if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga, hs, c.tag_lo, c.k0, c.k1, edge_a);
-        if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb, hs, c.tag_lo, c.k0, c.k1, edge_b);
+        if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga & c.rmask, hs, c.tag_lo, c.k0, c.k1, edge_a);
+        if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb & c.rmask, hs, c.tag_lo, c.k0, c.k1, edge_b);
     }
     uint32_t n0 = nib_pack(d0), n1 = nib_pack(d1);
     if (OPEN) {  // what lies beyond the open edge stays empty (existing-site masks in the nibble layout)
@@ -444,7 +494,7 @@ static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const Ph
 }
 
 template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN = false, bool SEAM = false>
-static __device__ __forceinline__ void sweep_pairs_nib(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t a, int rg, int n, bool tail,
+static __device__ __forceinline__ void sweep_pairs_nib(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t y0, uint32_t a, int rg, int n, bool tail,
                                                        uint32_t cq) {
     int to_wrap = EDGE ? c.wrap_tr - __builtin_amdgcn_readfirstlane(rg) : 0;
     bool live = true;  // the last of the n + 1 trips runs under the lane mask `tail`: one copy of the body, a wave without a lane skips it
@@ -452,7 +502,7 @@ static __device__ __forceinline__ void sweep_pairs_nib(const Rows2Ctx& c, const 
     for (int i = n; i >= 0; --i) {
         if (i == 0) live = tail;
         asm volatile("" : "+v"(a), "+v"(rg));
-        if (live) pair_step_nib<NO, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, a, rg, to_wrap, cq);
+        if (live) pair_step_nib<NO, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, y0, a, rg, to_wrap, cq);
         a += 2 * RL * 2 * NO * 4;
         rg += 2 * RL;
         to_wrap -= 2 * RL;
@@ -477,12 +527,13 @@ static __device__ __forceinline__ void half_sweep(const Rows2Ctx& c, const Philo
             rg = 1 + hsi + 2 * al;
         } else {
             int rgf = c.rg_tile0 + 1 + hsi;
-            if (!OPEN && rgf >= c.total_rows) rgf -= c.total_rows;
+            if (!OPEN && rgf >= c.total_rows) rgf -= c.total_rows;  // (a window past the wrap row: only where c.rmask takes the wrap)
             rg = rgf + 2 * al;
         }
         const uint32_t hs = 2u * sweep + (uint32_t)KAPPA;
-        if constexpr (NIB) sweep_pairs_nib<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, a, rg, n, tail, cq);
-        else sweep_pairs<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, a, rg, n, tail, cq);
+        const uint32_t y0 = philox_y0(hs, c.k0);
+        if constexpr (NIB) sweep_pairs_nib<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, y0, a, rg, n, tail, cq);
+        else sweep_pairs<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, y0, a, rg, n, tail, cq);
     }
 }
 
@@ -528,13 +579,8 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
                                                  const PhiloxKeys& K, const ResidentParams* R = nullptr) {
     constexpr int NO = WO + 2;
     constexpr int RLMAX = THREADS / NO;
-    // tile row ty: rows [row_off, row_off + H) of the launch's range
-    int H = p.tile_h, row_off = ty * p.tile_h;
-    if (p.flex_ty > 0) {
-        const long long half = (p.r_end - p.r_begin + 1) / 2;  // (an open lattice of odd height: the last tile row ends one row past it)
-        row_off = 2 * (int)(ty * half / p.flex_ty);
-        H = 2 * (int)((ty + 1) * half / p.flex_ty) - row_off;
-    }
+    int H, row_off;
+    tile_rows(p, ty, row_off, H);
     const int TR = H + 4 * k;
     // Row lanes: threads [0, RL*NO) sweep (thread = one octet column x every RL-th row pair); all threads load and
     // store.  What a half-sweep costs is the busiest SIMD's sum of wave-iterations: with every lane in use the last,
@@ -615,18 +661,20 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
         }
     }
 
-    long long rg0 = p.row0 + Rb;
-    if (!OPEN) {
-        rg0 %= p.total_rows;
-        if (rg0 < 0) rg0 += p.total_rows;
-    }
-    const bool edge = !OPEN && (rg0 + TR > p.total_rows);  // open lattices do not wrap: rows beyond the edge are discarded
+    // A window that holds the lattice's wrap row: where the height is a power of two the pair loop's row counter runs on past the
+    // last row (up to rg0 + TR - 1 < 2 total_rows) and the Philox head masks it -- the plain loop; other heights take the EDGE loop,
+    // whose tiles are 1-2 us per generation slower than the plain ones and set every tile's pace (profiles/k1_row_mask_ab.txt).
+    // Open lattices do not wrap (rows beyond the edge are discarded, and may be negative: never masked).
+    long long rg0;
+    const bool holds_wrap = tile_holds_wrap(p, ty, k, rg0);
+    const bool edge = holds_wrap && !wrap_by_mask(p);
 
     Rows2Ctx c;
     c.s_thr = s_thr;
     c.total_rows = (int)p.total_rows;
     c.rg_tile0 = (int)rg0;
     c.wrap_tr = (int)(p.total_rows - rg0);
+    asm volatile("v_mov_b32 %0, %1" : "=v"(c.rmask) : "s"(holds_wrap && !edge ? (uint32_t)p.total_rows - 1u : 0xFFFFFFFFu));
     c.tag_hi = p.tag_hi; c.tag_lo = p.tag_lo; c.k0 = p.k0; c.k1 = p.k1;
     // the threshold byte tables live in VGPRs: v_perm_b32 may read only one SGPR, so SGPR tables cost a v_mov per use
     c.tblH0 = p.tblH0; c.tblH1 = p.tblH1; c.tblL0 = p.tblL0; c.tblL1 = p.tblL1;
@@ -976,7 +1024,9 @@ int lattice_env(const char* name, int dflt) {
 // 1000^2; profiles/r01_k1_experiments.txt): a half-sweep costs 0.25 us + 0.225 us per wave-iteration of the busiest SIMD (6 %
 // more on nibble planes); between generations `between` us: the strip exchange costs 4.3 us when the tiles stay resident in LDS,
 // the tile store + launch gap + stage about 12 us when they do not.  (The fit is older than the counted-down EDGE form of
-// edge_rows, which took about 0.1 us per sweep off 4096^2 and 0.2 us off 8192^2; it has not been re-fitted since.)
+// edge_rows, which took about 0.1 us per sweep off 4096^2 and 0.2 us off 8192^2, and older than the row wrap in the Philox head,
+// which took another 0.05 us and 0.4 us off them (profiles/k1_row_mask_ab.txt).  It has not been re-fitted: the chooser compares
+// shapes for one lattice, and both changes shorten the generations of every shape on that lattice's height alike.)
 double gen_time_us(const TileVariant& c, int h, double between) {
     const int pairs = (h + 4 * 8 - 2) / 2, waves = (pairs * (c.WO + 2) + 63) / 64;
     return 16.0 * (0.25 + (c.nib ? 1.06 : 1.0) * 0.225 * ((waves + 3) / 4)) + between;
@@ -1311,9 +1361,16 @@ int run_resident(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps,
             TSU_HIP_TRY(ctx, hipMalloc(&d_dbg, (size_t)4 * ntiles * sizeof(long long)));
             P.r.dbg = d_dbg;
         }
-        if (verbose)
-            fprintf(stderr, "[tsu] k1_resident variant %d: %d tiles (%d per CU fit), %d generations of %d sweeps, %zu KB of strips\n",
-                    c.v, ntiles, fit_per_cu, P.r.n_gen, kmax, xneed * 8 / 1024);
+        if (verbose) {
+            // how the tiles whose windows hold the lattice's wrap row take it (tile_body): in the Philox head or in the EDGE loop
+            bool any_wrap = false;
+            for (int ty = 0; ty < c.tiles_y && !any_wrap; ++ty) {
+                long long rg0;
+                any_wrap = tile_holds_wrap(P.t, ty, kmax, rg0);
+            }
+            fprintf(stderr, "[tsu] k1_resident variant %d: %d tiles (%d per CU fit), %d generations of %d sweeps, %zu KB of strips, row wrap: %s\n",
+                    c.v, ntiles, fit_per_cu, P.r.n_gen, kmax, xneed * 8 / 1024, !any_wrap ? "none" : (wrap_by_mask(P.t) ? "mask" : "compare"));
+        }
         {
             const int rcx = tsu_grid_exclusive_begin(ctx);
             if (rcx != TSU_OK) return rcx;
@@ -1528,7 +1585,7 @@ __global__ __launch_bounds__(1024) void k1_planes(const PlanesItem* __restrict__
             const uint64_t S = par ? ((C >> 8) | ((A & 0xFFull) << shl)) : ((C << 8) | ((A >> shr) & 0xFFull));
             const uint64_t cnt = U + D + C + S;  // bytes <= 4: no carries between sites
             const uint32_t cnt_lo = (uint32_t)cnt, cnt_hi = (uint32_t)(cnt >> 32);
-            const u32x4 w = philox_vk((uint32_t)q, (uint32_t)r, hs, tag_hi, K);
+            const u32x4 w = philox_vk((uint32_t)q, (uint32_t)r, 0xFFFFFFFFu, philox_y0(hs, k0), hs, tag_hi, K);
             u32x4 d;
             uint32_t edge = 0;
             if (OPEN) {
