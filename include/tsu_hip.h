@@ -354,6 +354,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * Python. */
 #include "tsu_hip_ensemble.h"
 
+/* K5: walker batches on a sparse graph, many tempering ladders or annealing restarts of one tsu_sparse graph per launch (the
+ * tsu_sparse_batch handle): declared in tsu_hip_sparse_batch.h, which this header includes; its prototypes are
+ * _hip.SPARSE_BATCH_SIGNATURES in Python. */
+#include "tsu_hip_sparse_batch.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

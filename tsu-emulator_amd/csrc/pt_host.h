@@ -219,6 +219,10 @@ void pt_enqueue_energies(pt_ladder* P, unsigned blocks, Partials&& partials) {
     pt_energy_final<<<(unsigned)P->nw, 256, 0, P->ctx->stream>>>(P->d_part, P->d_ipart, (int)blocks, P->d_E, P->d_M);
 }
 
+// the swap pass of `rows` ladders (one workgroup each) on `st`: the one launch of k7_pt_swap, for the lattice handles' rounds below and
+// for the walker batches on a sparse graph (sparse_batch.hip), which fill a PTSwap from tables of their own
+inline void pt_enqueue_swap(const PTSwap& sw, unsigned rows, hipStream_t st) { k7_pt_swap<<<rows, 64, 0, st>>>(sw); }
+
 // ---------------------------------------------------------------- correlation recording (corr_dev.h)
 // (templates: the population handle, pop_host.h, keeps its axes under the same names)
 template <class H>
@@ -479,7 +483,7 @@ int pt_run(pt_ladder* P, int n_rounds, int swap_interval, int do_swap, int recor
             sw.hM = record ? P->d_hM + row : nullptr;
             sw.hW = record ? P->d_hW + row : nullptr;
             sw.t = P->rounds;
-            k7_pt_swap<<<(unsigned)(S * nl), 64, 0, ctx->stream>>>(sw);
+            pt_enqueue_swap(sw, (unsigned)(S * nl), ctx->stream);
             if (record && nl == 2)
                 pt_overlap<<<dim3(blocks, (unsigned)SR, 1), 256, 0, ctx->stream>>>(P->d_s, P->d_was, R, P->pitch, P->nrows, P->cols,
                                                                                   P->d_hq + (size_t)t * SR);

@@ -25,6 +25,7 @@ from .core import (  # noqa: F401
 from .core import ThermalSamplingUnit as TSU  # noqa: F401
 from .gibbs import GibbsConfig, GibbsSampler, HardwareEmulator  # noqa: F401
 from .models import (  # noqa: F401
+    GraphTempering,
     IsingChain,
     IsingGrid,
     IsingModel,
@@ -53,4 +54,5 @@ __all__ = [
     "PopulationAnnealing", "PopulationAnnealing3D",
     "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
     "tempering_ensemble_scan", "tempering_ensemble_scan_3d",
+    "GraphTempering",
 ]

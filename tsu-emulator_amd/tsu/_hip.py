@@ -238,6 +238,24 @@ for _pre, _shape, _nj in (("tsu_pte2d_", [C.c_int, C.c_int, C.c_int], 2), ("tsu_
         _pre + "profiles": (C.c_int, [_vp, C.c_int, C.c_int] + [_i64p] * _nj),
     })
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_sparse_batch.h (the header tsu_hip.h includes) one to one
+SPARSE_BATCH_SIGNATURES = {
+    "tsu_sparse_batch_create": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "tsu_sparse_batch_destroy": (C.c_int, [_vp]),
+    "tsu_sparse_batch_set_temperatures": (C.c_int, [_vp, _f64p]),
+    "tsu_sparse_batch_init": (C.c_int, [_vp, C.c_uint64, C.c_int]),
+    "tsu_sparse_batch_set_state": (C.c_int, [_vp, C.c_int, C.c_int, _i8p]),
+    "tsu_sparse_batch_get_state": (C.c_int, [_vp, C.c_int, C.c_int, _i8p]),
+    "tsu_sparse_batch_run": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tsu_sparse_batch_history": (C.c_int, [_vp, _f64p, _i64p, _i32p]),
+    "tsu_sparse_batch_stats": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i32p, _u64p]),
+    "tsu_sparse_batch_energies": (C.c_int, [_vp, _f64p, _i64p]),
+    "tsu_sparse_batch_track_best": (C.c_int, [_vp, C.c_int]),
+    "tsu_sparse_batch_best": (C.c_int, [_vp, C.c_int, _f64p, _i8p, _i32p]),
+    "tsu_sparse_batch_plan": (C.c_int, [_vp, _i32p]),
+    "tsu_sparse_batch_launch_count": (C.c_int, [_vp, _u64p]),
+}
+
 _lib = None
 
 
@@ -256,7 +274,7 @@ def load_library():
         raise HipUnavailableError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items())
                               + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())
-                              + list(ENSEMBLE_SIGNATURES.items())):
+                              + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1427,6 +1445,104 @@ class SparseSystem:
         e, m = C.c_double(0), C.c_int64(0)
         self.ctx.check(self.lib.tsu_sparse_energy(self.h, C.byref(e), C.byref(m)))
         return e.value, m.value
+
+
+SPARSE_BATCH_PLAN_FIELDS = ("route", "walkers_per_thread", "padded_walkers", "launches_per_sweep", "launches_per_round_fixed",
+                            "energy_segments")
+BATCH_ROUTE_COLOR, BATCH_ROUTE_SMALL = 0, 1
+BATCH_MAX_TEMPS, BATCH_MAX_WALKERS = 256, 65535
+
+
+class SparseBatch:
+    """tsu_sparse_batch handle: ``n_ladders`` ladders of ``n_temps`` walkers on the graph of one :class:`SparseSystem` (which it keeps
+    alive).  Walker g = ladder * n_temps + w starts at slot w; sweeps, energies and swap passes are batched launches and ``run`` waits
+    for nothing (include/tsu_hip_sparse_batch.h).  States are {0,1} int8 in site order."""
+
+    def __init__(self, graph, n_temps, n_ladders=1):
+        self.graph = graph
+        self.ctx, self.lib = graph.ctx, graph.lib
+        self.n, self.R, self.nl = graph.n, int(n_temps), int(n_ladders)
+        h = _vp()
+        self.ctx.check(self.lib.tsu_sparse_batch_create(graph.h, self.R, self.nl, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_sparse_batch_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def set_temperatures(self, T):
+        t = np.ascontiguousarray(T, dtype=np.float64).reshape(self.R)
+        self.ctx.check(self.lib.tsu_sparse_batch_set_temperatures(self.h, _ptr(t, _f64p)))
+
+    def init(self, seed, initial=0):
+        self.ctx.check(self.lib.tsu_sparse_batch_init(self.h, int(seed), int(initial)))
+
+    def set_state(self, ladder, slot, bits):
+        b = np.ascontiguousarray(bits, dtype=np.int8).reshape(self.n)
+        self.ctx.check(self.lib.tsu_sparse_batch_set_state(self.h, int(ladder), int(slot), _ptr(b, _i8p)))
+
+    def get_state(self, ladder, slot):
+        out = np.empty(self.n, dtype=np.int8)
+        self.ctx.check(self.lib.tsu_sparse_batch_get_state(self.h, int(ladder), int(slot), _ptr(out, _i8p)))
+        return out
+
+    def run(self, n_rounds, swap_interval, do_swap=True, record=True):
+        self.ctx.check(self.lib.tsu_sparse_batch_run(self.h, int(n_rounds), int(swap_interval), int(bool(do_swap)), int(bool(record))))
+        if record:
+            self._hist_rounds = int(n_rounds)
+        else:
+            self._hist_rounds = 0
+
+    def history(self):
+        """E, M, walker of the last recording run, each (rounds, n_ladders, n_temps)."""
+        n = getattr(self, "_hist_rounds", 0)
+        E = np.zeros((n, self.nl, self.R), dtype=np.float64)
+        M = np.zeros((n, self.nl, self.R), dtype=np.int64)
+        W = np.zeros((n, self.nl, self.R), dtype=np.int32)
+        self.ctx.check(self.lib.tsu_sparse_batch_history(self.h, _ptr(E, _f64p), _ptr(M, _i64p), _ptr(W, _i32p)))
+        return E, M, W
+
+    def stats(self):
+        att = np.zeros((self.nl, self.R - 1), dtype=np.int64)
+        acc = np.zeros((self.nl, self.R - 1), dtype=np.int64)
+        trips = np.zeros((self.nl, self.R), dtype=np.int64)
+        was = np.zeros((self.nl, self.R), dtype=np.int32)
+        sweeps = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_sparse_batch_stats(self.h, _ptr(att, _i64p), _ptr(acc, _i64p), _ptr(trips, _i64p), _ptr(was, _i32p),
+                                                       C.byref(sweeps)))
+        return {"attempts": att, "accepts": acc, "round_trips": trips, "walker_at_slot": was, "sweep_count": int(sweeps.value)}
+
+    def energies(self):
+        """(E, sum of spins) of every walker now, each (n_ladders, n_temps) indexed by WALKER."""
+        E = np.zeros((self.nl, self.R), dtype=np.float64)
+        M = np.zeros((self.nl, self.R), dtype=np.int64)
+        self.ctx.check(self.lib.tsu_sparse_batch_energies(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
+        return E, M
+
+    def track_best(self, enable=True):
+        self.ctx.check(self.lib.tsu_sparse_batch_track_best(self.h, int(bool(enable))))
+
+    def best(self, ladder, bits=True):
+        """(energy, bits or None, walker) of the ladder's lowest best energy (the first such walker)."""
+        e, w = C.c_double(0), C.c_int32(0)
+        out = np.empty(self.n, dtype=np.int8) if bits else None
+        self.ctx.check(self.lib.tsu_sparse_batch_best(self.h, int(ladder), C.byref(e), None if out is None else _ptr(out, _i8p), C.byref(w)))
+        return e.value, out, int(w.value)
+
+    def plan(self):
+        rec = np.zeros(len(SPARSE_BATCH_PLAN_FIELDS), dtype=np.int32)
+        self.ctx.check(self.lib.tsu_sparse_batch_plan(self.h, _ptr(rec, _i32p)))
+        return dict(zip(SPARSE_BATCH_PLAN_FIELDS, (int(v) for v in rec)))
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_sparse_batch_launch_count(self.h, C.byref(n)))
+        return int(n.value)
 
 
 class LangevinChains:

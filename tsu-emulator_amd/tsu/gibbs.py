@@ -433,7 +433,15 @@ class GibbsSampler:
     # ------------------------------------------------------------------ host loops around the sweep
     def parallel_tempering(self, coupling: np.ndarray, temperatures: List[float], bias: Optional[np.ndarray] = None,
                            n_samples: int = 1000, swap_interval: int = 10) -> Tuple[np.ndarray, dict]:
-        """Reference: tsu/gibbs.py:238-338 (replica exchange; swap rule :317-323)."""
+        """Reference: tsu/gibbs.py:238-338 (replica exchange; swap rule :317-323).
+
+        A ``scipy.sparse`` ``coupling`` has no reference counterpart (the reference tempers a dense matrix only): it runs as one
+        ladder of a walker batch on the graph (``tsu.models.GraphTempering``), with the swap passes on the device and the
+        detailed-balance rule ``(1/T_i - 1/T_j) (E_i - E_j)`` instead of the reference's inverted ``E_j - E_i``.  Like every sparse
+        entry it needs ``rng="philox"`` and sequential order.  Same ``(samples, info)`` and ``info`` keys; ``energies`` are the
+        device's record."""
+        if _is_sparse(coupling):
+            return self._parallel_tempering_sparse(coupling, temperatures, bias, n_samples, swap_interval)
         n_replicas = len(temperatures)
         coupling = np.asarray(coupling)
         n_bits = coupling.shape[0]
@@ -472,6 +480,43 @@ class GibbsSampler:
                 self._held = None
             for rep in samplers:
                 rep.invalidate()
+
+    def _parallel_tempering_sparse(self, coupling, temperatures, bias, n_samples, swap_interval):
+        from .models.graph_tempering import GraphTempering
+        if self.rng != "philox":
+            raise ValueError("sparse couplings run in colour-parallel order: rng must be 'philox'")
+        if self.config.update_order != "sequential":
+            raise ValueError("sparse couplings run in colour-parallel order: update_order must be 'sequential'")
+        n_replicas = len(temperatures)
+        n_sweeps, n_burnin = int(self.config.n_sweeps), int(self.config.n_burnin)
+        pt = GraphTempering(coupling, temperatures, bias=bias, ladders=1, seed=self._philox_seed(), initial="zeros")
+        try:
+            n_bits = pt.n
+            for i in range(n_replicas):
+                pt.set_state(i, np.random.randint(0, 2, size=n_bits))
+            if n_burnin > 0:
+                pt.run(1, n_burnin, swap=False, record=False)
+            samples = np.zeros((n_samples, n_bits), dtype=int)
+            energies_history = [[] for _ in range(n_replicas)]
+            for k in range(1, n_samples + 1):
+                pt.run(1, max(1, n_sweeps), swap=(k % swap_interval == 0), record=True)
+                row = pt.history()["E"][0]
+                for i in range(n_replicas):
+                    energies_history[i].append(float(row[i]))
+                samples[k - 1] = pt.state(0)
+            attempts, accepts = pt.swap_counts()
+            swap_attempts, swap_accepts = int(attempts.sum()), int(accepts.sum())
+            states = [pt.state(i).astype(int) for i in range(n_replicas)]
+        finally:
+            pt.close()
+        info = {
+            "swap_acceptance_rate": swap_accepts / swap_attempts if swap_attempts > 0 else 0,
+            "swap_attempts": swap_attempts,
+            "swap_accepts": swap_accepts,
+            "energies": energies_history,
+            "final_states": states,
+        }
+        return samples, info
 
     def _parallel_tempering_run(self, samplers, states, coupling, bias, temperatures, n_samples, swap_interval, energy_of):
         n_replicas = len(temperatures)
