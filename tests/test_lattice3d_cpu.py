@@ -287,3 +287,23 @@ def test_symbols_in_header_library_and_signatures():
         assert hasattr(mod, "IsingModel3D") and hasattr(mod, "temperature_scan_3d")
         assert "IsingModel3D" in mod.__all__ and "temperature_scan_3d" in mod.__all__
 
+
+
+def test_decision_rule_is_written_once():
+    """K7 and K8, single lattices and walker groups, run one octet body (disorder_dev.h): over all of csrc the exact threshold and
+    the screen are each called once, the lo16 draw does not appear in either dimension's file, and there is one energy lane and one
+    ensemble struct.  Comments are not code: they are dropped before counting."""
+    import re
+    csrc = os.path.join(ROOT, "tsu-emulator_amd", "csrc")
+    raw = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    code = "\n".join(re.sub(r"//[^\n]*", "", s) for s in raw.values())
+    for fn, ret in (("exact_thr", "uint64_t"), ("screen", "int")):
+        defs = len(re.findall(rf"\b{ret}\s+{fn}\s*\(", code))
+        uses = len(re.findall(rf"\b{fn}\s*\(", code)) - defs
+        assert (defs, uses) == (1, 1), (fn, defs, uses)
+    for name in ("ising2d_disorder.hip", "ising3d.hip"):
+        assert "TSU_TAG_ISING_LO" not in raw[name], name
+    assert set(re.findall(r"\b\w*energy_lane\w*\b", code)) == {"energy_lane"}
+    assert len(re.findall(r"\bdouble\s+energy_lane\s*\(", code)) == 1
+    assert len(re.findall(r"\bstruct\s+PTEns\b", code)) == 1
+    assert "disorder_dev.h" in open(os.path.join(csrc, "build.sh")).read()

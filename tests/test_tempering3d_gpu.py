@@ -180,7 +180,7 @@ def test_without_swaps_equals_temperature_scan_3d(hip, shape, periodic, replicas
 @pytest.mark.parametrize("rows,cols,periodic", [(6, 40, True), (5, 37, False)])
 def test_one_layer_ladder_has_the_2d_ladders_spins(hip, rows, cols, periodic):
     """D = 1, open z, swap=False: the spins of the 2-D TemperingLattice on the same arrays.  Then four swapping, recorded rounds
-    on both: with one open layer k8_energy_lane adds h, J_right and J_down in k7_energy_lane's order over the same lanes, so the
+    on both: with one open layer energy_lane<3> adds h, J_right and J_down in energy_lane<2>'s order over the same lanes, so the
     energies, and with them the swaps, the history, the counters and the spins at every slot, are equal exactly."""
     shape = (1, rows, cols)
     jr, jd, _, h = _disorder(shape, (False, periodic, periodic), 11)

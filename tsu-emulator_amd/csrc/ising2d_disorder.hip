@@ -13,9 +13,9 @@
 // k7_sweep: one launch per half-sweep, one lane per octet (16 consecutive columns of one row = 8 sites of the colour, the
 // unit of one Philox block), 64 x 4 lanes per workgroup = one row per wave, so the column parity of the colour is uniform
 // in a wave.  The lane screens its 8 sites in fp32 and only takes the float64 threshold of the contract where the fp32
-// probability lies within a margin of the hi16 uniform (see screen() for the bound).  The spins are updated in place (a
-// colour reads only the other colour), 16-byte masked stores, pad bytes untouched.  Every whole lattice K1 takes runs here
-// (one-row and one-column lattices included); slabs are refused.
+// probability lies within a margin of the hi16 uniform (disorder_dev.h: the bound with screen, and the octet itself, Octet, which is
+// K8's with the z terms compiled out).  The spins are updated in place (a colour reads only the other colour), 16-byte masked stores,
+// pad bytes untouched.  Every whole lattice K1 takes runs here (one-row and one-column lattices included); slabs are refused.
 //
 // Bytes: per half-sweep the launch reads every byte of the three disorder rows it touches (12 B per site: the lines hold both
 // colours) and the spins (~3 B per site, up / down rows from L2), writes 1 B per site: ~28 B per site and sweep against the
@@ -27,10 +27,11 @@
 // populations' rows) is link_dev.h's, a 2-D lattice being its one-layer case.
 //
 // Parallel tempering (tsu_pt2d_*): ladders of R walkers on ONE disorder ("Parallel tempering (K7)").
-// k7_pt_sweep is k7_sweep for a group of W walkers per lane: the octet's disorder is loaded once and every walker of the group
-// takes K7's decision at the temperature of its slot (a device table the swap kernel keeps), so the 24 B per site of disorder
-// a sweep reads are shared by W walkers.  k7_pt_energy runs k7_energy's decomposition per walker (the same bits as the
-// single-lattice call) and sums the spins alongside.  The rest of a ladder does not know the dimension and is shared with the 3-D
+// k7_pt_sweep is k7_sweep for a group of W walkers per lane: the octet's disorder is loaded and its 8 sites are staged once
+// (octet_group, disorder_dev.h) and every walker of the group takes K7's decision at the temperature of its slot (a device table the
+// swap kernel keeps), so the 24 B per site of disorder a sweep reads are shared by W walkers.  k7_pt_energy runs k7_energy's
+// decomposition per walker through the same device helper (energy_lane: the same bits as the single-lattice call) and sums the
+// spins alongside.  The rest of a ladder does not know the dimension and is shared with the 3-D
 // ladders: the handle's tables and the host side of every entry point (pt_host.h: create, init, the run loop, history, ..), the
 // final sums and q per slot (pt_energy_final, pt_overlap, reduce_dev.h) and the swap pass (k7_pt_swap, pt_dev.h).  This file
 // passes in how a half-sweep and an energy partial pass are launched, and the hook that ends a round's sweeps with the replica
@@ -69,138 +70,30 @@ struct tsu_pte2d : pte_handle {
 namespace {
 
 struct K7Params {
-    int8_t* s;           // owned row 0 of the current spin buffer
-    const float* jr;     // J_right, J_down, h: row pitch = `pitch` elements
-    const float* jd;
-    const float* h;
-    long long pitch;
-    int rows, cols, periodic;
-    float c32;           // fl32(2 / T): the screen's scale
-    double T;
-    uint32_t k0, k1, hs, tag_hi, tag_lo;
+    Geo g;      // J_right, J_down, h: row pitch = the spin buffer's
+    Walker w;   // owned row 0 of the current spin buffer, T, keys and tags
+    uint32_t hs;
 };
 
-// sbyte, fat, load16f, exact_thr and screen (with the derivation of its margin) live in disorder_dev.h, the workgroup sums, the final
-// sums, the pair lane and kEnergyBlocks in reduce_dev.h: both shared with K8
+// The octet (Octet: loads, screen, exact branch, lo16 draw, store), the energy lane, Geo / Walker / PTParams / PTEns live in
+// disorder_dev.h, the workgroup sums, the final sums, the pair lane and kEnergyBlocks in reduce_dev.h: all shared with K8
 
-// one octet of the colour whose sites sit at chunk positions PAR, PAR + 2, ..
-template <int PAR>
-__device__ __forceinline__ void k7_octet(const K7Params& p, int r, int q) {
-    const long long row = (long long)r * p.pitch;
-    const int c0 = 16 * q;
-    const bool has_up = r > 0 || p.periodic, has_dn = r + 1 < p.rows || p.periodic;
-    const long long rowu = (long long)(r > 0 ? r - 1 : p.rows - 1) * p.pitch;
-    const long long rowd = (long long)(r + 1 < p.rows ? r + 1 : 0) * p.pitch;
-    const uint4 zero4 = make_uint4(0, 0, 0, 0);
-    const uint4 C = *reinterpret_cast<const uint4*>(p.s + row + c0);
-    const uint4 U = has_up ? *reinterpret_cast<const uint4*>(p.s + rowu + c0) : zero4;
-    const uint4 D = has_dn ? *reinterpret_cast<const uint4*>(p.s + rowd + c0) : zero4;
-    float4 jr[4], jd[4], ju[4], hh[4];
-    load16f(p.jr + row + c0, jr);
-    load16f(p.jd + row + c0, jd);
-    load16f(p.h + row + c0, hh);
-    if (has_up) load16f(p.jd + rowu + c0, ju);
-    else
-        for (int k = 0; k < 4; ++k) ju[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    // column c0 - 1 (left of position 0), column c0 + 16 (right of position 15), column 0 (right of the last column, periodic)
-    const bool has_prev = q > 0 || p.periodic;
-    const int cprev = q > 0 ? c0 - 1 : p.cols - 1;
-    const int s_prev = has_prev ? (int)p.s[row + cprev] : 0;
-    const float j_prev = has_prev ? p.jr[row + cprev] : 0.0f;
-    const int s_next = (c0 + 16 < p.cols) ? (int)p.s[row + c0 + 16] : 0;
-    const int s_first = p.periodic ? (int)p.s[row] : 0;
-
-    const u32x4 w = tsu_philox((uint32_t)q, (uint32_t)r, p.hs, p.tag_hi, p.k0, p.k1);
-    const uint32_t wv[4] = {w.x, w.y, w.z, w.w};
-    bool have_lo = false;
-    uint32_t lv[4] = {0, 0, 0, 0};
-    uint32_t out[4] = {C.x, C.y, C.z, C.w};
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        const int i = 2 * m + PAR, c = c0 + i;
-        if (c >= p.cols) break;
-        const bool has_left = i > 0 || has_prev, has_right = c + 1 < p.cols || p.periodic;
-        const int su = sbyte(U, i), sd = sbyte(D, i);
-        const int sl = i > 0 ? sbyte(C, i - 1) : s_prev;
-        const int sr = c + 1 < p.cols ? (i < 15 ? sbyte(C, i + 1) : s_next) : s_first;
-        const float Ju = has_up ? fat(ju, i) : 0.0f, Jd = has_dn ? fat(jd, i) : 0.0f;
-        const float Jl = has_left ? (i > 0 ? fat(jr, i - 1) : j_prev) : 0.0f;
-        const float Jr = has_right ? fat(jr, i) : 0.0f;
-        const float hf = fat(hh, i);
-        // missing neighbours carry J = 0 here: exact in fp32, and the screen only needs a bound
-        const float f32 = (((Ju * (float)su + Jd * (float)sd) + Jl * (float)sl) + Jr * (float)sr) + hf;
-        const float a32 = fabsf(Ju) + fabsf(Jd) + fabsf(Jl) + fabsf(Jr) + fabsf(hf);
-        const uint32_t hi = ((wv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu) ^ 0x8000u;
-        int dec = screen(f32, a32, p.c32, hi);
-        if (dec == 0) {
-            // the contract's sum: neighbours in the order up, down, left, right, a missing one skipped, then h
-            double f = 0.0;
-            bool any = false;
-            if (has_up) { f = (double)Ju * su; any = true; }
-            if (has_dn) { f = any ? f + (double)Jd * sd : (double)Jd * sd; any = true; }
-            if (has_left) { f = any ? f + (double)Jl * sl : (double)Jl * sl; any = true; }
-            if (has_right) { f = any ? f + (double)Jr * sr : (double)Jr * sr; any = true; }
-            f = any ? f + (double)hf : (double)hf;
-            const uint64_t thr = exact_thr(f, p.T);
-            const uint32_t thi = (uint32_t)(thr >> 16);
-            bool accept = hi < thi;
-            if (hi == thi) {  // tie on the top 16 bits: the low half, as K1 draws it
-                if (!have_lo) {
-                    const u32x4 l = tsu_philox((uint32_t)q, (uint32_t)r, p.hs, p.tag_lo, p.k0, p.k1);
-                    lv[0] = l.x; lv[1] = l.y; lv[2] = l.z; lv[3] = l.w;
-                    have_lo = true;
-                }
-                const uint32_t lo = (lv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu;
-                accept = (((uint64_t)hi << 16) | lo) < thr;
-            }
-            dec = accept ? 1 : -1;
-        }
-        const uint32_t b = dec > 0 ? 0x01u : 0xFFu;
-        const int sh = 8 * (i & 3);
-        out[i >> 2] = (out[i >> 2] & ~(0xFFu << sh)) | (b << sh);
-    }
-    *reinterpret_cast<uint4*>(p.s + row + c0) = make_uint4(out[0], out[1], out[2], out[3]);
+// lane = octet q of row r: grid (ceil(nchunks / 64), ceil(rows / 4)), 64 x 4 lanes
+__device__ __forceinline__ bool k7_lane(const Geo& g, int& r, int& q) {
+    q = blockIdx.x * 64 + threadIdx.x;
+    r = blockIdx.y * 4 + threadIdx.y;
+    return r < g.rows && 16 * q < g.cols;
 }
 
-// grid (ceil(nchunks / 64), ceil(rows / 4)), 64 x 4 lanes: lane = octet q of row r
 __global__ __launch_bounds__(256) void k7_sweep(K7Params p, int colour) {
-    const int q = blockIdx.x * 64 + threadIdx.x;
-    const int r = blockIdx.y * 4 + threadIdx.y;
-    if (r >= p.rows || 16 * q >= p.cols) return;
-    if (((r + colour) & 1) == 0) k7_octet<0>(p, r, q);
-    else k7_octet<1>(p, r, q);
-}
-
-// E partial of a lane: lane = chunk (r, q), grid-stride over blockIdx.x in a fixed order; ssum = the lane's sum of spins
-__device__ __forceinline__ double k7_energy_lane(const K7Params& p, long long& ssum) {
-    const int nchunks = (p.cols + 15) >> 4;
-    const long long total = (long long)p.rows * nchunks;
-    double e = 0.0;
-    long long m = 0;
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
-        const int r = (int)(t / nchunks), q = (int)(t - (long long)r * nchunks);
-        const long long row = (long long)r * p.pitch;
-        const bool has_dn = r + 1 < p.rows || p.periodic;
-        const long long rowd = (long long)(r + 1 < p.rows ? r + 1 : 0) * p.pitch;
-        for (int i = 0; i < 16; ++i) {
-            const int c = 16 * q + i;
-            if (c >= p.cols) break;
-            const int s = p.s[row + c];
-            double l = (double)p.h[row + c];
-            if (c + 1 < p.cols || p.periodic) l += (double)p.jr[row + c] * p.s[row + (c + 1 < p.cols ? c + 1 : 0)];
-            if (has_dn) l += (double)p.jd[row + c] * p.s[rowd + c];
-            e += s * l;
-            m += s;
-        }
-    }
-    ssum = m;
-    return e;
+    int r, q;
+    if (k7_lane(p.g, r, q)) octet_single<2>(p.g, p.w, p.hs, 0, r, q, colour);
 }
 
 // E partials: one per workgroup
 __global__ __launch_bounds__(256) void k7_energy(K7Params p, double* __restrict__ part) {
     long long m;
-    const double e = block_sum(k7_energy_lane(p, m));
+    const double e = block_sum(energy_lane<2>(p.g, p.w.s, m));
     if (threadIdx.x == 0) part[blockIdx.x] = e;
 }
 
@@ -214,277 +107,100 @@ __global__ __launch_bounds__(256) void k7_overlap(const int8_t* __restrict__ a, 
 // ------------------------------------------------------------------ parallel tempering
 // the swap pass lives in pt_dev.h, the final sums and q per slot in reduce_dev.h, the host side in pt_host.h: shared with ising3d.hip
 
-struct PTParams {
-    int8_t* const* s;     // walker g = ladder * R + w -> owned row 0 of its spin plane (one pitch for all)
-    const uint32_t* key;  // walker -> Philox key (k0, k1) of seed + g
-    const int32_t* slot;  // walker -> its slot in its ladder
-    const double* T;      // slot -> T
-    const float* c32;     // slot -> fl32(2 / T)
-    const float* jr;      // the one disorder (K7Params layout)
-    const float* jd;
-    const float* h;
-    long long pitch;
-    int rows, cols, periodic;
-    int nw, W;            // walkers; walkers per lane (group z of the grid: walkers [z W, z W + W))
-    uint32_t hs;
-};
-
-// k7_octet for the walkers [g0, g1): the colour's couplings and fields are loaded once, then each walker takes the same
-// decision as k7_octet at the temperature of its slot, with its own key (replica 0)
-template <int PAR>
-__device__ __forceinline__ void k7_pt_octet(const PTParams& p, int r, int q, int g0, int g1) {
-    const long long row = (long long)r * p.pitch;
-    const int c0 = 16 * q;
-    const bool has_up = r > 0 || p.periodic, has_dn = r + 1 < p.rows || p.periodic;
-    const long long rowu = (long long)(r > 0 ? r - 1 : p.rows - 1) * p.pitch;
-    const long long rowd = (long long)(r + 1 < p.rows ? r + 1 : 0) * p.pitch;
-    const bool has_prev = q > 0 || p.periodic;
-    const int cprev = q > 0 ? c0 - 1 : p.cols - 1;
-    // the colour's 8 sites: J to the up, down, left and right neighbour (0 where it is missing), h, and the screen's sum of |terms|
-    float Ju[8], Jd[8], Jl[8], Jr[8], hf[8], a32[8];
-    {
-        float4 jr[4], jd[4], ju[4], hh[4];
-        load16f(p.jr + row + c0, jr);
-        load16f(p.jd + row + c0, jd);
-        load16f(p.h + row + c0, hh);
-        if (has_up) load16f(p.jd + rowu + c0, ju);
-        else
-            for (int k = 0; k < 4; ++k) ju[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-        const float j_prev = has_prev ? p.jr[row + cprev] : 0.0f;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int i = 2 * m + PAR, c = c0 + i;
-            const bool has_left = i > 0 || has_prev, has_right = c + 1 < p.cols || p.periodic;
-            Ju[m] = has_up ? fat(ju, i) : 0.0f;
-            Jd[m] = has_dn ? fat(jd, i) : 0.0f;
-            Jl[m] = has_left ? (i > 0 ? fat(jr, i - 1) : j_prev) : 0.0f;
-            Jr[m] = has_right ? fat(jr, i) : 0.0f;
-            hf[m] = fat(hh, i);
-            a32[m] = fabsf(Ju[m]) + fabsf(Jd[m]) + fabsf(Jl[m]) + fabsf(Jr[m]) + fabsf(hf[m]);
-        }
-    }
-    const uint4 zero4 = make_uint4(0, 0, 0, 0);
-#pragma unroll 1
-    for (int g = g0; g < g1; ++g) {
-        int8_t* const s = p.s[g];
-        const int slot = p.slot[g];
-        const double T = p.T[slot];
-        const float c32 = p.c32[slot];
-        const uint32_t k0 = p.key[2 * g], k1 = p.key[2 * g + 1];
-        const uint4 C = *reinterpret_cast<const uint4*>(s + row + c0);
-        const uint4 U = has_up ? *reinterpret_cast<const uint4*>(s + rowu + c0) : zero4;
-        const uint4 D = has_dn ? *reinterpret_cast<const uint4*>(s + rowd + c0) : zero4;
-        const int s_prev = has_prev ? (int)s[row + cprev] : 0;
-        const int s_next = (c0 + 16 < p.cols) ? (int)s[row + c0 + 16] : 0;
-        const int s_first = p.periodic ? (int)s[row] : 0;
-        const u32x4 w = tsu_philox((uint32_t)q, (uint32_t)r, p.hs, TSU_TAG_ISING_HI, k0, k1);
-        const uint32_t wv[4] = {w.x, w.y, w.z, w.w};
-        bool have_lo = false;
-        uint32_t lv[4] = {0, 0, 0, 0};
-        uint32_t out[4] = {C.x, C.y, C.z, C.w};
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int i = 2 * m + PAR, c = c0 + i;
-            if (c >= p.cols) break;
-            const bool has_left = i > 0 || has_prev, has_right = c + 1 < p.cols || p.periodic;
-            const int su = sbyte(U, i), sd = sbyte(D, i);
-            const int sl = i > 0 ? sbyte(C, i - 1) : s_prev;
-            const int sr = c + 1 < p.cols ? (i < 15 ? sbyte(C, i + 1) : s_next) : s_first;
-            const float f32 = (((Ju[m] * (float)su + Jd[m] * (float)sd) + Jl[m] * (float)sl) + Jr[m] * (float)sr) + hf[m];
-            const uint32_t hi = ((wv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu) ^ 0x8000u;
-            int dec = screen(f32, a32[m], c32, hi);
-            if (dec == 0) {
-                // the contract's sum: neighbours in the order up, down, left, right, a missing one skipped, then h
-                double f = 0.0;
-                bool any = false;
-                if (has_up) { f = (double)Ju[m] * su; any = true; }
-                if (has_dn) { f = any ? f + (double)Jd[m] * sd : (double)Jd[m] * sd; any = true; }
-                if (has_left) { f = any ? f + (double)Jl[m] * sl : (double)Jl[m] * sl; any = true; }
-                if (has_right) { f = any ? f + (double)Jr[m] * sr : (double)Jr[m] * sr; any = true; }
-                f = any ? f + (double)hf[m] : (double)hf[m];
-                const uint64_t thr = exact_thr(f, T);
-                const uint32_t thi = (uint32_t)(thr >> 16);
-                bool accept = hi < thi;
-                if (hi == thi) {  // tie on the top 16 bits: the low half, as K1 draws it
-                    if (!have_lo) {
-                        const u32x4 l = tsu_philox((uint32_t)q, (uint32_t)r, p.hs, TSU_TAG_ISING_LO, k0, k1);
-                        lv[0] = l.x; lv[1] = l.y; lv[2] = l.z; lv[3] = l.w;
-                        have_lo = true;
-                    }
-                    const uint32_t lo = (lv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu;
-                    accept = (((uint64_t)hi << 16) | lo) < thr;
-                }
-                dec = accept ? 1 : -1;
-            }
-            const uint32_t b = dec > 0 ? 0x01u : 0xFFu;
-            const int sh = 8 * (i & 3);
-            out[i >> 2] = (out[i >> 2] & ~(0xFFu << sh)) | (b << sh);
-        }
-        *reinterpret_cast<uint4*>(s + row + c0) = make_uint4(out[0], out[1], out[2], out[3]);
-    }
-}
-
 // grid (ceil(nchunks / 64), ceil(rows / 4), ceil(nw / W)), 64 x 4 lanes: lane = octet q of row r for the walkers of group z
 __global__ __launch_bounds__(256) void k7_pt_sweep(PTParams p, int colour) {
-    const int q = blockIdx.x * 64 + threadIdx.x;
-    const int r = blockIdx.y * 4 + threadIdx.y;
-    if (r >= p.rows || 16 * q >= p.cols) return;
-    const int g0 = blockIdx.z * p.W, g1 = min(g0 + p.W, p.nw);
-    if (((r + colour) & 1) == 0) k7_pt_octet<0>(p, r, q, g0, g1);
-    else k7_pt_octet<1>(p, r, q, g0, g1);
-}
-
-// The ensemble's sample index: grid z of the sweep = sample * groups + walker group, walkers [base + group W, ..) clipped to the
-// sample's own [base, base + nper), base = sample * nper; the sample's disorder sits dstride floats after its predecessor's
-struct PTEns {
-    long long dstride;  // floats of a sample's disorder (3 planes)
-    int nper;           // walkers of a sample (nl * R)
-    int groups;         // walker groups of a sample: ceil(nper / W)
-};
-
-__device__ __forceinline__ void pte_sample(PTParams& p, const PTEns& e, int sample) {
-    const long long off = (long long)sample * e.dstride;
-    p.jr += off;
-    p.jd += off;
-    p.h += off;
+    int r, q;
+    if (!k7_lane(p.g, r, q)) return;
+    const int g0 = blockIdx.z * p.W;
+    octet_group<2>(p, 0, r, q, g0, min(g0 + p.W, p.nw), colour);
 }
 
 // k7_pt_sweep for an ensemble, a kernel of its own so that the ladders' code object stays what it was: the same lane and the same
 // octet, for the walkers of one group of one sample on that sample's disorder.  The sample and its offsets are wave-uniform.
 __global__ __launch_bounds__(256) void k7_pte_sweep(PTParams p, PTEns e, int colour) {
-    const int q = blockIdx.x * 64 + threadIdx.x;
-    const int r = blockIdx.y * 4 + threadIdx.y;
-    if (r >= p.rows || 16 * q >= p.cols) return;
-    const int sample = blockIdx.z / e.groups, group = blockIdx.z - sample * e.groups;
-    const int base = sample * e.nper;
-    const int g0 = base + group * p.W, g1 = min(g0 + p.W, base + e.nper);
-    pte_sample(p, e, sample);
-    if (((r + colour) & 1) == 0) k7_pt_octet<0>(p, r, q, g0, g1);
-    else k7_pt_octet<1>(p, r, q, g0, g1);
-}
-
-__device__ __forceinline__ K7Params pt_walker_params(const PTParams& pp, int g) {
-    K7Params p;
-    p.s = pp.s[g];
-    p.jr = pp.jr;
-    p.jd = pp.jd;
-    p.h = pp.h;
-    p.pitch = pp.pitch;
-    p.rows = pp.rows;
-    p.cols = pp.cols;
-    p.periodic = pp.periodic;
-    p.c32 = 0.0f;
-    p.T = 0.0;
-    p.k0 = p.k1 = p.hs = p.tag_hi = p.tag_lo = 0;
-    return p;
+    int r, q, g0, g1;
+    if (!k7_lane(p.g, r, q)) return;
+    pte_group(p, e, g0, g1);
+    octet_group<2>(p, 0, r, q, g0, g1, colour);
 }
 
 // grid (blocks_for(lattice), nw): workgroup x of walker y computes k7_energy's partial x of that walker alone, and its sum of spins
-__global__ __launch_bounds__(256) void k7_pt_energy(PTParams pp, double* __restrict__ part, long long* __restrict__ ipart) {
+__global__ __launch_bounds__(256) void k7_pt_energy(PTParams p, double* __restrict__ part, long long* __restrict__ ipart) {
     long long m;
-    const double e = block_sum(k7_energy_lane(pt_walker_params(pp, blockIdx.y), m));
-    const long long ms = block_isum(m);
-    if (threadIdx.x == 0) {
-        part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
-        ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
-    }
+    const double e = energy_lane<2>(p.g, p.s[blockIdx.y], m);
+    pt_energy_partials(e, m, part, ipart);
 }
 
 // k7_pt_energy for an ensemble: walker y on the disorder of its sample y / nper
-__global__ __launch_bounds__(256) void k7_pte_energy(PTParams pp, PTEns en, double* __restrict__ part, long long* __restrict__ ipart) {
-    pte_sample(pp, en, blockIdx.y / en.nper);
+__global__ __launch_bounds__(256) void k7_pte_energy(PTParams p, PTEns en, double* __restrict__ part, long long* __restrict__ ipart) {
+    pte_sample(p.g, en, blockIdx.y / en.nper);
     long long m;
-    const double e = block_sum(k7_energy_lane(pt_walker_params(pp, blockIdx.y), m));
-    const long long ms = block_isum(m);
-    if (threadIdx.x == 0) {
-        part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
-        ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
-    }
+    const double e = energy_lane<2>(p.g, p.s[blockIdx.y], m);
+    pt_energy_partials(e, m, part, ipart);
 }
 
 bool whole_lattice(const tsu_ising2d* L) { return L->ghost == 0 && L->row0 == 0 && L->total_rows == L->rows; }
 
-K7Params make_params(const tsu_ising2d* L) {
-    K7Params p;
+// the lattice's shape on the three disorder planes that start at `dis` (its own, or a sample's of an ensemble)
+Geo make_geo(const tsu_ising2d* L, const float* dis) {
     const size_t plane = (size_t)L->rows * L->pitch;
-    p.s = L->alloc[L->cur];
-    p.jr = L->d_dis;
-    p.jd = L->d_dis ? L->d_dis + plane : nullptr;
-    p.h = L->d_dis ? L->d_dis + 2 * plane : nullptr;
-    p.pitch = (long long)L->pitch;
-    p.rows = L->rows;
-    p.cols = L->cols;
-    p.periodic = L->periodic;
-    p.c32 = 0.0f;
-    p.T = 0.0;
-    p.k0 = p.k1 = p.hs = p.tag_hi = p.tag_lo = 0;
+    Geo g = {};
+    g.jr = dis;
+    g.jd = dis ? dis + plane : nullptr;
+    g.h = dis ? dis + 2 * plane : nullptr;
+    g.pitch = (long long)L->pitch;
+    g.depth = 1;
+    g.rows = L->rows;
+    g.cols = L->cols;
+    g.pr = g.pc = L->periodic;
+    return g;
+}
+
+K7Params make_params(const tsu_ising2d* L) {
+    K7Params p = {};
+    p.g = make_geo(L, L->d_dis);
+    p.w.s = L->alloc[L->cur];
     return p;
 }
 
+// the shape a ladder, an ensemble or a population keeps of its lattices
+template <class H>
+void set_shape(H* P, const tsu_ising2d* L) {
+    P->nrows = L->rows;
+    P->pitch = (long long)L->pitch;
+    P->cols = L->cols;
+    P->n_axes = 2;
+    P->lrows = L->rows;
+    P->axis_len[0] = L->rows;
+    P->axis_len[1] = L->cols;
+    P->axis_per[0] = P->axis_per[1] = L->periodic;
+}
+
 unsigned blocks_for(const tsu_ising2d* L) { return reduce_blocks((long long)L->rows * ((L->cols + 15) / 16)); }
+
+// grid of the sweeps: k7_lane's, with `groups` walker groups (or samples x groups) as its z dimension
+dim3 sweep_grid(const Geo& g, unsigned groups) {
+    const int nchunks = (g.cols + 15) >> 4;
+    return dim3((unsigned)((nchunks + 63) / 64), (unsigned)((g.rows + 3) / 4), groups);
+}
 
 void pt_free(tsu_pt2d* P) {
     pt2d_icm_free(P);
     pt_delete(P, tsu_ising2d_destroy);
 }
 
-PTParams pt_params(const tsu_pt2d* P) {
-    const tsu_ising2d* L = P->lat[0];
-    const size_t plane = (size_t)L->rows * L->pitch;
-    PTParams p;
-    p.s = P->d_s;
-    p.key = P->d_key;
-    p.slot = P->d_slot;
-    p.T = P->d_T;
-    p.c32 = P->d_c32;
-    p.jr = L->d_dis;
-    p.jd = L->d_dis ? L->d_dis + plane : nullptr;
-    p.h = L->d_dis ? L->d_dis + 2 * plane : nullptr;
-    p.pitch = (long long)L->pitch;
-    p.rows = L->rows;
-    p.cols = L->cols;
-    p.periodic = L->periodic;
-    p.nw = P->nw;
-    p.W = 1;
-    p.hs = 0;
-    return p;
-}
+PTParams pt_params(const tsu_pt2d* P) { return ladder_params(P, make_geo(P->lat[0], P->lat[0]->d_dis), P->nw, 1); }
 
-// k7_pt_energy into d_part / d_ipart (asynchronous): the partial pass pt_host.h's energies take
-auto pt_partials(tsu_pt2d* P, const PTParams& p) {
-    return [P, &p](unsigned blocks) { k7_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
+// k7_pt_energy for nw walkers into d_part / d_ipart (asynchronous): the partial pass pt_host.h's and pop_host.h's energies take
+template <class H>
+auto pt_partials(H* P, int nw, const PTParams& p) {
+    return [P, nw, &p](unsigned blocks) { k7_pt_energy<<<dim3(blocks, (unsigned)nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
 }
 
 void pte_free(tsu_pte2d* P) { pte_delete(P, tsu_ising2d_destroy); }
 
 // the ladders' parameters for an ensemble: sample 0's disorder (the kernels add the sample's offset), the walkers of all samples
-PTParams pte_params(const tsu_pte2d* P) {
-    PTParams p;
-    p.s = P->d_s;
-    p.key = P->d_key;
-    p.slot = P->d_slot;
-    p.T = P->d_T;
-    p.c32 = P->d_c32;
-    p.jr = P->d_dis;
-    p.jd = P->d_dis + P->plane;
-    p.h = P->d_dis + 2 * P->plane;
-    p.pitch = P->pitch;
-    p.rows = P->lat->rows;
-    p.cols = P->lat->cols;
-    p.periodic = P->lat->periodic;
-    p.nw = P->nw;
-    p.W = 1;
-    p.hs = 0;
-    return p;
-}
-
-PTEns pte_ens(const tsu_pte2d* P, int W) {
-    PTEns e;
-    e.dstride = 3 * (long long)P->plane;
-    e.nper = P->nl * P->R;
-    e.groups = (int)pte_groups(P, W);
-    return e;
-}
+PTParams pte_params(const tsu_pte2d* P) { return ladder_params(P, make_geo(P->lat, P->d_dis), P->nw, 1); }
 
 // k7_pte_energy into d_part / d_ipart (asynchronous)
 auto pte_partials(tsu_pte2d* P, const PTParams& p, const PTEns& e) {
@@ -496,42 +212,17 @@ auto pte_partials(tsu_pte2d* P, const PTParams& p, const PTEns& e) {
 void pa_free(tsu_pa2d* P) { pop_delete(P, tsu_ising2d_destroy); }
 
 // the ladders' parameters for a population: walker -> plane, key and slot 0; T / c32 are set per step
-PTParams pa_params(const tsu_pa2d* P) {
-    const tsu_ising2d* L = P->lat;
-    const size_t plane = (size_t)L->rows * L->pitch;
-    PTParams p;
-    p.s = P->d_s;
-    p.key = P->d_key;
-    p.slot = P->d_slot;
-    p.T = P->d_T;
-    p.c32 = P->d_c32;
-    p.jr = L->d_dis;
-    p.jd = L->d_dis ? L->d_dis + plane : nullptr;
-    p.h = L->d_dis ? L->d_dis + 2 * plane : nullptr;
-    p.pitch = (long long)L->pitch;
-    p.rows = L->rows;
-    p.cols = L->cols;
-    p.periodic = L->periodic;
-    p.nw = P->R;
-    p.W = pop_group(P);
-    p.hs = 0;
-    return p;
-}
+PTParams pa_params(const tsu_pa2d* P) { return ladder_params(P, make_geo(P->lat, P->lat->d_dis), P->R, pop_group(P)); }
 
-// half-sweep hs of every walker at step k's temperature / the energy partial pass: what pop_host.h's init and run take
+// half-sweep hs of every walker at step k's temperature: what pop_host.h's init and run take
 auto pa_sweep(tsu_pa2d* P, PTParams& p) {
-    const int nchunks = (P->lat->cols + 15) >> 4;
-    const dim3 grid((unsigned)((nchunks + 63) / 64), (unsigned)((P->lat->rows + 3) / 4), (unsigned)((P->R + p.W - 1) / p.W));
+    const dim3 grid = sweep_grid(p.g, (unsigned)((P->R + p.W - 1) / p.W));
     return [P, &p, grid](uint32_t hs, int colour, int k) {
         p.hs = hs;
         p.T = P->d_T + k;
         p.c32 = P->d_c32 + k;
         k7_pt_sweep<<<grid, dim3(64, 4, 1), 0, P->ctx->stream>>>(p, colour);
     };
-}
-
-auto pa_partials(tsu_pa2d* P, const PTParams& p) {
-    return [P, &p](unsigned blocks) { k7_pt_energy<<<dim3(blocks, (unsigned)P->R, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
 }
 
 }  // namespace
@@ -588,11 +279,10 @@ int tsu_ising2d_disorder_sweep(tsu_ising2d* L, double T, int n_sweeps, uint64_t 
     if (n_sweeps == 0) return TSU_OK;
     if (L->timing) TSU_HIP_TRY(ctx, hipEventRecord(L->ev0, ctx->stream));
     K7Params p = make_params(L);
-    ising2d_set_keys(p, seed, replica);
-    p.T = T;
-    p.c32 = (float)(2.0 / T);
-    const int nchunks = (L->cols + 15) >> 4;
-    const dim3 grid((unsigned)((nchunks + 63) / 64), (unsigned)((L->rows + 3) / 4), 1);
+    ising2d_set_keys(p.w, seed, replica);
+    p.w.T = T;
+    p.w.c32 = (float)(2.0 / T);
+    const dim3 grid = sweep_grid(p.g, 1);
     for (int s = 0; s < n_sweeps; ++s)
         for (int colour = 0; colour < 2; ++colour) {
             p.hs = 2u * (sweep0 + (uint32_t)s) + (uint32_t)colour;
@@ -711,14 +401,7 @@ int tsu_pt2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int n_temps,
         ctx, "pt2d", n_temps, n_ladders, out,
         [=](tsu_ising2d** L) { return tsu_ising2d_create(ctx, rows, cols, periodic, L); },  // every whole lattice K7 takes
         [](tsu_pt2d* P, int8_t** planes) {
-            P->nrows = P->lat[0]->rows;
-            P->pitch = (long long)P->lat[0]->pitch;
-            P->cols = P->lat[0]->cols;
-            P->n_axes = 2;
-            P->lrows = P->lat[0]->rows;
-            P->axis_len[0] = P->lat[0]->rows;
-            P->axis_len[1] = P->lat[0]->cols;
-            P->axis_per[0] = P->axis_per[1] = P->lat[0]->periodic;
+            set_shape(P, P->lat[0]);
             for (int g = 0; g < P->nw; ++g) planes[g] = P->lat[g]->alloc[P->lat[g]->cur];
         },
         pt_free);
@@ -766,15 +449,14 @@ int tsu_pt2d_run(tsu_pt2d* P, int n_rounds, int swap_interval, int do_swap, int 
     TSU_REQUIRE(ctx, (uint64_t)P->icm_passes + (uint64_t)n_rounds <= 0xFFFFFFFFull, "pt2d_run: cluster-pass counter overflow");
     PTParams p = pt_params(P);
     p.W = pt_group(P);
-    const int nchunks = (L->cols + 15) >> 4;
-    const dim3 grid((unsigned)((nchunks + 63) / 64), (unsigned)((L->rows + 3) / 4), (unsigned)((P->nw + p.W - 1) / p.W));
+    const dim3 grid = sweep_grid(p.g, (unsigned)((P->nw + p.W - 1) / p.W));
     return pt_run(
         P, n_rounds, swap_interval, do_swap, record,
         [&](uint32_t hs, int colour) {
             p.hs = hs;
             k7_pt_sweep<<<grid, dim3(64, 4, 1), 0, ctx->stream>>>(p, colour);
         },
-        pt_partials(P, p),
+        pt_partials(P, P->nw, p),
         [P] {  // replica cluster moves
             return P->icm_every >= 1 && P->rounds % (uint32_t)P->icm_every == 0 ? pt2d_icm_enqueue(P) : (int)TSU_OK;
         });
@@ -795,7 +477,7 @@ int tsu_pt2d_energies(tsu_pt2d* P, double* E, int64_t* sum_s) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
     const PTParams p = pt_params(P);
-    return pt_energies(P, P->lat[0]->have_disorder, E, sum_s, pt_partials(P, p));
+    return pt_energies(P, P->lat[0]->have_disorder, E, sum_s, pt_partials(P, P->nw, p));
 }
 
 int tsu_pt2d_get_spins(tsu_pt2d* P, int ladder, int slot, int8_t* host) {
@@ -861,14 +543,7 @@ int tsu_pte2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int n_sampl
         [=](tsu_pte2d* P) {  // every whole lattice K7 takes
             const int rc = tsu_ising2d_create(ctx, rows, cols, periodic, &P->lat);
             if (rc != TSU_OK) return rc;
-            P->nrows = P->lat->rows;
-            P->pitch = (long long)P->lat->pitch;
-            P->cols = P->lat->cols;
-            P->n_axes = 2;
-            P->lrows = P->lat->rows;
-            P->axis_len[0] = P->lat->rows;
-            P->axis_len[1] = P->lat->cols;
-            P->axis_per[0] = P->axis_per[1] = P->lat->periodic;
+            set_shape(P, P->lat);
             P->n_dis = 3;
             return (int)TSU_OK;
         },
@@ -911,8 +586,7 @@ int tsu_pte2d_run(tsu_pte2d* P, int n_rounds, int swap_interval, int do_swap, in
     PTParams p = pte_params(P);
     p.W = pt_group(P);
     const PTEns e = pte_ens(P, p.W);
-    const int nchunks = (p.cols + 15) >> 4;
-    const dim3 grid((unsigned)((nchunks + 63) / 64), (unsigned)((p.rows + 3) / 4), (unsigned)P->S * (unsigned)e.groups);
+    const dim3 grid = sweep_grid(p.g, (unsigned)P->S * (unsigned)e.groups);
     return pt_run(
         P, n_rounds, swap_interval, do_swap, record,
         [&](uint32_t hs, int colour) {
@@ -996,14 +670,7 @@ int tsu_pa2d_create(tsu_ctx* ctx, int rows, int cols, int periodic, int populati
         [=](tsu_pa2d* P) {  // every whole lattice K7 takes
             const int rc = tsu_ising2d_create(ctx, rows, cols, periodic, &P->lat);
             if (rc != TSU_OK) return rc;
-            P->nrows = P->lat->rows;
-            P->pitch = (long long)P->lat->pitch;
-            P->cols = P->lat->cols;
-            P->n_axes = 2;
-            P->lrows = P->lat->rows;
-            P->axis_len[0] = P->lat->rows;
-            P->axis_len[1] = P->lat->cols;
-            P->axis_per[0] = P->axis_per[1] = P->lat->periodic;
+            set_shape(P, P->lat);
             return (int)TSU_OK;
         },
         pa_free);
@@ -1033,7 +700,7 @@ int tsu_pa2d_init(tsu_pa2d* P, uint64_t seed, int initial_sweeps) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
     PTParams p = pa_params(P);
-    return pop_init(P, P->lat->have_disorder, seed, initial_sweeps, pa_sweep(P, p), pa_partials(P, p));
+    return pop_init(P, P->lat->have_disorder, seed, initial_sweeps, pa_sweep(P, p), pt_partials(P, P->R, p));
 }
 
 int tsu_pa2d_run(tsu_pa2d* P, int n_steps, int sweeps_per_step, int resample, int record) {
@@ -1042,7 +709,7 @@ int tsu_pa2d_run(tsu_pa2d* P, int n_steps, int sweeps_per_step, int resample, in
     const int rc = pop_run_check(P, P->lat->have_disorder, n_steps, sweeps_per_step);
     if (rc != TSU_OK) return rc;
     PTParams p = pa_params(P);
-    return pop_run(P, n_steps, sweeps_per_step, resample, record, pa_sweep(P, p), pa_partials(P, p));
+    return pop_run(P, n_steps, sweeps_per_step, resample, record, pa_sweep(P, p), pt_partials(P, P->R, p));
 }
 
 int tsu_pa2d_history(tsu_pa2d* P, double* E, int64_t* M, uint32_t* W, int32_t* parent, uint64_t* S, uint64_t* U, double* E_min) {
@@ -1054,7 +721,7 @@ int tsu_pa2d_energies(tsu_pa2d* P, double* E, int64_t* sum_s) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
     const PTParams p = pa_params(P);
-    return pop_energies(P, P->lat->have_disorder, E, sum_s, pa_partials(P, p));
+    return pop_energies(P, P->lat->have_disorder, E, sum_s, pt_partials(P, P->R, p));
 }
 
 int tsu_pa2d_get_spins(tsu_pa2d* P, int i, int8_t* host) {

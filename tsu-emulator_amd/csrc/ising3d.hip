@@ -23,8 +23,8 @@
 // parities are then taken one after the other; the result does not depend on it).  With C >= 1024 this is K7's shape: one row
 // per wave.  The lane loads 16 bytes of its own row, of rows r -+ 1 of the layer and of the same row of layers z -+ 1, 16 floats
 // of J_right, J_down, J_layer and h at the site and of J_down[r-1] and J_layer[z-1]; it screens its 8 sites in fp32 and takes
-// the float64 threshold (and the lo16 block) only where the screen cannot decide (disorder_dev.h: the bound for seven terms);
-// one 16-byte store, the other colour's and the pad bytes written back as read.
+// the float64 threshold (and the lo16 block) only where the screen cannot decide (disorder_dev.h: the bound for seven terms, and the
+// octet itself, Octet, shared with K7); one 16-byte store, the other colour's and the pad bytes written back as read.
 //
 // Bytes: a half-sweep reads every byte of the four arrays (16 B per site: a line holds both colours; J_down[r-1] and
 // J_layer[z-1] are the own rows of other lanes of the launch and come from L2) and the spins (1 B per site from HBM, the four
@@ -37,9 +37,9 @@
 //
 // Parallel tempering (tsu_pt3d_*): ladders of R walkers on ONE disorder ("Parallel tempering in 3-D (K8)").
 // k8_pt_sweep is k8_sweep for a group of W walkers per lane (the walker group is the grid's z dimension): the octet's six
-// couplings, field and screen bound are staged once and every walker of the group takes k8_octet's decision at the temperature
-// of its slot, so the 32 B per site of disorder a sweep reads are shared by W walkers.  k8_pt_energy runs k8_energy's
-// decomposition per walker through the same device helper (the bits of tsu_ising3d_energy) and sums the spins alongside.  The
+// couplings, field and screen bound are staged once (octet_group, disorder_dev.h) and every walker of the group takes k8_sweep's
+// decision at the temperature of its slot, so the 32 B per site of disorder a sweep reads are shared by W walkers.  k8_pt_energy runs k8_energy's
+// decomposition per walker through the same device helper (energy_lane: the bits of tsu_ising3d_energy) and sums the spins alongside.  The
 // rest of a ladder does not know the dimension and is the 2-D ladders': the handle's tables and the host side of every entry point
 // (pt_host.h), the final sums and q per slot (pt_energy_final, pt_overlap, reduce_dev.h) and the swap pass (pt_dev.h).  This file
 // passes in how a half-sweep and an energy partial pass are launched.  No host value changes between rounds: a run of many rounds
@@ -79,115 +79,15 @@ struct tsu_pte3d : pte_handle {
 namespace {
 
 struct K8Params {
-    int8_t* s;
-    const float* jr;     // J_right, J_down, J_layer, h
-    const float* jd;
-    const float* jl;
-    const float* h;
-    long long pitch;
-    long long nrows;     // depth * rows
-    int depth, rows, cols;
-    int pz, pr, pc;
-    int lshift;          // log2 of the lanes per row
-    float c32;           // fl32(2 / T): the screen's scale
-    double T;
-    uint32_t k0, k1, hs, tag_hi, tag_lo;
+    Geo g;            // J_right, J_down, J_layer, h
+    Walker w;         // the spins, T, keys and tags
+    uint32_t hs;
+    long long nrows;  // depth * rows
+    int lshift;       // log2 of the lanes per row
 };
 
-__device__ __forceinline__ void zero16f(float4* a) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) a[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
-// one octet of the colour whose sites sit at chunk positions PAR, PAR + 2, ..
-template <int PAR>
-__device__ __forceinline__ void k8_octet(const K8Params& p, int z, int r, int q) {
-    const long long rho = (long long)z * p.rows + r;
-    const long long row = rho * p.pitch;
-    const int c0 = 16 * q;
-    const bool has_bk = z > 0 || p.pz, has_fw = z + 1 < p.depth || p.pz;
-    const bool has_up = r > 0 || p.pr, has_dn = r + 1 < p.rows || p.pr;
-    const long long rowb = ((long long)(z > 0 ? z - 1 : p.depth - 1) * p.rows + r) * p.pitch;
-    const long long rowf = ((long long)(z + 1 < p.depth ? z + 1 : 0) * p.rows + r) * p.pitch;
-    const long long rowu = ((long long)z * p.rows + (r > 0 ? r - 1 : p.rows - 1)) * p.pitch;
-    const long long rowd = ((long long)z * p.rows + (r + 1 < p.rows ? r + 1 : 0)) * p.pitch;
-    const uint4 zero4 = make_uint4(0, 0, 0, 0);
-    const uint4 C = *reinterpret_cast<const uint4*>(p.s + row + c0);
-    const uint4 B = has_bk ? *reinterpret_cast<const uint4*>(p.s + rowb + c0) : zero4;
-    const uint4 F = has_fw ? *reinterpret_cast<const uint4*>(p.s + rowf + c0) : zero4;
-    const uint4 U = has_up ? *reinterpret_cast<const uint4*>(p.s + rowu + c0) : zero4;
-    const uint4 D = has_dn ? *reinterpret_cast<const uint4*>(p.s + rowd + c0) : zero4;
-    float4 jr[4], jd[4], jl[4], ju[4], jb[4], hh[4];
-    load16f(p.jr + row + c0, jr);
-    load16f(p.jd + row + c0, jd);
-    load16f(p.jl + row + c0, jl);
-    load16f(p.h + row + c0, hh);
-    if (has_up) load16f(p.jd + rowu + c0, ju);
-    else zero16f(ju);
-    if (has_bk) load16f(p.jl + rowb + c0, jb);
-    else zero16f(jb);
-    // column c0 - 1 (left of position 0), column c0 + 16 (right of position 15), column 0 (right of the last column, periodic)
-    const bool has_prev = q > 0 || p.pc;
-    const int cprev = q > 0 ? c0 - 1 : p.cols - 1;
-    const int s_prev = has_prev ? (int)p.s[row + cprev] : 0;
-    const float j_prev = has_prev ? p.jr[row + cprev] : 0.0f;
-    const int s_next = (c0 + 16 < p.cols) ? (int)p.s[row + c0 + 16] : 0;
-    const int s_first = p.pc ? (int)p.s[row] : 0;
-
-    const u32x4 w = tsu_philox((uint32_t)q, (uint32_t)rho, p.hs, p.tag_hi, p.k0, p.k1);
-    const uint32_t wv[4] = {w.x, w.y, w.z, w.w};
-    bool have_lo = false;
-    uint32_t lv[4] = {0, 0, 0, 0};
-    uint32_t out[4] = {C.x, C.y, C.z, C.w};
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-        const int i = 2 * m + PAR, c = c0 + i;
-        if (c >= p.cols) break;
-        const bool has_left = i > 0 || has_prev, has_right = c + 1 < p.cols || p.pc;
-        const int sb = sbyte(B, i), sf = sbyte(F, i), su = sbyte(U, i), sd = sbyte(D, i);
-        const int sl = i > 0 ? sbyte(C, i - 1) : s_prev;
-        const int sr = c + 1 < p.cols ? (i < 15 ? sbyte(C, i + 1) : s_next) : s_first;
-        const float Jb = has_bk ? fat(jb, i) : 0.0f, Jf = has_fw ? fat(jl, i) : 0.0f;
-        const float Ju = has_up ? fat(ju, i) : 0.0f, Jd = has_dn ? fat(jd, i) : 0.0f;
-        const float Jl = has_left ? (i > 0 ? fat(jr, i - 1) : j_prev) : 0.0f;
-        const float Jr = has_right ? fat(jr, i) : 0.0f;
-        const float hf = fat(hh, i);
-        // missing neighbours carry J = 0 here: exact in fp32, and the screen only needs a bound (six additions, seven terms)
-        const float f32 = (((((Jb * (float)sb + Jf * (float)sf) + Ju * (float)su) + Jd * (float)sd) + Jl * (float)sl) + Jr * (float)sr) + hf;
-        const float a32 = fabsf(Jb) + fabsf(Jf) + fabsf(Ju) + fabsf(Jd) + fabsf(Jl) + fabsf(Jr) + fabsf(hf);
-        const uint32_t hi = ((wv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu) ^ 0x8000u;
-        int dec = screen(f32, a32, p.c32, hi);
-        if (dec == 0) {
-            // the contract's sum: neighbours in the order z-1, z+1, r-1, r+1, c-1, c+1, a missing one skipped, then h
-            double f = 0.0;
-            bool any = false;
-            if (has_bk) { f = (double)Jb * sb; any = true; }
-            if (has_fw) { f = any ? f + (double)Jf * sf : (double)Jf * sf; any = true; }
-            if (has_up) { f = any ? f + (double)Ju * su : (double)Ju * su; any = true; }
-            if (has_dn) { f = any ? f + (double)Jd * sd : (double)Jd * sd; any = true; }
-            if (has_left) { f = any ? f + (double)Jl * sl : (double)Jl * sl; any = true; }
-            if (has_right) { f = any ? f + (double)Jr * sr : (double)Jr * sr; any = true; }
-            f = any ? f + (double)hf : (double)hf;
-            const uint64_t thr = exact_thr(f, p.T);
-            const uint32_t thi = (uint32_t)(thr >> 16);
-            bool accept = hi < thi;
-            if (hi == thi) {  // tie on the top 16 bits: the low half, as K1 draws it
-                if (!have_lo) {
-                    const u32x4 l = tsu_philox((uint32_t)q, (uint32_t)rho, p.hs, p.tag_lo, p.k0, p.k1);
-                    lv[0] = l.x; lv[1] = l.y; lv[2] = l.z; lv[3] = l.w;
-                    have_lo = true;
-                }
-                const uint32_t lo = (lv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu;
-                accept = (((uint64_t)hi << 16) | lo) < thr;
-            }
-            dec = accept ? 1 : -1;
-        }
-        const uint32_t b = dec > 0 ? 0x01u : 0xFFu;
-        const int sh = 8 * (i & 3);
-        out[i >> 2] = (out[i >> 2] & ~(0xFFu << sh)) | (b << sh);
-    }
-    *reinterpret_cast<uint4*>(p.s + row + c0) = make_uint4(out[0], out[1], out[2], out[3]);
-}
+// The octet (Octet: loads, screen, exact branch, lo16 draw, store), the energy lane, Geo / Walker / PTParams / PTEns live in
+// disorder_dev.h, the workgroup sums, the final sums, the pair lane and kEnergyBlocks in reduce_dev.h: all shared with K7
 
 // (row rho, octet q) of a lane: grid (ceil(nrows / (256 >> lshift)), ceil(nchunks / 64)), 256 lanes.  Local row slot j of the
 // workgroup's 256 >> lshift rows: the first half of the slots take the even local rows, the second half the odd ones.
@@ -199,16 +99,23 @@ __device__ __forceinline__ bool k8_lane(const P& p, long long& rho, int& q) {
     const int local = j < half ? 2 * j : 2 * (j - half) + 1;
     q = blockIdx.y * 64 + (t & ((1 << p.lshift) - 1));
     rho = (long long)blockIdx.x * rpb + local;
-    return rho < p.nrows && 16 * q < p.cols;
+    return rho < p.nrows && 16 * q < p.g.cols;
+}
+
+// the same lane as (layer z, row r, octet q): what the sweeps take
+template <class P>
+__device__ __forceinline__ bool k8_lane(const P& p, int& z, int& r, int& q) {
+    long long rho;
+    if (!k8_lane(p, rho, q)) return false;
+    z = (int)(rho / p.g.rows);
+    r = (int)(rho - (long long)z * p.g.rows);
+    return true;
 }
 
 __global__ __launch_bounds__(256) void k8_sweep(K8Params p, int colour) {
-    long long rho;
-    int q;
-    if (!k8_lane(p, rho, q)) return;
-    const int z = (int)(rho / p.rows), r = (int)(rho - (long long)z * p.rows);
-    if (((z + r + colour) & 1) == 0) k8_octet<0>(p, z, r, q);
-    else k8_octet<1>(p, z, r, q);
+    int z, r, q;
+    if (!k8_lane(p, z, r, q)) return;
+    octet_single<3>(p.g, p.w, p.hs, z, r, q, colour);
 }
 
 // i.i.d. +-1: the bits of tsu_ising2d_randomize for a (depth * rows) x cols lattice (global row rho); pad bytes 0
@@ -216,7 +123,7 @@ __global__ __launch_bounds__(256) void k8_randomize(K8Params p, uint32_t tag) {
     long long rho;
     int q;
     if (!k8_lane(p, rho, q)) return;
-    const u32x4 w = tsu_philox((uint32_t)(q >> 3), (uint32_t)rho, 0u, tag, p.k0, p.k1);
+    const u32x4 w = tsu_philox((uint32_t)(q >> 3), (uint32_t)rho, 0u, tag, p.w.k0, p.w.k1);
     const uint32_t wv[4] = {w.x, w.y, w.z, w.w};
     const uint32_t bits = (wv[(q & 7) >> 1] >> (16 * (q & 1))) & 0xFFFFu;
     uint32_t o[4];
@@ -227,12 +134,12 @@ __global__ __launch_bounds__(256) void k8_randomize(K8Params p, uint32_t tag) {
         for (int b = 0; b < 4; ++b) {
             const int i = 4 * k + b;
             uint32_t byte = ((bits >> i) & 1u) ? 0x01u : 0xFFu;
-            if (16 * q + i >= p.cols) byte = 0;
+            if (16 * q + i >= p.g.cols) byte = 0;
             v |= byte << (8 * b);
         }
         o[k] = v;
     }
-    *reinterpret_cast<uint4*>(p.s + rho * p.pitch + 16 * q) = make_uint4(o[0], o[1], o[2], o[3]);
+    *reinterpret_cast<uint4*>(p.w.s + rho * p.g.pitch + 16 * q) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
 __global__ __launch_bounds__(256) void k8_fill(K8Params p, int value) {
@@ -245,50 +152,18 @@ __global__ __launch_bounds__(256) void k8_fill(K8Params p, int value) {
         uint32_t v = 0;
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            const uint32_t byte = (16 * q + 4 * k + b < p.cols) ? (uint32_t)(uint8_t)value : 0u;
+            const uint32_t byte = (16 * q + 4 * k + b < p.g.cols) ? (uint32_t)(uint8_t)value : 0u;
             v |= byte << (8 * b);
         }
         o[k] = v;
     }
-    *reinterpret_cast<uint4*>(p.s + rho * p.pitch + 16 * q) = make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-// E partial of a lane: lane = chunk (rho, q), grid-stride over blockIdx.x in a fixed order; a site adds
-// s (((h + J_right s_right) + J_down s_down) + J_layer s_layer), a bond missing on an open axis skipped; ssum = the lane's sum
-// of spins.  Shared by the single-lattice and the ladder kernels: the lane order is part of the contract.
-__device__ __forceinline__ double k8_energy_lane(const K8Params& p, long long& ssum) {
-    const int nchunks = (p.cols + 15) >> 4;
-    const long long total = p.nrows * nchunks;
-    double e = 0.0;
-    long long m = 0;
-    for (long long t = (long long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long long)gridDim.x * 256) {
-        const long long rho = t / nchunks;
-        const int q = (int)(t - rho * nchunks);
-        const int z = (int)(rho / p.rows), r = (int)(rho - (long long)z * p.rows);
-        const long long row = rho * p.pitch;
-        const bool has_dn = r + 1 < p.rows || p.pr, has_fw = z + 1 < p.depth || p.pz;
-        const long long rowd = ((long long)z * p.rows + (r + 1 < p.rows ? r + 1 : 0)) * p.pitch;
-        const long long rowf = ((long long)(z + 1 < p.depth ? z + 1 : 0) * p.rows + r) * p.pitch;
-        for (int i = 0; i < 16; ++i) {
-            const int c = 16 * q + i;
-            if (c >= p.cols) break;
-            const int s = p.s[row + c];
-            double l = (double)p.h[row + c];
-            if (c + 1 < p.cols || p.pc) l += (double)p.jr[row + c] * p.s[row + (c + 1 < p.cols ? c + 1 : 0)];
-            if (has_dn) l += (double)p.jd[row + c] * p.s[rowd + c];
-            if (has_fw) l += (double)p.jl[row + c] * p.s[rowf + c];
-            e += s * l;
-            m += s;
-        }
-    }
-    ssum = m;
-    return e;
+    *reinterpret_cast<uint4*>(p.w.s + rho * p.g.pitch + 16 * q) = make_uint4(o[0], o[1], o[2], o[3]);
 }
 
 // E partials: one per workgroup
 __global__ __launch_bounds__(256) void k8_energy(K8Params p, double* __restrict__ part) {
     long long m;
-    const double e = block_sum(k8_energy_lane(p, m));
+    const double e = block_sum(energy_lane<3>(p.g, p.w.s, m));
     if (threadIdx.x == 0) part[blockIdx.x] = e;
 }
 
@@ -307,253 +182,97 @@ __global__ __launch_bounds__(256) void k8_sum(const int8_t* __restrict__ a, long
 }
 
 // ------------------------------------------------------------------ parallel tempering
-struct PT3Params {
-    int8_t* const* s;     // walker g = ladder * R + w -> its spins (one pitch for all)
-    const uint32_t* key;  // walker -> Philox key (k0, k1) of seed + g
-    const int32_t* slot;  // walker -> its slot in its ladder
-    const double* T;      // slot -> T
-    const float* c32;     // slot -> fl32(2 / T)
-    const float* jr;      // the one disorder (K8Params layout)
-    const float* jd;
-    const float* jl;
-    const float* h;
-    long long pitch;
-    long long nrows;
-    int depth, rows, cols;
-    int pz, pr, pc;
-    int lshift;
-    int nw, W;            // walkers; walkers per lane (group z of the grid: walkers [z W, z W + W))
-    uint32_t hs;
-};
-
-// k8_octet for the walkers [g0, g1): the colour's couplings, fields and the screen's sum of |terms| are staged once, then each
-// walker takes the same decision as k8_octet at the temperature of its slot, with its own key (replica 0)
-template <int PAR>
-__device__ __forceinline__ void k8_pt_octet(const PT3Params& p, int z, int r, int q, int g0, int g1) {
-    const long long rho = (long long)z * p.rows + r;
-    const long long row = rho * p.pitch;
-    const int c0 = 16 * q;
-    const bool has_bk = z > 0 || p.pz, has_fw = z + 1 < p.depth || p.pz;
-    const bool has_up = r > 0 || p.pr, has_dn = r + 1 < p.rows || p.pr;
-    const long long rowb = ((long long)(z > 0 ? z - 1 : p.depth - 1) * p.rows + r) * p.pitch;
-    const long long rowf = ((long long)(z + 1 < p.depth ? z + 1 : 0) * p.rows + r) * p.pitch;
-    const long long rowu = ((long long)z * p.rows + (r > 0 ? r - 1 : p.rows - 1)) * p.pitch;
-    const long long rowd = ((long long)z * p.rows + (r + 1 < p.rows ? r + 1 : 0)) * p.pitch;
-    const bool has_prev = q > 0 || p.pc;
-    const int cprev = q > 0 ? c0 - 1 : p.cols - 1;
-    // the colour's 8 sites: J to the six neighbours (0 where one is missing), h, and the screen's sum of |terms|
-    float Jb[8], Jf[8], Ju[8], Jd[8], Jl[8], Jr[8], hf[8], a32[8];
-    {
-        float4 jr[4], jd[4], jl[4], ju[4], jb[4], hh[4];
-        load16f(p.jr + row + c0, jr);
-        load16f(p.jd + row + c0, jd);
-        load16f(p.jl + row + c0, jl);
-        load16f(p.h + row + c0, hh);
-        if (has_up) load16f(p.jd + rowu + c0, ju);
-        else zero16f(ju);
-        if (has_bk) load16f(p.jl + rowb + c0, jb);
-        else zero16f(jb);
-        const float j_prev = has_prev ? p.jr[row + cprev] : 0.0f;
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int i = 2 * m + PAR, c = c0 + i;
-            const bool has_left = i > 0 || has_prev, has_right = c + 1 < p.cols || p.pc;
-            Jb[m] = has_bk ? fat(jb, i) : 0.0f;
-            Jf[m] = has_fw ? fat(jl, i) : 0.0f;
-            Ju[m] = has_up ? fat(ju, i) : 0.0f;
-            Jd[m] = has_dn ? fat(jd, i) : 0.0f;
-            Jl[m] = has_left ? (i > 0 ? fat(jr, i - 1) : j_prev) : 0.0f;
-            Jr[m] = has_right ? fat(jr, i) : 0.0f;
-            hf[m] = fat(hh, i);
-            a32[m] = fabsf(Jb[m]) + fabsf(Jf[m]) + fabsf(Ju[m]) + fabsf(Jd[m]) + fabsf(Jl[m]) + fabsf(Jr[m]) + fabsf(hf[m]);
-        }
-    }
-    const uint4 zero4 = make_uint4(0, 0, 0, 0);
-#pragma unroll 1
-    for (int g = g0; g < g1; ++g) {
-        int8_t* const s = p.s[g];
-        const int slot = p.slot[g];
-        const double T = p.T[slot];
-        const float c32 = p.c32[slot];
-        const uint32_t k0 = p.key[2 * g], k1 = p.key[2 * g + 1];
-        const uint4 C = *reinterpret_cast<const uint4*>(s + row + c0);
-        const uint4 B = has_bk ? *reinterpret_cast<const uint4*>(s + rowb + c0) : zero4;
-        const uint4 F = has_fw ? *reinterpret_cast<const uint4*>(s + rowf + c0) : zero4;
-        const uint4 U = has_up ? *reinterpret_cast<const uint4*>(s + rowu + c0) : zero4;
-        const uint4 D = has_dn ? *reinterpret_cast<const uint4*>(s + rowd + c0) : zero4;
-        const int s_prev = has_prev ? (int)s[row + cprev] : 0;
-        const int s_next = (c0 + 16 < p.cols) ? (int)s[row + c0 + 16] : 0;
-        const int s_first = p.pc ? (int)s[row] : 0;
-        const u32x4 w = tsu_philox((uint32_t)q, (uint32_t)rho, p.hs, TSU_TAG_ISING_HI, k0, k1);
-        const uint32_t wv[4] = {w.x, w.y, w.z, w.w};
-        bool have_lo = false;
-        uint32_t lv[4] = {0, 0, 0, 0};
-        uint32_t out[4] = {C.x, C.y, C.z, C.w};
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int i = 2 * m + PAR, c = c0 + i;
-            if (c >= p.cols) break;
-            const bool has_left = i > 0 || has_prev, has_right = c + 1 < p.cols || p.pc;
-            const int sb = sbyte(B, i), sf = sbyte(F, i), su = sbyte(U, i), sd = sbyte(D, i);
-            const int sl = i > 0 ? sbyte(C, i - 1) : s_prev;
-            const int sr = c + 1 < p.cols ? (i < 15 ? sbyte(C, i + 1) : s_next) : s_first;
-            const float f32 =
-                (((((Jb[m] * (float)sb + Jf[m] * (float)sf) + Ju[m] * (float)su) + Jd[m] * (float)sd) + Jl[m] * (float)sl) + Jr[m] * (float)sr) +
-                hf[m];
-            const uint32_t hi = ((wv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu) ^ 0x8000u;
-            int dec = screen(f32, a32[m], c32, hi);
-            if (dec == 0) {
-                // the contract's sum: neighbours in the order z-1, z+1, r-1, r+1, c-1, c+1, a missing one skipped, then h
-                double f = 0.0;
-                bool any = false;
-                if (has_bk) { f = (double)Jb[m] * sb; any = true; }
-                if (has_fw) { f = any ? f + (double)Jf[m] * sf : (double)Jf[m] * sf; any = true; }
-                if (has_up) { f = any ? f + (double)Ju[m] * su : (double)Ju[m] * su; any = true; }
-                if (has_dn) { f = any ? f + (double)Jd[m] * sd : (double)Jd[m] * sd; any = true; }
-                if (has_left) { f = any ? f + (double)Jl[m] * sl : (double)Jl[m] * sl; any = true; }
-                if (has_right) { f = any ? f + (double)Jr[m] * sr : (double)Jr[m] * sr; any = true; }
-                f = any ? f + (double)hf[m] : (double)hf[m];
-                const uint64_t thr = exact_thr(f, T);
-                const uint32_t thi = (uint32_t)(thr >> 16);
-                bool accept = hi < thi;
-                if (hi == thi) {  // tie on the top 16 bits: the low half, as K1 draws it
-                    if (!have_lo) {
-                        const u32x4 l = tsu_philox((uint32_t)q, (uint32_t)rho, p.hs, TSU_TAG_ISING_LO, k0, k1);
-                        lv[0] = l.x; lv[1] = l.y; lv[2] = l.z; lv[3] = l.w;
-                        have_lo = true;
-                    }
-                    const uint32_t lo = (lv[m >> 1] >> (16 * (m & 1))) & 0xFFFFu;
-                    accept = (((uint64_t)hi << 16) | lo) < thr;
-                }
-                dec = accept ? 1 : -1;
-            }
-            const uint32_t b = dec > 0 ? 0x01u : 0xFFu;
-            const int sh = 8 * (i & 3);
-            out[i >> 2] = (out[i >> 2] & ~(0xFFu << sh)) | (b << sh);
-        }
-        *reinterpret_cast<uint4*>(s + row + c0) = make_uint4(out[0], out[1], out[2], out[3]);
-    }
-}
-
 // k8_sweep's grid with the walker group as its z dimension: lane = octet q of row rho (k8_lane) for the walkers of group z.
 // The 64 staged floats and five spin vectors fit 255 VGPRs without scratch; the second launch bound keeps the allocator from
 // spreading into AGPRs, which would halve the waves per SIMD for nothing.
-__global__ __launch_bounds__(256, 2) void k8_pt_sweep(PT3Params p, int colour) {
-    long long rho;
-    int q;
-    if (!k8_lane(p, rho, q)) return;
-    const int z = (int)(rho / p.rows), r = (int)(rho - (long long)z * p.rows);
-    const int g0 = blockIdx.z * p.W, g1 = min(g0 + p.W, p.nw);
-    if (((z + r + colour) & 1) == 0) k8_pt_octet<0>(p, z, r, q, g0, g1);
-    else k8_pt_octet<1>(p, z, r, q, g0, g1);
-}
-
-// The ensemble's sample index: grid z of the sweep = sample * groups + walker group, walkers [base + group W, ..) clipped to the
-// sample's own [base, base + nper), base = sample * nper; the sample's disorder sits dstride floats after its predecessor's
-struct PTEns {
-    long long dstride;  // floats of a sample's disorder (4 planes)
-    int nper;           // walkers of a sample (nl * R)
-    int groups;         // walker groups of a sample: ceil(nper / W)
-};
-
-__device__ __forceinline__ void pte_sample(PT3Params& p, const PTEns& e, int sample) {
-    const long long off = (long long)sample * e.dstride;
-    p.jr += off;
-    p.jd += off;
-    p.jl += off;
-    p.h += off;
+__global__ __launch_bounds__(256, 2) void k8_pt_sweep(PTParams p, int colour) {
+    int z, r, q;
+    if (!k8_lane(p, z, r, q)) return;
+    const int g0 = blockIdx.z * p.W;
+    octet_group<3>(p, z, r, q, g0, min(g0 + p.W, p.nw), colour);
 }
 
 // k8_pt_sweep for an ensemble, a kernel of its own so that the ladders' code object stays what it was: the same lane and the same
 // octet, for the walkers of one group of one sample on that sample's disorder.  The sample and its offsets are wave-uniform.
-__global__ __launch_bounds__(256, 2) void k8_pte_sweep(PT3Params p, PTEns e, int colour) {
-    long long rho;
-    int q;
-    if (!k8_lane(p, rho, q)) return;
-    const int z = (int)(rho / p.rows), r = (int)(rho - (long long)z * p.rows);
-    const int sample = blockIdx.z / e.groups, group = blockIdx.z - sample * e.groups;
-    const int base = sample * e.nper;
-    const int g0 = base + group * p.W, g1 = min(g0 + p.W, base + e.nper);
-    pte_sample(p, e, sample);
-    if (((z + r + colour) & 1) == 0) k8_pt_octet<0>(p, z, r, q, g0, g1);
-    else k8_pt_octet<1>(p, z, r, q, g0, g1);
-}
-
-__device__ __forceinline__ K8Params pt_walker_params(const PT3Params& pp, int g) {
-    K8Params p;
-    p.s = pp.s[g];
-    p.jr = pp.jr;
-    p.jd = pp.jd;
-    p.jl = pp.jl;
-    p.h = pp.h;
-    p.pitch = pp.pitch;
-    p.nrows = pp.nrows;
-    p.depth = pp.depth;
-    p.rows = pp.rows;
-    p.cols = pp.cols;
-    p.pz = pp.pz;
-    p.pr = pp.pr;
-    p.pc = pp.pc;
-    p.lshift = pp.lshift;
-    p.c32 = 0.0f;
-    p.T = 0.0;
-    p.k0 = p.k1 = p.hs = p.tag_hi = p.tag_lo = 0;
-    return p;
+__global__ __launch_bounds__(256, 2) void k8_pte_sweep(PTParams p, PTEns e, int colour) {
+    int z, r, q, g0, g1;
+    if (!k8_lane(p, z, r, q)) return;
+    pte_group(p, e, g0, g1);
+    octet_group<3>(p, z, r, q, g0, g1, colour);
 }
 
 // grid (blocks_for(lattice), nw): workgroup x of walker y computes k8_energy's partial x of that walker alone, and its sum of spins
-__global__ __launch_bounds__(256) void k8_pt_energy(PT3Params pp, double* __restrict__ part, long long* __restrict__ ipart) {
+__global__ __launch_bounds__(256) void k8_pt_energy(PTParams p, double* __restrict__ part, long long* __restrict__ ipart) {
     long long m;
-    const double e = block_sum(k8_energy_lane(pt_walker_params(pp, blockIdx.y), m));
-    const long long ms = block_isum(m);
-    if (threadIdx.x == 0) {
-        part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
-        ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
-    }
+    const double e = energy_lane<3>(p.g, p.s[blockIdx.y], m);
+    pt_energy_partials(e, m, part, ipart);
 }
 
 // k8_pt_energy for an ensemble: walker y on the disorder of its sample y / nper
-__global__ __launch_bounds__(256) void k8_pte_energy(PT3Params pp, PTEns en, double* __restrict__ part, long long* __restrict__ ipart) {
-    pte_sample(pp, en, blockIdx.y / en.nper);
+__global__ __launch_bounds__(256) void k8_pte_energy(PTParams p, PTEns en, double* __restrict__ part, long long* __restrict__ ipart) {
+    pte_sample(p.g, en, blockIdx.y / en.nper);
     long long m;
-    const double e = block_sum(k8_energy_lane(pt_walker_params(pp, blockIdx.y), m));
-    const long long ms = block_isum(m);
-    if (threadIdx.x == 0) {
-        part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
-        ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
-    }
+    const double e = energy_lane<3>(p.g, p.s[blockIdx.y], m);
+    pt_energy_partials(e, m, part, ipart);
+}
+
+// the lattice's shape on the four disorder planes that start at `dis` (its own, or a sample's of an ensemble)
+Geo make_geo(const tsu_ising3d* L, const float* dis) {
+    const size_t plane = (size_t)L->depth * L->rows * L->pitch;
+    Geo g = {};
+    g.jr = dis;
+    g.jd = dis ? dis + plane : nullptr;
+    g.jl = dis ? dis + 2 * plane : nullptr;
+    g.h = dis ? dis + 3 * plane : nullptr;
+    g.pitch = (long long)L->pitch;
+    g.depth = L->depth;
+    g.rows = L->rows;
+    g.cols = L->cols;
+    g.pz = L->pz;
+    g.pr = L->pr;
+    g.pc = L->pc;
+    return g;
+}
+
+// k8_lane's mapping for the lattice: nrows and the lanes per row, into a K8Params or a PTParams
+template <class P>
+void set_lanes(P& p, const tsu_ising3d* L) {
+    const int nchunks = (L->cols + 15) >> 4;
+    p.nrows = (long long)L->depth * L->rows;
+    p.lshift = 0;
+    while (p.lshift < 6 && (1 << p.lshift) < nchunks) ++p.lshift;
 }
 
 K8Params make_params(const tsu_ising3d* L) {
-    K8Params p;
-    const size_t plane = (size_t)L->depth * L->rows * L->pitch;
-    p.s = L->s;
-    p.jr = L->d_dis;
-    p.jd = L->d_dis ? L->d_dis + plane : nullptr;
-    p.jl = L->d_dis ? L->d_dis + 2 * plane : nullptr;
-    p.h = L->d_dis ? L->d_dis + 3 * plane : nullptr;
-    p.pitch = (long long)L->pitch;
-    p.nrows = (long long)L->depth * L->rows;
-    p.depth = L->depth;
-    p.rows = L->rows;
-    p.cols = L->cols;
-    p.pz = L->pz;
-    p.pr = L->pr;
-    p.pc = L->pc;
-    const int nchunks = (L->cols + 15) >> 4;
-    p.lshift = 0;
-    while (p.lshift < 6 && (1 << p.lshift) < nchunks) ++p.lshift;
-    p.c32 = 0.0f;
-    p.T = 0.0;
-    p.k0 = p.k1 = p.hs = p.tag_hi = p.tag_lo = 0;
+    K8Params p = {};
+    p.g = make_geo(L, L->d_dis);
+    p.w.s = L->s;
+    set_lanes(p, L);
     return p;
 }
 
-// grid of the lane-per-octet kernels (k8_lane)
-dim3 octet_grid(const K8Params& p) {
+// grid of the lane-per-octet kernels (k8_lane), with `groups` walker groups (or samples x groups) as its z dimension
+template <class P>
+dim3 octet_grid(const P& p, unsigned groups = 1) {
     const long long rpb = 256 >> p.lshift;
-    const int nchunks = (p.cols + 15) >> 4;
-    return dim3((unsigned)((p.nrows + rpb - 1) / rpb), (unsigned)((nchunks + 63) / 64), 1);
+    const int nchunks = (p.g.cols + 15) >> 4;
+    return dim3((unsigned)((p.nrows + rpb - 1) / rpb), (unsigned)((nchunks + 63) / 64), groups);
+}
+
+// the shape a ladder, an ensemble or a population keeps of its lattices
+template <class H>
+void set_shape(H* P, const tsu_ising3d* L) {
+    P->nrows = (long long)L->depth * L->rows;
+    P->pitch = (long long)L->pitch;
+    P->cols = L->cols;
+    P->n_axes = 3;
+    P->lrows = L->rows;
+    P->axis_len[0] = L->depth;
+    P->axis_len[1] = L->rows;
+    P->axis_len[2] = L->cols;
+    P->axis_per[0] = L->pz;
+    P->axis_per[1] = L->pr;
+    P->axis_per[2] = L->pc;
 }
 
 unsigned blocks_for(const tsu_ising3d* L) { return reduce_blocks((long long)L->depth * L->rows * ((L->cols + 15) / 16)); }
@@ -570,78 +289,29 @@ int read_acc(tsu_ising3d* L, int64_t* out) {
 
 void pt_free(tsu_pt3d* P) { pt_delete(P, tsu_ising3d_destroy); }
 
-PT3Params pt_params(const tsu_pt3d* P) {
-    const K8Params k = make_params(P->lat[0]);
-    PT3Params p;
-    p.s = P->d_s;
-    p.key = P->d_key;
-    p.slot = P->d_slot;
-    p.T = P->d_T;
-    p.c32 = P->d_c32;
-    p.jr = k.jr;
-    p.jd = k.jd;
-    p.jl = k.jl;
-    p.h = k.h;
-    p.pitch = k.pitch;
-    p.nrows = k.nrows;
-    p.depth = k.depth;
-    p.rows = k.rows;
-    p.cols = k.cols;
-    p.pz = k.pz;
-    p.pr = k.pr;
-    p.pc = k.pc;
-    p.lshift = k.lshift;
-    p.nw = P->nw;
-    p.W = 1;
-    p.hs = 0;
+// the parameters of nw walkers at W per lane, on lattice L's shape and the disorder at `dis`
+template <class H>
+PTParams ladder_on(const H* P, const tsu_ising3d* L, const float* dis, int nw, int W) {
+    PTParams p = ladder_params(P, make_geo(L, dis), nw, W);
+    set_lanes(p, L);
     return p;
 }
 
-// k8_pt_energy into d_part / d_ipart (asynchronous): the partial pass pt_host.h's energies take
-auto pt_partials(tsu_pt3d* P, const PT3Params& p) {
-    return [P, &p](unsigned blocks) { k8_pt_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
+PTParams pt_params(const tsu_pt3d* P) { return ladder_on(P, P->lat[0], P->lat[0]->d_dis, P->nw, 1); }
+
+// k8_pt_energy for nw walkers into d_part / d_ipart (asynchronous): the partial pass pt_host.h's and pop_host.h's energies take
+template <class H>
+auto pt_partials(H* P, int nw, const PTParams& p) {
+    return [P, nw, &p](unsigned blocks) { k8_pt_energy<<<dim3(blocks, (unsigned)nw, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
 }
 
 void pte_free(tsu_pte3d* P) { pte_delete(P, tsu_ising3d_destroy); }
 
 // the ladders' parameters for an ensemble: sample 0's disorder (the kernels add the sample's offset), the walkers of all samples
-PT3Params pte_params(const tsu_pte3d* P) {
-    const K8Params k = make_params(P->lat);
-    PT3Params p;
-    p.s = P->d_s;
-    p.key = P->d_key;
-    p.slot = P->d_slot;
-    p.T = P->d_T;
-    p.c32 = P->d_c32;
-    p.jr = P->d_dis;
-    p.jd = P->d_dis + P->plane;
-    p.jl = P->d_dis + 2 * P->plane;
-    p.h = P->d_dis + 3 * P->plane;
-    p.pitch = k.pitch;
-    p.nrows = k.nrows;
-    p.depth = k.depth;
-    p.rows = k.rows;
-    p.cols = k.cols;
-    p.pz = k.pz;
-    p.pr = k.pr;
-    p.pc = k.pc;
-    p.lshift = k.lshift;
-    p.nw = P->nw;
-    p.W = 1;
-    p.hs = 0;
-    return p;
-}
-
-PTEns pte_ens(const tsu_pte3d* P, int W) {
-    PTEns e;
-    e.dstride = 4 * (long long)P->plane;
-    e.nper = P->nl * P->R;
-    e.groups = (int)pte_groups(P, W);
-    return e;
-}
+PTParams pte_params(const tsu_pte3d* P) { return ladder_on(P, P->lat, P->d_dis, P->nw, 1); }
 
 // k8_pte_energy into d_part / d_ipart (asynchronous)
-auto pte_partials(tsu_pte3d* P, const PT3Params& p, const PTEns& e) {
+auto pte_partials(tsu_pte3d* P, const PTParams& p, const PTEns& e) {
     return [P, &p, &e](unsigned blocks) {
         k8_pte_energy<<<dim3(blocks, (unsigned)P->nw, 1), 256, 0, P->ctx->stream>>>(p, e, P->d_part, P->d_ipart);
     };
@@ -650,47 +320,17 @@ auto pte_partials(tsu_pte3d* P, const PT3Params& p, const PTEns& e) {
 void pa_free(tsu_pa3d* P) { pop_delete(P, tsu_ising3d_destroy); }
 
 // the ladders' parameters for a population: walker -> plane, key and slot 0; T / c32 are set per step
-PT3Params pa_params(const tsu_pa3d* P) {
-    const K8Params k = make_params(P->lat);
-    PT3Params p;
-    p.s = P->d_s;
-    p.key = P->d_key;
-    p.slot = P->d_slot;
-    p.T = P->d_T;
-    p.c32 = P->d_c32;
-    p.jr = k.jr;
-    p.jd = k.jd;
-    p.jl = k.jl;
-    p.h = k.h;
-    p.pitch = k.pitch;
-    p.nrows = k.nrows;
-    p.depth = k.depth;
-    p.rows = k.rows;
-    p.cols = k.cols;
-    p.pz = k.pz;
-    p.pr = k.pr;
-    p.pc = k.pc;
-    p.lshift = k.lshift;
-    p.nw = P->R;
-    p.W = pop_group(P);
-    p.hs = 0;
-    return p;
-}
+PTParams pa_params(const tsu_pa3d* P) { return ladder_on(P, P->lat, P->lat->d_dis, P->R, pop_group(P)); }
 
-// half-sweep hs of every walker at step k's temperature / the energy partial pass: what pop_host.h's init and run take
-auto pa_sweep(tsu_pa3d* P, PT3Params& p) {
-    const dim3 og = octet_grid(make_params(P->lat));
-    const dim3 grid(og.x, og.y, (unsigned)((P->R + p.W - 1) / p.W));
+// half-sweep hs of every walker at step k's temperature: what pop_host.h's init and run take
+auto pa_sweep(tsu_pa3d* P, PTParams& p) {
+    const dim3 grid = octet_grid(p, (unsigned)((P->R + p.W - 1) / p.W));
     return [P, &p, grid](uint32_t hs, int colour, int k) {
         p.hs = hs;
         p.T = P->d_T + k;
         p.c32 = P->d_c32 + k;
         k8_pt_sweep<<<grid, 256, 0, P->ctx->stream>>>(p, colour);
     };
-}
-
-auto pa_partials(tsu_pa3d* P, const PT3Params& p) {
-    return [P, &p](unsigned blocks) { k8_pt_energy<<<dim3(blocks, (unsigned)P->R, 1), 256, 0, P->ctx->stream>>>(p, P->d_part, P->d_ipart); };
 }
 
 }  // namespace
@@ -779,8 +419,8 @@ int tsu_ising3d_randomize(tsu_ising3d* L, uint64_t seed, uint32_t replica) {
     if (!L) return TSU_E_INVALID;
     tsu_ctx* ctx = L->ctx;
     K8Params p = make_params(L);
-    p.k0 = (uint32_t)seed;
-    p.k1 = (uint32_t)(seed >> 32);
+    p.w.k0 = (uint32_t)seed;
+    p.w.k1 = (uint32_t)(seed >> 32);
     k8_randomize<<<octet_grid(p), 256, 0, ctx->stream>>>(p, TSU_TAG_INIT | (replica << 8));
     TSU_HIP_TRY(ctx, hipGetLastError());
     return TSU_OK;
@@ -846,9 +486,9 @@ int tsu_ising3d_sweep(tsu_ising3d* L, double T, int n_sweeps, uint64_t seed, uin
     TSU_REQUIRE(ctx, (uint64_t)sweep0 + (uint64_t)n_sweeps <= (1ull << 31), "ising3d_sweep: sweep counter overflow");
     if (n_sweeps == 0) return TSU_OK;
     K8Params p = make_params(L);
-    ising2d_set_keys(p, seed, replica);
-    p.T = T;
-    p.c32 = (float)(2.0 / T);
+    ising2d_set_keys(p.w, seed, replica);
+    p.w.T = T;
+    p.w.c32 = (float)(2.0 / T);
     const dim3 grid = octet_grid(p);
     for (int s = 0; s < n_sweeps; ++s)
         for (int colour = 0; colour < 2; ++colour) {
@@ -963,17 +603,7 @@ int tsu_pt3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_ma
         ctx, "pt3d", n_temps, n_ladders, out,
         [=](tsu_ising3d** L) { return tsu_ising3d_create(ctx, depth, rows, cols, periodic_mask, L); },
         [](tsu_pt3d* P, int8_t** planes) {
-            P->nrows = (long long)P->lat[0]->depth * P->lat[0]->rows;
-            P->pitch = (long long)P->lat[0]->pitch;
-            P->cols = P->lat[0]->cols;
-            P->n_axes = 3;
-            P->lrows = P->lat[0]->rows;
-            P->axis_len[0] = P->lat[0]->depth;
-            P->axis_len[1] = P->lat[0]->rows;
-            P->axis_len[2] = P->lat[0]->cols;
-            P->axis_per[0] = P->lat[0]->pz;
-            P->axis_per[1] = P->lat[0]->pr;
-            P->axis_per[2] = P->lat[0]->pc;
+            set_shape(P, P->lat[0]);
             for (int g = 0; g < P->nw; ++g) planes[g] = P->lat[g]->s;
         },
         pt_free);
@@ -1016,17 +646,16 @@ int tsu_pt3d_run(tsu_pt3d* P, int n_rounds, int swap_interval, int do_swap, int 
     tsu_ising3d* L = P->lat[0];
     const int rc = pt_run_check(P, L->have_disorder, n_rounds, swap_interval);
     if (rc != TSU_OK) return rc;
-    PT3Params p = pt_params(P);
+    PTParams p = pt_params(P);
     p.W = pt_group(P);
-    const dim3 og = octet_grid(make_params(L));
-    const dim3 grid(og.x, og.y, (unsigned)((P->nw + p.W - 1) / p.W));
+    const dim3 grid = octet_grid(p, (unsigned)((P->nw + p.W - 1) / p.W));
     return pt_run(
         P, n_rounds, swap_interval, do_swap, record,
         [&](uint32_t hs, int colour) {
             p.hs = hs;
             k8_pt_sweep<<<grid, 256, 0, ctx->stream>>>(p, colour);
         },
-        pt_partials(P, p), [] { return (int)TSU_OK; });
+        pt_partials(P, P->nw, p), [] { return (int)TSU_OK; });
 }
 
 int tsu_pt3d_history(tsu_pt3d* P, double* E, int64_t* M, int64_t* q, int32_t* walker) {
@@ -1043,8 +672,8 @@ int tsu_pt3d_stats(tsu_pt3d* P, int64_t* attempts, int64_t* accepts, int64_t* ro
 int tsu_pt3d_energies(tsu_pt3d* P, double* E, int64_t* sum_s) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
-    const PT3Params p = pt_params(P);
-    return pt_energies(P, P->lat[0]->have_disorder, E, sum_s, pt_partials(P, p));
+    const PTParams p = pt_params(P);
+    return pt_energies(P, P->lat[0]->have_disorder, E, sum_s, pt_partials(P, P->nw, p));
 }
 
 int tsu_pt3d_get_spins(tsu_pt3d* P, int ladder, int slot, int8_t* host) {
@@ -1111,17 +740,7 @@ int tsu_pte3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_m
         [=](tsu_pte3d* P) {
             const int rc = tsu_ising3d_create(ctx, depth, rows, cols, periodic_mask, &P->lat);
             if (rc != TSU_OK) return rc;
-            P->nrows = (long long)P->lat->depth * P->lat->rows;
-            P->pitch = (long long)P->lat->pitch;
-            P->cols = P->lat->cols;
-            P->n_axes = 3;
-            P->lrows = P->lat->rows;
-            P->axis_len[0] = P->lat->depth;
-            P->axis_len[1] = P->lat->rows;
-            P->axis_len[2] = P->lat->cols;
-            P->axis_per[0] = P->lat->pz;
-            P->axis_per[1] = P->lat->pr;
-            P->axis_per[2] = P->lat->pc;
+            set_shape(P, P->lat);
             P->n_dis = 4;
             return (int)TSU_OK;
         },
@@ -1161,11 +780,10 @@ int tsu_pte3d_run(tsu_pte3d* P, int n_rounds, int swap_interval, int do_swap, in
     tsu_ctx* ctx = P->ctx;
     const int rc = pt_run_check(P, P->have_disorder, n_rounds, swap_interval);
     if (rc != TSU_OK) return rc;
-    PT3Params p = pte_params(P);
+    PTParams p = pte_params(P);
     p.W = pt_group(P);
     const PTEns e = pte_ens(P, p.W);
-    const dim3 og = octet_grid(make_params(P->lat));
-    const dim3 grid(og.x, og.y, (unsigned)P->S * (unsigned)e.groups);
+    const dim3 grid = octet_grid(p, (unsigned)P->S * (unsigned)e.groups);
     return pt_run(
         P, n_rounds, swap_interval, do_swap, record,
         [&](uint32_t hs, int colour) {
@@ -1189,7 +807,7 @@ int tsu_pte3d_stats(tsu_pte3d* P, int64_t* attempts, int64_t* accepts, int64_t* 
 int tsu_pte3d_energies(tsu_pte3d* P, double* E, int64_t* sum_s) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
-    const PT3Params p = pte_params(P);
+    const PTParams p = pte_params(P);
     const PTEns e = pte_ens(P, 1);
     return pt_energies(P, P->have_disorder, E, sum_s, pte_partials(P, p, e));
 }
@@ -1249,17 +867,7 @@ int tsu_pa3d_create(tsu_ctx* ctx, int depth, int rows, int cols, int periodic_ma
         [=](tsu_pa3d* P) {
             const int rc = tsu_ising3d_create(ctx, depth, rows, cols, periodic_mask, &P->lat);
             if (rc != TSU_OK) return rc;
-            P->nrows = (long long)P->lat->depth * P->lat->rows;
-            P->pitch = (long long)P->lat->pitch;
-            P->cols = P->lat->cols;
-            P->n_axes = 3;
-            P->lrows = P->lat->rows;
-            P->axis_len[0] = P->lat->depth;
-            P->axis_len[1] = P->lat->rows;
-            P->axis_len[2] = P->lat->cols;
-            P->axis_per[0] = P->lat->pz;
-            P->axis_per[1] = P->lat->pr;
-            P->axis_per[2] = P->lat->pc;
+            set_shape(P, P->lat);
             return (int)TSU_OK;
         },
         pa_free);
@@ -1288,8 +896,8 @@ int tsu_pa3d_set_schedule(tsu_pa3d* P, const double* betas, int n) {
 int tsu_pa3d_init(tsu_pa3d* P, uint64_t seed, int initial_sweeps) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
-    PT3Params p = pa_params(P);
-    return pop_init(P, P->lat->have_disorder, seed, initial_sweeps, pa_sweep(P, p), pa_partials(P, p));
+    PTParams p = pa_params(P);
+    return pop_init(P, P->lat->have_disorder, seed, initial_sweeps, pa_sweep(P, p), pt_partials(P, P->R, p));
 }
 
 int tsu_pa3d_run(tsu_pa3d* P, int n_steps, int sweeps_per_step, int resample, int record) {
@@ -1297,8 +905,8 @@ int tsu_pa3d_run(tsu_pa3d* P, int n_steps, int sweeps_per_step, int resample, in
     if (!P) return TSU_E_INVALID;
     const int rc = pop_run_check(P, P->lat->have_disorder, n_steps, sweeps_per_step);
     if (rc != TSU_OK) return rc;
-    PT3Params p = pa_params(P);
-    return pop_run(P, n_steps, sweeps_per_step, resample, record, pa_sweep(P, p), pa_partials(P, p));
+    PTParams p = pa_params(P);
+    return pop_run(P, n_steps, sweeps_per_step, resample, record, pa_sweep(P, p), pt_partials(P, P->R, p));
 }
 
 int tsu_pa3d_history(tsu_pa3d* P, double* E, int64_t* M, uint32_t* W, int32_t* parent, uint64_t* S, uint64_t* U, double* E_min) {
@@ -1309,8 +917,8 @@ int tsu_pa3d_history(tsu_pa3d* P, double* E, int64_t* M, uint32_t* W, int32_t* p
 int tsu_pa3d_energies(tsu_pa3d* P, double* E, int64_t* sum_s) {
     TSU_ENTER(P ? P->ctx : nullptr);
     if (!P) return TSU_E_INVALID;
-    const PT3Params p = pa_params(P);
-    return pop_energies(P, P->lat->have_disorder, E, sum_s, pa_partials(P, p));
+    const PTParams p = pa_params(P);
+    return pop_energies(P, P->lat->have_disorder, E, sum_s, pt_partials(P, P->R, p));
 }
 
 int tsu_pa3d_get_spins(tsu_pa3d* P, int i, int8_t* host) {

@@ -2,7 +2,7 @@
 // L = sum over bonds (i, j) of p_i p_j with p = s^a s^b, for lattice pairs, for every slot of a two-ladder tempering handle and
 // for the walker pairs of a population.  Dimension-blind like reduce_dev.h and corr_dev.h: a plane is `nrows` rows of `pitch` bytes
 // of which the first `cols` count, row rho = z lrows + r, one periodic flag per axis (a 2-D lattice: one layer, open z).  The bonds
-// are the bonds of the energy passes (k7_energy_lane, k8_energy_lane): every site's right, down and layer bond, the last bond of an
+// are the bonds of the energy passes (energy_lane, disorder_dev.h): every site's right, down and layer bond, the last bond of an
 // open axis dropped, the wrap bond of a periodic axis kept, so an axis of length 1 or 2 counts its wrap as the energy does.
 //
 // Integers only.  Spins are the bytes 0x01 / 0xFF, so x = a ^ b is 0x00 (p = +1) or 0xFE (p = -1) per site and 0x00 on the pad

@@ -13,6 +13,7 @@
 #include <new>
 #include <vector>
 
+#include "disorder_dev.h"
 #include "pt_host.h"
 
 constexpr int kPteMaxWalkers = 65535;  // grid y of the energy partial pass
@@ -183,7 +184,14 @@ int pte_set_spins(pte_handle* P, int sample, int ladder, int slot, const int8_t*
     return TSU_OK;
 }
 
-// the sweep's grid z of an ensemble: groups of W walkers within each sample's nl R walkers
-unsigned pte_groups(const pte_handle* P, int W) { return (unsigned)((P->nl * P->R + W - 1) / W); }
+// what the ensemble kernels take beside the ladders' parameters (disorder_dev.h) at W walkers per lane: the sweep's grid z is groups
+// of W walkers within each sample's nl R walkers, a sample's disorder its n_dis planes
+PTEns pte_ens(const pte_handle* P, int W) {
+    PTEns e;
+    e.dstride = (long long)P->n_dis * (long long)P->plane;
+    e.nper = P->nl * P->R;
+    e.groups = (e.nper + W - 1) / W;
+    return e;
+}
 
 }  // namespace

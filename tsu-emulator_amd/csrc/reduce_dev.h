@@ -1,7 +1,7 @@
 // reduce_dev.h -- the reductions the disordered lattices share: K7 (ising2d_disorder.hip, 2-D) and K8 (ising3d.hip, 3-D), single
 // lattices and tempering ladders alike.  Nothing here knows the lattice's dimension: a spin plane is `nrows` rows of `pitch` bytes
-// (nrows = rows in 2-D, depth * rows in 3-D) of which the first `cols` count.  What reads the disorder layout (the energy lanes,
-// the sweeps) stays with its dimension.  Everything here has internal linkage: each translation unit that includes the header
+// (nrows = rows in 2-D, depth * rows in 3-D) of which the first `cols` count.  What reads the disorder layout (the energy lane,
+// the octet) is disorder_dev.h's.  Everything here has internal linkage: each translation unit that includes the header
 // gets its own copy of the kernels.
 #pragma once
 #include "disorder_dev.h"
@@ -53,6 +53,17 @@ __global__ __launch_bounds__(256) void pt_energy_final(const double* __restrict_
     if (threadIdx.x == 0) {
         E[blockIdx.x] = e;
         M[blockIdx.x] = ms;
+    }
+}
+
+// the tail of the ladders' energy kernels, grid (blocks, walkers): workgroup x's partial of walker y's energy and sum of spins from
+// the lanes' shares
+__device__ __forceinline__ void pt_energy_partials(double e_lane, long long m_lane, double* __restrict__ part, long long* __restrict__ ipart) {
+    const double e = block_sum(e_lane);
+    const long long ms = block_isum(m_lane);
+    if (threadIdx.x == 0) {
+        part[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = e;
+        ipart[(size_t)blockIdx.y * kEnergyBlocks + blockIdx.x] = ms;
     }
 }
 
