@@ -112,6 +112,8 @@ def main():
             print(f"\n{name}\n  VGPRs {r['NumVgprs']}, scratch {r['ScratchSize']} bytes, occupancy {r['Occupancy']}, code {r['codeLenInByte']} bytes")
             for a, b in pair_loops(body):
                 h = hot_path(body, a, b)
+                if not h.get("v_mad_u64_u32"):  # a range made of cold blocks only (the lane loop of the tie call between two back edges)
+                    continue
                 valu = sorted(((k, v) for k, v in h.items() if k.startswith("v_")), key=lambda kv: (-kv[1], kv[0]))
                 seam = h.get("v_lshrrev_b64") or h.get("v_and_b32_e32", 0) >= 9
                 form = "SEAM" if seam else ("EDGE" if h.get("s_cselect_b32") else "plain")

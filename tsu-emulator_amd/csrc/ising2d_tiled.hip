@@ -4,10 +4,10 @@
 // identical); what changes is the schedule:
 //   * a workgroup stages a (H + 4k) x (16 WO + 32) tile of the int8 lattice into LDS, de-interleaved into two
 //     colour planes of 0/1 "up" flags (8 same-colour sites of a row = one octet = one uint64),
-//   * keeps the two planes interleaved row by row: behind one guard octet, tile row r is its NO = WO + 2 octets of plane 0
-//     followed by its NO octets of plane 1, then one spare row and the 25 thresholds of the tie path.  Row stride (2 NO octets)
-//     and plane distance (NO octets) are compile-time constants for a tile of any height, so the pair loop carries ONE LDS
-//     address and every read and write of a pair is that address plus an immediate (see pair_step),
+//   * keeps the two planes interleaved row by row: behind the pair table of the compare and one guard octet, tile row r is its
+//     NO = WO + 2 octets of plane 0 followed by its NO octets of plane 1, then one spare row and the 25 thresholds of the tie
+//     path.  Row stride (2 NO octets) and plane distance (NO octets) are compile-time constants for a tile of any height, so the
+//     pair loop carries ONE LDS address and every read and write of a pair is that address plus an immediate (see pair_step),
 //   * runs 2k half-sweeps entirely in LDS (the region that is still exact shrinks by one site per half-sweep:
 //     2k halo rows, one halo octet = 16 columns >= 2k each side), and
 //   * writes the H x 16 WO interior to the OTHER lattice buffer (neighbouring tiles read this tile's pre-launch
@@ -15,9 +15,10 @@
 // When every tile of the lattice has its own workgroup on the chip (up to 2^25 sites), k1_resident keeps the tiles in
 // LDS for a whole call and only exchanges boundary strips between generations of k sweeps (see ResidentParams).
 // HBM traffic is 2/k bytes per spin update instead of 2 (far less when resident); the kernel is VALU bound (Philox), so per octet:
-//   one Philox4x32-10 block -> 8 x 16 random bits; neighbour sums with packed byte adds; 16-bit thresholds
-//   picked per site with v_perm_b32 byte look-ups; v_pk_sub_i16 (saturating) compares two sites per
-//   instruction; only an exact tie of the top 16 bits (2^-16 per site) evaluates the low half.
+//   one Philox4x32-10 block -> 8 x 16 random bits; neighbour sums with packed byte adds; the 16-bit thresholds of two
+//   sites at a time from a 25-dword LDS table indexed by their two counts (v_dot4_u32_u8 + ds_read_b32; open lattices, whose
+//   edge sites have other degrees, pick them per site with v_perm_b32 byte look-ups); v_pk_sub_i16 (saturating) compares two
+//   sites per instruction; only an exact tie of the top 16 bits (2^-16 per site) evaluates the low half.
 // The form of the pair loop (plain / EDGE / SEAM / OPEN) and par0, the column parity of the colour updated in a half-sweep's first
 // row, are fixed per tile: half-sweep hsi starts at tile row 1 + hsi and updates colour hsi & 1, whose sum is always odd, so par0
 // depends on the parity of the window's first global row alone (odd only for a row slab that starts on an odd row).  Both are
@@ -180,14 +181,22 @@ static __device__ __forceinline__ u32x4 philox_vk(uint32_t c0, uint32_t row, uin
     return u32x4{c0, c1, c2, c3};
 }
 
+#define TSU_LDS __attribute__((address_space(3)))
+static __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const TSU_LDS char*)p; }
+template <typename T>
+static __device__ __forceinline__ T lds_ld(uint32_t a) { return *(const TSU_LDS T*)(uintptr_t)a; }
+template <typename T>
+static __device__ __forceinline__ void lds_st(uint32_t a, T v) { *(TSU_LDS T*)(uintptr_t)a = v; }
+
 struct Rows2Ctx {
     const uint64_t* s_thr;
     int total_rows;
     int rg_tile0, wrap_tr;  // global row of tile row 0 (wrapped on a periodic lattice); EDGE tiles: the tile row whose global row is 0 again
     uint32_t rmask;         // total_rows - 1 where the Philox head takes the row wrap (see philox_vk and tile_body), else all ones
     uint32_t tag_hi, tag_lo, k0, k1;
-    uint32_t tblH0, tblH1, tblL0, tblL1;
-    uint32_t t3H0, t3H1, t3L0, t3L1;  // open lattices: degree 3 / degree 2 byte tables
+    uint32_t tbl2;                        // periodic lattices: LDS byte address of the pair table (see pair_thresholds)
+    uint32_t tblH0, tblH1, tblL0, tblL1;  // open lattices: the degree-4 byte tables (see compare_octet_open)
+    uint32_t t3H0, t3H1, t3L0, t3L1;      // open lattices: degree 3 / degree 2 byte tables
     int last_row;                     // open lattices: global index of the lattice's bottom row
     bool lft, rgt;                    // open lattices: this thread's octet holds the lattice's first / last column
     uint32_t r_par, r_slot;           // open lattices: column parity of the last column and its site within the octet
@@ -208,6 +217,38 @@ static __device__ __forceinline__ u32x4 compare_octet(const u32x4& w, uint32_t c
     d.z = subsat16(w.z, perm(Hh, Lh, 0x05010400u));
     d.w = subsat16(w.w, perm(Hh, Lh, 0x07030602u));
     return d;
+}
+
+// The periodic tile kernels make the same compare without a v_perm.  The 16-bit thresholds of the site pair (j, j + 1) depend on
+// the pair's two counts alone, 25 combinations, and w.x .. w.w hold such pairs: tbl2 (LDS, 25 dwords, built per tile in tile_body)
+// holds t16(c0) | t16(c1) << 16 at dword c0 + 5 c1, already in the layout of a w word, and one v_dot4_u32_u8 with the byte weights
+// (4, 20, 0, 0) or (0, 0, 4, 20) turns the four byte counts of a dword into the byte offset of sites (0, 1) or (2, 3).  The table
+// sits at a compile-time LDS address, so the offset is the whole VGPR address and the base the instruction's offset field.  Per
+// octet 4 v_dot4 + 4 ds_read_b32 for 8 v_perm; 25 consecutive dwords are 25 banks and equal addresses broadcast.
+// (profiles/k1_pair_table_microbench.txt, k1_pair_table_ab.txt)
+struct PairCounts {
+    uint32_t c0l, c0h, c1l, c1h;  // up-counts of the pair's two octets, a byte per site: sites 0..3 and 4..7 of row a, of row b
+};
+struct PairThr {
+    uint32_t t[8];  // threshold words of row a's octet (against w.x .. w.w), then of row b's
+};
+// issues the eight table reads of a pair; pair_step puts them in front of the second Philox block, which hides their latency
+static __device__ __forceinline__ PairThr pair_thresholds(const PairCounts& n, uint32_t tbl2) {
+    constexpr uint32_t W01 = 0x00001404u, W23 = 0x14040000u;
+    const uint32_t cnt[4] = {n.c0l, n.c0h, n.c1l, n.c1h};
+    uint32_t off[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        off[2 * j] = __builtin_amdgcn_udot4(cnt[j], W01, 0u, false);
+        off[2 * j + 1] = __builtin_amdgcn_udot4(cnt[j], W23, 0u, false);
+    }
+    PairThr T;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) T.t[j] = lds_ld<uint32_t>(tbl2 + off[j]);
+    return T;
+}
+static __device__ __forceinline__ u32x4 compare_octet_thr(const u32x4& w, const uint32_t* t) {
+    return u32x4{subsat16(w.x, t[0]), subsat16(w.y, t[1]), subsat16(w.z, t[2]), subsat16(w.w, t[3])};
 }
 
 // Open lattices: as compare_octet, then the sites with fewer than four neighbours take their thresholds from the
@@ -285,12 +326,12 @@ static __device__ __forceinline__ void edge_rows(const Rows2Ctx& c, int to_wrap,
 // NO - 1 read them while another wave may be storing them, without synchronisation.  Either value is a 0/1 flag and the sites
 // it reaches never count, so results do not depend on it -- but the contents of the halo octets' far side (columns that a
 // tile computes along and discards) are not deterministic from run to run.  Nothing may rely on them: compare or dump interiors.
-#define TSU_LDS __attribute__((address_space(3)))
-static __device__ __forceinline__ uint32_t lds_addr(const void* p) { return (uint32_t)(uintptr_t)(const TSU_LDS char*)p; }
-template <typename T>
-static __device__ __forceinline__ T lds_ld(uint32_t a) { return *(const TSU_LDS T*)(uintptr_t)a; }
-template <typename T>
-static __device__ __forceinline__ void lds_st(uint32_t a, T v) { *(TSU_LDS T*)(uintptr_t)a = v; }
+// In front of the guard octet: the pair table of the periodic compare, 25 dwords rounded up to whole octets so that the planes keep
+// their 8-byte alignment.  The tile kernels have no static LDS, so their dynamic LDS, and with it the table, starts at LDS address 0:
+// a constant that the table reads carry in their offset field (through `lds` it would be a register and cost an add per read).
+// A static __shared__ variable in a tile kernel would move the planes onto the table: every K1 parity test then fails.
+constexpr int TBL2_OCTETS = 13;
+constexpr uint32_t TBL2_LDS_ADDR = 0;
 
 // every indexer of the colour planes outside the pair loop: octet o of tile row r of plane pl
 template <typename E, int NO>
@@ -308,8 +349,7 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
                                                  uint32_t cq) {
     constexpr int RS = 2 * NO * 8;                    // row stride
     constexpr int DO = (KAPPA ? NO : -NO) * 8;        // source plane -> destination plane
-    // issue the six LDS reads, run the two Philox blocks (which do not depend on them) while they are in flight,
-    // and only then consume the neighbour rows
+    // issue the six LDS reads and run the Philox blocks (which do not depend on them) while they are in flight
     const uint64_t R0 = lds_ld<uint64_t>(a), R1 = lds_ld<uint64_t>(a + RS);
     const uint64_t R2 = lds_ld<uint64_t>(a + 2 * RS), R3 = lds_ld<uint64_t>(a + 3 * RS);
     // side octets: the last site of the previous octet (the top byte of its high dword) or the first site of the next one.  One of
@@ -326,30 +366,45 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
     // over is taken from / put at position v - 1 instead of 7 (sh_next / sh_prev; 56 for every other octet)
     const uint64_t Na = SEAM ? lds_ld<uint64_t>(a + RS + (P0 ? 8 : -8)) : 0ull;
     const uint64_t Nb = SEAM ? lds_ld<uint64_t>(a + 2 * RS + (P0 ? -8 : 8)) : 0ull;
-    __builtin_amdgcn_sched_barrier(0);  // the reads stay above the Philox blocks ...
+    __builtin_amdgcn_sched_barrier(0);  // the reads stay above the Philox blocks
     int rga = rg, rgb = rg + 1;
     if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
+    // Periodic lattices take the counts and issue the eight threshold reads between the two Philox blocks (by then the plane
+    // reads have landed), so that the table's latency passes under the second block; open lattices, which compare through
+    // v_perm tables in registers, consume the planes below both blocks
+    constexpr bool EARLY = !OPEN;
+    auto counts = [&]() -> PairCounts {
+        const uint32_t C0l = (uint32_t)R1, C0h = (uint32_t)(R1 >> 32), C1l = (uint32_t)R2, C1h = (uint32_t)(R2 >> 32);
+        // horizontal neighbours: compact bytes (j, j+1) when the parity is 1, (j-1, j) when it is 0
+        uint32_t S0l = P0 ? __builtin_amdgcn_alignbyte(C0h, C0l, 1) : __builtin_amdgcn_alignbyte(C0l, A0, 3);
+        uint32_t S0h = P0 ? __builtin_amdgcn_alignbyte(A0, C0h, 1) : __builtin_amdgcn_alignbyte(C0h, C0l, 3);
+        uint32_t S1l = P0 ? __builtin_amdgcn_alignbyte(C1l, A1, 3) : __builtin_amdgcn_alignbyte(C1h, C1l, 1);
+        uint32_t S1h = P0 ? __builtin_amdgcn_alignbyte(C1h, C1l, 3) : __builtin_amdgcn_alignbyte(A1, C1h, 1);
+        if (SEAM) {
+            const uint64_t nxa = (Na & 0xFFull) << c.sh_next, pva = (Na >> c.sh_prev) & 0xFFull;
+            const uint64_t nxb = (Nb & 0xFFull) << c.sh_next, pvb = (Nb >> c.sh_prev) & 0xFFull;
+            const uint64_t Sa = P0 ? ((R1 >> 8) | nxa) : ((R1 << 8) | pva);
+            const uint64_t Sb = P0 ? ((R2 << 8) | pvb) : ((R2 >> 8) | nxb);
+            S0l = (uint32_t)Sa; S0h = (uint32_t)(Sa >> 32);
+            S1l = (uint32_t)Sb; S1h = (uint32_t)(Sb >> 32);
+        }
+        // R1 + R2 is shared by both rows' vertical+centre sums
+        const uint32_t ml = C0l + C1l, mh = C0h + C1h;
+        return PairCounts{(uint32_t)R0 + ml + S0l, (uint32_t)(R0 >> 32) + mh + S0h, (uint32_t)R3 + ml + S1l, (uint32_t)(R3 >> 32) + mh + S1h};
+    };
+    PairCounts n;
+    PairThr T;
     const u32x4 w0 = philox_vk(cq, (uint32_t)rga, c.rmask, y0, hs, c.tag_hi, K);
-    const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.rmask, y0, hs, c.tag_hi, K);
-    __builtin_amdgcn_sched_barrier(0);  // ... and their first use stays below
-    const uint32_t C0l = (uint32_t)R1, C0h = (uint32_t)(R1 >> 32), C1l = (uint32_t)R2, C1h = (uint32_t)(R2 >> 32);
-    // horizontal neighbours: compact bytes (j, j+1) when the parity is 1, (j-1, j) when it is 0
-    uint32_t S0l = P0 ? __builtin_amdgcn_alignbyte(C0h, C0l, 1) : __builtin_amdgcn_alignbyte(C0l, A0, 3);
-    uint32_t S0h = P0 ? __builtin_amdgcn_alignbyte(A0, C0h, 1) : __builtin_amdgcn_alignbyte(C0h, C0l, 3);
-    uint32_t S1l = P0 ? __builtin_amdgcn_alignbyte(C1l, A1, 3) : __builtin_amdgcn_alignbyte(C1h, C1l, 1);
-    uint32_t S1h = P0 ? __builtin_amdgcn_alignbyte(C1h, C1l, 3) : __builtin_amdgcn_alignbyte(A1, C1h, 1);
-    if (SEAM) {
-        const uint64_t nxa = (Na & 0xFFull) << c.sh_next, pva = (Na >> c.sh_prev) & 0xFFull;
-        const uint64_t nxb = (Nb & 0xFFull) << c.sh_next, pvb = (Nb >> c.sh_prev) & 0xFFull;
-        const uint64_t Sa = P0 ? ((R1 >> 8) | nxa) : ((R1 << 8) | pva);
-        const uint64_t Sb = P0 ? ((R2 << 8) | pvb) : ((R2 >> 8) | nxb);
-        S0l = (uint32_t)Sa; S0h = (uint32_t)(Sa >> 32);
-        S1l = (uint32_t)Sb; S1h = (uint32_t)(Sb >> 32);
+    if constexpr (EARLY) {
+        __builtin_amdgcn_sched_barrier(0);
+        n = counts();
+        T = pair_thresholds(n, c.tbl2);
+        __builtin_amdgcn_sched_barrier(0);
     }
-    // R1 + R2 is shared by both rows' vertical+centre sums
-    const uint32_t ml = C0l + C1l, mh = C0h + C1h;
-    const uint32_t cnt0l = (uint32_t)R0 + ml + S0l, cnt0h = (uint32_t)(R0 >> 32) + mh + S0h;
-    const uint32_t cnt1l = (uint32_t)R3 + ml + S1l, cnt1h = (uint32_t)(R3 >> 32) + mh + S1h;
+    const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.rmask, y0, hs, c.tag_hi, K);
+    __builtin_amdgcn_sched_barrier(0);
+    if constexpr (!EARLY) n = counts();
+    const uint32_t cnt0l = n.c0l, cnt0h = n.c0h, cnt1l = n.c1l, cnt1h = n.c1h;
     u32x4 d0, d1;
     uint32_t edge_a = 0, edge_b = 0;
     if (OPEN) {
@@ -362,8 +417,8 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
         edge_a = (ea ? 1u : 0u) | (la ? 2u : 0u) | (ra ? 4u : 0u) | (c.r_slot << 4);
         edge_b = (eb ? 1u : 0u) | (lb ? 2u : 0u) | (rb ? 4u : 0u) | (c.r_slot << 4);
     } else {
-        d0 = compare_octet(w0, cnt0l, cnt0h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
-        d1 = compare_octet(w1, cnt1l, cnt1h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
+        d0 = compare_octet_thr(w0, T.t);
+        d1 = compare_octet_thr(w1, T.t + 4);
     }
     const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
     if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
@@ -451,17 +506,29 @@ static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const Ph
     __builtin_amdgcn_sched_barrier(0);
     int rga = rg, rgb = rg + 1;
     if (EDGE) edge_rows<NO>(c, to_wrap, rg, rga, rgb);
+    constexpr bool EARLY = !OPEN;  // as in pair_step
+    auto counts = [&]() -> PairCounts {
+        const uint32_t Sa = SEAM ? (P0 ? nib_shift_next_seam(R1, A0, c.sh_next) : nib_shift_prev_seam(R1, A0, c.sh_prev))
+                                 : (P0 ? nib_shift_next(R1, A0) : nib_shift_prev(R1, A0));
+        const uint32_t Sb = SEAM ? (P0 ? nib_shift_prev_seam(R2, A1, c.sh_prev) : nib_shift_next_seam(R2, A1, c.sh_next))
+                                 : (P0 ? nib_shift_prev(R2, A1) : nib_shift_next(R2, A1));
+        const uint32_t mid = R1 + R2;  // shared by both rows' vertical + centre sums
+        const uint32_t cnt0 = R0 + mid + Sa, cnt1 = R3 + mid + Sb;
+        return PairCounts{cnt0 & 0x0F0F0F0Fu, (cnt0 >> 4) & 0x0F0F0F0Fu, cnt1 & 0x0F0F0F0Fu, (cnt1 >> 4) & 0x0F0F0F0Fu};
+    };
+    PairCounts n;
+    PairThr T;
     const u32x4 w0 = philox_vk(cq, (uint32_t)rga, c.rmask, y0, hs, c.tag_hi, K);
+    if constexpr (EARLY) {
+        __builtin_amdgcn_sched_barrier(0);
+        n = counts();
+        T = pair_thresholds(n, c.tbl2);
+        __builtin_amdgcn_sched_barrier(0);
+    }
     const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.rmask, y0, hs, c.tag_hi, K);
     __builtin_amdgcn_sched_barrier(0);
-    const uint32_t Sa = SEAM ? (P0 ? nib_shift_next_seam(R1, A0, c.sh_next) : nib_shift_prev_seam(R1, A0, c.sh_prev))
-                             : (P0 ? nib_shift_next(R1, A0) : nib_shift_prev(R1, A0));
-    const uint32_t Sb = SEAM ? (P0 ? nib_shift_prev_seam(R2, A1, c.sh_prev) : nib_shift_next_seam(R2, A1, c.sh_next))
-                             : (P0 ? nib_shift_prev(R2, A1) : nib_shift_next(R2, A1));
-    const uint32_t mid = R1 + R2;  // shared by both rows' vertical + centre sums
-    const uint32_t cnt0 = R0 + mid + Sa, cnt1 = R3 + mid + Sb;
-    const uint32_t cnt0l = cnt0 & 0x0F0F0F0Fu, cnt0h = (cnt0 >> 4) & 0x0F0F0F0Fu;
-    const uint32_t cnt1l = cnt1 & 0x0F0F0F0Fu, cnt1h = (cnt1 >> 4) & 0x0F0F0F0Fu;
+    if constexpr (!EARLY) n = counts();
+    const uint32_t cnt0l = n.c0l, cnt0h = n.c0h, cnt1l = n.c1l, cnt1h = n.c1h;
     u32x4 d0, d1;
     uint32_t edge_a = 0, edge_b = 0;
     if (OPEN) {  // as in pair_step: the counts are bytes by now, the degree-3 / degree-2 patches are the byte form's
@@ -472,8 +539,8 @@ static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const Ph
         edge_a = (ea ? 1u : 0u) | (la ? 2u : 0u) | (ra ? 4u : 0u) | (c.r_slot << 4);
         edge_b = (eb ? 1u : 0u) | (lb ? 2u : 0u) | (rb ? 4u : 0u) | (c.r_slot << 4);
     } else {
-        d0 = compare_octet(w0, cnt0l, cnt0h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
-        d1 = compare_octet(w1, cnt1l, cnt1h, c.tblH0, c.tblH1, c.tblL0, c.tblL1);
+        d0 = compare_octet_thr(w0, T.t);
+        d1 = compare_octet_thr(w1, T.t + 4);
     }
     const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
     if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
@@ -588,12 +655,21 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     // SIMDs (+5 % on 4096^2 against the smallest lane count that reaches the same iteration count).
     constexpr int RL = RLMAX;
     using E = typename std::conditional<NIB, uint32_t, uint64_t>::type;  // one octet of a colour plane
+    // the pair table of the periodic compare (pair_thresholds) at the start of the workgroup's LDS, the guard octet behind it
+    uint64_t* const guard = lds + TBL2_OCTETS;
     // the colour planes, interleaved row by row (see TilePlanes): plane 0 of row 0 starts behind the guard octet
-    const TilePlanes<E, NO> P{reinterpret_cast<E*>(lds + 1)};
+    const TilePlanes<E, NO> P{reinterpret_cast<E*>(guard + 1)};
     // one spare row behind the planes: "octet NO" of plane 1 of the last row is read there (rounded up to the uint64 grid)
     uint64_t* s_thr = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(P.base + 2 * TR * NO + NO + 1) + 7u) & ~(uintptr_t)7u);
     const int tid = threadIdx.x;
     if (tid < 25) s_thr[tid] = p.thr[tid];
+    if (!OPEN && tid < 25) {  // the top 16 bits of the degree-4 thresholds, as pack_thresholds makes them for the byte tables
+        auto t16 = [&](int up) {
+            const uint64_t thi = p.thr[4 * 5 + up] >> 16;
+            return (uint32_t)(thi > 65535u ? 65535u : thi) ^ 0x8000u;
+        };
+        reinterpret_cast<uint32_t*>(lds)[tid] = t16(tid % 5) | (t16(tid / 5) << 16);
+    }
 
     const int q0 = tx * WO + p.q_shift, r0 = p.r_begin + row_off, Rb = r0 - 2 * k;
 
@@ -676,8 +752,8 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     c.wrap_tr = (int)(p.total_rows - rg0);
     asm volatile("v_mov_b32 %0, %1" : "=v"(c.rmask) : "s"(holds_wrap && !edge ? (uint32_t)p.total_rows - 1u : 0xFFFFFFFFu));
     c.tag_hi = p.tag_hi; c.tag_lo = p.tag_lo; c.k0 = p.k0; c.k1 = p.k1;
-    // the threshold byte tables live in VGPRs: v_perm_b32 may read only one SGPR, so SGPR tables cost a v_mov per use
-    c.tblH0 = p.tblH0; c.tblH1 = p.tblH1; c.tblL0 = p.tblL0; c.tblL1 = p.tblL1;
+    c.tbl2 = TBL2_LDS_ADDR;
+    c.tblH0 = c.tblH1 = c.tblL0 = c.tblL1 = 0;
     c.t3H0 = p.t3H0; c.t3H1 = p.t3H1; c.t3L0 = p.t3L0; c.t3L1 = p.t3L1;
     c.last_row = (int)p.total_rows - 1;
     c.lft = OPEN && cqi == 0;
@@ -701,10 +777,13 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     int w0 = (q0 - 1) % p.nchunks;
     if (w0 < 0) w0 += p.nchunks;
     const bool seam = ragged && (w0 == 0 || w0 + NO - 1 >= p.nchunks - 1);
-    asm volatile("v_mov_b32 %0, %1" : "=v"(c.tblH0) : "s"(p.tblH0));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(c.tblH1) : "s"(p.tblH1));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(c.tblL0) : "s"(p.tblL0));
-    asm volatile("v_mov_b32 %0, %1" : "=v"(c.tblL1) : "s"(p.tblL1));
+    if constexpr (OPEN) {
+        // the threshold byte tables live in VGPRs: v_perm_b32 may read only one SGPR, so SGPR tables cost a v_mov per use
+        asm volatile("v_mov_b32 %0, %1" : "=v"(c.tblH0) : "s"(p.tblH0));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(c.tblH1) : "s"(p.tblH1));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(c.tblL0) : "s"(p.tblL0));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(c.tblL1) : "s"(p.tblL1));
+    }
 
     const int n_gen = RESIDENT ? R->n_gen : 1;
     long long tl0 = 0, tl[4] = {0, 0, 0, 0};
@@ -718,7 +797,7 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     }
     // RESIDENT: "a neighbour wait expired in this workgroup" -- kept in the guard octet in front of plane 0 (only ever read
     // as "octet -1" padding of row 0): a static __shared__ word would push a 160 KB workgroup past the CU's LDS
-    volatile int& s_fail = *reinterpret_cast<volatile int*>(lds);
+    volatile int& s_fail = *reinterpret_cast<volatile int*>(guard);
     if (RESIDENT && tid == 0) s_fail = 0;
 
     // ---- the strip exchange between generations (RESIDENT).  Only colour plane 1 travels: a generation starts with the
@@ -783,7 +862,9 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
         // a thread is issued before the first is looked at, and unconditionally: a neighbour index always names a real
         // tile, a missing neighbour's value is neither checked nor stored.
         constexpr int FI = (2 * 8 * NO + THREADS - 1) / THREADS;   // k <= 8
-        constexpr int TH_MAX = 160 * 1024 / (int)sizeof(E) / (2 * NO) - 32;  // tallest (stretched slab) tile whose planes fit the CU's LDS
+        // tallest (stretched slab) tile whose planes fit the CU's LDS (an upper bound: tile_lds_bytes also counts the pair table,
+        // the guard octet, the spare row and the tie path's thresholds)
+        constexpr int TH_MAX = 160 * 1024 / (int)sizeof(E) / (2 * NO) - 32;
         constexpr int SI = (TH_MAX + THREADS - 1) / THREADS;
         const uint64_t* au[FI];
         const uint64_t* ad[FI];
@@ -963,10 +1044,10 @@ struct TileVariant {
     int per_cu;                      // workgroups of this shape one CU is meant to hold (tiles per round; LDS share of a stretched tile)
 };
 
-// LDS of one workgroup: guard octet, two colour planes of TR x NO octets (+ one spare row), 25 thresholds
+// LDS of one workgroup: pair table, guard octet, two colour planes of TR x NO octets (+ one spare row), 25 thresholds
 size_t tile_lds_bytes(const TileVariant& tv, int TR) {
     const size_t es = tv.nib ? 4 : 8, NO = (size_t)tv.WO + 2;
-    return 8 + (((size_t)2 * TR * NO + NO + 1) * es + 7) / 8 * 8 + 8 + 25 * sizeof(uint64_t);
+    return 8 * TBL2_OCTETS + 8 + (((size_t)2 * TR * NO + NO + 1) * es + 7) / 8 * 8 + 8 + 25 * sizeof(uint64_t);
 }
 // the tile shapes the chooser (plan_call) can reach.  Round 1's table had 32 entries, 24 of them reachable only through
 // the TSU_TILE_VARIANT development switch; numbers quoted in profiles/r01_* map as 6 -> 0, 8 -> 1, 9 -> 2, 22 -> 3, 23 -> 4,
