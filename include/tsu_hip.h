@@ -359,6 +359,10 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * _hip.SPARSE_BATCH_SIGNATURES in Python. */
 #include "tsu_hip_sparse_batch.h"
 
+/* K7 / K8: a probe of the two numbers of the heat-bath kernels' fp32 screen, for tests of its error bound: declared in
+ * tsu_hip_probe.h, which this header includes; its prototypes are _hip.PROBE_SIGNATURES in Python. */
+#include "tsu_hip_probe.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -37,8 +37,11 @@ __device__ __forceinline__ uint64_t exact_thr(double f, double T) {
 // t = p32 2^16 is compared with the hi16 uniform: u in [hi 2^16, hi 2^16 + 65535] is below thr for sure when
 // t - dt >= hi + 1 and not below it when t + dt <= hi, dt a bound of |t - thr / 2^16|.  With u = 2^-24, S = the sum of the
 // |terms|, A = 2 S / T and n fp32 additions in the field (the products J s are exact, s = +-1):  the additions err by
-// <= n u S; times fl(2 / T) adds 2 u |x|: |dx| <= (n + 3) u A.  __expf (v_exp_f32 on x log2 e) errs by <= (|x| + 2) u
-// relative, so e = exp(-x) by <= ((n + 5) A + 4) u relative (|x| <= A); p = rcp(1 + e) moves by p (1 - p) <= 1/4 of that plus
+// <= n u S; times fl(2 / T) adds 2 u |x|: |dx| <= (n + 3) u A.  __expf(-x) is v_exp_f32 of fl(-x fl32(log2 e)): the constant
+// is 0.23 u short and the product rounds by u, 1.23 |x| u relative after the exponential, and v_exp_f32 adds 1 ulp <= 2 u:
+// (1.23 |x| + 2) u, with 3 u for the add and rcp.  The device stays inside both over the fp32 range (tsu_probe_screen,
+// tests/test_screen_gpu.py, profiles/screen_probe.txt; it exceeds (|x| + 2) u, which stood here before).  So e = exp(-x) errs by
+// <= ((n + 4.23) A + 2) u <= ((n + 5) A + 4) u relative (|x| <= A); p = rcp(1 + e) moves by p (1 - p) <= 1/4 of that plus
 // 3 u p of its own rounding: |dp| <= ((n + 5) A / 4 + 4) u + 3 u.  The +-20 clamp of the exact p adds 2.1e-9 = 2^-28.9, and
 // the rounding of thr half a unit of 2^-32.  In units of 2^-16: dt <= (((n + 5) A / 4 + 7) + 2^-4.9) / 256 + 2^-17.
 //   K7, five terms, n = 4: dt <= (2.25 A + 7.04) / 256 + 2^-17 < (A + 4) / 64 = the margin below, a factor >= 1.7 to spare;
@@ -46,6 +49,8 @@ __device__ __forceinline__ uint64_t exact_thr(double f, double T) {
 //   spare (4 / 2.75 as A grows, 16 / 7.05 at A = 0).  The comparisons themselves round h + 1 + m and h - m to fp32 (half an
 //   ulp at 2^16: 1 / 256) and A, m carry a relative (n + 2) u: both far inside what is to spare ((1.25 A + 8.9) / 256).
 // Non-finite A or t (huge disorder, tiny T) fail both comparisons and go to the exact branch.
+// The four lines for x, A, t, m are restated in probe.hip (tsu_probe_screen), word for word: tests/test_screen_cpu.py compares the
+// two texts.  A helper shared by both changed the instruction order of the sweeps, so the lines stay here as they were.
 __device__ __forceinline__ int screen(float f32, float a32, float c32, uint32_t hi) {
     const float x = f32 * c32;
     const float A = a32 * fabsf(c32);

@@ -256,6 +256,11 @@ SPARSE_BATCH_SIGNATURES = {
     "tsu_sparse_batch_launch_count": (C.c_int, [_vp, _u64p]),
 }
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_probe.h (the header tsu_hip.h includes) one to one
+PROBE_SIGNATURES = {
+    "tsu_probe_screen": (C.c_int, [_vp, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p]),
+}
+
 _lib = None
 
 
@@ -274,7 +279,8 @@ def load_library():
         raise HipUnavailableError(f"cannot load {LIB_PATH}: {e}") from e
     for name, (res, args) in (list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items())
                               + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())
-                              + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())):
+                              + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())
+                              + list(PROBE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -383,6 +389,15 @@ def ising2d_thresholds(J, h, T, mode=MODE_PHYSICAL):
     if rc != TSU_OK:
         raise ValueError("Temperature must be positive" if not T > 0 else "invalid threshold arguments")
     return t
+
+
+def probe_screen(f32, a32, c32, ctx=None):
+    """(t, m) of the K7 / K8 screen as the device computes them (tsu_probe_screen): float32 arrays of the inputs' common shape."""
+    ctx = ctx or Context.default()
+    f, a, c = (np.ascontiguousarray(v, dtype=np.float32) for v in np.broadcast_arrays(f32, a32, c32))
+    t, m = np.empty_like(f), np.empty_like(f)
+    ctx.check(ctx.lib.tsu_probe_screen(ctx.h, f.size, _ptr(f, _f32p), _ptr(a, _f32p), _ptr(c, _f32p), _ptr(t, _f32p), _ptr(m, _f32p)))
+    return t, m
 
 
 def cluster_threshold(J, T):
