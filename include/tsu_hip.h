@@ -363,6 +363,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * tsu_hip_probe.h, which this header includes; its prototypes are _hip.PROBE_SIGNATURES in Python. */
 #include "tsu_hip_probe.h"
 
+/* K8: ghost-spin Swendsen-Wang steps, the cluster steps of the 3-D handle in a field (tsu_ising3d_cluster_sweep_field /
+ * _cluster_sweep_field_batch): declared in tsu_hip_cluster_field.h, which this header includes; its prototypes are
+ * _hip.CLUSTER_FIELD_SIGNATURES in Python. */
+#include "tsu_hip_cluster_field.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -24,6 +24,15 @@
 // Nothing waits on another workgroup.  Every union / find loop draws on a per-lane budget; when it runs out the kernel raises
 // h_err = 2 and gives up on that bond instead of spinning (the next synchronising call of the handle reports it); on the small
 // route the lattice then keeps the spins it had before the call.
+// In a field (tsu_ising3d_cluster_sweep_field, the <true> instantiations of the four kernels): every site has one more bond, to a
+// ghost spin fixed at +1:
+//   ghost   the bond of site i with stored fp32 field h_i is active iff h_i s_i > 0 and u_g < thr(|h_i|) (the same thr, 64-bit
+//           compare; h_i = 0 is never active), u_g = word c & 3 of Philox(c >> 2, rho, t, TAG_SW_GHOST | rep << 8)
+//   frozen  a component with an active ghost bond keeps its spins and draws no coin; every other one flips by its root's coin
+// The ghost is label -1 (uf_dev.h, ufg_find / ufg_union): an index below every site, so the min-index union-find takes it as it
+// is.  k8_sw_local writes -1 as the global label of a site whose tile root is frozen, k8_sw_merge takes -1 on either side,
+// k8_sw_resolve reads a negative root as "no flip".  No extra array, LDS or launch; with h = 0 everywhere the spins are those of
+// the zero-field step.  The <false> instantiations are the zero-field kernels as they were.
 // No fp32 screen of u_b: only satisfied bonds (J s s' > 0) reach the float64 expm1, and the kernels are bound by the LDS / L2
 // atomics of the union-find, not by it.
 #include <math.h>
@@ -49,6 +58,9 @@ __device__ __forceinline__ bool bond3_on(float J, int sa, int sb, uint32_t u, do
     return (uint64_t)u < (uint64_t)floor(p * 4294967296.0);
 }
 
+// h s > 0: the ghost bond of the site can be active (bond3_on(h, s, 1, u_g, T) then decides)
+__device__ __forceinline__ bool ghost_sat(float h, int s) { return ((h > 0.0f) - (h < 0.0f)) * s > 0; }
+
 __device__ __forceinline__ uint32_t word_of(const u32x4& w, int m) { return m == 0 ? w.x : (m == 1 ? w.y : (m == 2 ? w.z : w.w)); }
 
 // ---------------------------------------------------------------- one workgroup per lattice
@@ -57,10 +69,25 @@ struct Sw3Item {
     const float* jr;
     const float* jd;
     const float* jl;
+    const float* h;  // read by the ghost kernels only
     double T;
-    uint32_t k0, k1, tag_bond, tag_layer, tag_flip, step0;
+    uint32_t k0, k1, tag_bond, tag_layer, tag_flip, tag_ghost, step0;
 };
 
+// the union / find of a kernel: with a ghost, label -1 is legal
+template <bool GHOST, int SCOPE>
+__device__ __forceinline__ bool sw_union(int* L, int a, int b, int& budget) {
+    if constexpr (GHOST) return ufg_union<SCOPE>(L, a, b, budget);
+    else return uf_union<SCOPE>(L, a, b, budget);
+}
+
+template <bool GHOST, int SCOPE>
+__device__ __forceinline__ int sw_find(int* L, int x, int& budget) {
+    if constexpr (GHOST) return ufg_find<SCOPE>(L, x, budget);
+    else return uf_find<SCOPE>(L, x, budget);
+}
+
+template <bool GHOST>
 __global__ __launch_bounds__(kMaxThreads) void k8_sw_small(const Sw3Item* __restrict__ items, Sw3Item one, int depth, int rows, int cols,
                                                            long long pitch, int pz, int pr, int pc, int n_steps, int* err) {
     extern __shared__ int s_lab[];
@@ -86,6 +113,8 @@ __global__ __launch_bounds__(kMaxThreads) void k8_sw_small(const Sw3Item* __rest
             const u32x4 wl = tsu_philox((uint32_t)cp >> 1, (uint32_t)rho, t, it.tag_layer, it.k0, it.k1);
             const int rd = r + 1 < rows ? rho + 1 : (pr ? z * rows : -1);      // global row of the down neighbour
             const int rf = z + 1 < depth ? rho + rows : (pz ? r : -1);         // ... of the layer neighbour
+            u32x4 wg = {0u, 0u, 0u, 0u};  // the ghost bonds' block, drawn once a site of the pair has h s > 0
+            bool have_wg = false;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const int c = 2 * cp + j;
@@ -93,19 +122,29 @@ __global__ __launch_bounds__(kMaxThreads) void k8_sw_small(const Sw3Item* __rest
                 const int i = rho * cols + c, si = s_spin[i];
                 const long long g = (long long)rho * pitch + c;
                 const int cr = c + 1 < cols ? c + 1 : (pc ? 0 : -1);
+                const float h = GHOST ? it.h[g] : 0.0f;  // read ahead of the unions, whose atomics it would otherwise wait behind
                 if (cr >= 0 && bond3_on(it.jr[g], si, s_spin[rho * cols + cr], j ? w.z : w.x, it.T))
-                    if (!uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, rho * cols + cr, budget)) s_bad = 1;
+                    if (!sw_union<GHOST, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, rho * cols + cr, budget)) s_bad = 1;
                 if (rd >= 0 && bond3_on(it.jd[g], si, s_spin[rd * cols + c], j ? w.w : w.y, it.T))
-                    if (!uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, rd * cols + c, budget)) s_bad = 1;
+                    if (!sw_union<GHOST, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, rd * cols + c, budget)) s_bad = 1;
                 if (rf >= 0 && bond3_on(it.jl[g], si, s_spin[rf * cols + c], word_of(wl, c & 3), it.T))
-                    if (!uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, rf * cols + c, budget)) s_bad = 1;
+                    if (!sw_union<GHOST, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, rf * cols + c, budget)) s_bad = 1;
+                if constexpr (GHOST) {
+                    if (ghost_sat(h, si)) {
+                        if (!have_wg) wg = tsu_philox((uint32_t)cp >> 1, (uint32_t)rho, t, it.tag_ghost, it.k0, it.k1);
+                        have_wg = true;
+                        if (bond3_on(h, si, 1, word_of(wg, c & 3), it.T))
+                            if (!ufg_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, -1, budget)) s_bad = 1;
+                    }
+                }
             }
         }
         __syncthreads();
         for (int i = tid; i < n; i += nt) {
             budget = kBudget;
-            const int root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, budget);
+            const int root = sw_find<GHOST, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, budget);
             if (budget < 0) s_bad = 1;
+            if (GHOST && root < 0) continue;  // frozen: no coin
             const int rr = root / cols, rc = root - rr * cols;
             if (flip_bit(rr, rc, t, it.tag_flip, it.k0, it.k1)) s_spin[i] = (int8_t)-s_spin[i];
         }
@@ -128,20 +167,23 @@ struct Sw3Params {
     const float* jr;
     const float* jd;
     const float* jl;
-    int* labels;  // depth * rows * cols
+    const float* h;  // read by the ghost kernels only
+    int* labels;  // depth * rows * cols; -1 (ghost kernels only): the site's component is frozen
     long long pitch;
     int depth, rows, cols;
     int pz, pr, pc;
     int tz, tr, tc;  // tile shape (tc even: a right / down Philox block never straddles two tiles)
     int nz, nr, nc;  // tiles per axis
     double T;
-    uint32_t k0, k1, tag_bond, tag_layer, tag_flip, t;
+    uint32_t k0, k1, tag_bond, tag_layer, tag_flip, tag_ghost, t;
     int* err;
 };
 
 // tile blockIdx.x (row-major over nz x nr x nc) of tz x tr x tc sites; bonds with both ends in the tile, none across its faces
 // or a wrap.  LDS: tz*tr*tc int32 labels (tile-local, row-major: the same order as the global indices inside a tile) and as many
-// spins.  Writes the global index of every site's tile root.
+// spins.  Writes the global index of every site's tile root; GHOST: the ghost bond of every site of the tile too, and -1 where the
+// tile root is frozen.
+template <bool GHOST>
 __global__ __launch_bounds__(kMaxThreads) void k8_sw_local(Sw3Params p) {
     extern __shared__ int s_lab[];
     const int TZ = p.tz, TR = p.tr, TC = p.tc, n = TZ * TR * TC;
@@ -166,18 +208,29 @@ __global__ __launch_bounds__(kMaxThreads) void k8_sw_local(Sw3Params p) {
         const long long rho = (long long)(z0 + lz) * p.rows + r0 + lr;
         const u32x4 w = tsu_philox((uint32_t)(c0 + lc0) >> 1, (uint32_t)rho, p.t, p.tag_bond, p.k0, p.k1);
         const u32x4 wl = tsu_philox((uint32_t)(c0 + lc0) >> 2, (uint32_t)rho, p.t, p.tag_layer, p.k0, p.k1);
+        u32x4 wg = {0u, 0u, 0u, 0u};
+        bool have_wg = false;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int lc = lc0 + j;
             if (lc >= tc) break;
             const int i = (lz * TR + lr) * TC + lc, si = s_spin[i];
             const long long g = rho * p.pitch + c0 + lc;
+            const float h = GHOST ? p.h[g] : 0.0f;  // read ahead of the unions, whose atomics it would otherwise wait behind
             if (lc + 1 < tc && bond3_on(p.jr[g], si, s_spin[i + 1], j ? w.z : w.x, p.T))
-                bad |= !uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + 1, budget);
+                bad |= !sw_union<GHOST, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + 1, budget);
             if (lr + 1 < tr && bond3_on(p.jd[g], si, s_spin[i + TC], j ? w.w : w.y, p.T))
-                bad |= !uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + TC, budget);
+                bad |= !sw_union<GHOST, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + TC, budget);
             if (lz + 1 < tz && bond3_on(p.jl[g], si, s_spin[i + TR * TC], word_of(wl, (c0 + lc) & 3), p.T))
-                bad |= !uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + TR * TC, budget);
+                bad |= !sw_union<GHOST, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + TR * TC, budget);
+            if constexpr (GHOST) {
+                if (ghost_sat(h, si)) {
+                    if (!have_wg) wg = tsu_philox((uint32_t)(c0 + lc0) >> 2, (uint32_t)rho, p.t, p.tag_ghost, p.k0, p.k1);
+                    have_wg = true;
+                    if (bond3_on(h, si, 1, word_of(wg, (c0 + lc) & 3), p.T))
+                        bad |= !ufg_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, -1, budget);
+                }
+            }
         }
     }
     __syncthreads();
@@ -185,16 +238,19 @@ __global__ __launch_bounds__(kMaxThreads) void k8_sw_local(Sw3Params p) {
         const int lz = i / (TR * TC), rem = i - lz * TR * TC, lr = rem / TC, lc = rem - lr * TC;
         if (lz >= tz || lr >= tr || lc >= tc) continue;
         budget = kBudget;
-        const int root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, budget);
+        const int root = sw_find<GHOST, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, budget);
         bad |= budget < 0;
         const int rz = root / (TR * TC), rrem = root - rz * TR * TC, rr = rrem / TC, rc = rrem - rr * TC;
-        p.labels[((long long)(z0 + lz) * p.rows + r0 + lr) * p.cols + c0 + lc] = ((z0 + rz) * p.rows + r0 + rr) * p.cols + c0 + rc;
+        const int label = ((z0 + rz) * p.rows + r0 + rr) * p.cols + c0 + rc;
+        p.labels[((long long)(z0 + lz) * p.rows + r0 + lr) * p.cols + c0 + lc] = (GHOST && root < 0) ? -1 : label;
     }
     if (bad) raise_err(p.err);
 }
 
 // lanes [0, sc D R): right bonds of the column seams (seam k < nc - 1 at column (k + 1) tc - 1, the last one of a periodic axis at
-// column cols - 1, wrapping to 0); then sr D C lanes for the down bonds of the row seams; then sz R C lanes for the layer bonds
+// column cols - 1, wrapping to 0); then sr D C lanes for the down bonds of the row seams; then sz R C lanes for the layer bonds.
+// GHOST: either label may be -1 (a frozen tile root); joining it with a free root freezes that root's tree
+template <bool GHOST>
 __global__ __launch_bounds__(256) void k8_sw_merge(Sw3Params p, int sc, int sr, int sz) {
     const long long lane = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long nrows = (long long)p.depth * p.rows;
@@ -242,11 +298,13 @@ __global__ __launch_bounds__(256) void k8_sw_merge(Sw3Params p, int sc, int sr, 
     if (!bond3_on(J, sa, sb, u, p.T)) return;
     int budget = kBudget;
     const int a = p.labels[rho * p.cols + c], b = p.labels[rho2 * p.cols + c2];
-    if (!uf_union<__HIP_MEMORY_SCOPE_AGENT>(p.labels, a, b, budget)) raise_err(p.err);
+    if (!sw_union<GHOST, __HIP_MEMORY_SCOPE_AGENT>(p.labels, a, b, budget)) raise_err(p.err);
 }
 
 // one lane per 4 sites of a global row (one 4-byte load and store; the pad bytes beyond cols are 0 and stay 0): the root of each
-// site, the root's coin (one Philox block per distinct root of the lane), the spin rewritten
+// site, the root's coin (one Philox block per distinct root of the lane), the spin rewritten.  GHOST: a chain that ends in -1 is a
+// frozen component: no coin, the spin stays
+template <bool GHOST>
 __global__ __launch_bounds__(256) void k8_sw_resolve(Sw3Params p, int quads) {
     const long long lane = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long rho = lane / quads;
@@ -261,14 +319,20 @@ __global__ __launch_bounds__(256) void k8_sw_resolve(Sw3Params p, int quads) {
         if (c0 + j >= p.cols) break;
         const long long g = rho * p.cols + c0 + j;
         int x = p.labels[g], budget = kBudget;
-        for (int y = p.labels[x]; y != x; y = p.labels[x]) {
-            x = y;
-            if (--budget < 0) {
-                bad = true;
-                break;
+        if (!GHOST || x >= 0) {
+            for (int y = p.labels[x]; y != x; y = p.labels[x]) {
+                x = y;
+                if (GHOST && x < 0) break;
+                if (--budget < 0) {
+                    bad = true;
+                    break;
+                }
             }
         }
-        if (x != last) {
+        if (GHOST && x < 0) {
+            last = x;
+            last_flip = false;
+        } else if (x != last) {
             const int rr = x / p.cols, rc = x - rr * p.cols;
             last = x;
             last_flip = flip_bit(rr, rc, p.t, p.tag_flip, p.k0, p.k1);
@@ -330,12 +394,14 @@ Sw3Item make_item(const tsu_ising3d* L, double T, uint64_t seed, uint32_t step0,
     it.jr = L->d_dis;
     it.jd = L->d_dis + plane;
     it.jl = L->d_dis + 2 * plane;
+    it.h = L->d_dis + 3 * plane;  // zeros when no field was given
     it.T = T;
     it.k0 = (uint32_t)seed;
     it.k1 = (uint32_t)(seed >> 32);
     it.tag_bond = TSU_TAG_SW_BOND | (replica << 8);
     it.tag_layer = TSU_TAG_SW_LAYER | (replica << 8);
     it.tag_flip = TSU_TAG_SW_FLIP | (replica << 8);
+    it.tag_ghost = TSU_TAG_SW_GHOST | (replica << 8);
     it.step0 = step0;
     return it;
 }
@@ -345,6 +411,7 @@ int threads_for(long long work_items) {
     return (int)(t < kMaxThreads ? t : kMaxThreads);
 }
 
+template <bool GHOST>
 int run_small(tsu_ising3d* const* lats, int n, const Sw3Item* items, int n_steps) {
     tsu_ising3d* L0 = lats[0];
     tsu_ctx* ctx = L0->ctx;
@@ -352,7 +419,7 @@ int run_small(tsu_ising3d* const* lats, int n, const Sw3Item* items, int n_steps
     int rc = ensure_err(L0, &d_err);
     if (rc != TSU_OK) return rc;
     const size_t lds = (size_t)sites_of(L0) * 5;
-    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)k8_sw_small, (int)lds));
+    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)k8_sw_small<GHOST>, (int)lds));
     const Sw3Item* d_items = nullptr;
     if (n > 1) {
         const size_t bytes = (size_t)n * sizeof(Sw3Item);
@@ -363,13 +430,14 @@ int run_small(tsu_ising3d* const* lats, int n, const Sw3Item* items, int n_steps
         d_items = (const Sw3Item*)L0->d_sw_batch;
     }
     const int threads = threads_for((long long)L0->depth * L0->rows * ((L0->cols + 1) / 2));
-    hipLaunchKernelGGL(k8_sw_small, dim3((unsigned)n), dim3((unsigned)threads), lds, ctx->stream, d_items, items[0], L0->depth, L0->rows,
+    hipLaunchKernelGGL(k8_sw_small<GHOST>, dim3((unsigned)n), dim3((unsigned)threads), lds, ctx->stream, d_items, items[0], L0->depth, L0->rows,
                        L0->cols, (long long)L0->pitch, L0->pz, L0->pr, L0->pc, n_steps, d_err);
     TSU_HIP_TRY(ctx, hipGetLastError());
     for (int i = 0; i < n; ++i) lats[i]->sw_launches += 1;
     return TSU_OK;
 }
 
+template <bool GHOST>
 int run_tiles(tsu_ising3d* L, const Sw3Item& it, int n_steps) {
     tsu_ctx* ctx = L->ctx;
     Tile t;
@@ -393,6 +461,7 @@ int run_tiles(tsu_ising3d* L, const Sw3Item& it, int n_steps) {
     p.jr = it.jr;
     p.jd = it.jd;
     p.jl = it.jl;
+    p.h = it.h;
     p.labels = L->d_labels;
     p.pitch = (long long)L->pitch;
     p.depth = L->depth;
@@ -413,6 +482,7 @@ int run_tiles(tsu_ising3d* L, const Sw3Item& it, int n_steps) {
     p.tag_bond = it.tag_bond;
     p.tag_layer = it.tag_layer;
     p.tag_flip = it.tag_flip;
+    p.tag_ghost = it.tag_ghost;
     p.t = 0;
     int rc = ensure_err(L, &p.err);
     if (rc != TSU_OK) return rc;
@@ -422,33 +492,74 @@ int run_tiles(tsu_ising3d* L, const Sw3Item& it, int n_steps) {
     const long long merge_lanes = (long long)sc * L->depth * L->rows + (long long)sr * L->depth * L->cols + (long long)sz * L->rows * L->cols;
     const int tile_sites = t.z * t.r * t.c;
     const size_t lds = (size_t)tile_sites * 5;
-    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)k8_sw_local, (int)lds));
+    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)k8_sw_local<GHOST>, (int)lds));
     const int local_threads = threads_for((tile_sites + 15) / 16);
     const int quads = (L->cols + 3) / 4;
     const unsigned resolve_blocks = (unsigned)(((long long)quads * L->depth * L->rows + 255) / 256);
     for (int s = 0; s < n_steps; ++s) {
         p.t = it.step0 + (uint32_t)s;
-        hipLaunchKernelGGL(k8_sw_local, dim3((unsigned)n_tiles), dim3((unsigned)local_threads), lds, ctx->stream, p);
+        hipLaunchKernelGGL(k8_sw_local<GHOST>, dim3((unsigned)n_tiles), dim3((unsigned)local_threads), lds, ctx->stream, p);
         if (merge_lanes > 0)
-            hipLaunchKernelGGL(k8_sw_merge, dim3((unsigned)((merge_lanes + 255) / 256)), dim3(256), 0, ctx->stream, p, sc, sr, sz);
-        hipLaunchKernelGGL(k8_sw_resolve, dim3(resolve_blocks), dim3(256), 0, ctx->stream, p, quads);
+            hipLaunchKernelGGL(k8_sw_merge<GHOST>, dim3((unsigned)((merge_lanes + 255) / 256)), dim3(256), 0, ctx->stream, p, sc, sr, sz);
+        hipLaunchKernelGGL(k8_sw_resolve<GHOST>, dim3(resolve_blocks), dim3(256), 0, ctx->stream, p, quads);
         L->sw_launches += merge_lanes > 0 ? 3 : 2;
     }
     TSU_HIP_TRY(ctx, hipGetLastError());
     return TSU_OK;
 }
 
-int check_call(tsu_ising3d* L, double T, int n_steps, uint32_t step0) {
+int check_call(tsu_ising3d* L, double T, int n_steps, uint32_t step0, bool ghost) {
     tsu_ctx* ctx = L->ctx;
     TSU_REQUIRE(ctx, L->have_disorder, "ising3d_cluster_sweep: call tsu_ising3d_set_disorder first");
     TSU_REQUIRE(ctx, T > 0.0 && isfinite(T), "Temperature must be positive");
-    if (L->have_field)
+    if (L->have_field && !ghost)
         return tsu_fail(ctx, TSU_E_UNSUPPORTED, "ising3d_cluster: Swendsen-Wang cluster steps need zero field (a field would need a ghost spin)");
     if (sites_of(L) >= (1ll << 31))
         return tsu_fail(ctx, TSU_E_UNSUPPORTED, "ising3d_cluster: %lld sites exceed 32-bit labels", sites_of(L));
     TSU_REQUIRE(ctx, n_steps >= 0, "ising3d_cluster: n_steps must be >= 0");
     TSU_REQUIRE(ctx, (uint64_t)step0 + (uint64_t)n_steps <= (1ull << 32), "ising3d_cluster: step counter overflow");
     return ising3d_check_err(L);  // a cap that expired in an earlier call
+}
+
+// GHOST = false: the zero-field entry points (a stored field is refused); true: the ghost-spin ones
+template <bool GHOST>
+int sweep_one(tsu_ising3d* L, double T, int n_steps, uint64_t seed, uint32_t step0, uint32_t replica) {
+    if (!L) return TSU_E_INVALID;
+    int rc = check_call(L, T, n_steps, step0, GHOST);
+    if (rc != TSU_OK || n_steps == 0) return rc;
+    const Sw3Item it = make_item(L, T, seed, step0, replica);
+    return small_route(L) ? run_small<GHOST>(&L, 1, &it, n_steps) : run_tiles<GHOST>(L, it, n_steps);
+}
+
+template <bool GHOST>
+int sweep_batch(tsu_ising3d* const* lats, int n_lats, int n_steps, const double* Ts, const uint64_t* seeds, const uint32_t* step0s,
+                const uint32_t* replicas) {
+    if (!lats || n_lats < 1 || !lats[0]) return TSU_E_INVALID;
+    tsu_ctx* ctx = lats[0]->ctx;
+    TSU_REQUIRE(ctx, Ts && seeds && step0s && replicas, "ising3d_cluster_sweep_batch: Ts, seeds, step0s and replicas are per-lattice arrays");
+    const tsu_ising3d* A = lats[0];
+    bool one_launch = true;  // every lattice on k8_sw_small, all of one shape and boundary
+    for (int i = 0; i < n_lats; ++i) {
+        tsu_ising3d* L = lats[i];
+        TSU_REQUIRE(ctx, L && L->ctx == ctx, "ising3d_cluster_sweep_batch: lattice %d is NULL or belongs to another context", i);
+        for (int k = 0; k < i; ++k)
+            TSU_REQUIRE(ctx, lats[k] != L, "ising3d_cluster_sweep_batch: lattice %d appears twice", i);
+        int rc = check_call(L, Ts[i], n_steps, step0s[i], GHOST);
+        if (rc != TSU_OK) return rc;
+        one_launch = one_launch && small_route(L) && L->depth == A->depth && L->rows == A->rows && L->cols == A->cols && L->pz == A->pz &&
+                     L->pr == A->pr && L->pc == A->pc;
+    }
+    if (n_steps == 0) return TSU_OK;
+    if (one_launch) {
+        std::vector<Sw3Item> items((size_t)n_lats);
+        for (int i = 0; i < n_lats; ++i) items[(size_t)i] = make_item(lats[i], Ts[i], seeds[i], step0s[i], replicas[i]);
+        return run_small<GHOST>(lats, n_lats, items.data(), n_steps);
+    }
+    for (int i = 0; i < n_lats; ++i) {
+        int rc = sweep_one<GHOST>(lats[i], Ts[i], n_steps, seeds[i], step0s[i], replicas[i]);
+        if (rc != TSU_OK) return rc;
+    }
+    return TSU_OK;
 }
 
 }  // namespace
@@ -475,42 +586,24 @@ extern "C" {
 
 int tsu_ising3d_cluster_sweep(tsu_ising3d* L, double T, int n_steps, uint64_t seed, uint32_t step0, uint32_t replica) {
     TSU_ENTER(L ? L->ctx : nullptr);
-    if (!L) return TSU_E_INVALID;
-    int rc = check_call(L, T, n_steps, step0);
-    if (rc != TSU_OK || n_steps == 0) return rc;
-    const Sw3Item it = make_item(L, T, seed, step0, replica);
-    return small_route(L) ? run_small(&L, 1, &it, n_steps) : run_tiles(L, it, n_steps);
+    return sweep_one<false>(L, T, n_steps, seed, step0, replica);
 }
 
 int tsu_ising3d_cluster_sweep_batch(tsu_ising3d* const* lats, int n_lats, int n_steps, const double* Ts, const uint64_t* seeds,
                                     const uint32_t* step0s, const uint32_t* replicas) {
     TSU_ENTER((lats && n_lats > 0 && lats[0]) ? lats[0]->ctx : nullptr);
-    if (!lats || n_lats < 1 || !lats[0]) return TSU_E_INVALID;
-    tsu_ctx* ctx = lats[0]->ctx;
-    TSU_REQUIRE(ctx, Ts && seeds && step0s && replicas, "ising3d_cluster_sweep_batch: Ts, seeds, step0s and replicas are per-lattice arrays");
-    const tsu_ising3d* A = lats[0];
-    bool one_launch = true;  // every lattice on k8_sw_small, all of one shape and boundary
-    for (int i = 0; i < n_lats; ++i) {
-        tsu_ising3d* L = lats[i];
-        TSU_REQUIRE(ctx, L && L->ctx == ctx, "ising3d_cluster_sweep_batch: lattice %d is NULL or belongs to another context", i);
-        for (int k = 0; k < i; ++k)
-            TSU_REQUIRE(ctx, lats[k] != L, "ising3d_cluster_sweep_batch: lattice %d appears twice", i);
-        int rc = check_call(L, Ts[i], n_steps, step0s[i]);
-        if (rc != TSU_OK) return rc;
-        one_launch = one_launch && small_route(L) && L->depth == A->depth && L->rows == A->rows && L->cols == A->cols && L->pz == A->pz &&
-                     L->pr == A->pr && L->pc == A->pc;
-    }
-    if (n_steps == 0) return TSU_OK;
-    if (one_launch) {
-        std::vector<Sw3Item> items((size_t)n_lats);
-        for (int i = 0; i < n_lats; ++i) items[(size_t)i] = make_item(lats[i], Ts[i], seeds[i], step0s[i], replicas[i]);
-        return run_small(lats, n_lats, items.data(), n_steps);
-    }
-    for (int i = 0; i < n_lats; ++i) {
-        int rc = tsu_ising3d_cluster_sweep(lats[i], Ts[i], n_steps, seeds[i], step0s[i], replicas[i]);
-        if (rc != TSU_OK) return rc;
-    }
-    return TSU_OK;
+    return sweep_batch<false>(lats, n_lats, n_steps, Ts, seeds, step0s, replicas);
+}
+
+int tsu_ising3d_cluster_sweep_field(tsu_ising3d* L, double T, int n_steps, uint64_t seed, uint32_t step0, uint32_t replica) {
+    TSU_ENTER(L ? L->ctx : nullptr);
+    return sweep_one<true>(L, T, n_steps, seed, step0, replica);
+}
+
+int tsu_ising3d_cluster_sweep_field_batch(tsu_ising3d* const* lats, int n_lats, int n_steps, const double* Ts, const uint64_t* seeds,
+                                          const uint32_t* step0s, const uint32_t* replicas) {
+    TSU_ENTER((lats && n_lats > 0 && lats[0]) ? lats[0]->ctx : nullptr);
+    return sweep_batch<true>(lats, n_lats, n_steps, Ts, seeds, step0s, replicas);
 }
 
 int tsu_ising3d_cluster_launch_count(tsu_ising3d* L, uint64_t* n) {

@@ -106,7 +106,8 @@ enum : uint32_t {
     TSU_TAG_PT_SWAP = 8,
     TSU_TAG_PT_ICM = 9,
     TSU_TAG_SW_LAYER = 10,
-    TSU_TAG_POP_RESAMPLE = 11
+    TSU_TAG_POP_RESAMPLE = 11,
+    TSU_TAG_SW_GHOST = 12
 };
 
 struct u32x4 {

@@ -1,5 +1,6 @@
-// uf_dev.h -- device helpers shared by the cluster kernels (K6 ising2d_cluster.hip, K7 replica cluster moves ising2d_icm.hip):
-// union-find with min-index roots in LDS or HBM, the capped-loop error flag and the one-coin-per-root rule.
+// uf_dev.h -- device helpers shared by the cluster kernels (K6 ising2d_cluster.hip, K7 replica cluster moves ising2d_icm.hip, K8
+// ising3d_cluster.hip): union-find with min-index roots in LDS or HBM, the same with a ghost label -1 (K8 in a field only), the
+// capped-loop error flag and the one-coin-per-root rule.
 #pragma once
 #include "tsu_common.h"
 
@@ -35,6 +36,48 @@ __device__ __forceinline__ bool uf_union(int* L, int a, int b, int& budget) {
     for (;;) {
         a = uf_find<SCOPE>(L, a, budget);
         b = uf_find<SCOPE>(L, b, budget);
+        if (budget < 0) return false;
+        if (a == b) return true;
+        if (a < b) {
+            const int t = a;
+            a = b;
+            b = t;
+        }
+        const int old = __hip_atomic_fetch_min(L + a, b, __ATOMIC_RELAXED, SCOPE);
+        if (old == a) return true;
+        a = old;
+        if (--budget < 0) return false;
+    }
+}
+
+// ---------------------------------------------------------------- the same with a ghost: label -1 (K8 cluster steps in a field)
+// The ghost is an index below every site, so min-index roots take it as they are: a tree linked under -1 is frozen.  A find that
+// loads a negative parent returns -1 and never indexes with it; a or b may be -1 themselves.
+template <int SCOPE>
+__device__ __forceinline__ int ufg_find(int* L, int x, int& budget) {
+    if (x < 0) return -1;
+    int p = uf_load<SCOPE>(L, x);
+    while (p != x) {
+        if (p < 0) return -1;
+        const int gp = uf_load<SCOPE>(L, p);
+        if (gp == p) return p;
+        __hip_atomic_fetch_min(L + x, gp, __ATOMIC_RELAXED, SCOPE);
+        if (gp < 0) return -1;
+        x = gp;
+        p = uf_load<SCOPE>(L, x);
+        if (--budget < 0) return x;
+    }
+    return x;
+}
+
+// uf_union with ufg_find: joins two free trees, a free and a frozen one (b = -1 is a site's ghost bond), or two frozen ones (both
+// roots -1: nothing to do).  The larger root is a site (>= 0), so the atomicMin never indexes with the ghost; if that root got a
+// parent meanwhile (-1 included) the loop goes on from it.
+template <int SCOPE>
+__device__ __forceinline__ bool ufg_union(int* L, int a, int b, int& budget) {
+    for (;;) {
+        a = ufg_find<SCOPE>(L, a, budget);
+        b = ufg_find<SCOPE>(L, b, budget);
         if (budget < 0) return false;
         if (a == b) return true;
         if (a < b) {

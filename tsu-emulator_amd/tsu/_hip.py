@@ -261,6 +261,13 @@ PROBE_SIGNATURES = {
     "tsu_probe_screen": (C.c_int, [_vp, C.c_int64, _f32p, _f32p, _f32p, _f32p, _f32p]),
 }
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_cluster_field.h (the header tsu_hip.h includes) one to one
+CLUSTER_FIELD_SIGNATURES = {
+    "tsu_ising3d_cluster_sweep_field": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_ising3d_cluster_sweep_field_batch": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64),
+                                                        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+}
+
 _lib = None
 
 
@@ -280,7 +287,7 @@ def load_library():
     for name, (res, args) in (list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items())
                               + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())
                               + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())
-                              + list(PROBE_SIGNATURES.items())):
+                              + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -650,6 +657,11 @@ class Lattice3D:
     def cluster_sweep(self, T, n_steps, seed, step0=0, replica=0):
         """n_steps Swendsen-Wang steps on the stored couplings at temperature T, zero field (step counters step0 ..)."""
         self.ctx.check(self.lib.tsu_ising3d_cluster_sweep(self.h, float(T), int(n_steps), int(seed), int(step0), int(replica)))
+
+    def cluster_sweep_field(self, T, n_steps, seed, step0=0, replica=0):
+        """n_steps ghost-spin Swendsen-Wang steps on the stored couplings and field at temperature T (step counters step0 ..); with
+        zero field the spins of ``cluster_sweep``."""
+        self.ctx.check(self.lib.tsu_ising3d_cluster_sweep_field(self.h, float(T), int(n_steps), int(seed), int(step0), int(replica)))
 
     def cluster_launch_count(self):
         n = C.c_uint64(0)
@@ -1186,9 +1198,7 @@ def cluster_sweep_batch(lattices, n_steps, Js, Ts, seeds, step0s, replicas=None)
     ctx.check(lattices[0].lib.tsu_ising2d_cluster_sweep_batch(hs, n, int(n_steps), js, ts, sd, s0, rp))
 
 
-def cluster_sweep_batch_3d(lattices, n_steps, Ts, seeds, step0s, replicas=None):
-    """n_steps Swendsen-Wang steps of every 3-D lattice (own disorder, T, seed, step counter, replica id); small lattices of one
-    shape and boundary run in one launch.  Same results as stepping them one by one."""
+def _cluster_batch_3d(entry, lattices, n_steps, Ts, seeds, step0s, replicas):
     n = len(lattices)
     if n == 0:
         return
@@ -1198,7 +1208,19 @@ def cluster_sweep_batch_3d(lattices, n_steps, Ts, seeds, step0s, replicas=None):
     sd = (C.c_uint64 * n)(*[int(v) for v in seeds])
     s0 = (C.c_uint32 * n)(*[int(v) for v in step0s])
     rp = (C.c_uint32 * n)(*([0] * n if replicas is None else [int(v) for v in replicas]))
-    ctx.check(lattices[0].lib.tsu_ising3d_cluster_sweep_batch(hs, n, int(n_steps), ts, sd, s0, rp))
+    ctx.check(getattr(lattices[0].lib, entry)(hs, n, int(n_steps), ts, sd, s0, rp))
+
+
+def cluster_sweep_batch_3d(lattices, n_steps, Ts, seeds, step0s, replicas=None):
+    """n_steps Swendsen-Wang steps of every 3-D lattice (own disorder, T, seed, step counter, replica id); small lattices of one
+    shape and boundary run in one launch.  Same results as stepping them one by one."""
+    _cluster_batch_3d("tsu_ising3d_cluster_sweep_batch", lattices, n_steps, Ts, seeds, step0s, replicas)
+
+
+def cluster_sweep_field_batch_3d(lattices, n_steps, Ts, seeds, step0s, replicas=None):
+    """:func:`cluster_sweep_batch_3d` with ghost-spin steps (``Lattice3D.cluster_sweep_field``): every lattice's stored field takes
+    part."""
+    _cluster_batch_3d("tsu_ising3d_cluster_sweep_field_batch", lattices, n_steps, Ts, seeds, step0s, replicas)
 
 
 def observables_batch(lattices):

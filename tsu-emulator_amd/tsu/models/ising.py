@@ -418,12 +418,18 @@ class IsingGrid(IsingModel):
         return (horizontal_boundaries + vertical_boundaries) // 2 + 1
 
 
-_ALGORITHMS = ("gibbs", "swendsen_wang")
+_ALGORITHMS = ("gibbs", "swendsen_wang", "swendsen_wang_ghost")
 
 
 def _check_algorithm(algorithm: str) -> None:
     if algorithm not in _ALGORITHMS:
         raise ValueError(f"algorithm must be one of {_ALGORITHMS}, got {algorithm!r}")
+
+
+def _refuse_ghost_2d() -> None:
+    """The ghost-spin steps live on the 3-D handle; a one-layer lattice there is the 2-D model."""
+    raise _hip.UnsupportedError("ghost-spin Swendsen-Wang steps (algorithm='swendsen_wang_ghost') run on the 3-D lattice handle: "
+                                "use IsingModel3D(size=(1, R, C), periodic=(False, p, p)) for an R x C lattice in a field")
 
 
 def _check_cluster_model(external_field: float, bias_mode: str) -> None:
@@ -633,6 +639,8 @@ class IsingModel2D:
     def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000,
                     algorithm: str = "gibbs") -> "IsingModel2D":
         _check_algorithm(algorithm)
+        if algorithm == "swendsen_wang_ghost":
+            _refuse_ghost_2d()
         if temperature is not None:
             if temperature <= 0:
                 raise ValueError("Temperature must be positive")
@@ -733,6 +741,8 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
     (``replicas=2``) taken with every measurement (:meth:`IsingModel2D.fourier_modes`).
     """
     _check_algorithm(algorithm)
+    if algorithm == "swendsen_wang_ghost":
+        _refuse_ghost_2d()
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
     if correlation:
@@ -891,8 +901,10 @@ class IsingModel3D:
     open axis the last slice of that axis's J must be 0.  Uniform ``coupling=`` / ``external_field=`` are the constant-array case
     of the same kernel.  The arrays are rounded once to float32 (``disorder`` returns the rounded copies).
     ``gibbs_update()`` = one checkerboard heat-bath sweep; ``cluster_update()`` = one Swendsen-Wang step on the stored couplings
-    (zero field only; its own counter ``cluster_count``); ``energy()`` / ``magnetization()`` / ``overlap(other)`` are device
-    reductions; ``equilibrate(T)`` sets the temperature, runs ``n_sweeps`` sweeps (or SW steps) and returns ``self``.
+    (zero field only; its own counter ``cluster_count``); ``ghost_cluster_update()`` = one ghost-spin Swendsen-Wang step on the
+    couplings and the field (the same counter); ``energy()`` / ``magnetization()`` / ``overlap(other)`` are device
+    reductions; ``equilibrate(T)`` sets the temperature, runs ``n_sweeps`` sweeps (or SW steps, ``algorithm="swendsen_wang"`` /
+    ``"swendsen_wang_ghost"``) and returns ``self``.
     """
 
     def __init__(self, size, coupling: float = 1.0, temperature: float = 1.0, periodic=True, external_field: float = 0.0,
@@ -944,6 +956,15 @@ class IsingModel3D:
         self.cluster_count += int(n_steps)
         return self
 
+    def ghost_cluster_update(self, n_steps: int = 1) -> "IsingModel3D":
+        """n_steps ghost-spin Swendsen-Wang steps on the stored couplings and field: every site is also bonded to a ghost spin
+        fixed at +1 with coupling h_i, and a cluster that reaches the ghost does not flip.  Samples exp(-E / T) / Z of
+        :meth:`energy`; with zero field these are the steps of :meth:`cluster_update`.  Advances ``cluster_count``, the counter
+        the two kinds of cluster step share."""
+        self._lat.cluster_sweep_field(self.temperature, int(n_steps), self.seed, self.cluster_count)
+        self.cluster_count += int(n_steps)
+        return self
+
     def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000,
                     algorithm: str = "gibbs") -> "IsingModel3D":
         _check_algorithm(algorithm)
@@ -955,6 +976,8 @@ class IsingModel3D:
             self.temperature = float(temperature)
         if algorithm == "swendsen_wang":
             return self.cluster_update(n_sweeps)
+        if algorithm == "swendsen_wang_ghost":
+            return self.ghost_cluster_update(n_sweeps)
         return self.gibbs_update(n_sweeps)
 
     def magnetization(self) -> float:
@@ -1001,13 +1024,16 @@ class IsingModel3D:
 
 def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                         measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", algorithm: str = "gibbs", *,
-                        couplings=None, field=None, replicas: int = 1, correlation: bool = False) -> dict:
+                        couplings=None, field=None, replicas: int = 1, correlation: bool = False,
+                        external_field: float = 0.0) -> dict:
     """:func:`temperature_scan` for a cubic lattice (K8): one :class:`IsingModel3D` per temperature stays on the device and
     |M|, E/N, chi and C come from the device reductions.  ``couplings`` / ``field``: the same quenched disorder at every
     temperature.  Model i of replica k has seed ``seed + k len(temperatures) + i``.  ``replicas=2``: the result gains
     ``overlap`` = <|q|>, ``overlap_sq`` = <q^2> and ``binder`` = (3 - <q^4> / <q^2>^2) / 2 of q = overlap / N; the other keys are
     those of the first replica.  ``algorithm="swendsen_wang"``: ``n_equilibrate`` and ``measure_every`` count Swendsen-Wang steps
     on the couplings (zero field only); lattices of at most 16384 sites advance together, one launch per batch of steps.
+    ``algorithm="swendsen_wang_ghost"``: the same with ghost-spin steps (:meth:`IsingModel3D.ghost_cluster_update`), which take
+    ``field=`` / ``external_field=``.
     ``correlation=True`` (at least one periodic axis): the result gains ``chi_k`` = <|F_d|^2> / N and ``xi`` (both ``(n_T, 3)``, NaN on
     an open axis) and ``xi_over_L`` = the mean of xi_d / L_d over the periodic axes, from the k_min modes of the spins
     (``replicas=1``) or of the overlap field (``replicas=2``) taken with every measurement."""
@@ -1021,7 +1047,7 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
     if correlation:
         _check_correlation(_hip.periodic_axes(periodic))
     # validated once, before any device call
-    disorder = _disorder_arrays_3d(shape, _hip.periodic_axes(periodic), float(coupling), 0.0, couplings, field)
+    disorder = _disorder_arrays_3d(shape, _hip.periodic_axes(periodic), float(coupling), float(external_field), couplings, field)
     if algorithm == "swendsen_wang":
         _check_cluster_field_3d(disorder[3])
     out = {k: np.zeros(len(temperatures)) for k in ("magnetization", "energy", "susceptibility", "specific_heat")}
@@ -1032,9 +1058,10 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
               for k in range(replicas) for i, T in enumerate(temperatures)]
 
     def advance(n):
-        if algorithm == "swendsen_wang":  # the streams (seed, own step counter) are those of stepping the models one by one
-            _hip.cluster_sweep_batch_3d([m._lat for m in models], n, [m.temperature for m in models], [m.seed for m in models],
-                                        [m.cluster_count for m in models])
+        if algorithm != "gibbs":  # the streams (seed, own step counter) are those of stepping the models one by one
+            batch = _hip.cluster_sweep_batch_3d if algorithm == "swendsen_wang" else _hip.cluster_sweep_field_batch_3d
+            batch([m._lat for m in models], n, [m.temperature for m in models], [m.seed for m in models],
+                  [m.cluster_count for m in models])
             for m in models:
                 m.cluster_count += int(n)
             return
