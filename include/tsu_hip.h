@@ -18,6 +18,12 @@
  *     (sweep, step, randomize) are asynchronous.
  *   - randomness is counter-based Philox4x32-10 keyed by (seed, position, sweep/step counter): results
  *     do not depend on launch geometry, tile size, number of sweeps per call, or slab decomposition.
+ *   - limits of the counters, the same at every entry point (TSU_E_INVALID beyond them, nothing launched, no state touched):
+ *       replica ids (scalar or per-lattice / per-replica arrays) are below 2^24: the id shares a Philox counter word with the
+ *         8-bit stream tag (TAG | replica << 8);
+ *       lattice sweeps (K1, K7, K8: the half-sweep counter is 2 sweep + colour) take sweep0 + n_sweeps <= 2^31;
+ *       cluster steps take step0 + n_steps <= 2^32; dense and sparse sweeps (K2, K5) take sweep0 + total sweeps <= 2^32;
+ *       a counter never wraps to replay the stream of sweep 0.  Langevin chain ids and step counters are full 32-bit words.
  */
 #ifndef TSU_HIP_H
 #define TSU_HIP_H
@@ -109,7 +115,8 @@ int tsu_ising2d_set_thresholds(tsu_ising2d* lat, const uint64_t table[25]);
 int tsu_ising2d_set_model(tsu_ising2d* lat, double J, double h, double T, int mode);
 int tsu_ising2d_set_kernel(tsu_ising2d* lat, int kernel, int sweeps_per_launch);
 
-/* n_sweeps full checkerboard sweeps, sweep counters sweep0 .. sweep0+n_sweeps-1 (asynchronous).
+/* n_sweeps full checkerboard sweeps, sweep counters sweep0 .. sweep0+n_sweeps-1 (asynchronous); sweep0 + n_sweeps <= 2^31,
+ * replica < 2^24 (so for every entry point below that takes them).
  * For a slab: ghost rows must be fresh on entry and n_sweeps <= ghost/2. */
 int tsu_ising2d_sweep(tsu_ising2d* lat, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica);
 
@@ -152,6 +159,11 @@ int tsu_ising2d_set_timing(tsu_ising2d* lat, int enable);
 int tsu_ising2d_last_sweep_ms(tsu_ising2d* lat, float* ms);
 /* sweep-kernel launches issued for this lattice so far (a tile-resident launch runs many generations of sweeps) */
 int tsu_ising2d_launch_count(tsu_ising2d* lat, uint64_t* n_launches);
+/* Read-only view of the tile-resident kernel's strip numbering (no reference counterpart: lets a test see that it crossed a
+ * restart).  *generation: generations numbered so far in the running numbering (0 before the first tile-resident launch);
+ * *restarts: how often a numbering started at 1 over a cleared strip buffer: the first tile-resident launch, every launch that
+ * would have reached generation 16383, and every change of the strip layout (tile shape, sweeps per generation). */
+int tsu_ising2d_strip_numbering(tsu_ising2d* lat, uint32_t* generation, uint64_t* restarts);
 
 /* ------------------------------------------------------------------ Swendsen-Wang cluster steps (K6)
  * No reference counterpart (the reference has local updates only).  One step samples exp(J sum_<ij> s_i s_j / T) at zero
@@ -403,6 +415,8 @@ int tsu_dense_get_state(tsu_dense* d, int8_t* bits_host);
  * sweep0+s) or n_sweeps*n doubles consumed in visiting order (replays np.random.rand, gibbs.py:126). */
 int tsu_dense_sweep(tsu_dense* d, double T, int n_sweeps, const int64_t* order, uint64_t seed, uint32_t sweep0,
                     uint32_t replica, const double* replay_uniforms);
+/* tsu_dense_sweep, _sample, _anneal and _sweep_replicas (per replica): sweep0 + all sweeps of the call <= 2^32, replica < 2^24;
+ * otherwise TSU_E_INVALID ("... sweep counter overflow") before anything is launched. */
 /* The whole sampling run of GibbsSampler.sample_boltzmann (tsu/gibbs.py:196-213) from the resident state:
  * n_burnin sweeps, then n_samples x (n_sweeps sweeps, record the state).  samples_host receives n_samples*n bits.
  * order / replay_uniforms cover all (n_burnin + n_samples*n_sweeps) sweeps, row per sweep; sweep numbers for the
@@ -456,6 +470,7 @@ int tsu_sparse_create(tsu_ctx* ctx, int n, const int64_t* row_ptr /*n+1*/, const
 int tsu_sparse_destroy(tsu_sparse* g);
 int tsu_sparse_set_state(tsu_sparse* g, const int8_t* bits_host); /* n bits {0,1}, site order */
 int tsu_sparse_get_state(tsu_sparse* g, int8_t* bits_host);
+/* sweep and sample: sweep0 + all sweeps of the call <= 2^32, replica < 2^24 (TSU_E_INVALID otherwise, nothing launched) */
 int tsu_sparse_sweep(tsu_sparse* g, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica);
 /* n_burnin sweeps, then n_samples x (n_sweeps sweeps, record): samples_host receives n_samples*n bits (site order) */
 int tsu_sparse_sample(tsu_sparse* g, double T, int n_burnin, int n_sweeps, int n_samples, uint64_t seed, uint32_t sweep0,

@@ -1,0 +1,49 @@
+"""The far-end inputs of tests/test_far_end_gpu.py and tests/test_far_end_cpu.py: ONE table of seeds, replica ids and counter
+positions that every case takes, so that no kernel is compared at the start of a run only (seed below 2^16, counters of a few
+hundred, replica ids 0 .. 10).
+
+  SEED_HI      both Philox key words are non-zero and differ; the top bit of the seed (of key word k1) is set
+  SEED_CARRY   handles that derive walker keys as seed + i: the carry into the high key word falls inside the batch
+  REPLICAS     the largest replica id (2^24 - 1: it shares its counter word with the 8-bit stream tag) and one with every byte used
+  lattice sweeps (K1, K7, K8): hs = 2 sweep + colour, sweep0 + n <= 2^31
+      end(n)        the call ends exactly at the limit: its last half-sweep is hs = 2^32 - 1
+      straddle(n)   the call starts at sweep 2^30 - 3: hs crosses 2^31, the sign bit of an int
+  cluster steps, dense and sparse sweeps (K6, K8 clusters, K2, K5): a full uint32 counter, counter0 + n <= 2^32
+      end32(n), straddle32(n)
+"""
+SEED_HI = 0xFEDCBA9876543210
+SEED_CARRY = 2 ** 32 - 2
+REPLICA_MAX = 2 ** 24 - 1
+REPLICA_BYTES = 0xABCDEF
+REPLICAS = (REPLICA_MAX, REPLICA_BYTES)
+
+LATTICE_LIMIT = 2 ** 31   # sweep0 + n_sweeps of K1, K7, K8
+COUNTER_LIMIT = 2 ** 32   # step0 + n_steps of the cluster steps, sweep0 + n_sweeps of K2 and K5
+REPLICA_LIMIT = 2 ** 24
+
+
+def end(n):
+    return LATTICE_LIMIT - n
+
+
+def straddle(n):
+    assert n > 3
+    return 2 ** 30 - 3
+
+
+def end32(n):
+    return COUNTER_LIMIT - n
+
+
+def straddle32(n):
+    assert n > 2
+    return 2 ** 31 - 2
+
+
+def lattice_positions(n):
+    """(name, sweep0) of the two calls of n sweeps every lattice case makes, in this order on one handle."""
+    return (("straddle", straddle(n)), ("end", end(n)))
+
+
+def counter_positions(n):
+    return (("straddle", straddle32(n)), ("end", end32(n)))

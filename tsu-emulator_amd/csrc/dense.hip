@@ -812,6 +812,8 @@ static int dense_sweep(tsu_dense* d, double T, int n_sweeps, const int64_t* orde
     tsu_ctx* ctx = d->ctx;
     TSU_REQUIRE(ctx, T > 0.0, "Temperature must be positive");
     TSU_REQUIRE(ctx, n_sweeps >= 0, "dense_sweep: n_sweeps must be >= 0");
+    TSU_REQUIRE(ctx, (uint64_t)sweep0 + (uint64_t)n_sweeps <= (1ull << 32), "dense_sweep: sweep counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "dense_sweep");
     if (n_sweeps == 0) return TSU_OK;
     const int rc = dense_upload_inputs(d, n_sweeps, order, checked, replay_uniforms, nullptr);
     if (rc != TSU_OK) return rc;
@@ -869,6 +871,7 @@ static int dense_run(tsu_dense* d, double T, const double* temps, int n_burnin, 
     TSU_REQUIRE(ctx, n_samples == 0 || samples_host != nullptr, "dense_sample: NULL output");
     const long long total = (long long)n_burnin + (long long)n_samples * n_sweeps;
     TSU_REQUIRE(ctx, total <= (1ll << 30) && (uint64_t)sweep0 + (uint64_t)total <= (1ull << 32), "dense_sample: sweep counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "dense_sample");
     const int n = d->n;
     const size_t out_bytes = (size_t)n_samples * n;
     TSU_HIP_TRY(ctx, dense_grow(d->samples, d->samples_cap, out_bytes));
@@ -947,6 +950,8 @@ int tsu_dense_sweep_replicas(tsu_dense* d, int n_replicas, const double* tempera
     for (int r = 0; r < n_replicas; ++r) {
         TSU_REQUIRE(ctx, temperatures[r] > 0.0, "Temperature must be positive");
         TSU_REQUIRE(ctx, dense_bits01(states_host + (size_t)r * n, (size_t)n), "dense_set_state: state must be 0/1");
+        TSU_REQUIRE(ctx, (uint64_t)sweep0s[r] + (uint64_t)n_sweeps <= (1ull << 32), "dense_sweep_replicas: sweep counter overflow");
+        TSU_REQUIRE_REPLICA(ctx, replicas[r], "dense_sweep_replicas");
     }
     if (n_sweeps == 0) return TSU_OK;
     d->rep_match = 0;  // (the kept rows are about to change)

@@ -24,6 +24,7 @@ struct tsu_ising2d {
     size_t xbuf_cap;     // bytes allocated (so are batch_cap and obs_batch_cap: ising2d_grow)
     uint32_t xgen;       // generations numbered so far in d_xbuf (every strip element carries its generation number)
     uint64_t xsig;       // strip layout the numbering belongs to (0: buffer not cleared yet)
+    uint64_t xrestarts;  // times the numbering started at 1 over a cleared buffer (first use, generation limit, another strip layout)
     void* d_batch;       // tsu_ising2d_sweep_batch: device copy of the per-lattice launch items
     size_t batch_cap;
     void* d_obs_batch;   // tsu_ising2d_observables_batch: [n][2] sums of the batch (lives with its first lattice)

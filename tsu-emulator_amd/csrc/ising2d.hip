@@ -382,6 +382,7 @@ int tsu_ising2d_create_slab(tsu_ctx* ctx, int64_t total_rows, int cols, int peri
     L->xbuf_cap = 0;
     L->xgen = 0;
     L->xsig = 0;
+    L->xrestarts = 0;
     L->d_batch = nullptr;
     L->batch_cap = 0;
     L->d_obs_batch = nullptr;
@@ -489,6 +490,7 @@ int tsu_ising2d_randomize(tsu_ising2d* L, uint64_t seed, uint32_t replica) {
     TSU_ENTER(L ? L->ctx : nullptr);
     if (!L) return TSU_E_INVALID;
     tsu_ctx* ctx = L->ctx;
+    TSU_REQUIRE_REPLICA(ctx, replica, "ising2d_randomize");
     K1Params p = make_params(L, L->alloc[L->cur]);
     p.r_lo = -p.top_rows;
     p.r_hi = L->rows + p.bot_rows;
@@ -563,6 +565,7 @@ int tsu_ising2d_sweep_part(tsu_ising2d* L, int n_sweeps, uint64_t seed, uint32_t
     TSU_REQUIRE(ctx, n_sweeps >= 0, "ising2d_sweep: n_sweeps must be >= 0");
     TSU_REQUIRE(ctx, L->have_table, "ising2d_sweep: call tsu_ising2d_set_model / set_thresholds first");
     TSU_REQUIRE(ctx, (uint64_t)sweep0 + (uint64_t)n_sweeps <= (1ull << 31), "ising2d_sweep: sweep counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "ising2d_sweep");
     TSU_REQUIRE(ctx, L->ghost == 0 || 2 * n_sweeps <= L->ghost,
                 "ising2d_sweep: %d sweeps need %d ghost rows, slab has %d", n_sweeps, 2 * n_sweeps, L->ghost);
     if (n_sweeps == 0) return TSU_OK;
@@ -620,6 +623,14 @@ int tsu_ising2d_launch_count(tsu_ising2d* L, uint64_t* n) {
     return TSU_OK;
 }
 
+int tsu_ising2d_strip_numbering(tsu_ising2d* L, uint32_t* generation, uint64_t* restarts) {
+    TSU_ENTER(L ? L->ctx : nullptr);
+    if (!L || !generation || !restarts) return TSU_E_INVALID;
+    *generation = L->xgen;
+    *restarts = L->xrestarts;
+    return TSU_OK;
+}
+
 int tsu_ising2d_last_sweep_ms(tsu_ising2d* L, float* ms) {
     TSU_ENTER(L ? L->ctx : nullptr);
     if (!L || !ms) return TSU_E_INVALID;
@@ -656,6 +667,11 @@ int tsu_ising2d_sample(tsu_ising2d* L, int n_burnin, int n_sweeps, int n_samples
     TSU_REQUIRE(ctx, n_burnin >= 0 && n_sweeps > 0 && n_samples >= 0, "ising2d_sample: need n_burnin >= 0, n_sweeps > 0, n_samples >= 0");
     TSU_REQUIRE(ctx, n_samples == 0 || samples_host, "ising2d_sample: NULL output");
     TSU_REQUIRE(ctx, L->ghost == 0, "ising2d_sample: whole lattices only (a slab's ghost rows need the exchange between sweeps)");
+    // the whole run is checked before its first launch (the sweeps below would refuse only once they reach the limit)
+    TSU_REQUIRE(ctx, L->have_table, "ising2d_sweep: call tsu_ising2d_set_model / set_thresholds first");
+    TSU_REQUIRE(ctx, (uint64_t)sweep0 + (uint64_t)n_burnin + (uint64_t)n_samples * (uint64_t)n_sweeps <= (1ull << 31),
+                "ising2d_sample: sweep counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "ising2d_sample");
     const size_t site_bytes = (size_t)L->rows * (size_t)L->cols, bytes = site_bytes * (size_t)n_samples;
     int8_t* d_samples = nullptr;
     if (bytes) TSU_HIP_TRY(ctx, hipMalloc(&d_samples, bytes));
@@ -690,6 +706,7 @@ int tsu_ising2d_sweep_batch(tsu_ising2d* const* lats, int n_lats, int n_sweeps, 
         TSU_REQUIRE(ctx, L && L->ctx == ctx, "ising2d_sweep_batch: lattice %d is NULL or belongs to another context", i);
         TSU_REQUIRE(ctx, L->have_table, "ising2d_sweep: call tsu_ising2d_set_model / set_thresholds first");
         TSU_REQUIRE(ctx, (uint64_t)sweep0s[i] + (uint64_t)n_sweeps <= (1ull << 31), "ising2d_sweep: sweep counter overflow");
+        TSU_REQUIRE_REPLICA(ctx, replicas[i], "ising2d_sweep_batch");
         one_launch = one_launch && k1_path(L, TSU_PART_ALL) == K1_PLANES && L->rows == lats[0]->rows && L->cols == lats[0]->cols &&
                      L->periodic == lats[0]->periodic;
     }

@@ -352,7 +352,7 @@ int run_tiles(tsu_ising2d* L, const SwItem& it, int n_steps) {
     return TSU_OK;
 }
 
-int check_call(tsu_ising2d* L, double J, double T, int n_steps, uint32_t step0) {
+int check_call(tsu_ising2d* L, double J, double T, int n_steps, uint32_t step0, uint32_t replica) {
     tsu_ctx* ctx = L->ctx;
     if (!whole_lattice(L))
         return tsu_fail(ctx, TSU_E_UNSUPPORTED, "ising2d_cluster: whole lattices only (a slab would need a cluster merge across ranks)");
@@ -360,6 +360,7 @@ int check_call(tsu_ising2d* L, double J, double T, int n_steps, uint32_t step0) 
     if (rc != TSU_OK) return rc;
     TSU_REQUIRE(ctx, n_steps >= 0, "ising2d_cluster: n_steps must be >= 0");
     TSU_REQUIRE(ctx, (uint64_t)step0 + (uint64_t)n_steps <= (1ull << 32), "ising2d_cluster: step counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "ising2d_cluster");
     return ising2d_check_err(L);  // a cap that expired in an earlier call
 }
 
@@ -376,7 +377,7 @@ int tsu_ising2d_cluster_threshold(double J, double T, uint64_t* thr) {
 int tsu_ising2d_cluster_sweep(tsu_ising2d* L, double J, double T, int n_steps, uint64_t seed, uint32_t step0, uint32_t replica) {
     TSU_ENTER(L ? L->ctx : nullptr);
     if (!L) return TSU_E_INVALID;
-    int rc = check_call(L, J, T, n_steps, step0);
+    int rc = check_call(L, J, T, n_steps, step0, replica);
     if (rc != TSU_OK || n_steps == 0) return rc;
     const SwItem it = make_item(L, J, T, seed, step0, replica);
     return small_route(L) ? run_small(&L, 1, &it, n_steps) : run_tiles(L, it, n_steps);
@@ -392,7 +393,7 @@ int tsu_ising2d_cluster_sweep_batch(tsu_ising2d* const* lats, int n_lats, int n_
     for (int i = 0; i < n_lats; ++i) {
         tsu_ising2d* L = lats[i];
         TSU_REQUIRE(ctx, L && L->ctx == ctx, "ising2d_cluster_sweep_batch: lattice %d is NULL or belongs to another context", i);
-        int rc = check_call(L, Js[i], Ts[i], n_steps, step0s[i]);
+        int rc = check_call(L, Js[i], Ts[i], n_steps, step0s[i], replicas[i]);
         if (rc != TSU_OK) return rc;
         one_launch = one_launch && small_route(L) && L->rows == lats[0]->rows && L->cols == lats[0]->cols && L->periodic == lats[0]->periodic;
     }

@@ -276,6 +276,7 @@ int tsu_ising2d_disorder_sweep(tsu_ising2d* L, double T, int n_sweeps, uint64_t 
     TSU_REQUIRE(ctx, T > 0.0 && std::isfinite(T), "Temperature must be positive");
     TSU_REQUIRE(ctx, n_sweeps >= 0, "ising2d_sweep: n_sweeps must be >= 0");
     TSU_REQUIRE(ctx, (uint64_t)sweep0 + (uint64_t)n_sweeps <= (1ull << 31), "ising2d_sweep: sweep counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "ising2d_disorder_sweep");
     if (n_sweeps == 0) return TSU_OK;
     if (L->timing) TSU_HIP_TRY(ctx, hipEventRecord(L->ev0, ctx->stream));
     K7Params p = make_params(L);

@@ -1427,6 +1427,7 @@ int run_resident(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps,
         P.r.xbuf = L->d_xbuf;
         const bool renumber = L->xsig != xsig || L->xgen + (uint32_t)((chunk + kmax - 1) / kmax) + 2u >= 16383u;
         if (renumber) {
+            L->xrestarts += 1;
             L->xsig = xsig;
             L->xgen = 0;
         }

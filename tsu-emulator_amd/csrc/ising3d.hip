@@ -418,6 +418,7 @@ int tsu_ising3d_randomize(tsu_ising3d* L, uint64_t seed, uint32_t replica) {
     TSU_ENTER(L ? L->ctx : nullptr);
     if (!L) return TSU_E_INVALID;
     tsu_ctx* ctx = L->ctx;
+    TSU_REQUIRE_REPLICA(ctx, replica, "ising3d_randomize");
     K8Params p = make_params(L);
     p.w.k0 = (uint32_t)seed;
     p.w.k1 = (uint32_t)(seed >> 32);
@@ -484,6 +485,7 @@ int tsu_ising3d_sweep(tsu_ising3d* L, double T, int n_sweeps, uint64_t seed, uin
     TSU_REQUIRE(ctx, T > 0.0 && std::isfinite(T), "Temperature must be positive");
     TSU_REQUIRE(ctx, n_sweeps >= 0, "ising3d_sweep: n_sweeps must be >= 0");
     TSU_REQUIRE(ctx, (uint64_t)sweep0 + (uint64_t)n_sweeps <= (1ull << 31), "ising3d_sweep: sweep counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "ising3d_sweep");
     if (n_sweeps == 0) return TSU_OK;
     K8Params p = make_params(L);
     ising2d_set_keys(p.w, seed, replica);

@@ -508,7 +508,7 @@ int run_tiles(tsu_ising3d* L, const Sw3Item& it, int n_steps) {
     return TSU_OK;
 }
 
-int check_call(tsu_ising3d* L, double T, int n_steps, uint32_t step0, bool ghost) {
+int check_call(tsu_ising3d* L, double T, int n_steps, uint32_t step0, uint32_t replica, bool ghost) {
     tsu_ctx* ctx = L->ctx;
     TSU_REQUIRE(ctx, L->have_disorder, "ising3d_cluster_sweep: call tsu_ising3d_set_disorder first");
     TSU_REQUIRE(ctx, T > 0.0 && isfinite(T), "Temperature must be positive");
@@ -518,6 +518,7 @@ int check_call(tsu_ising3d* L, double T, int n_steps, uint32_t step0, bool ghost
         return tsu_fail(ctx, TSU_E_UNSUPPORTED, "ising3d_cluster: %lld sites exceed 32-bit labels", sites_of(L));
     TSU_REQUIRE(ctx, n_steps >= 0, "ising3d_cluster: n_steps must be >= 0");
     TSU_REQUIRE(ctx, (uint64_t)step0 + (uint64_t)n_steps <= (1ull << 32), "ising3d_cluster: step counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "ising3d_cluster");
     return ising3d_check_err(L);  // a cap that expired in an earlier call
 }
 
@@ -525,7 +526,7 @@ int check_call(tsu_ising3d* L, double T, int n_steps, uint32_t step0, bool ghost
 template <bool GHOST>
 int sweep_one(tsu_ising3d* L, double T, int n_steps, uint64_t seed, uint32_t step0, uint32_t replica) {
     if (!L) return TSU_E_INVALID;
-    int rc = check_call(L, T, n_steps, step0, GHOST);
+    int rc = check_call(L, T, n_steps, step0, replica, GHOST);
     if (rc != TSU_OK || n_steps == 0) return rc;
     const Sw3Item it = make_item(L, T, seed, step0, replica);
     return small_route(L) ? run_small<GHOST>(&L, 1, &it, n_steps) : run_tiles<GHOST>(L, it, n_steps);
@@ -544,7 +545,7 @@ int sweep_batch(tsu_ising3d* const* lats, int n_lats, int n_steps, const double*
         TSU_REQUIRE(ctx, L && L->ctx == ctx, "ising3d_cluster_sweep_batch: lattice %d is NULL or belongs to another context", i);
         for (int k = 0; k < i; ++k)
             TSU_REQUIRE(ctx, lats[k] != L, "ising3d_cluster_sweep_batch: lattice %d appears twice", i);
-        int rc = check_call(L, Ts[i], n_steps, step0s[i], GHOST);
+        int rc = check_call(L, Ts[i], n_steps, step0s[i], replicas[i], GHOST);
         if (rc != TSU_OK) return rc;
         one_launch = one_launch && small_route(L) && L->depth == A->depth && L->rows == A->rows && L->cols == A->cols && L->pz == A->pz &&
                      L->pr == A->pr && L->pc == A->pc;

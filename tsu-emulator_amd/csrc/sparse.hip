@@ -469,6 +469,8 @@ int tsu_sparse_sweep(tsu_sparse* g, double T, int n_sweeps, uint64_t seed, uint3
     if (!g) return TSU_E_INVALID;
     TSU_REQUIRE(g->ctx, T > 0.0, "Temperature must be positive");
     TSU_REQUIRE(g->ctx, n_sweeps >= 0, "tsu_sparse_sweep: n_sweeps must be >= 0");
+    TSU_REQUIRE(g->ctx, (uint64_t)sweep0 + (uint64_t)n_sweeps <= (1ull << 32), "sparse_sweep: sweep counter overflow");
+    TSU_REQUIRE_REPLICA(g->ctx, replica, "sparse_sweep");
     return run_sweeps(g, T, n_sweeps, seed, sweep0, replica, nullptr, 0, 1);
 }
 
@@ -479,6 +481,10 @@ int tsu_sparse_sample(tsu_sparse* g, double T, int n_burnin, int n_sweeps, int n
     tsu_ctx* ctx = g->ctx;
     TSU_REQUIRE(ctx, T > 0.0, "Temperature must be positive");
     TSU_REQUIRE(ctx, n_burnin >= 0 && n_sweeps > 0 && n_samples >= 0 && (samples_host || n_samples == 0), "tsu_sparse_sample: bad arguments");
+    const long long total = (long long)n_burnin + (long long)n_samples * n_sweeps;
+    TSU_REQUIRE(ctx, total < (1ll << 31), "tsu_sparse_sample: too many sweeps in one call");
+    TSU_REQUIRE(ctx, (uint64_t)sweep0 + (uint64_t)total <= (1ull << 32), "sparse_sample: sweep counter overflow");
+    TSU_REQUIRE_REPLICA(ctx, replica, "sparse_sample");
     const size_t need = (size_t)n_samples * (size_t)g->n;
     if (need > g->samples_cap) {
         if (g->samples) (void)hipFree(g->samples);
@@ -487,8 +493,6 @@ int tsu_sparse_sample(tsu_sparse* g, double T, int n_burnin, int n_sweeps, int n
         TSU_HIP_TRY(ctx, hipMalloc((void**)&g->samples, need));
         g->samples_cap = need;
     }
-    const long long total = (long long)n_burnin + (long long)n_samples * n_sweeps;
-    TSU_REQUIRE(ctx, total < (1ll << 31), "tsu_sparse_sample: too many sweeps in one call");
     int rc = run_sweeps(g, T, (int)total, seed, sweep0, replica, n_samples ? g->samples : nullptr, n_burnin, n_sweeps);
     if (rc != TSU_OK) return rc;
     if (n_samples) TSU_HIP_TRY(ctx, hipMemcpyAsync(samples_host, g->samples, need, hipMemcpyDeviceToHost, ctx->stream));

@@ -87,6 +87,12 @@ int tsu_fail(tsu_ctx* ctx, int code, const char* fmt, ...);
         if (!(cond)) return tsu_fail((ctx), TSU_E_INVALID, __VA_ARGS__); \
     } while (0)
 
+// A replica id shares Philox counter word 3 with the 8-bit stream tag (TAG | replica << 8): ids of 2^24 and more
+// would be cut to their low 24 bits and replay another replica's stream, so every entry point refuses them.
+#define TSU_REPLICA_LIMIT (1u << 24)
+#define TSU_REQUIRE_REPLICA(ctx, replica, who) \
+    TSU_REQUIRE((ctx), (uint32_t)(replica) < TSU_REPLICA_LIMIT, who ": replica id %u is not below 2^24", (unsigned)(replica))
+
 // ------------------------------------------------------------------ Philox4x32-10 (device + host)
 #define TSU_PHILOX_M0 0xD2511F53u
 #define TSU_PHILOX_M1 0xCD9E8D57u

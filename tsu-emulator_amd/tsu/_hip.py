@@ -75,6 +75,7 @@ SIGNATURES = {
     "tsu_ising2d_set_timing": (C.c_int, [_vp, C.c_int]),
     "tsu_ising2d_last_sweep_ms": (C.c_int, [_vp, _f32p]),
     "tsu_ising2d_launch_count": (C.c_int, [_vp, _u64p]),
+    "tsu_ising2d_strip_numbering": (C.c_int, [_vp, _u32p, _u64p]),
     "tsu_ising2d_cluster_threshold": (C.c_int, [C.c_double, C.c_double, _u64p]),
     "tsu_ising2d_cluster_sweep": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
     "tsu_ising2d_cluster_sweep_batch": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -299,6 +300,42 @@ def _ptr(a, t):
     return a.ctypes.data_as(t)
 
 
+REPLICA_LIMIT = 1 << 24  # TSU_REPLICA_LIMIT: a replica id shares its Philox counter word with the 8-bit stream tag
+
+
+def _uint(name, value, bits):
+    """``value`` as an int that fits an unsigned C integer of ``bits`` bits; ValueError otherwise (ctypes would wrap it silently)."""
+    v = int(value)
+    if not 0 <= v < (1 << bits):
+        raise ValueError(f"{name} = {v} does not fit an unsigned {bits}-bit integer")
+    return v
+
+
+def _seed(seed):
+    return _uint("seed", seed, 64)
+
+
+def _counter(name, value):
+    """A sweep0 / step0 / chain0 argument: a uint32 of the C ABI."""
+    return _uint(name, value, 32)
+
+
+def _replica(replica):
+    v = _uint("replica", replica, 32)
+    if v >= REPLICA_LIMIT:
+        raise ValueError(f"replica = {v} is not below 2^24")
+    return v
+
+
+def _uint_array(name, values, dtype, limit=None):
+    """Per-lattice / per-replica seeds, counters and replica ids as a contiguous unsigned array, range-checked first."""
+    bits = 8 * np.dtype(dtype).itemsize
+    vals = [_uint(name, v, bits) for v in np.asarray(values, dtype=object).ravel()]
+    if limit is not None and any(v >= limit for v in vals):
+        raise ValueError(f"{name}: every value must be below {limit}")
+    return np.array(vals, dtype=dtype)
+
+
 _live_contexts = weakref.WeakSet()
 
 
@@ -451,7 +488,7 @@ class Lattice:
         return out
 
     def randomize(self, seed, replica=0):
-        self.ctx.check(self.lib.tsu_ising2d_randomize(self.h, int(seed), int(replica)))
+        self.ctx.check(self.lib.tsu_ising2d_randomize(self.h, _seed(seed), _replica(replica)))
 
     def fill(self, value):
         self.ctx.check(self.lib.tsu_ising2d_fill(self.h, int(value)))
@@ -469,16 +506,16 @@ class Lattice:
         self.ctx.check(self.lib.tsu_ising2d_set_kernel(self.h, int(kernel), int(sweeps_per_launch)))
 
     def sweep(self, n_sweeps, seed, sweep0=0, replica=0):
-        self.ctx.check(self.lib.tsu_ising2d_sweep(self.h, int(n_sweeps), int(seed), int(sweep0), int(replica)))
+        self.ctx.check(self.lib.tsu_ising2d_sweep(self.h, int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
 
     def sweep_part(self, n_sweeps, seed, sweep0, part, replica=0):
-        self.ctx.check(self.lib.tsu_ising2d_sweep_part(self.h, int(n_sweeps), int(seed), int(sweep0), int(replica), int(part)))
+        self.ctx.check(self.lib.tsu_ising2d_sweep_part(self.h, int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica), int(part)))
 
     def sample(self, n_burnin, n_sweeps, n_samples, seed, sweep0=0, replica=0):
         """n_burnin sweeps, then n_samples x (n_sweeps sweeps, record): (n_samples, rows, cols) int8, one PCIe transfer."""
         out = np.empty((int(n_samples), self.rows, self.cols), dtype=np.int8)
-        self.ctx.check(self.lib.tsu_ising2d_sample(self.h, int(n_burnin), int(n_sweeps), int(n_samples), int(seed), int(sweep0),
-                                                   int(replica), _ptr(out, _i8p)))
+        self.ctx.check(self.lib.tsu_ising2d_sample(self.h, int(n_burnin), int(n_sweeps), int(n_samples), _seed(seed), _counter("sweep0", sweep0),
+                                                   _replica(replica), _ptr(out, _i8p)))
         return out
 
     def observables(self):
@@ -499,6 +536,13 @@ class Lattice:
         self.ctx.check(self.lib.tsu_ising2d_launch_count(self.h, C.byref(n)))
         return n.value
 
+    def strip_numbering(self):
+        """(generation, restarts) of the tile-resident kernel's strip numbering: generations numbered so far in the running
+        numbering, and how often a numbering started over a cleared strip buffer (read-only)."""
+        g, r = C.c_uint32(0), C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_ising2d_strip_numbering(self.h, C.byref(g), C.byref(r)))
+        return g.value, r.value
+
     def last_sweep_ms(self):
         ms = C.c_float(0)
         self.ctx.check(self.lib.tsu_ising2d_last_sweep_ms(self.h, C.byref(ms)))
@@ -506,8 +550,8 @@ class Lattice:
 
     def cluster_sweep(self, J, T, n_steps, seed, step0=0, replica=0):
         """n_steps Swendsen-Wang steps at coupling J, temperature T, zero field (step counters step0 ..)."""
-        self.ctx.check(self.lib.tsu_ising2d_cluster_sweep(self.h, float(J), float(T), int(n_steps), int(seed), int(step0),
-                                                          int(replica)))
+        self.ctx.check(self.lib.tsu_ising2d_cluster_sweep(self.h, float(J), float(T), int(n_steps), _seed(seed), _counter("step0", step0),
+                                                          _replica(replica)))
 
     def cluster_launch_count(self):
         n = C.c_uint64(0)
@@ -528,7 +572,7 @@ class Lattice:
 
     def disorder_sweep(self, T, n_sweeps, seed, sweep0=0, replica=0):
         """n_sweeps K7 heat-bath sweeps at temperature T (sweep counters sweep0 ..), K1's site uniforms."""
-        self.ctx.check(self.lib.tsu_ising2d_disorder_sweep(self.h, float(T), int(n_sweeps), int(seed), int(sweep0), int(replica)))
+        self.ctx.check(self.lib.tsu_ising2d_disorder_sweep(self.h, float(T), int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
 
     def disorder_energy(self):
         e = C.c_double(0)
@@ -604,7 +648,7 @@ class Lattice3D:
         return out
 
     def randomize(self, seed, replica=0):
-        self.ctx.check(self.lib.tsu_ising3d_randomize(self.h, int(seed), int(replica)))
+        self.ctx.check(self.lib.tsu_ising3d_randomize(self.h, _seed(seed), _replica(replica)))
 
     def fill(self, value):
         self.ctx.check(self.lib.tsu_ising3d_fill(self.h, int(value)))
@@ -618,7 +662,7 @@ class Lattice3D:
 
     def sweep(self, T, n_sweeps, seed, sweep0=0, replica=0):
         """n_sweeps K8 heat-bath sweeps at temperature T (sweep counters sweep0 ..)."""
-        self.ctx.check(self.lib.tsu_ising3d_sweep(self.h, float(T), int(n_sweeps), int(seed), int(sweep0), int(replica)))
+        self.ctx.check(self.lib.tsu_ising3d_sweep(self.h, float(T), int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
 
     def energy(self):
         e = C.c_double(0)
@@ -656,12 +700,12 @@ class Lattice3D:
 
     def cluster_sweep(self, T, n_steps, seed, step0=0, replica=0):
         """n_steps Swendsen-Wang steps on the stored couplings at temperature T, zero field (step counters step0 ..)."""
-        self.ctx.check(self.lib.tsu_ising3d_cluster_sweep(self.h, float(T), int(n_steps), int(seed), int(step0), int(replica)))
+        self.ctx.check(self.lib.tsu_ising3d_cluster_sweep(self.h, float(T), int(n_steps), _seed(seed), _counter("step0", step0), _replica(replica)))
 
     def cluster_sweep_field(self, T, n_steps, seed, step0=0, replica=0):
         """n_steps ghost-spin Swendsen-Wang steps on the stored couplings and field at temperature T (step counters step0 ..); with
         zero field the spins of ``cluster_sweep``."""
-        self.ctx.check(self.lib.tsu_ising3d_cluster_sweep_field(self.h, float(T), int(n_steps), int(seed), int(step0), int(replica)))
+        self.ctx.check(self.lib.tsu_ising3d_cluster_sweep_field(self.h, float(T), int(n_steps), _seed(seed), _counter("step0", step0), _replica(replica)))
 
     def cluster_launch_count(self):
         n = C.c_uint64(0)
@@ -709,7 +753,7 @@ class _TemperingHandle:
 
     def init(self, seed, initial=0):
         """initial 0: random (the lattice's randomize(seed + walker index)); +1 / -1: all up / down."""
-        self.ctx.check(self._fn("init")(self.h, int(seed), int(initial)))
+        self.ctx.check(self._fn("init")(self.h, _seed(seed), int(initial)))
         self._recorded = 0
 
     def run(self, n_rounds, swap_interval, swap=True, record=True):
@@ -1045,7 +1089,7 @@ class _PopulationHandle:
 
     def init(self, seed, initial_sweeps=0):
         """Walker i: key seed + i and the lattice's randomize(seed + i); initial_sweeps sweeps at 1 / beta[0] if beta[0] > 0."""
-        self.ctx.check(self._fn("init")(self.h, int(seed), int(initial_sweeps)))
+        self.ctx.check(self._fn("init")(self.h, _seed(seed), int(initial_sweeps)))
         self._recorded = None
         self.step_count = 0
         self.sweep_count = int(initial_sweeps) if self._beta0 > 0 else 0
@@ -1176,9 +1220,9 @@ def sweep_batch(lattices, n_sweeps, seeds, sweep0s, replicas=None):
         return
     ctx = lattices[0].ctx
     hs = (_vp * n)(*[l.h for l in lattices])
-    sd = (C.c_uint64 * n)(*[int(v) for v in seeds])
-    s0 = (C.c_uint32 * n)(*[int(v) for v in sweep0s])
-    rp = (C.c_uint32 * n)(*([0] * n if replicas is None else [int(v) for v in replicas]))
+    sd = (C.c_uint64 * n)(*_uint_array("seeds", seeds, np.uint64).tolist())
+    s0 = (C.c_uint32 * n)(*_uint_array("sweep0s", sweep0s, np.uint32).tolist())
+    rp = (C.c_uint32 * n)(*([0] * n if replicas is None else _uint_array("replicas", replicas, np.uint32, REPLICA_LIMIT).tolist()))
     ctx.check(lattices[0].lib.tsu_ising2d_sweep_batch(hs, n, int(n_sweeps), sd, s0, rp))
 
 
@@ -1192,9 +1236,9 @@ def cluster_sweep_batch(lattices, n_steps, Js, Ts, seeds, step0s, replicas=None)
     hs = (_vp * n)(*[l.h for l in lattices])
     js = (C.c_double * n)(*[float(v) for v in Js])
     ts = (C.c_double * n)(*[float(v) for v in Ts])
-    sd = (C.c_uint64 * n)(*[int(v) for v in seeds])
-    s0 = (C.c_uint32 * n)(*[int(v) for v in step0s])
-    rp = (C.c_uint32 * n)(*([0] * n if replicas is None else [int(v) for v in replicas]))
+    sd = (C.c_uint64 * n)(*_uint_array("seeds", seeds, np.uint64).tolist())
+    s0 = (C.c_uint32 * n)(*_uint_array("step0s", step0s, np.uint32).tolist())
+    rp = (C.c_uint32 * n)(*([0] * n if replicas is None else _uint_array("replicas", replicas, np.uint32, REPLICA_LIMIT).tolist()))
     ctx.check(lattices[0].lib.tsu_ising2d_cluster_sweep_batch(hs, n, int(n_steps), js, ts, sd, s0, rp))
 
 
@@ -1205,9 +1249,9 @@ def _cluster_batch_3d(entry, lattices, n_steps, Ts, seeds, step0s, replicas):
     ctx = lattices[0].ctx
     hs = (_vp * n)(*[l.h for l in lattices])
     ts = (C.c_double * n)(*[float(v) for v in Ts])
-    sd = (C.c_uint64 * n)(*[int(v) for v in seeds])
-    s0 = (C.c_uint32 * n)(*[int(v) for v in step0s])
-    rp = (C.c_uint32 * n)(*([0] * n if replicas is None else [int(v) for v in replicas]))
+    sd = (C.c_uint64 * n)(*_uint_array("seeds", seeds, np.uint64).tolist())
+    s0 = (C.c_uint32 * n)(*_uint_array("step0s", step0s, np.uint32).tolist())
+    rp = (C.c_uint32 * n)(*([0] * n if replicas is None else _uint_array("replicas", replicas, np.uint32, REPLICA_LIMIT).tolist()))
     ctx.check(getattr(lattices[0].lib, entry)(hs, n, int(n_steps), ts, sd, s0, rp))
 
 
@@ -1285,7 +1329,7 @@ class DenseSystem:
             n_sweeps, self.n)
         self._mirror = None
         self.ctx.check(self.lib.tsu_dense_sweep(self.h, float(T), int(n_sweeps), None if o is None else _ptr(o, _i64p),
-                                                int(seed), int(sweep0), int(replica),
+                                                _seed(seed), _counter("sweep0", sweep0), _replica(replica),
                                                 None if u is None else _ptr(u, _f64p)))
 
     def sample(self, T, n_burnin, n_sweeps, n_samples, seed=0, sweep0=0, replica=0, order=None, replay_uniforms=None):
@@ -1296,7 +1340,7 @@ class DenseSystem:
         out = np.empty((int(n_samples), self.n), dtype=np.int8)
         self._mirror = None
         self.ctx.check(self.lib.tsu_dense_sample(self.h, float(T), int(n_burnin), int(n_sweeps), int(n_samples),
-                                                 None if o is None else _ptr(o, _i64p), int(seed), int(sweep0), int(replica),
+                                                 None if o is None else _ptr(o, _i64p), _seed(seed), _counter("sweep0", sweep0), _replica(replica),
                                                  None if u is None else _ptr(u, _f64p), _ptr(out, _i8p)))
         return out
 
@@ -1308,8 +1352,8 @@ class DenseSystem:
         u = None if replay_uniforms is None else np.ascontiguousarray(replay_uniforms, dtype=np.float64).reshape(steps, self.n)
         out = np.empty((steps, self.n), dtype=np.int8)
         self._mirror = None
-        self.ctx.check(self.lib.tsu_dense_anneal(self.h, _ptr(t, _f64p), steps, None if o is None else _ptr(o, _i64p), int(seed),
-                                                 int(sweep0), int(replica), None if u is None else _ptr(u, _f64p), _ptr(out, _i8p)))
+        self.ctx.check(self.lib.tsu_dense_anneal(self.h, _ptr(t, _f64p), steps, None if o is None else _ptr(o, _i64p), _seed(seed),
+                                                 _counter("sweep0", sweep0), _replica(replica), None if u is None else _ptr(u, _f64p), _ptr(out, _i8p)))
         return out
 
     def sweep_replicas(self, states, temperatures, n_sweeps, seeds, sweep0s, replicas=None, replay_uniforms=None):
@@ -1317,9 +1361,9 @@ class DenseSystem:
         st = np.ascontiguousarray(states, dtype=np.int8).reshape(-1, self.n).copy()
         R = st.shape[0]
         t = np.ascontiguousarray(temperatures, dtype=np.float64).reshape(R)
-        sd = np.ascontiguousarray(seeds, dtype=np.uint64).reshape(R)
-        s0 = np.ascontiguousarray(sweep0s, dtype=np.uint32).reshape(R)
-        rp = np.zeros(R, dtype=np.uint32) if replicas is None else np.ascontiguousarray(replicas, dtype=np.uint32).reshape(R)
+        sd = _uint_array("seeds", seeds, np.uint64).reshape(R)
+        s0 = _uint_array("sweep0s", sweep0s, np.uint32).reshape(R)
+        rp = np.zeros(R, dtype=np.uint32) if replicas is None else _uint_array("replicas", replicas, np.uint32, REPLICA_LIMIT).reshape(R)
         u = None if replay_uniforms is None else np.ascontiguousarray(replay_uniforms, dtype=np.float64).reshape(R, int(n_sweeps), self.n)
         self._mirror = None  # (systems beyond the one-workgroup kernels are swept replica by replica through the resident state)
         self.ctx.check(self.lib.tsu_dense_sweep_replicas(self.h, R, _ptr(t, _f64p), int(n_sweeps), _ptr(st, _i8p), _ptr(sd, _u64p),
@@ -1462,12 +1506,12 @@ class SparseSystem:
         return out
 
     def sweep(self, T, n_sweeps, seed=0, sweep0=0, replica=0):
-        self.ctx.check(self.lib.tsu_sparse_sweep(self.h, float(T), int(n_sweeps), int(seed), int(sweep0), int(replica)))
+        self.ctx.check(self.lib.tsu_sparse_sweep(self.h, float(T), int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
 
     def sample(self, T, n_burnin, n_sweeps, n_samples, seed=0, sweep0=0, replica=0):
         out = np.empty((int(n_samples), self.n), dtype=np.int8)
-        self.ctx.check(self.lib.tsu_sparse_sample(self.h, float(T), int(n_burnin), int(n_sweeps), int(n_samples), int(seed),
-                                                  int(sweep0), int(replica), _ptr(out, _i8p)))
+        self.ctx.check(self.lib.tsu_sparse_sample(self.h, float(T), int(n_burnin), int(n_sweeps), int(n_samples), _seed(seed),
+                                                  _counter("sweep0", sweep0), _replica(replica), _ptr(out, _i8p)))
         return out
 
     def plan(self):
@@ -1517,7 +1561,7 @@ class SparseBatch:
         self.ctx.check(self.lib.tsu_sparse_batch_set_temperatures(self.h, _ptr(t, _f64p)))
 
     def init(self, seed, initial=0):
-        self.ctx.check(self.lib.tsu_sparse_batch_init(self.h, int(seed), int(initial)))
+        self.ctx.check(self.lib.tsu_sparse_batch_init(self.h, _seed(seed), int(initial)))
 
     def set_state(self, ladder, slot, bits):
         b = np.ascontiguousarray(bits, dtype=np.int8).reshape(self.n)
@@ -1646,12 +1690,12 @@ class LangevinChains:
 
     def restart(self, x_init, amp, seed, chain0=0):
         xi = np.ascontiguousarray(np.broadcast_to(np.asarray(x_init, dtype=np.float32), (self.dim,)))
-        self.ctx.check(self.lib.tsu_langevin_restart(self.h, _ptr(xi, _f32p), float(amp), int(seed), int(chain0)))
+        self.ctx.check(self.lib.tsu_langevin_restart(self.h, _ptr(xi, _f32p), float(amp), _seed(seed), _counter("chain0", chain0)))
 
     def step(self, n_steps, dt, gamma, T, seed, step0=0, chain0=0, trajectory=False):
         traj = np.empty((n_steps, self.n_chains, self.dim), dtype=np.float32) if trajectory else None
-        self.ctx.check(self.lib.tsu_langevin_step(self.h, int(n_steps), float(dt), float(gamma), float(T), int(seed),
-                                                  int(step0), int(chain0),
+        self.ctx.check(self.lib.tsu_langevin_step(self.h, int(n_steps), float(dt), float(gamma), float(T), _seed(seed),
+                                                  _counter("step0", step0), _counter("chain0", chain0),
                                                   None if traj is None else _ptr(traj, _f32p)))
         return traj
 
