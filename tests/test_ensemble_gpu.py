@@ -1,13 +1,30 @@
 """Tempering ensembles on the GPU (tsu_pte2d_* / tsu_pte3d_*, csrc/pte_host.h): sample s of an ensemble equals the standalone ladder
 (LatticeTempering / LatticeTempering3D) on that sample's disorder with seed = seeds[s] bit for bit -- spins at every slot, E, M, q,
 walker, q_link, modes, attempts, accepts, round trips, the slot tables and the counters -- for every walker group the sweeps use;
-seeds and disorders vary independently; split runs, S = 1 and swap=False; the spins round trip; the launch count; errors; the scan.
+the same with 129 temperatures, and at the ceiling of 65535 walkers; seeds and disorders vary independently; split runs, S = 1
+and swap=False; the spins round trip; the launch count; errors; the scan.
 The ladders' own tests compare them with the NumPy twins and with exact enumeration, so identity with the ladders carries those
 checks over to every sample."""
+import importlib.util
+import os
+import sys
+
 import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
+
+
+def _long_ladder():
+    """tests/helpers/long_ladder.py, one instance per process (the long-ladder tests share it)."""
+    name = "tsu_tests_long_ladder"
+    if name not in sys.modules:
+        spec = importlib.util.spec_from_file_location(name, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers", "long_ladder.py"))
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules[name] = mod
+        spec.loader.exec_module(mod)
+    return sys.modules[name]
+
 
 TS = [0.4, 0.9, 1.5, 2.27, 5.0]
 SEEDS = [7, 2 ** 32 + 9, 3]  # the high key word, and seeds that are not consecutive
@@ -54,7 +71,7 @@ def _flags(shape, periodic, ladders):
 
 def _record(pt, hist_of, spins_of, stats, energies):
     """Everything the contract names, of one sample: per ladder the history rows and the spins at every slot; the statistics."""
-    R, nl = len(TS), pt.ladders
+    R, nl = len(pt.temperatures), pt.ladders
     return {"hist": [hist_of(k) for k in range(nl)], "spins": [[spins_of(w, k) for w in range(R)] for k in range(nl)],
             "stats": stats, "E": energies[0], "M": energies[1]}
 
@@ -128,6 +145,106 @@ def test_every_sample_equals_its_ladder(hip, monkeypatch, shape, periodic, ladde
         for s in range(3):
             _assert_same(_sample_record(ens, s), want[s], f"sample {s} of {shape} group {group}")
         assert ens.sweep_count == 8
+    finally:
+        ens.close()
+
+
+_long_references = {}
+
+
+def _long_reference(shape, periodic, ladders):
+    key = (shape, periodic, ladders)
+    if key not in _long_references:
+        Ts = _long_ladder().temperatures(129)
+        js, h = _disorder(shape, periodic, 2, 200 + sum(shape))
+        flags = _flags(shape, periodic, ladders)
+        _long_references[key] = (Ts, js, h, [_ladder_record(shape, periodic, ladders, tuple(a[s] for a in js), h[s], SEEDS[s], Ts=Ts, **flags)
+                                             for s in range(2)])
+    return _long_references[key]
+
+
+@pytest.mark.parametrize("shape,periodic", [SHAPES_3D[0], SHAPES_2D[0]])
+@pytest.mark.parametrize("ladders", [1, 2])
+@pytest.mark.parametrize("group", ["1", "7", "nlR"])
+def test_every_sample_equals_its_long_ladder(hip, monkeypatch, shape, periodic, ladders, group):
+    """The identity above with S = 2 and 129 temperatures: the swap pass of a (sample, ladder) row takes three trips of its 64 lanes
+    and finds its tables at k R offsets, the per-slot passes decode (sample, slot) from grid indices up to 2 x 129, and
+    TSU_PT_GROUP=7 leaves ragged groups that end inside a sample (129 = 18 x 7 + 3, 258 = 36 x 7 + 6)."""
+    Ts, js, h, want = _long_reference(shape, periodic, ladders)
+    monkeypatch.setenv("TSU_PT_GROUP", str(ladders * len(Ts)) if group == "nlR" else group)
+    ens = _ensemble(shape, periodic, ladders, js, h, SEEDS[:2], Ts=Ts, **_flags(shape, periodic, ladders))
+    try:
+        ens.run(4, 2)
+        full = ens.history()
+        assert full["E"].shape == (2, 4, len(Ts)) and (("q" in full) == (ladders == 2))
+        for s in range(2):
+            _assert_same(_sample_record(ens, s), want[s], f"sample {s} of {shape} group {group}")
+            assert (want[s]["stats"]["walker_at_slot"][:, 64:] != np.arange(64, len(Ts))).any(), "no slot past 63 changed hands"
+        assert ens.sweep_count == 8
+    finally:
+        ens.close()
+
+
+def _ceiling_handles(hip, shape):
+    if len(shape) == 2:
+        return hip.TemperingEnsemble, hip.TemperingLattice
+    return hip.TemperingEnsemble3D, hip.TemperingLattice3D
+
+
+@pytest.mark.parametrize("shape", [(2, 2), (2, 2, 2)])
+@pytest.mark.parametrize("S,R,ladders", [(257, 255, 1), (127, 256, 2)])
+def test_the_walker_ceiling(hip, monkeypatch, shape, S, R, ladders):
+    """65535 walkers (257 x 255) and 65024 (127 x 2 x 256) on an open lattice of 4 or 8 sites, the raw handles: the energy passes
+    launch a grid of y = S nl R rows and the overlap pass y = S R, at or next to the grid-y limit.  One recorded round of two sweeps
+    with swaps on dyadic disorder (tests/helpers/long_ladder.py), different per sample: samples 0, S // 2 and S - 1 equal standalone
+    ladders on their disorder and seed -- history, tables, energies, spins at slots 0, 64 and R - 1; every sample's energies are
+    finite and its sums of spins even integers within +-N."""
+    monkeypatch.delenv("TSU_PT_GROUP", raising=False)
+    ll = _long_ladder()
+    Ensemble, Ladder = _ceiling_handles(hip, shape)
+    N = int(np.prod(shape))
+    Ts = ll.temperatures(R)
+    per_sample = [ll.dyadic_disorder(shape, False, 1000 + s) for s in range(S)]
+    dis = tuple(np.stack([d[j] for d in per_sample]) for j in range(len(shape) + 1))
+    picked = (0, S // 2, S - 1)
+    for a in picked:
+        for b in picked:
+            assert a == b or any((dis[j][a] != dis[j][b]).any() for j in range(len(dis)))
+    seeds = [5000 + 1000 * s for s in range(S)]
+    ens = Ensemble(*shape, False, S, R, ladders)
+    try:
+        ens.set_disorder(*dis)
+        ens.set_temperatures(Ts)
+        ens.init(seeds, 0)
+        ens.run(1, 2, swap=True, record=True)
+        hist, st, (E, M) = ens.history(), ens.stats(), ens.energies()
+        assert E.shape == M.shape == (S, ladders, R) and np.isfinite(E).all()
+        assert (np.abs(M) <= N).all() and (M % 2 == 0).all()
+        assert st["sweep_count"] == 2 and st["round_count"] == 1 and (st["attempts"] == 1).all()
+        assert (np.sort(st["walker_at_slot"], axis=-1) == np.arange(R)).all()
+        for s in picked:
+            one = Ladder(*shape, False, R, ladders)
+            try:
+                one.set_disorder(*per_sample[s])
+                one.set_temperatures(Ts)
+                one.init(seeds[s], 0)
+                one.run(1, 2, swap=True, record=True)
+                h1, s1, (E1, M1) = one.history(), one.stats(), one.energies()
+                for key in ("E", "M", "walker"):
+                    assert np.array_equal(hist[key][:, s], h1[key]), (s, key)
+                if ladders == 2:
+                    assert np.array_equal(hist["q"][:, s], h1["q"]), s
+                for key in STAT_KEYS:
+                    assert np.array_equal(st[key][s], s1[key]), (s, key)
+                assert np.array_equal(E[s], E1) and np.array_equal(M[s], M1), s
+                for k in range(ladders):
+                    for slot in (0, 64, R - 1):
+                        got = ens.get_spins(s, k, slot)
+                        assert np.array_equal(got, one.get_spins(k, slot)), (s, k, slot)
+                        assert E[s, k, st["walker_at_slot"][s, k, slot]] == ll.energy(got, False, per_sample[s])
+                assert s1["accepts"].sum() > 0
+            finally:
+                one.close()
     finally:
         ens.close()
 
