@@ -380,6 +380,10 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * _hip.CLUSTER_FIELD_SIGNATURES in Python. */
 #include "tsu_hip_cluster_field.h"
 
+/* K9: multispin-coded sweeps of the bimodal Edwards-Anderson glass, 64 disorder samples per word (tsu_msc_*): declared in
+ * tsu_hip_multispin.h, which this header includes; its prototypes are _hip.MULTISPIN_SIGNATURES in Python. */
+#include "tsu_hip_multispin.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

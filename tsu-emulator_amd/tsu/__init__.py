@@ -34,11 +34,13 @@ from .models import (  # noqa: F401
     LatticeTempering3D,
     LatticeTemperingEnsemble,
     LatticeTemperingEnsemble3D,
+    MultispinGlass3D,
     PopulationAnnealing,
     PopulationAnnealing3D,
     demonstrate_phase_transition,
     edwards_anderson_samples,
     ensemble_summary,
+    multispin_scan_3d,
     temperature_scan_3d,
     tempering_ensemble_scan,
     tempering_ensemble_scan_3d,
@@ -53,6 +55,6 @@ __all__ = [
     "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d",
     "PopulationAnnealing", "PopulationAnnealing3D",
     "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
-    "tempering_ensemble_scan", "tempering_ensemble_scan_3d",
+    "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d",
     "GraphTempering",
 ]

@@ -269,6 +269,25 @@ CLUSTER_FIELD_SIGNATURES = {
                                                         C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
 }
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_multispin.h (the header tsu_hip.h includes) one to one
+MULTISPIN_SIGNATURES = {
+    "tsu_msc_thresholds": (C.c_int, [C.c_double, _u64p]),
+    "tsu_msc_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "tsu_msc_destroy": (C.c_int, [_vp]),
+    "tsu_msc_route": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "tsu_msc_set_couplings": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
+    "tsu_msc_set_planes": (C.c_int, [_vp, _u64p]),
+    "tsu_msc_get_planes": (C.c_int, [_vp, _u64p]),
+    "tsu_msc_set_seeds": (C.c_int, [_vp, _u64p]),
+    "tsu_msc_randomize": (C.c_int, [_vp]),
+    "tsu_msc_fill": (C.c_int, [_vp, C.c_int8]),
+    "tsu_msc_set_temperatures": (C.c_int, [_vp, _f64p]),
+    "tsu_msc_sweep": (C.c_int, [_vp, C.c_int, C.c_uint32]),
+    "tsu_msc_measure": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i64p]),
+    "tsu_msc_launch_count": (C.c_int, [_vp, _u64p]),
+}
+MSC_ROUTE_AUTO, MSC_ROUTE_SMALL, MSC_ROUTE_HBM = 0, 1, 2
+
 _lib = None
 
 
@@ -288,7 +307,8 @@ def load_library():
     for name, (res, args) in (list(SIGNATURES.items()) + list(CLUSTER3D_SIGNATURES.items()) + list(CORRELATION_SIGNATURES.items())
                               + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())
                               + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())
-                              + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())):
+                              + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())
+                              + list(MULTISPIN_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -710,6 +730,123 @@ class Lattice3D:
     def cluster_launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_ising3d_cluster_launch_count(self.h, C.byref(n)))
+        return n.value
+
+
+def msc_thresholds(T):
+    """Host helper of the library (no GPU needed): K9's table[f + 6] for f = -6 .. 6 as uint64 (tsu_msc_thresholds)."""
+    lib = load_library()
+    t = np.zeros(13, dtype=np.uint64)
+    if lib.tsu_msc_thresholds(float(T), _ptr(t, _u64p)) != TSU_OK:
+        raise ValueError("Temperature must be positive")
+    return t
+
+
+def msc_pack(bits):
+    """(S, ...) booleans -> (ceil(S / 64), ...) uint64: bit b of word-plane w is sample 64 w + b; pad bits 0."""
+    bits = np.asarray(bits, dtype=bool)
+    S, shape = bits.shape[0], bits.shape[1:]
+    W = (S + 63) // 64
+    padded = np.zeros((W * 64,) + shape, dtype=np.uint8)
+    padded[:S] = bits
+    by_word = np.moveaxis(padded.reshape((W, 64) + shape), 1, -1)
+    return np.ascontiguousarray(np.packbits(by_word, axis=-1, bitorder="little")).view("<u8").reshape((W,) + shape)
+
+
+def msc_unpack(words, n_samples):
+    """(W, ...) uint64 -> (n_samples, ...) booleans, the inverse of :func:`msc_pack` (pad bits dropped)."""
+    words = np.ascontiguousarray(words, dtype="<u8")
+    W, shape = words.shape[0], words.shape[1:]
+    by_word = np.unpackbits(words.view(np.uint8).reshape((W,) + shape + (8,)), axis=-1, bitorder="little")
+    return np.moveaxis(by_word, -1, 1).reshape((W * 64,) + shape)[:int(n_samples)].astype(bool)
+
+
+class MultispinLattice:
+    """tsu_msc handle (K9): n_temps x replicas x ceil(n_samples / 64) planes of uint64, 64 samples of a +-1 glass per word."""
+
+    def __init__(self, depth, rows, cols, periodic, n_temps, replicas, n_samples, route=MSC_ROUTE_AUTO, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.shape = (int(depth), int(rows), int(cols))
+        self.periodic = periodic_axes(periodic)
+        self.n_temps, self.replicas, self.n_samples = int(n_temps), int(replicas), int(n_samples)
+        self.words = (self.n_samples + 63) // 64
+        mask = sum(1 << a for a in range(3) if self.periodic[a])
+        h = _vp()
+        self.ctx.check(self.lib.tsu_msc_create(self.ctx.h, *self.shape, mask, self.n_temps, self.replicas, self.n_samples, int(route),
+                                               C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_msc_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    @property
+    def route(self):
+        r = C.c_int(0)
+        self.ctx.check(self.lib.tsu_msc_route(self.h, C.byref(r)))
+        return r.value
+
+    def set_couplings(self, J_right, J_down, J_layer):
+        """Packed couplings, (words, depth, rows, cols) uint64 each; a set bit is J = -1."""
+        a = [np.ascontiguousarray(x, dtype=np.uint64).reshape((self.words,) + self.shape) for x in (J_right, J_down, J_layer)]
+        self.ctx.check(self.lib.tsu_msc_set_couplings(self.h, *(_ptr(x, _u64p) for x in a)))
+
+    def _plane_shape(self):
+        return (self.n_temps, self.replicas, self.words) + self.shape
+
+    def set_planes(self, planes):
+        p = np.ascontiguousarray(planes, dtype=np.uint64).reshape(self._plane_shape())
+        self.ctx.check(self.lib.tsu_msc_set_planes(self.h, _ptr(p, _u64p)))
+
+    def get_planes(self):
+        out = np.empty(self._plane_shape(), dtype=np.uint64)
+        self.ctx.check(self.lib.tsu_msc_get_planes(self.h, _ptr(out, _u64p)))
+        return out
+
+    def set_seeds(self, seeds):
+        s = _uint_array("seeds", seeds, np.uint64)
+        if s.size != self.n_temps * self.replicas:
+            raise ValueError(f"seeds must hold n_temps x replicas = {self.n_temps * self.replicas} values, got {s.size}")
+        self.ctx.check(self.lib.tsu_msc_set_seeds(self.h, _ptr(s, _u64p)))
+
+    def randomize(self):
+        self.ctx.check(self.lib.tsu_msc_randomize(self.h))
+
+    def fill(self, value):
+        self.ctx.check(self.lib.tsu_msc_fill(self.h, int(value)))
+
+    def set_temperatures(self, T):
+        t = np.ascontiguousarray(T, dtype=np.float64).ravel()
+        if t.size != self.n_temps:
+            raise ValueError(f"expected {self.n_temps} temperatures, got {t.size}")
+        self.ctx.check(self.lib.tsu_msc_set_temperatures(self.h, _ptr(t, _f64p)))
+
+    def sweep(self, n_sweeps, sweep0=0):
+        self.ctx.check(self.lib.tsu_msc_sweep(self.h, int(n_sweeps), _counter("sweep0", sweep0)))
+
+    def measure(self):
+        """(unsat, sum, q, q_link): int64 arrays (n_temps, replicas, S), (n_temps, replicas, S), and with two replicas
+        (n_temps, S) each (else None); pad columns dropped."""
+        cols = self.words * 64
+        unsat = np.zeros((self.n_temps, self.replicas, cols), np.int64)
+        ssum = np.zeros_like(unsat)
+        two = self.replicas == 2
+        q = np.zeros((self.n_temps, cols), np.int64) if two else None
+        ql = np.zeros((self.n_temps, cols), np.int64) if two else None
+        self.ctx.check(self.lib.tsu_msc_measure(self.h, _ptr(unsat, _i64p), _ptr(ssum, _i64p), _ptr(q, _i64p) if two else None,
+                                                _ptr(ql, _i64p) if two else None))
+        S = self.n_samples
+        return (unsat[..., :S].copy(), ssum[..., :S].copy(), q[..., :S].copy() if two else None, ql[..., :S].copy() if two else None)
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_msc_launch_count(self.h, C.byref(n)))
         return n.value
 
 

@@ -1757,6 +1757,215 @@ def tempering_ensemble_scan_3d(size, temperatures, *, couplings, field=None, n_e
     return _ensemble_scan(pt, temperatures, n_equilibrate, n_measure, measure_every, swap)
 
 
+# ---------------------------------------------------------------------------------------------------- multispin coding (K9)
+MULTISPIN_ROUTES = {"small": _hip.MSC_ROUTE_SMALL, "hbm": _hip.MSC_ROUTE_HBM}
+
+
+def _multispin_couplings(shape, periodic, couplings, field=None):
+    """Validate bimodal couplings of S samples (before any device call): every bond +-1, except the last slice of an open axis,
+    which must be 0 as :class:`IsingModel3D` demands.  Returns (S, the three (S, D, R, C) boolean arrays 'J = -1')."""
+    if field is not None:
+        raise ValueError("field: multispin coding runs the zero-field +-J glass (fields stay on IsingModel3D / the ensembles)")
+    for p, n, name in zip(periodic, shape, ("depth", "rows", "cols")):
+        if p and (n % 2 or n < 4):
+            raise ValueError(f"a periodic axis needs an even length >= 4 ({name} = {n})")
+    names = ("J_right", "J_down", "J_layer")
+    if couplings is None or len(couplings) not in (2, 3):
+        raise ValueError("couplings must be (J_right, J_down, J_layer), or (J_right, J_down) for size=(1, R, C)")
+    arrays = [np.asarray(a) for a in couplings]
+    if len(arrays) == 2:
+        if shape[0] != 1:
+            raise ValueError(f"two coupling arrays describe one layer: size must be (1, R, C), got {shape}")
+        arrays = [a.reshape((a.shape[0], 1) + a.shape[1:]) if a.ndim == 3 else a for a in arrays]
+        arrays.append(np.zeros((arrays[0].shape[0],) + shape, np.float32))
+    S = arrays[0].shape[0] if arrays[0].ndim == 4 else -1
+    out = []
+    # array k holds the bonds along lattice axis 2 - k (J_right: the last axis)
+    for k, (a, name) in enumerate(zip(arrays, names)):
+        if a.shape != (S,) + shape or S < 1:
+            raise ValueError(f"{name} must have shape (n_samples,) + {shape}, got {a.shape}")
+        axis = 2 - k
+        body = a
+        if not periodic[axis]:
+            last = np.take(a, -1, axis=axis + 1)
+            if np.any(last != 0):
+                raise ValueError(f"{name}: open {('depth', 'rows', 'cols')[axis]} axis: the last slice must be 0")
+            body = np.delete(a, -1, axis=axis + 1)
+        if not np.all((body == 1) | (body == -1)):
+            bad = body[(body != 1) & (body != -1)].ravel()[0]
+            raise ValueError(f"{name}: multispin coding takes J = +-1 only, got {bad!r} (Gaussian and diluted bonds stay on K7 / K8)")
+        out.append(a == -1)
+    return S, out
+
+
+class MultispinGlass3D:
+    """S disorder samples of the bimodal (J = +-1, zero field) Edwards-Anderson glass, 64 samples per 64-bit word (K9).
+
+    ``MultispinGlass3D(size, temperatures, couplings=edwards_anderson_samples(size, S, kind="bimodal"), replicas=2)``: every sample
+    runs at every temperature, ``replicas`` (1 or 2) independent copies each.  ``size=(1, R, C)`` with ``periodic=(False, p, p)`` takes
+    the ``dims=2`` arrays.  Sample s of (slot t, replica a) is, bit for bit, ``IsingModel3D(size, couplings=sample s,
+    temperature=T[t], periodic=..., seed=seeds[t][a])`` under ``gibbs_update()``; ``seeds[t][a] = seed + a * n_temps + t`` by default.
+
+    **The samples of one word share their random numbers** (the site's one uniform decides all 64): each sample's chain is exactly
+    the single lattice's, but samples 64 w .. 64 w + 63 are correlated with each other, so errors over samples inside one word are not
+    independent.  Two replicas of one sample therefore never share a word: they live in different planes with different seeds.
+
+    ``route``: ``"small"`` (planes of at most 8192 sites: the spins stay in LDS for all sweeps of a call, one launch per call) or
+    ``"hbm"`` (one launch per half-sweep for all planes); by default the small route where it fits.  No swaps between temperatures.
+    """
+
+    def __init__(self, size, temperatures, *, couplings, periodic=True, replicas: int = 1, seed: Optional[int] = None, seeds=None,
+                 initial: str = "random", route: Optional[str] = None, field=None):
+        self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
+        self.n_spins = self.depth * self.rows * self.cols
+        self.periodic = _hip.periodic_axes(periodic)
+        self.temperatures = np.asarray(temperatures, dtype=np.float64).ravel()
+        if self.temperatures.size < 1 or not np.all(self.temperatures > 0):
+            raise ValueError("Temperature must be positive")
+        if replicas not in (1, 2):
+            raise ValueError("replicas must be 1 or 2")
+        if initial not in ("random", "up", "down"):
+            raise ValueError("initial must be 'random', 'up' or 'down'")
+        if route is not None and route not in MULTISPIN_ROUTES:
+            raise ValueError("route must be 'small', 'hbm' or None")
+        self.n_samples, packed = _multispin_couplings(self.shape, self.periodic, couplings, field)
+        self.replicas = int(replicas)
+        nT = self.temperatures.size
+        if seeds is not None:
+            self.seeds = np.array([[int(x) for x in row] for row in np.asarray(seeds, dtype=object).reshape(nT, self.replicas)], dtype=object)
+        else:
+            base = int(seed) if seed is not None else (
+                int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
+            self.seeds = np.array([[base + a * nT + t for a in range(self.replicas)] for t in range(nT)], dtype=object)
+        self.n_bonds = lattice_bond_count(self.shape, self.periodic)
+        self.sweep_count = 0
+        self._msc = _hip.MultispinLattice(self.depth, self.rows, self.cols, self.periodic, nT, self.replicas, self.n_samples,
+                                          _hip.MSC_ROUTE_AUTO if route is None else MULTISPIN_ROUTES[route])
+        self._msc.set_couplings(*(_hip.msc_pack(a) for a in packed))
+        self._msc.set_temperatures(self.temperatures)
+        self._msc.set_seeds(self.seeds.ravel())
+        if initial == "random":
+            self._msc.randomize()
+        else:
+            self._msc.fill(1 if initial == "up" else -1)
+
+    def close(self) -> None:
+        self._msc.close()
+
+    @property
+    def route(self) -> str:
+        return "small" if self._msc.route == _hip.MSC_ROUTE_SMALL else "hbm"
+
+    @property
+    def launch_count(self) -> int:
+        return self._msc.launch_count()
+
+    def sweep(self, n: int = 1) -> "MultispinGlass3D":
+        """n heat-bath sweeps of every sample at every temperature (and of both replicas)."""
+        self._msc.sweep(int(n), self.sweep_count)
+        self.sweep_count += int(n)
+        return self
+
+    def _per_replica(self, x):
+        return x if self.replicas == 2 else x[:, 0]
+
+    def energies(self) -> np.ndarray:
+        """E = -sum_bonds J s s' per sample, float64 of exact integers: (n_temps, S), or (n_temps, 2, S) with two replicas."""
+        unsat = self._msc.measure()[0]
+        return self._per_replica((2 * unsat - self.n_bonds).astype(np.float64))
+
+    def magnetizations(self) -> np.ndarray:
+        """sum s / N per sample, the shape of :meth:`energies`."""
+        return self._per_replica(self._msc.measure()[1] / self.n_spins)
+
+    def overlaps(self) -> np.ndarray:
+        """q / N = sum_i a_i b_i / N of the two replicas, (n_temps, S)."""
+        if self.replicas != 2:
+            raise ValueError("overlaps need replicas=2")
+        return self._msc.measure()[2] / self.n_spins
+
+    def link_overlaps(self) -> np.ndarray:
+        """q_l = sum_bonds a_i a_j b_i b_j / N_b of the two replicas, (n_temps, S)."""
+        if self.replicas != 2:
+            raise ValueError("link_overlaps need replicas=2")
+        return self._msc.measure()[3] / self.n_bonds
+
+    def spin_array(self) -> np.ndarray:
+        """Every spin: int8 (n_temps, replicas, S, D, R, C)."""
+        planes = self._msc.get_planes()
+        nT, A = planes.shape[:2]
+        bits = np.stack([np.stack([_hip.msc_unpack(planes[t, a], self.n_samples) for a in range(A)]) for t in range(nT)])
+        return np.where(bits, 1, -1).astype(np.int8)
+
+    def _check_index(self, sample, slot, replica):
+        if not 0 <= int(sample) < self.n_samples:
+            raise ValueError(f"sample {sample} outside 0 .. {self.n_samples - 1}")
+        if not 0 <= int(slot) < self.temperatures.size:
+            raise ValueError(f"slot {slot} outside 0 .. {self.temperatures.size - 1}")
+        if not 0 <= int(replica) < self.replicas:
+            raise ValueError(f"replica {replica} outside 0 .. {self.replicas - 1}")
+
+    def spins(self, sample: int, slot: int, replica: int = 0) -> np.ndarray:
+        """int8 (D, R, C) spins of one sample at one temperature slot."""
+        self._check_index(sample, slot, replica)
+        word = self._msc.get_planes()[int(slot), int(replica), int(sample) // 64]
+        return np.where((word >> np.uint64(int(sample) % 64)) & np.uint64(1), 1, -1).astype(np.int8)
+
+    def set_spins(self, sample: int, slot: int, spins, replica: int = 0) -> None:
+        self._check_index(sample, slot, replica)
+        v = np.asarray(spins).reshape(self.shape)
+        if not np.all((v == 1) | (v == -1)):
+            raise ValueError("spins must be +1 / -1")
+        planes = self._msc.get_planes()
+        bit = np.uint64(1) << np.uint64(int(sample) % 64)
+        word = planes[int(slot), int(replica), int(sample) // 64]
+        planes[int(slot), int(replica), int(sample) // 64] = np.where(v == 1, word | bit, word & ~bit)
+        self._msc.set_planes(planes)
+
+
+def multispin_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 1000, n_measure: int = 50, measure_every: int = 1,
+                      replicas: int = 2, periodic=True, seed: Optional[int] = None, seeds=None, initial: str = "random",
+                      route: Optional[str] = None) -> dict:
+    """Equilibrate S bimodal samples at every temperature (:class:`MultispinGlass3D`, no swaps), then take ``n_measure`` measurements
+    ``measure_every`` sweeps apart.  Per sample, arrays (S, n_temps) under the keys of :func:`tempering_ensemble_scan_3d`:
+    ``energy`` (<E> / N of replica 0), ``magnetization`` (<|m|>) and, with two replicas, ``overlap`` (<|q|>), ``overlap_sq``,
+    ``overlap_4`` and ``link_overlap`` (<q_l>); ``"average"``: :func:`ensemble_summary` of them.  The samples of one 64-bit word
+    share their random numbers: errors over samples within a word are correlated."""
+    if replicas not in (1, 2):
+        raise ValueError("replicas must be 1 or 2")
+    if int(measure_every) < 1 or int(n_measure) < 1 or int(n_equilibrate) < 0:
+        raise ValueError("measure_every and n_measure must be >= 1, n_equilibrate >= 0")
+    temperatures = np.asarray(temperatures, dtype=float)
+    if seeds is None and seed is None:
+        seed = 0
+    g = MultispinGlass3D(size, temperatures, couplings=couplings, periodic=periodic, replicas=replicas, seed=seed, seeds=seeds,
+                         initial=initial, route=route)
+    try:
+        g.sweep(int(n_equilibrate))
+        N, nb = g.n_spins, g.n_bonds
+        acc = {k: [] for k in ("e", "m", "q", "ql")}
+        for _ in range(int(n_measure)):
+            g.sweep(int(measure_every))
+            unsat, ssum, q, ql = g._msc.measure()
+            acc["e"].append((2 * unsat[:, 0] - nb) / N)
+            acc["m"].append(ssum[:, 0] / N)
+            if replicas == 2:
+                acc["q"].append(q / N)
+                acc["ql"].append(ql / nb)
+        series = {k: np.stack(v) for k, v in acc.items() if v}  # (n_measure, n_temps, S)
+        res = {"energy": series["e"].mean(axis=0).T, "magnetization": np.abs(series["m"]).mean(axis=0).T}
+        if replicas == 2:
+            res["overlap"] = np.abs(series["q"]).mean(axis=0).T
+            res["overlap_sq"] = (series["q"] ** 2).mean(axis=0).T
+            res["overlap_4"] = (series["q"] ** 4).mean(axis=0).T
+            res["link_overlap"] = series["ql"].mean(axis=0).T
+        res["temperatures"] = temperatures
+        res["average"] = ensemble_summary(res)
+    finally:
+        g.close()
+    return res
+
+
 # ---------------------------------------------------------------------------------------------------- population annealing
 POPULATION_WEIGHT_ONE = 1 << 30  # the weight of a step's minimum-energy walker
 
