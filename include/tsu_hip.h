@@ -384,6 +384,10 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * tsu_hip_multispin.h, which this header includes; its prototypes are _hip.MULTISPIN_SIGNATURES in Python. */
 #include "tsu_hip_multispin.h"
 
+/* K9: parallel tempering of a multispin-coded glass, per-sample swaps and the masked exchange on the device (tsu_msc_pt_*):
+ * declared in tsu_hip_multispin_pt.h, which this header includes; its prototypes are _hip.MULTISPIN_PT_SIGNATURES in Python. */
+#include "tsu_hip_multispin_pt.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -23,25 +23,14 @@
 // and the differing bonds of the pair.  A lane adds its sites' one-bit words into bit-sliced vertical counters (8 planes: at most
 // 192 additions per lane), expands them per bit into LDS counters of the workgroup, and the workgroup adds those with 64-bit
 // vector atomics.
+//
+// The handle and what builds the kernels' parameters from it live in multispin_host.h, shared with multispin_pt.hip (tempering:
+// the swap plan and the masked exchange), which takes its measurements through msc_enqueue_measure below.
 #include <cmath>
 #include <new>
 #include <vector>
 
-#include "multispin_dev.h"
-
-struct tsu_msc {
-    tsu_ctx* ctx;
-    MscGeo g;
-    int nT, A, S, W;
-    int route;
-    uint64_t* d_s;       // nT * A * W planes
-    uint64_t* d_j;       // 3 * W planes
-    uint64_t* d_tab;     // nT * 13
-    uint32_t* d_key;     // nT * A * 2
-    unsigned long long* d_out;  // the measurement's counters
-    int have_T, have_seeds;
-    unsigned long long launches;
-};
+#include "multispin_host.h"
 
 namespace {
 
@@ -228,32 +217,20 @@ __global__ __launch_bounds__(256) void k9_measure(MscParams p, unsigned long lon
     }
 }
 
-long long msc_bonds(const MscGeo& g) {
-    const long long n = g.nsites;
-    return (g.pc ? n : n / g.cols * (g.cols - 1)) + (g.pr ? n : n / g.rows * (g.rows - 1)) + (g.pz ? n : n / g.depth * (g.depth - 1));
-}
-
 size_t msc_small_lds(const MscGeo& g) {
     return (size_t)((g.nsites + 1) & ~1) * 8 + 14 * 8 + (size_t)kAhead * g.nblk * 16 + (size_t)g.nblk * 4;
 }
 
 bool msc_fits_small(const MscGeo& g) { return g.nsites <= kSmallSites && g.nblk <= kSmallBlocks; }
 
-MscParams msc_params(const tsu_msc* h) {
-    MscParams p = {};
-    p.g = h->g;
-    p.s = h->d_s;
-    p.j = h->d_j;
-    p.tab = h->d_tab;
-    p.key = h->d_key;
-    p.A = h->A;
-    p.W = h->W;
-    return p;
-}
-
-size_t msc_planes(const tsu_msc* h) { return (size_t)h->nT * h->A * h->W; }
-
 }  // namespace
+
+hipError_t msc_enqueue_measure(tsu_msc* h, unsigned long long* row) {
+    const dim3 grid((unsigned)((h->g.nsites + 256 * kMeasureSites - 1) / (256 * kMeasureSites)), (unsigned)(h->nT * h->W), 1);
+    if (h->A == 2) k9_measure<2><<<grid, 256, 0, h->ctx->stream>>>(msc_params(h), row);
+    else k9_measure<1><<<grid, 256, 0, h->ctx->stream>>>(msc_params(h), row);
+    return hipGetLastError();
+}
 
 extern "C" {
 
@@ -334,6 +311,7 @@ int tsu_msc_destroy(tsu_msc* h) {
     TSU_ENTER(h ? h->ctx : nullptr);
     if (!h) return TSU_OK;
     (void)hipStreamSynchronize(h->ctx->stream);
+    msc_pt_free(h);
     if (h->d_s) (void)hipFree(h->d_s);
     if (h->d_j) (void)hipFree(h->d_j);
     if (h->d_tab) (void)hipFree(h->d_tab);
@@ -466,10 +444,7 @@ int tsu_msc_measure(tsu_msc* h, int64_t* unsat, int64_t* sum, int64_t* q, int64_
     const size_t col = (size_t)h->W * 64, n1 = (size_t)h->nT * h->A * col, nq = (size_t)h->nT * col;
     const size_t total = 2 * n1 + 2 * nq;
     TSU_HIP_TRY(ctx, hipMemsetAsync(h->d_out, 0, total * 8, ctx->stream));
-    const dim3 grid((unsigned)((h->g.nsites + 256 * kMeasureSites - 1) / (256 * kMeasureSites)), (unsigned)(h->nT * h->W), 1);
-    if (h->A == 2) k9_measure<2><<<grid, 256, 0, ctx->stream>>>(msc_params(h), h->d_out);
-    else k9_measure<1><<<grid, 256, 0, ctx->stream>>>(msc_params(h), h->d_out);
-    TSU_HIP_TRY(ctx, hipGetLastError());
+    TSU_HIP_TRY(ctx, msc_enqueue_measure(h, h->d_out));
     std::vector<unsigned long long> host(total);
     TSU_HIP_TRY(ctx, hipMemcpyAsync(host.data(), h->d_out, total * 8, hipMemcpyDeviceToHost, ctx->stream));
     TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

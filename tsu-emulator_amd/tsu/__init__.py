@@ -35,12 +35,14 @@ from .models import (  # noqa: F401
     LatticeTemperingEnsemble,
     LatticeTemperingEnsemble3D,
     MultispinGlass3D,
+    MultispinTempering3D,
     PopulationAnnealing,
     PopulationAnnealing3D,
     demonstrate_phase_transition,
     edwards_anderson_samples,
     ensemble_summary,
     multispin_scan_3d,
+    multispin_tempering_scan_3d,
     temperature_scan_3d,
     tempering_ensemble_scan,
     tempering_ensemble_scan_3d,
@@ -56,5 +58,5 @@ __all__ = [
     "PopulationAnnealing", "PopulationAnnealing3D",
     "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
     "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d",
-    "GraphTempering",
+    "GraphTempering", "MultispinTempering3D", "multispin_tempering_scan_3d",
 ]

@@ -288,6 +288,17 @@ MULTISPIN_SIGNATURES = {
 }
 MSC_ROUTE_AUTO, MSC_ROUTE_SMALL, MSC_ROUTE_HBM = 0, 1, 2
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_multispin_pt.h (the header tsu_hip.h includes) one to one
+MULTISPIN_PT_SIGNATURES = {
+    "tsu_msc_pt_enable": (C.c_int, [_vp, _f64p]),
+    "tsu_msc_pt_set_swap_seeds": (C.c_int, [_vp, _u64p]),
+    "tsu_msc_pt_run": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32]),
+    "tsu_msc_pt_stats": (C.c_int, [_vp, _i64p, _i64p, _i32p, _i32p, _i64p]),
+    "tsu_msc_pt_history": (C.c_int, [_vp, C.c_int, _i64p, _i64p, _i64p, _i64p]),
+    "tsu_msc_pt_launch_count": (C.c_int, [_vp, _u64p]),
+}
+MSC_PT_MAX_TEMPS = 256
+
 _lib = None
 
 
@@ -308,7 +319,7 @@ def load_library():
                               + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())
                               + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())
                               + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())
-                              + list(MULTISPIN_SIGNATURES.items())):
+                              + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -847,6 +858,53 @@ class MultispinLattice:
     def launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_msc_launch_count(self.h, C.byref(n)))
+        return n.value
+
+    # ---- tempering (tsu_msc_pt_*): per-sample swaps between the temperature slots, decided and applied on the device
+    def pt_enable(self, T):
+        t = np.ascontiguousarray(T, dtype=np.float64).ravel()
+        if t.size != self.n_temps:
+            raise ValueError(f"expected {self.n_temps} temperatures, got {t.size}")
+        self.ctx.check(self.lib.tsu_msc_pt_enable(self.h, _ptr(t, _f64p)))
+
+    def pt_set_swap_seeds(self, seeds):
+        s = _uint_array("swap_seeds", seeds, np.uint64)
+        if s.size != self.n_samples:
+            raise ValueError(f"swap_seeds must hold one value per sample ({self.n_samples}), got {s.size}")
+        self.ctx.check(self.lib.tsu_msc_pt_set_swap_seeds(self.h, _ptr(s, _u64p)))
+
+    def pt_run(self, n_rounds, swap_interval, swap=True, record=True, sweep0=0, round0=0):
+        self.ctx.check(self.lib.tsu_msc_pt_run(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record)),
+                                               _counter("sweep0", sweep0), _counter("round0", round0)))
+
+    def pt_stats(self):
+        """attempts, accepts (replicas, S, n_temps - 1) and labels, flags, trips (replicas, S, n_temps) of the swap passes so far."""
+        A, S, R = self.replicas, self.n_samples, self.n_temps
+        att = np.zeros((A, S, R - 1), np.int64)
+        acc = np.zeros_like(att)
+        lab = np.zeros((A, S, R), np.int32)
+        flg = np.zeros_like(lab)
+        trips = np.zeros((A, S, R), np.int64)
+        self.ctx.check(self.lib.tsu_msc_pt_stats(self.h, _ptr(att, _i64p), _ptr(acc, _i64p), _ptr(lab, _i32p), _ptr(flg, _i32p),
+                                                 _ptr(trips, _i64p)))
+        return {"attempts": att, "accepts": acc, "label_at_slot": lab, "flags": flg, "round_trips": trips}
+
+    def pt_history(self, n_rows):
+        """The rows the last ``pt_run`` recorded, each as :meth:`measure` gives it: (unsat, sum, q, q_link) with a leading round axis."""
+        n, cols = int(n_rows), self.words * 64
+        unsat = np.zeros((n, self.n_temps, self.replicas, cols), np.int64)
+        ssum = np.zeros_like(unsat)
+        two = self.replicas == 2
+        q = np.zeros((n, self.n_temps, cols), np.int64) if two else None
+        ql = np.zeros((n, self.n_temps, cols), np.int64) if two else None
+        self.ctx.check(self.lib.tsu_msc_pt_history(self.h, n, _ptr(unsat, _i64p), _ptr(ssum, _i64p), _ptr(q, _i64p) if two else None,
+                                                   _ptr(ql, _i64p) if two else None))
+        S = self.n_samples
+        return (unsat[..., :S].copy(), ssum[..., :S].copy(), q[..., :S].copy() if two else None, ql[..., :S].copy() if two else None)
+
+    def pt_launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_msc_pt_launch_count(self.h, C.byref(n)))
         return n.value
 
 

@@ -1811,7 +1811,8 @@ class MultispinGlass3D:
     independent.  Two replicas of one sample therefore never share a word: they live in different planes with different seeds.
 
     ``route``: ``"small"`` (planes of at most 8192 sites: the spins stay in LDS for all sweeps of a call, one launch per call) or
-    ``"hbm"`` (one launch per half-sweep for all planes); by default the small route where it fits.  No swaps between temperatures.
+    ``"hbm"`` (one launch per half-sweep for all planes); by default the small route where it fits.  No swaps between temperatures here:
+    :class:`MultispinTempering3D` adds them.
     """
 
     def __init__(self, size, temperatures, *, couplings, periodic=True, replicas: int = 1, seed: Optional[int] = None, seeds=None,
@@ -1839,6 +1840,7 @@ class MultispinGlass3D:
             self.seeds = np.array([[base + a * nT + t for a in range(self.replicas)] for t in range(nT)], dtype=object)
         self.n_bonds = lattice_bond_count(self.shape, self.periodic)
         self.sweep_count = 0
+        self._before_device()
         self._msc = _hip.MultispinLattice(self.depth, self.rows, self.cols, self.periodic, nT, self.replicas, self.n_samples,
                                           _hip.MSC_ROUTE_AUTO if route is None else MULTISPIN_ROUTES[route])
         self._msc.set_couplings(*(_hip.msc_pack(a) for a in packed))
@@ -1848,6 +1850,9 @@ class MultispinGlass3D:
             self._msc.randomize()
         else:
             self._msc.fill(1 if initial == "up" else -1)
+
+    def _before_device(self) -> None:
+        """What a subclass validates once the samples are counted and the seeds are fixed, before the handle exists."""
 
     def close(self) -> None:
         self._msc.close()
@@ -1959,6 +1964,154 @@ def multispin_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 100
             res["overlap_sq"] = (series["q"] ** 2).mean(axis=0).T
             res["overlap_4"] = (series["q"] ** 4).mean(axis=0).T
             res["link_overlap"] = series["ql"].mean(axis=0).T
+        res["temperatures"] = temperatures
+        res["average"] = ensemble_summary(res)
+    finally:
+        g.close()
+    return res
+
+
+class MultispinTempering3D(MultispinGlass3D):
+    """:class:`MultispinGlass3D` with parallel tempering: every sample (and each of its replicas) swaps between neighbouring
+    temperature slots on its own, decided and applied on the device with no host synchronisation inside ``run`` (K9).
+
+    A round is ``swap_interval`` sweeps of every plane, one measurement, one swap pass and the exchange.  The pass runs per sample
+    s and per replica a over the pairs i = 0 .. n_temps - 2 in order: with E_x the energy of the configuration now at slot i (the
+    one an earlier swap of the same pass moved there, if one did) and E_y that at slot i + 1, it accepts iff
+    ``delta = (1/T[i] - 1/T[i+1]) * (E_x - E_y) >= 0 or u < exp(delta)``, u the 53-bit uniform of index i, round counter and
+    replica a under the key ``swap_seeds[s]``.  **An accepted pair exchanges the two spin configurations of that sample**;
+    temperature, threshold table and sweep seed stay with the slot.  So sample s at slot t is, bit for bit,
+    ``IsingModel3D(couplings of s, temperature=T[t], seed=seeds[t][a])`` whose spins are replaced at every accepted swap by those
+    of the neighbouring slot.  It is *not* :class:`LatticeTempering3D` bit for bit: there the seed travels with the walker, here it
+    stays with the slot.
+
+    The swap uniforms are per sample, unlike the sweep uniforms, which the 64 samples of a word share: swaps decorrelate the
+    samples of a word only partially, and errors over samples inside one word remain correlated.
+
+    ``swap_seeds``: one per sample, or ``swap_seed`` for ``swap_seeds[s] = swap_seed + s``; by default
+    ``swap_seed = seed + 2 * n_temps`` (``seed``: the first plane's), the first value past the default sweep seeds.
+    2 to 256 temperatures."""
+
+    def __init__(self, size, temperatures, *, couplings, periodic=True, replicas: int = 1, seed: Optional[int] = None, seeds=None,
+                 initial: str = "random", route: Optional[str] = None, field=None, swap_seed: Optional[int] = None, swap_seeds=None):
+        nT = np.asarray(temperatures, dtype=np.float64).size
+        if not 2 <= nT <= _hip.MSC_PT_MAX_TEMPS:
+            raise ValueError(f"parallel tempering needs 2 to {_hip.MSC_PT_MAX_TEMPS} temperatures, got {nT}")
+        if swap_seed is not None and swap_seeds is not None:
+            raise ValueError("give either swap_seeds= (one per sample) or swap_seed=, not both")
+        self._swap_args = (swap_seed, swap_seeds)
+        self.round_count = 0
+        self._recorded = 0
+        super().__init__(size, temperatures, couplings=couplings, periodic=periodic, replicas=replicas, seed=seed, seeds=seeds,
+                         initial=initial, route=route, field=field)
+        self._msc.pt_enable(self.temperatures)
+        self._msc.pt_set_swap_seeds(self.swap_seeds)
+
+    def _before_device(self) -> None:
+        swap_seed, swap_seeds = self._swap_args
+        S = self.n_samples
+        if swap_seeds is None:
+            if swap_seed is None:  # the first value past the default sweep seeds
+                base = int(self.seeds[0][0]) + 2 * self.temperatures.size
+                swap_seeds = [(base + s) % 2 ** 64 for s in range(S)]
+            else:
+                swap_seeds = [int(swap_seed) + s for s in range(S)]
+        swap_seeds = [int(x) for x in np.asarray(swap_seeds, dtype=object).ravel()]
+        if len(swap_seeds) != S:
+            raise ValueError(f"need one swap seed per sample ({S}), got {len(swap_seeds)}")
+        if any(not 0 <= x < 2 ** 64 for x in swap_seeds):
+            raise ValueError("swap seeds must fit an unsigned 64-bit integer")
+        self.swap_seeds = swap_seeds
+
+    def run(self, n_rounds: int, swap_interval: int = 10, swap: bool = True, record: bool = True):
+        """n_rounds rounds of swap_interval sweeps each (0: a measurement and a swap pass alone); with ``record`` returns
+        :meth:`history`, else None."""
+        n, k = int(n_rounds), int(swap_interval)
+        if n < 0:
+            raise ValueError("n_rounds must be >= 0")
+        if k < 0:
+            raise ValueError("swap_interval must be >= 0")
+        self._msc.pt_run(n, k, swap, record, self.sweep_count, self.round_count)
+        self.sweep_count += n * k
+        self.round_count += n
+        self._recorded = n if record else 0
+        return self.history() if record else None
+
+    def history(self) -> dict:
+        """The rounds recorded by the last ``run``, each taken after the round's sweeps and before its swap pass, per slot and
+        sample as exact integers scaled like :meth:`energies`, :meth:`magnetizations`, :meth:`overlaps` and :meth:`link_overlaps`:
+        ``E`` and ``M`` (n_rounds, n_temps, S), or (n_rounds, n_temps, 2, S) with two replicas, and then also ``q`` and ``q_link``
+        (n_rounds, n_temps, S), of the two replicas that sat at the slot in that round."""
+        unsat, ssum, q, ql = self._msc.pt_history(self._recorded)
+        per = (lambda x: x) if self.replicas == 2 else (lambda x: x[:, :, 0])
+        out = {"E": per((2 * unsat - self.n_bonds).astype(np.float64)), "M": per(ssum / self.n_spins)}
+        if self.replicas == 2:
+            out["q"] = q / self.n_spins
+            out["q_link"] = ql / self.n_bonds
+        return out
+
+    def stats(self) -> dict:
+        """The device's counters: ``attempts`` and ``accepts`` (replicas, S, n_temps - 1) per pair, ``label_at_slot`` (replicas, S,
+        n_temps): which starting configuration sits at each slot, and per label ``flags`` (0 none, 1 bottom, 2 top) and
+        ``round_trips`` (replicas, S, n_temps)."""
+        return self._msc.pt_stats()
+
+    def acceptance(self) -> np.ndarray:
+        """(S, n_temps - 1): accepted / attempted swaps per adjacent pair of slots of each sample, its replicas pooled."""
+        st = self._msc.pt_stats()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return st["accepts"].sum(axis=0) / st["attempts"].sum(axis=0)
+
+    def round_trips(self) -> np.ndarray:
+        """(S,): round trips (slot 0 -> last slot -> slot 0) completed by all configurations of all replicas of each sample."""
+        return self._msc.pt_stats()["round_trips"].sum(axis=(0, 2))
+
+    def label_at_slot(self) -> np.ndarray:
+        """(S, replicas, n_temps): which starting configuration of the sample sits at each slot."""
+        return np.ascontiguousarray(np.moveaxis(self._msc.pt_stats()["label_at_slot"], 0, 1))
+
+    @property
+    def swap_launch_count(self) -> int:
+        """Launches of the measurement, plan and exchange kernels by ``run`` (``launch_count``: the sweeps')."""
+        return self._msc.pt_launch_count()
+
+
+def multispin_tempering_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 1000, n_measure: int = 50,
+                                measure_every: int = 10, replicas: int = 2, periodic=True, seed: Optional[int] = None, seeds=None,
+                                initial: str = "random", route: Optional[str] = None, swap_interval: Optional[int] = None,
+                                swap_seed: Optional[int] = None) -> dict:
+    """:func:`multispin_scan_3d` with parallel tempering (:class:`MultispinTempering3D`): rounds of ``swap_interval`` sweeps
+    (default: ``measure_every``), each followed by a swap pass; ``n_equilibrate`` sweeps of equilibration, then ``n_measure``
+    measurements ``measure_every`` sweeps apart taken from the device's record, one host transfer at the end.  ``n_equilibrate`` and
+    ``measure_every`` must be multiples of ``swap_interval``.  Returns :func:`multispin_scan_3d`'s keys plus ``acceptance``
+    (S, n_temps - 1) and ``round_trips`` (S,), and ``"average"``: :func:`ensemble_summary` of them."""
+    if replicas not in (1, 2):
+        raise ValueError("replicas must be 1 or 2")
+    if int(measure_every) < 1 or int(n_measure) < 1 or int(n_equilibrate) < 0:
+        raise ValueError("measure_every and n_measure must be >= 1, n_equilibrate >= 0")
+    k = int(measure_every) if swap_interval is None else int(swap_interval)
+    if k < 1 or int(measure_every) % k or int(n_equilibrate) % k:
+        raise ValueError("swap_interval must be >= 1 and divide measure_every and n_equilibrate")
+    temperatures = np.asarray(temperatures, dtype=float)
+    if seeds is None and seed is None:
+        seed = 0
+    g = MultispinTempering3D(size, temperatures, couplings=couplings, periodic=periodic, replicas=replicas, seed=seed, seeds=seeds,
+                             initial=initial, route=route, swap_seed=swap_seed)
+    try:
+        g.run(int(n_equilibrate) // k, k, record=False)
+        stride = int(measure_every) // k
+        h = g.run(int(n_measure) * stride, k, record=True)
+        rows = {key: v[stride - 1::stride] for key, v in h.items()}  # (n_measure, n_temps, [2,] S)
+        N = g.n_spins
+        e, m = (rows[key][:, :, 0] if replicas == 2 else rows[key] for key in ("E", "M"))
+        res = {"energy": (e / N).mean(axis=0).T, "magnetization": np.abs(m).mean(axis=0).T}
+        if replicas == 2:
+            res["overlap"] = np.abs(rows["q"]).mean(axis=0).T
+            res["overlap_sq"] = (rows["q"] ** 2).mean(axis=0).T
+            res["overlap_4"] = (rows["q"] ** 4).mean(axis=0).T
+            res["link_overlap"] = rows["q_link"].mean(axis=0).T
+        res["acceptance"] = g.acceptance()
+        res["round_trips"] = g.round_trips()
         res["temperatures"] = temperatures
         res["average"] = ensemble_summary(res)
     finally:
