@@ -10,6 +10,8 @@ hundred, replica ids 0 .. 10).
       straddle(n)   the call starts at sweep 2^30 - 3: hs crosses 2^31, the sign bit of an int
   cluster steps, dense and sparse sweeps (K6, K8 clusters, K2, K5): a full uint32 counter, counter0 + n <= 2^32
       end32(n), straddle32(n)
+  multispin coding (K9, tests/helpers/multispin_shapes.py): plane seeds SEED_HI + index, swap seeds SEED_CARRY + s (the carry at
+      sample 2), the sweep counter at straddle(n) and end(n), the round counter of its tempering at straddle32(n) and end32(n)
 """
 SEED_HI = 0xFEDCBA9876543210
 SEED_CARRY = 2 ** 32 - 2

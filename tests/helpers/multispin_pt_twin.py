@@ -90,8 +90,14 @@ def exchange(planes, masks):
 
 
 def _bits(words, S):
-    """(W, ...) uint64 -> (S,) counts of set bits per sample over all sites."""
-    return msc.unpack(words, S).reshape(S, -1).sum(axis=1).astype(np.int64)
+    """(W, ...) uint64 -> (S,) counts of set bits per sample over all sites (msc.unpack(words, S) summed per sample; the bits are
+    taken apart by bytes, so that thousands of samples cost no more than a few)."""
+    words = np.ascontiguousarray(words, dtype="<u8")
+    W = words.shape[0]
+    if words.size == 0:  # an open axis of length 1 has no bond
+        return np.zeros(S, np.int64)
+    bits =np.unpackbits(words.reshape(W, -1).view(np.uint8).reshape(W, -1, 8), axis=-1, bitorder="little")  # (W, sites, 64)
+    return bits.sum(axis=1, dtype=np.int64).reshape(W * 64)[:S]
 
 
 def measure(planes, periodic, jr, jd, jl, S):

@@ -874,6 +874,13 @@ class MultispinLattice:
         self.ctx.check(self.lib.tsu_msc_pt_set_swap_seeds(self.h, _ptr(s, _u64p)))
 
     def pt_run(self, n_rounds, swap_interval, swap=True, record=True, sweep0=0, round0=0):
+        # a run that ended exactly at a limit leaves round0 = 2^32, which no uint32 carries to the library's own check: refuse
+        # here in its words and its order (the sweep counter first)
+        if int(n_rounds) > 0 and int(swap_interval) >= 0:
+            if int(sweep0) + int(n_rounds) * int(swap_interval) > 1 << 31:
+                raise ValueError("msc_pt_run: sweep counter overflow")
+            if int(round0) + int(n_rounds) > 1 << 32:
+                raise ValueError("msc_pt_run: round counter overflow")
         self.ctx.check(self.lib.tsu_msc_pt_run(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record)),
                                                _counter("sweep0", sweep0), _counter("round0", round0)))
 
