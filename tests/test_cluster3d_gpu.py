@@ -223,6 +223,31 @@ def test_one_layer_equals_k6_on_the_device(hip, rows, cols, periodic, J, T):
         l3.close()
 
 
+@pytest.mark.parametrize("J", [1.0, -1.0])
+@pytest.mark.parametrize("rows,cols,periodic", [(37, 53, False), (24, 40, True)])
+def test_one_layer_equals_k6_on_the_tiled_route(hip, monkeypatch, rows, cols, periodic, J):
+    """The shapes above stay on the one-workgroup route.  Here both handles are forced onto tiles of 8 x 8 sites (ragged last tiles
+    at 37 x 53, the two wraps at 24 x 40): local, merge and resolve of K6 against the same three kernels of K8 on one layer."""
+    monkeypatch.setenv("TSU_SW_TILE", "8")
+    monkeypatch.setenv("TSU_SW3D_TILE", "1x8x8")
+    T = 2.269
+    l2 = hip.Lattice(rows, cols, periodic)
+    l3 = hip.Lattice3D(1, rows, cols, (False, periodic, periodic))
+    try:
+        for lat in (l2, l3):
+            lat.randomize(9)
+        _same(l3.get_spins()[0], l2.get_spins(), f"one layer {rows}x{cols}: the start")
+        jr, jd, jl = _disorder("ferro" if J > 0 else "antiferro", (1, rows, cols), (False, periodic, periodic), 0)
+        l3.set_disorder(jr, jd, jl)
+        l2.cluster_sweep(J, T, 3, 31, 5, 1)
+        l3.cluster_sweep(T, 3, 31, 5, 1)
+        _same(l3.get_spins()[0], l2.get_spins(), f"one layer {rows}x{cols} J={J} on tiles")
+        assert l2.cluster_launch_count() == 9 and l3.cluster_launch_count() == 9
+    finally:
+        l2.close()
+        l3.close()
+
+
 @pytest.mark.parametrize("shape", [(24, 36, 68), (8, 16, 32)])
 def test_one_cluster_across_every_seam_and_wrap(hip, shape):
     """All up, periodic, T = 0.01: every bond is active, one cluster spans all seams and the three wraps; the result is uniform."""

@@ -31,11 +31,7 @@ struct tsu_ising2d {
     size_t obs_batch_cap;
     int* h_err;          // host-mapped flag: 1 = a bounded wait of the tile-resident kernel expired, 2 = a capped union / find
                          // loop of a cluster kernel expired (results invalid either way)
-    int32_t* d_labels;   // K6 cluster labels, rows x cols int32 (ising2d_grow; 1 GiB at 16384^2)
-    size_t labels_cap;
-    void* d_sw_batch;    // tsu_ising2d_cluster_sweep_batch: device copy of the per-lattice items (lives with its first lattice)
-    size_t sw_batch_cap;
-    unsigned long long sw_launches;  // cluster-kernel launches so far (not counted in `launches`)
+    tsu_sw_scratch sw;   // K6 cluster steps: labels (1 GiB at 16384^2), batch items, launches (not counted in `launches`)
     float* d_dis;        // K7 quenched disorder: J_right, J_down, h planes of rows x pitch fp32 each (pads 0), first set_disorder
     int have_disorder;   // set_disorder called and not cleared since
     double* d_dis_part;  // K7 energy: per-workgroup partials + the total

@@ -388,11 +388,7 @@ int tsu_ising2d_create_slab(tsu_ctx* ctx, int64_t total_rows, int cols, int peri
     L->d_obs_batch = nullptr;
     L->obs_batch_cap = 0;
     L->h_err = nullptr;
-    L->d_labels = nullptr;
-    L->labels_cap = 0;
-    L->d_sw_batch = nullptr;
-    L->sw_batch_cap = 0;
-    L->sw_launches = 0;
+    L->sw = tsu_sw_scratch{};
     L->d_dis = nullptr;
     L->have_disorder = 0;
     L->d_dis_part = nullptr;
@@ -434,8 +430,7 @@ int tsu_ising2d_destroy(tsu_ising2d* L) {
     if (L->d_batch) (void)hipFree(L->d_batch);
     if (L->d_obs_batch) (void)hipFree(L->d_obs_batch);
     if (L->h_err) (void)hipHostFree(L->h_err);
-    if (L->d_labels) (void)hipFree(L->d_labels);
-    if (L->d_sw_batch) (void)hipFree(L->d_sw_batch);
+    tsu_sw_scratch_free(L->sw);
     if (L->d_dis) (void)hipFree(L->d_dis);
     if (L->d_dis_part) (void)hipFree(L->d_dis_part);
     if (L->d_prof) (void)hipFree(L->d_prof);

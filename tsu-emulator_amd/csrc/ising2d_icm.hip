@@ -3,7 +3,7 @@
 // One pass, for every participating slot i (T_i <= t_max), a / b = the walkers of ladder 0 / ladder 1 now at slot i:
 //   q       q_x = a_x b_x per site; sites with q = -1 are joined to their right and down lattice neighbours with q = -1 (wrapping
 //           on a periodic lattice), whatever J is on that bond; sites with q = +1 belong to no cluster
-//   labels  K6's union-find with min-index roots (uf_dev.h): the root of a cluster is its smallest index r * cols + c
+//   labels  union-find with min-index roots (uf_dev.h): the root of a cluster is its smallest index r * cols + c
 //   flip    the cluster rooted at (r, c) flips in BOTH walkers iff bit 31 of word c & 3 of
 //           Philox(c >> 2, r, m, TAG_PT_ICM | slot << 8) is set, key = the ladder's seed, m = the handle's cluster-pass counter
 // Flipping a q = -1 cluster in both walkers exchanges it between them: E_a + E_b and every q_x stay as they were, so the pass
@@ -17,10 +17,12 @@
 //                   both walkers rewritten; clusters and flipped sites counted with one atomic per workgroup
 // One launch (small) or three (tiled) per pass whatever the number of slots.  Every union / find loop draws on the per-lane
 // budget of uf_dev.h and raises h_err = 2 when it runs out; no kernel waits on another workgroup.
+// Shared with the Swendsen-Wang steps (sw_dev.h): the geometry struct, the seam decoder of the merge kernel and the root chase of the
+// resolve kernel.  The q-staging, the flags, the statistics and the two-walker stores are this file's own.
 #include <cstdlib>
 
 #include "ising2d_pt.h"
-#include "uf_dev.h"
+#include "sw_dev.h"
 
 namespace {
 
@@ -36,9 +38,8 @@ struct IcmParams {
     const int32_t* slots;  // participating slots (grid index -> slot)
     int32_t* labels;       // tiled route: [grid index][rows * cols]
     long long* stats;      // [3][R]: passes, clusters, flipped
-    long long pitch;
-    int R, rows, cols, periodic;
-    int th, tw, tiles_x, tiles_y;
+    SwGeom g;              // depth 1, pz 0, pr = pc = periodic; tiles of tr x tc sites on the tiled route
+    int R;
     uint32_t k0, k1, m;
     int* err;
 };
@@ -55,12 +56,12 @@ __global__ __launch_bounds__(kSmallThreads) void k7_icm_small(IcmParams p) {
     const int slot = p.slots[blockIdx.x];
     int8_t* const a = walker_plane(p, 0, slot);
     int8_t* const b = walker_plane(p, 1, slot);
-    const int rows = p.rows, cols = p.cols, n = rows * cols, tid = threadIdx.x, nt = blockDim.x;
+    const int rows = p.g.rows, cols = p.g.cols, n = rows * cols, tid = threadIdx.x, nt = blockDim.x;
     uint8_t* const s_q = reinterpret_cast<uint8_t*>(s_lab + n);
     if (tid == 0) s_bad = s_ncl = s_nfl = 0;
     for (int i = tid; i < n; i += nt) {
         const int r = i / cols, c = i - r * cols;
-        const long long g = (long long)r * p.pitch + c;
+        const long long g = (long long)r * p.g.pitch + c;
         const int sa = a[g], sb = b[g];
         s_q[i] = (uint8_t)((sa * sb < 0 ? 1 : 0) | (sa < 0 ? 4 : 0));
         s_lab[i] = i;
@@ -71,17 +72,17 @@ __global__ __launch_bounds__(kSmallThreads) void k7_icm_small(IcmParams p) {
     for (int i = tid; i < n; i += nt) {
         if (!(s_q[i] & 1)) continue;
         const int r = i / cols, c = i - r * cols;
-        const int cr = c + 1 < cols ? c + 1 : (p.periodic ? 0 : -1);
-        const int rd = r + 1 < rows ? r + 1 : (p.periodic ? 0 : -1);
-        if (cr >= 0 && (s_q[r * cols + cr] & 1)) bad |= !uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, r * cols + cr, budget);
-        if (rd >= 0 && (s_q[rd * cols + c] & 1)) bad |= !uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, rd * cols + c, budget);
+        const int cr = c + 1 < cols ? c + 1 : (p.g.pc ? 0 : -1);
+        const int rd = r + 1 < rows ? r + 1 : (p.g.pc ? 0 : -1);
+        if (cr >= 0 && (s_q[r * cols + cr] & 1)) bad |= !uf_union<false, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, r * cols + cr, budget);
+        if (rd >= 0 && (s_q[rd * cols + c] & 1)) bad |= !uf_union<false, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, rd * cols + c, budget);
     }
     __syncthreads();
     // every site's label becomes its root (a root is an ancestor: lanes still chasing through this site lose nothing)
     for (int i = tid; i < n; i += nt) {
         if (!(s_q[i] & 1)) continue;
         budget = kBudget;
-        const int root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, budget);
+        const int root = uf_find<false, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, budget);
         bad |= budget < 0;
         __hip_atomic_store(s_lab + i, root, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -104,7 +105,7 @@ __global__ __launch_bounds__(kSmallThreads) void k7_icm_small(IcmParams p) {
         const int f = s_q[i];
         if (!(f & 1) || !(s_q[s_lab[i]] & 2)) continue;
         const int r = i / cols, c = i - r * cols;
-        const long long g = (long long)r * p.pitch + c;
+        const long long g = (long long)r * p.g.pitch + c;
         const int8_t sa = (f & 4) ? (int8_t)-1 : (int8_t)1;  // b = -a here: flipping both exchanges them
         a[g] = (int8_t)-sa;
         b[g] = sa;
@@ -125,15 +126,15 @@ __global__ __launch_bounds__(kSmallThreads) void k7_icm_small(IcmParams p) {
 // row-major: the same order as global indices inside a tile) and th*tw q bytes (1 = q is -1; 0 outside the lattice).
 __global__ __launch_bounds__(kLocalThreads) void k7_icm_local(IcmParams p) {
     extern __shared__ int s_lab[];
-    const int TH = p.th, TW = p.tw, n = TH * TW;
+    const int TH = p.g.tr, TW = p.g.tc, n = TH * TW;
     uint8_t* const s_q = reinterpret_cast<uint8_t*>(s_lab + n);
     const int slot = p.slots[blockIdx.y];
     const int8_t* const a = walker_plane(p, 0, slot);
     const int8_t* const b = walker_plane(p, 1, slot);
-    int32_t* const labels = p.labels + (size_t)blockIdx.y * p.rows * p.cols;
-    const int ty = (int)(blockIdx.x / (unsigned)p.tiles_x), tx = (int)blockIdx.x - ty * p.tiles_x;
+    int32_t* const labels = p.labels + (size_t)blockIdx.y * p.g.rows * p.g.cols;
+    const int ty = (int)(blockIdx.x / (unsigned)p.g.nc), tx = (int)blockIdx.x - ty * p.g.nc;
     const int r0 = ty * TH, c0 = tx * TW;
-    const int th = p.rows - r0 < TH ? p.rows - r0 : TH, tw = p.cols - c0 < TW ? p.cols - c0 : TW;
+    const int th = p.g.rows - r0 < TH ? p.g.rows - r0 : TH, tw = p.g.cols - c0 < TW ? p.g.cols - c0 : TW;
     const int tid = threadIdx.x;
     if ((TW & 3) == 0) {
         // 4 sites per lane: c0 and the pitch are multiples of 4
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(kLocalThreads) void k7_icm_local(IcmParams p) {
             const int lr = i4 / qw, lc = 4 * (i4 - lr * qw);
             uint32_t q = 0;
             if (lr < th && lc < tw) {
-                const long long g = (long long)(r0 + lr) * p.pitch + c0 + lc;
+                const long long g = (long long)(r0 + lr) * p.g.pitch + c0 + lc;
                 const uint32_t va = *reinterpret_cast<const uint32_t*>(a + g), vb = *reinterpret_cast<const uint32_t*>(b + g);
                 q = ((va ^ vb) >> 7) & 0x01010101u;  // +1 = 0x01, -1 = 0xFF: bit 7 of the XOR is set iff the two spins differ
                 if (lc + 4 > tw) q &= 0xFFFFFFFFu >> (8 * (lc + 4 - tw));  // bytes beyond the last column
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(kLocalThreads) void k7_icm_local(IcmParams p) {
             const int lr = i / TW, lc = i - lr * TW;
             int q = 0;
             if (lr < th && lc < tw) {
-                const long long g = (long long)(r0 + lr) * p.pitch + c0 + lc;
+                const long long g = (long long)(r0 + lr) * p.g.pitch + c0 + lc;
                 q = (int)a[g] * (int)b[g] < 0;
             }
             s_q[i] = (uint8_t)q;
@@ -172,8 +173,8 @@ __global__ __launch_bounds__(kLocalThreads) void k7_icm_local(IcmParams p) {
     for (int i = tid; i < n; i += kLocalThreads) {
         if (!s_q[i]) continue;
         const int lr = i / TW, lc = i - lr * TW;
-        if (lc + 1 < tw && s_q[i + 1]) bad |= !uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + 1, budget);
-        if (lr + 1 < th && s_q[i + TW]) bad |= !uf_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + TW, budget);
+        if (lc + 1 < tw && s_q[i + 1]) bad |= !uf_union<false, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + 1, budget);
+        if (lr + 1 < th && s_q[i + TW]) bad |= !uf_union<false, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, i + TW, budget);
     }
     __syncthreads();
     for (int i = tid; i < n; i += kLocalThreads) {
@@ -182,43 +183,26 @@ __global__ __launch_bounds__(kLocalThreads) void k7_icm_local(IcmParams p) {
         int lab = kNone;
         if (s_q[i]) {
             budget = kBudget;
-            const int root = uf_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, budget);
+            const int root = uf_find<false, __HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, i, budget);
             bad |= budget < 0;
             const int rr = root / TW, rc = root - rr * TW;
-            lab = (r0 + rr) * p.cols + c0 + rc;
+            lab = (r0 + rr) * p.g.cols + c0 + rc;
         }
-        labels[(long long)(r0 + lr) * p.cols + c0 + lc] = lab;
+        labels[(long long)(r0 + lr) * p.g.cols + c0 + lc] = lab;
     }
     if (bad) raise_err(p.err);
 }
 
-// lanes [0, nv * rows): right bonds of the vertical seams (seam k < tiles_x - 1 at column (k + 1) tw - 1, the last one of a
-// periodic lattice at column cols - 1, wrapping to 0); then nh * cols lanes for the down bonds of the horizontal seams.  A
-// label other than kNone says q = -1 at that site: the spins are not read again.
-__global__ __launch_bounds__(256) void k7_icm_merge(IcmParams p, int nv, int nh) {
-    const long long lane = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long nvl = (long long)nv * p.rows, total = nvl + (long long)nh * p.cols;
-    if (lane >= total) return;
-    int32_t* const labels = p.labels + (size_t)blockIdx.y * p.rows * p.cols;
+// one lane per bond across a tile seam or the wrap (sw_seam: the vertical seams' right bonds, then the horizontal seams' down
+// bonds).  A label other than kNone says q = -1 at that site: the spins are not read again.
+__global__ __launch_bounds__(256) void k7_icm_merge(IcmParams p) {
     int r, c, r2, c2;
-    if (lane < nvl) {
-        const int k = (int)(lane / p.rows);
-        r = (int)(lane - (long long)k * p.rows);
-        c = k < p.tiles_x - 1 ? (k + 1) * p.tw - 1 : p.cols - 1;
-        r2 = r;
-        c2 = c + 1 < p.cols ? c + 1 : 0;
-    } else {
-        const long long l = lane - nvl;
-        const int k = (int)(l / p.cols);
-        c = (int)(l - (long long)k * p.cols);
-        r = k < p.tiles_y - 1 ? (k + 1) * p.th - 1 : p.rows - 1;
-        c2 = c;
-        r2 = r + 1 < p.rows ? r + 1 : 0;
-    }
-    const int la = labels[(long long)r * p.cols + c], lb = labels[(long long)r2 * p.cols + c2];
+    if (sw_seam<2>(p.g, (long long)blockIdx.x * 256 + threadIdx.x, r, c, r2, c2) < 0) return;
+    int32_t* const labels = p.labels + (size_t)blockIdx.y * p.g.rows * p.g.cols;
+    const int la = labels[(long long)r * p.g.cols + c], lb = labels[(long long)r2 * p.g.cols + c2];
     if (la == kNone || lb == kNone) return;
     int budget = kBudget;
-    if (!uf_union<__HIP_MEMORY_SCOPE_AGENT>(labels, la, lb, budget)) raise_err(p.err);
+    if (!uf_union<false, __HIP_MEMORY_SCOPE_AGENT>(labels, la, lb, budget)) raise_err(p.err);
 }
 
 // one lane per 4 sites of a row of slot blockIdx.y (one 4-byte load and store per walker; the pad bytes beyond cols are 0 and
@@ -232,28 +216,22 @@ __global__ __launch_bounds__(256) void k7_icm_resolve(IcmParams p, int quads) {
     const long long lane = (long long)blockIdx.x * 256 + threadIdx.x;
     const int r = (int)(lane / quads), c0 = 4 * (int)(lane - (long long)r * quads);
     int ncl = 0, nfl = 0;
-    if (r < p.rows) {
-        const int32_t* const labels = p.labels + (size_t)blockIdx.y * p.rows * p.cols;
+    if (r < p.g.rows) {
+        const int32_t* const labels = p.labels + (size_t)blockIdx.y * p.g.rows * p.g.cols;
         const uint32_t tag = TSU_TAG_PT_ICM | ((uint32_t)slot << 8);
         int last = kNone;
         bool last_flip = false, bad = false;
         uint32_t mask = 0;  // 0xFF in the bytes that flip
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            if (c0 + j >= p.cols) break;
-            const int g = r * p.cols + c0 + j;
-            int x = labels[g], budget = kBudget;
+            if (c0 + j >= p.g.cols) break;
+            const int g = r * p.g.cols + c0 + j;
+            int x = labels[g];
             if (x == kNone) continue;
             ncl += x == g;
-            for (int y = labels[x]; y != x; y = labels[x]) {
-                x = y;
-                if (--budget < 0) {
-                    bad = true;
-                    break;
-                }
-            }
+            x = sw_chase<false>(labels, x, bad);
             if (x != last) {
-                const int rr = x / p.cols, rc = x - rr * p.cols;
+                const int rr = x / p.g.cols, rc = x - rr * p.g.cols;
                 last = x;
                 last_flip = flip_bit(rr, rc, p.m, tag, p.k0, p.k1);
             }
@@ -264,7 +242,7 @@ __global__ __launch_bounds__(256) void k7_icm_resolve(IcmParams p, int quads) {
         }
         if (mask) {
             // negate the masked bytes: +1 = 0x01 <-> -1 = 0xFF is an XOR with 0xFE
-            const long long off = (long long)r * p.pitch + c0;
+            const long long off = (long long)r * p.g.pitch + c0;
             uint32_t* const pa = reinterpret_cast<uint32_t*>(walker_plane(p, 0, slot) + off);
             uint32_t* const pb = reinterpret_cast<uint32_t*>(walker_plane(p, 1, slot) + off);
             *pa ^= mask & 0xFEFEFEFEu;
@@ -297,16 +275,6 @@ int grow_labels(tsu_pt2d* P) {
         return tsu_fail(P->ctx, e == hipErrorOutOfMemory ? TSU_E_NOMEM : TSU_E_HIP,
                         "pt2d cluster moves: %zu bytes of labels (%d slots of %zu sites): %s", bytes, P->icm_n, sites_of(P),
                         hipGetErrorString(e));
-    return TSU_OK;
-}
-
-int ensure_err(tsu_ising2d* L, int** d_err) {
-    tsu_ctx* ctx = L->ctx;
-    if (!L->h_err) {
-        TSU_HIP_TRY(ctx, hipHostMalloc(&L->h_err, sizeof(int), hipHostMallocMapped));
-        *L->h_err = 0;
-    }
-    TSU_HIP_TRY(ctx, hipHostGetDevicePointer((void**)d_err, L->h_err, 0));
     return TSU_OK;
 }
 
@@ -360,16 +328,17 @@ int pt2d_icm_enqueue(tsu_pt2d* P) {
     p.slots = P->d_icm_slots;
     p.labels = nullptr;
     p.stats = P->d_icm_stats;
-    p.pitch = (long long)L->pitch;
+    p.g = SwGeom{};
+    p.g.pitch = (long long)L->pitch;
+    p.g.depth = 1;
+    p.g.rows = L->rows;
+    p.g.cols = L->cols;
+    p.g.pr = p.g.pc = L->periodic;
     p.R = P->R;
-    p.rows = L->rows;
-    p.cols = L->cols;
-    p.periodic = L->periodic;
-    p.th = p.tw = p.tiles_x = p.tiles_y = 0;
     p.k0 = P->key0;
     p.k1 = P->key1;
     p.m = m;
-    int rc = ensure_err(P->lat[0], &p.err);
+    int rc = tsu_err_flag(ctx, P->lat[0]->h_err, &p.err);
     if (rc != TSU_OK) return rc;
     const unsigned ns = (unsigned)P->icm_n;
     if (small) {
@@ -385,19 +354,18 @@ int pt2d_icm_enqueue(tsu_pt2d* P) {
         rc = grow_labels(P);
         if (rc != TSU_OK) return rc;
         p.labels = P->d_icm_labels;
-        p.th = p.tw = edge;
-        p.tiles_x = (L->cols + edge - 1) / edge;
-        p.tiles_y = (L->rows + edge - 1) / edge;
-        const int nv = p.tiles_x - 1 + (L->periodic ? 1 : 0), nh = p.tiles_y - 1 + (L->periodic ? 1 : 0);
-        const long long merge_lanes = (long long)nv * L->rows + (long long)nh * L->cols;
+        p.g.tr = p.g.tc = edge;
+        p.g.nc = (L->cols + edge - 1) / edge;
+        p.g.nr = (L->rows + edge - 1) / edge;
+        const long long merge_lanes = sw_seam_lanes<2>(p.g);
         const size_t lds = (size_t)edge * edge * 5;
         const int quads = (L->cols + 3) / 4;
-        const unsigned tiles = (unsigned)((long long)p.tiles_x * p.tiles_y);
+        const unsigned tiles = (unsigned)((long long)p.g.nc * p.g.nr);
         const unsigned resolve_blocks = (unsigned)(((long long)quads * L->rows + 255) / 256);
         hipLaunchKernelGGL(k7_icm_local, dim3(tiles, ns), dim3(kLocalThreads), lds, ctx->stream, p);
         // a lattice of one tile without a wrap has no seam; the launch stays so that a pass is three launches on this route
         hipLaunchKernelGGL(k7_icm_merge, dim3((unsigned)((merge_lanes + 255) / 256 > 0 ? (merge_lanes + 255) / 256 : 1), ns), dim3(256), 0,
-                           ctx->stream, p, nv, nh);
+                           ctx->stream, p);
         hipLaunchKernelGGL(k7_icm_resolve, dim3(resolve_blocks, ns), dim3(256), 0, ctx->stream, p, quads);
         P->icm_launches += 3;
     }

@@ -1398,12 +1398,8 @@ int run_resident(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps,
     // strip layout of this call: the element numbering may only run on while it stays the same
     const uint64_t xsig = ((uint64_t)(c.v + 1) << 48) ^ ((uint64_t)ntiles << 28) ^ ((uint64_t)kmax << 20) ^ ((uint64_t)c.tile_h << 4) ^
                           ((uint64_t)c.flex_ty << 36) ^ (uint64_t)p.open;
-    if (!L->h_err) {
-        TSU_HIP_TRY(ctx, hipHostMalloc(&L->h_err, sizeof(int), hipHostMallocMapped));
-        *L->h_err = 0;
-    }
     int* d_err = nullptr;
-    TSU_HIP_TRY(ctx, hipHostGetDevicePointer((void**)&d_err, L->h_err, 0));
+    if (const int rc = tsu_err_flag(ctx, L->h_err, &d_err); rc != TSU_OK) return rc;
     const int verbose = lattice_env("TSU_K1_VERBOSE", 0);
     // one launch per 1024 generations at most (a whole lattice may be asked for millions of sweeps; a slab's call
     // is one refresh period anyway)

@@ -15,15 +15,10 @@ struct tsu_ising3d {
     double* d_part;      // energy: per-workgroup partials + the total
     long long* d_acc;    // sum of spins / overlap accumulator
     unsigned long long launches;  // k8_sweep launches so far
-    int32_t* d_labels;   // cluster labels, depth * rows * cols int32, allocated by the first cluster call on the tiled route
-    size_t labels_cap;
-    void* d_sw_batch;    // tsu_ising3d_cluster_sweep_batch: device copy of the per-lattice items (lives with its first lattice)
-    size_t sw_batch_cap;
+    tsu_sw_scratch sw;   // cluster steps: labels, batch items, launches (not counted in `launches`)
     int* h_err;          // host-mapped flag: 2 = a capped union / find loop of a cluster kernel expired (results invalid)
-    unsigned long long sw_launches;  // cluster-kernel launches so far (not counted in `launches`)
     long long* d_prof;   // tsu_ising3d_profiles: depth + rows + cols int64 bins (first call)
 };
 
-// ising3d_cluster.hip: report (and clear) a flag a cluster kernel left in h_err; release what the cluster calls allocated
+// ising3d_cluster.hip: report (and clear) a flag a cluster kernel left in h_err
 int ising3d_check_err(tsu_ising3d* L);
-void ising3d_cluster_free(tsu_ising3d* L);

@@ -387,7 +387,8 @@ int tsu_ising3d_destroy(tsu_ising3d* L) {
     if (L->d_part) (void)hipFree(L->d_part);
     if (L->d_acc) (void)hipFree(L->d_acc);
     if (L->d_prof) (void)hipFree(L->d_prof);
-    ising3d_cluster_free(L);
+    if (L->h_err) (void)hipHostFree(L->h_err);
+    tsu_sw_scratch_free(L->sw);
     delete L;
     return TSU_OK;
 }

@@ -1,0 +1,176 @@
+// sw_host.h -- the host side of a Swendsen-Wang call, written once for K6 (ising2d_cluster.hip) and K8 (ising3d_cluster.hip): the
+// counter checks, the one-workgroup launch with its batch upload, the loop of the multi-tile route and the batch entry point's loop.
+// A traits struct Tr per dimension supplies what differs:
+//   Lattice, Bonds, Model      the handle (with ctx, h_err and a tsu_sw_scratch sw), the bond policy of sw_dev.h, the model
+//                              parameters of one call (K6: J and T; K8: T)
+//   who, refuse_twice          the prefix of every message; whether a batch refuses a lattice listed twice
+//   small, local, merge, resolve   the kernels
+//   check_model(L, m)          the checks only this dimension has, made ahead of the counter checks
+//   check_err(L)               report (and clear) a flag an earlier call's kernel left
+//   geom(L), spins(L), bonds(L, m)   extents, pitch and wraps (DIM = 2: depth 1, pz 0); row 0; the policy's values
+//   tile_forced()              the environment switch of the tile shape is set: every lattice on the multi-tile route
+//   tile(L, g)                 the tile shape into g, checked
+//   local_threads(g)           lanes of a tile's workgroup
+//   grow_labels(L, bytes)      the labels buffer, with this dimension's message when memory runs out
+#pragma once
+#include <vector>
+
+#include "ising2d.h"
+#include "sw_dev.h"
+
+namespace {
+
+constexpr int kSwSmallSites = 16384;  // one-workgroup route: at most this many sites (80 KB of LDS); also the largest tile
+constexpr int kSwMaxThreads = 1024;
+
+template <int DIM>
+long long sw_sites(const SwGeom& g) {
+    return (long long)(DIM == 3 ? g.depth : 1) * g.rows * g.cols;
+}
+
+inline int sw_threads(long long work_items) {
+    const long long t = (work_items + 63) / 64 * 64;
+    return (int)(t < kSwMaxThreads ? t : kSwMaxThreads);
+}
+
+template <class Tr>
+bool sw_small_route(const typename Tr::Lattice* L) {
+    return !Tr::tile_forced() && sw_sites<Tr::DIM>(Tr::geom(L)) <= kSwSmallSites;
+}
+
+template <class Tr>
+SwItem<typename Tr::Bonds> sw_make_item(const typename Tr::Lattice* L, const typename Tr::Model& m, uint64_t seed, uint32_t step0,
+                                        uint32_t replica) {
+    SwItem<typename Tr::Bonds> it;
+    it.s = Tr::spins(L);
+    it.b = Tr::bonds(L, m);
+    it.k.k0 = (uint32_t)seed;
+    it.k.k1 = (uint32_t)(seed >> 32);
+    it.k.tag_bond = TSU_TAG_SW_BOND | (replica << 8);
+    it.k.tag_layer = TSU_TAG_SW_LAYER | (replica << 8);
+    it.k.tag_flip = TSU_TAG_SW_FLIP | (replica << 8);
+    it.k.tag_ghost = TSU_TAG_SW_GHOST | (replica << 8);
+    it.k.t = step0;
+    return it;
+}
+
+template <class Tr>
+int sw_check_call(typename Tr::Lattice* L, const typename Tr::Model& m, int n_steps, uint32_t step0, uint32_t replica) {
+    tsu_ctx* ctx = L->ctx;
+    const int rc = Tr::check_model(L, m);
+    if (rc != TSU_OK) return rc;
+    TSU_REQUIRE(ctx, n_steps >= 0, "%s: n_steps must be >= 0", Tr::who);
+    TSU_REQUIRE(ctx, (uint64_t)step0 + (uint64_t)n_steps <= (1ull << 32), "%s: step counter overflow", Tr::who);
+    TSU_REQUIRE(ctx, replica < TSU_REPLICA_LIMIT, "%s: replica id %u is not below 2^24", Tr::who, (unsigned)replica);
+    return Tr::check_err(L);  // a cap that expired in an earlier call
+}
+
+// n lattices of one shape and boundary, one workgroup each, all steps in one launch
+template <class Tr>
+int sw_run_small(typename Tr::Lattice* const* lats, int n, const SwItem<typename Tr::Bonds>* items, int n_steps) {
+    using Item = SwItem<typename Tr::Bonds>;
+    typename Tr::Lattice* L0 = lats[0];
+    tsu_ctx* ctx = L0->ctx;
+    int* d_err = nullptr;
+    const int rc = tsu_err_flag(ctx, L0->h_err, &d_err);
+    if (rc != TSU_OK) return rc;
+    const SwGeom g = Tr::geom(L0);
+    const size_t lds = (size_t)sw_sites<Tr::DIM>(g) * 5;
+    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)Tr::small, (int)lds));
+    const Item* d_items = nullptr;
+    if (n > 1) {
+        const size_t bytes = (size_t)n * sizeof(Item);
+        TSU_HIP_TRY(ctx, ising2d_grow(L0->sw.d_batch, L0->sw.batch_cap, bytes));
+        // the host array dies with this call: wait for the copy (a few KB); the launch itself stays asynchronous
+        TSU_HIP_TRY(ctx, hipMemcpyAsync(L0->sw.d_batch, items, bytes, hipMemcpyHostToDevice, ctx->stream));
+        TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        d_items = (const Item*)L0->sw.d_batch;
+    }
+    const int threads = sw_threads(sw_sites<Tr::DIM>(g) / g.cols * ((g.cols + 1) / 2));
+    hipLaunchKernelGGL(Tr::small, dim3((unsigned)n), dim3((unsigned)threads), lds, ctx->stream, d_items, items[0], g, n_steps, d_err);
+    TSU_HIP_TRY(ctx, hipGetLastError());
+    for (int i = 0; i < n; ++i) lats[i]->sw.launches += 1;
+    return TSU_OK;
+}
+
+// local, merge (when the lattice has a seam or a wrap) and resolve, once per step
+template <class Tr>
+int sw_run_tiles(typename Tr::Lattice* L, const SwItem<typename Tr::Bonds>& it, int n_steps) {
+    tsu_ctx* ctx = L->ctx;
+    SwParams<typename Tr::Bonds> p;
+    SwGeom& g = p.g;
+    g = Tr::geom(L);
+    int rc = Tr::tile(L, g);
+    if (rc != TSU_OK) return rc;
+    g.nz = (g.depth + g.tz - 1) / g.tz;
+    g.nr = (g.rows + g.tr - 1) / g.tr;
+    g.nc = (g.cols + g.tc - 1) / g.tc;
+    rc = Tr::grow_labels(L, (size_t)sw_sites<Tr::DIM>(g) * sizeof(int32_t));
+    if (rc != TSU_OK) return rc;
+    p.s = it.s;
+    p.labels = L->sw.d_labels;
+    p.b = it.b;
+    p.k = it.k;
+    rc = tsu_err_flag(ctx, L->h_err, &p.err);
+    if (rc != TSU_OK) return rc;
+    const long long n_tiles = (long long)g.nz * g.nr * g.nc;
+    TSU_REQUIRE(ctx, n_tiles < (1ll << 31), "%s: %lld tiles exceed the grid", Tr::who, n_tiles);
+    const long long merge_lanes = sw_seam_lanes<Tr::DIM>(g);
+    const size_t lds = (size_t)g.tz * g.tr * g.tc * 5;
+    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)Tr::local, (int)lds));
+    const unsigned local_threads = (unsigned)Tr::local_threads(g);
+    const int quads = (g.cols + 3) / 4;
+    const unsigned resolve_blocks = (unsigned)((sw_sites<Tr::DIM>(g) / g.cols * quads + 255) / 256);
+    for (int s = 0; s < n_steps; ++s) {
+        p.k.t = it.k.t + (uint32_t)s;
+        hipLaunchKernelGGL(Tr::local, dim3((unsigned)n_tiles), dim3(local_threads), lds, ctx->stream, p);
+        if (merge_lanes > 0) hipLaunchKernelGGL(Tr::merge, dim3((unsigned)((merge_lanes + 255) / 256)), dim3(256), 0, ctx->stream, p);
+        hipLaunchKernelGGL(Tr::resolve, dim3(resolve_blocks), dim3(256), 0, ctx->stream, p, quads);
+        L->sw.launches += merge_lanes > 0 ? 3 : 2;
+    }
+    TSU_HIP_TRY(ctx, hipGetLastError());
+    return TSU_OK;
+}
+
+template <class Tr>
+int sw_sweep(typename Tr::Lattice* L, const typename Tr::Model& m, int n_steps, uint64_t seed, uint32_t step0, uint32_t replica) {
+    if (!L) return TSU_E_INVALID;
+    const int rc = sw_check_call<Tr>(L, m, n_steps, step0, replica);
+    if (rc != TSU_OK || n_steps == 0) return rc;
+    const auto it = sw_make_item<Tr>(L, m, seed, step0, replica);
+    return sw_small_route<Tr>(L) ? sw_run_small<Tr>(&L, 1, &it, n_steps) : sw_run_tiles<Tr>(L, it, n_steps);
+}
+
+// every lattice checked first; one launch if all of them take the one-workgroup route with one shape and boundary, else one by one.
+// model_of(i): the Model of lattice i
+template <class Tr, class ModelOf>
+int sw_sweep_batch(typename Tr::Lattice* const* lats, int n_lats, int n_steps, ModelOf model_of, const uint64_t* seeds,
+                   const uint32_t* step0s, const uint32_t* replicas) {
+    tsu_ctx* ctx = lats[0]->ctx;
+    const SwGeom a = Tr::geom(lats[0]);
+    bool one_launch = true;
+    for (int i = 0; i < n_lats; ++i) {
+        typename Tr::Lattice* L = lats[i];
+        TSU_REQUIRE(ctx, L && L->ctx == ctx, "%s_sweep_batch: lattice %d is NULL or belongs to another context", Tr::who, i);
+        if (Tr::refuse_twice)
+            for (int k = 0; k < i; ++k) TSU_REQUIRE(ctx, lats[k] != L, "%s_sweep_batch: lattice %d appears twice", Tr::who, i);
+        const int rc = sw_check_call<Tr>(L, model_of(i), n_steps, step0s[i], replicas[i]);
+        if (rc != TSU_OK) return rc;
+        const SwGeom g = Tr::geom(L);
+        one_launch = one_launch && sw_small_route<Tr>(L) && g.depth == a.depth && g.rows == a.rows && g.cols == a.cols && g.pz == a.pz &&
+                     g.pr == a.pr && g.pc == a.pc;
+    }
+    if (n_steps == 0) return TSU_OK;
+    if (one_launch) {
+        std::vector<SwItem<typename Tr::Bonds>> items((size_t)n_lats);
+        for (int i = 0; i < n_lats; ++i) items[(size_t)i] = sw_make_item<Tr>(lats[i], model_of(i), seeds[i], step0s[i], replicas[i]);
+        return sw_run_small<Tr>(lats, n_lats, items.data(), n_steps);
+    }
+    for (int i = 0; i < n_lats; ++i) {
+        const int rc = sw_sweep<Tr>(lats[i], model_of(i), n_steps, seeds[i], step0s[i], replicas[i]);
+        if (rc != TSU_OK) return rc;
+    }
+    return TSU_OK;
+}
+
+}  // namespace

@@ -93,6 +93,32 @@ int tsu_fail(tsu_ctx* ctx, int code, const char* fmt, ...);
 #define TSU_REQUIRE_REPLICA(ctx, replica, who) \
     TSU_REQUIRE((ctx), (uint32_t)(replica) < TSU_REPLICA_LIMIT, who ": replica id %u is not below 2^24", (unsigned)(replica))
 
+// The host-mapped error flag of a handle (a kernel that gives up stores a code in it; the handle's next synchronising call reports
+// it): allocated and cleared on first use; *d_err is its device address.
+static inline int tsu_err_flag(tsu_ctx* ctx, int*& h_err, int** d_err) {
+    if (!h_err) {
+        TSU_HIP_TRY(ctx, hipHostMalloc(&h_err, sizeof(int), hipHostMallocMapped));
+        *h_err = 0;
+    }
+    TSU_HIP_TRY(ctx, hipHostGetDevicePointer((void**)d_err, h_err, 0));
+    return TSU_OK;
+}
+
+// What the Swendsen-Wang calls of a lattice handle (2-D or 3-D, sw_host.h) allocate and count
+struct tsu_sw_scratch {
+    int32_t* d_labels;  // cluster labels, one int32 a site, allocated by the first call on the multi-tile route
+    size_t labels_cap;
+    void* d_batch;      // a batch's per-lattice items on the device (lives with the batch's first lattice)
+    size_t batch_cap;
+    unsigned long long launches;  // cluster-kernel launches so far
+};
+
+static inline void tsu_sw_scratch_free(tsu_sw_scratch& s) {
+    if (s.d_labels) (void)hipFree(s.d_labels);
+    if (s.d_batch) (void)hipFree(s.d_batch);
+    s = tsu_sw_scratch{};
+}
+
 // ------------------------------------------------------------------ Philox4x32-10 (device + host)
 #define TSU_PHILOX_M0 0xD2511F53u
 #define TSU_PHILOX_M1 0xCD9E8D57u
