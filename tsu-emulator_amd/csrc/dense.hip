@@ -145,7 +145,6 @@ __global__ __launch_bounds__(256) void k2_block(const TJ* __restrict__ J, const 
 // 128 + k; J sits in LDS as columns (fp32 J: up to 192 sites = 148 KB, fp64: up to 128); every sweep recomputes the
 // fields from scratch (like the reference's np.dot per site) and resolves the sequential pass slot after slot by a
 // fixed-point iteration over the slot's 64 sites.  No barrier, no launch and no global memory access inside a sweep.
-#define K2W_MAX_SLOTS 3
 // u < sigmoid(x) <=> x > logit(u): a float32 logit is computed once per site and sweep, outside the flip-to-flip
 // chain, so a decision inside the chain is one multiply, a conversion and a few float compares.  The float quantities
 // carry errors below 1e-5 (1 + |logit|); whenever x is within 1e-4 (1 + |logit|) of the logit, or within 1e-3 of the
@@ -315,19 +314,6 @@ __global__ __launch_bounds__(64) void k2_small_replicas(const TJ* __restrict__ J
                         rp.T, nullptr, n_sweeps, 1, 0, rp.sweep0, rp.tag, rp.k0, rp.k1);
 }
 
-// largest n on the one-workgroup kernel: the measured crossover against the cooperative kernel
-// (tools/dense_mid_times.py): fp32 J ~600 sites, fp64 J ~470 against the barrier kernel; against the pipeline (which now starts
-// at n = 452 with a streamer grid sized to the system) fp32 ~530: n = 500 30 us here / 34 there, n = 576 41 / 36
-static bool k2wg_takes(const tsu_dense* d) {
-    return d->n <= (d->dtype == TSU_DTYPE_F64 ? 448 : 528);
-}
-
-// slots per lane the one-wave kernels need for this system, 0 if it does not fit one CU's LDS
-static int k2w_slots(const tsu_dense* d) {
-    const int m = (d->n + 63) / 64;
-    return m <= (d->dtype == TSU_DTYPE_F64 ? 2 : K2W_MAX_SLOTS) ? m : 0;
-}
-
 static size_t k2w_lds_bytes(const tsu_dense* d, int m) {
     return (size_t)d->n * (size_t)(64 * m + 1) * (d->dtype == TSU_DTYPE_F64 ? 8 : 4);
 }
@@ -336,7 +322,7 @@ typedef void (*k2w_run_fn)(const void*, const double*, int8_t*, const double*, i
                            uint32_t, uint32_t, uint32_t);
 typedef void (*k2w_rep_fn)(const void*, const double*, int8_t*, const double*, const K2Replica*, int, int);
 
-// one launch of the one-wave kernel (grid 1) for a system k2w_slots accepts
+// one launch of the one-wave kernel (grid 1) for a system dense_route sends here (m slots)
 static hipError_t k2w_launch(const tsu_dense* d, int m, hipStream_t stream, const double* uniforms, int8_t* samples, double T,
                              const double* temps, int n_burnin, int n_sweeps, int n_samples, uint32_t sweep0, uint32_t tag, uint32_t k0,
                              uint32_t k1) {
@@ -696,9 +682,9 @@ int tsu_dense_destroy(tsu_dense* d) {
     if (d->samples) (void)hipFree(d->samples);
     if (d->temps) (void)hipFree(d->temps);
     if (d->rep_buf) (void)hipFree(d->rep_buf);
-    if (d->rep_fields[0]) (void)hipFree(d->rep_fields[0]);
-    if (d->rep_fields[1]) (void)hipFree(d->rep_fields[1]);
-    free(d->rep_prev);
+    if (d->kept.rep_fields[0]) (void)hipFree(d->kept.rep_fields[0]);
+    if (d->kept.rep_fields[1]) (void)hipFree(d->kept.rep_fields[1]);
+    free(d->kept.rep_prev);
     if (d->h_flags) (void)hipHostFree(d->h_flags);
     if (d->h_stage) (void)hipHostFree(d->h_stage);
     if (d->h_rep) (void)hipHostFree(d->h_rep);
@@ -745,11 +731,10 @@ int tsu_dense_set_state(tsu_dense* d, const int8_t* bits_host) {
     TSU_REQUIRE(d->ctx, dense_bits01(bits_host, (size_t)d->n), "dense_set_state: state must be 0/1");
     TSU_HIP_TRY(d->ctx, hipMemcpyAsync(d->state, bits_host, (size_t)d->n, hipMemcpyHostToDevice, d->ctx->stream));
     TSU_HIP_TRY(d->ctx, hipStreamSynchronize(d->ctx->stream));
-    dense_forget_fields(d);  // the kept fields belong to the old state ...
+    d->kept.forget();  // the kept fields belong to the old state ...
     // ... but the state may be one the last replica call returned (a tempering loop asks for every replica's energy between its
     // sweeps, gibbs.py:303-323): its fields are still there
-    for (int p = 0; p < d->rep_prev_n && !d->rep_match; ++p)
-        if (memcmp(bits_host, d->rep_prev + (size_t)p * d->n, (size_t)d->n) == 0) d->rep_match = p + 1;
+    d->kept.match_state(bits_host, (size_t)d->n);
     return TSU_OK;
 }
 
@@ -819,38 +804,32 @@ static int dense_sweep(tsu_dense* d, double T, int n_sweeps, const int64_t* orde
     if (rc != TSU_OK) return rc;
     if (order || replay_uniforms) TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));  // host buffers are the caller's
     const double* uni = replay_uniforms ? d->uniforms : nullptr;
-    const uint32_t tag = TSU_TAG_DENSE | (replica << 8);
-    if (!order) {
-        // systems of at most 192 (fp32) / 128 (fp64) sites: all sweeps of the call in one launch of a single wave
-        const int wave_m = k2w_slots(d);
-        if (wave_m) {
-            TSU_HIP_TRY(ctx, k2w_launch(d, wave_m, ctx->stream, uni, nullptr, T, nullptr, n_sweeps, 1, 0, sweep0, tag, (uint32_t)seed,
-                                        (uint32_t)(seed >> 32)));
-            return TSU_OK;
+    const DenseStream st = dense_stream(seed, replica);
+    const DenseRouted to = dense_route(d->n, d->dtype == TSU_DTYPE_F64, order != nullptr, d->kept.natural_off());
+    if (to.route == DenseRoute::Wave) {  // all sweeps of the call in one launch of a single wave
+        TSU_HIP_TRY(ctx, k2w_launch(d, to.m, ctx->stream, uni, nullptr, T, nullptr, n_sweeps, 1, 0, sweep0, st.tag, st.k0, st.k1));
+        return TSU_OK;
+    }
+    if (to.route == DenseRoute::Workgroup) {  // one workgroup, thread per site, all sweeps of the call in one launch
+        static const bool verbose_wg = dense_env("TSU_K2_VERBOSE", 0) != 0;
+        TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, uni, nullptr, T, nullptr, n_sweeps, 1, 0, sweep0, st.tag, st.k0, st.k1,
+                                     verbose_wg ? (unsigned*)d->d_energy : nullptr));
+        if (verbose_wg) {
+            unsigned w = 0;
+            TSU_HIP_TRY(ctx, hipMemcpyAsync(&w, d->d_energy, 4, hipMemcpyDeviceToHost, ctx->stream));
+            TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            fprintf(stderr, "[tsu] k2_wg n=%d: %d sweeps, slowest fixed point %u iterations\n", d->n, n_sweeps, w);
         }
-        if (k2wg_takes(d)) {
-            // mid-size systems: one workgroup, thread per site, all sweeps of the call in one launch
-            static const bool verbose_wg = dense_env("TSU_K2_VERBOSE", 0) != 0;
-            TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, uni, nullptr, T, nullptr, n_sweeps, 1, 0, sweep0, tag, (uint32_t)seed, (uint32_t)(seed >> 32),
-                                         verbose_wg ? (unsigned*)d->d_energy : nullptr));
-            if (verbose_wg) {
-                unsigned w = 0;
-                TSU_HIP_TRY(ctx, hipMemcpyAsync(&w, d->d_energy, 4, hipMemcpyDeviceToHost, ctx->stream));
-                TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                fprintf(stderr, "[tsu] k2_wg n=%d: %d sweeps, slowest fixed point %u iterations\n", d->n, n_sweeps, w);
-            }
-            return TSU_OK;
-        }
+        return TSU_OK;
     }
     // larger systems, and a caller's order from 128 sites: the whole call in one launch (tsu_dense_one_launch); the block-by-block
     // path takes what none of those kernels does
-    if (d->n >= 2 * DB) {
-        int done = 0;
-        const int rc1 = tsu_dense_one_launch(d, T, nullptr, n_sweeps, 0, 1, nullptr, seed, sweep0, replica, uni, order ? d->order : nullptr, true, &done);
-        if (rc1 != TSU_OK || done) return rc1;
-    } else {
-        dense_forget_fields(d);
+    if (to.route == DenseRoute::OneLaunch) {
+        DenseOutcome done;
+        const int rc1 = tsu_dense_one_launch(d, {T, nullptr, n_sweeps, 0, 1, nullptr, seed, sweep0, replica, uni, order ? d->order : nullptr, true}, &done);
+        if (rc1 != TSU_OK || done == DenseOutcome::Done) return rc1;
     }
+    d->kept.forget();
     if (d->dtype == TSU_DTYPE_F64) return dense_sweep_impl<double>(d, T, n_sweeps, order != nullptr, seed, sweep0, replica, uni != nullptr);
     return dense_sweep_impl<float>(d, T, n_sweeps, order != nullptr, seed, sweep0, replica, uni != nullptr);
 }
@@ -875,33 +854,31 @@ static int dense_run(tsu_dense* d, double T, const double* temps, int n_burnin, 
     const int n = d->n;
     const size_t out_bytes = (size_t)n_samples * n;
     TSU_HIP_TRY(ctx, dense_grow(d->samples, d->samples_cap, out_bytes));
-    const uint32_t tag = TSU_TAG_DENSE | (replica << 8);
-    const int wave_m = order ? 0 : k2w_slots(d);
-    const bool small = wave_m || (!order && k2wg_takes(d));
+    const DenseStream st = dense_stream(seed, replica);
     // The whole run in ONE launch: on the small kernels, or above them on a one-launch kernel, which records the states itself and takes
-    // a temperature per sweep (a loop of calls costs ~60 us per call beside sweeps of 40-100 us at n = 1000-4000) -- where one may
-    // take it (natural order: not after a failed cooperative launch) and the staged orders / uniforms stay within 512 MB
-    const bool one = total > 0 && (small || (n >= 2 * DB && (order || !d->co_disabled) &&
-                                             ((!replay_uniforms && !order) || (size_t)total * n * 8 <= ((size_t)1 << 29))));
-    int done = 0;
+    // a temperature per sweep (a loop of calls costs ~60 us per call beside sweeps of 40-100 us at n = 1000-4000) -- where the route
+    // allows it (dense_route: the staged orders / uniforms count)
+    const DenseRouted to = dense_route(n, d->dtype == TSU_DTYPE_F64, order != nullptr, d->kept.natural_off(),
+                                       (replay_uniforms || order) ? (size_t)total * n * 8 : 0);
+    const bool small = to.route == DenseRoute::Wave || to.route == DenseRoute::Workgroup;
+    const bool one = total > 0 && to.route != DenseRoute::Blocks;
+    DenseOutcome done = DenseOutcome::Declined;
     if (one) {
         const int rc = dense_upload_inputs(d, (int)total, order, false, replay_uniforms, temps);
         if (rc != TSU_OK) return rc;
         const double* uni = replay_uniforms ? d->uniforms : nullptr;
         const double* temps_dev = temps ? d->temps : nullptr;
-        if (wave_m)
-            TSU_HIP_TRY(ctx, k2w_launch(d, wave_m, ctx->stream, uni, d->samples, T, temps_dev, n_burnin, n_sweeps, n_samples, sweep0, tag,
-                                        (uint32_t)seed, (uint32_t)(seed >> 32)));
+        if (to.route == DenseRoute::Wave)
+            TSU_HIP_TRY(ctx, k2w_launch(d, to.m, ctx->stream, uni, d->samples, T, temps_dev, n_burnin, n_sweeps, n_samples, sweep0, st.tag, st.k0, st.k1));
         else if (small)
-            TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, uni, d->samples, T, temps_dev, n_burnin, n_sweeps, n_samples, sweep0, tag, (uint32_t)seed,
-                                         (uint32_t)(seed >> 32), nullptr));
+            TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, uni, d->samples, T, temps_dev, n_burnin, n_sweeps, n_samples, sweep0, st.tag, st.k0, st.k1, nullptr));
         else {
-            const int rc1 = tsu_dense_one_launch(d, T, temps_dev, (int)total, n_burnin, n_sweeps, d->samples, seed, sweep0, replica, uni,
-                                                 order ? d->order : nullptr, false, &done);
+            const int rc1 = tsu_dense_one_launch(d, {T, temps_dev, (int)total, n_burnin, n_sweeps, d->samples, seed, sweep0, replica, uni,
+                                                     order ? d->order : nullptr, false}, &done);
             if (rc1 != TSU_OK) return rc1;
         }
     }
-    if (!small && !done) {
+    if (!small && done != DenseOutcome::Done) {
         // otherwise the sweep paths, one call per recorded state; samples gathered on the device (with a schedule every recorded state
         // is one sweep: n_burnin == 0 and n_sweeps == 1).  Orders staged above were checked there.
         int rc = dense_sweep(d, T, n_burnin, order, seed, sweep0, replica, replay_uniforms, one);
@@ -954,10 +931,9 @@ int tsu_dense_sweep_replicas(tsu_dense* d, int n_replicas, const double* tempera
         TSU_REQUIRE_REPLICA(ctx, replicas[r], "dense_sweep_replicas");
     }
     if (n_sweeps == 0) return TSU_OK;
-    d->rep_match = 0;  // (the kept rows are about to change)
-    const int wave_m = k2w_slots(d);
-    const bool wg = !wave_m && k2wg_takes(d);
-    if (!wave_m && !wg) {
+    DenseKept& k = d->kept;
+    const DenseRouted to = dense_route(n, d->dtype == TSU_DTYPE_F64, false);
+    if (to.route != DenseRoute::Wave && to.route != DenseRoute::Workgroup) {
         // larger systems: up to eight replicas advance together in one launch of the owner-computes kernel (dense_own.hip: every row
         // of J^T is loaded once for all of them), groups of eight one after the other; if the kernel declines, one replica after the
         // other through the sweep paths
@@ -979,40 +955,28 @@ int tsu_dense_sweep_replicas(tsu_dense* d, int n_replicas, const double* tempera
                 d->h_rep = nullptr;
                 (void)hipGetLastError();
             }
-            // one group of replicas: their fields stay on the device from call to call; a state that comes back byte for byte as one
-            // of those the last call returned (in any position: tempering swaps them) resumes from that state's fields
-            const bool keep = n_replicas <= 8;
-            if (keep && !d->rep_prev) {
-                d->rep_prev = (int8_t*)malloc((size_t)8 * n);
-                if (d->rep_prev && hipMalloc(&d->rep_fields[0], (size_t)8 * n * sizeof(double)) == hipSuccess &&
-                    hipMalloc(&d->rep_fields[1], (size_t)8 * n * sizeof(double)) == hipSuccess) {
-                    d->rep_prev_n = 0;
-                } else {
-                    if (d->rep_fields[0]) (void)hipFree(d->rep_fields[0]);
-                    if (d->rep_fields[1]) (void)hipFree(d->rep_fields[1]);
-                    d->rep_fields[0] = d->rep_fields[1] = nullptr;
-                    free(d->rep_prev);
-                    d->rep_prev = nullptr;
+            // one group of replicas: their fields stay on the device from call to call (DenseKept::begin_group)
+            if (n_replicas <= 8 && !k.rep_prev) {
+                k.rep_prev = (int8_t*)malloc((size_t)8 * n);
+                if (!k.rep_prev || hipMalloc(&k.rep_fields[0], (size_t)8 * n * sizeof(double)) != hipSuccess ||
+                    hipMalloc(&k.rep_fields[1], (size_t)8 * n * sizeof(double)) != hipSuccess) {
+                    if (k.rep_fields[0]) (void)hipFree(k.rep_fields[0]);
+                    if (k.rep_fields[1]) (void)hipFree(k.rep_fields[1]);
+                    k.rep_fields[0] = k.rep_fields[1] = nullptr;
+                    free(k.rep_prev);
+                    k.rep_prev = nullptr;
                     (void)hipGetLastError();
                 }
             }
-            const bool can_keep = keep && d->rep_prev && d->rep_fields[1];
-            bool all_known = can_keep && d->rep_prev_n > 0;
-            OwnRep reps[8];
+            int src[8];
+            const DenseResume keep = k.begin_group(states_host + (size_t)r0 * n, (size_t)n, m, mp, n_replicas <= 8 && k.rep_prev && k.rep_fields[1], src);
+            OwnGroup grp;
+            grp.R = mp;
+            grp.states_dev = ds;
             for (int q = 0; q < mp; ++q) {
                 const int r = r0 + (q < m ? q : 0);
-                reps[q].src = -1;
-                if (can_keep)
-                    for (int t = 0; t < d->rep_prev_n && reps[q].src < 0; ++t) {
-                        const int p = (q + t) % d->rep_prev_n;  // (its own position first)
-                        if (memcmp(states_host + (size_t)r * n, d->rep_prev + (size_t)p * n, (size_t)n) == 0) reps[q].src = p;
-                    }
-                all_known = all_known && reps[q].src >= 0;
-                reps[q].T = temperatures[r];
-                reps[q].sweep0 = sweep0s[r];
-                reps[q].tag = TSU_TAG_DENSE | (replicas[r] << 8);
-                reps[q].k0 = (uint32_t)seeds[r];
-                reps[q].k1 = (uint32_t)(seeds[r] >> 32);
+                const DenseStream st = dense_stream(seeds[r], replicas[r]);
+                grp.reps[q] = {temperatures[r], sweep0s[r], st.tag, st.k0, st.k1, src[q]};
                 if (d->h_rep) memcpy(d->h_rep + (size_t)q * n, states_host + (size_t)r * n, (size_t)n);
                 else TSU_HIP_TRY(ctx, hipMemcpyAsync(ds + (size_t)q * n, states_host + (size_t)r * n, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
                 if (du)
@@ -1020,28 +984,20 @@ int tsu_dense_sweep_replicas(tsu_dense* d, int n_replicas, const double* tempera
                                                     hipMemcpyHostToDevice, ctx->stream));
             }
             if (d->h_rep) TSU_HIP_TRY(ctx, hipMemcpyAsync(ds, d->h_rep, (size_t)mp * n, hipMemcpyHostToDevice, ctx->stream));
-            int done = 0;
-            const int own_failed = d->own_failed;
-            const int rc = tsu_dense_own_run(d, mp, reps, ds, n_sweeps, du, nullptr, nullptr, nullptr, 0, 1, all_known, can_keep, &done);
-            if (rc != TSU_OK) {
-                d->rep_prev_n = 0;
-                return rc;
-            }
-            if (!done) {
-                // the replicas' states live in a scratch buffer: nothing of the system was touched, and a give-up here does not take
-                // k2_own away from the single chain (nor does it clear a single-chain give-up: that one stays sticky)
-                d->own_failed = own_failed;
-                d->rep_prev_n = 0;
+            // (the replicas' states live in a scratch buffer: a launch that declines or gives up touched nothing of the system, and
+            // neither takes k2_own away from the single chain nor clears a single-chain give-up)
+            DenseOutcome done = DenseOutcome::GaveUp;
+            const int rc = tsu_dense_own_run(d, {1.0, nullptr, n_sweeps, 0, 1, nullptr, 0, 0, 0, du, nullptr, true}, &grp, keep, &done);
+            if (rc != TSU_OK || done != DenseOutcome::Done) {
+                k.end_group(done, keep, n_sweeps, nullptr, (size_t)n, 0);
+                if (rc != TSU_OK) return rc;
                 all_done = false;
                 break;
             }
             TSU_HIP_TRY(ctx, hipMemcpyAsync(d->h_rep ? d->h_rep : states_host + (size_t)r0 * n, ds, (size_t)m * n, hipMemcpyDeviceToHost, ctx->stream));
             TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             if (d->h_rep) memcpy(states_host + (size_t)r0 * n, d->h_rep, (size_t)m * n);
-            if (can_keep) {
-                memcpy(d->rep_prev, states_host + (size_t)r0 * n, (size_t)m * n);
-                d->rep_prev_n = m;
-            }
+            k.end_group(done, keep, n_sweeps, states_host + (size_t)r0 * n, (size_t)n, m);
             r_done = r0 + m;
         }
         if (all_done) return TSU_OK;
@@ -1064,17 +1020,14 @@ int tsu_dense_sweep_replicas(tsu_dense* d, int n_replicas, const double* tempera
     K2Replica* d_reps = (K2Replica*)((char*)d->rep_buf + ((sbytes + 7) / 8) * 8 + ubytes);
     std::vector<K2Replica> reps((size_t)n_replicas);
     for (int r = 0; r < n_replicas; ++r) {
-        reps[(size_t)r].T = temperatures[r];
-        reps[(size_t)r].sweep0 = sweep0s[r];
-        reps[(size_t)r].tag = TSU_TAG_DENSE | (replicas[r] << 8);
-        reps[(size_t)r].k0 = (uint32_t)seeds[r];
-        reps[(size_t)r].k1 = (uint32_t)(seeds[r] >> 32);
+        const DenseStream st = dense_stream(seeds[r], replicas[r]);
+        reps[(size_t)r] = {temperatures[r], sweep0s[r], st.tag, st.k0, st.k1};
     }
     TSU_HIP_TRY(ctx, hipMemcpyAsync(d_states, states_host, sbytes, hipMemcpyHostToDevice, ctx->stream));
     if (ubytes) TSU_HIP_TRY(ctx, hipMemcpyAsync(d_uni, replay_uniforms, ubytes, hipMemcpyHostToDevice, ctx->stream));
     TSU_HIP_TRY(ctx, hipMemcpyAsync(d_reps, reps.data(), rbytes, hipMemcpyHostToDevice, ctx->stream));
-    if (wave_m)
-        TSU_HIP_TRY(ctx, k2w_launch_replicas(d, wave_m, ctx->stream, n_replicas, d_states, d_uni, d_reps, n_sweeps));
+    if (to.route == DenseRoute::Wave)
+        TSU_HIP_TRY(ctx, k2w_launch_replicas(d, to.m, ctx->stream, n_replicas, d_states, d_uni, d_reps, n_sweeps));
     else  // one workgroup per replica
         TSU_HIP_TRY(ctx, k2wg_launch(d, ctx->stream, d_uni, nullptr, 1.0, nullptr, n_sweeps, 1, 0, 0, 0, 0, 0, nullptr, n_replicas, d_states, d_reps));
     TSU_HIP_TRY(ctx, hipMemcpyAsync(states_host, d_states, sbytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -1090,10 +1043,10 @@ int tsu_dense_energy(tsu_dense* d, double* energy) {
     // the fields f = J s + b: those the pipeline kept for exactly this state (a loop of sweep + energy calls then streams J once per
     // step instead of three times), or one pass over J
     const double* fields = d->field;
-    if (d->fields_valid && d->co_fields) {
+    if (d->kept.fields_valid && d->co_fields) {
         fields = d->co_fields;
-    } else if (d->rep_match > 0 && d->rep_match <= d->rep_prev_n && d->rep_fields[d->rep_cur]) {
-        fields = d->rep_fields[d->rep_cur] + (size_t)(d->rep_match - 1) * d->n;
+    } else if (d->kept.matched_row() >= 0 && d->kept.rep_in()) {
+        fields = d->kept.rep_in() + (size_t)d->kept.matched_row() * d->n;
     } else {
         unsigned mv_grid = (unsigned)(((size_t)d->n * 64 + 255) / 256);
         if (d->dtype == TSU_DTYPE_F64)
@@ -1137,11 +1090,9 @@ int tsu_dense_energies(tsu_dense* d, const int8_t* states_host, int n_states, do
         const int8_t* s = d->samples + (size_t)k * n;
         // ... unless the state is one the last replica call returned: its fields are still on the device (a tempering ladder asks
         // for its chains' energies between their sweeps)
-        const double* kept = nullptr;
-        for (int p = 0; p < d->rep_prev_n && !kept && d->rep_fields[d->rep_cur]; ++p)
-            if (memcmp(states_host + (size_t)k * n, d->rep_prev + (size_t)p * n, n) == 0) kept = d->rep_fields[d->rep_cur] + (size_t)p * n;
-        if (kept) {
-            k2_energy<<<1, 1024, 0, ctx->stream>>>(kept, s, d->bias, d_e + k, d->n);
+        const int row = d->kept.rep_in() ? d->kept.find(states_host + (size_t)k * n, n) : -1;
+        if (row >= 0) {
+            k2_energy<<<1, 1024, 0, ctx->stream>>>(d->kept.rep_in() + (size_t)row * n, s, d->bias, d_e + k, d->n);
             continue;
         }
         if (d->dtype == TSU_DTYPE_F64)

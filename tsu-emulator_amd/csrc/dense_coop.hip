@@ -20,8 +20,6 @@
 //       superblock's rows                                                                                         B
 #include "dense_dev.h"
 
-#define CO_THREADS 1024
-#define CO_MAX_N 65536         // bytes of LDS for the staged state vector (phase A)
 #define CO_SLOTS 64            // iterations recorded per superblock; more than that = not converged (never seen)
 
 struct CoopParams {
@@ -349,7 +347,6 @@ __global__ __launch_bounds__(CO_THREADS) void k2_coop(CoopParams P) {
 #define PP_SB_MAX 8192
 #define PP_TEAMS 4                // 64-row groups per solver workgroup
 #define PP_GRAN_MAX (PP_SB_MAX / 32)
-#define PP_MAXR 24                // rows one streamer wave may own
 #define PB_SOLVED BAR_CNT(1)       // counter words on pages of their own (the grid-barrier layout is not used here)
 // C1 and T count ~240 streamer workgroups each: sharded eight ways by workgroup index (one atomic per ~12 ns on ONE word would put
 // 3 us of arrivals in front of every wait; the guide's "fanin" row), the waiter's first eight lanes poll one shard each
@@ -382,7 +379,7 @@ struct PipeParams {
     const double* temps;  // one temperature per sweep of the call (an annealing schedule), or nullptr: T
     int8_t* samples;      // the state after sweep rec_from + m rec_every (m = 1, 2, ...) goes to samples + (m - 1) n, or nullptr
     int rec_from, rec_every;
-    double* fields_all;  // [n] fields of every row, kept from call to call (see dense.h)
+    double* fields_all;  // [n] fields of every row, kept from call to call (see dense_plan.h)
     int resume;          // fields_all holds the fields of the state the call starts from: no pass over J to rebuild them
     int persist;         // leave the fields of the final state in fields_all (the call's last sweep then updates every row)
     int refresh_off;     // sweeps since the fields were last computed from scratch, at the start of the call
@@ -801,109 +798,89 @@ __global__ __launch_bounds__(CO_THREADS) void k2_pipe(PipeParams P) {
 #undef PP_MARK
 }
 
-template <typename TJ>
-static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, const double* uniforms,
-                      int* done, bool fields_were_valid, const double* temps_dev, int8_t* samples_dev, int rec_from, int rec_every) {
+// ---------------------------------------------------------------------------------------------------------------------- host side
+int dense_launch(tsu_dense* d, const DenseLaunch& L, DenseFlags* out) {
     tsu_ctx* ctx = d->ctx;
-    const int n = d->n;
-    *done = 0;
-    // superblock: 4096 (2048 for systems that fit one): re-measured on the finished pipeline (profiles/r02_k2_notes.txt) -- 8192,
-    // which had won up to n = 12288 half-way through its development, loses everywhere now
-    const int sb = n <= 2048 ? 2048 : 4096;
-    const int ns = sb / 256;
-    // small systems: fewer streamer workgroups (every workgroup takes part in the hand-off counters, and a system of a few hundred
-    // rows has no work for 4000 waves); from 2048 rows up every CU streams.  128 workgroups per 1024 rows: measured (n = 580 / 1024:
-    // 36 / 42 us per sweep; with every CU 46 / 49, with 64 per 1024 rows 40 / 44)
-    int grid = ctx->cus;
-    const int want = ns + (int)(((long long)n * 128 + 1023) / 1024);
-    if (want < grid) grid = want;
-    // smallest system: 452, just above the one-workgroup kernel (k2_wg: 528 fp32 / 448 fp64 sites): 45-50 us per sweep at
-    // n = 580 .. 1020 against 50-62 us on the barrier kernel
-    if (n > CO_MAX_N || n < 452 || grid < 2 * ns) return TSU_OK;
-    if ((long long)(grid - ns) * (CO_THREADS / 64) * PP_MAXR < n) return TSU_OK;
-    if (n % 4) return TSU_OK;  // state / flips travel as dwords
-    const bool vec = (n % JVec<TJ>::W) == 0;
-    // loads in flight per lane on the rows that are not urgent (they run beside the solvers' latency-bound iterations, whose
-    // hand-offs and gathers queue behind them): ONE while those rows take less time than the iterations anyway (N = 16384:
-    // 0.386 -> 0.353 ms per sweep; profiles/r02_k2_notes.txt), eight once the strips dominate
-    const bool gentle = n <= 20480;
-    void (*kern)(PipeParams) = sb == 2048 ? (vec ? k2_pipe<TJ, true, 2048, 1> : k2_pipe<TJ, false, 2048, 1>)
-                               : gentle   ? (vec ? k2_pipe<TJ, true, 4096, 1> : k2_pipe<TJ, false, 4096, 1>)
-                                          : (vec ? k2_pipe<TJ, true, 4096, 8> : k2_pipe<TJ, false, 4096, 8>);
-    const size_t lds_bytes = (size_t)((n > sb ? n : sb) + 15) / 16 * 16;
-    if (tsu_func_allow_lds(ctx, (const void*)kern, (int)lds_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return TSU_OK;
-    }
+    static const int verbose = dense_env("TSU_K2_VERBOSE", 0);
+    out->status = DenseFlags::Ran, out->timed = false, out->err = out->slowest = out->not_converged = 0;
     int per_cu = 0;
-    if (tsu_func_blocks_per_cu(ctx, (const void*)kern, CO_THREADS, lds_bytes, &per_cu) != hipSuccess || per_cu < 1) {
+    if (L.lds_bytes > L.lds_free && tsu_func_allow_lds(ctx, L.kern, (int)L.lds_bytes) != hipSuccess) out->status = DenseFlags::NoLds;
+    else if (tsu_func_blocks_per_cu(ctx, L.kern, (int)L.threads, L.lds_bytes, &per_cu) != hipSuccess || per_cu < 1) out->status = DenseFlags::NoRoom;
+    if (out->status != DenseFlags::Ran) {
         (void)hipGetLastError();
         return TSU_OK;
     }
     if (!d->co_bar) TSU_HIP_TRY(ctx, hipMalloc(&d->co_bar, BAR_WORDS * sizeof(unsigned)));
+    if (L.whole_bar) TSU_HIP_TRY(ctx, hipMemsetAsync(d->co_bar, 0, BAR_WORDS * sizeof(unsigned), ctx->stream));
+    else TSU_HIP_TRY(ctx, hipMemsetAsync(d->co_bar + BAR_ERR, 0, 4 * sizeof(unsigned), ctx->stream));
+    *L.bar = d->co_bar;
+    unsigned long long* d_tl = nullptr;
+    if (verbose >= 2) {
+        TSU_HIP_TRY(ctx, hipMalloc(&d_tl, L.tl_words * sizeof(unsigned long long)));
+        TSU_HIP_TRY(ctx, hipMemsetAsync(d_tl, 0, L.tl_words * sizeof(unsigned long long), ctx->stream));
+    }
+    *L.timeline = d_tl;
+    // such launches are chained per device; the launch goes through tsu_launch_grid_sync (cooperative API by default).  The kernels'
+    // bounded waits stay: they turn a GPU shared with another process's long kernel into a give-up instead of a hang.
+    int rc = tsu_grid_exclusive_begin(ctx);
+    if (rc != TSU_OK) return rc;
+    if (tsu_launch_grid_sync(ctx, L.kern, dim3(L.grid), dim3(L.threads), L.params, L.lds_bytes, ctx->stream) != hipSuccess) {
+        (void)hipGetLastError();  // launch not possible in this configuration: not an error, the caller's other paths take the call
+        if (d_tl) (void)hipFree(d_tl);
+        out->status = DenseFlags::Refused;
+        return TSU_OK;
+    }
+    rc = tsu_grid_exclusive_end(ctx);
+    if (rc != TSU_OK) return rc;
+    if (!d->h_flags && hipHostMalloc((void**)&d->h_flags, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) {
+        d->h_flags = nullptr;
+        (void)hipGetLastError();
+    }
+    unsigned hbuf[4];
+    unsigned* h = d->h_flags ? d->h_flags : hbuf;
+    TSU_HIP_TRY(ctx, hipMemcpyAsync(h + 1, d->co_bar + BAR_ERR, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    out->err = h[1], out->slowest = h[2], out->not_converged = h[3];
+    if (d_tl) {
+        (void)hipMemcpy(out->tl, d_tl, L.tl_words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+        (void)hipFree(d_tl);
+        out->timed = true;
+    }
+    return TSU_OK;
+}
+
+template <typename TJ>
+static int pipe_sweep(tsu_dense* d, const DenseCall& c, const DenseResume& keep, DenseOutcome* out) {
+    tsu_ctx* ctx = d->ctx;
+    const int n = d->n;
+    *out = DenseOutcome::Declined;
+    const PipePlan pl = pipe_plan(n, sizeof(TJ) == 8, ctx->cus);
+    if (!pl.takes) return TSU_OK;
+    static_assert(JVec<float>::W == 4 && JVec<double>::W == 2, "pipe_plan / coop_plan: vec");
+    const bool vec = pl.vec;
+    void (*kern)(PipeParams) = pl.sb == 2048 ? (vec ? k2_pipe<TJ, true, 2048, 1> : k2_pipe<TJ, false, 2048, 1>)
+                               : pl.u2 == 1  ? (vec ? k2_pipe<TJ, true, 4096, 1> : k2_pipe<TJ, false, 4096, 1>)
+                                             : (vec ? k2_pipe<TJ, true, 4096, 8> : k2_pipe<TJ, false, 4096, 8>);
     if (!d->co_d1) TSU_HIP_TRY(ctx, hipMalloc(&d->co_d1, (size_t)n));
     if (!d->pp_masks) TSU_HIP_TRY(ctx, hipMalloc(&d->pp_masks, 3 * PP_GRAN_MAX * sizeof(unsigned long long)));
     if (!d->co_corr) TSU_HIP_TRY(ctx, hipMalloc(&d->co_corr, (size_t)n * 8));
     if (!d->co_d0) TSU_HIP_TRY(ctx, hipMalloc(&d->co_d0, (size_t)n));
     if (!d->co_fields) TSU_HIP_TRY(ctx, hipMalloc(&d->co_fields, (size_t)n * 8));
-    TSU_HIP_TRY(ctx, hipMemsetAsync(d->co_bar, 0, BAR_WORDS * sizeof(unsigned), ctx->stream));
     TSU_HIP_TRY(ctx, hipMemsetAsync(d->pp_masks, 0, 3 * PP_GRAN_MAX * sizeof(unsigned long long), ctx->stream));
+    const DenseStream st = dense_stream(c.seed, c.replica);
     PipeParams P;
-    P.J = d->J;
-    P.JT = d->JT;
-    P.bias = d->bias;
-    P.state = d->state;
-    P.f = d->field;
-    P.d1 = d->co_d1;
-    P.uniforms = uniforms;
-    P.masks = d->pp_masks;
-    P.corr = d->co_corr;
-    P.d0 = d->co_d0;
-    P.bar = d->co_bar;
-    P.n = n;
-    P.n_sweeps = n_sweeps;
-    P.T = T;
-    P.sweep0 = sweep0;
-    P.tag = TSU_TAG_DENSE | (replica << 8);
-    P.k0 = (uint32_t)seed;
-    P.k1 = (uint32_t)(seed >> 32);
-    // fields from call to call: resume when the previous pipeline call left them for exactly this state and no refresh is due;
-    // keep them from the second consecutive call on (a lone call does not pay for rows it would not need again)
-    P.fields_all = d->co_fields;
-    P.temps = temps_dev;
-    P.samples = samples_dev;
-    P.rec_from = rec_from;
-    P.rec_every = rec_every > 0 ? rec_every : 1;
-    P.resume = fields_were_valid && (d->since_refresh % CO_REFRESH) != 0 ? 1 : 0;
-    P.refresh_off = P.resume ? d->since_refresh : 0;
-    P.persist = d->pipe_streak >= 1 ? 1 : 0;
-    unsigned long long* d_tl = nullptr;
-    if (dense_env("TSU_K2_VERBOSE", 0) >= 2) {
-        TSU_HIP_TRY(ctx, hipMalloc(&d_tl, 10 * sizeof(unsigned long long)));
-        TSU_HIP_TRY(ctx, hipMemsetAsync(d_tl, 0, 10 * sizeof(unsigned long long), ctx->stream));
-    }
-    P.timeline = d_tl;
-    {
-        const int rcx = tsu_grid_exclusive_begin(ctx);
-        if (rcx != TSU_OK) return rcx;
-    }
-    hipError_t e = tsu_launch_grid_sync(ctx, (const void*)kern, dim3((unsigned)grid), dim3(CO_THREADS), &P, lds_bytes, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (d_tl) (void)hipFree(d_tl);
-        return TSU_OK;
-    }
-    {
-        const int rcx = tsu_grid_exclusive_end(ctx);
-        if (rcx != TSU_OK) return rcx;
-    }
-    unsigned h[4];
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(h + 1, d->co_bar + BAR_ERR, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (d_tl) {
-        unsigned long long tl[10];
-        (void)hipMemcpy(tl, d_tl, sizeof(tl), hipMemcpyDeviceToHost);
-        (void)hipFree(d_tl);
+    P.J = d->J, P.JT = d->JT, P.bias = d->bias, P.state = d->state, P.f = d->field, P.fields_all = d->co_fields;
+    P.d0 = d->co_d0, P.d1 = d->co_d1, P.corr = d->co_corr, P.masks = d->pp_masks;
+    P.n = n, P.n_sweeps = c.n_sweeps, P.T = c.T, P.temps = c.temps_dev, P.uniforms = c.uniforms_dev;
+    P.sweep0 = c.sweep0, P.tag = st.tag, P.k0 = st.k0, P.k1 = st.k1;
+    P.samples = c.samples_dev, P.rec_from = c.rec_from, P.rec_every = c.rec_every > 0 ? c.rec_every : 1;
+    P.resume = keep.resume, P.refresh_off = keep.refresh_off, P.persist = keep.persist;
+    DenseFlags fl;
+    const int rc = dense_launch(d, {(const void*)kern, (unsigned)pl.grid, CO_THREADS, pl.lds_bytes, 0, &P, &P.bar, &P.timeline, 10, true}, &fl);
+    if (rc != TSU_OK || fl.status != DenseFlags::Ran) return rc;
+    if (fl.timed) {
+        const unsigned long long* tl = fl.tl;
+        const int sb = pl.sb, n_sweeps = c.n_sweeps;
         const double nsb_tot = (double)n_sweeps * ((n + sb - 1) / sb);
         fprintf(stderr, "[tsu] k2_pipe n=%d (superblocks of %d), %d sweeps; per superblock: wait C1 %.1f us, poll %.1f us, gather+decide %.1f us, commit+prologue %.1f us, "
                         "%.1f iterations, %.0f toggles\n", n, sb, n_sweeps, tl[0] / 100.0 / nsb_tot, tl[1] / 100.0 / nsb_tot, tl[2] / 100.0 / nsb_tot,
@@ -911,180 +888,111 @@ static int pipe_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint3
         fprintf(stderr, "[tsu]   streamer wave: wait SOLVED %.1f us, stage flips %.1f us, priority rows + signal %.1f us, other rows %.1f us\n",
                 tl[6] / 100.0 / nsb_tot, tl[7] / 100.0 / nsb_tot, tl[8] / 100.0 / nsb_tot, tl[9] / 100.0 / nsb_tot);
     }
-    if (h[1] || h[3]) {
-        // a wait expired (GPU shared with another long-running kernel) or -- never seen -- no fixed point: the state is restored
-        // from the backup and the other paths take the call
-        fprintf(stderr, "[tsu] dense sweep (pipeline): %s; continuing on the barrier path\n", h[1] ? "a wait timed out (GPU shared?)" : "no fixed point");
-        d->pp_failed = 1;
+    if (fl.err || fl.not_converged) {
+        // a wait expired (GPU shared with another long-running kernel) or -- never seen -- no fixed point
+        fprintf(stderr, "[tsu] dense sweep (pipeline): %s; continuing on the barrier path\n", fl.err ? "a wait timed out (GPU shared?)" : "no fixed point");
+        *out = DenseOutcome::GaveUp;
         return TSU_OK;
     }
-    *done = 1;
+    *out = DenseOutcome::Done;
     d->n_pipe += 1;
-    d->since_refresh = (P.refresh_off + n_sweeps) % CO_REFRESH;
-    d->fields_valid = P.persist;
-    d->pipe_streak += 1;
     return TSU_OK;
 }
 
+// *disable: the grid does not fit, the launch was refused or the barrier timed out (the driver's sticky switch)
 template <typename TJ>
-static int coop_sweep(tsu_dense* d, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica, const double* uniforms,
-                      int* done) {
+static int coop_sweep(tsu_dense* d, const DenseCall& c, DenseOutcome* out, bool* disable) {
     tsu_ctx* ctx = d->ctx;
     const int n = d->n;
-    *done = 0;
-    if (n > CO_MAX_N) return TSU_OK;  // the staged state vector must fit in LDS: larger systems take the block-by-block path
-    const bool vec = (n % JVec<TJ>::W) == 0;
-    void (*kern)(CoopParams) = vec ? k2_coop<TJ, true> : k2_coop<TJ, false>;
-    const size_t lds_bytes = (size_t)((n > SB_SIZE ? n : SB_SIZE) + 15) / 16 * 16;
-    if (lds_bytes > 48 * 1024 && tsu_func_allow_lds(ctx, (const void*)kern, (int)lds_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return TSU_OK;
-    }
-    int per_cu = 0;
-    if (tsu_func_blocks_per_cu(ctx, (const void*)kern, CO_THREADS, lds_bytes, &per_cu) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        d->co_disabled = 1;
-        return TSU_OK;
-    }
-    const int nsb = (n + SB_SIZE - 1) / SB_SIZE;
-    const size_t count_ints = (size_t)n_sweeps * nsb * CO_SLOTS;
+    *out = DenseOutcome::Declined;
+    const CoopPlan pl = coop_plan(n, sizeof(TJ) == 8, ctx->cus);
+    if (!pl.takes) return TSU_OK;
+    void (*kern)(CoopParams) = pl.vec ? k2_coop<TJ, true> : k2_coop<TJ, false>;
+    const size_t count_ints = (size_t)c.n_sweeps * pl.nsb * CO_SLOTS;
     // (the pipeline kernel may have created some of these already)
     if (!d->co_logit) TSU_HIP_TRY(ctx, hipMalloc(&d->co_logit, (size_t)n * 8));
     if (!d->co_corr) TSU_HIP_TRY(ctx, hipMalloc(&d->co_corr, (size_t)n * 8));
     if (!d->co_d0) TSU_HIP_TRY(ctx, hipMalloc(&d->co_d0, (size_t)n));
     if (!d->co_d1) TSU_HIP_TRY(ctx, hipMalloc(&d->co_d1, (size_t)n));
     if (!d->co_lists) TSU_HIP_TRY(ctx, hipMalloc(&d->co_lists, 2 * SB_SIZE * sizeof(int)));
-    if (!d->co_bar) TSU_HIP_TRY(ctx, hipMalloc(&d->co_bar, BAR_WORDS * sizeof(unsigned)));
     TSU_HIP_TRY(ctx, dense_grow(d->co_counts, d->co_counts_cap, count_ints * sizeof(int)));
     TSU_HIP_TRY(ctx, hipMemsetAsync(d->co_counts, 0, count_ints * sizeof(int), ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemsetAsync(d->co_bar, 0, BAR_WORDS * sizeof(unsigned), ctx->stream));
+    const DenseStream st = dense_stream(c.seed, c.replica);
     CoopParams P;
-    P.J = d->J;
-    P.bias = d->bias;
-    P.s0 = d->state;
-    P.s1 = d->state2;
-    P.f = d->field;
-    P.lg = d->co_logit;
-    P.corr = d->co_corr;
-    P.d0 = d->co_d0;
-    P.d1 = d->co_d1;
-    P.uniforms = uniforms;
-    P.lists = d->co_lists;
-    P.counts = d->co_counts;
-    P.bar = d->co_bar;
-    P.n = n;
-    P.n_sweeps = n_sweeps;
-    P.T = T;
-    P.sweep0 = sweep0;
-    P.tag = TSU_TAG_DENSE | (replica << 8);
-    P.k0 = (uint32_t)seed;
-    P.k1 = (uint32_t)(seed >> 32);
-    const int verbose = dense_env("TSU_K2_VERBOSE", 0);
-    unsigned long long* d_tl = nullptr;
-    if (verbose >= 2) TSU_HIP_TRY(ctx, hipMalloc(&d_tl, 8 * sizeof(unsigned long long)));
-    P.timeline = d_tl;
-    // one workgroup per CU: every phase is either a stream (16 waves x 8 loads in flight per CU) or tiny, and fewer
-    // arrivals make a cheaper barrier; small systems use fewer workgroups still
-    int grid = ctx->cus;
-    const int useful = (n + CO_THREADS / 64 - 1) / (CO_THREADS / 64);
-    if (grid > useful) grid = useful;
-    // The grid is one workgroup per CU at most and fits the device (occupancy query above); the launch goes through
-    // tsu_launch_grid_sync (cooperative API by default).  The bounded wait in the barrier stays: it turns a GPU shared
-    // with another process's long kernel into the fallback below instead of a hang.
-    {
-        const int rcx = tsu_grid_exclusive_begin(ctx);
-        if (rcx != TSU_OK) return rcx;
-    }
-    hipError_t e = tsu_launch_grid_sync(ctx, (const void*)kern, dim3((unsigned)grid), dim3(CO_THREADS), &P, lds_bytes, ctx->stream);
-    if (e != hipSuccess) {  // launch not possible in this configuration: not an error, use the other path
-        (void)hipGetLastError();
-        d->co_disabled = 1;
+    P.J = d->J, P.bias = d->bias, P.s0 = d->state, P.s1 = d->state2, P.f = d->field, P.lg = d->co_logit;
+    P.d0 = d->co_d0, P.d1 = d->co_d1, P.corr = d->co_corr, P.lists = d->co_lists, P.counts = d->co_counts;
+    P.n = n, P.n_sweeps = c.n_sweeps, P.T = c.T, P.uniforms = c.uniforms_dev;
+    P.sweep0 = c.sweep0, P.tag = st.tag, P.k0 = st.k0, P.k1 = st.k1;
+    DenseFlags fl;
+    const int rc = dense_launch(d, {(const void*)kern, (unsigned)pl.grid, CO_THREADS, pl.lds_bytes, 48 * 1024, &P, &P.bar, &P.timeline, 8, true}, &fl);
+    if (rc != TSU_OK) return rc;
+    if (fl.status != DenseFlags::Ran) {
+        *disable = fl.status != DenseFlags::NoLds;
         return TSU_OK;
     }
-    {
-        const int rcx = tsu_grid_exclusive_end(ctx);
-        if (rcx != TSU_OK) return rcx;
-    }
-    unsigned h[4];  // [1] = error flag, [2] = slowest fixed point, [3] = not-converged flag
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(h + 1, d->co_bar + BAR_ERR, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (h[1]) {
+    if (fl.err) {
         // a workgroup waited 4 s at a barrier: the grid was not co-resident (GPU shared with another long-running
         // kernel).  The state is restored from the backup and the block-by-block path takes the call.
         fprintf(stderr, "[tsu] dense sweep: grid barrier timed out (GPU shared?); continuing on the block-by-block path\n");
-        d->co_disabled = 1;
-        if (d_tl) (void)hipFree(d_tl);
+        *disable = true;
+        *out = DenseOutcome::GaveUp;
         return TSU_OK;
     }
-    if (d_tl) {
-        unsigned long long tl[8];
-        (void)hipMemcpy(tl, d_tl, sizeof(tl), hipMemcpyDeviceToHost);
-        (void)hipFree(d_tl);
+    if (fl.timed) {
+        const unsigned long long* tl = fl.tl;
         const char* nm[4] = {"A field", "T triangular", "I incremental", "C commit+strips"};
         for (int q = 0; q < 4; ++q)
             fprintf(stderr, "[tsu]   phase %-16s %6llu x  %8.1f us total  %6.2f us each\n", nm[q], tl[4 + q], tl[q] / 100.0, tl[4 + q] ? tl[q] / 100.0 / tl[4 + q] : 0.0);
     }
-    if (verbose)
-        fprintf(stderr, "[tsu] dense cooperative: n=%d, %d workgroups, %d sweeps, slowest fixed point after %u iterations%s\n", n, grid,
-                n_sweeps, h[2], h[3] ? " (NOT converged)" : "");
-    if (h[3]) return TSU_OK;  // *done stays 0: the state is restored and the block-by-block path takes the call
-    if (n_sweeps & 1) {
+    if (dense_env("TSU_K2_VERBOSE", 0))
+        fprintf(stderr, "[tsu] dense cooperative: n=%d, %d workgroups, %d sweeps, slowest fixed point after %u iterations%s\n", n, pl.grid,
+                c.n_sweeps, fl.slowest, fl.not_converged ? " (NOT converged)" : "");
+    *out = fl.not_converged ? DenseOutcome::GaveUp : DenseOutcome::Done;
+    if (!fl.not_converged && (c.n_sweeps & 1)) {
         int8_t* tmp = d->state;
         d->state = d->state2;
         d->state2 = tmp;
     }
-    *done = 1;
     return TSU_OK;
 }
 
-int tsu_dense_one_launch(tsu_dense* d, double T, const double* temps_dev, int n_sweeps, int rec_from, int rec_every, int8_t* samples_dev,
-                         uint64_t seed, uint32_t sweep0, uint32_t replica, const double* uniforms_dev, const int64_t* order_dev, bool plain,
-                         int* done) {
+int tsu_dense_one_launch(tsu_dense* d, const DenseCall& c, DenseOutcome* out) {
     tsu_ctx* ctx = d->ctx;
+    DenseKept& k = d->kept;
     const bool f64 = d->dtype == TSU_DTYPE_F64;
-    *done = 0;
-    // whatever runs below, the fields kept from the last call stop being those of d->state: the kernel that takes the call sets them
-    // again, and it is handed the streak of consecutive one-launch calls (the second one starts to keep the fields)
-    bool fields_were_valid = d->fields_valid != 0;
-    const int streak = d->pipe_streak;
-    dense_forget_fields(d);
-    // (natural order: a cooperative launch that could not run or timed out once takes all three kernels out for this handle)
-    if (n_sweeps <= 0 || (!order_dev && d->co_disabled)) return TSU_OK;
+    *out = DenseOutcome::Declined;
+    // (whatever runs below, the kept fields stop being those of d->state -- begin_single forgets them first, the kernels that use none
+    // come after a forget() -- until the kernel that takes the call sets them again)
+    if (c.n_sweeps <= 0) {
+        k.forget();
+        return TSU_OK;
+    }
     TSU_HIP_TRY(ctx, hipMemcpyAsync(d->backup, d->state, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
-    if (!d->own_failed) {
-        OwnRep rep;
-        rep.T = T;
-        rep.sweep0 = sweep0;
-        rep.tag = TSU_TAG_DENSE | (replica << 8);
-        rep.k0 = (uint32_t)seed;
-        rep.k1 = (uint32_t)(seed >> 32);
-        d->pipe_streak = streak;
-        const int rc = tsu_dense_own_run(d, 1, &rep, d->state, n_sweeps, uniforms_dev, order_dev, temps_dev, samples_dev, rec_from, rec_every,
-                                         fields_were_valid, true, done);
-        if (!*done) d->pipe_streak = 0;
-        if (rc != TSU_OK || *done) return rc;
-        if (d->own_failed) {  // it ran and gave up half way (later calls skip it): back to the state at the start of the call
+    // k2_own, then k2_pipe (natural order only): each is skipped once it has given up on this handle
+    for (int which = 0; which < (c.order_dev ? 1 : 2); ++which) {
+        int& failed = which == 0 ? k.own_failed : k.pp_failed;
+        if (failed) continue;
+        const DenseResume keep = k.begin_single();
+        const int rc = which == 0 ? tsu_dense_own_run(d, c, nullptr, keep, out)
+                       : f64      ? pipe_sweep<double>(d, c, keep, out)
+                                  : pipe_sweep<float>(d, c, keep, out);
+        if (rc != TSU_OK) return rc;
+        k.end_single(*out, keep, c.n_sweeps);
+        if (*out == DenseOutcome::Done) return TSU_OK;
+        if (*out == DenseOutcome::GaveUp) {  // it ran and left the state half updated: back to the state at the start of the call
+            failed = 1;
             TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
-            fields_were_valid = false;
         }
     }
-    if (order_dev) return TSU_OK;  // the other two run in natural order only
-    if (!d->pp_failed) {
-        d->pipe_streak = streak;
-        const int rc = f64 ? pipe_sweep<double>(d, T, n_sweeps, seed, sweep0, replica, uniforms_dev, done, fields_were_valid, temps_dev, samples_dev,
-                                                rec_from, rec_every)
-                           : pipe_sweep<float>(d, T, n_sweeps, seed, sweep0, replica, uniforms_dev, done, fields_were_valid, temps_dev, samples_dev,
-                                               rec_from, rec_every);
-        if (!*done) d->pipe_streak = 0;
-        if (rc != TSU_OK || *done) return rc;
-        if (d->pp_failed)  // as above
-            TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    if (!plain) return TSU_OK;  // (k2_coop neither records states nor follows a schedule)
-    const int rc = f64 ? coop_sweep<double>(d, T, n_sweeps, seed, sweep0, replica, uniforms_dev, done)
-                       : coop_sweep<float>(d, T, n_sweeps, seed, sweep0, replica, uniforms_dev, done);
-    if (rc != TSU_OK || *done) return rc;
+    k.forget();
+    *out = DenseOutcome::Declined;
+    if (c.order_dev || !c.plain) return TSU_OK;  // (k2_coop runs in natural order only and neither records states nor follows a schedule)
+    bool disable = false;
+    const int rc = f64 ? coop_sweep<double>(d, c, out, &disable) : coop_sweep<float>(d, c, out, &disable);
+    if (disable) k.co_disabled = 1;
+    if (rc != TSU_OK || *out == DenseOutcome::Done) return rc;
     // declined, could not launch, timed out or found no fixed point
+    *out = DenseOutcome::Declined;
     TSU_HIP_TRY(ctx, hipMemcpyAsync(d->state, d->backup, (size_t)d->n, hipMemcpyDeviceToDevice, ctx->stream));
     return TSU_OK;
 }

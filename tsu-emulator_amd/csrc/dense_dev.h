@@ -3,7 +3,6 @@
 #pragma once
 #include "dense.h"
 
-#define CO_REFRESH 64          // sweeps between two full recomputations of the fields (bounds floating-point drift)
 #define CO_TIMEOUT 400000000ll // wall_clock64 ticks (100 MHz): 4 s
 
 #define BAR_PAGE 1024                 // unsigned per 4 KiB page
@@ -67,3 +66,25 @@ static __device__ __forceinline__ void st(V* p, V v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- launch envelope
+// What the three one-launch kernels do around their launch, once (dense_coop.hip): the LDS opt-in and the occupancy query, the counter
+// page (made on first use) and its clear, the TSU_K2_VERBOSE=2 timeline buffer, the chained launch of a co-resident grid, the three words
+// at BAR_ERR back through pinned memory (a copy into pageable memory is staged and costs ~10 us more per call), the synchronise and the
+// timeline's fetch.
+struct DenseLaunch {
+    const void* kern;
+    unsigned grid, threads;
+    size_t lds_bytes, lds_free;     // dynamic LDS; how much of it needs no opt-in (0: always ask)
+    void* params;                   // the kernel's parameter struct; the envelope fills in ...
+    unsigned** bar;                 // ... its counter page
+    unsigned long long** timeline;  // ... and its timeline (tl_words of them, or nullptr)
+    int tl_words;
+    bool whole_bar;  // clear the whole page (k2_coop's barrier, k2_pipe's hand-off counters) or only the four words at BAR_ERR (k2_own)
+};
+struct DenseFlags {
+    enum { Ran, NoLds, NoRoom, Refused } status;  // not Ran: nothing ran (no LDS opt-in / the grid does not fit / the runtime refused it)
+    bool timed;                                   // tl holds a timeline
+    unsigned err, slowest, not_converged;         // a wait timed out / slowest fixed point / no fixed point
+    unsigned long long tl[12];                    // (timed only)
+};
+int dense_launch(tsu_dense* d, const DenseLaunch& L, DenseFlags* out);

@@ -22,7 +22,7 @@
 //     polls replica rho's granules, scans its toggles and gathers short lists by itself (rep_step); long lists go to all sixteen
 //     waves as a union list -- a row of J^T loaded once for the union of the replicas' toggles and applied to each replica's
 //     accumulator with that replica's sign -- built by all sixteen waves (build_par).  The replicas' fields stay on the device
-//     from call to call (dense.h: rep_fields).
+//     from call to call (dense_plan.h: rep_fields).
 //   * Solo generations (one chain): after the first correction pass a generation moves a handful of sites; the deciding wave then
 //     runs it alone -- decide, publish, poll, scan, gather, reduce -- with no workgroup barrier; the other waves are called in for
 //     long lists only.
@@ -31,13 +31,6 @@
 
 #include "dense_dev.h"
 
-#define OWN_THREADS 1024
-#define OWN_WAVES (OWN_THREADS / 64)
-#define OWN_RING 8              // superblocks whose final masks are kept (a workgroup is active at least once per sweep, and cannot be
-                                // active before it has applied every earlier superblock: nobody lags more than a sweep = at most
-                                // OWN_RING superblocks, checked by the host)
-#define OWN_TAG_SPAN 16384u     // generation g of superblock number q carries tag q * SPAN + g + 1 (0 = never written)
-#define OWN_MAX_R 8
 #define OWN_SOLO_MAX 32           // toggle-list entries (before the workgroup's last row) a deciding wave gathers by itself (natural order; a caller's: 48)
 #ifndef OWN_REP_QUAD
 #define OWN_REP_QUAD 0          // replicas: 0 = one row per lane, scalar multipliers (own_axpy_rep); 1 = the quad layout in groups of four replicas
@@ -57,7 +50,7 @@ struct OwnParams {
     const int64_t* order;        // [n_sweeps][n] visiting orders, or nullptr (natural order)
     const double* temps;         // one temperature per sweep (R == 1), or nullptr
     int8_t* samples;             // (R == 1) the state after sweep rec_from + m rec_every goes to samples + (m - 1) n, or nullptr
-    double* fields_all;          // [R][n] fields kept from call to call (dense.h): read at the start of a resumed call (row rep[rho].src) ...
+    double* fields_all;          // [R][n] fields kept from call to call (dense_plan.h): read at the start of a resumed call (row rep[rho].src) ...
     double* fields_out;          // ... written at the end of a call that keeps them (several replicas: another buffer -- the rows change places)
     unsigned long long* timeline;
     int n, n_sweeps;
@@ -1347,99 +1340,33 @@ __global__ __launch_bounds__(OWN_THREADS) void k2_own(OwnParams P) {
 typedef void (*own_kern)(OwnParams);
 
 template <typename TJ>
-static own_kern own_pick(int M, int R, bool ord) {
-    if (ord) return M == 1 ? k2_own<TJ, 1, 1, true> : M == 2 ? k2_own<TJ, 2, 1, true> : k2_own<TJ, 4, 1, true>;
-    if (R == 1) return M == 1 ? k2_own<TJ, 1, 1, false> : M == 2 ? k2_own<TJ, 2, 1, false> : k2_own<TJ, 4, 1, false>;
-    if (M != 1) return nullptr;
-    return R == 2 ? k2_own<TJ, 1, 2, false> : R == 4 ? k2_own<TJ, 1, 4, false> : R == 8 ? k2_own<TJ, 1, 8, false> : nullptr;
+static own_kern own_pick(int sel) {  // (OwnPlan::sel)
+    if (sel < 3) return sel == 0 ? k2_own<TJ, 1, 1, true> : sel == 1 ? k2_own<TJ, 2, 1, true> : k2_own<TJ, 4, 1, true>;
+    if (sel < 6) return sel == 3 ? k2_own<TJ, 1, 1, false> : sel == 4 ? k2_own<TJ, 2, 1, false> : k2_own<TJ, 4, 1, false>;
+    return sel == 6 ? k2_own<TJ, 1, 2, false> : sel == 7 ? k2_own<TJ, 1, 4, false> : sel == 8 ? k2_own<TJ, 1, 8, false> : nullptr;
 }
 
-// One launch of k2_own: n_sweeps sweeps of R states.  *done = 0: the kernel does not take this call (the caller's other paths do;
-// nothing was written) or it gave up half way (d->own_failed set: the caller restores the state from its backup).
-//   states_dev: [R][n] device states (R == 1: d->state), uniforms_dev: [R][n_sweeps][n] or nullptr, order_dev: [n_sweeps][n] or nullptr
-int tsu_dense_own_run(tsu_dense* d, int R_real, const OwnRep* reps, int8_t* states_dev, int n_sweeps, const double* uniforms_dev,
-                      const int64_t* order_dev, const double* temps_dev, int8_t* samples_dev, int rec_from, int rec_every, bool fields_were_valid,
-                      bool allow_persist, int* done) {
+int tsu_dense_own_run(tsu_dense* d, const DenseCall& c, const OwnGroup* g, const DenseResume& keep, DenseOutcome* out) {
     tsu_ctx* ctx = d->ctx;
-    const int n = d->n;
-    *done = 0;
-    static const int use_own = dense_env("TSU_K2_OWN", 1);
-    static const int own_min = dense_env("TSU_K2_OWN_MIN", 2048);
-    const int sb_env = dense_env("TSU_K2_OWN_SB", 0), m_env = dense_env("TSU_K2_OWN_M", 0);  // (read per call: tests vary them)
-    if (!use_own || d->own_failed || n < own_min || n > 65536 || n_sweeps <= 0) return TSU_OK;
-    const bool ord = order_dev != nullptr;
-    if (R_real < 1 || R_real > OWN_MAX_R || (ord && R_real != 1)) return TSU_OK;
-    const int R = R_real == 1 ? 1 : R_real == 2 ? 2 : R_real <= 4 ? 4 : 8;
-    int M = 0;
-    for (int m = (m_env == 2 || m_env == 4) ? m_env : 1; m <= 4; m *= 2)
-        if ((n + 64 * m - 1) / (64 * m) <= ctx->cus) {
-            M = m;
-            break;
-        }
-    if (!M || (R > 1 && M != 1) || n % 4) return TSU_OK;  // (rows travel as quads)
-    const int RW = 64 * M, W = (n + RW - 1) / RW, G = W * M;
-    if (W < 2) return TSU_OK;
-    // superblock: 4096 positions in natural order; a caller's order pays more per generation (every workgroup polls every group and
-    // follows every toggle), so fewer, longer fixed points win there: the largest of 16384 / 8192 / 4096 whose toggle list fits the LDS
-    // (n = 16384: 0.429 / 0.349 / 0.317 / 0.293 ms per sweep at 2048 / 4096 / 8192 / 16384)
-    int sb = 0, sbw = 0, lmax = 0, nsb = 0, NP = 0;
-    const int NA = ord ? 2 : R;
-    size_t lds_bytes = 0;
-    const int cands[3] = {16384, 8192, 4096};
-    for (int ci = sb_env > 0 ? 2 : (ord ? 0 : 2); ci < 3; ++ci) {
-        sb = sb_env > 0 ? sb_env : cands[ci];
-        if (R > 1 && sb > 4096) sb = 4096;  // (replicas: a deciding wave polls one group per lane)
-        if (sb < RW) sb = RW;
-        if (sb > 16384) sb = 16384;
-        sbw = sb / RW;
-        if (sbw > W) sbw = W;
-        lmax = sbw * RW;
-        nsb = ord ? (n + sbw * RW - 1) / (sbw * RW) : (W + sbw - 1) / sbw;
-        NP = ord ? G : sbw * M;
-        lds_bytes = ((size_t)8 * (R * G + 2 * R * NP) + (size_t)8 * OWN_WAVES * NA * M * 64 + (size_t)4 * lmax + (size_t)8 * (3 * R + 1) * M * 64 +
-                     (ord ? (size_t)2 * n : (R > 1 ? (size_t)R * 64 * 4 : 0)) + 15) / 16 * 16;
-        if (lds_bytes <= 150 * 1024) break;
-    }
-    if (!ord && nsb > OWN_RING) return TSU_OK;
-    if ((long long)n_sweeps * nsb >= (long long)(0xFFFFFFFFu / OWN_TAG_SPAN) - 2) return TSU_OK;  // generation tags are 32 bits
-    if (lds_bytes > 150 * 1024) return TSU_OK;
-    own_kern kern = d->dtype == TSU_DTYPE_F64 ? own_pick<double>(M, R, ord) : own_pick<float>(M, R, ord);
-    if (!kern) return TSU_OK;
-    if (tsu_func_allow_lds(ctx, (const void*)kern, (int)lds_bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        return TSU_OK;
-    }
-    int per_cu = 0;
-    if (tsu_func_blocks_per_cu(ctx, (const void*)kern, OWN_THREADS, lds_bytes, &per_cu) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        return TSU_OK;
-    }
-    const size_t gen_words = (size_t)OWN_NGEN * R * G * 2, fin_words = (size_t)OWN_RING * R * G * 2;
+    const int n = d->n, n_sweeps = c.n_sweeps;
+    *out = DenseOutcome::Declined;
+    const bool ord = c.order_dev != nullptr;
+    const OwnPlan pl = own_plan(n, ctx->cus, ord, g ? g->R : 1, n_sweeps, own_env());
+    if (!pl.takes || !d->kept.own_usable()) return TSU_OK;
+    const int R = pl.R, M = pl.M, RW = 64 * M;
+    own_kern kern = d->dtype == TSU_DTYPE_F64 ? own_pick<double>(pl.sel) : own_pick<float>(pl.sel);
+    const size_t gen_words = (size_t)OWN_NGEN * R * pl.G * 2, fin_words = (size_t)OWN_RING * R * pl.G * 2;
     TSU_HIP_TRY(ctx, dense_grow(d->own_gran, d->own_cap, (gen_words + fin_words) * 8));
-    if (!d->co_bar) TSU_HIP_TRY(ctx, hipMalloc(&d->co_bar, BAR_WORDS * sizeof(unsigned)));
     if (!d->co_fields) TSU_HIP_TRY(ctx, hipMalloc(&d->co_fields, (size_t)n * 8));
     TSU_HIP_TRY(ctx, hipMemsetAsync(d->own_gran, 0, (gen_words + fin_words) * 8, ctx->stream));
-    TSU_HIP_TRY(ctx, hipMemsetAsync(d->co_bar + BAR_ERR, 0, 4 * sizeof(unsigned), ctx->stream));
     OwnParams P;
     memset(&P, 0, sizeof(P));
-    P.JT = d->JT;
-    P.bias = d->bias;
-    P.state = states_dev;
-    P.uniforms = uniforms_dev;
-    P.gen = d->own_gran;
-    P.fin = d->own_gran + gen_words;
-    P.bar = d->co_bar;
-    P.order = order_dev;
-    P.temps = temps_dev;
-    P.samples = samples_dev;
-    P.fields_all = R_real > 1 ? d->rep_fields[d->rep_cur] : d->co_fields;
-    P.fields_out = R_real > 1 ? d->rep_fields[d->rep_cur ^ 1] : d->co_fields;
-    P.n = n;
-    P.n_sweeps = n_sweeps;
-    P.sbw = sbw;
-    P.lmax = lmax;
-    P.rec_from = rec_from;
-    P.rec_every = rec_every > 0 ? rec_every : 1;
+    P.JT = d->JT, P.bias = d->bias, P.state = g ? g->states_dev : d->state, P.uniforms = c.uniforms_dev;
+    P.gen = d->own_gran, P.fin = d->own_gran + gen_words;
+    P.fields_all = g ? d->kept.rep_in() : d->co_fields, P.fields_out = g ? d->kept.rep_out() : d->co_fields;
+    P.n = n, P.n_sweeps = n_sweeps, P.sbw = pl.sbw, P.lmax = pl.lmax, P.order = c.order_dev, P.temps = c.temps_dev;
+    P.samples = c.samples_dev, P.rec_from = c.rec_from, P.rec_every = c.rec_every > 0 ? c.rec_every : 1;
+    P.resume = keep.resume, P.refresh_off = keep.refresh_off, P.persist = keep.persist;
     P.fail_at = dense_env("TSU_K2_OWN_TEST_FAIL", -1);
     // lists a deciding wave gathers by itself: up to 32 entries in natural order, 48 in a caller's order and for replicas (n = 16384:
     // natural order is flat from 16 to 32, the other two from 48 to 64); a replica's own short list has 64 slots
@@ -1448,73 +1375,30 @@ int tsu_dense_own_run(tsu_dense* d, int R_real, const OwnRep* reps, int8_t* stat
     if (P.solo_max < 0) P.solo_max = 0;
     // solo generations (one chain): the deciding wave polls one group per lane in natural order, four in a caller's order.  (Replicas
     // always run their generations wave by wave: rep_step.)  Both switches are read per call: A/B measurements.
-    P.solo = dense_env("TSU_K2_OWN_SOLO", 1) && (ord ? NP <= 256 : NP <= 64) && (R == 1 || M == 1);
-    for (int r = 0; r < R; ++r) P.rep[r] = reps[r < R_real ? r : 0];  // (padding replicas repeat replica 0 on its own state copy: see the caller)
-    const bool single = R_real == 1 && allow_persist;
-    P.resume = single && fields_were_valid && (d->since_refresh % CO_REFRESH) != 0 ? 1 : 0;
-    P.refresh_off = P.resume ? d->since_refresh : 0;
-    P.persist = single && d->pipe_streak >= 1 ? 1 : 0;
-    if (R_real > 1) {  // (replicas: the caller matched the incoming states with the ones whose fields are kept: rep[].src)
-        const bool rk = allow_persist && d->rep_fields[0] && d->rep_fields[1];
-        P.resume = rk && fields_were_valid && (d->rep_since % CO_REFRESH) != 0 ? 1 : 0;
-        P.refresh_off = P.resume ? d->rep_since : 0;
-        P.persist = rk ? 1 : 0;
+    P.solo = dense_env("TSU_K2_OWN_SOLO", 1) && (ord ? pl.NP <= 256 : pl.NP <= 64) && (R == 1 || M == 1);
+    if (g) {
+        for (int r = 0; r < R; ++r) P.rep[r] = g->reps[r < g->R ? r : 0];  // (padding replicas repeat replica 0 on its own state copy: see the caller)
+    } else {
+        const DenseStream st = dense_stream(c.seed, c.replica);
+        P.rep[0] = {c.T, c.sweep0, st.tag, st.k0, st.k1, 0};
     }
-    static const int verbose = dense_env("TSU_K2_VERBOSE", 0);
-    unsigned long long* d_tl = nullptr;
-    if (verbose >= 2) {
-        TSU_HIP_TRY(ctx, hipMalloc(&d_tl, 12 * sizeof(unsigned long long)));
-        TSU_HIP_TRY(ctx, hipMemsetAsync(d_tl, 0, 12 * sizeof(unsigned long long), ctx->stream));
-    }
-    P.timeline = d_tl;
-    {
-        const int rcx = tsu_grid_exclusive_begin(ctx);
-        if (rcx != TSU_OK) return rcx;
-    }
-    hipError_t e = tsu_launch_grid_sync(ctx, (const void*)kern, dim3((unsigned)W), dim3(OWN_THREADS), &P, lds_bytes, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        if (d_tl) (void)hipFree(d_tl);
-        return TSU_OK;
-    }
-    {
-        const int rcx = tsu_grid_exclusive_end(ctx);
-        if (rcx != TSU_OK) return rcx;
-    }
-    // (the error words come back into pinned memory: a copy into pageable memory is staged and costs ~10 us more per call)
-    if (!d->h_flags && hipHostMalloc((void**)&d->h_flags, 4 * sizeof(unsigned), hipHostMallocDefault) != hipSuccess) {
-        d->h_flags = nullptr;
-        (void)hipGetLastError();
-    }
-    unsigned hbuf[4];
-    unsigned* h = d->h_flags ? d->h_flags : hbuf;
-    TSU_HIP_TRY(ctx, hipMemcpyAsync(h + 1, d->co_bar + BAR_ERR, 3 * sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (d_tl) {
-        unsigned long long tl[12];
-        (void)hipMemcpy(tl, d_tl, sizeof(tl), hipMemcpyDeviceToHost);
-        (void)hipFree(d_tl);
-        const double per = (double)n_sweeps * (ord ? nsb : 1);  // the timed workgroup is active once per sweep in natural order
+    DenseFlags fl;
+    const int rc = dense_launch(d, {(const void*)kern, (unsigned)pl.W, OWN_THREADS, pl.lds_bytes, 0, &P, &P.bar, &P.timeline, 12, false}, &fl);
+    if (rc != TSU_OK || fl.status != DenseFlags::Ran) return rc;
+    if (fl.timed) {
+        const unsigned long long* tl = fl.tl;
+        const double per = (double)n_sweeps * (ord ? pl.nsb : 1);  // the timed workgroup is active once per sweep in natural order
         fprintf(stderr, "[tsu] k2_own n=%d R=%d M=%d %s, superblocks of %d, %d sweeps; last workgroup, per active superblock: prologue %.1f us, first poll %.1f us, first axpy %.1f us, "
                         "later polls %.1f us, later axpy+decide %.1f us, commit+strip %.1f us, %.1f generations, %.0f toggles (later generations, poller wave: polling %.1f us, list building %.1f us); per sweep as a bystander: wait %.1f us, strips %.1f us\n",
-                n, R, M, ord ? "caller's order" : "natural order", sbw * RW, n_sweeps, tl[0] / 100.0 / per, tl[9] / 100.0 / per, tl[8] / 100.0 / per, tl[1] / 100.0 / per, tl[2] / 100.0 / per,
+                n, R, M, ord ? "caller's order" : "natural order", pl.sbw * RW, n_sweeps, tl[0] / 100.0 / per, tl[9] / 100.0 / per, tl[8] / 100.0 / per, tl[1] / 100.0 / per, tl[2] / 100.0 / per,
                 tl[3] / 100.0 / per, tl[4] / per, tl[5] / per, tl[10] / 100.0 / per, tl[11] / 100.0 / per, tl[6] / 100.0 / n_sweeps, tl[7] / 100.0 / n_sweeps);
     }
-    if (h[1] || h[3]) {
-        fprintf(stderr, "[tsu] dense sweep (owner kernel): %s; continuing on the other paths\n", h[1] ? "a wait timed out (GPU shared?)" : "no fixed point");
-        d->own_failed = 1;
+    if (fl.err || fl.not_converged) {
+        fprintf(stderr, "[tsu] dense sweep (owner kernel): %s; continuing on the other paths\n", fl.err ? "a wait timed out (GPU shared?)" : "no fixed point");
+        *out = DenseOutcome::GaveUp;
         return TSU_OK;
     }
-    *done = 1;
+    *out = DenseOutcome::Done;
     d->n_own += 1;
-    if (R_real > 1 && P.persist) {
-        d->rep_since = (P.refresh_off + n_sweeps) % CO_REFRESH;
-        d->rep_cur ^= 1;
-    }
-    if (R_real == 1 && allow_persist) {
-        d->since_refresh = (P.refresh_off + n_sweeps) % CO_REFRESH;
-        d->fields_valid = P.persist;
-        d->pipe_streak += 1;
-    }
     return TSU_OK;
 }
