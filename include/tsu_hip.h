@@ -388,6 +388,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * declared in tsu_hip_multispin_pt.h, which this header includes; its prototypes are _hip.MULTISPIN_PT_SIGNATURES in Python. */
 #include "tsu_hip_multispin_pt.h"
 
+/* K9: axis profiles and k_min modes of the overlap field of a multispin-coded glass, on the handle and in the tempering record
+ * (tsu_msc_profiles / _set_correlation / _modes / _pt_history_modes): declared in tsu_hip_multispin_corr.h, which this header
+ * includes; its prototypes are _hip.MULTISPIN_CORR_SIGNATURES in Python. */
+#include "tsu_hip_multispin_corr.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -312,6 +312,7 @@ int tsu_msc_destroy(tsu_msc* h) {
     if (!h) return TSU_OK;
     (void)hipStreamSynchronize(h->ctx->stream);
     msc_pt_free(h);
+    msc_corr_free(h);
     if (h->d_s) (void)hipFree(h->d_s);
     if (h->d_j) (void)hipFree(h->d_j);
     if (h->d_tab) (void)hipFree(h->d_tab);

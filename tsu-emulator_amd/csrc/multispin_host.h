@@ -1,10 +1,11 @@
 // multispin_host.h -- what K9's translation units share on the host: the tsu_msc handle (multispin.hip owns it), the kernels'
-// parameter block built from it, and the two entry points that cross between multispin.hip and multispin_pt.hip.  Neither of those
-// is part of the C ABI: both are hidden symbols of libtsu_hip.so.
+// parameter block built from it, and the entry points that cross between multispin.hip, multispin_pt.hip and multispin_corr.hip.
+// None of those is part of the C ABI: all are hidden symbols of libtsu_hip.so.
 #pragma once
 #include "multispin_dev.h"
 
-struct msc_pt;  // the tempering state of a handle (multispin_pt.hip); NULL until tsu_msc_pt_enable
+struct msc_pt;    // the tempering state of a handle (multispin_pt.hip); NULL until tsu_msc_pt_enable
+struct msc_corr;  // the profiles' scratch and the correlation state (multispin_corr.hip); NULL until first used
 
 struct tsu_msc {
     tsu_ctx* ctx;
@@ -19,6 +20,7 @@ struct tsu_msc {
     int have_T, have_seeds;
     unsigned long long launches;
     msc_pt* pt;
+    msc_corr* corr;
 };
 
 namespace {
@@ -55,3 +57,13 @@ inline size_t msc_row_len(const tsu_msc* h) {
 __attribute__((visibility("hidden"))) hipError_t msc_enqueue_measure(tsu_msc* h, unsigned long long* row);
 // multispin_pt.hip: frees h->pt (tsu_msc_destroy calls it after the stream has drained)
 __attribute__((visibility("hidden"))) void msc_pt_free(tsu_msc* h);
+// multispin_corr.hip: frees h->corr (tsu_msc_destroy calls it after the stream has drained)
+__attribute__((visibility("hidden"))) void msc_corr_free(tsu_msc* h);
+// multispin_corr.hip, for tsu_msc_pt_run.  msc_corr_on: tsu_msc_set_correlation switched the modes on.  Then a run calls
+// msc_corr_record_begin once (a record of n_rows rows of modes replaces the last run's; 0: that run records none; returns a TSU_
+// code) and, per recording round, msc_corr_enqueue_row between the round's measurement and its swap pass: kMscCorrLaunches
+// launches on the handle's stream that write the modes of the planes as they are into row r.  Asynchronous.
+constexpr int kMscCorrLaunches = 2;  // k9_profile, k9_modes
+__attribute__((visibility("hidden"))) int msc_corr_on(const tsu_msc* h);
+__attribute__((visibility("hidden"))) int msc_corr_record_begin(tsu_msc* h, int n_rows);
+__attribute__((visibility("hidden"))) hipError_t msc_corr_enqueue_row(tsu_msc* h, int r);

@@ -4,8 +4,9 @@
 // exchanges configurations, per bit: for two planes x, y of neighbouring slots and a 64-bit accept mask m,
 // d = (x ^ y) & m; x ^= d; y ^= d (include/tsu_hip_multispin_pt.h, DESIGN.md section 3 "Tempering of multispin-coded glasses").
 //
-// A round is: the sweeps (tsu_msc_sweep), one k9_measure into a device row (the record's row, when one is kept), k9_pt_plan,
-// k9_pt_apply.  Nothing comes back to the host inside tsu_msc_pt_run.
+// A round is: the sweeps (tsu_msc_sweep), one k9_measure into a device row (the record's row, when one is kept), with
+// tsu_msc_set_correlation on and a record the k_min modes of the same planes (multispin_corr.hip), k9_pt_plan, k9_pt_apply.
+// Nothing comes back to the host inside tsu_msc_pt_run.
 //
 // k9_pt_plan: one workgroup of four waves per (replica a, word-plane w); lane b of every wave is sample 64 w + b.  The waves copy
 // the columns of the row's unsatisfied-bond counts and of the label / flag tables into LDS ([slot][64]).  Wave 0 walks the pairs
@@ -293,6 +294,11 @@ int tsu_msc_pt_run(tsu_msc* h, int n_rounds, int swap_interval, int do_swap, int
         }
         if (record) TSU_HIP_TRY(ctx, hipMemsetAsync(pt->d_hist, 0, bytes, ctx->stream));
     }
+    const bool modes = msc_corr_on(h);  // off: every launch below is what it was without the correlation code
+    if (modes) {
+        const int rc = msc_corr_record_begin(h, record ? n_rounds : 0);
+        if (rc != TSU_OK) return rc;
+    }
     const int AW = h->A * h->W;
     MscPtPlan plan = {};
     plan.dbeta = pt->d_dbeta;
@@ -321,6 +327,10 @@ int tsu_msc_pt_run(tsu_msc* h, int n_rounds, int swap_interval, int do_swap, int
         TSU_HIP_TRY(ctx, msc_enqueue_measure(h, row));
         pt->launches += 1;
         if (record) pt->hist_rows = r + 1;
+        if (record && modes) {  // before the pass: the modes of the configurations the row's q belongs to
+            TSU_HIP_TRY(ctx, msc_corr_enqueue_row(h, r));
+            pt->launches += kMscCorrLaunches;
+        }
         if (!do_swap) continue;
         plan.row = row;
         plan.round = round0 + (uint32_t)r;

@@ -299,6 +299,14 @@ MULTISPIN_PT_SIGNATURES = {
 }
 MSC_PT_MAX_TEMPS = 256
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_multispin_corr.h (the header tsu_hip.h includes) one to one
+MULTISPIN_CORR_SIGNATURES = {
+    "tsu_msc_profiles": (C.c_int, [_vp, _i64p, _i64p, _i64p]),
+    "tsu_msc_set_correlation": (C.c_int, [_vp, C.c_int, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]),
+    "tsu_msc_modes": (C.c_int, [_vp, _f64p]),
+    "tsu_msc_pt_history_modes": (C.c_int, [_vp, C.c_int, _f64p]),
+}
+
 _lib = None
 
 
@@ -319,7 +327,8 @@ def load_library():
                               + list(POPULATION_SIGNATURES.items()) + list(OVERLAP_SIGNATURES.items())
                               + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())
                               + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())
-                              + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())):
+                              + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())
+                              + list(MULTISPIN_CORR_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -913,6 +922,60 @@ class MultispinLattice:
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_msc_pt_launch_count(self.h, C.byref(n)))
         return n.value
+
+    # ---- correlation (tsu_msc_profiles / _set_correlation / _modes / _pt_history_modes): axis profiles and k_min modes
+    def profiles(self):
+        """(P_z, P_r, P_c): int64 (n_temps, S, L_d) profiles of a * b (two replicas) or of the spins (one); pad columns dropped."""
+        cols, S = self.words * 64, self.n_samples
+        out = [np.zeros((self.n_temps, cols, n), np.int64) for n in self.shape]
+        self.ctx.check(self.lib.tsu_msc_profiles(self.h, *(_ptr(x, _i64p) for x in out)))
+        return tuple(x[:, :S].copy() for x in out)
+
+    def set_correlation(self, tables):
+        """``tables``: per axis (cos, sin) float64 arrays of the axis's length, or None for an open axis; ``None`` switches the
+        modes off."""
+        if tables is None:
+            self.ctx.check(self.lib.tsu_msc_set_correlation(self.h, 0, None, None, None, None, None, None))
+            self._mode_axes = None
+            return
+        if len(tables) != 3:
+            raise ValueError("set_correlation: one (cos, sin) pair or None per axis (depth, rows, cols)")
+        keep, args = [], []
+        for n, t in zip(self.shape, tables):
+            if t is None:
+                args += [None, None]
+                continue
+            pair = [np.ascontiguousarray(x, dtype=np.float64).ravel() for x in t]
+            if len(pair) != 2 or any(x.size != n for x in pair):
+                raise ValueError(f"set_correlation: the tables of an axis of length {n} must be two arrays of that length")
+            keep += pair
+            args += [_ptr(x, _f64p) for x in pair]
+        self.ctx.check(self.lib.tsu_msc_set_correlation(self.h, 1, *args))
+        self._mode_axes = [a for a in range(3) if tables[a] is not None]
+
+    def _modes_out(self, raw):
+        """[..., 64 W, periodic axes, 2] doubles -> complex128 [..., S, 3], NaN on the open axes."""
+        out = np.full(raw.shape[:-3] + (self.n_samples, 3), complex(np.nan, np.nan), dtype=np.complex128)
+        for k, a in enumerate(self._mode_axes):  # the parts are stored as they are: no arithmetic that could turn -0.0 into 0.0
+            out.real[..., a] = raw[..., :self.n_samples, k, 0]
+            out.imag[..., a] = raw[..., :self.n_samples, k, 1]
+        return out
+
+    def modes(self):
+        """complex128 (n_temps, S, 3): the k_min modes of the planes as they are, NaN on the open axes."""
+        if not getattr(self, "_mode_axes", None):
+            raise ValueError("msc_modes: call set_correlation first")
+        raw = np.zeros((self.n_temps, self.words * 64, len(self._mode_axes), 2), np.float64)
+        self.ctx.check(self.lib.tsu_msc_modes(self.h, _ptr(raw, _f64p)))
+        return self._modes_out(raw)
+
+    def pt_history_modes(self, n_rows):
+        """complex128 (n_rows, n_temps, S, 3): the modes the last ``pt_run`` recorded."""
+        if not getattr(self, "_mode_axes", None):
+            raise ValueError("msc_pt_history_modes: call set_correlation first")
+        raw = np.zeros((int(n_rows), self.n_temps, self.words * 64, len(self._mode_axes), 2), np.float64)
+        self.ctx.check(self.lib.tsu_msc_pt_history_modes(self.h, int(n_rows), _ptr(raw, _f64p)))
+        return self._modes_out(raw)
 
 
 class _TemperingHandle:

@@ -1813,13 +1813,20 @@ class MultispinGlass3D:
     ``route``: ``"small"`` (planes of at most 8192 sites: the spins stay in LDS for all sweeps of a call, one launch per call) or
     ``"hbm"`` (one launch per half-sweep for all planes); by default the small route where it fits.  No swaps between temperatures here:
     :class:`MultispinTempering3D` adds them.
+
+    ``correlation=True`` (needs a periodic axis) switches on the k_min Fourier modes of the site field f = a b of the two replicas
+    of a slot (f = s with one replica): :meth:`fourier_modes`, from the exact integer :meth:`axis_profiles` in the fixed float64
+    order of :meth:`IsingModel3D.fourier_modes`, bit for bit what that gives for the sample's two lattices.
     """
 
     def __init__(self, size, temperatures, *, couplings, periodic=True, replicas: int = 1, seed: Optional[int] = None, seeds=None,
-                 initial: str = "random", route: Optional[str] = None, field=None):
+                 initial: str = "random", route: Optional[str] = None, field=None, correlation: bool = False):
         self.depth, self.rows, self.cols = self.shape = _shape_3d(size)
         self.n_spins = self.depth * self.rows * self.cols
         self.periodic = _hip.periodic_axes(periodic)
+        self.correlation = bool(correlation)
+        if self.correlation:
+            _check_correlation(self.periodic)
         self.temperatures = np.asarray(temperatures, dtype=np.float64).ravel()
         if self.temperatures.size < 1 or not np.all(self.temperatures > 0):
             raise ValueError("Temperature must be positive")
@@ -1846,6 +1853,8 @@ class MultispinGlass3D:
         self._msc.set_couplings(*(_hip.msc_pack(a) for a in packed))
         self._msc.set_temperatures(self.temperatures)
         self._msc.set_seeds(self.seeds.ravel())
+        if self.correlation:
+            self._msc.set_correlation([_kmin_tables(n) if p else None for n, p in zip(self.shape, self.periodic)])
         if initial == "random":
             self._msc.randomize()
         else:
@@ -1895,6 +1904,18 @@ class MultispinGlass3D:
             raise ValueError("link_overlaps need replicas=2")
         return self._msc.measure()[3] / self.n_bonds
 
+    def axis_profiles(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(P_z, P_r, P_c): int64 (n_temps, S, L_d), the exact sums of a_i b_i of the slot's two replicas (of s_i with one replica)
+        over the sites with each coordinate on the axis; each sums to the sample's q N (sum s).  Works without ``correlation``."""
+        return self._msc.profiles()
+
+    def fourier_modes(self) -> np.ndarray:
+        """complex128 (n_temps, S, 3): F_d = sum_x P_d[x] exp(2 pi i x / L_d) of :meth:`axis_profiles` per axis, NaN on an open
+        axis.  Needs ``correlation=True``."""
+        if not self.correlation:
+            raise ValueError("fourier_modes needs correlation=True")
+        return self._msc.modes()
+
     def spin_array(self) -> np.ndarray:
         """Every spin: int8 (n_temps, replicas, S, D, R, C)."""
         planes = self._msc.get_planes()
@@ -1930,12 +1951,16 @@ class MultispinGlass3D:
 
 def multispin_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 1000, n_measure: int = 50, measure_every: int = 1,
                       replicas: int = 2, periodic=True, seed: Optional[int] = None, seeds=None, initial: str = "random",
-                      route: Optional[str] = None) -> dict:
+                      route: Optional[str] = None, correlation: bool = False) -> dict:
     """Equilibrate S bimodal samples at every temperature (:class:`MultispinGlass3D`, no swaps), then take ``n_measure`` measurements
     ``measure_every`` sweeps apart.  Per sample, arrays (S, n_temps) under the keys of :func:`tempering_ensemble_scan_3d`:
     ``energy`` (<E> / N of replica 0), ``magnetization`` (<|m|>) and, with two replicas, ``overlap`` (<|q|>), ``overlap_sq``,
     ``overlap_4`` and ``link_overlap`` (<q_l>); ``"average"``: :func:`ensemble_summary` of them.  The samples of one 64-bit word
-    share their random numbers: errors over samples within a word are correlated."""
+    share their random numbers: errors over samples within a word are correlated.
+
+    ``correlation=True`` adds, per sample, ``F2`` (S, n_temps, 3) = <|F_d|^2> of the k_min modes of the overlap field (of the spins
+    with one replica; NaN on open axes), ``f2`` (S, n_temps) = <(q N)^2> (<(sum s)^2>), and ``chi_k``, ``xi`` and ``xi_over_L`` from
+    them, and to ``"average"`` [chi(k_min)], xi and xi_L / L with their jackknife errors; one synchronisation per measurement."""
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
     if int(measure_every) < 1 or int(n_measure) < 1 or int(n_equilibrate) < 0:
@@ -1944,11 +1969,11 @@ def multispin_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 100
     if seeds is None and seed is None:
         seed = 0
     g = MultispinGlass3D(size, temperatures, couplings=couplings, periodic=periodic, replicas=replicas, seed=seed, seeds=seeds,
-                         initial=initial, route=route)
+                         initial=initial, route=route, correlation=correlation)
     try:
         g.sweep(int(n_equilibrate))
         N, nb = g.n_spins, g.n_bonds
-        acc = {k: [] for k in ("e", "m", "q", "ql")}
+        acc = {k: [] for k in ("e", "m", "q", "ql", "F")}
         for _ in range(int(n_measure)):
             g.sweep(int(measure_every))
             unsat, ssum, q, ql = g._msc.measure()
@@ -1957,6 +1982,8 @@ def multispin_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 100
             if replicas == 2:
                 acc["q"].append(q / N)
                 acc["ql"].append(ql / nb)
+            if correlation:
+                acc["F"].append(g.fourier_modes())
         series = {k: np.stack(v) for k, v in acc.items() if v}  # (n_measure, n_temps, S)
         res = {"energy": series["e"].mean(axis=0).T, "magnetization": np.abs(series["m"]).mean(axis=0).T}
         if replicas == 2:
@@ -1964,11 +1991,25 @@ def multispin_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 100
             res["overlap_sq"] = (series["q"] ** 2).mean(axis=0).T
             res["overlap_4"] = (series["q"] ** 4).mean(axis=0).T
             res["link_overlap"] = series["ql"].mean(axis=0).T
+        if correlation:
+            _multispin_correlation(res, g, series["F"], series["q"] if replicas == 2 else series["m"])
         res["temperatures"] = temperatures
-        res["average"] = ensemble_summary(res)
+        res["average"] = ensemble_summary(res, N, g.shape, g.periodic) if correlation else ensemble_summary(res)
     finally:
         g.close()
     return res
+
+
+def _multispin_correlation(res: dict, g, modes, f) -> None:
+    """The per-sample correlation results of the multispin scans from the measurements' modes (n_measure, n_temps, S, 3) and total
+    field per site f = q / N (or m) (n_measure, n_temps, S): ``F2``, ``f2``, and ``_correlation_summary``'s ``chi_k``, ``xi`` and
+    ``xi_over_L`` of each sample."""
+    N = g.n_spins
+    res["F2"] = np.moveaxis(np.mean(np.abs(modes) ** 2, axis=0), 1, 0)  # (S, n_temps, 3)
+    res["f2"] = np.mean(f ** 2, axis=0).T * float(N) ** 2
+    per = [_correlation_summary({}, N, g.shape, g.periodic, f2, F2) for f2, F2 in zip(res["f2"], res["F2"])]
+    for key in ("chi_k", "xi", "xi_over_L"):
+        res[key] = np.stack([o[key] for o in per])
 
 
 class MultispinTempering3D(MultispinGlass3D):
@@ -1990,10 +2031,14 @@ class MultispinTempering3D(MultispinGlass3D):
 
     ``swap_seeds``: one per sample, or ``swap_seed`` for ``swap_seeds[s] = swap_seed + s``; by default
     ``swap_seed = seed + 2 * n_temps`` (``seed``: the first plane's), the first value past the default sweep seeds.
-    2 to 256 temperatures."""
+    2 to 256 temperatures.
+
+    ``correlation=True``: every recorded round also records, on the device, the k_min modes of the planes the round's measurement
+    saw (``history()["modes"]``); a recording round then takes two more launches."""
 
     def __init__(self, size, temperatures, *, couplings, periodic=True, replicas: int = 1, seed: Optional[int] = None, seeds=None,
-                 initial: str = "random", route: Optional[str] = None, field=None, swap_seed: Optional[int] = None, swap_seeds=None):
+                 initial: str = "random", route: Optional[str] = None, field=None, swap_seed: Optional[int] = None, swap_seeds=None,
+                 correlation: bool = False):
         nT = np.asarray(temperatures, dtype=np.float64).size
         if not 2 <= nT <= _hip.MSC_PT_MAX_TEMPS:
             raise ValueError(f"parallel tempering needs 2 to {_hip.MSC_PT_MAX_TEMPS} temperatures, got {nT}")
@@ -2003,7 +2048,7 @@ class MultispinTempering3D(MultispinGlass3D):
         self.round_count = 0
         self._recorded = 0
         super().__init__(size, temperatures, couplings=couplings, periodic=periodic, replicas=replicas, seed=seed, seeds=seeds,
-                         initial=initial, route=route, field=field)
+                         initial=initial, route=route, field=field, correlation=correlation)
         self._msc.pt_enable(self.temperatures)
         self._msc.pt_set_swap_seeds(self.swap_seeds)
 
@@ -2041,13 +2086,18 @@ class MultispinTempering3D(MultispinGlass3D):
         """The rounds recorded by the last ``run``, each taken after the round's sweeps and before its swap pass, per slot and
         sample as exact integers scaled like :meth:`energies`, :meth:`magnetizations`, :meth:`overlaps` and :meth:`link_overlaps`:
         ``E`` and ``M`` (n_rounds, n_temps, S), or (n_rounds, n_temps, 2, S) with two replicas, and then also ``q`` and ``q_link``
-        (n_rounds, n_temps, S), of the two replicas that sat at the slot in that round."""
+        (n_rounds, n_temps, S), of the two replicas that sat at the slot in that round.  With ``correlation=True`` also ``modes``:
+        complex128 (n_rounds, n_temps, S, 3), the k_min modes of the overlap field of those two replicas (of the spins with one
+        replica) per axis, NaN on open axes."""
         unsat, ssum, q, ql = self._msc.pt_history(self._recorded)
         per = (lambda x: x) if self.replicas == 2 else (lambda x: x[:, :, 0])
         out = {"E": per((2 * unsat - self.n_bonds).astype(np.float64)), "M": per(ssum / self.n_spins)}
         if self.replicas == 2:
             out["q"] = q / self.n_spins
             out["q_link"] = ql / self.n_bonds
+        if self.correlation:
+            out["modes"] = (self._msc.pt_history_modes(self._recorded) if self._recorded else
+                            np.zeros((0, self.temperatures.size, self.n_samples, 3), np.complex128))
         return out
 
     def stats(self) -> dict:
@@ -2079,12 +2129,13 @@ class MultispinTempering3D(MultispinGlass3D):
 def multispin_tempering_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 1000, n_measure: int = 50,
                                 measure_every: int = 10, replicas: int = 2, periodic=True, seed: Optional[int] = None, seeds=None,
                                 initial: str = "random", route: Optional[str] = None, swap_interval: Optional[int] = None,
-                                swap_seed: Optional[int] = None) -> dict:
+                                swap_seed: Optional[int] = None, correlation: bool = False) -> dict:
     """:func:`multispin_scan_3d` with parallel tempering (:class:`MultispinTempering3D`): rounds of ``swap_interval`` sweeps
     (default: ``measure_every``), each followed by a swap pass; ``n_equilibrate`` sweeps of equilibration, then ``n_measure``
     measurements ``measure_every`` sweeps apart taken from the device's record, one host transfer at the end.  ``n_equilibrate`` and
     ``measure_every`` must be multiples of ``swap_interval``.  Returns :func:`multispin_scan_3d`'s keys plus ``acceptance``
-    (S, n_temps - 1) and ``round_trips`` (S,), and ``"average"``: :func:`ensemble_summary` of them."""
+    (S, n_temps - 1) and ``round_trips`` (S,), and ``"average"``: :func:`ensemble_summary` of them.  ``correlation=True`` adds what
+    it adds to :func:`multispin_scan_3d`, the modes taken from the device's record in the same one transfer."""
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
     if int(measure_every) < 1 or int(n_measure) < 1 or int(n_equilibrate) < 0:
@@ -2096,7 +2147,7 @@ def multispin_tempering_scan_3d(size, temperatures, *, couplings, n_equilibrate:
     if seeds is None and seed is None:
         seed = 0
     g = MultispinTempering3D(size, temperatures, couplings=couplings, periodic=periodic, replicas=replicas, seed=seed, seeds=seeds,
-                             initial=initial, route=route, swap_seed=swap_seed)
+                             initial=initial, route=route, swap_seed=swap_seed, correlation=correlation)
     try:
         g.run(int(n_equilibrate) // k, k, record=False)
         stride = int(measure_every) // k
@@ -2110,10 +2161,12 @@ def multispin_tempering_scan_3d(size, temperatures, *, couplings, n_equilibrate:
             res["overlap_sq"] = (rows["q"] ** 2).mean(axis=0).T
             res["overlap_4"] = (rows["q"] ** 4).mean(axis=0).T
             res["link_overlap"] = rows["q_link"].mean(axis=0).T
+        if correlation:
+            _multispin_correlation(res, g, rows["modes"], rows["q"] if replicas == 2 else m)
         res["acceptance"] = g.acceptance()
         res["round_trips"] = g.round_trips()
         res["temperatures"] = temperatures
-        res["average"] = ensemble_summary(res)
+        res["average"] = ensemble_summary(res, N, g.shape, g.periodic) if correlation else ensemble_summary(res)
     finally:
         g.close()
     return res
