@@ -393,6 +393,12 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * includes; its prototypes are _hip.MULTISPIN_CORR_SIGNATURES in Python. */
 #include "tsu_hip_multispin_corr.h"
 
+/* K9: real-space correlations C4(r) of the overlap field along the periodic axes, plane snapshots with their two-time
+ * correlations, and quench runs that record both with the measurements on the device (tsu_msc_c4 / _snapshot_slots / _snapshot /
+ * _snapshot_overlap / _quench_run / _quench_history): declared in tsu_hip_multispin_quench.h, which this header includes; its
+ * prototypes are _hip.MULTISPIN_QUENCH_SIGNATURES in Python. */
+#include "tsu_hip_multispin_quench.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -225,6 +225,24 @@ bool msc_fits_small(const MscGeo& g) { return g.nsites <= kSmallSites && g.nblk 
 
 }  // namespace
 
+hipError_t msc_enqueue_sweeps(tsu_msc* h, int n_sweeps, uint32_t sweep0, unsigned long long* launches) {
+    if (n_sweeps <= 0) return hipSuccess;
+    const MscParams p = msc_params(h);
+    const unsigned planes = (unsigned)msc_planes(h);
+    if (h->route == TSU_MSC_ROUTE_SMALL) {
+        k9_small<<<planes, kSmallLanes, msc_small_lds(h->g), h->ctx->stream>>>(p, n_sweeps, sweep0);
+        *launches += 1;
+    } else {
+        const dim3 grid((unsigned)((h->g.nblk + 255) / 256), 1, planes);
+        for (int s = 0; s < n_sweeps; ++s)
+            for (int colour = 0; colour < 2; ++colour) {
+                k9_sweep<<<grid, 256, 0, h->ctx->stream>>>(p, 2u * (sweep0 + (uint32_t)s) + (uint32_t)colour, colour);
+                *launches += 1;
+            }
+    }
+    return hipGetLastError();
+}
+
 hipError_t msc_enqueue_measure(tsu_msc* h, unsigned long long* row) {
     const dim3 grid((unsigned)((h->g.nsites + 256 * kMeasureSites - 1) / (256 * kMeasureSites)), (unsigned)(h->nT * h->W), 1);
     if (h->A == 2) k9_measure<2><<<grid, 256, 0, h->ctx->stream>>>(msc_params(h), row);
@@ -313,6 +331,7 @@ int tsu_msc_destroy(tsu_msc* h) {
     (void)hipStreamSynchronize(h->ctx->stream);
     msc_pt_free(h);
     msc_corr_free(h);
+    msc_quench_free(h);
     if (h->d_s) (void)hipFree(h->d_s);
     if (h->d_j) (void)hipFree(h->d_j);
     if (h->d_tab) (void)hipFree(h->d_tab);
@@ -419,21 +438,7 @@ int tsu_msc_sweep(tsu_msc* h, int n_sweeps, uint32_t sweep0) {
     TSU_REQUIRE(ctx, h->have_T && h->have_seeds, "msc_sweep: call tsu_msc_set_temperatures and tsu_msc_set_seeds first");
     TSU_REQUIRE(ctx, n_sweeps >= 0, "msc_sweep: n_sweeps must be >= 0");
     TSU_REQUIRE(ctx, (uint64_t)sweep0 + (uint64_t)n_sweeps <= (1ull << 31), "msc_sweep: sweep counter overflow");
-    if (n_sweeps == 0) return TSU_OK;
-    const MscParams p = msc_params(h);
-    const unsigned planes = (unsigned)msc_planes(h);
-    if (h->route == TSU_MSC_ROUTE_SMALL) {
-        k9_small<<<planes, kSmallLanes, msc_small_lds(h->g), ctx->stream>>>(p, n_sweeps, sweep0);
-        h->launches += 1;
-    } else {
-        const dim3 grid((unsigned)((h->g.nblk + 255) / 256), 1, planes);
-        for (int s = 0; s < n_sweeps; ++s)
-            for (int colour = 0; colour < 2; ++colour) {
-                k9_sweep<<<grid, 256, 0, ctx->stream>>>(p, 2u * (sweep0 + (uint32_t)s) + (uint32_t)colour, colour);
-                h->launches += 1;
-            }
-    }
-    TSU_HIP_TRY(ctx, hipGetLastError());
+    TSU_HIP_TRY(ctx, msc_enqueue_sweeps(h, n_sweeps, sweep0, &h->launches));
     return TSU_OK;
 }
 

@@ -1,11 +1,13 @@
 // multispin_host.h -- what K9's translation units share on the host: the tsu_msc handle (multispin.hip owns it), the kernels'
-// parameter block built from it, and the entry points that cross between multispin.hip, multispin_pt.hip and multispin_corr.hip.
+// parameter block built from it, and the entry points that cross between multispin.hip, multispin_pt.hip, multispin_corr.hip
+// and multispin_quench.hip.
 // None of those is part of the C ABI: all are hidden symbols of libtsu_hip.so.
 #pragma once
 #include "multispin_dev.h"
 
 struct msc_pt;    // the tempering state of a handle (multispin_pt.hip); NULL until tsu_msc_pt_enable
 struct msc_corr;  // the profiles' scratch and the correlation state (multispin_corr.hip); NULL until first used
+struct msc_quench;  // C4 rows, snapshots and the record of a quench run (multispin_quench.hip); NULL until first used
 
 struct tsu_msc {
     tsu_ctx* ctx;
@@ -21,6 +23,7 @@ struct tsu_msc {
     unsigned long long launches;
     msc_pt* pt;
     msc_corr* corr;
+    msc_quench* qn;
 };
 
 namespace {
@@ -55,10 +58,15 @@ inline size_t msc_row_len(const tsu_msc* h) {
 // multispin.hip: one launch of k9_measure on the handle's stream adding into `row` (msc_row_len entries, zeroed by the caller).
 // Asynchronous; returns the launch's hipError_t.
 __attribute__((visibility("hidden"))) hipError_t msc_enqueue_measure(tsu_msc* h, unsigned long long* row);
+// multispin.hip: n_sweeps sweeps from counter sweep0 by the handle's route on its stream, exactly tsu_msc_sweep's launches; adds
+// their number to *launches.  Asynchronous; returns the launches' hipError_t.
+__attribute__((visibility("hidden"))) hipError_t msc_enqueue_sweeps(tsu_msc* h, int n_sweeps, uint32_t sweep0, unsigned long long* launches);
 // multispin_pt.hip: frees h->pt (tsu_msc_destroy calls it after the stream has drained)
 __attribute__((visibility("hidden"))) void msc_pt_free(tsu_msc* h);
 // multispin_corr.hip: frees h->corr (tsu_msc_destroy calls it after the stream has drained)
 __attribute__((visibility("hidden"))) void msc_corr_free(tsu_msc* h);
+// multispin_quench.hip: frees h->qn (tsu_msc_destroy calls it after the stream has drained)
+__attribute__((visibility("hidden"))) void msc_quench_free(tsu_msc* h);
 // multispin_corr.hip, for tsu_msc_pt_run.  msc_corr_on: tsu_msc_set_correlation switched the modes on.  Then a run calls
 // msc_corr_record_begin once (a record of n_rows rows of modes replaces the last run's; 0: that run records none; returns a TSU_
 // code) and, per recording round, msc_corr_enqueue_row between the round's measurement and its swap pass: kMscCorrLaunches

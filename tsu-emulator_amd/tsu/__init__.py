@@ -41,6 +41,7 @@ from .models import (  # noqa: F401
     demonstrate_phase_transition,
     edwards_anderson_samples,
     ensemble_summary,
+    multispin_quench_3d,
     multispin_scan_3d,
     multispin_tempering_scan_3d,
     temperature_scan_3d,
@@ -58,5 +59,5 @@ __all__ = [
     "PopulationAnnealing", "PopulationAnnealing3D",
     "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
     "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d",
-    "GraphTempering", "MultispinTempering3D", "multispin_tempering_scan_3d",
+    "GraphTempering", "multispin_quench_3d", "MultispinTempering3D", "multispin_tempering_scan_3d",
 ]

@@ -307,6 +307,18 @@ MULTISPIN_CORR_SIGNATURES = {
     "tsu_msc_pt_history_modes": (C.c_int, [_vp, C.c_int, _f64p]),
 }
 
+# name -> (restype, argtypes): mirrors include/tsu_hip_multispin_quench.h (the header tsu_hip.h includes) one to one
+MULTISPIN_QUENCH_SIGNATURES = {
+    "tsu_msc_c4": (C.c_int, [_vp, _i64p, _i64p, _i64p]),
+    "tsu_msc_snapshot_slots": (C.c_int, [_vp, C.c_int]),
+    "tsu_msc_snapshot": (C.c_int, [_vp, C.c_int]),
+    "tsu_msc_snapshot_overlap": (C.c_int, [_vp, C.c_int, _i64p]),
+    "tsu_msc_quench_run": (C.c_int, [_vp, C.c_int, _i32p, C.c_uint32, C.c_int, _i32p]),
+    "tsu_msc_quench_history": (C.c_int, [_vp, C.c_int, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p]),
+}
+MSC_SNAPSHOT_SLOTS = 8     # TSU_MSC_SNAPSHOT_SLOTS
+MSC_C4_MAX_AXIS = 16382    # TSU_MSC_C4_MAX_AXIS
+
 _lib = None
 
 
@@ -328,7 +340,7 @@ def load_library():
                               + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())
                               + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())
                               + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())
-                              + list(MULTISPIN_CORR_SIGNATURES.items())):
+                              + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -976,6 +988,58 @@ class MultispinLattice:
         raw = np.zeros((int(n_rows), self.n_temps, self.words * 64, len(self._mode_axes), 2), np.float64)
         self.ctx.check(self.lib.tsu_msc_pt_history_modes(self.h, int(n_rows), _ptr(raw, _f64p)))
         return self._modes_out(raw)
+
+    # ---- real space and quenches (tsu_msc_c4 / _snapshot* / _quench_*): C_d[r] of the overlap field, two-time correlations
+    def _c4_arrays(self, lead=()):
+        cols = self.words * 64
+        return [np.zeros(tuple(lead) + (self.n_temps, cols, n // 2 + 1), np.int64) if p else None for n, p in zip(self.shape, self.periodic)]
+
+    def _c4_out(self, arrays):
+        return tuple(None if x is None else x[..., :self.n_samples, :].copy() for x in arrays)
+
+    def c4(self):
+        """(C_z, C_r, C_c): int64 (n_temps, S, L_d / 2 + 1) sums of f_x f_{x + r e_d} per periodic axis, None for an open one; pad
+        columns dropped."""
+        out = self._c4_arrays()
+        self.ctx.check(self.lib.tsu_msc_c4(self.h, *(None if x is None else _ptr(x, _i64p) for x in out)))
+        return self._c4_out(out)
+
+    def snapshot_slots(self, n):
+        self.ctx.check(self.lib.tsu_msc_snapshot_slots(self.h, int(n)))
+
+    def snapshot(self, slot=0):
+        self.ctx.check(self.lib.tsu_msc_snapshot(self.h, int(slot)))
+
+    def snapshot_overlap(self, slot=0):
+        """int64 (n_temps, replicas, S): sum_x s_x(now) s_x(snapshot) per plane and sample; pad columns dropped."""
+        out = np.zeros((self.n_temps, self.replicas, self.words * 64), np.int64)
+        self.ctx.check(self.lib.tsu_msc_snapshot_overlap(self.h, int(slot), _ptr(out, _i64p)))
+        return out[..., :self.n_samples].copy()
+
+    def quench_run(self, times, sweep0=0, wait_index=()):
+        t = np.ascontiguousarray(times, dtype=np.int32).ravel()
+        wi = np.ascontiguousarray(wait_index, dtype=np.int32).ravel()
+        self.ctx.check(self.lib.tsu_msc_quench_run(self.h, t.size, _ptr(t, _i32p), _counter("sweep0", sweep0), wi.size,
+                                                   _ptr(wi, _i32p) if wi.size else None))
+        self._quench_shape = (int(t.size), int(wi.size))
+
+    def quench_history(self):
+        """The rows of the last ``quench_run``: (unsat, sum, q, q_link) as :meth:`pt_history` gives them, the 3-tuple of
+        :meth:`c4` with a leading time axis, and two_time int64 (n_wait, n_times, n_temps, replicas, S)."""
+        n, nw = self._quench_shape
+        cols, S = self.words * 64, self.n_samples
+        unsat = np.zeros((n, self.n_temps, self.replicas, cols), np.int64)
+        ssum = np.zeros_like(unsat)
+        two = self.replicas == 2
+        q = np.zeros((n, self.n_temps, cols), np.int64) if two else None
+        ql = np.zeros((n, self.n_temps, cols), np.int64) if two else None
+        c4 = self._c4_arrays((n,))
+        tt = np.zeros((nw, n, self.n_temps, self.replicas, cols), np.int64)
+        self.ctx.check(self.lib.tsu_msc_quench_history(
+            self.h, n, _ptr(unsat, _i64p), _ptr(ssum, _i64p), _ptr(q, _i64p) if two else None, _ptr(ql, _i64p) if two else None,
+            *(None if x is None else _ptr(x, _i64p) for x in c4), _ptr(tt, _i64p) if nw else None))
+        meas = (unsat[..., :S].copy(), ssum[..., :S].copy(), q[..., :S].copy() if two else None, ql[..., :S].copy() if two else None)
+        return meas, self._c4_out(c4), tt[..., :S].copy()
 
 
 class _TemperingHandle:

@@ -4,7 +4,7 @@ from .ising import (IsingChain, IsingConfig, IsingGrid, IsingModel, IsingModel2D
                     demonstrate_phase_transition, temperature_scan, temperature_scan_3d, tempering_scan, tempering_scan_3d,
                     LatticeTemperingEnsemble, LatticeTemperingEnsemble3D, edwards_anderson_samples, ensemble_summary,
                     tempering_ensemble_scan, tempering_ensemble_scan_3d, MultispinGlass3D, multispin_scan_3d,
-                    MultispinTempering3D, multispin_tempering_scan_3d)
+                    multispin_quench_3d, MultispinTempering3D, multispin_tempering_scan_3d)
 from .graph_tempering import GraphTempering
 
 __all__ = ["IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "IsingConfig", "demonstrate_phase_transition", "temperature_scan",
@@ -12,4 +12,4 @@ __all__ = ["IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "IsingConfig
            "PopulationAnnealing", "PopulationAnnealing3D", "population_annealing_scan", "population_annealing_scan_3d",
            "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
            "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d", "GraphTempering",
-           "MultispinTempering3D", "multispin_tempering_scan_3d"]
+           "multispin_quench_3d", "MultispinTempering3D", "multispin_tempering_scan_3d"]

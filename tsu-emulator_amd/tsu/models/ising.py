@@ -1847,6 +1847,7 @@ class MultispinGlass3D:
             self.seeds = np.array([[base + a * nT + t for a in range(self.replicas)] for t in range(nT)], dtype=object)
         self.n_bonds = lattice_bond_count(self.shape, self.periodic)
         self.sweep_count = 0
+        self._snap_slots, self._snap_taken = 0, set()
         self._before_device()
         self._msc = _hip.MultispinLattice(self.depth, self.rows, self.cols, self.periodic, nT, self.replicas, self.n_samples,
                                           _hip.MSC_ROUTE_AUTO if route is None else MULTISPIN_ROUTES[route])
@@ -1947,6 +1948,156 @@ class MultispinGlass3D:
         word = planes[int(slot), int(replica), int(sample) // 64]
         planes[int(slot), int(replica), int(sample) // 64] = np.where(v == 1, word | bit, word & ~bit)
         self._msc.set_planes(planes)
+
+    # ---- real space and quenches: C4(r) along the periodic axes, snapshots and two-time correlations (k9_c4, k9_twotime)
+    def overlap_correlation(self):
+        """(C_z, C_r, C_c): int64 (n_temps, S, L_d / 2 + 1) per periodic axis, ``None`` for an open one:
+        C_d[r] = sum_x f_x f_{x + r e_d} over all N sites with wrap-around, r = 0 .. L_d / 2, of the site field f = a b of the slot's
+        two replicas (f = s with one replica).  Exact integers; C_d[0] = N."""
+        _check_quench_lattice(self.shape, self.periodic)
+        return self._msc.c4()
+
+    def _need_slots(self, n: int) -> None:
+        if n > self._snap_slots:
+            self._msc.snapshot_slots(n)  # the snapshots of the slots that were there stay
+            self._snap_slots = n
+
+    def snapshot(self, slot: int = 0) -> None:
+        """Store the current planes in ``slot`` (0 .. 7) on the device, for :meth:`two_time`."""
+        if not 0 <= int(slot) < _hip.MSC_SNAPSHOT_SLOTS:
+            raise ValueError(f"slot {slot} outside 0 .. {_hip.MSC_SNAPSHOT_SLOTS - 1}")
+        self._need_slots(int(slot) + 1)
+        self._msc.snapshot(int(slot))
+        self._snap_taken.add(int(slot))
+
+    def two_time(self, slot: int = 0) -> np.ndarray:
+        """sum_x s_x(now) s_x(snapshot in ``slot``) per sample, exact int64 in the shape of :meth:`energies`."""
+        if int(slot) not in self._snap_taken:
+            raise ValueError(f"slot {slot} holds no snapshot")
+        return self._per_replica(self._msc.snapshot_overlap(int(slot)))
+
+    def quench(self, times, waiting_times=()) -> dict:
+        """Run ``times[-1]`` sweeps and record, at every ``times[k]`` (strictly ascending sweep counts since the start of the call,
+        0: before the first sweep), the measurements, C4 along the periodic axes and, against a snapshot taken at each of
+        ``waiting_times`` (a subset of ``times``, at most 8), the two-time correlations; everything is enqueued at once and fetched
+        in one transfer.  Returns ``times``, ``energy`` and ``magnetization`` (n_times,) + the shape of :meth:`energies`, with two
+        replicas ``overlap`` and ``link_overlap`` (n_times, n_temps, S), ``c4``: the 3-tuple of :meth:`overlap_correlation` with a
+        leading time axis, ``waiting_times`` and ``two_time``: float64 (n_wait, n_times) + the shape of :meth:`energies`,
+        sum_x s_x(t) s_x(t_w), NaN where t < t_w.  Advances ``sweep_count``; the planes end as after ``sweep(times[-1])``."""
+        t, wi = _quench_times(times, waiting_times)
+        _check_quench_lattice(self.shape, self.periodic)
+        if self.sweep_count + int(t[-1]) > 1 << 31:
+            raise ValueError("msc_quench_run: sweep counter overflow")
+        self._need_slots(len(wi))
+        self._msc.quench_run(t, self.sweep_count, wi)
+        self.sweep_count += int(t[-1])
+        self._snap_taken.update(range(len(wi)))
+        (unsat, ssum, q, ql), c4, tt = self._msc.quench_history()
+        per = (lambda x: x) if self.replicas == 2 else (lambda x: x[:, :, 0])
+        out = {"times": t.astype(np.int64), "energy": per((2 * unsat - self.n_bonds).astype(np.float64)),
+               "magnetization": per(ssum / self.n_spins)}
+        if self.replicas == 2:
+            out["overlap"] = q / self.n_spins
+            out["link_overlap"] = ql / self.n_bonds
+        out["c4"] = c4
+        out["waiting_times"] = t[wi].astype(np.int64)
+        two = tt.astype(np.float64)
+        for j, k in enumerate(wi):
+            two[j, :k] = np.nan
+        out["two_time"] = two if self.replicas == 2 else two[:, :, :, 0]
+        return out
+
+
+def _quench_times(times, waiting_times):
+    """Validate a quench's times (before any device call): (times as int32, the indices of the waiting times into them)."""
+    raw = np.asarray(times)
+    if raw.ndim != 1 or raw.size < 1 or not np.all(raw == np.floor(raw)):
+        raise ValueError("times must be a non-empty 1-D sequence of integer sweep counts")
+    t = raw.astype(np.int64)
+    if t[0] < 0 or np.any(np.diff(t) <= 0) or t[-1] > 1 << 31:
+        raise ValueError("times must be strictly ascending, starting at 0 or later")
+    w = [int(x) for x in np.asarray(waiting_times).ravel()]
+    if len(w) > _hip.MSC_SNAPSHOT_SLOTS:
+        raise ValueError(f"at most {_hip.MSC_SNAPSHOT_SLOTS} waiting_times, got {len(w)}")
+    if len(set(w)) != len(w) or w != sorted(w):
+        raise ValueError("waiting_times must be strictly ascending")
+    missing = [x for x in w if x not in set(t.tolist())]
+    if missing:
+        raise ValueError(f"waiting_times must be a subset of times ({missing[0]} is not among them)")
+    where = {int(x): k for k, x in enumerate(t)}
+    return t.astype(np.int32), [where[x] for x in w]
+
+
+def _check_quench_lattice(shape, periodic) -> None:
+    if not any(periodic):
+        raise ValueError("overlap correlations need at least one periodic axis")
+    for n, p in zip(shape, periodic):
+        if p and n > _hip.MSC_C4_MAX_AXIS:
+            raise ValueError(f"overlap correlations take periodic axes of at most {_hip.MSC_C4_MAX_AXIS} sites, got {n}")
+
+
+def _xi12(c4, cut: float = 3.0):
+    """The coherence-length estimator of :func:`multispin_quench_3d` from per-sample correlators ``c4`` (..., S, r_max + 1):
+    (c4_mean, c4_error, xi12, xi12_error, r_cut).  c4_mean and c4_error are the mean and its standard error over the sample axis;
+    r_cut (...,) is the last r before c4_mean[r] < cut * c4_error[r] for the first time, or r_max; xi12 = I_2 / I_1 with
+    I_k = sum_{r = 0}^{r_cut} r^k c4_mean[r]; its error is the delete-one jackknife over samples with r_cut held fixed."""
+    c4 = np.asarray(c4, dtype=np.float64)
+    S, R = c4.shape[-2], c4.shape[-1]
+    mean = c4.mean(axis=-2)
+    err = np.full(mean.shape, np.nan) if S < 2 else np.std(c4, axis=-2, ddof=1) / np.sqrt(S)
+    with np.errstate(invalid="ignore"):
+        below = mean < float(cut) * err  # NaN errors (one sample) never trigger
+    r_cut = np.where(below.any(axis=-1), below.argmax(axis=-1) - 1, R - 1)
+    r = np.arange(R, dtype=np.float64)
+    keep = r <= r_cut[..., None]
+
+    def ratio(m):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.sum(np.where(keep, r ** 2 * m, 0.0), axis=-1) / np.sum(np.where(keep, r * m, 0.0), axis=-1)
+
+    xi = ratio(mean)
+    if S < 2:
+        return mean, err, xi, np.full(xi.shape, np.nan), r_cut
+    tot = c4.sum(axis=-2)
+    th = np.stack([ratio((tot - c4[..., i, :]) / (S - 1)) for i in range(S)])
+    return mean, err, xi, np.sqrt((S - 1) / S * np.sum((th - th.mean(axis=0)) ** 2, axis=0)), r_cut
+
+
+def multispin_quench_3d(size, temperatures, *, couplings, times, waiting_times=(), replicas: int = 2, periodic=True,
+                        seed: Optional[int] = None, seeds=None, route: Optional[str] = None, cut: float = 3.0) -> dict:
+    """Quench S bimodal samples from T = infinity (``initial="random"``) to every temperature (:class:`MultispinGlass3D`, no swaps)
+    and record at ``times`` (sweeps since the quench): :meth:`MultispinGlass3D.quench`'s dict, plus
+
+    * ``c4_mean`` (n_times, n_temps, r_max + 1): C_d[r] / N averaged over the samples and over the periodic axes of the longest
+      length among them (r_max = half that length), and ``c4_error``, its standard error over samples;
+    * ``xi12`` and ``xi12_error`` (n_times, n_temps): the coherence length I_2 / I_1, I_k = sum_{r = 0}^{r_cut} r^k c4_mean[r],
+      r_cut the last r before c4_mean[r] < ``cut`` * c4_error[r] for the first time, or r_max (``r_cut`` holds it); the error is a
+      delete-one jackknife over samples with r_cut held fixed.  The sum stops at r_cut: no tail is extrapolated;
+    * ``aging`` (n_wait, n_times, n_temps): C(t, t_w) / N averaged over samples and replicas, NaN where t < t_w.
+
+    **The 64 samples of a word share their random numbers, and with ``initial="random"`` they also share their starting
+    configuration**: errors over samples within one word are therefore correlated (samples in different words differ in neither)."""
+    if replicas not in (1, 2):
+        raise ValueError("replicas must be 1 or 2")
+    _quench_times(times, waiting_times)
+    shape, per = _shape_3d(size), _hip.periodic_axes(periodic)
+    _check_quench_lattice(shape, per)
+    if seeds is None and seed is None:
+        seed = 0
+    g = MultispinGlass3D(size, temperatures, couplings=couplings, periodic=periodic, replicas=replicas, seed=seed, seeds=seeds,
+                         initial="random", route=route)
+    try:
+        res = g.quench(times, waiting_times)
+    finally:
+        g.close()
+    longest = max(n for n, p in zip(shape, per) if p)
+    axes = [d for d in range(3) if per[d] and shape[d] == longest]
+    c4 = np.mean([res["c4"][d] for d in axes], axis=0) / float(g.n_spins)  # (n_times, n_temps, S, r_max + 1)
+    res["c4_mean"], res["c4_error"], res["xi12"], res["xi12_error"], res["r_cut"] = _xi12(c4, cut)
+    two = res["two_time"] / float(g.n_spins)
+    res["aging"] = two.mean(axis=-1) if replicas == 1 else two.mean(axis=(-1, -2))
+    res["temperatures"] = np.asarray(temperatures, dtype=float)
+    return res
 
 
 def multispin_scan_3d(size, temperatures, *, couplings, n_equilibrate: int = 1000, n_measure: int = 50, measure_every: int = 1,
