@@ -4,7 +4,8 @@
     python tools/k1_loop_counts.py tiled.s [--before parent.s] [kernel-name-substring ...]
 
 First a table of every k1_* kernel in the file: VGPRs, scratch bytes and occupancy as the compiler reports them (with --before:
-beside the same figures of another build, regressions marked).  Then, for every kernel whose mangled name contains one of the
+beside the same figures of another build, regressions marked; a kernel whose template gained a trailing bool parameter since then is
+compared with the other build's kernel of the name without it).  Then, for every kernel whose mangled name contains one of the
 substrings (default: the two flagship tile-resident kernels), the VALU mnemonic histogram of every pair loop.
 
 A pair loop is a loop (a label and the last backward branch to it or to a label just behind it) that holds LDS reads and at least
@@ -97,8 +98,10 @@ def main():
         if "k1_" not in name:
             continue
         r = resources(body)
-        if before and name in before:
-            p = resources(before[name])
+        # a kernel template that gained a trailing bool parameter: compare with the build before under the name without it
+        was = name if not before or name in before else re.sub(r"Lb[01]E(Ev)", r"\1", name, count=1)
+        if before and was in before:
+            p = resources(before[was])
             worse = r["ScratchSize"] > p["ScratchSize"] or r["Occupancy"] < p["Occupancy"]
             print(f"  {name:78s} {p['NumVgprs']:3d} -> {r['NumVgprs']:3d}   {p['ScratchSize']:2d} -> {r['ScratchSize']:2d}   {p['Occupancy']} -> {r['Occupancy']}"
                   + ("   worse" if worse else ""))

@@ -3,7 +3,7 @@
 // Same Markov kernel and the same Philox stream as k1_generic / oracle ora_ising2d_sweep (results are bit
 // identical); what changes is the schedule:
 //   * a workgroup stages a (H + 4k) x (16 WO + 32) tile of the int8 lattice into LDS, de-interleaved into two
-//     colour planes of 0/1 "up" flags (8 same-colour sites of a row = one octet = one uint64),
+//     colour planes of 0/1 "up" flags (8 same-colour sites of a row = one octet = one uint64; 0/8 in the QUAD kernels),
 //   * keeps the two planes interleaved row by row: behind the pair table of the compare and one guard octet, tile row r is its
 //     NO = WO + 2 octets of plane 0 followed by its NO octets of plane 1, then one spare row and the 25 thresholds of the tie
 //     path.  Row stride (2 NO octets) and plane distance (NO octets) are compile-time constants for a tile of any height, so the
@@ -16,8 +16,9 @@
 // LDS for a whole call and only exchanges boundary strips between generations of k sweeps (see ResidentParams).
 // HBM traffic is 2/k bytes per spin update instead of 2 (far less when resident); the kernel is VALU bound (Philox), so per octet:
 //   one Philox4x32-10 block -> 8 x 16 random bits; neighbour sums with packed byte adds; the 16-bit thresholds of two
-//   sites at a time from a 25-dword LDS table indexed by their two counts (v_dot4_u32_u8 + ds_read_b32; open lattices, whose
-//   edge sites have other degrees, pick them per site with v_perm_b32 byte look-ups); v_pk_sub_i16 (saturating) compares two
+//   sites at a time from a 25-dword LDS table indexed by their two counts (v_dot4_u32_u8 + ds_read_b32; periodic byte planes
+//   with 5 KB of LDS to spare: of four sites at a time from a 625-entry table, up-flags stored as 8, see pair_thresholds; open
+//   lattices, whose edge sites have other degrees, pick them per site with v_perm_b32 byte look-ups); v_pk_sub_i16 (saturating) compares two
 //   sites per instruction; only an exact tie of the top 16 bits (2^-16 per site) evaluates the low half.
 // The form of the pair loop (plain / EDGE / SEAM / OPEN) and par0, the column parity of the colour updated in a half-sweep's first
 // row, are fixed per tile: half-sweep hsi starts at tile row 1 + hsi and updates colour hsi & 1, whose sum is always odd, so par0
@@ -91,17 +92,19 @@ static __device__ __forceinline__ uint32_t minu16(uint32_t a, uint32_t b) {
 
 // exact resolution of the (rare) fields whose top 16 bits tie with the threshold: d fields that are 0.
 // Cold path (probability 2^-16 per site): kept out of line and register-to-register (no arrays by address).
+template <uint32_t CSHIFT = 0>
 static __device__ __noinline__ u32x4 resolve_ties(u32x4 d, u32x4 w, uint32_t cnt_lo, uint32_t cnt_hi, const uint64_t* s_thr,
                                                   uint32_t cq, uint32_t Rg, uint32_t hs, uint32_t tag_lo, uint32_t k0,
                                                   uint32_t k1, uint32_t edge = 0) {
     // edge (open lattices): bit 0 = the row is the lattice's top or bottom row, bit 1 = site 0 of the octet is in the
     // lattice's first column, bit 2 = site (edge >> 4) is in its last column; degree = 4 minus the missing neighbours
+    // CSHIFT: the counts arrive scaled by 1 << CSHIFT (3 with the quad table, see pair_thresholds)
     const u32x4 l = tsu_philox(cq, Rg, hs, tag_lo, k0, k1);
 #define TSU_FIX(DW, WW, LW, CNT, B0, M0)                                                                        \
     _Pragma("unroll") for (int hlf = 0; hlf < 2; ++hlf) {                                                       \
         const uint32_t sh = 16u * hlf;                                                                          \
         if (((DW >> sh) & 0xFFFFu) == 0) {                                                                      \
-            const uint32_t c = (CNT >> (8 * (B0 + hlf))) & 0xFFu;                                               \
+            const uint32_t c = ((CNT >> (8 * (B0 + hlf))) & 0xFFu) >> CSHIFT;                                   \
             const uint32_t m = M0 + hlf;                                                                        \
             const uint32_t deg = 4u - (edge & 1u) - ((m == 0 && (edge & 2u)) ? 1u : 0u) - ((m == (edge >> 4) && (edge & 4u)) ? 1u : 0u); \
             const uint64_t u = ((uint64_t)(((WW >> sh) & 0xFFFFu) ^ 0x8000u) << 16) | ((LW >> sh) & 0xFFFFu);   \
@@ -232,10 +235,31 @@ struct PairCounts {
 struct PairThr {
     uint32_t t[8];  // threshold words of row a's octet (against w.x .. w.w), then of row b's
 };
-// issues the eight table reads of a pair; pair_step puts them in front of the second Philox block, which hides their latency
+// QUAD (byte planes whose tile leaves the LDS for it, see tile_body): one look-up serves the four sites of a count dword.  Entry
+// i = c0 + 5 c1 + 25 c2 + 125 c3 of tbl4 (625 x 8 bytes) holds t16(c0) | t16(c1) << 16 | t16(c2) << 32 | t16(c3) << 48, two
+// consecutive w words.  The byte offset 8 i must come out of one v_dot4 and 8 x 125 is no byte weight, so the colour planes of
+// these kernels hold their up-flags as 8 instead of 1: the counts arrive scaled by 8 (a byte is at most 32, nothing carries) and
+// the weights are (1, 5, 25, 125).  Per pair 4 v_dot4 + 4 ds_read_b64 for 8 + 8.  Scattered 8-byte reads over 5 KB do meet bank
+// conflicts, which lanes on neighbouring octets of an ordered lattice mostly avoid (profiles/k1_quad_table_microbench.txt).
+constexpr uint32_t QUAD_FLAG = 8u, QUAD_SHIFT = 3u;
+// issues the table reads of a pair; pair_step puts them in front of the second Philox block, which hides their latency
+template <bool QUAD>
 static __device__ __forceinline__ PairThr pair_thresholds(const PairCounts& n, uint32_t tbl2) {
-    constexpr uint32_t W01 = 0x00001404u, W23 = 0x14040000u;
+    constexpr uint32_t W01 = 0x00001404u, W23 = 0x14040000u, WQ = 0x7D190501u;
     const uint32_t cnt[4] = {n.c0l, n.c0h, n.c1l, n.c1h};
+    if constexpr (QUAD) {
+        uint32_t off4[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) off4[j] = __builtin_amdgcn_udot4(cnt[j], WQ, 0u, false);
+        PairThr T;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const uint64_t e = lds_ld<uint64_t>(tbl2 + off4[j]);
+            T.t[2 * j] = (uint32_t)e;
+            T.t[2 * j + 1] = (uint32_t)(e >> 32);
+        }
+        return T;
+    }
     uint32_t off[8];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -282,11 +306,13 @@ static __device__ __forceinline__ bool has_zero_field(const u32x4& d) {
     return ((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0);
 }
 
+template <bool QUAD = false>
 static __device__ __forceinline__ uint64_t pack_flags(const u32x4& d) {
     // v_perm_b32 selectors 8..11 replicate the sign bit of the four 16-bit fields of {S0,S1} (bits 15, 31, 47, 63)
     // into a whole byte: one instruction turns the four "accept" signs into 0x00 / 0xFF bytes
-    const uint32_t nlo = perm(d.y, d.x, 0x0B0A0908u) & 0x01010101u;
-    const uint32_t nhi = perm(d.w, d.z, 0x0B0A0908u) & 0x01010101u;
+    constexpr uint32_t FLM = (QUAD ? QUAD_FLAG : 1u) * 0x01010101u;
+    const uint32_t nlo = perm(d.y, d.x, 0x0B0A0908u) & FLM;
+    const uint32_t nhi = perm(d.w, d.z, 0x0B0A0908u) & FLM;
     return (uint64_t)nlo | ((uint64_t)nhi << 32);
 }
 
@@ -331,6 +357,7 @@ static __device__ __forceinline__ void edge_rows(const Rows2Ctx& c, int to_wrap,
 // a constant that the table reads carry in their offset field (through `lds` it would be a register and cost an add per read).
 // A static __shared__ variable in a tile kernel would move the planes onto the table: every K1 parity test then fails.
 constexpr int TBL2_OCTETS = 13;
+constexpr int TBL4_OCTETS = 625;  // the quad table (see pair_thresholds) in its place
 constexpr uint32_t TBL2_LDS_ADDR = 0;
 
 // every indexer of the colour planes outside the pair loop: octet o of tile row r of plane pl
@@ -344,7 +371,7 @@ struct TilePlanes {
 // KAPPA = colour of the half-sweep (the destination plane; the source is the other one)
 // P0 = column parity of the updated colour in row tr (and 1-P0 in the row below it); it is the same for every half-sweep of
 // a tile: the first row of half-sweep hsi is tile row 1 + hsi and its colour hsi & 1, and their sum is always odd
-template <int NO, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM>
+template <int NO, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM, bool QUAD>
 static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t y0, uint32_t a, int rg, int to_wrap,
                                                  uint32_t cq) {
     constexpr int RS = 2 * NO * 8;                    // row stride
@@ -398,7 +425,7 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
     if constexpr (EARLY) {
         __builtin_amdgcn_sched_barrier(0);
         n = counts();
-        T = pair_thresholds(n, c.tbl2);
+        T = pair_thresholds<QUAD>(n, c.tbl2);
         __builtin_amdgcn_sched_barrier(0);
     }
     const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.rmask, y0, hs, c.tag_hi, K);
@@ -422,10 +449,10 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
     }
     const uint32_t mn = minu16(minu16(minu16(d0.x, d0.y), minu16(d0.z, d0.w)), minu16(minu16(d1.x, d1.y), minu16(d1.z, d1.w)));
     if (__builtin_expect(((mn & 0xFFFFu) == 0) | ((mn >> 16) == 0), 0)) {
-        if (has_zero_field(d0)) d0 = resolve_ties(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga & c.rmask, hs, c.tag_lo, c.k0, c.k1, edge_a);
-        if (has_zero_field(d1)) d1 = resolve_ties(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb & c.rmask, hs, c.tag_lo, c.k0, c.k1, edge_b);
+        if (has_zero_field(d0)) d0 = resolve_ties<QUAD ? QUAD_SHIFT : 0u>(d0, w0, cnt0l, cnt0h, c.s_thr, cq, (uint32_t)rga & c.rmask, hs, c.tag_lo, c.k0, c.k1, edge_a);
+        if (has_zero_field(d1)) d1 = resolve_ties<QUAD ? QUAD_SHIFT : 0u>(d1, w1, cnt1l, cnt1h, c.s_thr, cq, (uint32_t)rgb & c.rmask, hs, c.tag_lo, c.k0, c.k1, edge_b);
     }
-    uint64_t n0 = pack_flags(d0), n1 = pack_flags(d1);
+    uint64_t n0 = pack_flags<QUAD>(d0), n1 = pack_flags<QUAD>(d1);
     if (OPEN) {  // what lies beyond the open edge stays empty (it is a neighbour of the edge sites in the next half-sweep)
         n0 = (rga < 0 || rga > c.last_row) ? 0 : (n0 & (P0 ? c.vm_o : c.vm_e));
         n1 = (rgb < 0 || rgb > c.last_row) ? 0 : (n1 & (P0 ? c.vm_e : c.vm_o));
@@ -445,7 +472,7 @@ static __device__ __forceinline__ void pair_step(const Rows2Ctx& c, const Philox
 // induction variables (kept opaque so that the compiler neither re-derives them from the trip counter nor the trip counter
 // from them); every other address is an immediate, see pair_step.
 // EDGE (the tile's window crosses the lattice's last row): rg counts tile rows and the wrap is applied per wave, see edge_rows
-template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM = false>
+template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM, bool QUAD>
 static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const PhiloxKeys& K, uint32_t hs, uint32_t y0, uint32_t a, int rg, int n, bool tail,
                                                    uint32_t cq) {
     int to_wrap = EDGE ? c.wrap_tr - __builtin_amdgcn_readfirstlane(rg) : 0;  // from the wave's first lane (lanes ascend in rows)
@@ -454,7 +481,7 @@ static __device__ __forceinline__ void sweep_pairs(const Rows2Ctx& c, const Phil
     for (int i = n; i >= 0; --i) {
         if (i == 0) live = tail;
         asm volatile("" : "+v"(a), "+v"(rg));
-        if (live) pair_step<NO, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, y0, a, rg, to_wrap, cq);
+        if (live) pair_step<NO, KAPPA, P0, EDGE, OPEN, SEAM, QUAD>(c, K, hs, y0, a, rg, to_wrap, cq);
         a += 2 * RL * 2 * NO * 8;
         rg += 2 * RL;
         to_wrap -= 2 * RL;
@@ -522,7 +549,7 @@ static __device__ __forceinline__ void pair_step_nib(const Rows2Ctx& c, const Ph
     if constexpr (EARLY) {
         __builtin_amdgcn_sched_barrier(0);
         n = counts();
-        T = pair_thresholds(n, c.tbl2);
+        T = pair_thresholds<false>(n, c.tbl2);
         __builtin_amdgcn_sched_barrier(0);
     }
     const u32x4 w1 = philox_vk(cq, (uint32_t)rgb, c.rmask, y0, hs, c.tag_hi, K);
@@ -578,7 +605,7 @@ static __device__ __forceinline__ void sweep_pairs_nib(const Rows2Ctx& c, const 
 
 // Half-sweep hsi = 2 s + KAPPA of a generation on one tile of TR rows: rows [1 + hsi, TR - 2 - hsi] in pairs (TR is even),
 // thread (al, octet) takes every RL-th pair from pair al on.  a_thr = LDS byte address of (row 2 al, the thread's octet, plane 0)
-template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM, bool NIB>
+template <int NO, int RL, int KAPPA, int P0, bool EDGE, bool OPEN, bool SEAM, bool NIB, bool QUAD>
 static __device__ __forceinline__ void half_sweep(const Rows2Ctx& c, const PhiloxKeys& K, int TR, uint32_t sweep, int s, uint32_t a_thr, int al,
                                                   uint32_t cq) {
     constexpr int ES = NIB ? 4 : 8;
@@ -600,18 +627,18 @@ static __device__ __forceinline__ void half_sweep(const Rows2Ctx& c, const Philo
         const uint32_t hs = 2u * sweep + (uint32_t)KAPPA;
         const uint32_t y0 = philox_y0(hs, c.k0);
         if constexpr (NIB) sweep_pairs_nib<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, y0, a, rg, n, tail, cq);
-        else sweep_pairs<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM>(c, K, hs, y0, a, rg, n, tail, cq);
+        else sweep_pairs<NO, RL, KAPPA, P0, EDGE, OPEN, SEAM, QUAD>(c, K, hs, y0, a, rg, n, tail, cq);
     }
 }
 
 // the kg sweeps of one generation, two half-sweeps per trip: colour 0, then colour 1
-template <int NO, int RL, int P0, bool EDGE, bool OPEN, bool SEAM, bool NIB>
+template <int NO, int RL, int P0, bool EDGE, bool OPEN, bool SEAM, bool NIB, bool QUAD>
 static __device__ __forceinline__ void sweep_generation(const Rows2Ctx& c, const PhiloxKeys& K, int TR, uint32_t sweep_g, int kg, uint32_t a_thr,
                                                         int al, uint32_t cq) {
 #pragma unroll 1
     for (int s = 0; s < kg; ++s) {
-        half_sweep<NO, RL, 0, P0, EDGE, OPEN, SEAM, NIB>(c, K, TR, sweep_g + (uint32_t)s, s, a_thr, al, cq);
-        half_sweep<NO, RL, 1, P0, EDGE, OPEN, SEAM, NIB>(c, K, TR, sweep_g + (uint32_t)s, s, a_thr, al, cq);
+        half_sweep<NO, RL, 0, P0, EDGE, OPEN, SEAM, NIB, QUAD>(c, K, TR, sweep_g + (uint32_t)s, s, a_thr, al, cq);
+        half_sweep<NO, RL, 1, P0, EDGE, OPEN, SEAM, NIB, QUAD>(c, K, TR, sweep_g + (uint32_t)s, s, a_thr, al, cq);
     }
 }
 
@@ -640,7 +667,9 @@ struct ResidentParams {
     long long* dbg;  // TSU_K1_VERBOSE=2: per tile, wall_clock64 ticks spent in [sweeps, publish, wait, fetch]
 };
 
-template <int HT, int WO, int THREADS, bool OPEN = false, bool RESIDENT = false, bool NIB = false>
+// QUAD: periodic byte planes with the 625-entry threshold table and up-flags stored as QUAD_FLAG (see pair_thresholds): the host
+// takes this form where the larger table fits beside the tile that the 25-entry form was planned with
+template <int HT, int WO, int THREADS, bool OPEN = false, bool RESIDENT = false, bool NIB = false, bool QUAD = false>
 static __device__ __forceinline__ void tile_body(const TiledParams& p, const int8_t* __restrict__ src, int8_t* __restrict__ dst,
                                                  const int k, const uint32_t sweep0, const int tx, const int ty, uint64_t* lds,
                                                  const PhiloxKeys& K, const ResidentParams* R = nullptr) {
@@ -656,19 +685,30 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     constexpr int RL = RLMAX;
     using E = typename std::conditional<NIB, uint32_t, uint64_t>::type;  // one octet of a colour plane
     // the pair table of the periodic compare (pair_thresholds) at the start of the workgroup's LDS, the guard octet behind it
-    uint64_t* const guard = lds + TBL2_OCTETS;
+    static_assert(!QUAD || (!OPEN && !NIB), "the quad table is for periodic byte planes");
+    constexpr uint32_t FL = QUAD ? QUAD_FLAG : 1u;  // an up-flag of the colour planes
+    uint64_t* const guard = lds + (QUAD ? TBL4_OCTETS : TBL2_OCTETS);
     // the colour planes, interleaved row by row (see TilePlanes): plane 0 of row 0 starts behind the guard octet
     const TilePlanes<E, NO> P{reinterpret_cast<E*>(guard + 1)};
     // one spare row behind the planes: "octet NO" of plane 1 of the last row is read there (rounded up to the uint64 grid)
     uint64_t* s_thr = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(P.base + 2 * TR * NO + NO + 1) + 7u) & ~(uintptr_t)7u);
     const int tid = threadIdx.x;
     if (tid < 25) s_thr[tid] = p.thr[tid];
-    if (!OPEN && tid < 25) {  // the top 16 bits of the degree-4 thresholds, as pack_thresholds makes them for the byte tables
-        auto t16 = [&](int up) {
-            const uint64_t thi = p.thr[4 * 5 + up] >> 16;
-            return (uint32_t)(thi > 65535u ? 65535u : thi) ^ 0x8000u;
-        };
-        reinterpret_cast<uint32_t*>(lds)[tid] = t16(tid % 5) | (t16(tid / 5) << 16);
+    // the top 16 bits of the degree-4 thresholds, as pack_thresholds makes them for the byte tables
+    auto t16 = [&](int up) {
+        const uint64_t thi = p.thr[4 * 5 + up] >> 16;
+        return (uint32_t)(thi > 65535u ? 65535u : thi) ^ 0x8000u;
+    };
+    if (!OPEN && !QUAD && tid < 25) reinterpret_cast<uint32_t*>(lds)[tid] = t16(tid % 5) | (t16(tid / 5) << 16);
+    if constexpr (QUAD) {
+        for (int i = tid; i < TBL4_OCTETS; i += THREADS) {
+            const uint32_t lo = t16(i % 5) | (t16(i / 5 % 5) << 16), hi = t16(i / 25 % 5) | (t16(i / 125) << 16);
+            lds[i] = (uint64_t)lo | ((uint64_t)hi << 32);
+        }
+        // "octet -1" of row 0 and "octet NO" of the last row (see TilePlanes) feed counts that nothing reads, but here a count is
+        // part of an 8-byte LDS address: they hold flags like every other octet (the guard's low word is s_fail, 0 while sweeping)
+        if (tid == 0) *guard = 0;
+        if (tid <= NO) P.base[2 * TR * NO + tid] = 0;
     }
 
     const int q0 = tx * WO + p.q_shift, r0 = p.r_begin + row_off, Rb = r0 - 2 * k;
@@ -689,7 +729,7 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     if (col_out) nv = 0;
     if (nv > 16) nv = 16;
     auto first_sites = [](int n) { return n >= 8 ? 0x0101010101010101ull : (((1ull << (8 * n)) - 1) & 0x0101010101010101ull); };
-    const uint64_t vm_e = first_sites((nv + 1) >> 1), vm_o = first_sites(nv >> 1);
+    const uint64_t vm_e = first_sites((nv + 1) >> 1) * FL, vm_o = first_sites(nv >> 1) * FL;
 
     if (al < RLMAX) {
         const int8_t* col = src + 16 * (long long)(OPEN ? (cqi < 0 ? 0 : (cqi >= p.nchunks ? p.nchunks - 1 : cqi)) : cqi);
@@ -714,8 +754,10 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
                     // de-interleave the two colours, then +1 (0x01) -> 1, -1 (0xFF) -> 0: bit 1 of the byte, inverted
                     const uint32_t e0 = perm(v[b].y, v[b].x, 0x06040200u), e1 = perm(v[b].w, v[b].z, 0x06040200u);
                     const uint32_t o0 = perm(v[b].y, v[b].x, 0x07050301u), o1 = perm(v[b].w, v[b].z, 0x07050301u);
-                    uint64_t ev = (uint64_t)(~(e0 >> 1) & 0x01010101u) | ((uint64_t)(~(e1 >> 1) & 0x01010101u) << 32);
-                    uint64_t od = (uint64_t)(~(o0 >> 1) & 0x01010101u) | ((uint64_t)(~(o1 >> 1) & 0x01010101u) << 32);
+                    // (QUAD: the flag is bit 3 of the byte)
+                    auto up = [](uint32_t x) { return ~(QUAD ? x << 2 : x >> 1) & (FL * 0x01010101u); };
+                    uint64_t ev = (uint64_t)up(e0) | ((uint64_t)up(e1) << 32);
+                    uint64_t od = (uint64_t)up(o0) | ((uint64_t)up(o1) << 32);
                     if (OPEN) {
                         const long long grow = p.row0 + Rb + tr;
                         if (grow < 0 || grow >= p.total_rows) ev = od = 0;  // beyond the open edge: nothing there
@@ -809,16 +851,22 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     // round trip that is repeated only for the elements that were not there yet.  (A slot is rewritten every second
     // generation and neighbours are never more than one generation apart, so a stale element always carries another
     // number; the host clears the buffer when the numbering restarts or the strip layout changes.)
-    // (nibble planes: an element is the octet's dword, the number sits above it in bits 32..45)
+    // (nibble planes: an element is the octet's dword, the number sits above it in bits 32..45; QUAD: the flag is bit 3 of a byte
+    // and the number takes bits 0..2 and 4..7 of bytes 0 and 1)
     const int n_tb = 2 * k * WO, n_lr = H;  // elements of a top/bottom and of a left/right strip
     const int xstride = 2 * n_tb + 2 * p.tile_h;  // (tile rows of a flexible cut differ by two rows: one slot size for all)
     // The last tile column of a lattice whose width is not a multiple of the tile width holds wi < WO lattice octets: its last
     // interior octet is tile octet wi, its right halo tile octet wi + 1; what lies beyond is the lattice's periodic continuation
     // from the stage, computed along and never read by anything that counts (it decays like the far side of any halo octet).
     const int wi = (p.nchunks + p.q_shift - q0) < WO ? (p.nchunks + p.q_shift - q0) : WO;
-    constexpr uint64_t TAG_MASK = NIB ? 0xFFFFFFFF00000000ull : 0xFEFEull, FLAG_MASK = NIB ? 0x11111111ull : 0x0101010101010101ull;
+    constexpr uint64_t TAG_MASK = NIB ? 0xFFFFFFFF00000000ull : (QUAD ? 0xF7F7ull : 0xFEFEull);
+    constexpr uint64_t FLAG_MASK = NIB ? 0x11111111ull : FL * 0x0101010101010101ull;
     auto strip_tag = [&](int gen) -> uint64_t {
         const uint32_t G = R->gen0 + (uint32_t)gen;
+        if (QUAD) {
+            auto beside_bit3 = [](uint32_t g7) { return (uint64_t)((g7 & 7u) | ((g7 >> 3) << 4)); };
+            return beside_bit3(G & 0x7Fu) | (beside_bit3((G >> 7) & 0x7Fu) << 8);
+        }
         return NIB ? ((uint64_t)G << 32) : (((uint64_t)(G & 0x7Fu) << 1) | ((uint64_t)((G >> 7) & 0x7Fu) << 9));
     };
     // publish generation gen's boundary strips: its first / last 2k interior rows and first / last interior octet column
@@ -943,7 +991,7 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     // thread (al, oct): LDS byte address of (row 2 al, its octet, plane 0), the start of its pair loop in half-sweep 0
     const uint32_t a_thr = lds_addr(P.base) + (uint32_t)((4 * al * NO + oct) * (int)sizeof(E));
     auto run_generation = [&](uint32_t sweep_g, int kg) {
-#define TSU_FORM(P0, EDGE_, OPEN_, SEAM_) sweep_generation<NO, RL, P0, EDGE_, OPEN_, SEAM_, NIB>(c, K, TR, sweep_g, kg, a_thr, al, cq)
+#define TSU_FORM(P0, EDGE_, OPEN_, SEAM_) sweep_generation<NO, RL, P0, EDGE_, OPEN_, SEAM_, NIB, QUAD>(c, K, TR, sweep_g, kg, a_thr, al, cq)
         if constexpr (OPEN) {
             if (par0) TSU_FORM(1, false, true, false);
             else TSU_FORM(0, false, true, false);
@@ -989,6 +1037,10 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
                     ev = (ev & 0x01010101ull) | (((ev >> 4) & 0x01010101ull) << 32);
                     od = (od & 0x01010101ull) | (((od >> 4) & 0x01010101ull) << 32);
                 }
+                if (QUAD) {  // the flag as 0 / 1, which the look-up below selects by
+                    ev >>= QUAD_SHIFT;
+                    od >>= QUAD_SHIFT;
+                }
                 // up flag -> spin byte: 1 -> 0x01, 0 -> 0xFF
                 const uint32_t e0 = perm(0u, 0x000001FFu, (uint32_t)ev), e1 = perm(0u, 0x000001FFu, (uint32_t)(ev >> 32));
                 const uint32_t o0 = perm(0u, 0x000001FFu, (uint32_t)od), o1 = perm(0u, 0x000001FFu, (uint32_t)(od >> 32));
@@ -1008,11 +1060,11 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     }
 }
 
-template <int H, int WO, int THREADS, int MINW = 1, bool OPEN = false, bool NIB = false>
+template <int H, int WO, int THREADS, int MINW = 1, bool OPEN = false, bool NIB = false, bool QUAD = false>
 __global__ __launch_bounds__(THREADS, MINW) void k1_tiled2(TiledParams p) {
     extern __shared__ uint64_t lds[];
     const PhiloxKeys K = make_keys(p.k0, p.k1);
-    tile_body<H, WO, THREADS, OPEN, false, NIB>(p, p.src, p.dst, p.k, p.sweep0, blockIdx.x % p.tiles_x,
+    tile_body<H, WO, THREADS, OPEN, false, NIB, QUAD>(p, p.src, p.dst, p.k, p.sweep0, blockIdx.x % p.tiles_x,
                                     p.ty_first + (blockIdx.x / p.tiles_x) * p.ty_stride, lds, K);
 }
 
@@ -1022,11 +1074,11 @@ struct ResidentLaunch {
     ResidentParams r;
 };
 
-template <int H, int WO, int THREADS, int MINW = 1, bool OPEN = false, bool NIB = false>
+template <int H, int WO, int THREADS, int MINW = 1, bool OPEN = false, bool NIB = false, bool QUAD = false>
 __global__ __launch_bounds__(THREADS, MINW) void k1_resident(ResidentLaunch P) {
     extern __shared__ uint64_t lds[];
     const PhiloxKeys K = make_keys(P.t.k0, P.t.k1);
-    tile_body<H, WO, THREADS, OPEN, true, NIB>(P.t, P.t.src, P.t.dst, P.t.k, P.t.sweep0, blockIdx.x % P.t.tiles_x, blockIdx.x / P.t.tiles_x,
+    tile_body<H, WO, THREADS, OPEN, true, NIB, QUAD>(P.t, P.t.src, P.t.dst, P.t.k, P.t.sweep0, blockIdx.x % P.t.tiles_x, blockIdx.x / P.t.tiles_x,
                                           lds, K, &P.r);
 }
 
@@ -1042,12 +1094,14 @@ struct TileVariant {
     void (*resident_open)(ResidentLaunch);
     int nib;                         // colour planes at 4 bits per site (periodic lattices, width a multiple of 16)
     int per_cu;                      // workgroups of this shape one CU is meant to hold (tiles per round; LDS share of a stretched tile)
+    void (*kernel_q)(TiledParams);   // periodic byte planes with the quad threshold table (nullptr: nibble planes keep the pair table)
+    void (*resident_q)(ResidentLaunch);
 };
 
 // LDS of one workgroup: pair table, guard octet, two colour planes of TR x NO octets (+ one spare row), 25 thresholds
-size_t tile_lds_bytes(const TileVariant& tv, int TR) {
+size_t tile_lds_bytes(const TileVariant& tv, int TR, bool quad = false) {
     const size_t es = tv.nib ? 4 : 8, NO = (size_t)tv.WO + 2;
-    return 8 * TBL2_OCTETS + 8 + (((size_t)2 * TR * NO + NO + 1) * es + 7) / 8 * 8 + 8 + 25 * sizeof(uint64_t);
+    return 8 * (quad ? TBL4_OCTETS : TBL2_OCTETS) + 8 + (((size_t)2 * TR * NO + NO + 1) * es + 7) / 8 * 8 + 8 + 25 * sizeof(uint64_t);
 }
 // the tile shapes the chooser (plan_call) can reach.  Round 1's table had 32 entries, 24 of them reachable only through
 // the TSU_TILE_VARIANT development switch; numbers quoted in profiles/r01_* map as 6 -> 0, 8 -> 1, 9 -> 2, 22 -> 3, 23 -> 4,
@@ -1055,18 +1109,26 @@ size_t tile_lds_bytes(const TileVariant& tv, int TR) {
 enum { V_64x512_T512 = 0, V_128x512_T512, V_128x512_T1024, V_256x512_T1024, V_128x256_T1024, V_64x512_T1024, V_64x256_T1024, V_32x256_T1024,
        V_N512x512_T1024, V_N256x512_T512 };
 const TileVariant kVariants[] = {
-    {64, 32, 512, k1_tiled2<64, 32, 512>, k1_resident<64, 32, 512>, k1_tiled2<64, 32, 512, 1, true>, nullptr, 0, 2},
-    {128, 32, 512, k1_tiled2<128, 32, 512>, k1_resident<128, 32, 512>, k1_tiled2<128, 32, 512, 1, true>, nullptr, 0, 2},
-    {128, 32, 1024, k1_tiled2<128, 32, 1024>, k1_resident<128, 32, 1024>, k1_tiled2<128, 32, 1024, 1, true>, k1_resident<128, 32, 1024, 1, true>, 0, 1},
-    {256, 32, 1024, k1_tiled2<256, 32, 1024, 4>, k1_resident<256, 32, 1024, 4>, k1_tiled2<256, 32, 1024, 4, true>, k1_resident<256, 32, 1024, 4, true>, 0, 1},  // one 148 KB workgroup per CU
-    {128, 16, 1024, k1_tiled2<128, 16, 1024>, k1_resident<128, 16, 1024>, k1_tiled2<128, 16, 1024, 1, true>, k1_resident<128, 16, 1024, 1, true>, 0, 1},  // narrower tiles for mid-size lattices
-    {64, 32, 1024, k1_tiled2<64, 32, 1024>, k1_resident<64, 32, 1024>, k1_tiled2<64, 32, 1024, 1, true>, k1_resident<64, 32, 1024, 1, true>, 0, 1},
-    {64, 16, 1024, k1_tiled2<64, 16, 1024>, k1_resident<64, 16, 1024>, k1_tiled2<64, 16, 1024, 1, true>, k1_resident<64, 16, 1024, 1, true>, 0, 1},
-    {32, 16, 1024, k1_tiled2<32, 16, 1024>, k1_resident<32, 16, 1024>, k1_tiled2<32, 16, 1024, 1, true>, k1_resident<32, 16, 1024, 1, true>, 0, 1},
+    {64, 32, 512, k1_tiled2<64, 32, 512>, k1_resident<64, 32, 512>, k1_tiled2<64, 32, 512, 1, true>, nullptr, 0, 2,
+     k1_tiled2<64, 32, 512, 1, false, false, true>, k1_resident<64, 32, 512, 1, false, false, true>},
+    {128, 32, 512, k1_tiled2<128, 32, 512>, k1_resident<128, 32, 512>, k1_tiled2<128, 32, 512, 1, true>, nullptr, 0, 2,
+     k1_tiled2<128, 32, 512, 1, false, false, true>, k1_resident<128, 32, 512, 1, false, false, true>},
+    {128, 32, 1024, k1_tiled2<128, 32, 1024>, k1_resident<128, 32, 1024>, k1_tiled2<128, 32, 1024, 1, true>, k1_resident<128, 32, 1024, 1, true>, 0, 1,
+     k1_tiled2<128, 32, 1024, 1, false, false, true>, k1_resident<128, 32, 1024, 1, false, false, true>},
+    {256, 32, 1024, k1_tiled2<256, 32, 1024, 4>, k1_resident<256, 32, 1024, 4>, k1_tiled2<256, 32, 1024, 4, true>, k1_resident<256, 32, 1024, 4, true>, 0, 1,
+     k1_tiled2<256, 32, 1024, 4, false, false, true>, k1_resident<256, 32, 1024, 4, false, false, true>},  // one 148 KB workgroup per CU
+    {128, 16, 1024, k1_tiled2<128, 16, 1024>, k1_resident<128, 16, 1024>, k1_tiled2<128, 16, 1024, 1, true>, k1_resident<128, 16, 1024, 1, true>, 0, 1,
+     k1_tiled2<128, 16, 1024, 1, false, false, true>, k1_resident<128, 16, 1024, 1, false, false, true>},  // narrower tiles for mid-size lattices
+    {64, 32, 1024, k1_tiled2<64, 32, 1024>, k1_resident<64, 32, 1024>, k1_tiled2<64, 32, 1024, 1, true>, k1_resident<64, 32, 1024, 1, true>, 0, 1,
+     k1_tiled2<64, 32, 1024, 1, false, false, true>, k1_resident<64, 32, 1024, 1, false, false, true>},
+    {64, 16, 1024, k1_tiled2<64, 16, 1024>, k1_resident<64, 16, 1024>, k1_tiled2<64, 16, 1024, 1, true>, k1_resident<64, 16, 1024, 1, true>, 0, 1,
+     k1_tiled2<64, 16, 1024, 1, false, false, true>, k1_resident<64, 16, 1024, 1, false, false, true>},
+    {32, 16, 1024, k1_tiled2<32, 16, 1024>, k1_resident<32, 16, 1024>, k1_tiled2<32, 16, 1024, 1, true>, k1_resident<32, 16, 1024, 1, true>, 0, 1,
+     k1_tiled2<32, 16, 1024, 1, false, false, true>, k1_resident<32, 16, 1024, 1, false, false, true>},
     // nibble planes: 512 x 512 sites per CU (148 KB) -- 8192^2 tile-resident; 256 x 512, two workgroups per CU, for what is larger still
     {512, 32, 1024, k1_tiled2<512, 32, 1024, 4, false, true>, k1_resident<512, 32, 1024, 4, false, true>, k1_tiled2<512, 32, 1024, 4, true, true>,
-     k1_resident<512, 32, 1024, 4, true, true>, 1, 1},
-    {256, 32, 512, k1_tiled2<256, 32, 512, 4, false, true>, nullptr, k1_tiled2<256, 32, 512, 4, true, true>, nullptr, 1, 2},
+     k1_resident<512, 32, 1024, 4, true, true>, 1, 1, nullptr, nullptr},
+    {256, 32, 512, k1_tiled2<256, 32, 512, 4, false, true>, nullptr, k1_tiled2<256, 32, 512, 4, true, true>, nullptr, 1, 2, nullptr, nullptr},
 };
 constexpr int kNumVariants = sizeof(kVariants) / sizeof(kVariants[0]);
 
@@ -1091,6 +1153,14 @@ int ragged_shift(const tsu_ising2d* L, int WO) {
 
 // LDS of one workgroup of this shape when per_cu of them share a CU
 size_t lds_share(const TileVariant& tv) { return (size_t)(160 / tv.per_cu) * 1024; }
+
+// The quad threshold table (pair_thresholds) is 4.9 KB larger than the pair table.  Tile shapes, heights and cuts are planned with
+// the pair table's size, as before; a launch whose tile of TR rows leaves room for the larger table within the variant's LDS share
+// takes the quad kernels, every other launch the pair-table ones: no lattice gets another plan.  (The tallest byte tile planned,
+// 256 + 32 rows of variant 3, uses 158.4 of 160 KB with it.)
+bool quad_fits(const tsu_ising2d* L, const TileVariant& tv, int TR) {
+    return L->periodic && tv.kernel_q && tile_lds_bytes(tv, TR, true) <= lds_share(tv);
+}
 
 // CUs of the lattice's device (256 when unknown)
 int chip_cus(const tsu_ising2d* L) { return L->ctx->cus > 0 ? L->ctx->cus : 256; }
@@ -1384,20 +1454,20 @@ void print_resident_timeline(const long long* d_dbg, int ntiles, int tiles_x, in
 }
 
 // ---- tile-resident generations: every tile has its own workgroup on the chip for the whole call (fit_per_cu: the occupancy check's)
-int run_resident(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps, uint32_t sweep0, int fit_per_cu) {
+int run_resident(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps, uint32_t sweep0, int fit_per_cu, bool quad) {
     tsu_ctx* ctx = L->ctx;
     const TileVariant& tv = kVariants[c.v];
-    void (*const res_kern)(ResidentLaunch) = L->periodic ? tv.resident : tv.resident_open;
+    void (*const res_kern)(ResidentLaunch) = quad ? tv.resident_q : (L->periodic ? tv.resident : tv.resident_open);
     const int kmax = c.kmax, ntiles = p.tiles_x * c.tiles_y;
     const bool whole = L->wrap_rows || (!L->periodic && L->ghost == 0 && L->total_rows == L->rows);
-    const size_t lds_bytes = tile_lds_bytes(tv, c.tile_h + 4 * kmax);
+    const size_t lds_bytes = tile_lds_bytes(tv, c.tile_h + 4 * kmax, quad);
     const size_t xstride = (size_t)2 * (2 * kmax * tv.WO) + (size_t)2 * c.tile_h;  // TOP, BOTTOM, LEFT, RIGHT of colour plane 1
     const size_t xneed = (size_t)2 * ntiles * xstride;
     if (L->xbuf_cap < xneed * sizeof(uint64_t)) L->xsig = 0;  // fresh memory: cleared before its first use below
     TSU_HIP_TRY(ctx, ising2d_grow(L->d_xbuf, L->xbuf_cap, xneed * sizeof(uint64_t)));
     // strip layout of this call: the element numbering may only run on while it stays the same
     const uint64_t xsig = ((uint64_t)(c.v + 1) << 48) ^ ((uint64_t)ntiles << 28) ^ ((uint64_t)kmax << 20) ^ ((uint64_t)c.tile_h << 4) ^
-                          ((uint64_t)c.flex_ty << 36) ^ (uint64_t)p.open;
+                          ((uint64_t)c.flex_ty << 36) ^ (uint64_t)p.open ^ ((uint64_t)quad << 1);  // (quad: other flag and number bits)
     int* d_err = nullptr;
     if (const int rc = tsu_err_flag(ctx, L->h_err, &d_err); rc != TSU_OK) return rc;
     const int verbose = lattice_env("TSU_K1_VERBOSE", 0);
@@ -1446,8 +1516,9 @@ int run_resident(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps,
                 long long rg0;
                 any_wrap = tile_holds_wrap(P.t, ty, kmax, rg0);
             }
-            fprintf(stderr, "[tsu] k1_resident variant %d: %d tiles (%d per CU fit), %d generations of %d sweeps, %zu KB of strips, row wrap: %s\n",
-                    c.v, ntiles, fit_per_cu, P.r.n_gen, kmax, xneed * 8 / 1024, !any_wrap ? "none" : (wrap_by_mask(P.t) ? "mask" : "compare"));
+            fprintf(stderr, "[tsu] k1_resident variant %d: %d tiles (%d per CU fit), %d generations of %d sweeps, %zu KB of strips, thresholds: %s, row wrap: %s\n",
+                    c.v, ntiles, fit_per_cu, P.r.n_gen, kmax, xneed * 8 / 1024, quad ? "quad table" : (L->periodic ? "pair table" : "v_perm"),
+                    !any_wrap ? "none" : (wrap_by_mask(P.t) ? "mask" : "compare"));
         }
         {
             const int rcx = tsu_grid_exclusive_begin(ctx);
@@ -1478,8 +1549,8 @@ int run_resident(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps,
 int run_generations(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_sweeps, uint32_t sweep0, int part) {
     tsu_ctx* ctx = L->ctx;
     const TileVariant& tv = kVariants[c.v];
-    void (*const kern)(TiledParams) = L->periodic ? tv.kernel : tv.open;
     const bool slab = !(L->wrap_rows || (!L->periodic && L->ghost == 0 && L->total_rows == L->rows));
+    const int verbose = lattice_env("TSU_K1_VERBOSE", 0);
     for (int done = 0; done < n_sweeps;) {
         const int k = n_sweeps - done < c.kmax ? n_sweeps - done : c.kmax;
         p.k = k;
@@ -1487,7 +1558,13 @@ int run_generations(tsu_ising2d* L, const CallPlan& c, TiledParams p, int n_swee
         p.src = L->alloc[L->cur] + (size_t)L->ghost * L->pitch;
         p.dst = L->alloc[L->cur ^ 1] + (size_t)L->ghost * L->pitch;
         const int tiles_y = launch_tiles(L, tv, k, n_sweeps - done, part, slab, p);
-        const size_t lds_bytes = tile_lds_bytes(tv, p.tile_h + 4 * k);
+        const bool quad = quad_fits(L, tv, p.tile_h + 4 * k);  // (after launch_tiles: the tile height is the pair table's)
+        void (*const kern)(TiledParams) = quad ? tv.kernel_q : (L->periodic ? tv.kernel : tv.open);
+        if (quad) TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)kern, 160 * 1024));
+        const size_t lds_bytes = tile_lds_bytes(tv, p.tile_h + 4 * k, quad);
+        if (verbose)
+            fprintf(stderr, "[tsu] k1_tiled2 variant %d: %d tile rows of %d, %d sweeps, thresholds: %s\n", c.v, tiles_y, p.tile_h, k,
+                    quad ? "quad table" : (L->periodic ? "pair table" : "v_perm"));
         // tile rows 0 and tiles_y-1 read ghost rows (2k <= H); the others only read owned rows
         int n_ty = tiles_y;
         p.ty_first = 0;
@@ -1569,13 +1646,16 @@ int tsu_ising2d_tiled_sweep(tsu_ising2d* L, int n_sweeps, uint64_t seed, uint32_
     p.open = L->periodic ? 0 : 1;
     TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)(L->periodic ? tv.kernel : tv.open), 160 * 1024));
     if (c.resident) {
-        void (*const res_kern)(ResidentLaunch) = L->periodic ? tv.resident : tv.resident_open;
-        TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)res_kern, 160 * 1024));
-        int fit_per_cu = 0;
-        // (occupancy for the standard tile height; a stretched slab tile was checked against the variant's LDS share)
-        TSU_HIP_TRY(ctx, tsu_func_blocks_per_cu(ctx, (const void*)res_kern, tv.threads, tile_lds_bytes(tv, (c.flex_ty > 0 ? c.tile_h : tv.H) + 4 * KMAX),
-                                                &fit_per_cu));
-        if ((long long)p.tiles_x * c.tiles_y <= (long long)fit_per_cu * ctx->cus) return run_resident(L, c, p, n_sweeps, sweep0, fit_per_cu);
+        // the quad kernel first, where its table fits beside the planned tile and the chip still holds every tile; else the planned form
+        for (int quad = quad_fits(L, tv, c.tile_h + 4 * c.kmax) ? 1 : 0; quad >= 0; --quad) {
+            void (*const res_kern)(ResidentLaunch) = quad ? tv.resident_q : (L->periodic ? tv.resident : tv.resident_open);
+            TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)res_kern, 160 * 1024));
+            int fit_per_cu = 0;
+            // (occupancy for the standard tile height; a stretched slab tile was checked against the variant's LDS share)
+            TSU_HIP_TRY(ctx, tsu_func_blocks_per_cu(ctx, (const void*)res_kern, tv.threads,
+                                                    tile_lds_bytes(tv, (c.flex_ty > 0 ? c.tile_h : tv.H) + 4 * KMAX, quad != 0), &fit_per_cu));
+            if ((long long)p.tiles_x * c.tiles_y <= (long long)fit_per_cu * ctx->cus) return run_resident(L, c, p, n_sweeps, sweep0, fit_per_cu, quad != 0);
+        }
     }
     return run_generations(L, c, p, n_sweeps, sweep0, part);
 }
