@@ -399,6 +399,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * prototypes are _hip.MULTISPIN_QUENCH_SIGNATURES in Python. */
 #include "tsu_hip_multispin_quench.h"
 
+/* K6 / K8: cluster-size records of the Swendsen-Wang steps, the exact integers behind the improved estimators
+ * (tsu_isingNd_cluster_measure / _cluster_record): declared in tsu_hip_cluster_measure.h, which this header includes; its prototypes
+ * are _hip.CLUSTER_MEASURE_SIGNATURES in Python. */
+#include "tsu_hip_cluster_measure.h"
+
 /* ------------------------------------------------------------------ multi-GPU: RCCL below the ABI
  * One process per GPU.  A lattice that does not fit (or should not be swept by) one GPU is cut into row slabs
  * (tsu_ising2d_create_slab); these entry points refresh the ghost rows from the neighbouring ranks with RCCL send/recv over

@@ -32,14 +32,23 @@ constexpr int kLocalThreads = 256;
 using Item = SwItem<SwUniformBonds>;
 using Params = SwParams<SwUniformBonds>;
 
-__global__ __launch_bounds__(kSwMaxThreads) void k6_small(const Item* __restrict__ items, Item one, SwGeom g, int n_steps, int* err) {
+// Rec: nothing (k6_small<>: the plain kernel, its arguments and code as they always were) or one SwRecOut (the measured
+// instantiation of tsu_hip_cluster_measure.h: one more dword of LDS a site for the roots' counts, a row per step)
+template <class... Rec>
+__global__ __launch_bounds__(kSwMaxThreads) void k6_small(const Item* __restrict__ items, Item one, SwGeom g, int n_steps, int* err, Rec... rec) {
+    constexpr bool MEAS = sizeof...(Rec) != 0;
     extern __shared__ int s_lab[];
     __shared__ int s_bad;
     const Item& it = items ? items[blockIdx.x] : one;
     constexpr int WG = __HIP_MEMORY_SCOPE_WORKGROUP;
     const int rows = g.rows, cols = g.cols, periodic = g.pr;
     const int n = rows * cols, tid = threadIdx.x, nt = blockDim.x;
-    int8_t* const s_spin = reinterpret_cast<int8_t*>(s_lab + n);
+    int8_t* const s_spin = reinterpret_cast<int8_t*>(s_lab + (MEAS ? 2 : 1) * n);
+    unsigned* const s_cnt = reinterpret_cast<unsigned*>(s_lab + n);  // MEAS only
+    unsigned long long* const s_row = sw_small_scratch<MEAS>();
+    unsigned* const s_fz = MEAS ? reinterpret_cast<unsigned*>(s_row + 6) : nullptr;
+    if constexpr (MEAS)
+        if (tid < 7) s_row[tid] = 0;
     if (tid == 0) s_bad = 0;
     for (int i = tid; i < n; i += nt) {
         const int r = i / cols, c = i - r * cols;
@@ -48,7 +57,10 @@ __global__ __launch_bounds__(kSwMaxThreads) void k6_small(const Item* __restrict
     const int hc = (cols + 1) >> 1, npairs = rows * hc;
     for (int s = 0; s < n_steps; ++s) {
         const uint32_t t = it.k.t + (uint32_t)s;
-        for (int i = tid; i < n; i += nt) s_lab[i] = i;
+        for (int i = tid; i < n; i += nt) {
+            s_lab[i] = i;
+            if constexpr (MEAS) s_cnt[i] = 0;
+        }
         __syncthreads();
         int budget = kBudget;
         for (int p = tid; p < npairs; p += nt) {
@@ -72,11 +84,13 @@ __global__ __launch_bounds__(kSwMaxThreads) void k6_small(const Item* __restrict
             budget = kBudget;
             const int root = uf_find<false, WG>(s_lab, i, budget);
             if (budget < 0) s_bad = 1;
+            if constexpr (MEAS) sw_tally(s_cnt, s_fz, budget >= 0, root, s_spin[i]);
             const int rr = root / cols, rc = root - rr * cols;
             if (flip_bit(rr, rc, t, it.k.tag_flip, it.k.k0, it.k.k1)) s_spin[i] = (int8_t)-s_spin[i];
         }
         __syncthreads();
         if (s_bad) break;
+        if constexpr (MEAS) sw_small_row(s_lab, s_cnt, s_fz, s_row, n, sw_rec_rows(rec...) + 8 * (long long)s);
     }
     if (s_bad) {
         if (tid == 0) raise_err(err);
@@ -169,7 +183,8 @@ struct K6 {
     };
     static constexpr const char* who = "ising2d_cluster";
     static constexpr bool refuse_twice = false;
-    static constexpr auto small = k6_small;
+    static constexpr auto small = k6_small<>;
+    static constexpr auto small_measured = k6_small<SwRecOut>;
     static constexpr auto local = k6_local;
     static constexpr auto merge = k6_merge;
     static constexpr auto resolve = k6_resolve;
@@ -241,6 +256,16 @@ int tsu_ising2d_cluster_launch_count(tsu_ising2d* L, uint64_t* n) {
     if (!L || !n) return TSU_E_INVALID;
     *n = L->sw.launches;
     return TSU_OK;
+}
+
+int tsu_ising2d_cluster_measure(tsu_ising2d* L, int on) {
+    TSU_ENTER(L ? L->ctx : nullptr);
+    return sw_measure<K6>(L, on);
+}
+
+int tsu_ising2d_cluster_record(tsu_ising2d* L, int64_t* rows, int max_rows, int* n_rows) {
+    TSU_ENTER(L ? L->ctx : nullptr);
+    return sw_record<K6>(L, rows, max_rows, n_rows);
 }
 
 }  // extern "C"

@@ -52,8 +52,11 @@ namespace {
 using Item = SwItem<SwStoredBonds>;
 using Params = SwParams<SwStoredBonds>;
 
-template <bool GHOST>
-__global__ __launch_bounds__(kSwMaxThreads) void k8_sw_small(const Item* __restrict__ items, Item one, SwGeom g, int n_steps, int* err) {
+// Rec: nothing (k8_sw_small<GHOST>: the plain kernel, its arguments and code as they always were) or one SwRecOut (the measured
+// instantiation of tsu_hip_cluster_measure.h: one more dword of LDS a site for the roots' counts, a row per step)
+template <bool GHOST, class... Rec>
+__global__ __launch_bounds__(kSwMaxThreads) void k8_sw_small(const Item* __restrict__ items, Item one, SwGeom g, int n_steps, int* err, Rec... rec) {
+    constexpr bool MEAS = sizeof...(Rec) != 0;
     extern __shared__ int s_lab[];
     __shared__ int s_bad;
     const Item& it = items ? items[blockIdx.x] : one;
@@ -62,7 +65,12 @@ __global__ __launch_bounds__(kSwMaxThreads) void k8_sw_small(const Item* __restr
     const int depth = g.depth, rows = g.rows, cols = g.cols, pz = g.pz, pr = g.pr, pc = g.pc;
     const long long pitch = g.pitch;
     const int nrows = depth * rows, n = nrows * cols, tid = threadIdx.x, nt = blockDim.x;
-    int8_t* const s_spin = reinterpret_cast<int8_t*>(s_lab + n);
+    int8_t* const s_spin = reinterpret_cast<int8_t*>(s_lab + (MEAS ? 2 : 1) * n);
+    unsigned* const s_cnt = reinterpret_cast<unsigned*>(s_lab + n);  // MEAS only
+    unsigned long long* const s_row = sw_small_scratch<MEAS>();
+    unsigned* const s_fz = MEAS ? reinterpret_cast<unsigned*>(s_row + 6) : nullptr;
+    if constexpr (MEAS)
+        if (tid < 7) s_row[tid] = 0;
     if (tid == 0) s_bad = 0;
     for (int i = tid; i < n; i += nt) {
         const int rho = i / cols, c = i - rho * cols;
@@ -71,7 +79,10 @@ __global__ __launch_bounds__(kSwMaxThreads) void k8_sw_small(const Item* __restr
     const int hc = (cols + 1) >> 1, npairs = nrows * hc;
     for (int s = 0; s < n_steps; ++s) {
         const uint32_t t = it.k.t + (uint32_t)s;
-        for (int i = tid; i < n; i += nt) s_lab[i] = i;
+        for (int i = tid; i < n; i += nt) {
+            s_lab[i] = i;
+            if constexpr (MEAS) s_cnt[i] = 0;
+        }
         __syncthreads();
         int budget = kBudget;
         for (int p = tid; p < npairs; p += nt) {
@@ -112,12 +123,14 @@ __global__ __launch_bounds__(kSwMaxThreads) void k8_sw_small(const Item* __restr
             budget = kBudget;
             const int root = uf_find<GHOST, WG>(s_lab, i, budget);
             if (budget < 0) s_bad = 1;
+            if constexpr (MEAS) sw_tally(s_cnt, s_fz, budget >= 0, root, s_spin[i]);
             if (GHOST && root < 0) continue;  // frozen: no coin
             const int rr = root / cols, rc = root - rr * cols;
             if (flip_bit(rr, rc, t, it.k.tag_flip, it.k.k0, it.k.k1)) s_spin[i] = (int8_t)-s_spin[i];
         }
         __syncthreads();
         if (s_bad) break;
+        if constexpr (MEAS) sw_small_row(s_lab, s_cnt, s_fz, s_row, n, sw_rec_rows(rec...) + 8 * (long long)s);
     }
     if (s_bad) {
         if (tid == 0) raise_err(err);
@@ -248,6 +261,7 @@ struct K8 {
     static constexpr const char* who = "ising3d_cluster";
     static constexpr bool refuse_twice = true;
     static constexpr auto small = k8_sw_small<GHOST>;
+    static constexpr auto small_measured = k8_sw_small<GHOST, SwRecOut>;
     static constexpr auto local = k8_sw_local<GHOST>;
     static constexpr auto merge = k8_sw_merge<GHOST>;
     static constexpr auto resolve = k8_sw_resolve<GHOST>;
@@ -361,6 +375,16 @@ int tsu_ising3d_cluster_launch_count(tsu_ising3d* L, uint64_t* n) {
     if (!L || !n) return TSU_E_INVALID;
     *n = L->sw.launches;
     return TSU_OK;
+}
+
+int tsu_ising3d_cluster_measure(tsu_ising3d* L, int on) {
+    TSU_ENTER(L ? L->ctx : nullptr);
+    return sw_measure<K8<false>>(L, on);
+}
+
+int tsu_ising3d_cluster_record(tsu_ising3d* L, int64_t* rows, int max_rows, int* n_rows) {
+    TSU_ENTER(L ? L->ctx : nullptr);
+    return sw_record<K8<false>>(L, rows, max_rows, n_rows);
 }
 
 }  // extern "C"

@@ -4,7 +4,7 @@
 //   Lattice, Bonds, Model      the handle (with ctx, h_err and a tsu_sw_scratch sw), the bond policy of sw_dev.h, the model
 //                              parameters of one call (K6: J and T; K8: T)
 //   who, refuse_twice          the prefix of every message; whether a batch refuses a lattice listed twice
-//   small, local, merge, resolve   the kernels
+//   small, local, merge, resolve   the kernels; small_measured: the one-workgroup kernel that also writes cluster-size records
 //   check_model(L, m)          the checks only this dimension has, made ahead of the counter checks
 //   check_err(L)               report (and clear) a flag an earlier call's kernel left
 //   geom(L), spins(L), bonds(L, m)   extents, pitch and wraps (DIM = 2: depth 1, pz 0); row 0; the policy's values
@@ -20,7 +20,7 @@
 
 namespace {
 
-constexpr int kSwSmallSites = 16384;  // one-workgroup route: at most this many sites (80 KB of LDS); also the largest tile
+constexpr int kSwSmallSites = 16384;  // one-workgroup route: at most this many sites (80 KB of LDS, 144 KB measured); also the largest tile
 constexpr int kSwMaxThreads = 1024;
 
 template <int DIM>
@@ -65,29 +65,58 @@ int sw_check_call(typename Tr::Lattice* L, const typename Tr::Model& m, int n_st
     return Tr::check_err(L);  // a cap that expired in an earlier call
 }
 
-// n lattices of one shape and boundary, one workgroup each, all steps in one launch
+// the record buffer of a measured call: n_steps rows, zeroed on the stream (a step whose cap expired leaves its row so)
+template <class Tr>
+int sw_prepare_record(typename Tr::Lattice* L, int n_steps) {
+    tsu_ctx* ctx = L->ctx;
+    const size_t bytes = (size_t)n_steps * TSU_CLUSTER_RECORD_WORDS * sizeof(int64_t);
+    TSU_HIP_TRY(ctx, ising2d_grow(L->sw.d_rec, L->sw.rec_cap, bytes));
+    TSU_HIP_TRY(ctx, hipMemsetAsync(L->sw.d_rec, 0, bytes, ctx->stream));
+    L->sw.rec_rows = n_steps;
+    return TSU_OK;
+}
+
+// n lattices of one shape and boundary, one workgroup each, all steps in one launch.  All of them agree on the measuring switch; on:
+// the measured instantiation (9 B of LDS a site instead of 5), every workgroup writing its lattice's rows
 template <class Tr>
 int sw_run_small(typename Tr::Lattice* const* lats, int n, const SwItem<typename Tr::Bonds>* items, int n_steps) {
     using Item = SwItem<typename Tr::Bonds>;
     typename Tr::Lattice* L0 = lats[0];
     tsu_ctx* ctx = L0->ctx;
     int* d_err = nullptr;
-    const int rc = tsu_err_flag(ctx, L0->h_err, &d_err);
+    int rc = tsu_err_flag(ctx, L0->h_err, &d_err);
     if (rc != TSU_OK) return rc;
+    const bool measure = L0->sw.measure != 0;
     const SwGeom g = Tr::geom(L0);
-    const size_t lds = (size_t)sw_sites<Tr::DIM>(g) * 5;
-    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)Tr::small, (int)lds));
+    const size_t lds = (size_t)sw_sites<Tr::DIM>(g) * (measure ? 9 : 5);
+    TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, measure ? (const void*)Tr::small_measured : (const void*)Tr::small, (int)lds));
+    SwRecOut rec = {nullptr, nullptr};
+    if (measure) {
+        for (int i = 0; i < n; ++i)
+            if ((rc = sw_prepare_record<Tr>(lats[i], n_steps)) != TSU_OK) return rc;
+        rec.rows_one = (long long*)L0->sw.d_rec;
+    }
     const Item* d_items = nullptr;
     if (n > 1) {
         const size_t bytes = (size_t)n * sizeof(Item);
         TSU_HIP_TRY(ctx, ising2d_grow(L0->sw.d_batch, L0->sw.batch_cap, bytes));
-        // the host array dies with this call: wait for the copy (a few KB); the launch itself stays asynchronous
+        std::vector<long long*> rows_of;
+        if (measure) {
+            for (int i = 0; i < n; ++i) rows_of.push_back((long long*)lats[i]->sw.d_rec);
+            TSU_HIP_TRY(ctx, ising2d_grow(L0->sw.d_recs, L0->sw.recs_cap, (size_t)n * sizeof(long long*)));
+            TSU_HIP_TRY(ctx, hipMemcpyAsync(L0->sw.d_recs, rows_of.data(), (size_t)n * sizeof(long long*), hipMemcpyHostToDevice, ctx->stream));
+            rec.rows_of = (long long* const*)L0->sw.d_recs;
+        }
+        // the host arrays die with this call: wait for the copies (a few KB); the launch itself stays asynchronous
         TSU_HIP_TRY(ctx, hipMemcpyAsync(L0->sw.d_batch, items, bytes, hipMemcpyHostToDevice, ctx->stream));
         TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         d_items = (const Item*)L0->sw.d_batch;
     }
     const int threads = sw_threads(sw_sites<Tr::DIM>(g) / g.cols * ((g.cols + 1) / 2));
-    hipLaunchKernelGGL(Tr::small, dim3((unsigned)n), dim3((unsigned)threads), lds, ctx->stream, d_items, items[0], g, n_steps, d_err);
+    if (measure)
+        hipLaunchKernelGGL(Tr::small_measured, dim3((unsigned)n), dim3((unsigned)threads), lds, ctx->stream, d_items, items[0], g, n_steps, d_err, rec);
+    else
+        hipLaunchKernelGGL(Tr::small, dim3((unsigned)n), dim3((unsigned)threads), lds, ctx->stream, d_items, items[0], g, n_steps, d_err);
     TSU_HIP_TRY(ctx, hipGetLastError());
     for (int i = 0; i < n; ++i) lats[i]->sw.launches += 1;
     return TSU_OK;
@@ -121,12 +150,36 @@ int sw_run_tiles(typename Tr::Lattice* L, const SwItem<typename Tr::Bonds>& it, 
     const unsigned local_threads = (unsigned)Tr::local_threads(g);
     const int quads = (g.cols + 3) / 4;
     const unsigned resolve_blocks = (unsigned)((sw_sites<Tr::DIM>(g) / g.cols * quads + 255) / 256);
+    // measuring (tsu_hip_cluster_measure.h): sw_meas_count between the local and the merge pass, sw_meas_fold (where there is a
+    // merge pass) and sw_meas_row after it; the unmeasured kernels and their launches are the same either way
+    const bool measure = L->sw.measure != 0;
+    SwMeasParams m = {};
+    unsigned meas_blocks = 0;
+    const size_t meas_lds = (size_t)g.tz * g.tr * g.tc * sizeof(unsigned);
+    if (measure) {
+        const long long sites = sw_sites<Tr::DIM>(g);
+        if ((rc = sw_prepare_record<Tr>(L, n_steps)) != TSU_OK) return rc;
+        TSU_HIP_TRY(ctx, ising2d_grow(L->sw.d_acc, L->sw.acc_cap, (size_t)(sites + 2) * sizeof(unsigned long long)));
+        TSU_HIP_TRY(ctx, hipMemsetAsync(L->sw.d_acc + sites, 0, 2 * sizeof(unsigned long long), ctx->stream));
+        TSU_HIP_TRY(ctx, tsu_func_allow_lds(ctx, (const void*)sw_meas_count<Tr::DIM>, (int)meas_lds));
+        m.s = p.s;
+        m.labels = p.labels;
+        m.acc = L->sw.d_acc;
+        m.sites = sites;
+        m.g = g;
+        m.err = p.err;
+        meas_blocks = (unsigned)((sites + 255) / 256 < 2048 ? (sites + 255) / 256 : 2048);
+    }
     for (int s = 0; s < n_steps; ++s) {
         p.k.t = it.k.t + (uint32_t)s;
+        if (measure) m.row = (unsigned long long*)L->sw.d_rec + (size_t)s * TSU_CLUSTER_RECORD_WORDS;
         hipLaunchKernelGGL(Tr::local, dim3((unsigned)n_tiles), dim3(local_threads), lds, ctx->stream, p);
+        if (measure) hipLaunchKernelGGL(sw_meas_count<Tr::DIM>, dim3((unsigned)n_tiles), dim3(256), meas_lds, ctx->stream, m);
         if (merge_lanes > 0) hipLaunchKernelGGL(Tr::merge, dim3((unsigned)((merge_lanes + 255) / 256)), dim3(256), 0, ctx->stream, p);
+        if (measure && merge_lanes > 0) hipLaunchKernelGGL(sw_meas_fold<Tr::DIM>, dim3(meas_blocks), dim3(256), 0, ctx->stream, m);
+        if (measure) hipLaunchKernelGGL(sw_meas_row<Tr::DIM>, dim3(meas_blocks), dim3(256), 0, ctx->stream, m);
         hipLaunchKernelGGL(Tr::resolve, dim3(resolve_blocks), dim3(256), 0, ctx->stream, p, quads);
-        L->sw.launches += merge_lanes > 0 ? 3 : 2;
+        L->sw.launches += (merge_lanes > 0 ? 3 : 2) + (measure ? (merge_lanes > 0 ? 3 : 2) : 0);
     }
     TSU_HIP_TRY(ctx, hipGetLastError());
     return TSU_OK;
@@ -141,7 +194,30 @@ int sw_sweep(typename Tr::Lattice* L, const typename Tr::Model& m, int n_steps, 
     return sw_small_route<Tr>(L) ? sw_run_small<Tr>(&L, 1, &it, n_steps) : sw_run_tiles<Tr>(L, it, n_steps);
 }
 
-// every lattice checked first; one launch if all of them take the one-workgroup route with one shape and boundary, else one by one.
+// the measuring switch of a handle, and the rows of its most recent measured call (tsu_hip_cluster_measure.h)
+template <class Tr>
+int sw_measure(typename Tr::Lattice* L, int on) {
+    if (!L) return TSU_E_INVALID;
+    L->sw.measure = on != 0;  // nothing is allocated before the next cluster call, nothing freed before the handle goes
+    return TSU_OK;
+}
+
+template <class Tr>
+int sw_record(typename Tr::Lattice* L, int64_t* rows, int max_rows, int* n_rows) {
+    if (!L) return TSU_E_INVALID;
+    tsu_ctx* ctx = L->ctx;
+    TSU_REQUIRE(ctx, n_rows && max_rows >= 0 && (rows || max_rows == 0), "%s_record: n_rows is NULL, max_rows negative or rows NULL", Tr::who);
+    TSU_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const int rc = Tr::check_err(L);
+    if (rc != TSU_OK) return rc;
+    *n_rows = L->sw.rec_rows;
+    const int n = L->sw.rec_rows < max_rows ? L->sw.rec_rows : max_rows;
+    if (n > 0) TSU_HIP_TRY(ctx, hipMemcpy(rows, L->sw.d_rec, (size_t)n * TSU_CLUSTER_RECORD_WORDS * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return TSU_OK;
+}
+
+// every lattice checked first; one launch if all of them take the one-workgroup route with one shape and boundary and agree on the
+// measuring switch, else one by one.
 // model_of(i): the Model of lattice i
 template <class Tr, class ModelOf>
 int sw_sweep_batch(typename Tr::Lattice* const* lats, int n_lats, int n_steps, ModelOf model_of, const uint64_t* seeds,
@@ -158,7 +234,7 @@ int sw_sweep_batch(typename Tr::Lattice* const* lats, int n_lats, int n_steps, M
         if (rc != TSU_OK) return rc;
         const SwGeom g = Tr::geom(L);
         one_launch = one_launch && sw_small_route<Tr>(L) && g.depth == a.depth && g.rows == a.rows && g.cols == a.cols && g.pz == a.pz &&
-                     g.pr == a.pr && g.pc == a.pc;
+                     g.pr == a.pr && g.pc == a.pc && (L->sw.measure != 0) == (lats[0]->sw.measure != 0);
     }
     if (n_steps == 0) return TSU_OK;
     if (one_launch) {

@@ -111,11 +111,23 @@ struct tsu_sw_scratch {
     void* d_batch;      // a batch's per-lattice items on the device (lives with the batch's first lattice)
     size_t batch_cap;
     unsigned long long launches;  // cluster-kernel launches so far
+    // cluster-size records (tsu_hip_cluster_measure.h): nothing is allocated until a cluster call runs with the switch on
+    int measure;        // the switch
+    int64_t* d_rec;     // 8 int64 words per step of the most recent measured call, zeroed per call
+    size_t rec_cap;
+    int rec_rows;       // rows of that call
+    unsigned long long* d_acc;  // multi-tile route: per-root (up, down) site counts, one packed 64-bit word a site
+    size_t acc_cap;
+    void* d_recs;       // a measured batch's per-lattice record pointers on the device (lives with the batch's first lattice)
+    size_t recs_cap;
 };
 
 static inline void tsu_sw_scratch_free(tsu_sw_scratch& s) {
     if (s.d_labels) (void)hipFree(s.d_labels);
     if (s.d_batch) (void)hipFree(s.d_batch);
+    if (s.d_rec) (void)hipFree(s.d_rec);
+    if (s.d_acc) (void)hipFree(s.d_acc);
+    if (s.d_recs) (void)hipFree(s.d_recs);
     s = tsu_sw_scratch{};
 }
 

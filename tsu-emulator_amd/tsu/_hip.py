@@ -316,6 +316,15 @@ MULTISPIN_QUENCH_SIGNATURES = {
     "tsu_msc_quench_run": (C.c_int, [_vp, C.c_int, _i32p, C.c_uint32, C.c_int, _i32p]),
     "tsu_msc_quench_history": (C.c_int, [_vp, C.c_int, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p, _i64p]),
 }
+# name -> (restype, argtypes): mirrors include/tsu_hip_cluster_measure.h (the header tsu_hip.h includes) one to one
+CLUSTER_MEASURE_SIGNATURES = {
+    "tsu_ising2d_cluster_measure": (C.c_int, [_vp, C.c_int]),
+    "tsu_ising3d_cluster_measure": (C.c_int, [_vp, C.c_int]),
+    "tsu_ising2d_cluster_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
+    "tsu_ising3d_cluster_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
+}
+CLUSTER_RECORD_WORDS = 8   # TSU_CLUSTER_RECORD_WORDS
+CLUSTER_RECORD_FIELDS = ("n_clusters", "largest", "sum_size2", "sum_m2", "sum_m4", "n_frozen", "m_frozen")
 MSC_SNAPSHOT_SLOTS = 8     # TSU_MSC_SNAPSHOT_SLOTS
 MSC_C4_MAX_AXIS = 16382    # TSU_MSC_C4_MAX_AXIS
 
@@ -340,7 +349,8 @@ def load_library():
                               + list(ENSEMBLE_SIGNATURES.items()) + list(SPARSE_BATCH_SIGNATURES.items())
                               + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())
                               + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())
-                              + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())):
+                              + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())
+                              + list(CLUSTER_MEASURE_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -496,6 +506,30 @@ def probe_screen(f32, a32, c32, ctx=None):
     return t, m
 
 
+def _cluster_record(lat, entry):
+    """The rows of a lattice's most recent measured cluster call as a dict of arrays over its steps (tsu_hip_cluster_measure.h):
+    int64 arrays, ``sum_m4`` an object array of Python ints joined from its two words."""
+    n = C.c_int(0)
+    lat.ctx.check(entry(lat.h, None, 0, C.byref(n)))
+    rows = np.zeros((n.value, CLUSTER_RECORD_WORDS), np.int64)
+    if n.value:
+        lat.ctx.check(entry(lat.h, _ptr(rows, _i64p), n.value, C.byref(n)))
+    return cluster_record_dict(rows)
+
+
+def cluster_record_dict(rows):
+    """(n_steps, 8) int64 rows -> the dict of ``cluster_record()``; the two words of ``sum_m4`` are read as unsigned."""
+    rows = np.asarray(rows, np.int64).reshape(-1, CLUSTER_RECORD_WORDS)
+    out = {"n_clusters": rows[:, 0].copy(), "largest": rows[:, 1].copy(), "sum_size2": rows[:, 2].copy(), "sum_m2": rows[:, 3].copy()}
+    m4 = np.empty(len(rows), object)
+    for i, (lo, hi) in enumerate(rows[:, 4:6].astype(np.uint64).tolist()):
+        m4[i] = (int(hi) << 64) | int(lo)
+    out["sum_m4"] = m4
+    out["n_frozen"] = rows[:, 6].copy()
+    out["m_frozen"] = rows[:, 7].copy()
+    return out
+
+
 def cluster_threshold(J, T):
     """Host helper of the library (no GPU needed): the Swendsen-Wang bond threshold floor(p 2^32), p = -expm1(-2|J|/T)."""
     lib = load_library()
@@ -609,6 +643,14 @@ class Lattice:
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_ising2d_cluster_launch_count(self.h, C.byref(n)))
         return n.value
+
+    def cluster_measure(self, on=True):
+        """The switch of the cluster-size records: while on, every cluster call records one row per step (same spins as off)."""
+        self.ctx.check(self.lib.tsu_ising2d_cluster_measure(self.h, 1 if on else 0))
+
+    def cluster_record(self):
+        """The rows of the most recent measured cluster call (synchronises): a dict of arrays over its steps."""
+        return _cluster_record(self, self.lib.tsu_ising2d_cluster_record)
 
     def set_disorder(self, J_right, J_down, h=None):
         """K7 quenched disorder: (rows, cols) arrays, rounded once to fp32 (h=None: zero field)."""
@@ -763,6 +805,14 @@ class Lattice3D:
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_ising3d_cluster_launch_count(self.h, C.byref(n)))
         return n.value
+
+    def cluster_measure(self, on=True):
+        """The switch of the cluster-size records: while on, every cluster call, zero-field or ghost, records one row per step."""
+        self.ctx.check(self.lib.tsu_ising3d_cluster_measure(self.h, 1 if on else 0))
+
+    def cluster_record(self):
+        """The rows of the most recent measured cluster call (synchronises): a dict of arrays over its steps."""
+        return _cluster_record(self, self.lib.tsu_ising3d_cluster_record)
 
 
 def msc_thresholds(T):

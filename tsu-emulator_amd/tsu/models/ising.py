@@ -441,6 +441,40 @@ def _check_cluster_model(external_field: float, bias_mode: str) -> None:
                                     "zero-field Ising measure)")
 
 
+def _set_cluster_measure(model, on: bool) -> None:
+    """Flip the handle's cluster-size record switch only when it changes (a host-side flag: no launch, no allocation)."""
+    if bool(on) != model._measuring:
+        model._lat.cluster_measure(bool(on))
+        model._measuring = bool(on)
+
+
+def _check_improved(improved: bool, algorithm: str) -> None:
+    if improved and algorithm == "gibbs":
+        raise _hip.UnsupportedError("improved=True needs the cluster decomposition of a Swendsen-Wang step: use "
+                                    "algorithm='swendsen_wang' (or 'swendsen_wang_ghost' on a 3-D lattice in a field)")
+
+
+def cluster_estimators(record: dict) -> dict:
+    """Improved estimators per step from a model's ``cluster_record()`` dict, float64 arrays from the exact integers (N is the
+    record's ``n_spins``):
+
+    ``m2`` = (sum_m2 + m_frozen^2) / N^2, whose mean is <M^2> / N^2 (the free clusters' signs average out given the bonds; the
+    frozen sites keep theirs); ``m4`` = (3 sum_m2^2 - 2 sum_m4) / N^4, whose mean is <M^4> / N^4 at zero field (NaN on a step
+    with frozen sites), computed in Python integers before the one division; ``m`` = m_frozen / N, whose mean is <M> / N with a
+    ghost spin (0 at zero field); ``mean_cluster_size`` = sum_size2 / N, the FK mean size of the free cluster of a site."""
+    N = int(record["n_spins"])
+    s2 = [int(v) for v in record["sum_m2"]]
+    s4 = [int(v) for v in record["sum_m4"]]
+    mf = [int(v) for v in record["m_frozen"]]
+    nf = [int(v) for v in record["n_frozen"]]
+    return {
+        "m2": np.array([(a + f * f) / N ** 2 for a, f in zip(s2, mf)], dtype=np.float64),
+        "m4": np.array([(3 * a * a - 2 * b) / N ** 4 if k == 0 else np.nan for a, b, k in zip(s2, s4, nf)], dtype=np.float64),
+        "m": np.array([f / N for f in mf], dtype=np.float64),
+        "mean_cluster_size": np.array([int(v) / N for v in record["sum_size2"]], dtype=np.float64),
+    }
+
+
 def _disorder_arrays(rows: int, cols: int, periodic: bool, coupling: float, external_field: float, bias_mode: str,
                      couplings, field):
     """Validate K7 disorder (before any device call) and round it once to fp32: (J_right, J_down, h or None)."""
@@ -588,6 +622,7 @@ class IsingModel2D:
             int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
         self.sweep_count = 0
         self.cluster_count = 0
+        self._measuring = False  # the handle's cluster-size record switch
         self._lat = _hip.Lattice(self.rows, self.cols, self.periodic)
         if initial == "random":
             self._lat.randomize(self.seed)
@@ -627,14 +662,25 @@ class IsingModel2D:
         self.sweep_count += int(n_sweeps)
         return self
 
-    def cluster_update(self, n_steps: int = 1) -> "IsingModel2D":
-        """n_steps Swendsen-Wang steps (K6); the heat-bath stream and ``sweep_count`` are not touched."""
+    def cluster_update(self, n_steps: int = 1, measure: bool = False) -> "IsingModel2D":
+        """n_steps Swendsen-Wang steps (K6); the heat-bath stream and ``sweep_count`` are not touched.  ``measure=True``: the same
+        spins, and one cluster-size row per step for :meth:`cluster_record`."""
         if self._disorder is not None:
             raise _hip.UnsupportedError("Swendsen-Wang cluster updates do not take a disordered lattice (couplings / field)")
         _check_cluster_model(self.external_field, self.bias_mode)
+        _set_cluster_measure(self, measure)
         self._lat.cluster_sweep(self.coupling, self.temperature, int(n_steps), self.seed, self.cluster_count)
         self.cluster_count += int(n_steps)
         return self
+
+    def cluster_record(self) -> dict:
+        """The cluster-size record of the last measured call (``cluster_update(measure=True)`` or a scan with ``improved=True``):
+        arrays over its steps, exact integers from the device: ``n_clusters``, ``largest``, ``sum_size2``, ``sum_m2`` (int64),
+        ``sum_m4`` (Python ints, it passes 2^64), ``n_frozen``, ``m_frozen`` (0 at zero field), and ``n_spins``.  Feed it to
+        :func:`cluster_estimators`."""
+        rec = self._lat.cluster_record()
+        rec["n_spins"] = self.n_spins
+        return rec
 
     def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000,
                     algorithm: str = "gibbs") -> "IsingModel2D":
@@ -726,7 +772,7 @@ def demonstrate_phase_transition(sizes: List[int] = [8, 16, 32], temperatures: O
 def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                      measure_every: int = 10, periodic: bool = True, seed: int = 0, bias_mode: str = "physical",
                      initial: str = "up", algorithm: str = "gibbs", *, couplings=None, field=None, replicas: int = 1,
-                     correlation: bool = False) -> dict:
+                     correlation: bool = False, improved: bool = False) -> dict:
     """GPU-resident form of :func:`demonstrate_phase_transition` (reference: ising.py:424-476) for lattices far
     beyond what a samples array can hold: one :class:`IsingModel2D` per temperature stays on the device, and
     |M|, E/N, chi = (<M^2> - <M>^2) N / T and C = (<E^2> - <E>^2) / (T^2 N) come from the device reductions
@@ -739,8 +785,12 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
     ``correlation=True`` (a periodic lattice): the result gains ``chi_k`` = <|F_d|^2> / N and ``xi`` (both ``(n_T, 2)``, per axis) and
     ``xi_over_L`` = the mean of xi_d / L_d, from the k_min modes F_d of the spins (``replicas=1``) or of the overlap field
     (``replicas=2``) taken with every measurement (:meth:`IsingModel2D.fourier_modes`).
+    ``improved=True`` (``algorithm="swendsen_wang"``): the measurement phase records the cluster sizes of its steps on the device
+    and the result gains the improved estimators of :func:`_improved_summary`, averaged over the rows of EVERY step of the
+    measurement phase, not only every ``measure_every``-th; all other keys keep their values bit for bit.
     """
     _check_algorithm(algorithm)
+    _check_improved(improved, algorithm)
     if algorithm == "swendsen_wang_ghost":
         _refuse_ghost_2d()
     if replicas not in (1, 2):
@@ -790,8 +840,13 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
     Ms, Es = np.zeros((nT, n_measure)), np.zeros((nT, n_measure))
     Qs = np.zeros((nT, n_measure))
     F2s = np.zeros((nT, n_measure, 2))
+    recs = [[] for _ in range(nT)]
+    for m in models if improved else ():  # every lattice of the batch, so that it keeps its one-launch route
+        _set_cluster_measure(m, True)
     for j in range(n_measure if models else 0):
         advance(int(measure_every))
+        for i in range(nT if improved else 0):
+            recs[i].append(models[i].cluster_record())
         for i, (sum_s, sum_bonds) in enumerate(_hip.observables_batch([m._lat for m in models[:nT]])):
             Ms[i, j] = sum_s / models[i].n_spins
             if disorder is not None:
@@ -804,6 +859,8 @@ def temperature_scan(size, temperatures, coupling: float = 1.0, n_equilibrate: i
                 F2s[i, j] = np.abs(models[i].fourier_modes(models[nT + i] if replicas == 2 else None)) ** 2
     del models
     out = _scan_summary(out, rows * cols, Ms, Es, Qs if replicas == 2 else None)
+    if improved:
+        _improved_summary(out, rows * cols, recs, ghost=False)
     if correlation:
         N = rows * cols
         f2 = np.mean((Qs if replicas == 2 else Ms) ** 2, axis=1) * float(N) ** 2
@@ -824,6 +881,37 @@ def _scan_summary(out: dict, N: int, Ms, Es, Qs=None) -> dict:
         out["overlap_sq"] = q2
         with np.errstate(divide="ignore", invalid="ignore"):
             out["binder"] = 0.5 * (3.0 - np.mean(Qs ** 4, axis=1) / q2 ** 2)
+    return out
+
+
+def _improved_summary(out: dict, N: int, recs, ghost: bool) -> dict:
+    """The scans' improved keys from recs[i], the cluster records of temperature i (one per measurement, each with the rows of
+    ``measure_every`` steps; the means run over all rows): ``m2_improved`` = <m2>; ``chi_improved`` = N m2_improved / T at zero
+    field, N (m2_improved - m_improved^2) / T with a ghost; ``binder_improved`` = (3 - <m4> / <m2>^2) / 2, zero field only;
+    ``m_improved`` = <m>, ghost only (m2, m4, m: :func:`cluster_estimators`); ``mean_cluster_size`` = <sum |C|^2> / N;
+    ``largest_cluster`` = <largest> / N, the fraction of the lattice in the largest free cluster; ``n_clusters`` = <n_clusters>."""
+    nT = len(out["temperatures"])
+    keys = ["m2_improved", "chi_improved", "mean_cluster_size", "largest_cluster", "n_clusters"] + (["m_improved"] if ghost else ["binder_improved"])
+    for k in keys:
+        out[k] = np.full(nT, np.nan)
+    for i, T in enumerate(out["temperatures"]):
+        if not recs[i]:
+            continue
+        rec = {k: np.concatenate([r[k] for r in recs[i]]) for k in _hip.CLUSTER_RECORD_FIELDS}
+        rec["n_spins"] = N
+        est = cluster_estimators(rec)
+        m2 = float(np.mean(est["m2"]))
+        out["m2_improved"][i] = m2
+        if ghost:
+            m = float(np.mean(est["m"]))
+            out["m_improved"][i] = m
+            out["chi_improved"][i] = N * (m2 - m * m) / T
+        else:
+            out["chi_improved"][i] = N * m2 / T
+            out["binder_improved"][i] = 0.5 * (3.0 - float(np.mean(est["m4"])) / m2 ** 2)
+        out["mean_cluster_size"][i] = float(np.mean(est["mean_cluster_size"]))
+        out["largest_cluster"][i] = float(np.mean(rec["largest"])) / N
+        out["n_clusters"][i] = float(np.mean(rec["n_clusters"]))
     return out
 
 
@@ -924,6 +1012,7 @@ class IsingModel3D:
             int(np.random.randint(0, 2 ** 31 - 1)) | (int(np.random.randint(0, 2 ** 31 - 1)) << 31))
         self.sweep_count = 0
         self.cluster_count = 0
+        self._measuring = False  # the handle's cluster-size record switch
         self._lat = _hip.Lattice3D(self.depth, self.rows, self.cols, self.periodic)
         if initial == "random":
             self._lat.randomize(self.seed)
@@ -949,21 +1038,32 @@ class IsingModel3D:
         self.sweep_count += int(n_sweeps)
         return self
 
-    def cluster_update(self, n_steps: int = 1) -> "IsingModel3D":
-        """n_steps Swendsen-Wang steps on the stored couplings; the heat-bath stream and ``sweep_count`` are not touched."""
+    def cluster_update(self, n_steps: int = 1, measure: bool = False) -> "IsingModel3D":
+        """n_steps Swendsen-Wang steps on the stored couplings; the heat-bath stream and ``sweep_count`` are not touched.
+        ``measure=True``: the same spins, and one cluster-size row per step for :meth:`cluster_record`."""
         _check_cluster_field_3d(self._disorder[3])
+        _set_cluster_measure(self, measure)
         self._lat.cluster_sweep(self.temperature, int(n_steps), self.seed, self.cluster_count)
         self.cluster_count += int(n_steps)
         return self
 
-    def ghost_cluster_update(self, n_steps: int = 1) -> "IsingModel3D":
+    def ghost_cluster_update(self, n_steps: int = 1, measure: bool = False) -> "IsingModel3D":
         """n_steps ghost-spin Swendsen-Wang steps on the stored couplings and field: every site is also bonded to a ghost spin
         fixed at +1 with coupling h_i, and a cluster that reaches the ghost does not flip.  Samples exp(-E / T) / Z of
         :meth:`energy`; with zero field these are the steps of :meth:`cluster_update`.  Advances ``cluster_count``, the counter
-        the two kinds of cluster step share."""
+        the two kinds of cluster step share.  ``measure=True``: the same spins, and one cluster-size row per step for
+        :meth:`cluster_record` (the sites frozen to the ghost in ``n_frozen`` / ``m_frozen``)."""
+        _set_cluster_measure(self, measure)
         self._lat.cluster_sweep_field(self.temperature, int(n_steps), self.seed, self.cluster_count)
         self.cluster_count += int(n_steps)
         return self
+
+    def cluster_record(self) -> dict:
+        """The cluster-size record of the last measured call (:meth:`IsingModel2D.cluster_record`); with ghost-spin steps
+        ``n_frozen`` sites of total spin ``m_frozen`` hang on the ghost and the other words count the free clusters only."""
+        rec = self._lat.cluster_record()
+        rec["n_spins"] = self.n_spins
+        return rec
 
     def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000,
                     algorithm: str = "gibbs") -> "IsingModel3D":
@@ -1025,7 +1125,7 @@ class IsingModel3D:
 def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
                         measure_every: int = 10, periodic=True, seed: int = 0, initial: str = "up", algorithm: str = "gibbs", *,
                         couplings=None, field=None, replicas: int = 1, correlation: bool = False,
-                        external_field: float = 0.0) -> dict:
+                        external_field: float = 0.0, improved: bool = False) -> dict:
     """:func:`temperature_scan` for a cubic lattice (K8): one :class:`IsingModel3D` per temperature stays on the device and
     |M|, E/N, chi and C come from the device reductions.  ``couplings`` / ``field``: the same quenched disorder at every
     temperature.  Model i of replica k has seed ``seed + k len(temperatures) + i``.  ``replicas=2``: the result gains
@@ -1036,8 +1136,13 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
     ``field=`` / ``external_field=``.
     ``correlation=True`` (at least one periodic axis): the result gains ``chi_k`` = <|F_d|^2> / N and ``xi`` (both ``(n_T, 3)``, NaN on
     an open axis) and ``xi_over_L`` = the mean of xi_d / L_d over the periodic axes, from the k_min modes of the spins
-    (``replicas=1``) or of the overlap field (``replicas=2``) taken with every measurement."""
+    (``replicas=1``) or of the overlap field (``replicas=2``) taken with every measurement.
+    ``improved=True`` (``algorithm="swendsen_wang"`` or ``"swendsen_wang_ghost"``): the measurement phase records the cluster
+    sizes of its steps on the device and the result gains the improved estimators of :func:`_improved_summary`, averaged over the
+    rows of EVERY step of the measurement phase, not only every ``measure_every``-th; all other keys keep their values bit for
+    bit."""
     _check_algorithm(algorithm)
+    _check_improved(improved, algorithm)
     if replicas not in (1, 2):
         raise ValueError("replicas must be 1 or 2")
     temperatures = np.asarray(temperatures, dtype=float)
@@ -1072,8 +1177,13 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
         advance(int(n_equilibrate))
     Ms, Es, Qs = np.zeros((nT, n_measure)), np.zeros((nT, n_measure)), np.zeros((nT, n_measure))
     F2s = np.zeros((nT, n_measure, 3))
+    recs = [[] for _ in range(nT)]
+    for m in models if improved else ():  # every lattice of the batch, so that it keeps its one-launch route
+        _set_cluster_measure(m, True)
     for j in range(n_measure if models else 0):
         advance(int(measure_every))
+        for i in range(nT if improved else 0):
+            recs[i].append(models[i].cluster_record())
         for i in range(nT):
             Ms[i, j] = models[i].magnetization()
             Es[i, j] = models[i].energy()
@@ -1084,6 +1194,8 @@ def temperature_scan_3d(size, temperatures, coupling: float = 1.0, n_equilibrate
     del models
     N = shape[0] * shape[1] * shape[2]
     out = _scan_summary(out, N, Ms, Es, Qs if replicas == 2 else None)
+    if improved:
+        _improved_summary(out, N, recs, ghost=algorithm == "swendsen_wang_ghost")
     if correlation:
         f2 = np.mean((Qs if replicas == 2 else Ms) ** 2, axis=1) * float(N) ** 2
         _correlation_summary(out, N, shape, _hip.periodic_axes(periodic), f2, np.mean(F2s, axis=1))
