@@ -399,6 +399,10 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * prototypes are _hip.MULTISPIN_QUENCH_SIGNATURES in Python. */
 #include "tsu_hip_multispin_quench.h"
 
+/* K10: q-state Potts lattices in 2-D on a handle of their own, heat-bath sweeps, Swendsen-Wang steps and exact integer observables
+ * (tsu_potts2d_*): declared in tsu_hip_potts.h, which this header includes; its prototypes are _hip.POTTS_SIGNATURES in Python. */
+#include "tsu_hip_potts.h"
+
 /* K6 / K8: cluster-size records of the Swendsen-Wang steps, the exact integers behind the improved estimators
  * (tsu_isingNd_cluster_measure / _cluster_record): declared in tsu_hip_cluster_measure.h, which this header includes; its prototypes
  * are _hip.CLUSTER_MEASURE_SIGNATURES in Python. */

@@ -38,6 +38,7 @@ from .models import (  # noqa: F401
     MultispinTempering3D,
     PopulationAnnealing,
     PopulationAnnealing3D,
+    PottsModel2D,
     cluster_estimators,
     demonstrate_phase_transition,
     edwards_anderson_samples,
@@ -45,6 +46,7 @@ from .models import (  # noqa: F401
     multispin_quench_3d,
     multispin_scan_3d,
     multispin_tempering_scan_3d,
+    potts_temperature_scan,
     temperature_scan_3d,
     tempering_ensemble_scan,
     tempering_ensemble_scan_3d,
@@ -57,7 +59,7 @@ __all__ = [
     "GibbsSampler", "GibbsConfig", "HardwareEmulator",
     "IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "demonstrate_phase_transition",
     "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d", "cluster_estimators",
-    "PopulationAnnealing","PopulationAnnealing3D",
+    "PopulationAnnealing","PopulationAnnealing3D", "PottsModel2D", "potts_temperature_scan",
     "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
     "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d",
     "GraphTempering", "multispin_quench_3d", "MultispinTempering3D", "multispin_tempering_scan_3d",

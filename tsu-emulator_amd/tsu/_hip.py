@@ -323,6 +323,28 @@ CLUSTER_MEASURE_SIGNATURES = {
     "tsu_ising2d_cluster_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
     "tsu_ising3d_cluster_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
 }
+# name -> (restype, argtypes): mirrors include/tsu_hip_potts.h (the header tsu_hip.h includes) one to one
+POTTS_SIGNATURES = {
+    "tsu_potts2d_check_model": (C.c_int, [C.c_int, C.c_double, _f64p, C.c_double, _f64p]),
+    "tsu_potts2d_cluster_threshold": (C.c_int, [C.c_double, C.c_double, _u64p]),
+    "tsu_potts2d_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "tsu_potts2d_destroy": (C.c_int, [_vp]),
+    "tsu_potts2d_set_model": (C.c_int, [_vp, C.c_double, _f64p]),
+    "tsu_potts2d_set_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_potts2d_get_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_potts2d_fill": (C.c_int, [_vp, C.c_int]),
+    "tsu_potts2d_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts2d_cluster_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts2d_route": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
+    "tsu_potts2d_measure": (C.c_int, [_vp, _i64p]),
+    "tsu_potts2d_run": (C.c_int, [_vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts2d_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
+    "tsu_potts2d_launch_count": (C.c_int, [_vp, _u64p]),
+}
+POTTS_RECORD_WORDS = 9     # TSU_POTTS_RECORD_WORDS
+POTTS_MAX_Q = 8            # TSU_POTTS_MAX_Q
+POTTS_HEAT_BATH, POTTS_SWENDSEN_WANG = 0, 1
+POTTS_ROUTES = ("k10_small", "k10_sweep", "k10_sw_small", "k10_sw_tiles")  # TSU_POTTS_ROUTE_*
 CLUSTER_RECORD_WORDS = 8   # TSU_CLUSTER_RECORD_WORDS
 CLUSTER_RECORD_FIELDS = ("n_clusters", "largest", "sum_size2", "sum_m2", "sum_m4", "n_frozen", "m_frozen")
 MSC_SNAPSHOT_SLOTS = 8     # TSU_MSC_SNAPSHOT_SLOTS
@@ -350,7 +372,7 @@ def load_library():
                               + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())
                               + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())
                               + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())
-                              + list(CLUSTER_MEASURE_SIGNATURES.items())):
+                              + list(CLUSTER_MEASURE_SIGNATURES.items()) + list(POTTS_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -696,6 +718,107 @@ class Lattice:
         pr, pc = np.zeros(self.rows, np.int64), np.zeros(self.cols, np.int64)
         self.ctx.check(self.lib.tsu_ising2d_profiles(self.h, None if other is None else other.h, _ptr(pr, _i64p), _ptr(pc, _i64p)))
         return pr, pc
+
+
+def potts_tables(q, J, h, T):
+    """Host helper of the library (no GPU needed): (E[0 .. 4], F[0 .. q - 1]) of the Potts heat-bath rule, or ValueError with the
+    model refused (tsu_potts2d_check_model)."""
+    lib = load_library()
+    hh = None if h is None else np.ascontiguousarray(h, dtype=np.float64)
+    if hh is not None and hh.shape != (int(q),) and 2 <= int(q) <= POTTS_MAX_Q:
+        raise ValueError(f"h must hold q = {int(q)} values")
+    t = np.zeros(5 + POTTS_MAX_Q, np.float64)
+    rc = lib.tsu_potts2d_check_model(int(q), float(J), None if hh is None else _ptr(hh, _f64p), float(T), _ptr(t, _f64p))
+    if rc != TSU_OK:
+        raise ValueError("the Potts model (q, J, h, T) is refused: q outside 2 .. 8, a non-finite value, T <= 0 or "
+                         "(4 |J| + max h - min h) / T > 600")
+    return t[:5].copy(), t[5:5 + int(q)].copy()
+
+
+def potts_cluster_threshold(J, T):
+    """Host helper of the library (no GPU needed): the Potts bond threshold floor(-expm1(-J / T) 2^32)."""
+    lib = load_library()
+    t = C.c_uint64(0)
+    if lib.tsu_potts2d_cluster_threshold(float(J), float(T), C.byref(t)) != TSU_OK:
+        raise ValueError("the Potts cluster threshold needs finite J > 0 and T > 0")
+    return t.value
+
+
+class PottsLattice:
+    """tsu_potts2d handle: a rows x cols lattice of colours 0 .. q - 1 (int8) on the GPU (K10)."""
+
+    def __init__(self, rows, cols, q, periodic=True, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.rows, self.cols, self.q, self.periodic = int(rows), int(cols), int(q), bool(periodic)
+        h = _vp()
+        self.ctx.check(self.lib.tsu_potts2d_create(self.ctx.h, self.rows, self.cols, self.q, int(self.periodic), C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_potts2d_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def set_model(self, J, h=None):
+        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float64)
+        if hh is not None and hh.shape != (self.q,):
+            raise ValueError(f"h must hold q = {self.q} values")
+        self.ctx.check(self.lib.tsu_potts2d_set_model(self.h, float(J), None if hh is None else _ptr(hh, _f64p)))
+
+    def set_spins(self, colours):
+        s = np.ascontiguousarray(colours, dtype=np.int8)
+        if s.size != self.rows * self.cols:
+            raise ValueError(f"colours must hold {self.rows} x {self.cols} values")
+        self.ctx.check(self.lib.tsu_potts2d_set_spins(self.h, _ptr(s, _i8p)))
+
+    def get_spins(self):
+        out = np.empty((self.rows, self.cols), dtype=np.int8)
+        self.ctx.check(self.lib.tsu_potts2d_get_spins(self.h, _ptr(out, _i8p)))
+        return out
+
+    def fill(self, colour):
+        self.ctx.check(self.lib.tsu_potts2d_fill(self.h, int(colour)))
+
+    def sweep(self, T, n_sweeps, seed, sweep0=0, replica=0):
+        self.ctx.check(self.lib.tsu_potts2d_sweep(self.h, float(T), int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
+
+    def cluster_sweep(self, T, n_steps, seed, step0=0, replica=0):
+        self.ctx.check(self.lib.tsu_potts2d_cluster_sweep(self.h, float(T), int(n_steps), _seed(seed), _counter("step0", step0),
+                                                          _replica(replica)))
+
+    def route(self, algorithm=POTTS_HEAT_BATH):
+        r = C.c_int(-1)
+        self.ctx.check(self.lib.tsu_potts2d_route(self.h, int(algorithm), C.byref(r)))
+        return POTTS_ROUTES[r.value]
+
+    def measure(self):
+        """(n_eq, N_0 .. N_{q-1}) of the current state as exact integers (synchronises)."""
+        row = np.zeros(POTTS_RECORD_WORDS, np.int64)
+        self.ctx.check(self.lib.tsu_potts2d_measure(self.h, _ptr(row, _i64p)))
+        return int(row[0]), row[1:1 + self.q].copy()
+
+    def run(self, T, n_meas, sweeps_between, algorithm, seed, counter0=0, replica=0):
+        self.ctx.check(self.lib.tsu_potts2d_run(self.h, float(T), int(n_meas), int(sweeps_between), int(algorithm), _seed(seed),
+                                                _counter("counter0", counter0), _replica(replica)))
+
+    def record(self):
+        """The rows of the most recent run (synchronises): (n_meas, 9) int64, n_eq then N_0 .. N_7."""
+        n = C.c_int(0)
+        self.ctx.check(self.lib.tsu_potts2d_record(self.h, None, 0, C.byref(n)))
+        rows = np.zeros((n.value, POTTS_RECORD_WORDS), np.int64)
+        if n.value:
+            self.ctx.check(self.lib.tsu_potts2d_record(self.h, _ptr(rows, _i64p), n.value, C.byref(n)))
+        return rows
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_potts2d_launch_count(self.h, C.byref(n)))
+        return n.value
 
 
 def periodic_axes(periodic):

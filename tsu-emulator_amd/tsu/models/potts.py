@@ -1,0 +1,181 @@
+"""q-state Potts lattices in 2-D (K10): the categorical counterpart of :class:`IsingModel2D`.
+
+The reference names categorical cells (``ThermalSamplingUnit.sample_categorical``, tsu/core.py) and has no lattice of them; this
+module is the package's own.  Site (r, c) holds a colour 0 .. q - 1; E = -J n_eq - sum_c h_c N_c with n_eq the bonds whose two ends
+agree and N_c the sites of colour c.  Heat-bath sweeps take J of either sign and a per-colour field; Swendsen-Wang steps need J > 0
+and a zero field.  Everything runs in ``csrc/potts2d.hip``; the initial colours come from NumPy on the host.
+"""
+import math
+from typing import Optional
+
+import numpy as np
+
+from .. import _hip
+from ..core import ConfigurationError
+
+ALGORITHMS = {"heat_bath": _hip.POTTS_HEAT_BATH, "swendsen_wang": _hip.POTTS_SWENDSEN_WANG}
+
+
+def check_potts_model(q, coupling, field, temperature):
+    """The refusals of the model, made on the host before the device is touched; returns the field as a float64 array of q values."""
+    if isinstance(q, bool) or int(q) != q or not 2 <= int(q) <= _hip.POTTS_MAX_Q:
+        raise ConfigurationError(f"q must be an integer in 2 .. {_hip.POTTS_MAX_Q} (got {q!r})")
+    q = int(q)
+    h = np.zeros(q) if field is None else np.array(field, dtype=np.float64)
+    if h.shape != (q,):
+        raise ConfigurationError(f"field must hold q = {q} values, one per colour")
+    J, T = float(coupling), float(temperature)
+    if not (math.isfinite(J) and math.isfinite(T) and np.all(np.isfinite(h))):
+        raise ConfigurationError("coupling, field and temperature must be finite")
+    if not T > 0:
+        raise ConfigurationError("Temperature must be positive")
+    if (4.0 * abs(J) + float(h.max() - h.min())) / T > 600.0:
+        raise ConfigurationError("(4 |J| + max h - min h) / T exceeds 600: the heat-bath weights would leave the float64 range")
+    return h
+
+
+def _algorithm(name: str) -> int:
+    if name not in ALGORITHMS:
+        raise ValueError("algorithm must be 'heat_bath' or 'swendsen_wang'")
+    return ALGORITHMS[name]
+
+
+class PottsModel2D:
+    """A q-state Potts lattice that lives on the GPU between calls.
+
+    ``gibbs_update(n)`` = n checkerboard heat-bath sweeps (counter ``sweep_count``); ``cluster_update(n)`` = n Swendsen-Wang steps
+    (J > 0, zero field; counter ``cluster_count``); ``energy()``, ``colour_counts()`` and ``order_parameter()`` come from exact
+    integers reduced on the device.  ``spins`` is an int8 array of colours 0 .. q - 1.
+    """
+
+    def __init__(self, size, q, temperature: float = 1.0, coupling: float = 1.0, field=None, periodic: bool = True,
+                 seed: Optional[int] = None):
+        self.field = check_potts_model(q, coupling, field, temperature)
+        self.q = int(q)
+        self.rows, self.cols = (int(size), int(size)) if np.isscalar(size) else tuple(int(v) for v in size)
+        if self.rows < 1 or self.cols < 1:
+            raise ConfigurationError("size must be positive")
+        self.periodic = bool(periodic)
+        if self.periodic and (self.rows % 2 or self.cols % 2):
+            raise ConfigurationError("a periodic lattice needs even rows and columns")
+        self.n_spins = self.rows * self.cols
+        self.coupling = float(coupling)
+        self.temperature = float(temperature)
+        self.seed = int(seed) if seed is not None else int(np.random.default_rng().integers(0, 2 ** 63))
+        self.sweep_count = 0
+        self.cluster_count = 0
+        self._lat = _hip.PottsLattice(self.rows, self.cols, self.q, self.periodic)
+        self._lat.set_model(self.coupling, self.field)
+        self._lat.set_spins(np.random.default_rng(self.seed).integers(0, self.q, size=(self.rows, self.cols)).astype(np.int8))
+
+    def close(self) -> None:
+        self._lat.close()
+
+    @property
+    def spins(self) -> np.ndarray:
+        return self._lat.get_spins()
+
+    @spins.setter
+    def spins(self, colours) -> None:
+        s = np.asarray(colours)
+        if s.shape != (self.rows, self.cols):
+            raise ValueError(f"spins must have shape {(self.rows, self.cols)}")
+        if not np.issubdtype(s.dtype, np.integer) or s.min() < 0 or s.max() >= self.q:
+            raise ValueError(f"spins must be integer colours in 0 .. {self.q - 1}")
+        self._lat.set_spins(s.astype(np.int8))
+
+    def fill(self, colour: int) -> "PottsModel2D":
+        if not 0 <= int(colour) < self.q:
+            raise ValueError(f"colour must be in 0 .. {self.q - 1}")
+        self._lat.fill(int(colour))
+        return self
+
+    def _set_temperature(self, temperature) -> None:
+        if temperature is not None:
+            check_potts_model(self.q, self.coupling, self.field, temperature)
+            self.temperature = float(temperature)
+
+    def gibbs_update(self, n_sweeps: int = 1) -> "PottsModel2D":
+        self._lat.sweep(self.temperature, int(n_sweeps), self.seed, self.sweep_count & 0xFFFFFFFF)
+        self.sweep_count += int(n_sweeps)
+        return self
+
+    def cluster_update(self, n_steps: int = 1) -> "PottsModel2D":
+        """n Swendsen-Wang steps; :class:`tsu._hip.UnsupportedError` for J <= 0 or a field, the state untouched."""
+        self._lat.cluster_sweep(self.temperature, int(n_steps), self.seed, self.cluster_count)
+        self.cluster_count += int(n_steps)
+        return self
+
+    def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000, algorithm: str = "heat_bath") -> "PottsModel2D":
+        alg = _algorithm(algorithm)
+        self._set_temperature(temperature)
+        return self.cluster_update(n_sweeps) if alg == _hip.POTTS_SWENDSEN_WANG else self.gibbs_update(n_sweeps)
+
+    def run(self, n_measure: int, measure_every: int = 1, algorithm: str = "heat_bath") -> np.ndarray:
+        """``n_measure`` times ``measure_every`` updates and one measurement, without a host round trip in between: the
+        ``(n_measure, 1 + q)`` int64 rows (n_eq, N_0 .. N_{q-1}).  The counters run on as for the single calls."""
+        alg = _algorithm(algorithm)
+        sw = alg == _hip.POTTS_SWENDSEN_WANG
+        self._lat.run(self.temperature, int(n_measure), int(measure_every), alg, self.seed,
+                      self.cluster_count if sw else self.sweep_count & 0xFFFFFFFF)
+        if sw:
+            self.cluster_count += int(n_measure) * int(measure_every)
+        else:
+            self.sweep_count += int(n_measure) * int(measure_every)
+        return self._lat.record()[:, :1 + self.q]
+
+    def colour_counts(self) -> np.ndarray:
+        return self._lat.measure()[1]
+
+    def equal_bonds(self) -> int:
+        return self._lat.measure()[0]
+
+    def energy(self) -> float:
+        n_eq, N = self._lat.measure()
+        return -self.coupling * n_eq - float(np.dot(self.field, N))
+
+    def order_parameter(self) -> float:
+        return float(potts_order_parameter(self.colour_counts(), self.q))
+
+    def route(self, algorithm: str = "heat_bath") -> str:
+        return self._lat.route(_algorithm(algorithm))
+
+    def launch_count(self) -> int:
+        return self._lat.launch_count()
+
+
+def potts_order_parameter(counts, q: int):
+    """m = (q max_c N_c / N - 1) / (q - 1) from colour counts (last axis)."""
+    counts = np.asarray(counts)
+    return (q * counts.max(axis=-1) / counts.sum(axis=-1) - 1.0) / (q - 1.0)
+
+
+def potts_temperature_scan(size, q, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
+                           measure_every: int = 1, algorithm: str = "heat_bath", periodic: bool = True, seed: int = 0) -> dict:
+    """Per temperature: equilibrate a fresh lattice, then ``n_measure`` measurements ``measure_every`` updates apart, recorded on
+    the device (tsu_potts2d_run).  Returns arrays over the temperatures: ``energy`` (per site), ``order_parameter``,
+    ``specific_heat`` = N var(e) / T^2, ``susceptibility`` = N var(m) / T and the ``binder`` cumulant 1 - <m^4> / (3 <m^2>^2)."""
+    _algorithm(algorithm)
+    temperatures = [float(t) for t in temperatures]
+    if int(n_measure) < 1 or int(measure_every) < 1 or int(n_equilibrate) < 0:
+        raise ValueError("n_measure and measure_every must be >= 1, n_equilibrate >= 0")
+    for t in temperatures:
+        check_potts_model(q, coupling, None, t)
+    out = {k: [] for k in ("energy", "order_parameter", "specific_heat", "susceptibility", "binder")}
+    for t in temperatures:
+        model = PottsModel2D(size, q, temperature=t, coupling=coupling, periodic=periodic, seed=seed)
+        model.equilibrate(n_sweeps=int(n_equilibrate), algorithm=algorithm)
+        rows = model.run(int(n_measure), int(measure_every), algorithm)
+        N = model.n_spins
+        model.close()
+        e = -float(coupling) * rows[:, 0] / N
+        m = potts_order_parameter(rows[:, 1:], int(q))
+        out["energy"].append(e.mean())
+        out["order_parameter"].append(m.mean())
+        out["specific_heat"].append(N * e.var() / t ** 2)
+        out["susceptibility"].append(N * m.var() / t)
+        m2 = np.mean(m ** 2)
+        out["binder"].append(1.0 - np.mean(m ** 4) / (3.0 * m2 ** 2) if m2 > 0 else float("nan"))
+    res = {k: np.array(v) for k, v in out.items()}
+    res["temperatures"] = np.array(temperatures)
+    return res
