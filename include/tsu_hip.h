@@ -403,6 +403,10 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * (tsu_potts2d_*): declared in tsu_hip_potts.h, which this header includes; its prototypes are _hip.POTTS_SIGNATURES in Python. */
 #include "tsu_hip_potts.h"
 
+/* K10 in 3-D: the same on the cubic lattice, one periodic flag per axis (tsu_potts3d_*): declared in tsu_hip_potts3d.h, which this
+ * header includes; its prototypes are _hip.POTTS3D_SIGNATURES in Python. */
+#include "tsu_hip_potts3d.h"
+
 /* K6 / K8: cluster-size records of the Swendsen-Wang steps, the exact integers behind the improved estimators
  * (tsu_isingNd_cluster_measure / _cluster_record): declared in tsu_hip_cluster_measure.h, which this header includes; its prototypes
  * are _hip.CLUSTER_MEASURE_SIGNATURES in Python. */

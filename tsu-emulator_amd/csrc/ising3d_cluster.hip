@@ -37,7 +37,7 @@
 // atomics of the union-find, not by it.
 // Shared with K6 (ising2d_cluster.hip): the structs, the bond policies, the seam decoder, the root chase and the resolve pass
 // (sw_dev.h, DIM = 3) and the whole host side (sw_host.h, with the traits below).  This file keeps what only K8 has: the disorder and
-// field checks, the tile choice and TSU_SW3D_TILE, the refusal of a lattice listed twice in a batch, the labels out-of-memory
+// field checks, the refusal of a lattice listed twice in a batch, the labels out-of-memory
 // message, the entry points, and the bodies of the kernels that run a union-find (k8_sw_small, k8_sw_local, k8_sw_merge: sw_dev.h
 // says why).
 #include <math.h>
@@ -240,15 +240,6 @@ __global__ __launch_bounds__(256) void k8_sw_resolve(Params p, int quads) {
     sw_resolve<3, GHOST>(p, quads);
 }
 
-// TSU_SW3D_TILE=<tz>x<tr>x<tc> (tests only, read per call): that tile shape, and every lattice on the multi-tile route.
-// 1: a shape was read; 0: the switch is not set; -1: it does not parse
-int tile_switch(SwGeom* t) {
-    const char* e = getenv("TSU_SW3D_TILE");
-    if (!e || !*e) return 0;
-    char tail = 0;
-    return sscanf(e, "%dx%dx%d%c", &t->tz, &t->tr, &t->tc, &tail) == 3 ? 1 : -1;
-}
-
 // GHOST = false: the zero-field entry points (a stored field is refused); true: the ghost-spin ones
 template <bool GHOST>
 struct K8 {
@@ -293,31 +284,9 @@ struct K8 {
         const size_t plane = (size_t)L->depth * L->rows * L->pitch;
         return Bonds{L->d_dis, L->d_dis + plane, L->d_dis + 2 * plane, L->d_dis + 3 * plane, m.T};  // h: zeros when no field was given
     }
-    static bool tile_forced() {
-        SwGeom t;
-        return tile_switch(&t) != 0;
-    }
-    // The default tile.  16 x 32 x 32 (80 KB of LDS, 1024 lanes, two tiles a CU) leaves 1/16 + 1/32 + 1/32 = 12.5 % of a site's
-    // three bonds' worth on seams (4.2 % of the bonds); 8 x 16 x 32 (20 KB, 256 lanes) leaves 21.9 % (7.3 % of the bonds) but gives
-    // four times the workgroups.  The large tile is taken once it fills the chip (one tile per CU at least), the small one below
-    // that (DESIGN.md section 5, K8 cluster steps).
-    static int tile(Lattice* L, SwGeom& g) {
-        tsu_ctx* ctx = L->ctx;
-        const int sw = tile_switch(&g);
-        TSU_REQUIRE(ctx, sw >= 0, "TSU_SW3D_TILE must read <tz>x<tr>x<tc>");
-        if (sw == 0) {
-            const long long n_big = (long long)((L->depth + 15) / 16) * ((L->rows + 31) / 32) * ((L->cols + 31) / 32);
-            const bool big = n_big >= (ctx->cus > 0 ? ctx->cus : 256);
-            g.tz = big ? 16 : 8;
-            g.tr = big ? 32 : 16;
-            g.tc = 32;
-        }
-        TSU_REQUIRE(ctx, g.tz >= 1 && g.tr >= 1 && g.tc >= 2 && (g.tc & 1) == 0 && g.tz <= kSwSmallSites && g.tr <= kSwSmallSites &&
-                             g.tc <= kSwSmallSites && (long long)g.tz * g.tr * g.tc <= kSwSmallSites,
-                    "TSU_SW3D_TILE: a tile needs positive extents, an even width and at most %d sites (got %d x %d x %d)", kSwSmallSites, g.tz,
-                    g.tr, g.tc);
-        return TSU_OK;
-    }
+    static bool tile_forced() { return sw3d_tile_forced(); }
+    // TSU_SW3D_TILE and the default tile: sw_host.h (sw3d_tile), shared with the 3-D Potts lattice
+    static int tile(Lattice* L, SwGeom& g) { return sw3d_tile(L->ctx, L->depth, L->rows, L->cols, g); }
     static int local_threads(const SwGeom& g) { return sw_threads((g.tz * g.tr * g.tc + 15) / 16); }
     static int grow_labels(Lattice* L, size_t bytes) {
         const hipError_t e = ising2d_grow(L->sw.d_labels, L->sw.labels_cap, bytes);

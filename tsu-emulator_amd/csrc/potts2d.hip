@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "potts_dev.h"
+#include "potts_kern_dev.h"
 #include "sw_host.h"
 
 struct tsu_potts2d {
@@ -51,10 +52,6 @@ struct PottsGeom {
     int rows, cols, periodic;
 };
 
-struct PottsKeys {
-    uint32_t k0, k1, tag_hi, tag_lo;
-};
-
 struct PottsSweep {
     int8_t* s;
     PottsGeom g;
@@ -62,22 +59,6 @@ struct PottsSweep {
     uint32_t hs;  // k10_sweep: the half-sweep; k10_small: the first sweep of the call
     PottsTab t;
 };
-
-// The Philox blocks of an octet's colour: hi16 at once, lo16 when the first site needs it
-struct PottsDraw {
-    uint32_t h0, h1, h2, h3, l0, l1, l2, l3;  // plain words: the struct stays in registers
-    bool have_lo;
-};
-
-__device__ __forceinline__ PottsDraw potts_draw(const PottsKeys& k, uint32_t hs, int r, int o) {
-    const u32x4 h = tsu_philox((uint32_t)o, (uint32_t)r, hs, k.tag_hi, k.k0, k.k1);
-    return PottsDraw{h.x, h.y, h.z, h.w, 0, 0, 0, 0, false};
-}
-
-__device__ __forceinline__ uint32_t half_of(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3, int m) {
-    const uint32_t w = (m >> 1) == 0 ? w0 : ((m >> 1) == 1 ? w1 : ((m >> 1) == 2 ? w2 : w3));
-    return (w >> (16 * (m & 1))) & 0xFFFFu;
-}
 
 // Site m of the octet (r, o) with the neighbour colours up, dn, lf, rt (-1: none): its new colour
 __device__ __forceinline__ int potts_site(const PottsTab& t, const PottsKeys& k, uint32_t hs, int r, int o, int m, int up, int dn, int lf,
@@ -128,12 +109,6 @@ struct PottsPlane {  // a lattice in HBM or LDS, pitch = cols
     __device__ __forceinline__ int at(int r, int c) const { return s[(long long)r * cols + c]; }
     __device__ __forceinline__ void put(int r, int c, int v) const { s[(long long)r * cols + c] = (int8_t)v; }
 };
-
-// byte i (0 .. 15) of a 16-byte load: a colour, 0 .. 7
-__device__ __forceinline__ int colour_at(const uint4& v, int i) {
-    const uint32_t w = i < 4 ? v.x : (i < 8 ? v.y : (i < 12 ? v.z : v.w));
-    return (int)((w >> (8 * (i & 3))) & 0xFFu);
-}
 
 // The same half-sweep of an octet of a lattice whose rows are whole octets (cols % 16 == 0, so every 16-byte row segment is aligned
 // and holds sites only): three 16-byte loads and one edge byte instead of 32 byte loads, one 16-byte store (the other colour's bytes
@@ -244,23 +219,9 @@ __global__ __launch_bounds__(256) void k10_measure(PottsMeasure p) {
     if (threadIdx.x < TSU_POTTS_RECORD_WORDS && s_row[threadIdx.x] != 0) atomicAdd(&p.row[threadIdx.x], s_row[threadIdx.x]);
 }
 
-// ---------------------------------------------------------------- Swendsen-Wang steps
-struct PottsBonds {  // the bond policy: two equal colours and u < thr (thr may be 2^32: 64-bit compare)
-    uint64_t thr;
-    int q;
-    __device__ __forceinline__ static bool sat(int sa, int sb) { return sa == sb; }
-    __device__ __forceinline__ bool on(int sa, int sb, uint32_t u) const { return sa == sb && (uint64_t)u < thr; }
-};
-
+// ---------------------------------------------------------------- Swendsen-Wang steps (PottsBonds, root_colour: potts_kern_dev.h)
 using Item = SwItem<PottsBonds>;
 using Params = SwParams<PottsBonds>;
-
-// the colour of the cluster rooted at (r, c): ((uint64)W q) >> 32, W = word c & 3 of Philox(c >> 2, r, t, tag): the word whose top
-// bit is K6's coin.  Uniform over the q colours to within q 2^-32
-__device__ __forceinline__ int root_colour(int r, int c, int q, uint32_t t, uint32_t tag, uint32_t k0, uint32_t k1) {
-    const u32x4 w = tsu_philox((uint32_t)c >> 2, (uint32_t)r, t, tag, k0, k1);
-    return (int)(((uint64_t)word_of(w, c & 3) * (uint64_t)q) >> 32);
-}
 
 // Rec: always empty (the Potts handle keeps no cluster-size records); the pack is there because sw_host.h names a measured
 // instantiation of every one-workgroup kernel

@@ -13,6 +13,9 @@
 //   local_threads(g)           lanes of a tile's workgroup
 //   grow_labels(L, bytes)      the labels buffer, with this dimension's message when memory runs out
 #pragma once
+#include <stdio.h>
+#include <stdlib.h>
+
 #include <vector>
 
 #include "ising2d.h"
@@ -31,6 +34,42 @@ long long sw_sites(const SwGeom& g) {
 inline int sw_threads(long long work_items) {
     const long long t = (work_items + 63) / 64 * 64;
     return (int)(t < kSwMaxThreads ? t : kSwMaxThreads);
+}
+
+// ---------------------------------------------------------------- the tiles of a 3-D lattice (K8, and K10 in 3-D)
+// TSU_SW3D_TILE=<tz>x<tr>x<tc> (tests only, read per call): that tile shape, and every lattice on the multi-tile route.
+// 1: a shape was read; 0: the switch is not set; -1: it does not parse
+inline int sw3d_tile_switch(SwGeom* t) {
+    const char* e = getenv("TSU_SW3D_TILE");
+    if (!e || !*e) return 0;
+    char tail = 0;
+    return sscanf(e, "%dx%dx%d%c", &t->tz, &t->tr, &t->tc, &tail) == 3 ? 1 : -1;
+}
+
+inline bool sw3d_tile_forced() {
+    SwGeom t;
+    return sw3d_tile_switch(&t) != 0;
+}
+
+// The tile shape into g, checked.  The default: 16 x 32 x 32 (80 KB of LDS, 1024 lanes, two tiles a CU) leaves 1/16 + 1/32 + 1/32 =
+// 12.5 % of a site's three bonds' worth on seams (4.2 % of the bonds); 8 x 16 x 32 (20 KB, 256 lanes) leaves 21.9 % (7.3 % of the
+// bonds) but gives four times the workgroups.  The large tile is taken once it fills the chip (one tile per CU at least), the small
+// one below that (DESIGN.md section 5, K8 cluster steps).
+inline int sw3d_tile(tsu_ctx* ctx, int depth, int rows, int cols, SwGeom& g) {
+    const int sw = sw3d_tile_switch(&g);
+    TSU_REQUIRE(ctx, sw >= 0, "TSU_SW3D_TILE must read <tz>x<tr>x<tc>");
+    if (sw == 0) {
+        const long long n_big = (long long)((depth + 15) / 16) * ((rows + 31) / 32) * ((cols + 31) / 32);
+        const bool big = n_big >= (ctx->cus > 0 ? ctx->cus : 256);
+        g.tz = big ? 16 : 8;
+        g.tr = big ? 32 : 16;
+        g.tc = 32;
+    }
+    TSU_REQUIRE(ctx, g.tz >= 1 && g.tr >= 1 && g.tc >= 2 && (g.tc & 1) == 0 && g.tz <= kSwSmallSites && g.tr <= kSwSmallSites &&
+                         g.tc <= kSwSmallSites && (long long)g.tz * g.tr * g.tc <= kSwSmallSites,
+                "TSU_SW3D_TILE: a tile needs positive extents, an even width and at most %d sites (got %d x %d x %d)", kSwSmallSites, g.tz,
+                g.tr, g.tc);
+    return TSU_OK;
 }
 
 template <class Tr>

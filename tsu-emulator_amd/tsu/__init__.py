@@ -39,6 +39,7 @@ from .models import (  # noqa: F401
     PopulationAnnealing,
     PopulationAnnealing3D,
     PottsModel2D,
+    PottsModel3D,
     cluster_estimators,
     demonstrate_phase_transition,
     edwards_anderson_samples,
@@ -47,6 +48,7 @@ from .models import (  # noqa: F401
     multispin_scan_3d,
     multispin_tempering_scan_3d,
     potts_temperature_scan,
+    potts_temperature_scan_3d,
     temperature_scan_3d,
     tempering_ensemble_scan,
     tempering_ensemble_scan_3d,
@@ -59,7 +61,7 @@ __all__ = [
     "GibbsSampler", "GibbsConfig", "HardwareEmulator",
     "IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "demonstrate_phase_transition",
     "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d", "cluster_estimators",
-    "PopulationAnnealing","PopulationAnnealing3D", "PottsModel2D", "potts_temperature_scan",
+    "PopulationAnnealing","PopulationAnnealing3D", "PottsModel2D", "potts_temperature_scan", "PottsModel3D", "potts_temperature_scan_3d",
     "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
     "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d",
     "GraphTempering", "multispin_quench_3d", "MultispinTempering3D", "multispin_tempering_scan_3d",

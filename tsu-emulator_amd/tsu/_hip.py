@@ -341,10 +341,28 @@ POTTS_SIGNATURES = {
     "tsu_potts2d_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
     "tsu_potts2d_launch_count": (C.c_int, [_vp, _u64p]),
 }
+# name -> (restype, argtypes): mirrors include/tsu_hip_potts3d.h (the header tsu_hip.h includes) one to one
+POTTS3D_SIGNATURES = {
+    "tsu_potts3d_check_model": (C.c_int, [C.c_int, C.c_double, _f64p, C.c_double, _f64p]),
+    "tsu_potts3d_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "tsu_potts3d_destroy": (C.c_int, [_vp]),
+    "tsu_potts3d_set_model": (C.c_int, [_vp, C.c_double, _f64p]),
+    "tsu_potts3d_set_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_potts3d_get_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_potts3d_fill": (C.c_int, [_vp, C.c_int]),
+    "tsu_potts3d_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts3d_cluster_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts3d_route": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
+    "tsu_potts3d_measure": (C.c_int, [_vp, _i64p]),
+    "tsu_potts3d_run": (C.c_int, [_vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts3d_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
+    "tsu_potts3d_launch_count": (C.c_int, [_vp, _u64p]),
+}
 POTTS_RECORD_WORDS = 9     # TSU_POTTS_RECORD_WORDS
 POTTS_MAX_Q = 8            # TSU_POTTS_MAX_Q
 POTTS_HEAT_BATH, POTTS_SWENDSEN_WANG = 0, 1
 POTTS_ROUTES = ("k10_small", "k10_sweep", "k10_sw_small", "k10_sw_tiles")  # TSU_POTTS_ROUTE_*
+POTTS3D_ROUTES = ("k10_3d_small", "k10_3d_sweep", "k10_3d_sw_small", "k10_3d_sw_tiles")  # TSU_POTTS3D_ROUTE_*
 CLUSTER_RECORD_WORDS = 8   # TSU_CLUSTER_RECORD_WORDS
 CLUSTER_RECORD_FIELDS = ("n_clusters", "largest", "sum_size2", "sum_m2", "sum_m4", "n_frozen", "m_frozen")
 MSC_SNAPSHOT_SLOTS = 8     # TSU_MSC_SNAPSHOT_SLOTS
@@ -372,7 +390,8 @@ def load_library():
                               + list(PROBE_SIGNATURES.items()) + list(CLUSTER_FIELD_SIGNATURES.items())
                               + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())
                               + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())
-                              + list(CLUSTER_MEASURE_SIGNATURES.items()) + list(POTTS_SIGNATURES.items())):
+                              + list(CLUSTER_MEASURE_SIGNATURES.items()) + list(POTTS_SIGNATURES.items())
+                              + list(POTTS3D_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -829,6 +848,101 @@ def periodic_axes(periodic):
     if len(p) != 3:
         raise ValueError("periodic must be a bool or a triple (p_z, p_r, p_c)")
     return p
+
+
+def potts3d_tables(q, J, h, T):
+    """Host helper of the library (no GPU needed): (E[0 .. 6], F[0 .. q - 1]) of the six-neighbour Potts heat-bath rule, or ValueError
+    with the model refused (tsu_potts3d_check_model)."""
+    lib = load_library()
+    hh = None if h is None else np.ascontiguousarray(h, dtype=np.float64)
+    if hh is not None and hh.shape != (int(q),) and 2 <= int(q) <= POTTS_MAX_Q:
+        raise ValueError(f"h must hold q = {int(q)} values")
+    t = np.zeros(7 + POTTS_MAX_Q, np.float64)
+    rc = lib.tsu_potts3d_check_model(int(q), float(J), None if hh is None else _ptr(hh, _f64p), float(T), _ptr(t, _f64p))
+    if rc != TSU_OK:
+        raise ValueError("the Potts model (q, J, h, T) is refused: q outside 2 .. 8, a non-finite value, T <= 0 or "
+                         "(6 |J| + max h - min h) / T > 600")
+    return t[:7].copy(), t[7:7 + int(q)].copy()
+
+
+class PottsLattice3D:
+    """tsu_potts3d handle: a depth x rows x cols lattice of colours 0 .. q - 1 (int8) on the GPU (K10 in 3-D); periodic is a bool
+    (all three axes) or (p_z, p_r, p_c)."""
+
+    def __init__(self, depth, rows, cols, q, periodic=True, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.depth, self.rows, self.cols, self.q = int(depth), int(rows), int(cols), int(q)
+        self.periodic = periodic_axes(periodic)
+        h = _vp()
+        pz, pr, pc = (int(x) for x in self.periodic)
+        self.ctx.check(self.lib.tsu_potts3d_create(self.ctx.h, self.depth, self.rows, self.cols, self.q, pz, pr, pc, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_potts3d_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def set_model(self, J, h=None):
+        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float64)
+        if hh is not None and hh.shape != (self.q,):
+            raise ValueError(f"h must hold q = {self.q} values")
+        self.ctx.check(self.lib.tsu_potts3d_set_model(self.h, float(J), None if hh is None else _ptr(hh, _f64p)))
+
+    def set_spins(self, colours):
+        s = np.ascontiguousarray(colours, dtype=np.int8)
+        if s.size != self.depth * self.rows * self.cols:
+            raise ValueError(f"colours must hold {self.depth} x {self.rows} x {self.cols} values")
+        self.ctx.check(self.lib.tsu_potts3d_set_spins(self.h, _ptr(s, _i8p)))
+
+    def get_spins(self):
+        out = np.empty((self.depth, self.rows, self.cols), dtype=np.int8)
+        self.ctx.check(self.lib.tsu_potts3d_get_spins(self.h, _ptr(out, _i8p)))
+        return out
+
+    def fill(self, colour):
+        self.ctx.check(self.lib.tsu_potts3d_fill(self.h, int(colour)))
+
+    def sweep(self, T, n_sweeps, seed, sweep0=0, replica=0):
+        self.ctx.check(self.lib.tsu_potts3d_sweep(self.h, float(T), int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
+
+    def cluster_sweep(self, T, n_steps, seed, step0=0, replica=0):
+        self.ctx.check(self.lib.tsu_potts3d_cluster_sweep(self.h, float(T), int(n_steps), _seed(seed), _counter("step0", step0),
+                                                          _replica(replica)))
+
+    def route(self, algorithm=POTTS_HEAT_BATH):
+        r = C.c_int(-1)
+        self.ctx.check(self.lib.tsu_potts3d_route(self.h, int(algorithm), C.byref(r)))
+        return POTTS3D_ROUTES[r.value]
+
+    def measure(self):
+        """(n_eq, N_0 .. N_{q-1}) of the current state as exact integers (synchronises)."""
+        row = np.zeros(POTTS_RECORD_WORDS, np.int64)
+        self.ctx.check(self.lib.tsu_potts3d_measure(self.h, _ptr(row, _i64p)))
+        return int(row[0]), row[1:1 + self.q].copy()
+
+    def run(self, T, n_meas, sweeps_between, algorithm, seed, counter0=0, replica=0):
+        self.ctx.check(self.lib.tsu_potts3d_run(self.h, float(T), int(n_meas), int(sweeps_between), int(algorithm), _seed(seed),
+                                                _counter("counter0", counter0), _replica(replica)))
+
+    def record(self):
+        """The rows of the most recent run (synchronises): (n_meas, 9) int64, n_eq then N_0 .. N_7."""
+        n = C.c_int(0)
+        self.ctx.check(self.lib.tsu_potts3d_record(self.h, None, 0, C.byref(n)))
+        rows = np.zeros((n.value, POTTS_RECORD_WORDS), np.int64)
+        if n.value:
+            self.ctx.check(self.lib.tsu_potts3d_record(self.h, _ptr(rows, _i64p), n.value, C.byref(n)))
+        return rows
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_potts3d_launch_count(self.h, C.byref(n)))
+        return n.value
 
 
 class Lattice3D:

@@ -6,12 +6,12 @@ from .ising import (IsingChain, IsingConfig, IsingGrid, IsingModel, IsingModel2D
                     tempering_ensemble_scan, tempering_ensemble_scan_3d, MultispinGlass3D, multispin_scan_3d,
                     multispin_quench_3d, MultispinTempering3D, multispin_tempering_scan_3d)
 from .graph_tempering import GraphTempering
-from .potts import PottsModel2D, potts_temperature_scan
+from .potts import PottsModel2D, PottsModel3D, potts_temperature_scan, potts_temperature_scan_3d
 
 __all__ = ["IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "IsingConfig", "demonstrate_phase_transition", "temperature_scan", "cluster_estimators",
            "LatticeTempering", "tempering_scan", "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d",
            "PopulationAnnealing", "PopulationAnnealing3D", "population_annealing_scan", "population_annealing_scan_3d",
            "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
            "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d", "GraphTempering",
-           "PottsModel2D", "potts_temperature_scan",
+           "PottsModel2D", "potts_temperature_scan", "PottsModel3D", "potts_temperature_scan_3d",
            "multispin_quench_3d", "MultispinTempering3D", "multispin_tempering_scan_3d"]

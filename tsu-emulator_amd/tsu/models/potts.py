@@ -1,9 +1,9 @@
-"""q-state Potts lattices in 2-D (K10): the categorical counterpart of :class:`IsingModel2D`.
+"""q-state Potts lattices in 2-D and 3-D (K10): the categorical counterparts of :class:`IsingModel2D` and :class:`IsingModel3D`.
 
 The reference names categorical cells (``ThermalSamplingUnit.sample_categorical``, tsu/core.py) and has no lattice of them; this
 module is the package's own.  Site (r, c) holds a colour 0 .. q - 1; E = -J n_eq - sum_c h_c N_c with n_eq the bonds whose two ends
 agree and N_c the sites of colour c.  Heat-bath sweeps take J of either sign and a per-colour field; Swendsen-Wang steps need J > 0
-and a zero field.  Everything runs in ``csrc/potts2d.hip``; the initial colours come from NumPy on the host.
+and a zero field.  Everything runs in ``csrc/potts2d.hip`` and ``csrc/potts3d.hip``; the initial colours come from NumPy on the host.
 """
 import math
 from typing import Optional
@@ -16,8 +16,9 @@ from ..core import ConfigurationError
 ALGORITHMS = {"heat_bath": _hip.POTTS_HEAT_BATH, "swendsen_wang": _hip.POTTS_SWENDSEN_WANG}
 
 
-def check_potts_model(q, coupling, field, temperature):
-    """The refusals of the model, made on the host before the device is touched; returns the field as a float64 array of q values."""
+def check_potts_model(q, coupling, field, temperature, neighbours: int = 4):
+    """The refusals of the model, made on the host before the device is touched; returns the field as a float64 array of q values.
+    ``neighbours``: 4 on the square lattice, 6 on the cubic one (whatever its depth)."""
     if isinstance(q, bool) or int(q) != q or not 2 <= int(q) <= _hip.POTTS_MAX_Q:
         raise ConfigurationError(f"q must be an integer in 2 .. {_hip.POTTS_MAX_Q} (got {q!r})")
     q = int(q)
@@ -29,8 +30,8 @@ def check_potts_model(q, coupling, field, temperature):
         raise ConfigurationError("coupling, field and temperature must be finite")
     if not T > 0:
         raise ConfigurationError("Temperature must be positive")
-    if (4.0 * abs(J) + float(h.max() - h.min())) / T > 600.0:
-        raise ConfigurationError("(4 |J| + max h - min h) / T exceeds 600: the heat-bath weights would leave the float64 range")
+    if (float(neighbours) * abs(J) + float(h.max() - h.min())) / T > 600.0:
+        raise ConfigurationError(f"({neighbours} |J| + max h - min h) / T exceeds 600: the heat-bath weights would leave the float64 range")
     return h
 
 
@@ -40,33 +41,10 @@ def _algorithm(name: str) -> int:
     return ALGORITHMS[name]
 
 
-class PottsModel2D:
-    """A q-state Potts lattice that lives on the GPU between calls.
+class _PottsLattice:
+    """What the 2-D and the 3-D model share: everything but the constructor.  A subclass sets ``shape``, ``_neighbours`` and ``_lat``."""
 
-    ``gibbs_update(n)`` = n checkerboard heat-bath sweeps (counter ``sweep_count``); ``cluster_update(n)`` = n Swendsen-Wang steps
-    (J > 0, zero field; counter ``cluster_count``); ``energy()``, ``colour_counts()`` and ``order_parameter()`` come from exact
-    integers reduced on the device.  ``spins`` is an int8 array of colours 0 .. q - 1.
-    """
-
-    def __init__(self, size, q, temperature: float = 1.0, coupling: float = 1.0, field=None, periodic: bool = True,
-                 seed: Optional[int] = None):
-        self.field = check_potts_model(q, coupling, field, temperature)
-        self.q = int(q)
-        self.rows, self.cols = (int(size), int(size)) if np.isscalar(size) else tuple(int(v) for v in size)
-        if self.rows < 1 or self.cols < 1:
-            raise ConfigurationError("size must be positive")
-        self.periodic = bool(periodic)
-        if self.periodic and (self.rows % 2 or self.cols % 2):
-            raise ConfigurationError("a periodic lattice needs even rows and columns")
-        self.n_spins = self.rows * self.cols
-        self.coupling = float(coupling)
-        self.temperature = float(temperature)
-        self.seed = int(seed) if seed is not None else int(np.random.default_rng().integers(0, 2 ** 63))
-        self.sweep_count = 0
-        self.cluster_count = 0
-        self._lat = _hip.PottsLattice(self.rows, self.cols, self.q, self.periodic)
-        self._lat.set_model(self.coupling, self.field)
-        self._lat.set_spins(np.random.default_rng(self.seed).integers(0, self.q, size=(self.rows, self.cols)).astype(np.int8))
+    _neighbours = 4
 
     def close(self) -> None:
         self._lat.close()
@@ -78,13 +56,13 @@ class PottsModel2D:
     @spins.setter
     def spins(self, colours) -> None:
         s = np.asarray(colours)
-        if s.shape != (self.rows, self.cols):
-            raise ValueError(f"spins must have shape {(self.rows, self.cols)}")
+        if s.shape != self.shape:
+            raise ValueError(f"spins must have shape {self.shape}")
         if not np.issubdtype(s.dtype, np.integer) or s.min() < 0 or s.max() >= self.q:
             raise ValueError(f"spins must be integer colours in 0 .. {self.q - 1}")
         self._lat.set_spins(s.astype(np.int8))
 
-    def fill(self, colour: int) -> "PottsModel2D":
+    def fill(self, colour: int):
         if not 0 <= int(colour) < self.q:
             raise ValueError(f"colour must be in 0 .. {self.q - 1}")
         self._lat.fill(int(colour))
@@ -92,21 +70,21 @@ class PottsModel2D:
 
     def _set_temperature(self, temperature) -> None:
         if temperature is not None:
-            check_potts_model(self.q, self.coupling, self.field, temperature)
+            check_potts_model(self.q, self.coupling, self.field, temperature, self._neighbours)
             self.temperature = float(temperature)
 
-    def gibbs_update(self, n_sweeps: int = 1) -> "PottsModel2D":
+    def gibbs_update(self, n_sweeps: int = 1):
         self._lat.sweep(self.temperature, int(n_sweeps), self.seed, self.sweep_count & 0xFFFFFFFF)
         self.sweep_count += int(n_sweeps)
         return self
 
-    def cluster_update(self, n_steps: int = 1) -> "PottsModel2D":
+    def cluster_update(self, n_steps: int = 1):
         """n Swendsen-Wang steps; :class:`tsu._hip.UnsupportedError` for J <= 0 or a field, the state untouched."""
         self._lat.cluster_sweep(self.temperature, int(n_steps), self.seed, self.cluster_count)
         self.cluster_count += int(n_steps)
         return self
 
-    def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000, algorithm: str = "heat_bath") -> "PottsModel2D":
+    def equilibrate(self, temperature: Optional[float] = None, n_sweeps: int = 1000, algorithm: str = "heat_bath"):
         alg = _algorithm(algorithm)
         self._set_temperature(temperature)
         return self.cluster_update(n_sweeps) if alg == _hip.POTTS_SWENDSEN_WANG else self.gibbs_update(n_sweeps)
@@ -144,26 +122,93 @@ class PottsModel2D:
         return self._lat.launch_count()
 
 
+class PottsModel2D(_PottsLattice):
+    """A q-state Potts lattice that lives on the GPU between calls.
+
+    ``gibbs_update(n)`` = n checkerboard heat-bath sweeps (counter ``sweep_count``); ``cluster_update(n)`` = n Swendsen-Wang steps
+    (J > 0, zero field; counter ``cluster_count``); ``energy()``, ``colour_counts()`` and ``order_parameter()`` come from exact
+    integers reduced on the device.  ``spins`` is an int8 array of colours 0 .. q - 1.
+    """
+
+    def __init__(self, size, q, temperature: float = 1.0, coupling: float = 1.0, field=None, periodic: bool = True,
+                 seed: Optional[int] = None):
+        self.field = check_potts_model(q, coupling, field, temperature)
+        self.q = int(q)
+        self.rows, self.cols = (int(size), int(size)) if np.isscalar(size) else tuple(int(v) for v in size)
+        if self.rows < 1 or self.cols < 1:
+            raise ConfigurationError("size must be positive")
+        self.periodic = bool(periodic)
+        if self.periodic and (self.rows % 2 or self.cols % 2):
+            raise ConfigurationError("a periodic lattice needs even rows and columns")
+        self.shape = (self.rows, self.cols)
+        self.n_spins = self.rows * self.cols
+        self.coupling = float(coupling)
+        self.temperature = float(temperature)
+        self.seed = int(seed) if seed is not None else int(np.random.default_rng().integers(0, 2 ** 63))
+        self.sweep_count = 0
+        self.cluster_count = 0
+        self._lat = _hip.PottsLattice(self.rows, self.cols, self.q, self.periodic)
+        self._lat.set_model(self.coupling, self.field)
+        self._lat.set_spins(np.random.default_rng(self.seed).integers(0, self.q, size=(self.rows, self.cols)).astype(np.int8))
+
+
+class PottsModel3D(_PottsLattice):
+    """A q-state Potts lattice on the cubic lattice, ``size`` = (D, R, C) or one edge; ``periodic`` a bool (all three axes) or
+    ``(p_z, p_r, p_c)``; a periodic axis needs an even length, an open one any length >= 1 (one layer: D = 1 with an open z axis,
+    which takes :class:`PottsModel2D`'s colours bit for bit).  The methods are :class:`PottsModel2D`'s; ``spins`` has shape (D, R, C).
+    ``initial``: ``"random"`` (``default_rng(seed).integers(0, q, size)``) or one colour 0 .. q - 1 for every site.
+    """
+
+    _neighbours = 6
+
+    def __init__(self, size, q, temperature: float = 1.0, coupling: float = 1.0, field=None, periodic=True,
+                 seed: Optional[int] = None, initial="random"):
+        self.field = check_potts_model(q, coupling, field, temperature, 6)
+        self.q = int(q)
+        self.shape = (int(size),) * 3 if np.isscalar(size) else tuple(int(v) for v in size)
+        if len(self.shape) != 3 or min(self.shape) < 1:
+            raise ConfigurationError("size must be a positive edge or (depth, rows, cols)")
+        self.depth, self.rows, self.cols = self.shape
+        try:
+            self.periodic = _hip.periodic_axes(periodic)
+        except ValueError as e:
+            raise ConfigurationError(str(e)) from None
+        if any(p and n % 2 for p, n in zip(self.periodic, self.shape)):
+            raise ConfigurationError("a periodic axis needs an even length")
+        self.n_spins = self.depth * self.rows * self.cols
+        if self.n_spins >= 2 ** 31:
+            raise ConfigurationError("the lattice must hold fewer than 2^31 sites")
+        if not (initial == "random" or (not isinstance(initial, (str, bool)) and int(initial) == initial and 0 <= int(initial) < self.q)):
+            raise ConfigurationError(f"initial must be 'random' or a colour in 0 .. {self.q - 1}")
+        self.coupling = float(coupling)
+        self.temperature = float(temperature)
+        self.seed = int(seed) if seed is not None else int(np.random.default_rng().integers(0, 2 ** 63))
+        self.sweep_count = 0
+        self.cluster_count = 0
+        self._lat = _hip.PottsLattice3D(self.depth, self.rows, self.cols, self.q, self.periodic)
+        self._lat.set_model(self.coupling, self.field)
+        if initial == "random":
+            self._lat.set_spins(np.random.default_rng(self.seed).integers(0, self.q, size=self.shape).astype(np.int8))
+        else:
+            self._lat.fill(int(initial))
+
+
 def potts_order_parameter(counts, q: int):
     """m = (q max_c N_c / N - 1) / (q - 1) from colour counts (last axis)."""
     counts = np.asarray(counts)
     return (q * counts.max(axis=-1) / counts.sum(axis=-1) - 1.0) / (q - 1.0)
 
 
-def potts_temperature_scan(size, q, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
-                           measure_every: int = 1, algorithm: str = "heat_bath", periodic: bool = True, seed: int = 0) -> dict:
-    """Per temperature: equilibrate a fresh lattice, then ``n_measure`` measurements ``measure_every`` updates apart, recorded on
-    the device (tsu_potts2d_run).  Returns arrays over the temperatures: ``energy`` (per site), ``order_parameter``,
-    ``specific_heat`` = N var(e) / T^2, ``susceptibility`` = N var(m) / T and the ``binder`` cumulant 1 - <m^4> / (3 <m^2>^2)."""
+def _scan(model_class, size, q, temperatures, coupling, n_equilibrate, n_measure, measure_every, algorithm, periodic, seed) -> dict:
     _algorithm(algorithm)
     temperatures = [float(t) for t in temperatures]
     if int(n_measure) < 1 or int(measure_every) < 1 or int(n_equilibrate) < 0:
         raise ValueError("n_measure and measure_every must be >= 1, n_equilibrate >= 0")
     for t in temperatures:
-        check_potts_model(q, coupling, None, t)
+        check_potts_model(q, coupling, None, t, model_class._neighbours)
     out = {k: [] for k in ("energy", "order_parameter", "specific_heat", "susceptibility", "binder")}
     for t in temperatures:
-        model = PottsModel2D(size, q, temperature=t, coupling=coupling, periodic=periodic, seed=seed)
+        model = model_class(size, q, temperature=t, coupling=coupling, periodic=periodic, seed=seed)
         model.equilibrate(n_sweeps=int(n_equilibrate), algorithm=algorithm)
         rows = model.run(int(n_measure), int(measure_every), algorithm)
         N = model.n_spins
@@ -179,3 +224,17 @@ def potts_temperature_scan(size, q, temperatures, coupling: float = 1.0, n_equil
     res = {k: np.array(v) for k, v in out.items()}
     res["temperatures"] = np.array(temperatures)
     return res
+
+
+def potts_temperature_scan(size, q, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
+                           measure_every: int = 1, algorithm: str = "heat_bath", periodic: bool = True, seed: int = 0) -> dict:
+    """Per temperature: equilibrate a fresh lattice, then ``n_measure`` measurements ``measure_every`` updates apart, recorded on
+    the device (tsu_potts2d_run).  Returns arrays over the temperatures: ``energy`` (per site), ``order_parameter``,
+    ``specific_heat`` = N var(e) / T^2, ``susceptibility`` = N var(m) / T and the ``binder`` cumulant 1 - <m^4> / (3 <m^2>^2)."""
+    return _scan(PottsModel2D, size, q, temperatures, coupling, n_equilibrate, n_measure, measure_every, algorithm, periodic, seed)
+
+
+def potts_temperature_scan_3d(size, q, temperatures, coupling: float = 1.0, n_equilibrate: int = 1000, n_measure: int = 50,
+                              measure_every: int = 1, algorithm: str = "heat_bath", periodic=True, seed: int = 0) -> dict:
+    """:func:`potts_temperature_scan` on the cubic lattice (:class:`PottsModel3D`, tsu_potts3d_run): the same keys."""
+    return _scan(PottsModel3D, size, q, temperatures, coupling, n_equilibrate, n_measure, measure_every, algorithm, periodic, seed)
