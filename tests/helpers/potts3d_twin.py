@@ -130,6 +130,39 @@ def sweep(spins, q, periodic, J, h, T, n_sweeps, seed, sweep0=0, replica=0):
     return s
 
 
+# ---------------------------------------------------------------- the sites the low half of u decides (potts_twin.lo_mask)
+lo_mask, lo_octets, lo_fold = _p2.lo_mask, _p2.lo_octets, _p2.lo_fold  # octets of global rows: the masks fold as (D R, C)
+
+
+def lo_decided(spins, q, periodic, J, h, T, hs, seed, replica=0):
+    """The boolean mask of the sites of half-sweep hs (colour hs & 1) of `spins` that the low half of u decides."""
+    s = np.array(spins, dtype=np.int8)
+    assert s.ndim == 3
+    E, F = tables(q, J, h, T)
+    hs = int(hs) & 0xFFFFFFFF
+    nb = neighbours(s, periodic)
+    counts = [sum((x == c).astype(np.int64) for x in nb) for c in range(q)]
+    return lo_mask(cumulative(E, F, counts), site_uniforms(s.shape, hs, seed, replica)) & (colours(s.shape) == (hs & 1))
+
+
+def lo_trajectory(spins, q, periodic, J, h, T, n_sweeps, seed, sweep0=0, replica=0):
+    """`sweep` half-sweep by half-sweep: (the final state, the lo_decided mask of each of the 2 n_sweeps half-sweeps in order)."""
+    s = np.array(spins, dtype=np.int8)
+    assert s.ndim == 3
+    E, F = tables(q, J, h, T)
+    colour_of = colours(s.shape)
+    masks = []
+    for k in range(int(n_sweeps)):
+        for colour in (0, 1):
+            hs = (2 * ((int(sweep0) + k) & 0xFFFFFFFF) + colour) & 0xFFFFFFFF
+            u = site_uniforms(s.shape, hs, seed, replica)
+            nb = neighbours(s, periodic)
+            Z = cumulative(E, F, [sum((x == c).astype(np.int64) for x in nb) for c in range(q)])
+            masks.append(lo_mask(Z, u) & (colour_of == colour))
+            s = np.where(colour_of == colour, pick(Z, u), s).astype(np.int8)
+    return s, masks
+
+
 def _words(seed, rho, c, t, tag):
     return philox4x32_10(c, rho, t, tag, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
 

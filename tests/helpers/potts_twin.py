@@ -128,6 +128,64 @@ def sweep(spins, q, periodic, J, h, T, n_sweeps, seed, sweep0=0, replica=0):
     return s
 
 
+# ---------------------------------------------------------------- the sites the low half of u decides
+# The rule is monotone in u, so the kernels decide a site from the high half of u alone where the colour is the same at both ends
+# of the 65536 values that share it, and draw the lo16 Philox block of the octet only for the others (potts_site, potts_site6).
+def lo_mask(Z, u):
+    """Z: the cumulative sums of every site, u: its uint32 uniform -> the sites whose colour differs between u & 0xFFFF0000 and
+    u | 0xFFFF."""
+    u = np.asarray(u, dtype=np.uint32)
+    return pick(Z, u & np.uint32(0xFFFF0000)) != pick(Z, u | np.uint32(0xFFFF))
+
+
+def lo_decided(spins, q, periodic, J, h, T, hs, seed, replica=0):
+    """The boolean mask of the sites of half-sweep hs (colour hs & 1) of `spins` that the low half of u decides."""
+    s = np.array(spins, dtype=np.int8)
+    rows, cols = s.shape
+    E, F = tables(q, J, h, T)
+    hs = int(hs) & 0xFFFFFFFF
+    nb = neighbours(s, periodic)
+    counts = [sum((x == c).astype(np.int64) for x in nb) for c in range(q)]
+    mine = ((np.arange(rows)[:, None] + np.arange(cols)[None, :]) & 1) == (hs & 1)
+    return lo_mask(cumulative(E, F, counts), site_uniforms(rows, cols, hs, seed, replica)) & mine
+
+
+def lo_octets(mask):
+    """mask: (..., cols) booleans -> (global rows, octets) int64: the marked sites of every octet (16 columns of a global row)."""
+    mask = np.asarray(mask, dtype=bool)
+    cols = mask.shape[-1]
+    noct = (cols + 15) >> 4
+    wide = np.zeros((mask.size // cols, 16 * noct), np.int64)
+    wide[:, :cols] = mask.reshape(-1, cols)
+    return wide.reshape(-1, noct, 16).sum(axis=2)
+
+
+def lo_fold(mask):
+    """(the marked sites per octet position m = (c >> 1) & 7 as 8 ints, the number of octets that hold at least two of them)."""
+    mask = np.asarray(mask, dtype=bool)
+    m = (np.arange(mask.shape[-1]) >> 1) & 7
+    per_m = [int(mask[..., m == k].sum()) for k in range(8)]
+    return per_m, int((lo_octets(mask) >= 2).sum())
+
+
+def lo_trajectory(spins, q, periodic, J, h, T, n_sweeps, seed, sweep0=0, replica=0):
+    """`sweep` half-sweep by half-sweep: (the final state, the lo_decided mask of each of the 2 n_sweeps half-sweeps in order)."""
+    s = np.array(spins, dtype=np.int8)
+    rows, cols = s.shape
+    E, F = tables(q, J, h, T)
+    colour_of = (np.arange(rows)[:, None] + np.arange(cols)[None, :]) & 1
+    masks = []
+    for k in range(int(n_sweeps)):
+        for colour in (0, 1):
+            hs = (2 * ((int(sweep0) + k) & 0xFFFFFFFF) + colour) & 0xFFFFFFFF
+            u = site_uniforms(rows, cols, hs, seed, replica)
+            nb = neighbours(s, periodic)
+            Z = cumulative(E, F, [sum((x == c).astype(np.int64) for x in nb) for c in range(q)])
+            masks.append(lo_mask(Z, u) & (colour_of == colour))
+            s = np.where(colour_of == colour, pick(Z, u), s).astype(np.int8)
+    return s, masks
+
+
 def _words(seed, r, c, t, tag):
     return philox4x32_10(c, r, t, tag, int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF)
 
