@@ -407,6 +407,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * header includes; its prototypes are _hip.POTTS3D_SIGNATURES in Python. */
 #include "tsu_hip_potts3d.h"
 
+/* K11: multicanonical (flat-histogram) walkers of a Potts lattice, thousands of independent copies that share one weight table
+ * ln W[n_eq] and add to one exact histogram (tsu_potts_muca_*): declared in tsu_hip_potts_muca.h, which this header includes; its
+ * prototypes are _hip.POTTS_MUCA_SIGNATURES in Python. */
+#include "tsu_hip_potts_muca.h"
+
 /* K6 / K8: cluster-size records of the Swendsen-Wang steps, the exact integers behind the improved estimators
  * (tsu_isingNd_cluster_measure / _cluster_record): declared in tsu_hip_cluster_measure.h, which this header includes; its prototypes
  * are _hip.CLUSTER_MEASURE_SIGNATURES in Python. */

@@ -153,6 +153,7 @@ enum : uint32_t {
     TSU_TAG_POP_RESAMPLE = 11,
     TSU_TAG_SW_GHOST = 12
 };
+// 13 is taken as well: K11's multicanonical Potts walkers define it with their rule in potts_muca_dev.h (tests pin this enum to 0 .. 12)
 
 struct u32x4 {
     uint32_t x, y, z, w;

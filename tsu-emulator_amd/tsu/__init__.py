@@ -40,6 +40,7 @@ from .models import (  # noqa: F401
     PopulationAnnealing3D,
     PottsModel2D,
     PottsModel3D,
+    PottsMulticanonical,
     cluster_estimators,
     demonstrate_phase_transition,
     edwards_anderson_samples,
@@ -47,6 +48,7 @@ from .models import (  # noqa: F401
     multispin_quench_3d,
     multispin_scan_3d,
     multispin_tempering_scan_3d,
+    potts_multicanonical_scan,
     potts_temperature_scan,
     potts_temperature_scan_3d,
     temperature_scan_3d,
@@ -62,6 +64,7 @@ __all__ = [
     "IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "demonstrate_phase_transition",
     "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d", "cluster_estimators",
     "PopulationAnnealing","PopulationAnnealing3D", "PottsModel2D", "potts_temperature_scan", "PottsModel3D", "potts_temperature_scan_3d",
+    "PottsMulticanonical", "potts_multicanonical_scan",
     "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
     "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d",
     "GraphTempering", "multispin_quench_3d", "MultispinTempering3D", "multispin_tempering_scan_3d",

@@ -358,6 +358,29 @@ POTTS3D_SIGNATURES = {
     "tsu_potts3d_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
     "tsu_potts3d_launch_count": (C.c_int, [_vp, _u64p]),
 }
+# name -> (restype, argtypes): mirrors include/tsu_hip_potts_muca.h (the header tsu_hip.h includes) one to one
+POTTS_MUCA_SIGNATURES = {
+    "tsu_potts_muca_geometry": (C.c_int, [C.c_int, C.c_int, C.c_int, _i32p, _i64p, C.POINTER(C.c_int)]),
+    "tsu_potts_muca_thresholds": (C.c_int, [C.c_int64, C.c_int, _f64p, _u64p]),
+    "tsu_potts_muca_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.POINTER(_vp)]),
+    "tsu_potts_muca_destroy": (C.c_int, [_vp]),
+    "tsu_potts_muca_set_weights": (C.c_int, [_vp, _f64p, C.c_int64]),
+    "tsu_potts_muca_set_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_potts_muca_get_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_potts_muca_fill": (C.c_int, [_vp, C.c_int]),
+    "tsu_potts_muca_set_tunnel_bounds": (C.c_int, [_vp, C.c_int64, C.c_int64]),
+    "tsu_potts_muca_run": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts_muca_energies": (C.c_int, [_vp, _i32p]),
+    "tsu_potts_muca_tunnels": (C.c_int, [_vp, _u32p]),
+    "tsu_potts_muca_record": (C.c_int, [_vp, _u64p, _u64p, _u64p]),
+    "tsu_potts_muca_clear_record": (C.c_int, [_vp]),
+    "tsu_potts_muca_measure": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "tsu_potts_muca_route": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "tsu_potts_muca_launch_count": (C.c_int, [_vp, _u64p]),
+}
+POTTS_MUCA_ROUTES = ("k11_muca_lds", "k11_muca_global", "k11_muca_atomics")  # TSU_POTTS_MUCA_ROUTE_*
+POTTS_MUCA_MAX_SITES = 65536       # TSU_POTTS_MUCA_MAX_SITES
+POTTS_MUCA_MAX_WALKERS = 1 << 20   # TSU_POTTS_MUCA_MAX_WALKERS
 POTTS_RECORD_WORDS = 9     # TSU_POTTS_RECORD_WORDS
 POTTS_MAX_Q = 8            # TSU_POTTS_MAX_Q
 POTTS_HEAT_BATH, POTTS_SWENDSEN_WANG = 0, 1
@@ -391,7 +414,7 @@ def load_library():
                               + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())
                               + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())
                               + list(CLUSTER_MEASURE_SIGNATURES.items()) + list(POTTS_SIGNATURES.items())
-                              + list(POTTS3D_SIGNATURES.items())):
+                              + list(POTTS3D_SIGNATURES.items()) + list(POTTS_MUCA_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -942,6 +965,114 @@ class PottsLattice3D:
     def launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_potts3d_launch_count(self.h, C.byref(n)))
+        return n.value
+
+
+def potts_muca_geometry(depth, rows, cols, periodic):
+    """Host helper of the library (no GPU needed): (B, z_max) of a depth x rows x cols lattice, ValueError where it is refused."""
+    lib = load_library()
+    per = np.array([int(bool(x)) for x in periodic_axes(periodic)], np.int32)
+    b, z = C.c_int64(0), C.c_int(0)
+    if lib.tsu_potts_muca_geometry(int(depth), int(rows), int(cols), _ptr(per, _i32p), C.byref(b), C.byref(z)) != TSU_OK:
+        raise ValueError(f"a side < 1 or more than {POTTS_MUCA_MAX_SITES} sites")
+    return b.value, z.value
+
+
+def potts_muca_thresholds(bonds, z_max, lnw):
+    """Host helper of the library (no GPU needed): the (B + 1, 2 z_max + 1) uint64 acceptance table of ln W, the one the device decides
+    with (tsu_potts_muca_thresholds)."""
+    lib = load_library()
+    w = np.ascontiguousarray(lnw, dtype=np.float64)
+    if w.shape != (int(bonds) + 1,):
+        raise ValueError(f"lnw must hold B + 1 = {int(bonds) + 1} values")
+    out = np.zeros((int(bonds) + 1, 2 * int(z_max) + 1), np.uint64)
+    if lib.tsu_potts_muca_thresholds(int(bonds), int(z_max), _ptr(w, _f64p), _ptr(out, _u64p)) != TSU_OK:
+        raise ValueError("the table is refused: B < 0, z_max other than 4 or 6, or a non-finite ln W")
+    return out
+
+
+class PottsMucaWalkers:
+    """tsu_potts_muca handle (K11): `walkers` copies of a depth x rows x cols lattice of colours 0 .. q - 1 under one weight table
+    ln W[n_eq], with the shared exact record H, S1, S2."""
+
+    def __init__(self, depth, rows, cols, q, walkers, periodic=True, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.depth, self.rows, self.cols, self.q, self.walkers = int(depth), int(rows), int(cols), int(q), int(walkers)
+        self.periodic = periodic_axes(periodic)
+        per = np.array([int(x) for x in self.periodic], np.int32)
+        h = _vp()
+        self.ctx.check(self.lib.tsu_potts_muca_create(self.ctx.h, self.depth, self.rows, self.cols, self.q, _ptr(per, _i32p), self.walkers,
+                                                      C.byref(h)))
+        self.h = h
+        self.bonds, self.z_max = potts_muca_geometry(self.depth, self.rows, self.cols, self.periodic)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_potts_muca_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def set_weights(self, lnw):
+        w = np.ascontiguousarray(lnw, dtype=np.float64).ravel()
+        self.ctx.check(self.lib.tsu_potts_muca_set_weights(self.h, _ptr(w, _f64p), w.size))
+
+    def set_spins(self, colours):
+        s = np.ascontiguousarray(colours, dtype=np.int8)
+        if s.size != self.walkers * self.depth * self.rows * self.cols:
+            raise ValueError(f"colours must hold {self.walkers} x {self.depth} x {self.rows} x {self.cols} values")
+        self.ctx.check(self.lib.tsu_potts_muca_set_spins(self.h, _ptr(s, _i8p)))
+
+    def get_spins(self):
+        out = np.empty((self.walkers, self.depth, self.rows, self.cols), dtype=np.int8)
+        self.ctx.check(self.lib.tsu_potts_muca_get_spins(self.h, _ptr(out, _i8p)))
+        return out
+
+    def fill(self, colour):
+        self.ctx.check(self.lib.tsu_potts_muca_fill(self.h, int(colour)))
+
+    def set_tunnel_bounds(self, n_lo, n_hi):
+        self.ctx.check(self.lib.tsu_potts_muca_set_tunnel_bounds(self.h, int(n_lo), int(n_hi)))
+
+    def run(self, n_sweeps, seed, sweep0=0, replica=0):
+        self.ctx.check(self.lib.tsu_potts_muca_run(self.h, int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
+
+    def energies(self):
+        out = np.empty(self.walkers, np.int32)
+        self.ctx.check(self.lib.tsu_potts_muca_energies(self.h, _ptr(out, _i32p)))
+        return out
+
+    def tunnels(self):
+        out = np.empty(self.walkers, np.uint32)
+        self.ctx.check(self.lib.tsu_potts_muca_tunnels(self.h, _ptr(out, _u32p)))
+        return out
+
+    def record(self):
+        """(H, S1, S2), B + 1 uint64 words each (synchronises)."""
+        out = np.zeros((3, self.bonds + 1), np.uint64)
+        self.ctx.check(self.lib.tsu_potts_muca_record(self.h, _ptr(out[0], _u64p), _ptr(out[1], _u64p), _ptr(out[2], _u64p)))
+        return out[0], out[1], out[2]
+
+    def clear_record(self):
+        self.ctx.check(self.lib.tsu_potts_muca_clear_record(self.h))
+
+    def measure(self):
+        """Recomputes n_eq and N_c of every walker from the spins; True iff they equalled the incrementally kept ones."""
+        eq = C.c_int(0)
+        self.ctx.check(self.lib.tsu_potts_muca_measure(self.h, C.byref(eq)))
+        return bool(eq.value)
+
+    def route(self):
+        r = C.c_int(-1)
+        self.ctx.check(self.lib.tsu_potts_muca_route(self.h, C.byref(r)))
+        return POTTS_MUCA_ROUTES[r.value]
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_potts_muca_launch_count(self.h, C.byref(n)))
         return n.value
 
 
