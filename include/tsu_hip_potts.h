@@ -1,5 +1,5 @@
 /* tsu_hip_potts.h -- K10: q-state Potts lattices in 2-D, heat-bath sweeps and Swendsen-Wang steps on a handle of their own
- * (csrc/potts2d.hip, potts_dev.h).  The categorical counterpart of the two-valued lattice handle: the reference names such cells in
+ * (csrc/potts2d.hip: potts_host.h at DIM = 2).  The categorical counterpart of the two-valued lattice handle: the reference names such cells in
  * ThermalSamplingUnit.sample_categorical (tsu/core.py) and has no lattice of them.
  *
  * Part of the C ABI of libtsu_hip.so: included by tsu_hip.h (inside its extern "C" block); include tsu_hip.h, not this file.  Its

@@ -1,5 +1,5 @@
 /* tsu_hip_potts3d.h -- K10 in 3-D: q-state Potts lattices on the cubic lattice, heat-bath sweeps and Swendsen-Wang steps on a handle
- * of their own (csrc/potts3d.hip, potts_dev.h).  The 3-D counterpart of tsu_hip_potts.h, symbol for symbol, as tsu_ising3d is of
+ * of their own (csrc/potts3d.hip: potts_host.h at DIM = 3).  The 3-D counterpart of tsu_hip_potts.h, symbol for symbol, as tsu_ising3d is of
  * the two-valued 2-D lattice.
  *
  * Part of the C ABI of libtsu_hip.so: included by tsu_hip.h (inside its extern "C" block, after tsu_hip_potts.h, whose
@@ -20,10 +20,10 @@
 
 typedef struct tsu_potts3d tsu_potts3d;
 
-#define TSU_POTTS3D_ROUTE_SMALL 0    /* k10_3d_small: at most 16384 sites in one workgroup's LDS, all sweeps of a call in one launch */
-#define TSU_POTTS3D_ROUTE_SWEEP 1    /* k10_3d_sweep: one launch per half-sweep through HBM */
-#define TSU_POTTS3D_ROUTE_SW_SMALL 2 /* k10_3d_sw_small: at most 16384 sites, all steps of a call in one launch */
-#define TSU_POTTS3D_ROUTE_SW_TILES 3 /* k10_3d_sw_local / k10_3d_sw_merge / k10_3d_sw_resolve, once per step */
+#define TSU_POTTS3D_ROUTE_SMALL 0    /* route k10_3d_small (kernel k10_small<3>): at most 16384 sites in one workgroup's LDS, all sweeps of a call in one launch */
+#define TSU_POTTS3D_ROUTE_SWEEP 1    /* route k10_3d_sweep (k10_sweep<3>): one launch per half-sweep through HBM */
+#define TSU_POTTS3D_ROUTE_SW_SMALL 2 /* route k10_3d_sw_small (k10_sw_small<3>): at most 16384 sites, all steps of a call in one launch */
+#define TSU_POTTS3D_ROUTE_SW_TILES 3 /* route k10_3d_sw_tiles (k10_sw_local<3> / k10_sw_merge<3> / k10_sw_resolve<3>), once per step */
 
 /* Host only (no GPU needed): TSU_OK if (q, J, h[q] or NULL for zero, T) is a model the sweeps take, else TSU_E_INVALID: q outside
  * 2 .. 8, a non-finite J, h or T, T <= 0, (6 |J| + max h - min h) / T > 600 (the six-neighbour bound, whatever the depth), or an
@@ -46,7 +46,7 @@ int tsu_potts3d_fill(tsu_potts3d* lat, int colour);
  * (c >> 4, rho, hs, tag | replica << 8), TSU_TAG_ISING_HI and TSU_TAG_ISING_LO, key = seed); the rule is the same with up to six
  * neighbours: w_c = E[n_c] F[c], n_c = 0 .. 6 (csrc/potts_dev.h).  The counters are 32-bit words and wrap as in
  * 2-D; n_sweeps <= 2^31.  Results depend on (state, q, J, h, T, seed, sweep0, replica) only, never on the route.  TSU_POTTS_SMALL=0
- * in the environment (tests, read per call) sends every lattice to k10_3d_sweep. */
+ * in the environment (tests, read per call) sends every lattice to route k10_3d_sweep. */
 int tsu_potts3d_sweep(tsu_potts3d* lat, double T, int n_sweeps, uint64_t seed, uint32_t sweep0, uint32_t replica);
 
 /* n_steps Swendsen-Wang steps (J > 0 and h = 0; otherwise TSU_E_UNSUPPORTED and the state is untouched), step0 + n_steps <= 2^32.
@@ -61,7 +61,7 @@ int tsu_potts3d_cluster_sweep(tsu_potts3d* lat, double T, int n_steps, uint64_t 
 /* TSU_POTTS3D_ROUTE_* a call of this algorithm (TSU_POTTS_HEAT_BATH, TSU_POTTS_SWENDSEN_WANG) would take now */
 int tsu_potts3d_route(tsu_potts3d* lat, int algorithm, int* route);
 
-/* One measurement (k10_3d_measure; synchronises): row[0] = n_eq, row[1 + c] = N_c (TSU_POTTS_RECORD_WORDS words), exact integers */
+/* One measurement (k10_measure<3>; synchronises): row[0] = n_eq, row[1 + c] = N_c (TSU_POTTS_RECORD_WORDS words), exact integers */
 int tsu_potts3d_measure(tsu_potts3d* lat, int64_t* row);
 
 /* n_meas times: sweeps_between updates of `algorithm` at T, then one measurement into row k of the handle's record, all on the

@@ -232,10 +232,16 @@ def _build_rule_check(tmp_path):
 
 
 def test_the_kernels_use_the_shared_rule():
-    kernels = open(os.path.join(CSRC, "potts3d.hip")).read()
-    assert '#include "potts_dev.h"' in kernels and "potts_cum6(" in kernels and "potts_pick(" in kernels and "potts_tables6(" in kernels
+    # one body for both dimensions: the kernels in potts_kern_dev.h, the host side in potts_host.h, instantiated by potts3d.hip
+    kernels = open(os.path.join(CSRC, "potts_kern_dev.h")).read()
+    assert '#include "potts_dev.h"' in kernels and "potts_cum(" in kernels and "potts_pick(" in kernels and "PottsTabN<2 * DIM>" in kernels
+    host = open(os.path.join(CSRC, "potts_host.h")).read()
+    assert '#include "potts_kern_dev.h"' in host and "potts_tables(" in host and "PottsTabN<2 * L::DIM>" in host
+    unit = open(os.path.join(CSRC, "potts3d.hip")).read()
+    assert '#include "potts_host.h"' in unit and "PottsHandle<3>" in unit and "potts_check_model<6>" in unit
     rule = open(os.path.join(CSRC, "potts_dev.h")).read()
-    assert "struct PottsTab6" in rule and "double E[7]" in rule and "struct PottsTab {" in rule and "double E[5]" in rule
+    assert "struct PottsTabN" in rule and "double E[NB + 1]" in rule
+    assert "using PottsTab6 = PottsTabN<6>" in rule and "using PottsTab = PottsTabN<4>" in rule  # E[7] and E[5]
 
 
 def test_six_neighbour_rule_on_the_host_equals_the_twin_without_a_fused_multiply_add(tmp_path):

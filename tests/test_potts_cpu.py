@@ -150,7 +150,7 @@ def test_header_symbols_and_prototypes():
     assert not any(re.search(r"\b" + n + r"\s*\(", re.sub(r"/\*.*?\*/", "", top, flags=re.S)) for n in NEW_SYMBOLS)
     with open(os.path.join(CSRC, "build.sh")) as f:
         build = f.read()
-    assert "tsu_hip_potts.h" in build and "potts_dev.h" in build
+    assert "tsu_hip_potts.h" in build and "potts_dev.h" in build and "potts_host.h" in build
     with open(os.path.join(ROOT, "include", "tsu_hip_potts.h")) as f:
         header = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
     declared = sorted(set(re.findall(r"\b(tsu_[a-z0-9_]+)\s*\(", header)))
@@ -200,8 +200,10 @@ def test_rule_header_needs_no_hip_on_the_host():
     assert "__dmul_rn" in text and "__dadd_rn" in text
     plain = re.sub(r"#if defined\(__HIPCC__\).*?#else", "", text, count=1, flags=re.S)
     assert sorted(re.findall(r"#\s*include\s*[<\"]([^>\"]+)", plain)) == ["math.h", "stdint.h"]
-    kernels = open(os.path.join(CSRC, "potts2d.hip")).read()
+    kernels = open(os.path.join(CSRC, "potts_kern_dev.h")).read()  # the kernels of both handles; potts2d.hip instantiates them
     assert '#include "potts_dev.h"' in kernels and "potts_cum(" in kernels and "potts_pick(" in kernels
+    assert '#include "potts_host.h"' in open(os.path.join(CSRC, "potts2d.hip")).read()
+    assert '#include "potts_kern_dev.h"' in open(os.path.join(CSRC, "potts_host.h")).read()
 
 
 def test_rule_on_the_host_equals_the_twin_without_a_fused_multiply_add(tmp_path):

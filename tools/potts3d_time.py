@@ -99,10 +99,11 @@ def kernel_resources():
     for line in r.stderr.splitlines():
         m = re.search(r"Function Name: (\S+)", line)
         if m:
-            name = re.search(r"k10_3d_[a-z_]+", m.group(1))
-            name = name.group(0) if name else None
+            # potts3d.hip instantiates potts_kern_dev.h's templates at DIM = 3 only; the labels keep the 3-D route names' prefix
+            name = re.search(r"k10_[a-z_]+", m.group(1))
+            name = name.group(0).replace("k10_", "k10_3d_") if name else None
             if name == "k10_3d_sweep":  # its two instantiations: rows of whole octets (16-byte loads) or any width (byte loads)
-                name += "<rows16>" if "ILb1E" in m.group(1) else "<bytes>"
+                name += "<rows16>" if "Lb1E" in m.group(1) else "<bytes>"
             if name == "k10_3d_sw_small" and "SwRecOut" in m.group(1):
                 name = None  # the measured instantiation sw_host.h names; never launched
             if name:

@@ -2,7 +2,7 @@
 """Find half-sweeps in which one octet of a Potts lattice holds two sites that the low half of u decides (no GPU needed).
 
 K10's heat bath decides a site from hi16 of its uniform where it can and draws the octet's lo16 Philox block for the first site that
-needs it; a second such site of the same octet reuses the block (`d.have_lo` in potts_site / potts_site6).  That happens about
+needs it; a second such site of the same octet reuses the block (`d.have_lo` in potts_site, csrc/potts_kern_dev.h).  That happens about
 3e-7 times per octet and half-sweep, so no test meets it by chance.  With J = 0 the cumulative sums do not depend on the neighbours,
 so the sites are known from Philox alone: this script walks the half-sweeps of a (rows, cols) lattice with the twin's own uniforms,
 `cumulative` and `pick` (tests/helpers/potts_twin.py) and prints every (hs, global row, octet) that holds at least two of them.

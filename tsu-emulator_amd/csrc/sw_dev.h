@@ -10,12 +10,16 @@
 // The __global__ kernels of a step stay in their files with their own launch bounds (the measuring passes of the cluster-size
 // records, which read no bond, are at the end of this file).  DIM = 2 compiles every z term out (no depth, no third
 // seam family; rows stay ints).  The seam decoder and the root chase serve K7's replica cluster moves (ising2d_icm.hip) as well.
+// K10's Potts lattices (potts_kern_dev.h, both dimensions) use the structs, the seam decoder and the root chase with a bond policy
+// of their own (PottsBonds: two equal colours) and their own resolve pass, which writes a colour instead of flipping a spin.
 #pragma once
 #include <type_traits>
 
 #include "uf_dev.h"
 
 namespace {
+
+constexpr int kSwMaxThreads = 1024;  // the launch bound of the one-workgroup kernels and of the 3-D tile pass; the host's lane cap
 
 struct SwGeom {
     long long pitch;

@@ -1,6 +1,7 @@
-// sw_host.h -- the host side of a Swendsen-Wang call, written once for K6 (ising2d_cluster.hip) and K8 (ising3d_cluster.hip): the
-// counter checks, the one-workgroup launch with its batch upload, the loop of the multi-tile route and the batch entry point's loop.
-// A traits struct Tr per dimension supplies what differs:
+// sw_host.h -- the host side of a Swendsen-Wang call, written once for K6 (ising2d_cluster.hip), K8 (ising3d_cluster.hip) and K10
+// (potts_host.h: one traits template, PottsSw, for its 2-D and 3-D handles): the counter checks, the one-workgroup launch with its
+// batch upload, the loop of the multi-tile route and the batch entry point's loop.
+// A traits struct Tr per handle type supplies what differs:
 //   Lattice, Bonds, Model      the handle (with ctx, h_err and a tsu_sw_scratch sw), the bond policy of sw_dev.h, the model
 //                              parameters of one call (K6: J and T; K8: T)
 //   who, refuse_twice          the prefix of every message; whether a batch refuses a lattice listed twice
@@ -24,7 +25,6 @@
 namespace {
 
 constexpr int kSwSmallSites = 16384;  // one-workgroup route: at most this many sites (80 KB of LDS, 144 KB measured); also the largest tile
-constexpr int kSwMaxThreads = 1024;
 
 template <int DIM>
 long long sw_sites(const SwGeom& g) {

@@ -762,19 +762,30 @@ class Lattice:
         return pr, pc
 
 
-def potts_tables(q, J, h, T):
-    """Host helper of the library (no GPU needed): (E[0 .. 4], F[0 .. q - 1]) of the Potts heat-bath rule, or ValueError with the
-    model refused (tsu_potts2d_check_model)."""
+def _potts_tables(prefix, nb, q, J, h, T):
+    """(E[0 .. nb], F[0 .. q - 1]) of the heat-bath rule with nb neighbours, from tsu_<prefix>_check_model."""
     lib = load_library()
     hh = None if h is None else np.ascontiguousarray(h, dtype=np.float64)
     if hh is not None and hh.shape != (int(q),) and 2 <= int(q) <= POTTS_MAX_Q:
         raise ValueError(f"h must hold q = {int(q)} values")
-    t = np.zeros(5 + POTTS_MAX_Q, np.float64)
-    rc = lib.tsu_potts2d_check_model(int(q), float(J), None if hh is None else _ptr(hh, _f64p), float(T), _ptr(t, _f64p))
+    t = np.zeros(nb + 1 + POTTS_MAX_Q, np.float64)
+    rc = getattr(lib, f"tsu_{prefix}_check_model")(int(q), float(J), None if hh is None else _ptr(hh, _f64p), float(T), _ptr(t, _f64p))
     if rc != TSU_OK:
         raise ValueError("the Potts model (q, J, h, T) is refused: q outside 2 .. 8, a non-finite value, T <= 0 or "
-                         "(4 |J| + max h - min h) / T > 600")
-    return t[:5].copy(), t[5:5 + int(q)].copy()
+                         f"({nb} |J| + max h - min h) / T > 600")
+    return t[:nb + 1].copy(), t[nb + 1:nb + 1 + int(q)].copy()
+
+
+def potts_tables(q, J, h, T):
+    """Host helper of the library (no GPU needed): (E[0 .. 4], F[0 .. q - 1]) of the Potts heat-bath rule, or ValueError with the
+    model refused (tsu_potts2d_check_model)."""
+    return _potts_tables("potts2d", 4, q, J, h, T)
+
+
+def potts3d_tables(q, J, h, T):
+    """Host helper of the library (no GPU needed): (E[0 .. 6], F[0 .. q - 1]) of the six-neighbour Potts heat-bath rule, or ValueError
+    with the model refused (tsu_potts3d_check_model)."""
+    return _potts_tables("potts3d", 6, q, J, h, T)
 
 
 def potts_cluster_threshold(J, T):
@@ -784,83 +795,6 @@ def potts_cluster_threshold(J, T):
     if lib.tsu_potts2d_cluster_threshold(float(J), float(T), C.byref(t)) != TSU_OK:
         raise ValueError("the Potts cluster threshold needs finite J > 0 and T > 0")
     return t.value
-
-
-class PottsLattice:
-    """tsu_potts2d handle: a rows x cols lattice of colours 0 .. q - 1 (int8) on the GPU (K10)."""
-
-    def __init__(self, rows, cols, q, periodic=True, ctx=None):
-        self.ctx = ctx or Context.default()
-        self.lib = self.ctx.lib
-        self.rows, self.cols, self.q, self.periodic = int(rows), int(cols), int(q), bool(periodic)
-        h = _vp()
-        self.ctx.check(self.lib.tsu_potts2d_create(self.ctx.h, self.rows, self.cols, self.q, int(self.periodic), C.byref(h)))
-        self.h = h
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.lib.tsu_potts2d_destroy(self.h)
-            self.h = None
-
-    def __del__(self, _finalizing=sys.is_finalizing):
-        if not _finalizing():
-            self.close()
-
-    def set_model(self, J, h=None):
-        hh = None if h is None else np.ascontiguousarray(h, dtype=np.float64)
-        if hh is not None and hh.shape != (self.q,):
-            raise ValueError(f"h must hold q = {self.q} values")
-        self.ctx.check(self.lib.tsu_potts2d_set_model(self.h, float(J), None if hh is None else _ptr(hh, _f64p)))
-
-    def set_spins(self, colours):
-        s = np.ascontiguousarray(colours, dtype=np.int8)
-        if s.size != self.rows * self.cols:
-            raise ValueError(f"colours must hold {self.rows} x {self.cols} values")
-        self.ctx.check(self.lib.tsu_potts2d_set_spins(self.h, _ptr(s, _i8p)))
-
-    def get_spins(self):
-        out = np.empty((self.rows, self.cols), dtype=np.int8)
-        self.ctx.check(self.lib.tsu_potts2d_get_spins(self.h, _ptr(out, _i8p)))
-        return out
-
-    def fill(self, colour):
-        self.ctx.check(self.lib.tsu_potts2d_fill(self.h, int(colour)))
-
-    def sweep(self, T, n_sweeps, seed, sweep0=0, replica=0):
-        self.ctx.check(self.lib.tsu_potts2d_sweep(self.h, float(T), int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
-
-    def cluster_sweep(self, T, n_steps, seed, step0=0, replica=0):
-        self.ctx.check(self.lib.tsu_potts2d_cluster_sweep(self.h, float(T), int(n_steps), _seed(seed), _counter("step0", step0),
-                                                          _replica(replica)))
-
-    def route(self, algorithm=POTTS_HEAT_BATH):
-        r = C.c_int(-1)
-        self.ctx.check(self.lib.tsu_potts2d_route(self.h, int(algorithm), C.byref(r)))
-        return POTTS_ROUTES[r.value]
-
-    def measure(self):
-        """(n_eq, N_0 .. N_{q-1}) of the current state as exact integers (synchronises)."""
-        row = np.zeros(POTTS_RECORD_WORDS, np.int64)
-        self.ctx.check(self.lib.tsu_potts2d_measure(self.h, _ptr(row, _i64p)))
-        return int(row[0]), row[1:1 + self.q].copy()
-
-    def run(self, T, n_meas, sweeps_between, algorithm, seed, counter0=0, replica=0):
-        self.ctx.check(self.lib.tsu_potts2d_run(self.h, float(T), int(n_meas), int(sweeps_between), int(algorithm), _seed(seed),
-                                                _counter("counter0", counter0), _replica(replica)))
-
-    def record(self):
-        """The rows of the most recent run (synchronises): (n_meas, 9) int64, n_eq then N_0 .. N_7."""
-        n = C.c_int(0)
-        self.ctx.check(self.lib.tsu_potts2d_record(self.h, None, 0, C.byref(n)))
-        rows = np.zeros((n.value, POTTS_RECORD_WORDS), np.int64)
-        if n.value:
-            self.ctx.check(self.lib.tsu_potts2d_record(self.h, _ptr(rows, _i64p), n.value, C.byref(n)))
-        return rows
-
-    def launch_count(self):
-        n = C.c_uint64(0)
-        self.ctx.check(self.lib.tsu_potts2d_launch_count(self.h, C.byref(n)))
-        return n.value
 
 
 def periodic_axes(periodic):
@@ -873,38 +807,23 @@ def periodic_axes(periodic):
     return p
 
 
-def potts3d_tables(q, J, h, T):
-    """Host helper of the library (no GPU needed): (E[0 .. 6], F[0 .. q - 1]) of the six-neighbour Potts heat-bath rule, or ValueError
-    with the model refused (tsu_potts3d_check_model)."""
-    lib = load_library()
-    hh = None if h is None else np.ascontiguousarray(h, dtype=np.float64)
-    if hh is not None and hh.shape != (int(q),) and 2 <= int(q) <= POTTS_MAX_Q:
-        raise ValueError(f"h must hold q = {int(q)} values")
-    t = np.zeros(7 + POTTS_MAX_Q, np.float64)
-    rc = lib.tsu_potts3d_check_model(int(q), float(J), None if hh is None else _ptr(hh, _f64p), float(T), _ptr(t, _f64p))
-    if rc != TSU_OK:
-        raise ValueError("the Potts model (q, J, h, T) is refused: q outside 2 .. 8, a non-finite value, T <= 0 or "
-                         "(6 |J| + max h - min h) / T > 600")
-    return t[:7].copy(), t[7:7 + int(q)].copy()
+class _PottsHandle:
+    """What the two K10 handles share: every call but the constructor.  A subclass sets _prefix (the C symbols are
+    tsu_<prefix>_<call>) and _routes, and its constructor sets q and shape and creates the handle through _create."""
 
+    def _call(self, name, *args):
+        self.ctx.check(getattr(self.lib, f"tsu_{self._prefix}_{name}")(*args))
 
-class PottsLattice3D:
-    """tsu_potts3d handle: a depth x rows x cols lattice of colours 0 .. q - 1 (int8) on the GPU (K10 in 3-D); periodic is a bool
-    (all three axes) or (p_z, p_r, p_c)."""
-
-    def __init__(self, depth, rows, cols, q, periodic=True, ctx=None):
+    def _create(self, ctx, *args):
         self.ctx = ctx or Context.default()
         self.lib = self.ctx.lib
-        self.depth, self.rows, self.cols, self.q = int(depth), int(rows), int(cols), int(q)
-        self.periodic = periodic_axes(periodic)
         h = _vp()
-        pz, pr, pc = (int(x) for x in self.periodic)
-        self.ctx.check(self.lib.tsu_potts3d_create(self.ctx.h, self.depth, self.rows, self.cols, self.q, pz, pr, pc, C.byref(h)))
+        self._call("create", self.ctx.h, *args, C.byref(h))
         self.h = h
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.tsu_potts3d_destroy(self.h)
+            getattr(self.lib, f"tsu_{self._prefix}_destroy")(self.h)
             self.h = None
 
     def __del__(self, _finalizing=sys.is_finalizing):
@@ -915,57 +834,78 @@ class PottsLattice3D:
         hh = None if h is None else np.ascontiguousarray(h, dtype=np.float64)
         if hh is not None and hh.shape != (self.q,):
             raise ValueError(f"h must hold q = {self.q} values")
-        self.ctx.check(self.lib.tsu_potts3d_set_model(self.h, float(J), None if hh is None else _ptr(hh, _f64p)))
+        self._call("set_model", self.h, float(J), None if hh is None else _ptr(hh, _f64p))
 
     def set_spins(self, colours):
         s = np.ascontiguousarray(colours, dtype=np.int8)
-        if s.size != self.depth * self.rows * self.cols:
-            raise ValueError(f"colours must hold {self.depth} x {self.rows} x {self.cols} values")
-        self.ctx.check(self.lib.tsu_potts3d_set_spins(self.h, _ptr(s, _i8p)))
+        if s.size != int(np.prod(self.shape)):
+            raise ValueError("colours must hold " + " x ".join(str(n) for n in self.shape) + " values")
+        self._call("set_spins", self.h, _ptr(s, _i8p))
 
     def get_spins(self):
-        out = np.empty((self.depth, self.rows, self.cols), dtype=np.int8)
-        self.ctx.check(self.lib.tsu_potts3d_get_spins(self.h, _ptr(out, _i8p)))
+        out = np.empty(self.shape, dtype=np.int8)
+        self._call("get_spins", self.h, _ptr(out, _i8p))
         return out
 
     def fill(self, colour):
-        self.ctx.check(self.lib.tsu_potts3d_fill(self.h, int(colour)))
+        self._call("fill", self.h, int(colour))
 
     def sweep(self, T, n_sweeps, seed, sweep0=0, replica=0):
-        self.ctx.check(self.lib.tsu_potts3d_sweep(self.h, float(T), int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica)))
+        self._call("sweep", self.h, float(T), int(n_sweeps), _seed(seed), _counter("sweep0", sweep0), _replica(replica))
 
     def cluster_sweep(self, T, n_steps, seed, step0=0, replica=0):
-        self.ctx.check(self.lib.tsu_potts3d_cluster_sweep(self.h, float(T), int(n_steps), _seed(seed), _counter("step0", step0),
-                                                          _replica(replica)))
+        self._call("cluster_sweep", self.h, float(T), int(n_steps), _seed(seed), _counter("step0", step0), _replica(replica))
 
     def route(self, algorithm=POTTS_HEAT_BATH):
         r = C.c_int(-1)
-        self.ctx.check(self.lib.tsu_potts3d_route(self.h, int(algorithm), C.byref(r)))
-        return POTTS3D_ROUTES[r.value]
+        self._call("route", self.h, int(algorithm), C.byref(r))
+        return self._routes[r.value]
 
     def measure(self):
         """(n_eq, N_0 .. N_{q-1}) of the current state as exact integers (synchronises)."""
         row = np.zeros(POTTS_RECORD_WORDS, np.int64)
-        self.ctx.check(self.lib.tsu_potts3d_measure(self.h, _ptr(row, _i64p)))
+        self._call("measure", self.h, _ptr(row, _i64p))
         return int(row[0]), row[1:1 + self.q].copy()
 
     def run(self, T, n_meas, sweeps_between, algorithm, seed, counter0=0, replica=0):
-        self.ctx.check(self.lib.tsu_potts3d_run(self.h, float(T), int(n_meas), int(sweeps_between), int(algorithm), _seed(seed),
-                                                _counter("counter0", counter0), _replica(replica)))
+        self._call("run", self.h, float(T), int(n_meas), int(sweeps_between), int(algorithm), _seed(seed), _counter("counter0", counter0),
+                   _replica(replica))
 
     def record(self):
         """The rows of the most recent run (synchronises): (n_meas, 9) int64, n_eq then N_0 .. N_7."""
         n = C.c_int(0)
-        self.ctx.check(self.lib.tsu_potts3d_record(self.h, None, 0, C.byref(n)))
+        self._call("record", self.h, None, 0, C.byref(n))
         rows = np.zeros((n.value, POTTS_RECORD_WORDS), np.int64)
         if n.value:
-            self.ctx.check(self.lib.tsu_potts3d_record(self.h, _ptr(rows, _i64p), n.value, C.byref(n)))
+            self._call("record", self.h, _ptr(rows, _i64p), n.value, C.byref(n))
         return rows
 
     def launch_count(self):
         n = C.c_uint64(0)
-        self.ctx.check(self.lib.tsu_potts3d_launch_count(self.h, C.byref(n)))
+        self._call("launch_count", self.h, C.byref(n))
         return n.value
+
+
+class PottsLattice(_PottsHandle):
+    """tsu_potts2d handle: a rows x cols lattice of colours 0 .. q - 1 (int8) on the GPU (K10)."""
+    _prefix, _routes = "potts2d", POTTS_ROUTES
+
+    def __init__(self, rows, cols, q, periodic=True, ctx=None):
+        self.rows, self.cols, self.q, self.periodic = int(rows), int(cols), int(q), bool(periodic)
+        self.shape = (self.rows, self.cols)
+        self._create(ctx, self.rows, self.cols, self.q, int(self.periodic))
+
+
+class PottsLattice3D(_PottsHandle):
+    """tsu_potts3d handle: a depth x rows x cols lattice of colours 0 .. q - 1 (int8) on the GPU (K10 in 3-D); periodic is a bool
+    (all three axes) or (p_z, p_r, p_c)."""
+    _prefix, _routes = "potts3d", POTTS3D_ROUTES
+
+    def __init__(self, depth, rows, cols, q, periodic=True, ctx=None):
+        self.depth, self.rows, self.cols, self.q = int(depth), int(rows), int(cols), int(q)
+        self.periodic = periodic_axes(periodic)
+        self.shape = (self.depth, self.rows, self.cols)
+        self._create(ctx, self.depth, self.rows, self.cols, self.q, *(int(x) for x in self.periodic))
 
 
 def potts_muca_geometry(depth, rows, cols, periodic):
