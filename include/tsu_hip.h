@@ -412,6 +412,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * prototypes are _hip.POTTS_MUCA_SIGNATURES in Python. */
 #include "tsu_hip_potts_muca.h"
 
+/* K12: Potts lattices with per-bond couplings and per-site colour fields, 2-D and 3-D on one handle: heat-bath sweeps, Swendsen-Wang
+ * steps on non-negative couplings, integer observables and a float64 energy (tsu_potts_dis_*): declared in
+ * tsu_hip_potts_disorder.h, which this header includes; its prototypes are _hip.POTTS_DISORDER_SIGNATURES in Python. */
+#include "tsu_hip_potts_disorder.h"
+
 /* K6 / K8: cluster-size records of the Swendsen-Wang steps, the exact integers behind the improved estimators
  * (tsu_isingNd_cluster_measure / _cluster_record): declared in tsu_hip_cluster_measure.h, which this header includes; its prototypes
  * are _hip.CLUSTER_MEASURE_SIGNATURES in Python. */

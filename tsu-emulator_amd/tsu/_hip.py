@@ -378,6 +378,25 @@ POTTS_MUCA_SIGNATURES = {
     "tsu_potts_muca_route": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "tsu_potts_muca_launch_count": (C.c_int, [_vp, _u64p]),
 }
+# name -> (restype, argtypes): mirrors include/tsu_hip_potts_disorder.h (the header tsu_hip.h includes) one to one
+POTTS_DISORDER_SIGNATURES = {
+    "tsu_potts_dis_site_thresholds": (C.c_int, [C.c_int, _f64p, C.c_double, _u64p]),
+    "tsu_potts_dis_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.POINTER(_vp)]),
+    "tsu_potts_dis_destroy": (C.c_int, [_vp]),
+    "tsu_potts_dis_set_disorder": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p]),
+    "tsu_potts_dis_set_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_potts_dis_get_spins": (C.c_int, [_vp, _i8p]),
+    "tsu_potts_dis_fill": (C.c_int, [_vp, C.c_int]),
+    "tsu_potts_dis_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts_dis_cluster_sweep": (C.c_int, [_vp, C.c_double, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts_dis_route": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
+    "tsu_potts_dis_measure": (C.c_int, [_vp, _i64p, _f64p]),
+    "tsu_potts_dis_run": (C.c_int, [_vp, C.c_double, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_uint32]),
+    "tsu_potts_dis_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
+    "tsu_potts_dis_launch_count": (C.c_int, [_vp, _u64p]),
+}
+POTTS_DIS_RECORD_WORDS = 10  # TSU_POTTS_DIS_RECORD_WORDS
+POTTS_DIS_ROUTES = ("k12_small", "k12_sweep", "k12_sw_small", "k12_sw_tiles")  # TSU_POTTS_DIS_ROUTE_*
 POTTS_MUCA_ROUTES = ("k11_muca_lds", "k11_muca_global", "k11_muca_atomics")  # TSU_POTTS_MUCA_ROUTE_*
 POTTS_MUCA_MAX_SITES = 65536       # TSU_POTTS_MUCA_MAX_SITES
 POTTS_MUCA_MAX_WALKERS = 1 << 20   # TSU_POTTS_MUCA_MAX_WALKERS
@@ -414,7 +433,8 @@ def load_library():
                               + list(MULTISPIN_SIGNATURES.items()) + list(MULTISPIN_PT_SIGNATURES.items())
                               + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())
                               + list(CLUSTER_MEASURE_SIGNATURES.items()) + list(POTTS_SIGNATURES.items())
-                              + list(POTTS3D_SIGNATURES.items()) + list(POTTS_MUCA_SIGNATURES.items())):
+                              + list(POTTS3D_SIGNATURES.items()) + list(POTTS_MUCA_SIGNATURES.items())
+                              + list(POTTS_DISORDER_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -906,6 +926,58 @@ class PottsLattice3D(_PottsHandle):
         self.periodic = periodic_axes(periodic)
         self.shape = (self.depth, self.rows, self.cols)
         self._create(ctx, self.depth, self.rows, self.cols, self.q, *(int(x) for x in self.periodic))
+
+
+def potts_site_thresholds(a, T):
+    """Host helper of the library (no GPU needed): steps 2 - 5 of K12's heat-bath rule for one site, the integer thresholds
+    thr[0 .. q - 1] of the sums a[0 .. q - 1] at temperature T (tsu_potts_dis_site_thresholds)."""
+    lib = load_library()
+    aa = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    thr = np.zeros(aa.size, np.uint64)
+    if lib.tsu_potts_dis_site_thresholds(int(aa.size), _ptr(aa, _f64p), float(T), _ptr(thr, _u64p)) != TSU_OK:
+        raise ValueError("the site is refused: q outside 2 .. 8, a non-finite sum or T, or T <= 0")
+    return thr
+
+
+class PottsDisorderLattice(_PottsHandle):
+    """tsu_potts_dis handle (K12): a depth x rows x cols lattice of colours 0 .. q - 1 with per-bond couplings and a per-site colour
+    field; shape (rows, cols) gives the 2-D lattice (depth 1, open z).  The arrays are checked and rounded to fp32 by the caller
+    (tsu.models.potts); ``h`` is colour-major, (q,) + shape."""
+    _prefix, _routes = "potts_dis", POTTS_DIS_ROUTES
+
+    def __init__(self, shape, q, periodic=True, ctx=None):
+        self.shape = tuple(int(n) for n in shape)
+        self.q = int(q)
+        dims = (1,) + self.shape if len(self.shape) == 2 else self.shape
+        if len(self.shape) == 2:
+            self.periodic = (False, bool(periodic), bool(periodic))
+        else:
+            self.periodic = periodic_axes(periodic)
+        per = np.array([int(x) for x in self.periodic], np.int32)
+        self._create(ctx, *dims, self.q, _ptr(per, _i32p))
+
+    def set_disorder(self, J_right, J_down, J_layer=None, h=None):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (J_right, J_down, J_layer, h)]
+        for a, want in zip(arrs, (self.shape, self.shape, self.shape, (self.q,) + self.shape)):
+            if a is not None and a.shape != want:
+                raise ValueError(f"a disorder array has shape {a.shape}, expected {want}")
+        self._call("set_disorder", self.h, *(None if a is None else _ptr(a, _f32p) for a in arrs))
+
+    def measure(self):
+        """(n_eq, N_0 .. N_{q-1}, E): exact integers and the float64 energy in the device's fixed order (synchronises)."""
+        row = np.zeros(POTTS_RECORD_WORDS, np.int64)
+        e = C.c_double(0.0)
+        self._call("measure", self.h, _ptr(row, _i64p), C.byref(e))
+        return int(row[0]), row[1:1 + self.q].copy(), e.value
+
+    def record(self):
+        """The rows of the most recent run (synchronises): ((n_meas, 9) int64: n_eq then N_0 .. N_7, (n_meas,) float64: E)."""
+        n = C.c_int(0)
+        self._call("record", self.h, None, 0, C.byref(n))
+        rows = np.zeros((n.value, POTTS_DIS_RECORD_WORDS), np.int64)
+        if n.value:
+            self._call("record", self.h, _ptr(rows, _i64p), n.value, C.byref(n))
+        return rows[:, :POTTS_RECORD_WORDS].copy(), rows[:, POTTS_RECORD_WORDS].copy().view(np.float64)
 
 
 def potts_muca_geometry(depth, rows, cols, periodic):
