@@ -853,21 +853,29 @@ static __device__ __forceinline__ void tile_body(const TiledParams& p, const int
     // number; the host clears the buffer when the numbering restarts or the strip layout changes.)
     // (nibble planes: an element is the octet's dword, the number sits above it in bits 32..45; QUAD: the flag is bit 3 of a byte
     // and the number takes bits 0..2 and 4..7 of bytes 0 and 1)
+    // On byte planes the number stands once more in the element's other dword (bytes 4 and 5) and the reader compares both
+    // copies: an element is accepted only whole, whatever the width and the atomicity of the load that fetched it.  (Nibble
+    // planes keep it above the flag dword alone: with both copies 8192^2 measured 0.6 % slower, profiles/k1_strip_dma_ab.txt.)  (An exchange that fetches the strips with 16-byte LDS-direct loads under a first pass of the
+    // next half-sweep was built on this and measured slower than this one: profiles/k1_strip_dma_notes.txt.)
     const int n_tb = 2 * k * WO, n_lr = H;  // elements of a top/bottom and of a left/right strip
     const int xstride = 2 * n_tb + 2 * p.tile_h;  // (tile rows of a flexible cut differ by two rows: one slot size for all)
     // The last tile column of a lattice whose width is not a multiple of the tile width holds wi < WO lattice octets: its last
     // interior octet is tile octet wi, its right halo tile octet wi + 1; what lies beyond is the lattice's periodic continuation
     // from the stage, computed along and never read by anything that counts (it decays like the far side of any halo octet).
     const int wi = (p.nchunks + p.q_shift - q0) < WO ? (p.nchunks + p.q_shift - q0) : WO;
-    constexpr uint64_t TAG_MASK = NIB ? 0xFFFFFFFF00000000ull : (QUAD ? 0xF7F7ull : 0xFEFEull);
+    constexpr uint64_t TAG_MASK = NIB ? 0xFFFFFFFF00000000ull : (QUAD ? 0x0000F7F70000F7F7ull : 0x0000FEFE0000FEFEull);
     constexpr uint64_t FLAG_MASK = NIB ? 0x11111111ull : FL * 0x0101010101010101ull;
     auto strip_tag = [&](int gen) -> uint64_t {
         const uint32_t G = R->gen0 + (uint32_t)gen;
+        if (NIB) return (uint64_t)G << 32;
+        uint64_t t;
         if (QUAD) {
             auto beside_bit3 = [](uint32_t g7) { return (uint64_t)((g7 & 7u) | ((g7 >> 3) << 4)); };
-            return beside_bit3(G & 0x7Fu) | (beside_bit3((G >> 7) & 0x7Fu) << 8);
+            t = beside_bit3(G & 0x7Fu) | (beside_bit3((G >> 7) & 0x7Fu) << 8);
+        } else {
+            t = ((uint64_t)(G & 0x7Fu) << 1) | ((uint64_t)((G >> 7) & 0x7Fu) << 9);
         }
-        return NIB ? ((uint64_t)G << 32) : (((uint64_t)(G & 0x7Fu) << 1) | ((uint64_t)((G >> 7) & 0x7Fu) << 9));
+        return t | (t << 32);
     };
     // publish generation gen's boundary strips: its first / last 2k interior rows and first / last interior octet column
     auto publish = [&](int gen) {
