@@ -417,6 +417,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * tsu_hip_potts_disorder.h, which this header includes; its prototypes are _hip.POTTS_DISORDER_SIGNATURES in Python. */
 #include "tsu_hip_potts_disorder.h"
 
+/* K13: parallel tempering of K12's lattices, one or two ladders of walkers on one disorder with the swap pass, the record and the
+ * two ladders' contingency tables on the device (tsu_potts_pt_*): declared in tsu_hip_potts_pt.h, which this header includes; its
+ * prototypes are _hip.POTTS_PT_SIGNATURES in Python. */
+#include "tsu_hip_potts_pt.h"
+
 /* K6 / K8: cluster-size records of the Swendsen-Wang steps, the exact integers behind the improved estimators
  * (tsu_isingNd_cluster_measure / _cluster_record): declared in tsu_hip_cluster_measure.h, which this header includes; its prototypes
  * are _hip.CLUSTER_MEASURE_SIGNATURES in Python. */

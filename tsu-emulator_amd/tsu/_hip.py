@@ -395,6 +395,26 @@ POTTS_DISORDER_SIGNATURES = {
     "tsu_potts_dis_record": (C.c_int, [_vp, _i64p, C.c_int, C.POINTER(C.c_int)]),
     "tsu_potts_dis_launch_count": (C.c_int, [_vp, _u64p]),
 }
+# name -> (restype, argtypes): mirrors include/tsu_hip_potts_pt.h (the header tsu_hip.h includes) one to one
+POTTS_PT_SIGNATURES = {
+    "tsu_potts_pt_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "tsu_potts_pt_destroy": (C.c_int, [_vp]),
+    "tsu_potts_pt_set_disorder": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p]),
+    "tsu_potts_pt_set_temperatures": (C.c_int, [_vp, _f64p]),
+    "tsu_potts_pt_set_spins": (C.c_int, [_vp, C.c_int, C.c_int, _i8p]),
+    "tsu_potts_pt_get_spins": (C.c_int, [_vp, C.c_int, C.c_int, _i8p]),
+    "tsu_potts_pt_init": (C.c_int, [_vp, C.c_uint64, C.c_int]),
+    "tsu_potts_pt_advance": (C.c_int, [_vp, C.c_uint64]),
+    "tsu_potts_pt_run": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tsu_potts_pt_history": (C.c_int, [_vp, _f64p, _i64p, _i64p, _i32p]),
+    "tsu_potts_pt_overlap_tables": (C.c_int, [_vp, _i64p]),
+    "tsu_potts_pt_stats": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i32p, _u64p, _u64p]),
+    "tsu_potts_pt_energies": (C.c_int, [_vp, _f64p, _i64p]),
+    "tsu_potts_pt_route": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "tsu_potts_pt_launch_count": (C.c_int, [_vp, _u64p]),
+}
+POTTS_PT_ROUTES = ("k13_pt_small", "k13_pt_sweep")  # TSU_POTTS_PT_ROUTE_*
+POTTS_PT_MAX_TEMPS = 256  # kPtMaxTemps
 POTTS_DIS_RECORD_WORDS = 10  # TSU_POTTS_DIS_RECORD_WORDS
 POTTS_DIS_ROUTES = ("k12_small", "k12_sweep", "k12_sw_small", "k12_sw_tiles")  # TSU_POTTS_DIS_ROUTE_*
 POTTS_MUCA_ROUTES = ("k11_muca_lds", "k11_muca_global", "k11_muca_atomics")  # TSU_POTTS_MUCA_ROUTE_*
@@ -434,7 +454,7 @@ def load_library():
                               + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())
                               + list(CLUSTER_MEASURE_SIGNATURES.items()) + list(POTTS_SIGNATURES.items())
                               + list(POTTS3D_SIGNATURES.items()) + list(POTTS_MUCA_SIGNATURES.items())
-                              + list(POTTS_DISORDER_SIGNATURES.items())):
+                              + list(POTTS_DISORDER_SIGNATURES.items()) + list(POTTS_PT_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -978,6 +998,114 @@ class PottsDisorderLattice(_PottsHandle):
         if n.value:
             self._call("record", self.h, _ptr(rows, _i64p), n.value, C.byref(n))
         return rows[:, :POTTS_RECORD_WORDS].copy(), rows[:, POTTS_RECORD_WORDS].copy().view(np.float64)
+
+
+class PottsTemperingLattice:
+    """tsu_potts_pt handle (K13 parallel tempering): n_ladders ladders of n_temps walkers of one K12 lattice sharing one disorder;
+    shape (rows, cols) gives the 2-D lattice (depth 1, open z).  Walker w of ladder k has Philox key seed + k n_temps + w and
+    starts at slot w.  The arrays are checked and rounded to fp32 by the caller (tsu.models.potts_tempering)."""
+
+    def __init__(self, shape, q, periodic, n_temps, n_ladders=1, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.shape = tuple(int(n) for n in shape)
+        self.q, self.n_temps, self.n_ladders = int(q), int(n_temps), int(n_ladders)
+        dims = (1,) + self.shape if len(self.shape) == 2 else self.shape
+        if len(self.shape) == 2:
+            self.periodic = (False, bool(periodic), bool(periodic))
+        else:
+            self.periodic = periodic_axes(periodic)
+        per = np.array([int(x) for x in self.periodic], np.int32)
+        self._recorded = 0
+        h = _vp()
+        self.ctx.check(self.lib.tsu_potts_pt_create(self.ctx.h, *dims, self.q, _ptr(per, _i32p), self.n_temps, self.n_ladders, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_potts_pt_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def set_disorder(self, J_right, J_down, J_layer=None, h=None):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (J_right, J_down, J_layer, h)]
+        for a, want in zip(arrs, (self.shape, self.shape, self.shape, (self.q,) + self.shape)):
+            if a is not None and a.shape != want:
+                raise ValueError(f"a disorder array has shape {a.shape}, expected {want}")
+        self.ctx.check(self.lib.tsu_potts_pt_set_disorder(self.h, *(None if a is None else _ptr(a, _f32p) for a in arrs)))
+
+    def set_temperatures(self, T):
+        t = np.ascontiguousarray(T, dtype=np.float64).ravel()
+        if t.size != self.n_temps:
+            raise ValueError(f"need {self.n_temps} temperatures, got {t.size}")
+        self.ctx.check(self.lib.tsu_potts_pt_set_temperatures(self.h, _ptr(t, _f64p)))
+
+    def init(self, seed, initial=-1):
+        """initial -1: the colours stay (set them with set_spins afterwards); a colour 0 .. q - 1: that colour everywhere."""
+        self.ctx.check(self.lib.tsu_potts_pt_init(self.h, _seed(seed), int(initial)))
+        self._recorded = 0
+
+    def advance(self, n_sweeps):
+        self.ctx.check(self.lib.tsu_potts_pt_advance(self.h, _uint("n_sweeps", n_sweeps, 64)))
+
+    def run(self, n_rounds, swap_interval, swap=True, record=True):
+        self._recorded = 0
+        self.ctx.check(self.lib.tsu_potts_pt_run(self.h, int(n_rounds), int(swap_interval), int(bool(swap)), int(bool(record))))
+        self._recorded = int(n_rounds) if record else 0
+
+    def history(self):
+        """The last run's rows: E, n_eq, walker as (n_rounds, n_ladders, n_temps); N as (.., q); tables (n_rounds, n_temps, q, q) or
+        None with one ladder."""
+        n, nl, R, q = self._recorded, self.n_ladders, self.n_temps, self.q
+        E = np.zeros((n, nl, R))
+        M = np.zeros((n, nl, R), np.int64)
+        N = np.zeros((n, nl, R, POTTS_MAX_Q), np.int64)
+        W = np.zeros((n, nl, R), np.int32)
+        self.ctx.check(self.lib.tsu_potts_pt_history(self.h, _ptr(E, _f64p), _ptr(M, _i64p), _ptr(N, _i64p), _ptr(W, _i32p)))
+        tables = None
+        if nl == 2:
+            tables = np.zeros((n, R, q, q), np.int64)
+            self.ctx.check(self.lib.tsu_potts_pt_overlap_tables(self.h, _ptr(tables, _i64p)))
+        return {"E": E, "n_eq": M, "N": N[..., :q].copy(), "walker": W, "tables": tables}
+
+    def stats(self):
+        nl, R = self.n_ladders, self.n_temps
+        att, acc = np.zeros((nl, R - 1), np.int64), np.zeros((nl, R - 1), np.int64)
+        trips, was = np.zeros((nl, R), np.int64), np.zeros((nl, R), np.int32)
+        sw, rd = C.c_uint64(0), C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_potts_pt_stats(self.h, _ptr(att, _i64p), _ptr(acc, _i64p), _ptr(trips, _i64p), _ptr(was, _i32p),
+                                                   C.byref(sw), C.byref(rd)))
+        return {"attempts": att, "accepts": acc, "round_trips": trips, "walker_at_slot": was, "sweep_count": sw.value,
+                "round_count": rd.value}
+
+    def energies(self):
+        """(E, n_eq) of every walker now, as (n_ladders, n_temps) arrays indexed by walker."""
+        E = np.zeros((self.n_ladders, self.n_temps))
+        M = np.zeros((self.n_ladders, self.n_temps), np.int64)
+        self.ctx.check(self.lib.tsu_potts_pt_energies(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
+        return E, M
+
+    def get_spins(self, ladder, slot):
+        out = np.empty(self.shape, dtype=np.int8)
+        self.ctx.check(self.lib.tsu_potts_pt_get_spins(self.h, int(ladder), int(slot), _ptr(out, _i8p)))
+        return out
+
+    def set_spins(self, ladder, slot, colours):
+        s = np.ascontiguousarray(colours, dtype=np.int8).reshape(self.shape)
+        self.ctx.check(self.lib.tsu_potts_pt_set_spins(self.h, int(ladder), int(slot), _ptr(s, _i8p)))
+
+    def route(self):
+        r = C.c_int(-1)
+        self.ctx.check(self.lib.tsu_potts_pt_route(self.h, C.byref(r)))
+        return POTTS_PT_ROUTES[r.value]
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_potts_pt_launch_count(self.h, C.byref(n)))
+        return n.value
 
 
 def potts_muca_geometry(depth, rows, cols, periodic):
