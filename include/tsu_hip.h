@@ -422,6 +422,11 @@ int tsu_pt3d_launch_count(tsu_pt3d* pt, uint64_t* n_launches);
  * prototypes are _hip.POTTS_PT_SIGNATURES in Python. */
 #include "tsu_hip_potts_pt.h"
 
+/* K14: population annealing of K12's lattices, a fixed-size population of walkers on one disorder with the resampling, the record
+ * and the sweeps of several walkers per workgroup on the device (tsu_potts_pop_*): declared in tsu_hip_potts_pop.h, which this
+ * header includes; its prototypes are _hip.POTTS_POP_SIGNATURES in Python. */
+#include "tsu_hip_potts_pop.h"
+
 /* K6 / K8: cluster-size records of the Swendsen-Wang steps, the exact integers behind the improved estimators
  * (tsu_isingNd_cluster_measure / _cluster_record): declared in tsu_hip_cluster_measure.h, which this header includes; its prototypes
  * are _hip.CLUSTER_MEASURE_SIGNATURES in Python. */

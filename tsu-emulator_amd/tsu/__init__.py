@@ -41,6 +41,8 @@ from .models import (  # noqa: F401
     PottsModel2D,
     PottsModel3D,
     PottsMulticanonical,
+    PottsPopulationAnnealing,
+    PottsPopulationAnnealing3D,
     PottsTempering,
     PottsTempering3D,
     cluster_estimators,
@@ -51,6 +53,8 @@ from .models import (  # noqa: F401
     multispin_scan_3d,
     multispin_tempering_scan_3d,
     potts_multicanonical_scan,
+    potts_population_annealing_scan,
+    potts_population_annealing_scan_3d,
     potts_temperature_scan,
     potts_temperature_scan_3d,
     potts_tempering_scan,
@@ -70,6 +74,7 @@ __all__ = [
     "PopulationAnnealing","PopulationAnnealing3D", "PottsModel2D", "potts_temperature_scan", "PottsModel3D", "potts_temperature_scan_3d",
     "PottsMulticanonical", "potts_multicanonical_scan",
     "PottsTempering", "PottsTempering3D", "potts_tempering_scan", "potts_tempering_scan_3d",
+    "PottsPopulationAnnealing", "PottsPopulationAnnealing3D", "potts_population_annealing_scan", "potts_population_annealing_scan_3d",
     "LatticeTemperingEnsemble", "LatticeTemperingEnsemble3D", "edwards_anderson_samples", "ensemble_summary",
     "tempering_ensemble_scan", "tempering_ensemble_scan_3d", "MultispinGlass3D", "multispin_scan_3d",
     "GraphTempering", "multispin_quench_3d", "MultispinTempering3D", "multispin_tempering_scan_3d",

@@ -413,6 +413,27 @@ POTTS_PT_SIGNATURES = {
     "tsu_potts_pt_route": (C.c_int, [_vp, C.POINTER(C.c_int)]),
     "tsu_potts_pt_launch_count": (C.c_int, [_vp, _u64p]),
 }
+# name -> (restype, argtypes): mirrors include/tsu_hip_potts_pop.h (the header tsu_hip.h includes) one to one
+POTTS_POP_SIGNATURES = {
+    "tsu_potts_pop_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int, C.POINTER(_vp)]),
+    "tsu_potts_pop_destroy": (C.c_int, [_vp]),
+    "tsu_potts_pop_set_disorder": (C.c_int, [_vp, _f32p, _f32p, _f32p, _f32p]),
+    "tsu_potts_pop_set_schedule": (C.c_int, [_vp, _f64p, C.c_int]),
+    "tsu_potts_pop_init": (C.c_int, [_vp, C.c_uint64, C.c_int, C.c_int]),
+    "tsu_potts_pop_advance": (C.c_int, [_vp, C.c_uint64]),
+    "tsu_potts_pop_run": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tsu_potts_pop_history": (C.c_int, [_vp, _f64p, _i64p, _i64p, _u32p, _i32p, _u64p, _u64p, _f64p]),
+    "tsu_potts_pop_energies": (C.c_int, [_vp, _f64p, _i64p]),
+    "tsu_potts_pop_get_spins": (C.c_int, [_vp, C.c_int, _i8p]),
+    "tsu_potts_pop_set_spins": (C.c_int, [_vp, C.c_int, _i8p]),
+    "tsu_potts_pop_get_padded": (C.c_int, [_vp, C.c_int, _i8p]),
+    "tsu_potts_pop_route": (C.c_int, [_vp, C.POINTER(C.c_int)]),
+    "tsu_potts_pop_plan": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "tsu_potts_pop_launch_count": (C.c_int, [_vp, _u64p]),
+}
+POTTS_POP_ROUTES = ("k14_pop_pack", "k14_pop_small", "k14_pop_sweep")  # TSU_POTTS_POP_ROUTE_*
+POTTS_POP_MAX_WALKERS = 65535  # kPopMaxWalkers
+POTTS_POP_DRAW = -2            # tsu_potts_pop_init's initial: the device draw
 POTTS_PT_ROUTES = ("k13_pt_small", "k13_pt_sweep")  # TSU_POTTS_PT_ROUTE_*
 POTTS_PT_MAX_TEMPS = 256  # kPtMaxTemps
 POTTS_DIS_RECORD_WORDS = 10  # TSU_POTTS_DIS_RECORD_WORDS
@@ -454,7 +475,8 @@ def load_library():
                               + list(MULTISPIN_CORR_SIGNATURES.items()) + list(MULTISPIN_QUENCH_SIGNATURES.items())
                               + list(CLUSTER_MEASURE_SIGNATURES.items()) + list(POTTS_SIGNATURES.items())
                               + list(POTTS3D_SIGNATURES.items()) + list(POTTS_MUCA_SIGNATURES.items())
-                              + list(POTTS_DISORDER_SIGNATURES.items()) + list(POTTS_PT_SIGNATURES.items())):
+                              + list(POTTS_DISORDER_SIGNATURES.items()) + list(POTTS_PT_SIGNATURES.items())
+                              + list(POTTS_POP_SIGNATURES.items())):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1105,6 +1127,111 @@ class PottsTemperingLattice:
     def launch_count(self):
         n = C.c_uint64(0)
         self.ctx.check(self.lib.tsu_potts_pt_launch_count(self.h, C.byref(n)))
+        return n.value
+
+
+class PottsPopulation:
+    """tsu_potts_pop handle (K14 population annealing): `population` walkers of one K12 lattice sharing one disorder; shape (rows,
+    cols) gives the 2-D lattice (depth 1, open z).  Walker i has Philox key seed + i.  The arrays are checked and rounded to fp32 by
+    the caller (tsu.models.potts_population)."""
+
+    def __init__(self, shape, q, periodic, population, ctx=None):
+        self.ctx = ctx or Context.default()
+        self.lib = self.ctx.lib
+        self.shape = tuple(int(n) for n in shape)
+        self.q, self.population = int(q), int(population)
+        dims = (1,) + self.shape if len(self.shape) == 2 else self.shape
+        if len(self.shape) == 2:
+            self.periodic = (False, bool(periodic), bool(periodic))
+        else:
+            self.periodic = periodic_axes(periodic)
+        per = np.array([int(x) for x in self.periodic], np.int32)
+        self._recorded = -1
+        h = _vp()
+        self.ctx.check(self.lib.tsu_potts_pop_create(self.ctx.h, *dims, self.q, _ptr(per, _i32p), self.population, C.byref(h)))
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tsu_potts_pop_destroy(self.h)
+            self.h = None
+
+    def __del__(self, _finalizing=sys.is_finalizing):
+        if not _finalizing():
+            self.close()
+
+    def set_disorder(self, J_right, J_down, J_layer=None, h=None):
+        arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (J_right, J_down, J_layer, h)]
+        for a, want in zip(arrs, (self.shape, self.shape, self.shape, (self.q,) + self.shape)):
+            if a is not None and a.shape != want:
+                raise ValueError(f"a disorder array has shape {a.shape}, expected {want}")
+        self.ctx.check(self.lib.tsu_potts_pop_set_disorder(self.h, *(None if a is None else _ptr(a, _f32p) for a in arrs)))
+
+    def set_schedule(self, betas):
+        b = np.ascontiguousarray(betas, dtype=np.float64).ravel()
+        self.ctx.check(self.lib.tsu_potts_pop_set_schedule(self.h, _ptr(b, _f64p), int(b.size)))
+
+    def init(self, seed, initial=POTTS_POP_DRAW, initial_sweeps=0):
+        """initial -2: the device draw; -1: the colours stay (set_spins); a colour 0 .. q - 1: that colour everywhere."""
+        self._recorded = -1
+        self.ctx.check(self.lib.tsu_potts_pop_init(self.h, _seed(seed), int(initial), int(initial_sweeps)))
+
+    def advance(self, n_sweeps):
+        self.ctx.check(self.lib.tsu_potts_pop_advance(self.h, _uint("n_sweeps", n_sweeps, 64)))
+
+    def run(self, n_steps, sweeps_per_step, resample=True, record=True):
+        self._recorded = -1
+        self.ctx.check(self.lib.tsu_potts_pop_run(self.h, int(n_steps), int(sweeps_per_step), int(bool(resample)), int(bool(record))))
+        self._recorded = int(n_steps) if record else -1
+
+    def history(self):
+        """The last recording run's rows: E, n_eq (n + 1, R); N (n + 1, R, q); W, parent (n, R); S, U, E_min (n,)."""
+        if self._recorded < 0:
+            raise ValueError("potts_pop_history: the last run recorded nothing")
+        n, R = self._recorded, self.population
+        E, M = np.zeros((n + 1, R)), np.zeros((n + 1, R), np.int64)
+        N = np.zeros((n + 1, R, POTTS_MAX_Q), np.int64)
+        W, P = np.zeros((n, R), np.uint32), np.zeros((n, R), np.int32)
+        S, U, Em = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n)
+        self.ctx.check(self.lib.tsu_potts_pop_history(self.h, _ptr(E, _f64p), _ptr(M, _i64p), _ptr(N, _i64p), _ptr(W, _u32p), _ptr(P, _i32p),
+                                                      _ptr(S, _u64p), _ptr(U, _u64p), _ptr(Em, _f64p)))
+        return {"E": E, "n_eq": M, "N": N[..., :self.q].copy(), "W": W, "parent": P, "S": S, "U": U, "E_min": Em}
+
+    def energies(self):
+        """(E, n_eq) of every walker now."""
+        E, M = np.zeros(self.population), np.zeros(self.population, np.int64)
+        self.ctx.check(self.lib.tsu_potts_pop_energies(self.h, _ptr(E, _f64p), _ptr(M, _i64p)))
+        return E, M
+
+    def get_spins(self, i):
+        out = np.empty(self.shape, dtype=np.int8)
+        self.ctx.check(self.lib.tsu_potts_pop_get_spins(self.h, int(i), _ptr(out, _i8p)))
+        return out
+
+    def set_spins(self, i, colours):
+        s = np.ascontiguousarray(colours, dtype=np.int8).reshape(self.shape)
+        self.ctx.check(self.lib.tsu_potts_pop_set_spins(self.h, int(i), _ptr(s, _i8p)))
+
+    def get_padded(self, i):
+        """Walker i's slot of the allocation: the colours and the pad bytes, sites rounded up to a multiple of 16 in all."""
+        out = np.empty((int(np.prod(self.shape)) + 15) // 16 * 16, dtype=np.int8)
+        self.ctx.check(self.lib.tsu_potts_pop_get_padded(self.h, int(i), _ptr(out, _i8p)))
+        return out
+
+    def route(self):
+        r = C.c_int(-1)
+        self.ctx.check(self.lib.tsu_potts_pop_route(self.h, C.byref(r)))
+        return POTTS_POP_ROUTES[r.value]
+
+    def plan(self):
+        """What the packing rule gives this handle now: route, walkers per workgroup, lanes per workgroup, LDS bytes."""
+        r, g, t, b = C.c_int(-1), C.c_int(0), C.c_int(0), C.c_int(0)
+        self.ctx.check(self.lib.tsu_potts_pop_plan(self.h, C.byref(r), C.byref(g), C.byref(t), C.byref(b)))
+        return {"route": POTTS_POP_ROUTES[r.value], "G": g.value, "threads": t.value, "lds_bytes": b.value}
+
+    def launch_count(self):
+        n = C.c_uint64(0)
+        self.ctx.check(self.lib.tsu_potts_pop_launch_count(self.h, C.byref(n)))
         return n.value
 
 

@@ -9,6 +9,8 @@ from .graph_tempering import GraphTempering
 from .potts import PottsModel2D, PottsModel3D, potts_temperature_scan, potts_temperature_scan_3d
 from .potts_muca import PottsMulticanonical, potts_multicanonical_scan
 from .potts_tempering import PottsTempering, PottsTempering3D, potts_tempering_scan, potts_tempering_scan_3d
+from .potts_population import (PottsPopulationAnnealing, PottsPopulationAnnealing3D, potts_population_annealing_scan,
+                               potts_population_annealing_scan_3d)
 
 __all__ = ["IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "IsingConfig", "demonstrate_phase_transition", "temperature_scan", "cluster_estimators",
            "LatticeTempering", "tempering_scan", "IsingModel3D", "temperature_scan_3d", "LatticeTempering3D", "tempering_scan_3d",
@@ -18,4 +20,5 @@ __all__ = ["IsingModel", "IsingChain", "IsingGrid", "IsingModel2D", "IsingConfig
            "PottsModel2D", "potts_temperature_scan", "PottsModel3D", "potts_temperature_scan_3d",
            "PottsMulticanonical", "potts_multicanonical_scan",
            "PottsTempering", "PottsTempering3D", "potts_tempering_scan", "potts_tempering_scan_3d",
+           "PottsPopulationAnnealing", "PottsPopulationAnnealing3D", "potts_population_annealing_scan", "potts_population_annealing_scan_3d",
            "multispin_quench_3d", "MultispinTempering3D", "multispin_tempering_scan_3d"]
